@@ -20,9 +20,12 @@ job rounds 1 and 2 were quoted on) for continuity.
   python bench.py --gpus N --single-process          ONE process drives N GPUs (what a JVM host does: ncclCommInitAll)
 
 value = cooccurrence pairs formed per second, whole job (all ranks), max-over-ranks time.  One JSON line on rank 0.
-Extra objects on the N = 1 line: roofline (+ roofline_lds / _llr / _pcie / _valu), cpu_baseline (the C oracle on all host
-cores, same workload), host_level (the PCIe-inclusive one-shot entry point a JNI shim binds), csr_row_scan_hbm_resident,
-config3 (+ its ingest_to_model and scipy legs).
+A plain run sets up, warms up, times --steps steps and prints the headline line (value, ms_per_step and the facts of the last
+step).  `--full` adds the passes of their own: single-build latency, the unordered-rows pass, the per-kernel table from a
+single-stream pass, roofline (+ roofline_lds / _llr / _pcie / _valu) and, on the N = 1 line, cpu_baseline (the C oracle on
+all host cores, same workload), host_level (the PCIe-inclusive one-shot entry point a JNI shim binds),
+csr_row_scan_hbm_resident, config3 (+ its ingest_to_model and scipy legs).
+`--dump-outputs DIR` writes what the last timed step returned (dump_outputs) as DIR/<name>.npy.
 """
 from __future__ import annotations
 
@@ -255,24 +258,32 @@ def ingest_leg(lib, dev, data, cfg, seed):
                     "CCO model build -> indicator rows D2H; median of 2 after 1 warm-up; string hashing (urcco_hash_strings on the host) not included"}
 
 
+CPU_BASELINE_BUDGET_S = 150.0   # host seconds the timed runs of the CPU baseline may take after its warm-up (config 4: 10-15 s a run on 16-128 cores)
+
+
 def cpu_oracle_leg(data, n_users, seed, pairs_gpu, runs):
     """CPU baseline on this box's host cores (BASELINE.md section 3): the C oracle (a restatement of the Mahout algorithm;
-    Mahout/Spark local[*] itself cannot run here: no JVM, un-vendored jars) on every core, on the SAME workload."""
+    Mahout/Spark local[*] itself cannot run here: no JVM, un-vendored jars) on every core, on the SAME workload.
+    Median of `runs` runs after a warm-up, fewer when they do not fit CPU_BASELINE_BUDGET_S at the warm-up's pace (on few
+    cores); when not even one does, the warm-up run is the one sample."""
     from oracle import c_oracle as O
     cores = min(os.cpu_count() or 1, O.lib().orc_max_threads())
     mats = [O.Csr(n_users, nc, rp, ci) for (_, nc, rp, ci) in data]
     ps = [O.DatasetParams(500, 50, None)] * len(mats)
-    times, cpu_pairs = [], 0
-    for it in range(runs + (1 if runs > 1 else 0)):
+
+    def once():
         t0 = time.perf_counter()
         ref = O.cross_occurrence_downsampled(mats, ps, seed, 0, cores)
         dt = time.perf_counter() - t0
-        cpu_pairs = sum(r.pairs for r in ref)
-        if it > 0 or runs == 1:
-            times.append(dt)
-        del ref
+        return dt, sum(r.pairs for r in ref)
+    first, cpu_pairs = once()
+    n = min(runs, int(CPU_BASELINE_BUDGET_S // first)) if runs > 1 else 0
+    times = [first] if n == 0 else []
+    for _ in range(n):
+        dt, cpu_pairs = once()
+        times.append(dt)
     cpu_s = statistics.median(times)
-    how = f"median of {runs} runs after 1 warm-up" if runs > 1 else "ONE run, no warm-up (the bounded sample: a run is tens of seconds of 100+ cores)"
+    how = f"median of {n} runs after 1 warm-up" if n > 0 else f"ONE run, no warm-up (the bounded sample: a run is {first:.0f} s of {cores} cores)"
     return {"value": round(cpu_pairs / cpu_s, 1), "unit": "pairs/s", "cores": cores, "kind": "port",
             "sample": f"the whole workload ({cpu_pairs} pairs), {how} ({cpu_s:.2f} s); C oracle, OpenMP (down-sampling, transposition and SpGEMM + LLR + top-k over "
                       "all cores); Mahout/Spark local[*] is not runnable in this image",
@@ -490,8 +501,57 @@ class Job:
         self.shards = []
 
 
-def measure(job: Job, args, full: bool):
-    """Timed region + (full) single-build latency, unordered-rows pass, per-kernel table from a single-stream pass."""
+DUMP_ROWS = 8192        # item rows of the indicator matrices --dump-outputs writes (a fixed, seeded sample; 8192 x k 50 x 2 arrays x 5 event types = 33 MB)
+DUMP_SEED = 4242
+
+
+def dump_outputs(job: Job, out_dir: str):
+    """--dump-outputs: what the last build returned to the caller (Context.results(): per event type an indicator CSR -- row_ptr, col_idx,
+    llr -- and the build's stats), as float64 .npy files in out_dir:
+      event_totals.npy               [event type, 3]: cooccurrence pairs, indicator entries, sum of the entries' column indices (whole matrices)
+      sampled_item_rows.npy          the DUMP_ROWS item rows (rows of every indicator matrix) drawn with DUMP_SEED, ascending
+      ev<d>_<event>_row_len.npy      their lengths
+      ev<d>_<event>_col_idx.npy      [row, k] their columns in the order the build ranked them, -1 past the row's end
+      ev<d>_<event>_llr.npy          [row, k] the LLR scores of the same entries, 0 past the row's end
+    Several GPUs: the rows of this process's item range(s) only."""
+    res = job.ctx.results()
+    n_items = job.cfg.events[0].n_items
+    rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n_items, min(DUMP_ROWS, n_items), replace=False))
+    os.makedirs(out_dir, exist_ok=True)
+    totals = []
+    kept = np.concatenate([rows[(rows >= ind.item_lo) & (rows < ind.item_hi)] for ind in res[0]])
+    np.save(os.path.join(out_dir, "sampled_item_rows.npy"), kept.astype(np.float64))
+    for d, (ev, per_gpu) in enumerate(zip(job.cfg.events, res)):
+        k = per_gpu[0].k
+        pairs = entries = col_sum = 0
+        lens, cols, llrs = [], [], []
+        for ind in per_gpu:
+            pairs += int(ind.stats[0])
+            if ind.item_hi <= ind.item_lo:
+                continue
+            rp = ind.row_ptr
+            nnz = int(rp[-1])
+            entries += nnz
+            col_sum += int(ind.col_idx[:nnz].sum(dtype=torch.int64))
+            r = torch.from_numpy(rows[(rows >= ind.item_lo) & (rows < ind.item_hi)] - ind.item_lo).to(rp.device)
+            start, ln = rp[r], rp[r + 1] - rp[r]
+            pos = torch.arange(k, device=rp.device)
+            live = pos[None, :] < ln[:, None]
+            idx = torch.where(live, start[:, None] + pos[None, :], 0)
+            lens.append(ln.cpu().numpy())
+            cols.append(torch.where(live, ind.col_idx[idx].to(torch.int64), -1).cpu().numpy())
+            llrs.append(torch.where(live, ind.llr[idx], 0.0).cpu().numpy())
+        totals.append([pairs, entries, col_sum])
+        stem = os.path.join(out_dir, f"ev{d}_{ev.name}")
+        np.save(stem + "_row_len.npy", np.concatenate(lens or [np.zeros(0)]).astype(np.float64))
+        np.save(stem + "_col_idx.npy", np.concatenate(cols or [np.zeros((0, k))]).astype(np.float64))
+        np.save(stem + "_llr.npy", np.concatenate(llrs or [np.zeros((0, k))]).astype(np.float64))
+    np.save(os.path.join(out_dir, "event_totals.npy"), np.array(totals, dtype=np.float64))
+
+
+def measure(job: Job, args, full: bool, dump_dir=None):
+    """Timed region (+ dump_outputs of its last step) + (full) single-build latency, unordered-rows pass, per-kernel table from a
+    single-stream pass."""
     from universal_recommender_amd import _lib
     world, rank, single_process = job.world, job.rank, job.single_process
     ctx, cfg = job.ctx, job.cfg
@@ -506,11 +566,13 @@ def measure(job: Job, args, full: bool):
         job.step()
     job.barrier()
     elapsed = time.perf_counter() - t0
+    if dump_dir is not None and rank == 0:
+        dump_outputs(job, dump_dir)     # before any other pass replaces the last step's results
     if args.timed_only:
         return {"ms_per_step": round(elapsed / args.steps * 1e3, 4)}
     # one build at a time (what a single `pio train` sees): every build followed by a wait
     single_build_ms = None
-    plain = world == 1 and n_local == 1 and not args.single_stream and not args.force_exchange
+    plain = full and world == 1 and n_local == 1 and not args.single_stream and not args.force_exchange
     if plain:
         lat = []
         for _ in range(max(5, args.steps // 2)):
@@ -523,15 +585,16 @@ def measure(job: Job, args, full: bool):
     # the same steps with URCCO_FLAG_UNORDERED_ROWS (rows = top-k sets without the in-kernel ranking pass: what the JNI shim
     # asks for -- the Scala host re-inserts by column index anyway) -- reported beside `value`, never as `value`
     unordered = None
-    if plain and full:
+    if plain:
         ctx.set_flags(job.base_flags | _lib.FLAG_UNORDERED_ROWS)
         unordered = job.timed(args.steps, args.warmup) / args.steps
         ctx.set_flags(job.base_flags)
+    timings, kernel_timing_mode = None, None
     if args.single_stream:
         timings = ctx.get_timings()
         ctx.set_timing(False)
         kernel_timing_mode = "timed region (one stream)"
-    else:
+    elif full:
         # The timed region overlaps the event types on separate HIP streams, so a kernel's event-bracketed duration there
         # includes time it shared the GPU with other kernels.  Per-kernel durations (roofline) are therefore taken from a
         # second pass of the same steps with the event types serialised on one stream (== `bench.py --single-stream`, the
@@ -578,7 +641,7 @@ def measure(job: Job, args, full: bool):
     out = {"elapsed": elapsed, "ms_per_step": ms_per_step, "value": value, "pairs": pairs, "pairs_per_event": pairs_per_event, "stats": stats,
            "nnz_out": nnz_out, "nnz_sampled": nnz_sampled, "nnz_raw_local": nnz_raw_local, "item_range": item_range, "items": items,
            "single_build_ms": single_build_ms, "unordered": unordered, "kernel_timing_mode": kernel_timing_mode}
-    if rank != 0:
+    if rank != 0 or not full:
         return out
 
     # ---- per-kernel table + roofline of the dominant kernel (this process's HIP-event timings, averaged over its GPUs) ----
@@ -677,6 +740,10 @@ def main():
     ap.add_argument("--gathered-primary", action="store_true",
                     help="A/B (N > 1 path): the primary's CSC from a pass of every rank over the whole gathered A' (rounds 1-2) instead of fragments")
     ap.add_argument("--timed-only", action="store_true", help="stop after the timed region (timeline captures)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the passes of their own: latency, unordered rows, per-kernel table, rooflines, CPU baselines, host-level / row-scan / LLR / config-3 legs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (a seeded sample of the indicator rows + whole-matrix totals) as DIR/<name>.npy")
     ap.add_argument("--seed", type=int, default=20260925)
     ap.add_argument("--emulate-ranks", type=int, default=0,
                     help="measurement mode: the per-rank critical path of a W-rank build on ONE GPU (prints its own JSON object, not the bench line)")
@@ -731,8 +798,8 @@ def main():
     workload = args.workload if args.workload != "auto" else "config4"
     mark(f"generating {workload} on the device")
     job = Job(library, workload, args, world, rank, devs, args.single_process)
-    mark("inputs resident; timed region + per-stage pass")
-    m = measure(job, args, full=True)
+    mark("inputs resident; timed region" + (" + per-stage pass" if args.full else ""))
+    m = measure(job, args, full=args.full, dump_dir=args.dump_outputs)
     mark("measured")
     if args.timed_only:
         print(json.dumps(m), flush=True)
@@ -747,7 +814,7 @@ def main():
     cfg = job.cfg
     pairs = m["pairs"]
     n1 = world == 1 and len(devs) == 1
-    main_run = n1 and args.scale == 1.0 and not args.single_stream and not args.force_exchange
+    main_run = args.full and n1 and args.scale == 1.0 and not args.single_stream and not args.force_exchange
 
     extras = {}
     cpu_baseline = None
@@ -798,7 +865,7 @@ def main():
     # (the counters must have been collected on THESE kernel sources, like the traffic figure)
     roofline_valu = None
     vpath, spath = os.path.join(ROOT, "profiles", "r03_valu_microbench.json"), os.path.join(ROOT, "profiles", f"r06_sq_counters_pmc_{workload}.json")
-    if n1 and os.path.exists(vpath) and os.path.exists(spath) and m["roofline"]["kernel"] in STAGE_TO_KERNEL:
+    if args.full and n1 and os.path.exists(vpath) and os.path.exists(spath) and m["roofline"]["kernel"] in STAGE_TO_KERNEL:
         vb = json.load(open(vpath))
         sj = json.load(open(spath))
         sq = sj["kernels"].get(STAGE_TO_KERNEL[m["roofline"]["kernel"]]) if sj.get("kernel_source_id") == kernel_source_id() else None
@@ -828,21 +895,25 @@ def main():
                    "launch": ("one process drives all GPUs (ncclCommInitAll inside the library)" if args.single_process and world > 1 else "one process per GPU"),
                    "parallelism": f"items range-partitioned over {world} GPU(s)" + (", RCCL inside the library: 2 all-reduces + 1 all-gather-v per event type, 1 all-reduce of the work key" if job.exchange else "")
                                   + ("" if args.single_stream else ", one HIP stream per event type")},
-        "pairs_per_step": pairs, "items_per_sec": round(m["items"] / (m["llr_ms"] / 1e3), 1) if m["llr_ms"] > 0 else None,
-        "items_per_sec_note": "sum over event types of nItems(A) / time of the SpGEMM+LLR+top-k stages (rank 0)",
+        "pairs_per_step": pairs,
         "indicator_entries": int(m["nnz_out"].sum()), "rows_by_accumulator": dict(zip(["micro", "wave", "block_small", "block", "cu_half", "cu", "multipass"], [int(sum(s[1 + b] for s in stats)) for b in range(NB)])),
-        "roofline": m["roofline"], "roofline_lds": m["roofline_lds"], "roofline_llr": roofline_llr, "roofline_valu": roofline_valu,
-        "serialised_ms": {"spgemm_llr_topk": round(m["spgemm_ms"], 4), "everything_else": round(m["non_spgemm_ms"], 4)},
-        "kernels": m["kernels"], "kernel_timing": m["kernel_timing_mode"], "cpu_baseline": cpu_baseline,
-        "gpu_over_cpu": round(m["value"] / cpu_baseline["value"], 1) if cpu_baseline else None,
         "input_generation_s": round(job.gen_s, 1),
-        "single_build_latency_ms": None if m["single_build_ms"] is None else round(m["single_build_ms"], 4),
-        "single_build_latency_note": "median wall time of one build followed by a wait (the timed region enqueues its builds back to back: consecutive builds overlap)",
-        "unordered_rows": None if m["unordered"] is None else {"flag": "URCCO_FLAG_UNORDERED_ROWS", "ms_per_step": round(m["unordered"] * 1e3, 4),
-                                                                 "pairs_per_s": round(pairs / m["unordered"], 1),
-                                                                 "note": "same build, indicator rows as unordered top-k sets (no ranking pass): what the JNI shim asks for; not the headline value"},
     }
-    line.update(extras)
+    if args.full:
+        line.update({
+            "items_per_sec": round(m["items"] / (m["llr_ms"] / 1e3), 1) if m["llr_ms"] > 0 else None,
+            "items_per_sec_note": "sum over event types of nItems(A) / time of the SpGEMM+LLR+top-k stages (rank 0)",
+            "roofline": m["roofline"], "roofline_lds": m["roofline_lds"], "roofline_llr": roofline_llr, "roofline_valu": roofline_valu,
+            "serialised_ms": {"spgemm_llr_topk": round(m["spgemm_ms"], 4), "everything_else": round(m["non_spgemm_ms"], 4)},
+            "kernels": m["kernels"], "kernel_timing": m["kernel_timing_mode"], "cpu_baseline": cpu_baseline,
+            "gpu_over_cpu": round(m["value"] / cpu_baseline["value"], 1) if cpu_baseline else None,
+            "single_build_latency_ms": None if m["single_build_ms"] is None else round(m["single_build_ms"], 4),
+            "single_build_latency_note": "median wall time of one build followed by a wait (the timed region enqueues its builds back to back: consecutive builds overlap)",
+            "unordered_rows": None if m["unordered"] is None else {"flag": "URCCO_FLAG_UNORDERED_ROWS", "ms_per_step": round(m["unordered"] * 1e3, 4),
+                                                                     "pairs_per_s": round(pairs / m["unordered"], 1),
+                                                                     "note": "same build, indicator rows as unordered top-k sets (no ranking pass): what the JNI shim asks for; not the headline value"},
+        })
+        line.update(extras)
     print(json.dumps(line), flush=True)   # flushed before any teardown: a process that dies later (abort() does not flush stdio) has still reported
     mark("line printed; tearing down")
     job.close()

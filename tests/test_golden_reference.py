@@ -165,13 +165,12 @@ def test_extract_jvalue_types_dates_and_ranks_before_indexing(sim_lib, tmp_path)
     from universal_recommender_amd.preparator import Preparator
     from universal_recommender_amd.ur_algorithm import URAlgorithm, URAlgorithmParams
     from universal_recommender_amd.ur_model import URModel, extractJvalue
-    engine = json.load(open("/root/reference/examples/handmade-engine.json")) if os.path.exists("/root/reference/examples/handmade-engine.json") else None
     doc, by_event, _, items = _load("handmade.json")
     eng = {"datasource": {"params": doc["datasource_params"]}, "algorithms": [{"name": "ur", "params": dict(doc["algorithm_params"], availableDateName="available",
                                                                                                       expireDateName="expires", dateName="date")}]}
-    if engine is not None:   # the committed parameters are the reference's (tests/golden/make_golden.py); here also its date names, when the reference is at hand
-        rp = [a for a in engine["algorithms"] if a["name"] == "ur"][0]["params"]
-        assert (rp["availableDateName"], rp["expireDateName"], rp["dateName"]) == ("available", "expires", "date")
+    # the committed parameters are the reference's handmade engine's (tests/golden/make_golden.py), its date names among them
+    rp = doc["algorithm_params"]
+    assert (rp["availableDateName"], rp["expireDateName"], rp["dateName"]) == ("available", "expires", "date")
     ap = URAlgorithmParams.from_engine_json(eng)
     ap.seed = 1
     algo = URAlgorithm(ap, library=sim_lib)

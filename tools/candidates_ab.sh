@@ -15,7 +15,7 @@ for v in cur "$@"; do
   echo "digest $(timeout 60 python tools/soak_once.py --mode multi --builds 1 2>/dev/null | grep 'DIGEST warmup' | md5sum | cut -c1-16)"
   timeout 60 python tools/ablate.py --config4 1.0 0 2>&1 | grep debug=
   timeout 60 python tools/rowscan_bench.py 2>&1 | tail -3
-  timeout 90 python bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
+  timeout 90 python bench.py --full --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-extras 2>/dev/null | python -c "
 import json, sys
 for line in sys.stdin:
     if line.startswith('{\"metric\"'):

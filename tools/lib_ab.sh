@@ -6,7 +6,7 @@ for i in $(seq 1 $REPS); do
   for v in cur "$@"; do
     n=$(basename $v .so)
     if [ $v = cur ]; then unset URCCO_LIB; else export URCCO_LIB=$PWD/$v; fi
-    timeout 600 python bench.py --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline --no-extras > $O/ab_${n}_$i.log 2>&1
+    timeout 600 python bench.py --full --steps ${STEPS:-30} --warmup 5 --no-cpu-baseline --no-extras > $O/ab_${n}_$i.log 2>&1
     echo "$n $i rc=$? $(python - $O/ab_${n}_$i.log <<'PY'
 import json, sys
 for line in open(sys.argv[1]):

@@ -8,7 +8,7 @@ for i in $(seq 1 $REPS); do
   for v in "$@"; do
     j=$((j+1))
     if [ "$v" = "-" ]; then e=""; else e="$v"; fi
-    env $e timeout 600 python bench.py --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-extras ${BENCH_ARGS} > $O/ab_${j}_$i.log 2>&1
+    env $e timeout 600 python bench.py --full --steps ${STEPS:-20} --warmup 5 --no-cpu-baseline --no-extras ${BENCH_ARGS} > $O/ab_${j}_$i.log 2>&1
     echo "[$v] $i rc=$? $(python tools/bench_brief.py $O/ab_${j}_$i.log)"
   done
 done
