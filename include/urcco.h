@@ -274,11 +274,23 @@ int urcco_context_build_device(urcco_context* ctx, const urcco_dev_dataset* data
                                int32_t random_seed, void* input_stream, urcco_dev_result* out);
 int urcco_context_wait_stream(urcco_context* ctx, void* stream); /* `stream` waits (on the device) for the last build */
 int urcco_context_synchronize(urcco_context* ctx);               /* the host waits */
-/* per-stage timing / ablation switches of every session of the context (see urcco_session_set_timing / _set_debug) */
+/* per-stage timing of every session of the context (see urcco_session_set_timing) */
 int urcco_context_set_timing(urcco_context* ctx, int32_t enable);
 int urcco_context_get_timings(urcco_context* ctx, double* ms, int64_t* launches);
 /* the same for ONE local GPU (rank first_rank + local_gpu): what bench.py --emulate-ranks reads per rank */
 int urcco_context_get_timings_gpu(urcco_context* ctx, int32_t local_gpu, double* ms, int64_t* launches);
+/* Debug bits of every session of the context (urcco_context_set_debug) or of one session (urcco_session_set_debug); 0 in production.
+ * The names are those of cco_kernels.h (urcco::DBG_*).
+ * SpGEMM row phases switched off, for profiling (results are meaningless):
+ *   1 GATHER_ONLY, 2 NO_LLR, 4 NO_TOPK, 8 NO_SELECT, 16 NO_RANK (no ranking / output), 512 NO_COUNT_GATHER (every cB = 100).
+ * A/B paths, results unchanged:
+ *   4096 UNFUSED_EXPAND       every event type prepares its own expand operands (no fused pass over the CSC of A')
+ *   8192 GATHERED_PRIMARY     several ranks: the primary's CSC from a pass over the whole gathered A' instead of fragments
+ *   16384 UNFILTERED_EXCHANGE several ranks: every row of B is exchanged (see urcco_dev_result::sampled_row_ptr)
+ *   1048576 UNPACKED_COUNTS   B' travels as plain column indices and the row kernels gather the counts (the form of rounds 1-5)
+ * Test hook: 131072 SELECT_DELAY = the first wave of every multi-wave team sleeps before it reads the select histogram
+ * (tests/test_gpu_parity.py::test_select_overlay_race_fixed).
+ * The row-kernel bits (1..16, 512, 131072) run the rows on separate instantiations that carry the switches. */
 int urcco_context_set_debug(urcco_context* ctx, int32_t flags);
 int urcco_context_set_flags(urcco_context* ctx, int32_t flags); /* URCCO_FLAG_* */
 
@@ -315,11 +327,7 @@ enum {
   URCCO_STAGE_EXCHANGE = 16 /* several ranks only: row lengths, need masks, masked lengths, packing per destination, row_ptr rebuild of what was received */
 };
 int urcco_session_set_timing(urcco_session* s, int32_t enable);
-/* Profiling aid: kernel ablation switches; results are meaningless when non-zero.  0 in production.
- * SpGEMM rows: 1 = gather only, 2 = no LLR, 4 = no top-k, 8 = no select, 16 = no rank / output.
- * CSR row scan: 32 = cheap hash, 64 = no threshold gather, 128 = no entry -> row lookup.
- * Test hooks of the top-k select (tests/test_gpu_parity.py::test_select_overlay_race_*): 131072 = the first wave of every multi-wave
- * team sleeps before it reads the select histogram, 262144 = skip the barrier in front of the ambiguous-set copy-out (round 3's race). */
+/* the debug bits of urcco_context_set_debug, for this session only */
 int urcco_session_set_debug(urcco_session* s, int32_t flags);
 int urcco_session_get_timings(urcco_session* s, double* ms /*[URCCO_N_STAGES]*/, int64_t* launches /*[URCCO_N_STAGES]*/);
 /* bytes of device scratch currently held */

@@ -223,3 +223,31 @@ def sort_rows(got):
     rows = np.repeat(np.arange(rp.size - 1), np.diff(rp))
     order = np.lexsort((ci, -llr, rows))
     return rp, ci[order], llr[order]
+
+
+def select_race_workload():
+    """The workload of the round-3 race in the top-k select (cco_rows.hip, the barrier in front of the ambiguous-set copy-out):
+    rows whose select is CERTAIN to consume the words a missing barrier would let a sibling wave clobber.  Two groups of items:
+    X (121 items) held together by 7 users, Y (100 items) held -- with X -- by 2 of them.  A row of X then has 120 candidates tied at the top LLR (more than
+    k = 50, at most the 128 the ambiguous set holds: the select finishes in its FIRST pass, whose histogram the 120 copied
+    keys overwrite completely) and 100 weaker ones, 221 distinct columns in all: the team's first wave owns the lowest columns --
+    the ones the tie at the cut selects -- and decides about them with whatever it read.  Work 5 x 121 + 2 x 221 = 1047 pairs -> the 256-thread
+    small-block class (as are the rows of Y: 442 pairs, 221 columns)."""
+    n_users, n_items, nx, ny = 2000, 512, 121, 100
+    rows = [np.zeros(0, np.int64) for _ in range(n_users)]
+    u = 0
+    for b in range(2):
+        base = b * (nx + ny)
+        for _ in range(5):
+            rows[u] = np.arange(base, base + nx, dtype=np.int64)
+            u += 1
+        for _ in range(2):
+            rows[u] = np.arange(base, base + nx + ny, dtype=np.int64)
+            u += 1
+    rp = np.zeros(n_users + 1, np.int64)
+    np.cumsum([len(r) for r in rows], out=rp[1:])
+    a = O.Csr(n_users, n_items, rp, np.concatenate(rows).astype(np.int32))
+    return [a, a]
+
+
+SELECT_RACE_ROWS_SMALL_BLOCK = 2 * (121 + 100)  # item rows of select_race_workload(), all in the 256-thread small-block class

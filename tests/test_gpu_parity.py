@@ -9,7 +9,7 @@ import pytest
 import torch
 
 import test_sim_kernel_logic as logic
-from helpers import LLR_TOL, check_indicators, compare_with_oracle, rand_csr, run_device, to_dev
+from helpers import LLR_TOL, SELECT_RACE_ROWS_SMALL_BLOCK, check_indicators, compare_with_oracle, rand_csr, run_device, select_race_workload, to_dev
 from oracle import c_oracle as O
 from oracle import cco_oracle as PO
 
@@ -257,26 +257,14 @@ def test_select_overlay_race_fixed(gpu_session):
     the rotating select histograms, and a wave that had finished its digit search wrote them while a sibling wave was still
     reading the counts.  debug 131072 makes that interleaving certain (the team's first wave sleeps before it reads the
     histogram); with the barrier in place the build must still equal the oracle row for row."""
-    import race_negative_control as nc
     from universal_recommender_amd import synth
     cfg = synth.config3(0.1)
     gpu_session.set_debug(131072)
     try:
-        _, _, stats = compare_with_oracle(gpu_session, nc.workload(), [P(), P()], 77, exact_ids=True)   # every row consumes the overlaid words
-        assert all(int(s[0][1 + 2]) == nc.N_ROWS_SMALL_BLOCK for s in stats), "the workload must put its rows into the 256-thread small-block class"
-        mats = [O.Csr(cfg.n_users, nc_, rp, ci) for (_, nc_, rp, ci) in synth.generate(cfg)][:2]
+        _, _, stats = compare_with_oracle(gpu_session, select_race_workload(), [P(), P()], 77, exact_ids=True)   # every row consumes the overlaid words
+        assert all(int(s[0][1 + 2]) == SELECT_RACE_ROWS_SMALL_BLOCK for s in stats), "the workload must put its rows into the 256-thread small-block class"
+        mats = [O.Csr(cfg.n_users, nc, rp, ci) for (_, nc, rp, ci) in synth.generate(cfg)][:2]
         _, _, stats = compare_with_oracle(gpu_session, mats, [P(), P()], 77)
         assert sum(int(s[0][1 + 2]) for s in stats) > 1000
     finally:
         gpu_session.set_debug(0)
-
-
-def test_select_overlay_race_negative_control():
-    """The same build with the barrier skipped (debug 262144 == round 3's code), in its own process: the race must show --
-    rows that differ from the build with the barrier, or a GPU fault."""
-    import subprocess
-    import sys
-    here = os.path.dirname(os.path.abspath(__file__))
-    out = subprocess.run([sys.executable, os.path.join(here, "race_negative_control.py")], capture_output=True, text=True, timeout=600)
-    died = out.returncode != 0 and "RACE_" not in out.stdout   # the HSA runtime aborts the process on some faults
-    assert died or "RACE_REPRODUCED" in out.stdout, out.stdout[-2000:] + out.stderr[-3000:]

@@ -641,14 +641,14 @@ def test_row_scan_large_matrix_edges(sim_session, mode):
 
 
 def test_select_ambiguous_set_overlays_the_histograms(sim_session):
-    """The workload of the round-3 race (tests/race_negative_control.py): 120 candidates tied at the top LLR (+ 100 weaker ones) per row in the 256-thread
+    """The workload of the round-3 race (helpers.select_race_workload): 120 candidates tied at the top LLR (+ 100 weaker ones) per row in the 256-thread
     small-block class, whose LDS layout overlays the ambiguous set on the select histograms.  The simulator runs the waves of a
-    team one after the other between rendezvous, so it cannot show the race itself (the -m gpu tests do, with a wave delayed on
-    hardware); here the logic of the path -- and of the barrier round 4 added -- is checked with exact ids, delay hook on."""
-    import race_negative_control as nc
+    team one after the other between rendezvous, so it cannot interleave them as the race needs (the -m gpu test runs the same
+    build with a wave delayed on hardware); here the logic of the path -- and of the barrier round 4 added -- is checked with exact ids, delay hook on."""
+    from helpers import SELECT_RACE_ROWS_SMALL_BLOCK, select_race_workload
     sim_session.set_debug(131072)
     try:
-        _, _, stats = compare_with_oracle(sim_session, nc.workload(), [P(), P()], 77, exact_ids=True)
+        _, _, stats = compare_with_oracle(sim_session, select_race_workload(), [P(), P()], 77, exact_ids=True)
     finally:
         sim_session.set_debug(0)
-    assert all(int(s[0][1 + 2]) == nc.N_ROWS_SMALL_BLOCK for s in stats)
+    assert all(int(s[0][1 + 2]) == SELECT_RACE_ROWS_SMALL_BLOCK for s in stats)

@@ -1,7 +1,6 @@
 #!/usr/bin/env python3
-"""Profiling aid: the CSR row scan (urcco_dev_downsample) alone on the config-3 matrices, with parts switched off
-(urcco_session_set_debug: 32 = cheap hash, 64 = no threshold gather, 128 = no row lookup).  Outputs of ablated runs
-are meaningless.  `--sim` = dry run on the test-only host simulator."""
+"""Profiling aid: the CSR row scan (urcco_dev_downsample) alone on the config-3 matrices.
+`--sim` = dry run on the test-only host simulator."""
 import os
 import sys
 import time
@@ -20,7 +19,6 @@ c4 = "--config4" in sys.argv  # the five matrices of BASELINE config 4, generate
 mode = _lib.RNG_MIX32 if "--rng32" in sys.argv else 0  # the 32-bit form of the down-sampling RNG (URCCO_RNG_MIX32)
 argv = [a for a in sys.argv[1:] if not a.startswith("--")]
 scale = float(argv[0]) if len(argv) > 0 else 1.0
-flags = [int(x) for x in argv[1].split(",")] if len(argv) > 1 else [0, 32, 64, 128, 224]
 reps = 2 if sim else 10
 dev = torch.device("cpu") if sim else torch.device("cuda", 0)
 if hbm or c4:
@@ -42,25 +40,22 @@ else:
     sess = DeviceSession(dev, _lib.load(os.environ.get("URCCO_LIB", _lib.DEFAULT_PATH)))
     sync = torch.cuda.synchronize
 raws = [sess.column_counts(m.col_idx, m.nnz_bound, m.n_cols) for m in mats]
-for f in flags:
-    sess.set_debug(f)
-    line = []
-    for i, (m, raw) in enumerate(zip(mats, raws)):
-        for _ in range(2):
-            out, post = sess.downsample(m, m.nnz_bound, raw, 1, 500, mode)
-        sync()
-        sess.set_timing(True)
-        t0 = time.perf_counter()
-        for _ in range(reps):
-            out, post = sess.downsample(m, m.nnz_bound, raw, 1, 500, mode)
-        sync()
-        wall = (time.perf_counter() - t0) / reps * 1e3
-        tm = sess.get_timings()
-        sess.set_timing(False)
-        parts = [tm[k][0] / reps for k in ("downsample_flags", "downsample_scan", "downsample_compact")]
-        scan = sum(parts)
-        kept = int(out.row_ptr[-1].item())
-        alg = m.nnz_bound * 4 + kept * 4 + (m.n_rows + 1) * 16
-        line.append(f"m{i}: nnz={m.nnz_bound} kept={kept} scan={scan:.4f} ms = " + "+".join(f"{x:.4f}" for x in parts) + f" ({alg / scan / 1e6:.0f} GB/s) wall={wall:.3f}")
-    print(f"debug={f}{' rng32' if mode else ''}: " + " | ".join(line), flush=True)
-sess.set_debug(0)
+line = []
+for i, (m, raw) in enumerate(zip(mats, raws)):
+    for _ in range(2):
+        out, post = sess.downsample(m, m.nnz_bound, raw, 1, 500, mode)
+    sync()
+    sess.set_timing(True)
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        out, post = sess.downsample(m, m.nnz_bound, raw, 1, 500, mode)
+    sync()
+    wall = (time.perf_counter() - t0) / reps * 1e3
+    tm = sess.get_timings()
+    sess.set_timing(False)
+    parts = [tm[k][0] / reps for k in ("downsample_flags", "downsample_scan", "downsample_compact")]
+    scan = sum(parts)
+    kept = int(out.row_ptr[-1].item())
+    alg = m.nnz_bound * 4 + kept * 4 + (m.n_rows + 1) * 16
+    line.append(f"m{i}: nnz={m.nnz_bound} kept={kept} scan={scan:.4f} ms = " + "+".join(f"{x:.4f}" for x in parts) + f" ({alg / scan / 1e6:.0f} GB/s) wall={wall:.3f}")
+print(f"rowscan{' rng32' if mode else ''}: " + " | ".join(line), flush=True)

@@ -393,20 +393,20 @@ __global__ __launch_bounds__(PL_THREADS, 6) void pl_partition_kernel(const int32
 }
 
 constexpr int PLH_THREADS = 1024;
-// LPS lanes walk one slice together, 16 ids (two 16-byte loads) per lane and step.  A slice of a 2M-column catalogue holds ~130 ids:
+// PL_LANES lanes walk one slice together, 16 ids (two 16-byte loads) per lane and step.  A slice of a 2M-column catalogue holds ~130 ids:
 // with 16 lanes per slice a step covers 256 and half of the lanes idle through the masked atomics; fewer lanes per slice waste less
 // but touch more parts (pages) per load instruction.  Measured on config 4's five raw matrices (profiles/r05_colcount_variants.log):
-// 16 / 8 / 4 lanes 3.07 / 3.02 / 3.19 ms, the bucket-contiguous form 3.45.  dbg (URCCO_PL_DEBUG, profiling only): 1 = no LDS atomics,
-// 2 = no loads -- which is how the same log prices the pass: without the atomics 1.76 ms, with neither 1.37: the RANDOM LDS atomics
+// 16 / 8 / 4 lanes 3.07 / 3.02 / 3.19 ms, the bucket-contiguous form 3.45.  The same log prices the pass with parts of it switched off:
+// without the LDS atomics 1.76 ms, without the loads as well 1.37: the RANDOM LDS atomics
 // (~1.1 lane updates per clock and CU: ~58 cycles per wave instruction against 4.6 for conflict-free addresses) are what the histogram
 // costs, not its loads -- the same bound the bucket-contiguous form sits on.
 // Buckets are split by WEIGHT: a bucket gets S blocks per average bucket weight it carries (pl_blockmap_kernel), each block an equal share of
 // the parts.  A catalogue's hottest item draws 6.6 % of a Zipf(1) matrix into ONE bucket -- 17x the average; with S blocks for every
 // bucket the few blocks of that bucket were the kernel (0.98 ms on config 4's largest matrix for 0.45 ms of evenly spread work).
-template <int LPS>
+constexpr int PL_LANES = 8;
 __global__ __launch_bounds__(PLH_THREADS) void pl_hist_kernel(const unsigned short* __restrict__ bucketed, const unsigned short* __restrict__ loc_t,
                                                               int n_buckets, int64_t n_parts, const int32_t* __restrict__ blk_prefix, int32_t n_cols,
-                                                              unsigned* __restrict__ partial, int dbg) {
+                                                              unsigned* __restrict__ partial) {
   __shared__ unsigned s_cnt[PL_BUCKET];
   const int blk = blockIdx.x;
   if (blk >= blk_prefix[n_buckets]) return;  // block-uniform
@@ -427,12 +427,11 @@ __global__ __launch_bounds__(PLH_THREADS) void pl_hist_kernel(const unsigned sho
   // Steps are aligned to 8 ids; ids of a step outside [lo, hi) -- the neighbouring buckets' -- are masked (the array has 64 bytes of slack
   // behind it).  (Measured: one WAVE per slice with 2-byte loads -- a chain of short waits -- took 2x the bucket-contiguous form; one
   // LANE per slice -- 64 parts, i.e. 64 pages, per load instruction -- 2.4x.)
-  constexpr int SPR = WAVE / LPS;  // slices per wave and round
+  constexpr int SPR = WAVE / PL_LANES;  // slices per wave and round
   constexpr int GP = 16;           // parts per group (a wave takes groups round robin; lane l < GP holds the bounds of part g + l)
   static_assert(GP % SPR == 0 && SPR <= GP, "rounds per group");
-  const int sub = lane / LPS, sl = lane % LPS;
+  const int sub = lane / PL_LANES, sl = lane % PL_LANES;
   const int64_t gstep = (int64_t)(PLH_THREADS / WAVE) * GP;
-  unsigned fake = 0u;
   int64_t g = p0 + (int64_t)wave * GP;
   unsigned lo_n = 0u, hi_n = 0u;  // the NEXT group's bounds travel while this group's slices are counted
   if (g < p1 && lane < GP && g + lane < p1) {
@@ -453,18 +452,9 @@ __global__ __launch_bounds__(PLH_THREADS) void pl_hist_kernel(const unsigned sho
       const unsigned lo_j = (unsigned)__shfl((int)lo, pj);
       const unsigned hi_j = (unsigned)__shfl((int)hi, pj);
       const unsigned short* src = bucketed + (g + pj) * PL_PART;
-      for (unsigned base = (lo_j & ~7u) + 16u * (unsigned)sl; base < hi_j; base += 16u * LPS) {
-        uint4 x0 = make_uint4(base, base + 2u, base + 4u, base + 6u), x1 = x0;
-        if (!(dbg & 2)) {
-          x0 = *reinterpret_cast<const uint4*>(src + base);
-          x1 = *reinterpret_cast<const uint4*>(src + base + 8);
-        }
+      for (unsigned base = (lo_j & ~7u) + 16u * (unsigned)sl; base < hi_j; base += 16u * PL_LANES) {
+        const uint4 x0 = *reinterpret_cast<const uint4*>(src + base), x1 = *reinterpret_cast<const uint4*>(src + base + 8);
         const unsigned wds[8] = {x0.x, x0.y, x0.z, x0.w, x1.x, x1.y, x1.z, x1.w};
-        if (dbg & 1) {
-#pragma unroll
-          for (int k = 0; k < 8; ++k) fake ^= wds[k];
-          continue;
-        }
 #pragma unroll
         for (int k = 0; k < 8; ++k) {
           const unsigned t = base + 2u * k;
@@ -474,7 +464,6 @@ __global__ __launch_bounds__(PLH_THREADS) void pl_hist_kernel(const unsigned sho
       }
     }
   }
-  if ((dbg & 1) && fake == 0x9e3779b9u) s_cnt[0] = 1u;
   __syncthreads();
   unsigned* out = partial + (int64_t)blk * PL_BUCKET;
   for (int c = threadIdx.x; c < width; c += PLH_THREADS) out[c] = s_cnt[c];
@@ -530,33 +519,18 @@ __global__ __launch_bounds__(SCAN_THREADS) void pl_blockmap_kernel(const long lo
   if (b == 0) blk_prefix[n_buckets] = (int32_t)tot;
 }
 
-// Environment knobs of the column counts.  The profiling-only ones are read ONCE per process (every launch called getenv
-// from several enqueueing threads); the two the test-suite toggles at run time -- URCCO_COLCOUNT_GLOBAL_LAYOUT and URCCO_PH_CHUNK_BIG_NNZ
-// -- stay per call, and column_counts_scratch_bytes sizes for whichever value the launch may later see (see there).
-struct PlKnobs {
-  long long block_ids = 49152;  // URCCO_PL_BLOCK_IDS: ids per average histogram block (0 = no such bound)
-  int debug = 0;                // URCCO_PL_DEBUG (profiling only): 1 = no LDS atomics, 2 = no loads (the counts are then meaningless)
-  int lanes = 8;                // URCCO_PL_LANES: lanes per slice (16, 8 or 4)
-  PlKnobs() {
-    if (const char* e = getenv("URCCO_PL_BLOCK_IDS")) if (*e) block_ids = atoll(e);
-    if (const char* e = getenv("URCCO_PL_DEBUG")) if (*e) debug = atoi(e);
-    if (const char* e = getenv("URCCO_PL_LANES")) if (*e) lanes = atoi(e);
-  }
-};
-static const PlKnobs& pl_knobs() {
-  static const PlKnobs k;
-  return k;
-}
+// ids per average histogram block (profiles/r05_colcount_block_ids_ab.log: at 8 emulated ranks the slowest rank 8.29 ms against 8.58
+// without the bound and 8.34 with twice as many ids; one rank flat)
+constexpr int64_t PL_BLOCK_IDS = 49152;
 // histogram blocks per AVERAGE bucket: a few thousand blocks in all, each with at least a handful of parts; bounded = false: without the
-// bound by work (an upper bound of the split for any knob value: what the scratch is sized for)
+// bound by work (an upper bound of the split: what the scratch is sized for)
 static inline int pl_splits(int n_buckets, int64_t n_parts, bool bounded = true) {
   int64_t S = (2048 + n_buckets - 1) / n_buckets;
   if (S > n_parts / 4) S = n_parts / 4;
   // ... and an average block should count a few ten thousand ids for the 64 KiB of LDS it clears and the 64 KiB of partial counters it
   // publishes (a rank's user shard at 8 ranks: 2200 blocks of ~20K ids each; the weight split keeps the hot buckets' blocks average too)
-  const int64_t ids = pl_knobs().block_ids;
-  if (bounded && ids > 0) {
-    const int64_t by_work = n_parts * PL_PART / ((int64_t)n_buckets * ids);
+  if (bounded) {
+    const int64_t by_work = n_parts * PL_PART / ((int64_t)n_buckets * PL_BLOCK_IDS);
     if (S > by_work) S = by_work;
   }
   if (S < 1) S = 1;
@@ -619,11 +593,8 @@ hipError_t launch_column_counts_partitioned(hipStream_t st, const int32_t* col_i
     hipError_t we = launch_slice_weights(st, loc_t, n_buckets, n_parts, weight);
     if (we != hipSuccess) return we;
     hipLaunchKernelGGL(pl_blockmap_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, weight, n_buckets, n_parts, S, blk_prefix);
-    const int dbg = pl_knobs().debug, lps = pl_knobs().lanes;
-    const dim3 hg((unsigned)pl_max_blocks(n_buckets, S)), hb(PLH_THREADS);
-    if (lps == 4) hipLaunchKernelGGL((pl_hist_kernel<4>), hg, hb, 0, st, bucketed, loc_t, n_buckets, n_parts, blk_prefix, n_cols, partial, dbg);
-    else if (lps == 8) hipLaunchKernelGGL((pl_hist_kernel<8>), hg, hb, 0, st, bucketed, loc_t, n_buckets, n_parts, blk_prefix, n_cols, partial, dbg);
-    else hipLaunchKernelGGL((pl_hist_kernel<16>), hg, hb, 0, st, bucketed, loc_t, n_buckets, n_parts, blk_prefix, n_cols, partial, dbg);
+    hipLaunchKernelGGL(pl_hist_kernel, dim3((unsigned)pl_max_blocks(n_buckets, S)), dim3(PLH_THREADS), 0, st, bucketed, loc_t, n_buckets, n_parts,
+                       blk_prefix, n_cols, partial);
     hipLaunchKernelGGL(pl_reduce_kernel, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, partial, blk_prefix, n_cols, counts);
     return hipGetLastError();
   }

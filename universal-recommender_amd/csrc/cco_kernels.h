@@ -23,6 +23,22 @@ constexpr int BIN_OFF_LEN = NBINS + 3;        // bin_off: [0 .. NBINS] list offs
 constexpr int CAND_SLOTS = 64;           // words the row kernels spread their candidate counts over (see CcoArgs::cand)
 constexpr int STATS_LEN = 32;            // [0] pairs, then NBINS each of rows / pairs / users / out entries per bin, [1 + 4 NBINS] table overflows
 
+// Bits of urcco_session_set_debug / urcco_context_set_debug (include/urcco.h documents them; bench.py and the tests pass the values).
+// SpGEMM row phases switched off (profiling only, results meaningless): the DBG instantiations of the row kernels.
+constexpr int32_t DBG_GATHER_ONLY = 1;
+constexpr int32_t DBG_NO_LLR = 2;
+constexpr int32_t DBG_NO_TOPK = 4;
+constexpr int32_t DBG_NO_SELECT = 8;
+constexpr int32_t DBG_NO_RANK = 16;
+constexpr int32_t DBG_NO_COUNT_GATHER = 512;
+// A/B paths of the host level
+constexpr int32_t DBG_UNFUSED_EXPAND = 4096;        // every event type prepares its own expand operands
+constexpr int32_t DBG_GATHERED_PRIMARY = 8192;      // the primary's CSC from a pass over the whole gathered A' instead of fragments
+constexpr int32_t DBG_UNFILTERED_EXCHANGE = 16384;  // several ranks: every row of B is exchanged
+constexpr int32_t DBG_SELECT_DELAY = 131072;        // test hook: the first wave of a multi-wave team dawdles before the select histogram
+constexpr int32_t DBG_UNPACKED_COUNTS = 1048576;    // B' travels as plain columns, the row kernels gather the counts
+constexpr int32_t DBG_ROW_KERNELS = DBG_GATHER_ONLY | DBG_NO_LLR | DBG_NO_TOPK | DBG_NO_SELECT | DBG_NO_RANK | DBG_NO_COUNT_GATHER | DBG_SELECT_DELAY;
+
 struct CcoArgs {
   // row lists per bin
   const int32_t* bin_rows;   // item ids grouped by bin
@@ -48,7 +64,7 @@ struct CcoArgs {
   const double* xlx_tab;     // [XLX_TABLE_HOST] xLogX of small integers
   const double* xlx_hi;      // [XLX_TABLE_HOST] xLogX(n_users - d): the k22 term without a logarithm
   const double* col_ent;     // [XLX_TABLE_HOST] columnEntropy of a column with d interactions, for the N of the build (behind xlx_hi in the same allocation)
-  int32_t debug;             // ablation switches for profiling (0 in production): 1 = gather only, 2 = no LLR, 4 = no top-k
+  int32_t debug;             // DBG_* bits (0 in production); the row kernels read those of DBG_ROW_KERNELS
   long long n_users;
   int32_t n_cols_b;
   int32_t item_lo;
@@ -91,7 +107,7 @@ hipError_t launch_slice_weights(hipStream_t st, const unsigned short* loc_t, int
 hipError_t launch_downsample_flags(hipStream_t st, int n_cu, int64_t n_rows, const int64_t* row_ptr, const int32_t* col_idx, int64_t nnz,
                                    int32_t n_cols, const int32_t* raw_counts, unsigned long long* thresholds, uint32_t seed, int32_t max_n,
                                    int row_rate_mode, int64_t row_base, int64_t* tile_rows, unsigned long long* flags, int64_t* tile_count,
-                                   int32_t* post_counts, int debug);
+                                   int32_t* post_counts);
 hipError_t launch_downsample_scan(hipStream_t st, int64_t nnz, int64_t* tile_count);
 hipError_t launch_downsample_compact(hipStream_t st, int64_t n_rows, const int64_t* row_ptr, const int32_t* col_idx, int64_t nnz,
                                      const int64_t* tile_rows, const unsigned long long* flags, const int64_t* tile_off, int64_t* out_row_ptr,

@@ -3,7 +3,6 @@
 #include "cco_kernels.h"
 
 #include <atomic>
-#include <cstdio>
 #include <cstdlib>
 
 #include "cco_common.h"
@@ -597,7 +596,7 @@ constexpr int URCCO_G_CU = 2;
 // from the row's work (1.25 x the expected distinct columns per pass must fit) and doubles whenever a pass still overflows --
 // at the latest when ceil(n_cols / P) columns are GUARANTEED to fit, so every row ends.  Round 2 served these rows from dense
 // counters in global memory (n_cols x 16 B of scratch per resident block, L2 atomics): 35.9 ms for 16K rows of config 5.
-// DBG: the ablation / test switches of CcoArgs::debug exist only in a second instantiation (profiling tools and the race regression tests
+// DBG: the ablation / test switches of CcoArgs::debug exist only in a second instantiation (profiling tools and the select race regression test
 // launch it); the production instantiation carries neither their branches nor the scalar register a.debug would occupy -- at eight waves
 // per SIMD a wave has 78 scalar registers and the one-wave class spilled 128 of them to vector lanes (round 5: 69 after this and the
 // single-check LLR).
@@ -858,7 +857,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
             at[q] = ~0u;
             if (on[q]) {
               const unsigned col = jj[q] & colmask;
-              if (dbg & 1) {  // ablation: gather only
+              if (dbg & DBG_GATHER_ONLY) {  // ablation: gather only
                 if (jj[q] == 0xffffffffu) tab[0] = 1u;
               } else if (MP) {
                 if ((col & mp_mask) == mp_q && !tab_insert<SH>(tab, (col >> mp_s) + 1u, cb, ident, at[q])) s_mpflag = 1u;
@@ -967,7 +966,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
             const int j = MP ? (int)((((vv[x] >> cb) - 1u) << mp_s) | mp_q) : (int)(vv[x] >> cb) - 1;
             // the candidate's cB: out of its slot of the key array, where the compaction left it (it came with the B' word) -- or, for a B' without counts aboard, the ONE scattered
             // gather per candidate of rounds 1-5 (ablation 512: a made-up count, no gather)
-            cbj[x] = packed ? (int)(unsigned)kk[t] : ((dbg & 512) ? (int)(vv[x] & cmask) + 100 : (use16 ? (int)cnt_b16[j] : cnt_b[j]));
+            cbj[x] = packed ? (int)(unsigned)kk[t] : ((dbg & DBG_NO_COUNT_GATHER) ? (int)(vv[x] & cmask) + 100 : (use16 ? (int)cnt_b16[j] : cnt_b[j]));
           }
         }
         // every operand of these U candidates of every lane inside the tables: the wave takes the straight-line table form (see llr_from_tables)
@@ -975,7 +974,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
 #pragma unroll
         for (int x = 0; x < U; ++x)
           if (vv[x] != 0u) in_tables = in_tables && llr_operands_in_tables(vv[x] & cmask, ca, (unsigned)cbj[x], n_users, col_ent);
-        const bool all_in_tables = !(dbg & 2) && __ballot(!in_tables) == 0ull;  // wave-uniform
+        const bool all_in_tables = !(dbg & DBG_NO_LLR) && __ballot(!in_tables) == 0ull;  // wave-uniform
 #pragma unroll
         for (int x = 0; x < U; ++x) {
           const unsigned t = t0 + (unsigned)x * T;
@@ -985,7 +984,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
             unsigned long long key = 0ull;
             if (!(a.exclude_self && j == i)) {
               const double llr = all_in_tables ? llr_from_tables(row_entropy, xlx_n, (unsigned)k11, (unsigned)ca, (unsigned)cbj[x], xlx_tab, xlx_hi, col_ent)
-                                               : ((dbg & 2) ? (double)k11
+                                               : ((dbg & DBG_NO_LLR) ? (double)k11
                                                             : llr_of(row_entropy, xlx_n, k11, ca, (long long)cbj[x], n_users, xlx_tab, xlx_hi, col_ent));
               if (llr > 0.0 && (!a.has_min_llr || llr >= a.min_llr)) key = (unsigned long long)__double_as_longlong(llr);
             }
@@ -1023,8 +1022,8 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
     unsigned long long thr_key = 0ull;
     unsigned thr_ncol = 0u;
     bool row_done = false;  // team-uniform: the select's finish has already written the row
-    if (!(dbg & 4)) {
-      if (dbg & 8) {  // ablation: no select (nothing passes)
+    if (!(dbg & DBG_NO_TOPK)) {
+      if (dbg & DBG_NO_SELECT) {  // ablation: no select (nothing passes)
         if (C > (unsigned)a.k) thr_key = ~0ull;
       } else if (C > (unsigned)a.k) {  // team-uniform
         // MSB-first radix select of the k-th composite, 8-bit digits, LDS histograms (three rotating 256-bin arrays of
@@ -1124,10 +1123,10 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
             list_n = uni(sel_res[0]);
           }
           first_pass = false;
-          // test hook (tests/test_gpu_parity.py::test_select_overlay_race_*): the team's FIRST wave -- it owns the lowest table entries, the
+          // test hook (tests/test_gpu_parity.py::test_select_overlay_race_fixed): the team's FIRST wave -- it owns the lowest table entries, the
           // ones a tie at the cut selects -- dawdles before it reads the histogram, so that its siblings are far ahead of it: the
           // interleaving the round-3 race needed, made certain
-          if (T != WAVE && (dbg & 131072) && tl / WAVE == 0) {
+          if (T != WAVE && (dbg & DBG_SELECT_DELAY) && tl / WAVE == 0) {
 #ifdef HIPSIM_HOST_BUILD
             __builtin_amdgcn_s_sleep(127);
 #else
@@ -1176,13 +1175,13 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
             // multi-wave class with the overlay -- then cut a row's top k at a threshold computed from clobbered counts: one or two
             // entries lost at the cut in ~1 build of 50 on config 4, now and then a garbage column and a wild store (the GPU memory
             // fault of profiles/r03_rocprofv3_stats_failure.txt; found by tools/race_hunt.py, profiles/r04_race_hunt.log).  prev_cnt is
-            // team-uniform, so every wave takes the barrier.  (debug 262144 skips it: the regression test's negative control.)
-            if (SHARE && T != WAVE && !(dbg & 262144)) team_sync<T>();
+            // team-uniform, so every wave takes the barrier.
+            if (SHARE && T != WAVE) team_sync<T>();
             // Round 5: when the cut bin AND everything above it (k - need composites) fit the set, they are copied out together and ranked ONCE --
             // the best k of that ranking ARE the row, in output order.  (Before: the bin's members ranked among themselves for the exact threshold,
             // a sweep for the survivors, the survivors ranked again: two sweeps and two rankings, at four vector instructions per compared element,
             // in classes that are bound by vector issue.)  The sweep then covers every candidate: what lies above the bin is not in the index list.
-            const bool merged = !MP && !a.unordered && !(dbg & 16) && ((unsigned)a.k - need) + prev_cnt <= (unsigned)SEL_M;  // team-uniform
+            const bool merged = !MP && !a.unordered && !(dbg & DBG_NO_RANK) && ((unsigned)a.k - need) + prev_cnt <= (unsigned)SEL_M;  // team-uniform
             const unsigned n_scan2 = (have_list && !merged) ? list_n : D;
             unsigned amb_n = 0u;  // (one-wave teams: the length of the set)
             for (unsigned base = 0; base < n_scan2; base += T) {  // scalar loop control, no divergent exits: claim_positions is a wave operation
@@ -1301,7 +1300,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
         }
       }
       team_sync<T>();
-      const unsigned n = (dbg & 16) ? 0u : (T == WAVE ? sel_n : uni(*nsel));  // ablation 16: no ranking / output
+      const unsigned n = (dbg & DBG_NO_RANK) ? 0u : (T == WAVE ? sel_n : uni(*nsel));  // ablation 16: no ranking / output
       if (MP) {
         // merge the pass's <= k survivors into the running top k: every element of both lists is ranked over both (by counting),
         // the best k land in the other running buffer at their rank -- which is the output order
@@ -1565,7 +1564,7 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
     unsigned jj = 0u;  // this lane's B' word: the column, and (packed) the column's count
     if ((unsigned)sl < total) {
       jj = (unsigned)b_col_idx[base_o + sl];
-      if (!(dbg & 1)) {
+      if (!(dbg & DBG_GATHER_ONLY)) {
         bool ok;
         slot = tab_insert_claim(tab, (jj & colmask) + 1u, cb, (unsigned)(G::TW - 1), 32 - G::LOG2TW, ident, &ok);
         if (!ok) atomicAdd(a.err, 1ull);
@@ -1594,19 +1593,19 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
     if (is_cand) {
       const int j = (int)(vv >> cb) - 1;
       const long long k11 = (long long)(vv & cmask);
-      const unsigned cbj = packed ? jj >> cshift : ((dbg & 512) ? (unsigned)k11 + 100u : (use16 ? ((j & 1) ? cb_raw >> 16 : cb_raw & 0xffffu) : cb_raw));
+      const unsigned cbj = packed ? jj >> cshift : ((dbg & DBG_NO_COUNT_GATHER) ? (unsigned)k11 + 100u : (use16 ? ((j & 1) ? cb_raw >> 16 : cb_raw & 0xffffu) : cb_raw));
       in_tables = llr_operands_in_tables((unsigned)k11, ca, cbj, n_users, col_ent);
     }
     // Every operand of every candidate inside the tables (always, once the interaction cut has capped the counts): the wave takes the
     // straight-line form -- five table reads in flight together, no logarithm behind a divergent branch.  Wave-uniform test.
-    const bool all_in_tables = !(dbg & 2) && __ballot(is_cand && !in_tables) == 0ull;
+    const bool all_in_tables = !(dbg & DBG_NO_LLR) && __ballot(is_cand && !in_tables) == 0ull;
     if (is_cand) {
       const int j = (int)(vv >> cb) - 1;
       const long long k11 = (long long)(vv & cmask);
       if (!(a.exclude_self && j == i)) {
-        const unsigned cbj = packed ? jj >> cshift : ((dbg & 512) ? (unsigned)k11 + 100u : (use16 ? ((j & 1) ? cb_raw >> 16 : cb_raw & 0xffffu) : cb_raw));
+        const unsigned cbj = packed ? jj >> cshift : ((dbg & DBG_NO_COUNT_GATHER) ? (unsigned)k11 + 100u : (use16 ? ((j & 1) ? cb_raw >> 16 : cb_raw & 0xffffu) : cb_raw));
         const double llr = all_in_tables ? llr_from_tables(row_entropy, xlx_n, (unsigned)k11, (unsigned)ca, cbj, xlx_tab, xlx_hi, col_ent)
-                                         : ((dbg & 2) ? (double)k11
+                                         : ((dbg & DBG_NO_LLR) ? (double)k11
                                                       : llr_of(row_entropy, xlx_n, k11, ca, (long long)cbj, n_users, xlx_tab, xlx_hi, col_ent));
         if (llr > 0.0 && (!a.has_min_llr || llr >= a.min_llr)) mk = (unsigned long long)__double_as_longlong(llr);
       }
@@ -1622,7 +1621,7 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
       URCCO_SETTLE(pf_w1); URCCO_SETTLE(pf_wp); URCCO_SETTLE(pf_start); URCCO_SETTLE(pf_ca); URCCO_SETTLE(pf_ent);
       URCCO_SETTLE(cs2); URCCO_SETTLE(ce2); URCCO_SETTLE(i_n3);
     };
-    if (a.unordered && all_fit_k && !(dbg & 4)) {  // every candidate is emitted: no ranking needed (wave-uniform)
+    if (a.unordered && all_fit_k && !(dbg & DBG_NO_TOPK)) {  // every candidate is emitted: no ranking needed (wave-uniform)
       const int64_t obase = ((int64_t)(i - a.item_lo)) * a.k;
       settle_prefetch();
       if (mk != 0ull) {
@@ -1631,7 +1630,7 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
         out_llr[obase + opos] = __longlong_as_double((long long)mk);
       }
       if (sl == 0 && live) out_count[i - a.item_lo] = n_valid;
-    } else if (!(dbg & 4)) {
+    } else if (!(dbg & DBG_NO_TOPK)) {
       const int64_t obase = ((int64_t)(i - a.item_lo)) * a.k;
       // candidates dense by lane, replicated while they fit twice / four times into the row's segment: replica q counts elements q, q + R, ...
       unsigned rank;
@@ -1897,40 +1896,19 @@ static int blocks_per_cu(int bin) {
 hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, int bin, int32_t n_rows) {
   // Persistent grids sized to the chip; each kernel reads its own row list length from bin_off on the device,
   // so no host synchronisation sits between binning and the SpGEMM.
-  // Several times as many blocks as fit the chip (tunable per class through URCCO_GRID_FACTORS="f0,f1,..,f5" for measurements):
-  // the later ones start as blocks of the first wave retire, which evens out the classes' ragged ends -- rows are dealt out by a
-  // static stride, so a block's share of heavy rows is luck -- and lets short kernels of the other event types' streams in: a grid
-  // that exactly fills the chip locks them out until it ends (measured: single-block kernels of another stream waited 0.2 ms).
+  // Several times as many blocks as fit the chip: the later ones start as blocks of the first wave retire, which evens out the
+  // classes' ragged ends -- rows are dealt out by a static stride, so a block's share of heavy rows is luck -- and lets short kernels
+  // of the other event types' streams in: a grid that exactly fills the chip locks them out until it ends (measured: single-block
+  // kernels of another stream waited 0.2 ms).
   // Round 2 (config 3): 2x, and 3x / 4x / 8x measured no better.  Round 5 (config 4 / 5, after the row kernels had lost a third of
   // their time): 8x for the four big classes and 4x for the 512/1024-thread classes = -0.55 / -0.8 ms per build, every class's own
   // time included (profiles/r05_grid_factors_ab.log); bounded by one row loop per 32 item rows of the build (small builds and the ranks of a sharded
   // build keep the 2x: a row loop's start-up -- three rows of prefetches -- is not free; at an eighth of config 4's rows 4x measured 0.12 ms
   // per rank slower than 2x).
-  struct Factors {  // initialised once, thread-safely: every event type's enqueueing thread comes through here in the first build
-    int f[7] = {8, 8, 8, 8, 4, 4, 2};
-    Factors() {
-      if (const char* e = getenv("URCCO_GRID_FACTORS")) {
-        int v[6];
-        if (sscanf(e, "%d,%d,%d,%d,%d,%d", &v[0], &v[1], &v[2], &v[3], &v[4], &v[5]) == 6)
-          for (int b = 0; b < 6; ++b)
-            if (v[b] >= 1 && v[b] <= 64) f[b] = v[b];
-      }
-    }
-  };
-  static const Factors factors;
-  const int* factor = factors.f;
+  static constexpr int factor[NBINS] = {8, 8, 8, 8, 4, 4, 2};
   // the micro class's sub-lists of shared waves (two / four rows per wave and pass) hold a third of the class's passes each at most: smaller grids,
-  // so that a wave still runs several passes behind its start-up (three rows of prefetches).  URCCO_MICRO_GRID="f32,f16" for measurements.
-  struct MicroFactors {
-    int f32 = 3, f16 = 2;
-    MicroFactors() {
-      if (const char* e = getenv("URCCO_MICRO_GRID")) {
-        int a = 0, b = 0;
-        if (sscanf(e, "%d,%d", &a, &b) == 2 && a >= 1 && a <= 64 && b >= 1 && b <= 64) { f32 = a; f16 = b; }
-      }
-    }
-  };
-  static const MicroFactors micro_factors;
+  // so that a wave still runs several passes behind its start-up (three rows of prefetches).
+  constexpr int micro_factor32 = 3, micro_factor16 = 2;
   auto grid = [&](int b, int f = 0) {
     const long long fill = (long long)n_cu * blocks_per_cu(b);  // blocks resident at once
     const long long teams = b <= 1 ? 4 : 1;                       // row loops per block (micro / one-wave classes: four one-wave teams)
@@ -1940,7 +1918,7 @@ hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, in
     if (blocks > cap) blocks = cap;
     return dim3((unsigned)blocks);
   };
-  const bool dbgk = (args.debug & (1 | 2 | 4 | 8 | 16 | 512 | 131072 | 262144)) != 0;  // the ablation / test switches live in the DBG instantiations only
+  const bool dbgk = (args.debug & DBG_ROW_KERNELS) != 0;  // the ablation / test switches live in the DBG instantiations only
   // A B' with counts aboard: BOTH instantiations are enqueued -- whether the counts fit is a device-side fact, the one whose turn it is not returns at
   // once.  The DBG instantiations exist for the plain form only (the ablation switches price the count gather among other things).
   CcoArgs plain = args;
@@ -1966,8 +1944,8 @@ hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, in
     case 0:  // the class's three sub-lists, the rows that keep a wave to themselves first (each kernel reads its own list bounds on the device)
       URCCO_LAUNCH_MICRO(64, grid(0));
       if (micro_split_for(n_rows)) {  // (the same rule as the binning pass: without the split the two sub-lists are empty)
-        URCCO_LAUNCH_MICRO(32, grid(0, micro_factors.f32));
-        URCCO_LAUNCH_MICRO(16, grid(0, micro_factors.f16));
+        URCCO_LAUNCH_MICRO(32, grid(0, micro_factor32));
+        URCCO_LAUNCH_MICRO(16, grid(0, micro_factor16));
       }
       break;
     case 1: URCCO_LAUNCH_ROWS(64, E0, URCCO_U_WAVE, false, grid(1), 256, 1); break;

@@ -63,11 +63,10 @@ __global__ __launch_bounds__(256) void tile_rows_kernel(int64_t n_rows, const in
 // rare: the tile notes whether it holds one and only then looks the row lengths up.  The row_ptr slice is read from
 // global memory (coalesced, twice: as a start and as the previous row's end), so a tile with any number of empty rows
 // needs no staging.
-// `debug` (profiling only, results meaningless): 32 = cheap hash, 64 = no threshold gather, 128 = no row lookup
 constexpr int DS_RUN = 8;
 constexpr int DS_RUNS = DS_TILE / (DS_THREADS * DS_RUN);  // 2
 constexpr int URCCO_DS_WAVES = 1;  // minimum waves per SIMD the flags kernel is compiled for (A/B knob: 8 caps it at 64 VGPRs)
-template <bool DEBUG, bool RNG32>
+template <bool RNG32>
 __global__ __launch_bounds__(DS_THREADS, URCCO_DS_WAVES) void downsample_flags_kernel(int64_t n_rows, const int64_t* __restrict__ rp,
                                                                       const int32_t* __restrict__ ci, int64_t nnz,
                                                                       const int64_t* __restrict__ g,
@@ -76,8 +75,7 @@ __global__ __launch_bounds__(DS_THREADS, URCCO_DS_WAVES) void downsample_flags_k
                                                                       int32_t max_n, int row_rate_mode, int64_t row_base,
                                                                       unsigned long long* __restrict__ flags,
                                                                       int64_t* __restrict__ tile_count,
-                                                                      int32_t* __restrict__ post_counts, int vec_ok, int debug_flags) {
-  const int debug = DEBUG ? debug_flags : 0;  // the ablation switches exist only in the profiling instantiation
+                                                                      int32_t* __restrict__ post_counts, int vec_ok) {
   __shared__ unsigned long long s_mask[DS_WORDS];  // bit p: a non-empty row starts at entry p of the tile
   __shared__ int s_row_at[DS_TILE];                // [p] (only where the bit is set): slice index of that row
   __shared__ int s_tbefore[DS_WORDS];              // slice index of the last row starting before word w (0: the row covering the tile start)
@@ -112,20 +110,18 @@ __global__ __launch_bounds__(DS_THREADS, URCCO_DS_WAVES) void downsample_flags_k
   const int64_t r_e = g1 < n_rows ? g1 : n_rows;
   const int64_t n_slice = r_e - r_s + 1;
   __syncthreads();
-  if (!(debug & 128)) {
-    int any_long = 0;
-    for (int64_t t = threadIdx.x; t + 1 < n_slice; t += DS_THREADS) {  // rows r_s + t, t < n_slice - 1 (row r_e starts behind the tile)
-      const int64_t a = rp[r_s + t] - e0, b = rp[r_s + t + 1] - e0;
-      if (b > a) {  // non-empty: the one row that owns the entries from a on
-        if (a >= 0) {  // a < DS_TILE: only r_e may start at or behind the tile end
-          s_row_at[a] = (int)t;
-          atomicOr(&s_mask[a >> 6], 1ull << (a & 63));
-        }
-        any_long |= (b - a > (int64_t)max_n) ? 1 : 0;
+  int any_long = 0;
+  for (int64_t t = threadIdx.x; t + 1 < n_slice; t += DS_THREADS) {  // rows r_s + t, t < n_slice - 1 (row r_e starts behind the tile)
+    const int64_t a = rp[r_s + t] - e0, b = rp[r_s + t + 1] - e0;
+    if (b > a) {  // non-empty: the one row that owns the entries from a on
+      if (a >= 0) {  // a < DS_TILE: only r_e may start at or behind the tile end
+        s_row_at[a] = (int)t;
+        atomicOr(&s_mask[a >> 6], 1ull << (a & 63));
       }
+      any_long |= (b - a > (int64_t)max_n) ? 1 : 0;
     }
-    if (any_long) s_long = 1;
   }
+  if (any_long) s_long = 1;
   __syncthreads();
   if (threadIdx.x < WAVE) {  // wave 0: slice index of the last row starting before each word (prefix maximum)
     const unsigned long long m = s_mask[lane];
@@ -151,7 +147,7 @@ __global__ __launch_bounds__(DS_THREADS, URCCO_DS_WAVES) void downsample_flags_k
     const int el0 = run * DS_RUN;
     unsigned thr_col[DS_RUN];  // the eight one-byte threshold gathers of the run travel together, under its row lookup
 #pragma unroll
-    for (int q = 0; q < DS_RUN; ++q) thr_col[q] = (debug & 64) ? 255u : (unsigned)thr8[cols[gq][q]];
+    for (int q = 0; q < DS_RUN; ++q) thr_col[q] = (unsigned)thr8[cols[gq][q]];
     const int w = el0 >> 6, sh = el0 & 63;
     const unsigned long long m = s_mask[w];
     const unsigned starts = (unsigned)(m >> sh) & 0xffu;             // rows starting inside the run
@@ -172,7 +168,7 @@ __global__ __launch_bounds__(DS_THREADS, URCCO_DS_WAVES) void downsample_flags_k
 #pragma unroll
     for (int q = 0; q < DS_RUN; ++q) {
       const unsigned long long h = RNG32 ? (unsigned long long)mix32_finish((uint32_t)cols[gq][q] ^ (key0 + (uint32_t)r_of[q] * MIX32_ROW))
-                                   : ((debug & 32) ? ((unsigned long long)((unsigned)cols[gq][q] * 0x9E3779B1u) << 21) : hash53(seed, row0 + (uint32_t)r_of[q], (uint32_t)cols[gq][q]));
+                                   : hash53(seed, row0 + (uint32_t)r_of[q], (uint32_t)cols[gq][q]);
       const unsigned h8 = (unsigned)(h >> (RNG32 ? THR8_SHIFT32 : THR8_SHIFT)), b = thr_col[q];
       bool keep = b == 255u || h8 < b;
       if (b == 254u || (b < 254u && h8 == b)) keep = h <= thresholds[cols[gq][q]];  // 1 sampled interaction in 256: the full threshold
@@ -296,7 +292,7 @@ __global__ __launch_bounds__(256) void sample_threshold_kernel(const int32_t* __
 hipError_t launch_downsample_flags(hipStream_t st, int n_cu, int64_t n_rows, const int64_t* row_ptr, const int32_t* col_idx, int64_t nnz,
                                    int32_t n_cols, const int32_t* raw_counts, unsigned long long* thresholds, uint32_t seed, int32_t max_n,
                                    int row_rate_mode, int64_t row_base, int64_t* tile_rows, unsigned long long* flags, int64_t* tile_count,
-                                   int32_t* post_counts, int debug) {
+                                   int32_t* post_counts) {
   if (nnz == 0) return hipSuccess;
   unsigned char* thr8 = reinterpret_cast<unsigned char*>(thresholds + n_cols);  // the scratch holds n_cols u64 + n_cols bytes
   const int rng32 = (row_rate_mode & 0x100) ? 1 : 0;  // URCCO_RNG_MIX32
@@ -308,19 +304,12 @@ hipError_t launch_downsample_flags(hipStream_t st, int n_cu, int64_t n_rows, con
   if (rblocks > rcap) rblocks = rcap;
   hipLaunchKernelGGL(tile_rows_kernel, dim3((unsigned)rblocks), dim3(256), 0, st, n_rows, row_ptr, tiles, tile_rows);
   const int vec_ok = (reinterpret_cast<uintptr_t>(col_idx) & 15) == 0;
-  if (debug & (32 | 64 | 128)) {
-    if (rng32)
-      hipLaunchKernelGGL((downsample_flags_kernel<true, true>), dim3((unsigned)tiles), dim3(DS_THREADS), 0, st, n_rows, row_ptr, col_idx, nnz, tile_rows, thresholds, thr8,
-                         seed, max_n, row_rate_mode, row_base, flags, tile_count, post_counts, vec_ok, debug);
-    else
-      hipLaunchKernelGGL((downsample_flags_kernel<true, false>), dim3((unsigned)tiles), dim3(DS_THREADS), 0, st, n_rows, row_ptr, col_idx, nnz, tile_rows, thresholds, thr8,
-                         seed, max_n, row_rate_mode, row_base, flags, tile_count, post_counts, vec_ok, debug);
-  } else if (rng32) {
-    hipLaunchKernelGGL((downsample_flags_kernel<false, true>), dim3((unsigned)tiles), dim3(DS_THREADS), 0, st, n_rows, row_ptr, col_idx, nnz, tile_rows, thresholds, thr8,
-                       seed, max_n, row_rate_mode, row_base, flags, tile_count, post_counts, vec_ok, 0);
+  if (rng32) {
+    hipLaunchKernelGGL((downsample_flags_kernel<true>), dim3((unsigned)tiles), dim3(DS_THREADS), 0, st, n_rows, row_ptr, col_idx, nnz, tile_rows, thresholds, thr8,
+                       seed, max_n, row_rate_mode, row_base, flags, tile_count, post_counts, vec_ok);
   } else {
-    hipLaunchKernelGGL((downsample_flags_kernel<false, false>), dim3((unsigned)tiles), dim3(DS_THREADS), 0, st, n_rows, row_ptr, col_idx, nnz, tile_rows, thresholds, thr8,
-                       seed, max_n, row_rate_mode, row_base, flags, tile_count, post_counts, vec_ok, 0);
+    hipLaunchKernelGGL((downsample_flags_kernel<false>), dim3((unsigned)tiles), dim3(DS_THREADS), 0, st, n_rows, row_ptr, col_idx, nnz, tile_rows, thresholds, thr8,
+                       seed, max_n, row_rate_mode, row_base, flags, tile_count, post_counts, vec_ok);
   }
   return hipGetLastError();
 }

@@ -262,7 +262,7 @@ int urcco_dev_downsample(urcco_session* s, int64_t n_rows, const int64_t* row_pt
   s->begin(URCCO_STAGE_DOWNSAMPLE_FLAGS);
   HIPC(urcco::launch_downsample_flags(s->stream, s->n_cu, n_rows, row_ptr, col_idx, nnz, n_cols, raw_counts, thresholds, (uint32_t)seed,
                                       max_elements_per_row, row_rate_mode, row_base, tile_rows, flags, tile_count,
-                                      ph_bytes > 0 ? nullptr : post_counts, s->debug));
+                                      ph_bytes > 0 ? nullptr : post_counts));
   s->end();
   s->begin(URCCO_STAGE_DOWNSAMPLE_SCAN);
   HIPC(urcco::launch_downsample_scan(s->stream, nnz, tile_count));
@@ -284,7 +284,7 @@ int urcco_dev_transpose(urcco_session* s, int64_t n_rows, const int64_t* row_ptr
       col_lo < 0 || col_hi < col_lo || col_hi > n_cols)
     return fail(URCCO_BAD_ARG, "urcco_dev_transpose: bad argument");
   const int64_t n_tiles = ((int64_t)n_cols + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
-  const int64_t tr_bytes = (s->debug & 256) ? 0 : urcco::transpose_scratch_bytes(n_rows, nnz, n_cols);  // 256: profiling, force the cursor-atomic kernel
+  const int64_t tr_bytes = urcco::transpose_scratch_bytes(n_rows, nnz, n_cols);
   URC(s->reserve(urcco_session::need((size_t)n_cols, 4) + urcco_session::need((size_t)n_tiles + 2, 8) + (size_t)tr_bytes + 256));
   int32_t* cursor = s->take<int32_t>((size_t)n_cols);
   int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
@@ -493,9 +493,9 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
   urcco::CcoArgs a;
   a.bin_rows = bin_rows; a.bin_off = bin_off;
   a.a_col_ptr = a_col_ptr; a.pstart = pstart; a.wp = wp; a.b_col_idx = b_col_idx;
-  // debug 1048576: the count gather of rounds 1-5 (A/B, tests).  pk_known: b_col_idx itself holds packed words (the rows a sharded build received
+  // DBG_UNPACKED_COUNTS: the count gather of rounds 1-5 (A/B, tests).  pk_known: b_col_idx itself holds packed words (the rows a sharded build received
   // travelled with their counts aboard -- the host learnt with the shard sizes that every count fits): no plain copy exists, every reader masks
-  a.b_packed = pk_known ? b_col_idx : ((b_packed && pack_bad && !(s->debug & 1048576)) ? b_packed : nullptr);
+  a.b_packed = pk_known ? b_col_idx : ((b_packed && pack_bad && !(s->debug & urcco::DBG_UNPACKED_COUNTS)) ? b_packed : nullptr);
   a.pack_bad = pack_bad;
   a.pk_known = pk_known ? 1 : 0;
   a.b_col_mask = pk_known ? (key_bits >= 32 ? 0xffffffffu : (1u << key_bits) - 1u) : 0xffffffffu;
@@ -503,7 +503,7 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
   a.n_users = n_users; a.n_cols_b = n_cols_b; a.item_lo = item_lo; a.exclude_self = exclude_self ? 1 : 0; a.k = k;
   a.has_min_llr = has_min_llr ? 1 : 0; a.min_llr = min_llr; a.count_bits = count_bits;
   a.col_bytes = n_cols_b <= (1 << 8) ? 1 : (n_cols_b <= (1 << 16) ? 2 : (n_cols_b <= (1 << 24) ? 3 : 4));
-  a.unordered = (s->unordered_rows || (s->debug & 32768)) ? 1 : 0;  // debug 32768: per-class measurement of the flag
+  a.unordered = s->unordered_rows ? 1 : 0;
   a.g_log2 = 4;  // 16 lanes stream one user's B' row: 64 B segments, matches the ~10-40 item rows the cut leaves
   a.out_count = out_count; a.out_idx = out_idx; a.out_llr = out_llr;
   a.err = reinterpret_cast<unsigned long long*>(stats + 1 + 4 * urcco::NBINS);
@@ -512,9 +512,9 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
   a.g_counts = s->g_counts; a.g_cand_key = s->g_cand_key; a.g_cand_col = s->g_cand_col; a.g_blocks = dense_bin6 ? s->g_blocks : 0;
   // Heaviest classes first (global, whole-CU, half-CU, ...): they have few, long rows and end raggedly; the fine-grained
   // one-wave and micro classes run last and finish sharply -- and, with a stream per event type, fill the heavy classes'
-  // tails of the other event types instead of leaving a tail of their own.  debug 65536 restores the ascending order.
+  // tails of the other event types instead of leaving a tail of their own.
   for (int step = 0; step < urcco::NBINS; ++step) {
-    const int bin = (s->debug & 65536) ? step : urcco::NBINS - 1 - step;
+    const int bin = urcco::NBINS - 1 - step;
     s->begin(URCCO_STAGE_CCO_BIN0 + bin);
     HIPC(urcco::launch_cco_rows_bin(s->stream, s->n_cu, a, bin, n));
     s->end();

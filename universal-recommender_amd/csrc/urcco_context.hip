@@ -636,17 +636,16 @@ int build_single(urcco_context* c, DevState& D, const std::vector<Shard>& sh, co
   // With two or more secondaries their expand preparation is FUSED: one pass over the CSC of A' gathers an interleaved
   // (start, length) record per user and writes every secondary's pstart / plen (one scattered sector per CSC entry instead of one
   // line per entry AND event type).  It runs on the first secondary's stream once every secondary has been sampled and A'
-  // transposed; the primary's own A'A does not wait for it.  (debug 4096: every event type prepares its own, as in round 2.)
+  // transposed; the primary's own A'A does not wait for it.  (DBG_UNFUSED_EXPAND: every event type prepares its own, as in round 2.)
   // Not under the host level's gate: there the secondaries land one after the other over tens of milliseconds, and a pass that needs
   // ALL of them sampled would hold every A'B_d back until the last upload has finished (measured on config 4, round 4: view's matrices
   // landed at 63 ms, its chain was enqueued at 102 ms -- the fused pass saves 2 ms of GPU time and cost 40 ms of wall time).
-  bool fuse = n_ds >= 3 && n_ds - 1 <= urcco::EXPAND_MULTI_MAX && !(c->debug & 4096) && gate == nullptr;
+  bool fuse = n_ds >= 3 && n_ds - 1 <= urcco::EXPAND_MULTI_MAX && !(c->debug & urcco::DBG_UNFUSED_EXPAND) && gate == nullptr;
   for (int d = 1; d < n_ds; ++d) fuse = fuse && sh[(size_t)d].nnz < ((int64_t)1 << 32);
   // Round 5: the PRIMARY's expand preparation rides on the same pass (A'A reads the down-sampled A as its B): its own pass was a second
   // scattered gather per CSC entry of A' -- 0.95 ms on config 4 against 1.1 ms for the four secondaries together -- and the price is that
-  // A'A starts once every secondary has been sampled instead of right behind the transposition (URCCO_FOLD_PRIMARY=0: as before).
-  static const bool fold_env = [] { const char* e = getenv("URCCO_FOLD_PRIMARY"); return !(e && e[0] == '0'); }();
-  const bool fold = fuse && fold_env && n_ds <= urcco::EXPAND_MULTI_MAX && sh[0].nnz < ((int64_t)1 << 32);
+  // A'A starts once every secondary has been sampled instead of right behind the transposition (profiles/r05_fold_primary_ab.log).
+  const bool fold = fuse && n_ds <= urcco::EXPAND_MULTI_MAX && sh[0].nnz < ((int64_t)1 << 32);
   const int f0 = fold ? 0 : 1;  // first event type of the fused pass
   std::vector<std::promise<int>> sampled((size_t)n_ds);
   std::vector<std::shared_future<int>> sampled_f((size_t)n_ds);
@@ -799,13 +798,13 @@ int build_single(urcco_context* c, DevState& D, const std::vector<Shard>& sh, co
 // several ranks (or the forced exchange path): SURVEY.md 8e.  `L` = this process's GPUs; every phase walks them.
 // ---------------------------------------------------------------------------------------------------------
 constexpr int XS = urcco::EXCH_SIZES;
-// the primary's CSC of a rank's item range comes from fragments (default) or, for A/B runs (debug bit 8192), from the pass every
+// the primary's CSC of a rank's item range comes from fragments (default) or, for A/B runs (DBG_GATHERED_PRIMARY), from the pass every
 // rank makes over the whole gathered A'
-bool fragments(const urcco_context* c) { return !(c->debug & 8192); }
+bool fragments(const urcco_context* c) { return !(c->debug & urcco::DBG_GATHERED_PRIMARY); }
 // Row-filtered exchange of the down-sampled matrices (cco_misc.hip, "Row-filtered exchange"): a rank receives the rows of B' only
 // of the users that hold an item of ITS range.  Needs the ranges on the device before any whole-matrix work (the fragments route) and
-// an all-to-all-v; debug bit 16384 restores the all-gather of every row (A/B).
-bool filtered(const urcco_context* c) { return fragments(c) && c->world <= 64 && !(c->debug & 16384) && (!c->have_cb || c->cb.all_to_all_v != nullptr); }
+// an all-to-all-v; DBG_UNFILTERED_EXCHANGE restores the all-gather of every row (A/B).
+bool filtered(const urcco_context* c) { return fragments(c) && c->world <= 64 && !(c->debug & urcco::DBG_UNFILTERED_EXCHANGE) && (!c->have_cb || c->cb.all_to_all_v != nullptr); }
 
 // this shard's part of the filtered exchange of event type d, up to the sizes: per-destination masked row lengths, their scan, the
 // totals per destination (own row of E.to_nnz); on event d's stream, behind the masks (D.need_ready)
@@ -877,10 +876,10 @@ int input_phase(urcco_context* c, int d, const std::vector<std::vector<Shard>>& 
     URC(E.sizes.ensure((size_t)XS * (size_t)c->world));
     E.s->begin(URCCO_STAGE_EXCHANGE);
     HIPC(urcco::launch_row_lengths(E.s->stream, D.n_cu, s.n_rows, E.s_rp.p, E.deg.p, E.deg16.p, E.sizes.p + XS * D.rank));
-    // (never: debug 1048576, and the primary of a build that gathers and transposes the WHOLE A' on every rank -- debug 8192 -- reads the received words as columns)
-    const bool no_pack = (c->debug & 1048576) != 0 || (d == 0 && !fragments(c));
+    // (never: DBG_UNPACKED_COUNTS, and the primary of a build that gathers and transposes the WHOLE A' on every rank -- DBG_GATHERED_PRIMARY -- reads the received words as columns)
+    const bool no_pack = (c->debug & urcco::DBG_UNPACKED_COUNTS) != 0 || (d == 0 && !fragments(c));
     // round 6: can a B' word of this event type carry its column's count?  A fact of the all-reduced count table -- every rank finds the same answer
-    // and learns the others' with the shard sizes -- and, when it can, this rank's shard is packed HERE, before it travels (debug 1048576: never)
+    // and learns the others' with the shard sizes -- and, when it can, this rank's shard is packed HERE, before it travels (DBG_UNPACKED_COUNTS: never)
     {
       int key_bits = 1;
       while (((int64_t)1 << key_bits) <= p.n_cols) ++key_bits;
@@ -1243,7 +1242,7 @@ int build_sharded(urcco_context* c, const std::vector<std::vector<Shard>>& sh, c
     for (int r = 0; r < W; ++r) b_nnz[(size_t)d] += sizes[(size_t)XS * r + 1];
     c->h_sizes[(size_t)d] = b_nnz[(size_t)d];
   }
-  bool fuse = n_ds >= 3 && n_ds - 1 <= urcco::EXPAND_MULTI_MAX && !(c->debug & 4096);
+  bool fuse = n_ds >= 3 && n_ds - 1 <= urcco::EXPAND_MULTI_MAX && !(c->debug & urcco::DBG_UNFUSED_EXPAND);
   for (int d = 1; d < n_ds; ++d) fuse = fuse && b_nnz[(size_t)d] < ((int64_t)1 << 32);
   URC(c->workers->run([&](size_t g) -> int {
     DevState& D = c->devs[g];

@@ -116,7 +116,7 @@ struct urcco_session {
   double* xlx_tab = nullptr;  // xLogX of small integers (N-independent), filled once
   double* xlx_hi = nullptr;   // xLogX(N - d) for the N of the last build
   long long xlx_hi_n = -1;
-  int debug = 0;              // kernel ablation switches (profiling only)
+  int debug = 0;              // urcco::DBG_* bits (urcco_session_set_debug)
   unsigned* marks = nullptr;  // URCCO_DEBUG_MARKS: pinned host words [0] last launch group begun, [1] last finished ((ordinal << 8) | stage)
   unsigned mark_seq = 0;
   int unordered_rows = 0;     // URCCO_FLAG_UNORDERED_ROWS of the owning context
