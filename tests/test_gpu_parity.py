@@ -45,6 +45,34 @@ def test_transposition_empty_row_runs_on_gpu(gpu_session):
     logic.test_large_transpose_long_runs_of_empty_rows(gpu_session)
 
 
+@pytest.mark.parametrize("case", [logic.test_partitioned_column_counts_bucket_contiguous_layout, logic.test_partitioned_column_counts_big_chunks_and_hot_columns],
+                         ids=lambda f: f.__name__)
+def test_column_count_layout_case_on_gpu(case, gpu_session, monkeypatch):
+    """The column-count cases that switch the layout and the chunk size through the environment (read per call)."""
+    case(gpu_session, monkeypatch)
+
+
+def test_multipass_class_adversarial_low_bits_on_gpu(gpu_session):
+    logic.test_multipass_class_adversarial_low_bits_and_k_limits(gpu_session)
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_row_scan_large_matrix_edges_on_gpu(gpu_session, mode):
+    logic.test_row_scan_large_matrix_edges(gpu_session, mode)
+
+
+@pytest.mark.parametrize("n_cols", logic.LAYOUT_WIDTHS)
+def test_column_layout_boundaries_on_gpu(gpu_session, n_cols):
+    """Part-local -> bucket-contiguous column counts (> 4,194,304 columns); atomic counts, in-scan post-sampling counts and the cursor-atomic
+    transposition (> 8,388,608) -- on both sides of each boundary."""
+    logic.column_layout_boundary_case(gpu_session, n_cols)
+
+
+@pytest.mark.parametrize("n_cols", logic.TIE_WIDTHS)
+def test_ties_cut_in_the_highest_column_digit_on_gpu(gpu_session, n_cols):
+    logic.column_digit_ties_case(gpu_session, n_cols)
+
+
 @pytest.mark.parametrize("wire", ["u16", "i32"])
 def test_merge_of_csc_fragments_on_gpu(gpu_session, wire):
     logic.test_merge_of_csc_fragments(gpu_session, wire)

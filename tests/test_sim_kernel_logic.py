@@ -652,3 +652,137 @@ def test_select_ambiguous_set_overlays_the_histograms(sim_session):
     finally:
         sim_session.set_debug(0)
     assert all(int(s[0][1 + 2]) == SELECT_RACE_ROWS_SMALL_BLOCK for s in stats)
+
+
+# ---- catalogue widths at which the code path changes (tests/test_gpu_wide_catalogues.py runs these on hardware) ----------------------
+# > 4,194,304 columns (PL_MAX_BUCKETS x 16384): column counts leave the part-local layout for the bucket-contiguous one; > 8,388,608 (PH_MAX_BUCKETS x
+# 8192, TP_MAX_BUCKETS x 16384): the atomic column-count kernel, post-sampling counts by L2 atomics inside the row scan, the cursor-atomic transposition.
+LAYOUT_WIDTHS = [4_194_304, 4_194_305, 8_388_608, 8_388_609]
+
+
+def csr_from_pairs(n_rows, n_cols, users, cols):
+    """Binary CSR of the (user, column) pairs, duplicates merged."""
+    key = np.unique(np.asarray(users, np.int64) * n_cols + np.asarray(cols, np.int64))
+    u = key // n_cols
+    rp = np.zeros(n_rows + 1, np.int64)
+    np.cumsum(np.bincount(u, minlength=n_rows), out=rp[1:])
+    return O.Csr(n_rows, n_cols, rp, (key - u * n_cols).astype(np.int32))
+
+
+def wide_pairs(rng, n_rows, n_cols, avg, head=2000, first_appearance=False):
+    """(users, cols) of Poisson(avg) entries per row over a catalogue too wide for a dense CDF (rand_csr): half the entries from a Zipf head
+    of `head` ids -- the first ids (first-appearance, i.e. popularity-ordered ids) or scattered over the width -- the rest uniform."""
+    deg = rng.poisson(avg, n_rows)
+    total = int(deg.sum())
+    if first_appearance:
+        ids = np.arange(head, dtype=np.int64)
+    else:
+        ids = rng.permutation(np.unique(rng.integers(0, n_cols, 2 * head)))[:head]
+    r = np.minimum(rng.zipf(1.2, total) - 1, ids.size - 1)
+    cols = np.where(rng.random(total) < 0.5, ids[r], rng.integers(0, n_cols, total))
+    return np.repeat(np.arange(n_rows, dtype=np.int64), deg), cols
+
+
+def _csc_as_sets(cp, ri):
+    """Row indices of a CSC sorted inside every column: the cursor-atomic transposition writes a column's rows in any order."""
+    col = np.repeat(np.arange(cp.size - 1, dtype=np.int64), np.diff(cp))
+    return ri[np.lexsort((ri, col))]
+
+
+def column_layout_boundary_case(sess, n_cols):
+    """Column counts, both row-rate modes under both RNGs, and the transposition of the raw and the down-sampled matrix at a catalogue width
+    where the code path changes (LAYOUT_WIDTHS), against the oracle: >= 2^20 entries, two columns held by 40,000 users (more than a 16-bit
+    partial counter holds), first-appearance ids that crowd the first buckets and ids scattered up to the last column.  The CSC is compared
+    per column as a set."""
+    R = O.RNG_MIX32
+    rng = np.random.default_rng(n_cols % 1000)
+    n_users = 70_000
+    u1, c1 = wide_pairs(rng, n_users, n_cols, 9, first_appearance=True)
+    u2, c2 = wide_pairs(rng, n_users, n_cols, 8)
+    hot_u = rng.choice(n_users, 40_000, replace=False)
+    users = np.concatenate([u1, u2, hot_u, hot_u, np.full(3, 17)])
+    cols = np.concatenate([c1, c2, np.zeros(40_000, np.int64), np.full(40_000, n_cols - 1), [n_cols - 2, n_cols // 2, (n_cols - 1) & ~16383]])
+    m = csr_from_pairs(n_users, n_cols, users, cols)
+    assert m.nnz >= (1 << 20)
+    raw_ref = O.column_counts(m)
+    assert raw_ref[0] >= 40_000 and raw_ref[n_cols - 1] >= 40_000
+    d = to_dev(m, sess.device)
+    cnt = sess.column_counts(d.col_idx, m.nnz, n_cols)
+    cp, ri = sess.transpose(d, cnt)
+    sess.synchronize()
+    assert np.array_equal(cnt.cpu().numpy(), raw_ref), "raw column counts differ"
+    ref_cp, ref_ri = O.transpose(m)
+    assert np.array_equal(cp.cpu().numpy(), ref_cp), "col_ptr of the raw matrix differs"
+    assert np.array_equal(_csc_as_sets(ref_cp, ri[:m.nnz].cpu().numpy()), _csc_as_sets(ref_cp, ref_ri)), "CSC of the raw matrix differs"
+    for mode in (0, 1, R, R | 1):
+        out, post = sess.downsample(d, m.nnz, cnt, 29, 40, mode)
+        sess.synchronize()
+        ref = O.downsample(m, raw_ref, 29, 40, mode)
+        assert np.array_equal(out.row_ptr.cpu().numpy(), ref.row_ptr), mode
+        assert np.array_equal(out.col_idx.cpu().numpy()[:ref.nnz], ref.col_idx), mode
+        post_ref = O.column_counts(ref)
+        assert np.array_equal(post.cpu().numpy()[:n_cols], post_ref), mode
+        if mode == (R | 1):
+            cp, ri = sess.transpose(out, post)
+            sess.synchronize()
+            ref_cp, ref_ri = O.transpose(ref)
+            assert np.array_equal(cp.cpu().numpy(), ref_cp), "col_ptr of the down-sampled matrix differs"
+            assert np.array_equal(_csc_as_sets(ref_cp, ri[:ref.nnz].cpu().numpy()), _csc_as_sets(ref_cp, ref_ri)), "CSC of the down-sampled matrix differs"
+
+
+@pytest.mark.parametrize("n_cols", LAYOUT_WIDTHS)
+def test_column_layout_boundaries(sim_session, n_cols):
+    column_layout_boundary_case(sim_session, n_cols)
+
+
+# Ties cut in the column digits at every col_bytes: widths just below and above each byte boundary of a column index.
+TIE_WIDTHS = [256, 257, 65_536, 65_537, 1 << 24, (1 << 24) + 1]
+
+
+def tied_columns(n_cols, n):
+    """n columns of B for a row whose candidates all tie: three small columns, columns spread over every value of the highest column digit
+    below 2^24 (so that the first column pass -- of the highest digit this width uses -- leaves fewer than k candidates in the top bin and
+    the cut falls in a lower bin), and the multiples of the highest used byte's unit below the width (columns that differ from 0 only in that
+    digit: 2^24 at 2^24 + 1 columns)."""
+    col_bytes = 1 if n_cols <= (1 << 8) else (2 if n_cols <= (1 << 16) else (3 if n_cols <= (1 << 24) else 4))
+    if col_bytes == 1:
+        return np.arange(n_cols - n, n_cols)
+    unit = 1 << (8 * (col_bytes - 1))
+    tops = [unit * j for j in range(1, 4) if unit * j < n_cols]
+    lo, hi = 1 << (8 * (min(col_bytes, 3) - 1)), min(n_cols, 1 << 24)
+    spread = np.linspace(lo, hi - 1, max(n - 3 - len(tops), 1)).astype(np.int64) if hi > lo else np.zeros(0, np.int64)
+    cols = np.unique(np.concatenate([[1, 2, 3], spread, tops]))
+    return np.union1d(cols, np.setdiff1d(np.arange(4, 4 + n), cols)[:max(n - cols.size, 0)])
+
+
+def tie_cases(n_cols):
+    """(holders, tied columns, k, accumulator class of the row): micro, one wave, small block / block, and bin 6 -- by the table's capacity
+    (multi-pass; k = 257: the global kernel) or, from 2^24 columns on (7 count bits), by the packed-count rule at cA = 128."""
+    cases = [(2, 30, 5, 0), (2, 150, 20, 1)]
+    if n_cols <= 257:
+        return cases + [(4, 200, 50, 2)]
+    cases += [(2, 1000, 50, 3), (2, 11_000, 50, 6), (2, 11_000, 257, 6)]
+    if n_cols >= (1 << 24):
+        cases += [(127, 60, 50, 5), (128, 60, 50, 6), (128, 300, 257, 6)]
+    return cases
+
+
+def column_digit_ties_case(sess, n_cols):
+    """Rows with more than k candidates of exactly equal LLR (the holders of the row's item hold exactly the same tied columns and nothing
+    else), so that the cut is decided in the column digits alone, down to the highest byte a column index of this width uses.  Exact ids;
+    the row must land in the intended accumulator class."""
+    for holders, n_tied, k, cls in tie_cases(n_cols):
+        cols = tied_columns(n_cols, n_tied)
+        assert cols.size > k and cols.max() < n_cols
+        n_users = holders + 40
+        a = csr_from_pairs(n_users, 2, np.concatenate([np.arange(holders), np.arange(holders, holders + 10)]),
+                           np.concatenate([np.zeros(holders, np.int64), np.ones(10, np.int64)]))
+        b = csr_from_pairs(n_users, n_cols, np.repeat(np.arange(holders), cols.size), np.tile(cols, holders))
+        _, _, st = compare_with_oracle(sess, [a, b], [P(100000, k), P(100000, k)], 5, exact_ids=True)
+        rows = st[1][0][1:8]
+        assert rows[cls] == 1 and rows.sum() == 1, (n_cols, holders, cols.size, k, rows)
+
+
+@pytest.mark.parametrize("n_cols", TIE_WIDTHS)
+def test_ties_cut_in_the_highest_column_digit(sim_session, n_cols):
+    column_digit_ties_case(sim_session, n_cols)

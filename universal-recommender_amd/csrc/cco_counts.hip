@@ -595,7 +595,7 @@ hipError_t launch_column_counts_partitioned(hipStream_t st, const int32_t* col_i
     hipLaunchKernelGGL(pl_blockmap_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, weight, n_buckets, n_parts, S, blk_prefix);
     hipLaunchKernelGGL(pl_hist_kernel, dim3((unsigned)pl_max_blocks(n_buckets, S)), dim3(PLH_THREADS), 0, st, bucketed, loc_t, n_buckets, n_parts,
                        blk_prefix, n_cols, partial);
-    hipLaunchKernelGGL(pl_reduce_kernel, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, partial, blk_prefix, n_cols, counts);
+    hipLaunchKernelGGL(pl_reduce_kernel, dim3((unsigned)(((int64_t)n_cols + 255) / 256)), dim3(256), 0, st, partial, blk_prefix, n_cols, counts);
     return hipGetLastError();
   }
   const int n_buckets = (int)(((int64_t)n_cols + PH_BUCKET - 1) >> PH_BITS);
@@ -615,7 +615,7 @@ hipError_t launch_column_counts_partitioned(hipStream_t st, const int32_t* col_i
   hipLaunchKernelGGL(ph_scatter_kernel, dim3((unsigned)n_parts), dim3(PHS_THREADS), 0, st, col_idx, nnz, nnz_dev, n_buckets, n_parts, offsets, bucketed, vec_ok);
   hipLaunchKernelGGL(ph_blockmap_kernel, dim3(1), dim3(SCAN_THREADS), 0, st, offsets, n_buckets, n_parts, blk_prefix, chunk);
   hipLaunchKernelGGL(ph_hist_kernel, dim3((unsigned)max_blocks), dim3(PHH_THREADS), 0, st, bucketed, offsets, n_buckets, n_parts, blk_prefix, partial, chunk);
-  hipLaunchKernelGGL(ph_reduce_kernel, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, partial, blk_prefix, n_cols, counts);
+  hipLaunchKernelGGL(ph_reduce_kernel, dim3((unsigned)(((int64_t)n_cols + 255) / 256)), dim3(256), 0, st, partial, blk_prefix, n_cols, counts);
   return hipGetLastError();
 }
 

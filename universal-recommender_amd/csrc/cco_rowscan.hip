@@ -297,7 +297,7 @@ hipError_t launch_downsample_flags(hipStream_t st, int n_cu, int64_t n_rows, con
   unsigned char* thr8 = reinterpret_cast<unsigned char*>(thresholds + n_cols);  // the scratch holds n_cols u64 + n_cols bytes
   const int rng32 = (row_rate_mode & 0x100) ? 1 : 0;  // URCCO_RNG_MIX32
   row_rate_mode &= 0xff;
-  hipLaunchKernelGGL(sample_threshold_kernel, dim3((unsigned)((n_cols + 255) / 256)), dim3(256), 0, st, raw_counts, n_cols, max_n, thresholds, thr8, rng32);
+  hipLaunchKernelGGL(sample_threshold_kernel, dim3((unsigned)(((int64_t)n_cols + 255) / 256)), dim3(256), 0, st, raw_counts, n_cols, max_n, thresholds, thr8, rng32);
   const int64_t tiles = (nnz + DS_TILE - 1) / DS_TILE;
   int64_t rblocks = (n_rows + 1 + 255) / 256;
   const int64_t rcap = (int64_t)n_cu * 8;
