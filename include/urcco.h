@@ -396,7 +396,10 @@ int urcco_dev_merge_fragments(urcco_session* s, int32_t world, int32_t item_lo, 
  * Outputs (strided, row r = item_lo + r): out_count[r] entries at out_idx/out_llr[r*k ..], sorted
  * (llr desc, col asc).  stats_dev (nullable, device int64[URCCO_STATS_LEN]): [0] pairs, then URCCO_N_BINS entries each
  * of rows / pairs / users (sum of cA) / emitted entries per accumulator bin (the last group only while timing is
- * enabled), then [1 + 4 * URCCO_N_BINS] accumulator-table overflows (an internal invariant: must be 0). */
+ * enabled), then [1 + 4 * URCCO_N_BINS] accumulator-table overflows (an internal invariant: must be 0).
+ * [URCCO_STATS_LEN - 1]: rows of the first accumulator bin (the micro class: <= 64 pairs and users) that were binned into its two
+ * shared-wave sub-lists (<= 16 / <= 32 pairs and users: four / two rows per wave) -- 0 when the build kept the class as one list
+ * (fewer item rows than URCCO_MICRO_SPLIT_ROWS, default 1,000,000): the word names the form of the micro class that ran. */
 #define URCCO_STATS_LEN 32
 #define URCCO_EXCH_SIZES 4 /* int64 words of a shard's record in urcco_dev_merge_fragments' sizes */
 int urcco_dev_cco_rows(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_items_a,

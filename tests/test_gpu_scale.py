@@ -88,36 +88,56 @@ def test_full_config4_every_row(gpu_session):
     assert sum(int(st[0]) for st, _ in res) > 1_000_000_000 and rows_by_bin[:6].min() > 0, rows_by_bin
 
 
-def test_full_config5_every_row(gpu_session):
-    """BASELINE config 5 at FULL size (config 4's shape with the hot head -- top 0.1 % of the items draw 40 % of the
-    interactions -- and 1 % heavy users x50), engine.json defaults as bench.py --workload config5 runs it: the heavy
-    users' rows are dropped by maxItemsPerUser (Int / Int row rate), the hot items' rows are too heavy for any single-pass
-    LDS accumulator (the multi-pass class)."""
-    from helpers import device_generated
-    from universal_recommender_amd import synth
-    cfg = synth.config5(1.0)
-    dev_mats, mats = device_generated(cfg, gpu_session.device)
-    assert max(int(np.diff(m.row_ptr).max()) for m in mats) > 500
-    # VERDICT r04 #4: the same job as EIGHT ranks (BASELINE config 5: "8 x MI355X") on this one GPU -- URCCO_FLAG_EMULATE_RANKS, the real
-    # 8-rank build with its collectives looped back on the device -- every rank's rows of the skewed catalogue against the same oracle pass
-    from helpers import RanksOfAJob, shard_rows, to_params
-    from universal_recommender_amd import _lib, sharded
+class RankStats:
+    """What a rank of a multi-rank build reports for one event type, copied to the host (the outputs themselves are views on context memory)."""
+
+    def __init__(self, ind):
+        self.item_lo, self.item_hi, self.stats = ind.item_lo, ind.item_hi, ind.stats.cpu().numpy().copy()
+
+
+def config5_one_rank_and_eight_ranks(sess, user_scale):
+    """BASELINE config 5 with `user_scale` of its 10M users x the full 2M / 2M / 2M / 200K / 2K item spaces, engine.json defaults, inputs generated on
+    the GPU: the one-rank build through the entry point bench.py times AND the same job as EIGHT ranks (BASELINE config 5: "8 x MI355X") on this one
+    GPU -- URCCO_FLAG_EMULATE_RANKS, the real 8-rank build with its collectives looped back on the device -- every row of both
+    against ONE oracle pass, the five down-sampled matrices bit for bit.  Returns (res, res8): per event type (stats vector, rows needing the
+    k-boundary tie rule) of the one-rank build, and res8[event type][rank] = RankStats."""
+    from helpers import RanksOfAJob, device_generated, shard_rows, to_params
+    from universal_recommender_amd import _lib, sharded, synth
     from universal_recommender_amd import device as D
+    cfg = synth.config5(user_scale, item_scale=1.0)
+    dev_mats, mats = device_generated(cfg, sess.device)
+    assert max(int(np.diff(m.row_ptr).max()) for m in mats) > 500
     W = 8
     shards, cuts = shard_rows(dev_mats, W)
-    coll = sharded.DeviceLoopbackCollectives(W, gpu_session.device)
-    ctx8 = D.Context(gpu_session.device, gpu_session.lib, W, _lib.FLAG_EMULATE_RANKS, collectives=coll)
+    coll = sharded.DeviceLoopbackCollectives(W, sess.device)
+    ctx8 = D.Context(sess.device, sess.lib, W, _lib.FLAG_EMULATE_RANKS, collectives=coll)
     try:
         ctx8.build(shards, to_params([P()] * 5), 20260925, cfg.n_users, cuts[:-1])
         res8 = ctx8.results()
         assert coll.error is None
-        _, res = compare_with_oracle_large(gpu_session, mats, [P()] * 5, 20260925, dev_mats=dev_mats, via_context=True,
+        _, res = compare_with_oracle_large(sess, mats, [P()] * 5, 20260925, dev_mats=dev_mats, via_context=True,
                                            also=[("8 emulated ranks", [RanksOfAJob(row) for row in res8])])
-        work = np.array([sum(int(res8[d][g].stats[0]) for d in range(5)) for g in range(W)], np.float64)
-        assert work.max() / work.mean() < 1.05, work           # work-balanced item ranges under the skew (SURVEY 8e)
+        per_rank = [[RankStats(x) for x in row] for row in res8]
     finally:
         res8 = None
         ctx8.close()
+    return res, per_rank
+
+
+def ranks_work_imbalance(res8):
+    """max / mean over the ranks of a build's pairs (all event types): what the work-balanced item ranges bound."""
+    work = np.array([sum(int(row[g].stats[0]) for row in res8) for g in range(len(res8[0]))], np.float64)
+    return work.max() / work.mean(), work
+
+
+def test_full_config5_every_row(gpu_session):
+    """BASELINE config 5 at FULL size (config 4's shape with the hot head -- top 0.1 % of the items draw 40 % of the
+    interactions -- and 1 % heavy users x50), engine.json defaults as bench.py --workload config5 runs it: the heavy
+    users' rows are dropped by maxItemsPerUser (Int / Int row rate), the hot items' rows are too heavy for any single-pass
+    LDS accumulator (the multi-pass class).  One rank and eight emulated ranks (config5_one_rank_and_eight_ranks)."""
+    res, res8 = config5_one_rank_and_eight_ranks(gpu_session, 1.0)
+    ratio, work = ranks_work_imbalance(res8)
+    assert ratio < 1.05, work                                   # work-balanced item ranges under the skew (SURVEY 8e)
     rows_by_bin = np.sum([st[1:8] for st, _ in res], axis=0)
     assert rows_by_bin[6] > 1000, rows_by_bin                   # the heavy-row class carries real work here
 

@@ -61,6 +61,64 @@ def test_micro_class_every_ranking_form(sim_session):
         assert stats[1][0][1] > 100, stats[1][0][1:8]   # rows of the micro class in A'B
 
 
+def micro_sub_range_rows(a, b, item_lo=0, item_hi=None):
+    """Plain numpy reference of the micro class's three size ranges for the item rows [item_lo, item_hi) of A'B, from the DOWN-SAMPLED
+    matrices: w[i] = sum over the users u of column i of A' of len(B' row u) (the row's pairs), cA[i] = users of column i; the class holds
+    the rows with 0 < w <= 64 and 0 < cA <= 64 (choose_bin, csrc/cco_rows.hip; a cA of <= 64 fits the packed count of every catalogue width).
+    Returns the rows with (w <= 16 and cA <= 16, the rest with w <= 32 and cA <= 32, the rest): with the class split, the first two are the
+    shared-wave sub-lists -- stats[STATS_LEN - 1] is their sum; unsplit, all three are the one list and the word is 0."""
+    item_hi = a.n_cols if item_hi is None else item_hi
+    users = np.repeat(np.arange(a.n_rows, dtype=np.int64), np.diff(a.row_ptr))
+    cols = a.col_idx[:a.nnz]
+    w = np.bincount(cols, weights=np.diff(b.row_ptr)[users].astype(np.float64), minlength=a.n_cols).astype(np.int64)   # (exact: far below 2^53)
+    ca = np.bincount(cols, minlength=a.n_cols)
+    w, ca = w[item_lo:item_hi], ca[item_lo:item_hi]
+    micro = (w > 0) & (ca > 0) & (w <= 64) & (ca <= 64)
+    s16 = micro & (w <= 16) & (ca <= 16)
+    s32 = micro & ~s16 & (w <= 32) & (ca <= 32)
+    return int(s16.sum()), int(s32.sum()), int((micro & ~s16 & ~s32).sum())
+
+
+def micro_sub_range_rows_of_build(mats, params, seed, mode=0, item_lo=0, item_hi=None):
+    """micro_sub_range_rows of every event type of a build, the matrices down-sampled by the oracle."""
+    ds = [O.downsample(m, O.column_counts(m), seed, p.max_elements_per_row, mode) for m, p in zip(mats, params)]
+    return [micro_sub_range_rows(ds[0], b, item_lo, item_hi) for b in ds]
+
+
+def test_stats_word_31_counts_the_shared_wave_rows(sim_session):
+    """stats[STATS_LEN - 1] = rows binned into the two shared-wave sub-lists of the first accumulator class (the word by which the GPU tests tell which
+    form of that class a build ran): exact against micro_sub_range_rows for every event type, on the builds of
+    test_micro_class_every_ranking_form and on a rand_csr build, whole and as an item range.  Both workloads hold rows in all three size
+    ranges, so a word that counted the wrong sub-lists (the <= 64 remainder too, only the first) differs.  The pytest process sets the
+    threshold of the split to 0 (conftest.py); under another value the word must be 0 for builds below it."""
+    import os
+    min_rows = int(os.environ.get("URCCO_MICRO_SPLIT_ROWS") or 1000000)
+
+    def check(mats, params, seed, item_lo=0, item_hi=None):
+        _, _, stats = compare_with_oracle(sim_session, mats, params, seed, 0, item_lo, item_hi)
+        ref = micro_sub_range_rows_of_build(mats, params, seed, 0, item_lo, item_hi)
+        n = (mats[0].n_cols if item_hi is None else item_hi) - item_lo
+        for (st, _, _), (r16, r32, r64) in zip(stats, ref):
+            assert int(st[1]) == r16 + r32 + r64, (st[1:8], r16, r32, r64)          # the reference's class membership is the library's
+            assert int(st[_lib.STATS_LEN - 1]) == (r16 + r32 if n >= min_rows else 0), (int(st[_lib.STATS_LEN - 1]), r16, r32, r64)
+        return np.array(ref)
+
+    rng = np.random.default_rng(77)
+    tot = np.zeros((2, 3), np.int64)
+    for b_cols, lo, hi, upi, k in [(5000, 1, 16, 4, 50), (5000, 8, 32, 2, 50), (5000, 20, 60, 1, 50), (5000, 1, 30, 3, 7), (40, 1, 12, 5, 50),
+                                   (40, 1, 12, 5, 3), (200, 0, 3, 20, 50), (300, 30, 64, 1, 64)]:
+        a, b = _micro_case(rng, 400, upi, b_cols, lo, hi)
+        tot += check([a, b], [P(100000, k), P(100000, k)], 13)
+    assert tot[1].min() > 100 and tot[0][:2].min() > 50, tot     # A'B: all three ranges; A'A (one item per user: w = cA <= 20): the two shared-wave ones
+    rng = np.random.default_rng(78)
+    mats = [rand_csr(rng, 3000, 2000, 4, zipf_s=0.8), rand_csr(rng, 3000, 500, 5), rand_csr(rng, 3000, 30, 2, empty_frac=0.3)]
+    params = [P(100000, 20), P(100000, 20), P(40, 50)]           # (the third event type IS down-sampled: the reference follows the oracle's B')
+    ref = check(mats, params, 5)
+    assert ref[:2].min() > 50 and ref[2].min() > 0, ref
+    part = check(mats, params, 5, 301, 1777)
+    assert part[:2].min() > 25 and np.all(part.sum(1) < ref.sum(1)), (part, ref)
+
+
 def test_global_accumulator_rows(sim_session):
     """Rows that cannot be bounded below an LDS table (w > 10240 with > 16384 columns) take the dense global path."""
     rng = np.random.default_rng(3)
@@ -486,7 +544,7 @@ def test_row_scan_tile_edges(sim_session, mode):
 def test_all_equal_llr_ties_cut_by_column(sim_session):
     """Every candidate of a row has the same LLR and there are more of them than k: the radix select finds no
     differing key byte and the cut is decided by the column order alone (llr desc, col asc).  A second block of
-    items shares only the exponent bytes.  Exact ids."""
+    items shares only the exponent bytes.  A third matrix puts such rows into the micro class (one wave, ranking by counting).  Exact ids."""
     rng = np.random.default_rng(17)
     n_users, n_items = 900, 300
     rows = []
@@ -504,6 +562,12 @@ def test_all_equal_llr_ties_cut_by_column(sim_session):
     a = O.Csr(n_users, n_items, rp, ci)
     for k in (5, 50, 64, 150):
         _, _, stats = compare_with_oracle(sim_session, [a, a], [P(100000, k), P(100000, k)], 3, exact_ids=True)
+    # the same in the micro class: 3 users hold the same 20 items and nothing else (cA = 3, w = 60 pairs): every row has 19 candidates of one LLR
+    m = _tied_block(40, 64, 3, np.arange(7, 27))
+    for k in (5, 19, 50):
+        out, _, stats = compare_with_oracle(sim_session, [m, m], [P(100000, k), P(100000, k)], 3, exact_ids=True)
+        assert int(stats[0][0][1]) == 20 and int(stats[1][0][1]) == 20, stats[0][0][1:8]
+        assert [int(np.diff(o.to_host()[0]).max()) for o in out] == [min(k, 19), min(k, 20)]
 
 
 def _tied_block(n_users, n_items, holders, block, extra_rows=()):

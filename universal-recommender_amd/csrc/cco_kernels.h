@@ -21,7 +21,8 @@ constexpr int XLX_TABLE_HOST = 4096;     // entries of the small-integer xLogX t
 constexpr int BIN_COLS_HOST = 3 * NBINS + 3;  // int64 per binning tile (rows per internal bin -- the micro class has three sub-lists --, pairs and users per bin, total)
 constexpr int BIN_OFF_LEN = NBINS + 3;        // bin_off: [0 .. NBINS] list offsets of the classes, then the starts of the micro class's second and third sub-list
 constexpr int CAND_SLOTS = 64;           // words the row kernels spread their candidate counts over (see CcoArgs::cand)
-constexpr int STATS_LEN = 32;            // [0] pairs, then NBINS each of rows / pairs / users / out entries per bin, [1 + 4 NBINS] table overflows
+constexpr int STATS_LEN = 32;            // [0] pairs, then NBINS each of rows / pairs / users / out entries per bin, [1 + 4 NBINS] table overflows,
+                                         // [STATS_LEN - 1] rows binned into the micro class's two shared-wave sub-lists (0: the class ran as one list)
 
 // Bits of urcco_session_set_debug / urcco_context_set_debug (include/urcco.h documents them; bench.py and the tests pass the values).
 // SpGEMM row phases switched off (profiling only, results meaningless): the DBG instantiations of the row kernels.

@@ -182,6 +182,7 @@ __global__ __launch_bounds__(BS_THREADS) void bin_scan_kernel(int64_t* __restric
         stats[1 + 2 * NBINS + k] = s_tot[IBINS + NBINS + k];      // users (sum of cA over the bin's rows)
       }
       stats[0] = s_tot[IBINS + 2 * NBINS];
+      stats[STATS_LEN - 1] = s_tot[0] + s_tot[1];                 // rows of the two shared-wave sub-lists: 0 = the micro class ran as one list
     }
   }
 }

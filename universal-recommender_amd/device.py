@@ -45,7 +45,8 @@ class DevIndicators:
     row_ptr: torch.Tensor   # int64 [n + 1]
     col_idx: torch.Tensor   # int32 [n * k] (first row_ptr[-1] live)
     llr: torch.Tensor       # float64 [n * k]
-    stats: torch.Tensor     # int64 [STATS_LEN]: pairs, then rows / pairs / users / emitted entries per accumulator bin
+    stats: torch.Tensor     # int64 [STATS_LEN]: pairs, then rows / pairs / users / emitted entries per accumulator bin; [STATS_LEN - 1]: rows of the
+                            # micro class binned into its two shared-wave sub-lists (0: the build kept the class as one list)
     sampled_row_ptr: Optional[torch.Tensor] = None  # row_ptr of the down-sampled B this GPU multiplied with (several ranks: only the rows its
                                                     # item range touches are filled, include/urcco.h urcco_dev_result)
     sampled_col_idx: Optional[torch.Tensor] = None  # col_idx of the same (first sampled_row_ptr[-1] entries live)
