@@ -439,6 +439,41 @@ int urcco_dev_compact_indicators(urcco_session* s, int32_t n_rows, int32_t k, co
 int urcco_dev_pop_counts(urcco_session* s, int64_t n_events, const int32_t* item_ids, const int64_t* times_ms, int32_t n_items,
                          int32_t n_intervals, const int64_t* bounds_host, int32_t* counts);
 
+/* Batch recommendations from a built model, where the indicator matrices already sit in HBM (the query half of the reference: URAlgorithm.predict /
+ * buildQuery, URAlgorithm.scala:484-953, minus Elasticsearch; DESIGN.md decision D15).  For query row q and item i of the primary's item dictionary
+ *   m_c(q, i)   = | T_c(q) ^ I_c(i) |                        exact integer, per should-clause c
+ *   score(q, i) = ((0.0 + boost_0 m_0) + boost_1 m_1) + ...  f64, clauses in call order, no contraction
+ * -- the reference's bool query (:594-603) with Elasticsearch's per-term weight replaced by 1: an item has a positive score exactly when ES gives it one.
+ * An item is eligible when it is not in the query's exclusion row (must_not ids, :715) and item_mask[i] != 0 (the available / expire date filter, :888-953,
+ * evaluated by the host).  Row q of the result = the eligible items in the total order (score desc, backfill position asc), cut to num: out_count[q] entries
+ * at out_idx / out_score[q * num ..] (the rest of a row is not written).  The backfill position of an item is its place in fill_order, a permutation of the
+ * items, strongest rank first (`sort: [_score desc, popRank desc]`, :730-738) -- without fill_order the item index.  Items nothing hit take part with score 0
+ * (the match_all clause of :668-681) unless URCCO_REC_NO_BACKFILL is set.  Ids and scores are reproducible bit for bit.
+ * Enqueues on the session's stream, does not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: num outside 1..URCCO_REC_MAX_NUM, n_clauses
+ * outside 0..URCCO_REC_MAX_CLAUSES (0 = pure backfill), a boost that is not positive and finite, a NULL half of a pointer pair. */
+#define URCCO_REC_MAX_CLAUSES 16
+#define URCCO_REC_MAX_NUM 256
+#define URCCO_REC_NO_BACKFILL 1
+#define URCCO_REC_STATS_LEN 8   /* [0] queries served by the LDS class, [1] by the global-accumulator class,
+                                   [2] candidate-table overflows (invariant: 0), [3] sum of candidates, rest 0 */
+typedef struct urcco_rec_clause {
+  int32_t n_cols;               /* columns of I_c = items of the clause's event type */
+  int32_t reserved;
+  double boost;                 /* > 0, finite */
+  const int64_t* ind_col_ptr;   /* device: CSC of I_c (n_items x n_cols), n_cols + 1 -- what urcco_dev_transpose makes of an indicator CSR */
+  const int32_t* ind_row_idx;   /* device: order inside a column unspecified */
+  const int64_t* q_row_ptr;     /* device: CSR of T_c (n_queries x n_cols), sorted unique columns */
+  const int32_t* q_col_idx;
+} urcco_rec_clause;
+
+int urcco_dev_recommend(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses,
+                        const int64_t* excl_row_ptr, const int32_t* excl_col_idx,  /* nullable pair: CSR n_queries x n_items */
+                        const uint8_t* item_mask,    /* nullable, [n_items] */
+                        const int32_t* fill_order,   /* nullable, [n_items], a permutation (caller's duty) */
+                        int32_t num, int32_t flags,
+                        int32_t* out_count, int32_t* out_idx, double* out_score,   /* strided by num, like urcco_dev_cco_rows */
+                        int64_t* stats_dev /* nullable, [URCCO_REC_STATS_LEN] */);
+
 /* Test hooks (device level): LLR of SimilarityAnalysis.logLikelihoodRatio evaluated by the device code for
  * n argument tuples; u01 of the down-sampling RNG.  All pointers device. */
 int urcco_dev_llr(urcco_session* s, int64_t n, const int64_t* with_a, const int64_t* with_b, const int64_t* with_ab,

@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Times urcco_dev_recommend (HIP events, warm, several repetitions) against the same result computed with PyTorch-ROCm plumbing on the same
+GPU: a chunked torch.sparse product per clause into a dense (queries x items) chunk, exclusions struck out, torch.topk.
+
+Shapes: a model of 200K items and 5 event types with k = 50 (BASELINE config 4's event mix at a tenth of its item spaces, built on the device
+by this library), 100K user queries whose histories are the users' own rows of the event matrices (lengths as synth.py draws them), the
+user's primary-event items as the blacklist, popularity as the backfill order, num = 20.
+usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N]"""
+import argparse
+import os
+import sys
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+import torch  # noqa: E402
+
+from universal_recommender_amd import _lib, synth  # noqa: E402
+from universal_recommender_amd.device import DatasetParams, DevCsr, DeviceSession, cross_occurrence_device  # noqa: E402
+from universal_recommender_amd.recommend import DeviceModel  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--users", type=int, default=1_000_000)
+ap.add_argument("--queries", type=int, default=100_000)
+ap.add_argument("--chunk", type=int, default=2048)
+ap.add_argument("--reps", type=int, default=5)
+ap.add_argument("--num", type=int, default=20)
+args = ap.parse_args()
+
+assert torch.cuda.is_available(), "needs the GPU: there is no CPU path to time"
+dev = torch.device("cuda", 0)
+cfg = synth.config4(args.users / 10_000_000, item_scale=0.1)
+mats = [DevCsr(cfg.n_users, nc, rp, ci, int(rp[-1].item())) for (_, nc, rp, ci) in synth.generate_device(cfg, dev)]
+sess = DeviceSession(dev, _lib.load(os.environ.get("URCCO_LIB", _lib.DEFAULT_PATH)))
+K = 50
+inds = cross_occurrence_device(sess, mats, [DatasetParams(500, K, None) for _ in mats], 1)
+sess.synchronize()
+names = [e.name for e in cfg.events]
+model = DeviceModel.from_indicators(sess, list(zip(names, inds)))
+n_items, nq, num = model.n_items, min(args.queries, cfg.n_users), args.num
+pop = torch.bincount(mats[0].col_idx[: mats[0].nnz_bound].to(torch.int64), minlength=n_items)
+fill = torch.sort(-pop, stable=True).indices.to(torch.int32)
+boosts = [1.0, 1.05, 2.0, 0.5, 20.0][: len(mats)]
+clauses, lens = [], []
+for c, m, b in zip(model.correlators, mats, boosts):
+    qrp = m.row_ptr[: nq + 1].contiguous()
+    clauses.append((c.n_cols, b, c.col_ptr, c.row_idx, qrp, m.col_idx))
+    lens.append(float(qrp[-1].item()) / nq)
+excl = (mats[0].row_ptr[: nq + 1].contiguous(), mats[0].col_idx)
+print(f"model: {n_items} items, {len(mats)} event types {[c.n_cols for c in model.correlators]}, k = {K}, indicator entries {[int(c.row_ptr[-1].item()) for c in model.correlators]}")
+print(f"queries: {nq} users, mean history length per event {[round(x, 1) for x in lens]}, num = {num}")
+
+
+def timed(fn, reps, warm=2):
+    for _ in range(warm):
+        fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(reps):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        out = fn()
+        e1.record()
+        torch.cuda.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return out, ms
+
+
+(count, idx, score, stats), ms_hip = timed(lambda: sess.recommend(nq, n_items, clauses, num, excl, None, fill, 0), args.reps)
+st = stats.cpu().tolist()
+print(f"urcco_dev_recommend: {min(ms_hip):.2f} ms best, {sorted(ms_hip)[len(ms_hip) // 2]:.2f} ms median of {args.reps} ({[round(x, 2) for x in ms_hip]})")
+print(f"  class split: {st[0]} queries in the LDS class, {st[1]} in the global class; table overflows {st[2]}; candidates {st[3]} ({st[3] / nq:.0f} per query)")
+
+# ---- the same with torch: per chunk of queries, sum_c boost_c * T_c[chunk] @ I_c' (sparse x sparse -> dense), key = score with the backfill position as tie break ----
+pos = torch.empty(n_items, dtype=torch.int64, device=dev)
+pos[fill.to(torch.int64)] = torch.arange(n_items, device=dev)
+tie = pos.to(torch.float64) * 1e-9   # scores are sums of boost * integer: gaps of >= 0.05 against at most 2e-4 of tie break
+ind_t = []
+for c in model.correlators:
+    nnz = int(c.row_ptr[-1].item())
+    i_csr = torch.sparse_csr_tensor(c.row_ptr, c.col_idx[:nnz].to(torch.int64), torch.ones(nnz, dtype=torch.float64, device=dev), size=(n_items, c.n_cols))
+    ind_t.append(i_csr.to_sparse_coo().t().coalesce())     # (n_cols x n_items)
+mode = {"name": "sparse x sparse"}
+
+
+def torch_path():
+    out_idx = torch.empty((nq, num), dtype=torch.int64, device=dev)
+    out_score = torch.empty((nq, num), dtype=torch.float64, device=dev)
+    for lo in range(0, nq, args.chunk):
+        hi = min(lo + args.chunk, nq)
+        dense = torch.zeros((hi - lo, n_items), dtype=torch.float64, device=dev)
+        for (n_cols, b, _, _, qrp, qci), it in zip(clauses, ind_t):
+            s, e = int(qrp[lo].item()), int(qrp[hi].item())
+            rows = torch.repeat_interleave(torch.arange(hi - lo, device=dev), (qrp[lo + 1: hi + 1] - qrp[lo: hi]))
+            t = torch.sparse_coo_tensor(torch.stack([rows, qci[s:e].to(torch.int64)]), torch.ones(e - s, dtype=torch.float64, device=dev), size=(hi - lo, n_cols)).coalesce()
+            if mode["name"] == "sparse x sparse":
+                dense += b * torch.sparse.mm(t, it).to_dense()
+            else:
+                dense += b * torch.sparse.mm(it.t(), t.to_dense().t()).t()
+        key = dense - tie
+        s, e = int(excl[0][lo].item()), int(excl[0][hi].item())
+        rows = torch.repeat_interleave(torch.arange(hi - lo, device=dev), (excl[0][lo + 1: hi + 1] - excl[0][lo: hi]))
+        key[rows, excl[1][s:e].to(torch.int64)] = float("-inf")
+        top = torch.topk(key, num, dim=1)
+        out_idx[lo:hi] = top.indices
+        out_score[lo:hi] = torch.gather(dense, 1, top.indices)
+    return out_idx, out_score
+
+
+try:
+    (t_idx, t_score), ms_torch = timed(torch_path, max(args.reps // 2, 1), warm=1)
+except RuntimeError as err:
+    print(f"  (torch: sparse x sparse product not available here: {str(err)[:120]}; using sparse x dense)")
+    mode["name"] = "sparse x dense"
+    (t_idx, t_score), ms_torch = timed(torch_path, max(args.reps // 2, 1), warm=1)
+print(f"torch ({mode['name']}, chunks of {args.chunk} queries, topk): {min(ms_torch):.2f} ms best ({[round(x, 2) for x in ms_torch]})")
+full = count.to(torch.int64) == num
+same_ids = (idx.to(torch.int64) == t_idx).all(1) | ~full
+same_scores = (score == t_score).all(1) | ~full
+print(f"agreement on the {int(full.sum())} full rows: ids {int(same_ids.sum())} / {nq}, scores {int(same_scores.sum())} / {nq}")
+print(f"ratio torch / hand-written: {min(ms_torch) / min(ms_hip):.2f}x")
+sess.close()

@@ -26,6 +26,11 @@ RNG_MIX32 = 0x100
 N_STAGES = 17
 N_BINS = 7
 STATS_LEN = 32
+REC_MAX_CLAUSES = 16   # urcco_dev_recommend (include/urcco.h URCCO_REC_*)
+REC_MAX_NUM = 256
+REC_NO_BACKFILL = 1
+REC_STATS_LEN = 8
+REC_LDS_LIMIT = 3072   # work bound w(q) up to which a query runs in the LDS class (csrc/cco_kernels.h)
 EXCH_SIZES = 4   # int64 words of a shard's record (include/urcco.h URCCO_EXCH_SIZES)
 STAGE_NAMES = ["column_counts", "downsample_flags", "downsample_scan", "downsample_compact", "transpose", "row_work", "binning",
                "entropy", "cco_rows_micro", "cco_rows_wave", "cco_rows_block_small", "cco_rows_block", "cco_rows_cu_half", "cco_rows_cu", "cco_rows_global", "compact_indicators", "exchange"]
@@ -97,6 +102,11 @@ class DatasetStats(C.Structure):
                 ("rows_by_bin", C.c_int64 * 7), ("ms_total", C.c_double)]
 
 
+class RecClause(C.Structure):
+    _fields_ = [("n_cols", C.c_int32), ("reserved", C.c_int32), ("boost", C.c_double), ("ind_col_ptr", C.c_void_p), ("ind_row_idx", C.c_void_p),
+                ("q_row_ptr", C.c_void_p), ("q_col_idx", C.c_void_p)]
+
+
 # every symbol include/urcco.h declares: (restype, argtypes)
 _p = C.c_void_p
 SYMBOLS = {
@@ -152,6 +162,7 @@ SYMBOLS = {
                                             C.c_int32, C.c_int32, C.c_double, _p, _p, _p, _p, _p, _p]),
     "urcco_dev_compact_indicators": (C.c_int, [_p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p]),
     "urcco_dev_pop_counts": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _p]),
+    "urcco_dev_recommend": (C.c_int, [_p, C.c_int64, C.c_int32, C.POINTER(RecClause), C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p]),
     "urcco_dev_llr": (C.c_int, [_p, C.c_int64, _p, _p, _p, _p, _p]),
     "urcco_dev_u01": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p]),
     "urcco_dev_u01_rng": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, C.c_int32, _p]),

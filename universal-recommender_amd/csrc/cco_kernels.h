@@ -215,6 +215,29 @@ hipError_t launch_compact_indicators(hipStream_t st, int32_t n_rows, int32_t k, 
 hipError_t launch_partition(hipStream_t st, int32_t n_items, const int64_t* work_prefix, int32_t n_parts, int32_t* bounds);
 hipError_t launch_scan_i64(hipStream_t st, const int64_t* in, int64_t n, int64_t* out, int64_t* tile_sums);
 
+// ---- batch recommendations from a built model (cco_recommend.h, compiled into cco_misc.hip) ----------------------
+constexpr int REC_MAX_CLAUSES = 16;   // == URCCO_REC_MAX_CLAUSES ... of include/urcco.h (checked in urcco_internal.h)
+constexpr int REC_MAX_NUM = 256;
+constexpr int REC_NO_BACKFILL = 1;
+constexpr int REC_STATS_LEN = 8;
+constexpr int REC_LDS_LIMIT = 3072;   // a query whose work bound w(q) (candidate touches + exclusions) is larger runs in the global-accumulator class
+struct RecClause {
+  const int64_t* ind_col_ptr;  // CSC of the indicator matrix I_c (n_items x n_cols)
+  const int32_t* ind_row_idx;
+  const int64_t* q_row_ptr;    // CSR of the query terms T_c (n_queries x n_cols)
+  const int32_t* q_col_idx;
+  double boost;
+  int32_t n_cols;
+  int32_t reserved;
+};
+struct RecArgs;  // cco_recommend.h
+int32_t recommend_global_blocks(int64_t n_queries, int32_t n_items, int n_cu);
+// ctr[4], list[n_queries], pos[n_items] (only with fill_order), g_state / g_m / g_list [g_blocks * n_items] words, g_score [g_blocks * n_items] doubles: scratch
+hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t n_items, const RecClause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
+                            const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
+                            int32_t* out_idx, double* out_score, int64_t* stats_dev, unsigned long long* ctr, int32_t* list, int32_t* pos, int32_t g_blocks,
+                            unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit = REC_LDS_LIMIT);
+
 hipError_t launch_llr_test(hipStream_t st, int64_t n, const int64_t* a, const int64_t* b, const int64_t* ab, const int64_t* nu, double* out);
 hipError_t launch_u01_test(hipStream_t st, int64_t n, uint32_t seed, const int32_t* row, const int32_t* col, double* out, int rng32 = 0);
 

@@ -5,9 +5,11 @@
 #include <atomic>
 #include <cstdio>
 #include <cstdlib>
+#include <cstring>
 
 #include "cco_common.h"
 #include "cco_device.h"
+#include "cco_recommend.h"
 
 
 namespace urcco {

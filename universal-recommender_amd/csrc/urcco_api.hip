@@ -683,6 +683,46 @@ int urcco_dev_pop_counts(urcco_session* s, int64_t n_events, const int32_t* item
   return URCCO_OK;
 }
 
+int urcco_dev_recommend(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
+                        const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
+                        int32_t* out_idx, double* out_score, int64_t* stats_dev) {
+  if (!s || n_queries < 0 || n_queries > 0x7fffffffll || n_items < 0 || n_items == 0x7fffffff) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: bad argument");
+  if (num < 1 || num > URCCO_REC_MAX_NUM) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: num must lie in 1..%d, got %d", URCCO_REC_MAX_NUM, num);
+  if (n_clauses < 0 || n_clauses > URCCO_REC_MAX_CLAUSES || (n_clauses > 0 && !clauses))
+    return fail(URCCO_BAD_ARG, "urcco_dev_recommend: between 0 and %d clauses, got %d", URCCO_REC_MAX_CLAUSES, n_clauses);
+  if ((excl_row_ptr == nullptr) != (excl_col_idx == nullptr)) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: the exclusion CSR needs both of its arrays");
+  if (flags & ~URCCO_REC_NO_BACKFILL) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: unknown flags %d", flags);
+  if (n_queries > 0 && (!out_count || !out_idx || !out_score)) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: output arrays missing");
+  urcco::RecClause cl[URCCO_REC_MAX_CLAUSES];
+  for (int c = 0; c < n_clauses; ++c) {
+    const urcco_rec_clause& in = clauses[c];
+    if (!(in.boost > 0.0) || in.boost > 1.7976931348623157e308) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: clause %d: the boost must be positive and finite", c);
+    if (in.n_cols < 0 || (in.ind_col_ptr == nullptr) != (in.ind_row_idx == nullptr) || (in.q_row_ptr == nullptr) != (in.q_col_idx == nullptr) || !in.ind_col_ptr || !in.q_row_ptr)
+      return fail(URCCO_BAD_ARG, "urcco_dev_recommend: clause %d: bad matrix", c);
+    cl[c] = urcco::RecClause{in.ind_col_ptr, in.ind_row_idx, in.q_row_ptr, in.q_col_idx, in.boost, in.n_cols, 0};
+  }
+  // URCCO_REC_LDS_LIMIT lowers the work bound up to which a query runs in the LDS class (read per call): small test shapes reach the global class with it
+  int32_t lds_limit = urcco::REC_LDS_LIMIT;
+  if (const char* e = getenv("URCCO_REC_LDS_LIMIT")) {
+    const long v = atol(e);
+    if (v >= 0 && v < lds_limit) lds_limit = (int32_t)v;
+  }
+  const int32_t g_blocks = urcco::recommend_global_blocks(n_queries, n_items, s->n_cu);
+  const size_t slice = (size_t)g_blocks * (size_t)(n_items > 0 ? n_items : 1);
+  URC(s->reserve(urcco_session::need(4, 8) + urcco_session::need((size_t)n_queries, 4) + urcco_session::need((size_t)n_items, 4) + 3 * urcco_session::need(slice, 4) +
+                 urcco_session::need(slice, 8)));
+  unsigned long long* ctr = s->take<unsigned long long>(4);
+  int32_t* list = s->take<int32_t>((size_t)n_queries);
+  int32_t* pos = s->take<int32_t>((size_t)n_items);
+  unsigned* g_state = s->take<unsigned>(slice);
+  unsigned* g_m = s->take<unsigned>(slice);
+  int32_t* g_list = s->take<int32_t>(slice);
+  double* g_score = s->take<double>(slice);
+  HIPC(urcco::launch_recommend(s->stream, s->n_cu, n_queries, n_items, cl, n_clauses, excl_row_ptr, excl_col_idx, item_mask, fill_order, num, flags, out_count, out_idx,
+                               out_score, stats_dev, ctr, list, pos, g_blocks, g_state, g_m, g_list, g_score, lds_limit));
+  return URCCO_OK;
+}
+
 int urcco_dev_llr(urcco_session* s, int64_t n, const int64_t* with_a, const int64_t* with_b, const int64_t* with_ab, const int64_t* n_users,
                   double* out) {
   if (!s || n < 0) return fail(URCCO_BAD_ARG, "urcco_dev_llr: bad argument");

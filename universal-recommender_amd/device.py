@@ -208,6 +208,27 @@ class DeviceSession:
                                                          _ptr(c_llr)))
         return DevIndicators(item_lo, item_hi, b.n_cols, k, c_rp, c_idx, c_llr, stats, b.row_ptr, b.col_idx)
 
+    def recommend(self, n_queries: int, n_items: int, clauses, num: int, excl=None, item_mask: Optional[torch.Tensor] = None,
+                  fill_order: Optional[torch.Tensor] = None, flags: int = 0, stats: bool = True):
+        """urcco_dev_recommend: the top `num` of sum_c boost_c |T_c(q) ^ I_c(i)| per query row over the eligible items, in the order (score
+        desc, backfill position asc).  clauses: (n_cols, boost, ind_col_ptr, ind_row_idx, q_row_ptr, q_col_idx) per should-clause, device
+        tensors (the CSC of the indicator matrix, the CSR of the query terms); excl: (row_ptr, col_idx) of the exclusion CSR or None.
+        Returns (count int32 [n_queries], idx int32 [n_queries, num], score float64 [n_queries, num], stats int64 [REC_STATS_LEN] or None);
+        only the first count[q] entries of a row are written.  Enqueues, does not synchronise."""
+        arr = (_lib.RecClause * max(len(clauses), 1))()
+        for c, (n_cols, boost, cp, ri, qrp, qci) in enumerate(clauses):
+            arr[c].n_cols, arr[c].boost = int(n_cols), float(boost)
+            arr[c].ind_col_ptr, arr[c].ind_row_idx, arr[c].q_row_ptr, arr[c].q_col_idx = _ptr(cp), _ptr(ri), _ptr(qrp), _ptr(qci)
+        o_count = self.empty(max(n_queries, 1), torch.int32)
+        o_idx = self.empty(max(n_queries * num, 1), torch.int32)
+        o_score = self.empty(max(n_queries * num, 1), torch.float64)
+        st = self.empty(_lib.REC_STATS_LEN, torch.int64) if stats else None
+        self._check(self.lib.urcco_dev_recommend(self.handle, n_queries, n_items, arr, len(clauses), _ptr(excl[0]) if excl is not None else None,
+                                                _ptr(excl[1]) if excl is not None else None, _ptr(item_mask), _ptr(fill_order), num, flags,
+                                                _ptr(o_count), _ptr(o_idx), _ptr(o_score), _ptr(st)))
+        n = max(n_queries, 0)
+        return o_count[:n], o_idx[: n * max(num, 0)].view(n, -1) if n and num > 0 else o_idx[:0], o_score[: n * max(num, 0)].view(n, -1) if n and num > 0 else o_score[:0], st
+
     def llr(self, with_a, with_b, with_ab, n_users) -> torch.Tensor:
         out = self.empty(with_a.numel(), torch.float64)
         self._check(self.lib.urcco_dev_llr(self.handle, with_a.numel(), _ptr(with_a), _ptr(with_b), _ptr(with_ab), _ptr(n_users), _ptr(out)))

@@ -3,7 +3,8 @@
 
 calcAll builds what the reference hands to URModel.save: the per-event indicator matrices (the CCO build on the GPU) and --
 `calcPopular` -- the item properties joined with the PopModel ranks (getRanksRDD :537-560, device interval histogram behind
-pop_model.py).  Elasticsearch and the query side are out of scope."""
+pop_model.py).  Elasticsearch is out of scope; the query side is served in batch form by recommend.py
+(batch_predict / predict below), with this library's own score in place of Elasticsearch's."""
 from __future__ import annotations
 
 import time
@@ -127,6 +128,13 @@ class URAlgorithmParams:
     dateName: Optional[str] = None
     numGPUs: Optional[int] = None      # additive key: GPUs of the node the CCO build may use; absent = 1, 0 = every visible one
     ccoBackend: Optional[str] = None   # additive key: "hip" (default) or "mahout" (the host falls back to the reference path: not available here)
+    # query side (:88-106; read by batch_predict)
+    num: Optional[int] = None                      # default number of results (20)
+    maxQueryEvents: Optional[int] = None           # :90
+    userBias: Optional[float] = None               # :199-200
+    itemBias: Optional[float] = None
+    blacklistEvents: Optional[List[str]] = None    # :236: None = the primary event, [] = no blacklist
+    returnSelf: Optional[bool] = None              # :237
 
     @staticmethod
     def from_engine_json(engine: dict, name: str = "ur") -> "URAlgorithmParams":
@@ -146,7 +154,8 @@ class URAlgorithmParams:
             maxEventsPerEventType=p.get("maxEventsPerEventType"), maxCorrelatorsPerEventType=p.get("maxCorrelatorsPerEventType"),
             indicators=None if inds is None else [IndicatorParams(i["name"], i.get("maxItemsPerUser"), i.get("maxCorrelatorsPerItem"),
                                                                   i.get("minLLR")) for i in inds],
-            seed=p.get("seed"))
+            seed=p.get("seed"), num=p.get("num"), maxQueryEvents=p.get("maxQueryEvents"), userBias=p.get("userBias"), itemBias=p.get("itemBias"),
+            blacklistEvents=p.get("blacklistEvents"), returnSelf=p.get("returnSelf"))
 
 
 def _get_or_else(v, default):
@@ -254,6 +263,15 @@ class URAlgorithm:
             res = SimilarityAnalysis.crossOccurrenceDownsampled(datasets, seed, device=self.device, library=self.library, numGPUs=self.numGPUs)
         return list(zip([n for n, _ in data.actions], res))                                    # :349
 
+
+    def batch_predict(self, model, queries: Sequence[dict], history: Dict[str, Dict[str, List[str]]], item_mask=None) -> List[dict]:
+        """URAlgorithm.predict (:484-535) for a batch of queries against a recommend.DeviceModel: user history, similar-item and itemSet
+        queries, blacklists, backfill by rank -- see recommend.batch_predict for what is mirrored and what is left out."""
+        from .recommend import batch_predict
+        return batch_predict(self, model, queries, history, item_mask)
+
+    def predict(self, model, query: dict, history: Dict[str, Dict[str, List[str]]], item_mask=None) -> dict:
+        return self.batch_predict(model, [query], history, item_mask)[0]
 
     def train_events_on_device(self, trainingData, sess) -> List[Tuple[str, IndexedDataset]]:
         """Preparator.prepare + URAlgorithm.calcAll without leaving the GPU in between: the event streams are hashed on
