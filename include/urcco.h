@@ -455,7 +455,8 @@ int urcco_dev_pop_counts(urcco_session* s, int64_t n_events, const int32_t* item
 #define URCCO_REC_MAX_NUM 256
 #define URCCO_REC_NO_BACKFILL 1
 #define URCCO_REC_STATS_LEN 8   /* [0] queries served by the LDS class, [1] by the global-accumulator class,
-                                   [2] candidate-table overflows (invariant: 0), [3] sum of candidates, rest 0 */
+                                   [2] candidate-table overflows (invariant: 0), [3] sum of candidates,
+                                   [4] backfill steps (urcco_dev_recommend_rules with rules only, else 0), rest 0 */
 typedef struct urcco_rec_clause {
   int32_t n_cols;               /* columns of I_c = items of the clause's event type */
   int32_t reserved;
@@ -473,6 +474,37 @@ int urcco_dev_recommend(urcco_session* s, int64_t n_queries, int32_t n_items, co
                         int32_t num, int32_t flags,
                         int32_t* out_count, int32_t* out_idx, double* out_score,   /* strided by num, like urcco_dev_cco_rows */
                         int64_t* stats_dev /* nullable, [URCCO_REC_STATS_LEN] */);
+
+/* urcco_dev_recommend under business rules (the reference's must / must_not clauses: buildQueryMust / buildQueryMustNot / getFilteringDateRange,
+ * URAlgorithm.scala:684-727, :841-953; DESIGN.md decision D16).  score(q, i) is the one above.  An item is eligible when it is not in the exclusion row,
+ * item_mask[i] != 0 AND every rule of the call holds for (q, i); the rules are conjunctive:
+ *   URCCO_RULE_ANY    row i of M and row q of the query matrix share at least one column   (`terms` in must: fields with bias < 0, user history or
+ *                     similar items as a filter, :688-708, :854) -- an empty query row matches no item, as an empty `terms` query does
+ *   URCCO_RULE_NONE   they share no column                                                   (fields with bias == 0 in must_not, :717-726, :863-864)
+ *   URCCO_RULE_RANGE  q_lo[q] <= item_value[i] < q_hi[q]; an item without a value (INT64_MIN) fails   (`range` in must: dateRange, available / expire
+ *                     dates, :872-953; gt x is lo = x + 1, an open side is INT64_MIN / INT64_MAX)
+ * M is a CSR over the items (an item x value property matrix, or an indicator matrix as the build leaves it): order inside a row unspecified, duplicates
+ * allowed, a column outside 0..n_cols never matches; the query rows have sorted unique columns.  The rules are evaluated on the device once per distinct
+ * item a query touches and once per walked backfill position; the backfill is the ELIGIBLE zero-score items in fill_order, so a rule that few items pass
+ * makes the walk long: stats[4] = backfill steps taken (256 positions each), summed over the queries -- only counted by this entry point with n_rules > 0.
+ * n_rules == 0 is urcco_dev_recommend itself (results and statistics).  URCCO_BAD_ARG, in addition: n_rules outside 0..URCCO_REC_MAX_RULES, an unknown
+ * kind, a NULL array that the kind needs, n_cols < 0. */
+#define URCCO_REC_MAX_RULES 16
+#define URCCO_RULE_ANY 0
+#define URCCO_RULE_NONE 1
+#define URCCO_RULE_RANGE 2
+typedef struct urcco_rec_rule {
+  int32_t kind, n_cols;
+  const int64_t* m_row_ptr; const int32_t* m_col_idx;   /* ANY/NONE: device CSR n_items x n_cols, row order unspecified */
+  const int64_t* q_row_ptr; const int32_t* q_col_idx;   /* ANY/NONE: device CSR n_queries x n_cols, sorted unique */
+  const int64_t* item_value;                            /* RANGE: device [n_items], INT64_MIN = none */
+  const int64_t* q_lo; const int64_t* q_hi;             /* RANGE: device [n_queries], lo <= v < hi */
+} urcco_rec_rule;
+
+int urcco_dev_recommend_rules(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses,
+                              const int64_t* excl_row_ptr, const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order,
+                              int32_t num, int32_t flags, int32_t* out_count, int32_t* out_idx, double* out_score, int64_t* stats_dev,
+                              const urcco_rec_rule* rules, int32_t n_rules);
 
 /* Test hooks (device level): LLR of SimilarityAnalysis.logLikelihoodRatio evaluated by the device code for
  * n argument tuples; u01 of the down-sampling RNG.  All pointers device. */

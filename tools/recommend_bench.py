@@ -5,7 +5,10 @@ GPU: a chunked torch.sparse product per clause into a dense (queries x items) ch
 Shapes: a model of 200K items and 5 event types with k = 50 (BASELINE config 4's event mix at a tenth of its item spaces, built on the device
 by this library), 100K user queries whose histories are the users' own rows of the event matrices (lengths as synth.py draws them), the
 user's primary-event items as the blacklist, popularity as the backfill order, num = 20.
-usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N]"""
+--rules: the same problem once more through urcco_dev_recommend_rules under one category filter (an ANY rule on a value that about half of the
+catalogue holds) and one NONE rule (a value a ninth of it holds), its time printed next to the rule-free call's; the first measurement of that
+path belongs under profiles/ (DESIGN.md section 7a).
+usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--rules]"""
 import argparse
 import os
 import sys
@@ -24,6 +27,7 @@ ap.add_argument("--queries", type=int, default=100_000)
 ap.add_argument("--chunk", type=int, default=2048)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--num", type=int, default=20)
+ap.add_argument("--rules", action="store_true", help="also time the call under an ANY and a NONE rule")
 args = ap.parse_args()
 
 assert torch.cuda.is_available(), "needs the GPU: there is no CPU path to time"
@@ -69,6 +73,24 @@ def timed(fn, reps, warm=2):
 st = stats.cpu().tolist()
 print(f"urcco_dev_recommend: {min(ms_hip):.2f} ms best, {sorted(ms_hip)[len(ms_hip) // 2]:.2f} ms median of {args.reps} ({[round(x, 2) for x in ms_hip]})")
 print(f"  class split: {st[0]} queries in the LDS class, {st[1]} in the global class; table overflows {st[2]}; candidates {st[3]} ({st[3] / nq:.0f} per query)")
+
+if args.rules:
+    # item x value matrix of 10 values: value 0 on every second item (the filter), value 1 + i % 9 on every item (the NONE rule names value 1)
+    g = torch.Generator(device="cpu").manual_seed(1)
+    half = (torch.rand(n_items, generator=g) < 0.5).to(dev)
+    item = torch.arange(n_items, device=dev)
+    m_rp = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(1 + half.to(torch.int64), 0)])
+    m_ci = torch.empty(int(m_rp[-1].item()), dtype=torch.int32, device=dev)
+    m_ci[m_rp[:-1]] = (1 + item % 9).to(torch.int32)
+    m_ci[m_rp[1:][half] - 1] = 0
+    one = torch.arange(nq + 1, dtype=torch.int64, device=dev)   # every query row holds one value
+    rules = [(_lib.RULE_ANY, 10, m_rp, m_ci, one, torch.zeros(nq, dtype=torch.int32, device=dev)),
+             (_lib.RULE_NONE, 10, m_rp, m_ci, one, torch.ones(nq, dtype=torch.int32, device=dev))]
+    (r_count, _, _, r_stats), ms_rules = timed(lambda: sess.recommend(nq, n_items, clauses, num, excl, None, fill, 0, rules=rules), args.reps)
+    rs = r_stats.cpu().tolist()
+    print(f"urcco_dev_recommend_rules (ANY on a value {float(half.float().mean()):.0%} of the items hold, NONE on a value a ninth hold): {min(ms_rules):.2f} ms best, "
+          f"{sorted(ms_rules)[len(ms_rules) // 2]:.2f} ms median of {args.reps} ({[round(x, 2) for x in ms_rules]}) -- rule-free call above: {min(ms_hip):.2f} ms")
+    print(f"  candidates {rs[3]} ({rs[3] / nq:.0f} per query, {st[3] / nq:.0f} without rules); backfill steps {rs[4]} ({rs[4] / nq:.2f} per query); full rows {int((r_count == num).sum())} / {nq}")
 
 # ---- the same with torch: per chunk of queries, sum_c boost_c * T_c[chunk] @ I_c' (sparse x sparse -> dense), key = score with the backfill position as tie break ----
 pos = torch.empty(n_items, dtype=torch.int64, device=dev)

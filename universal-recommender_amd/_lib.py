@@ -30,6 +30,8 @@ REC_MAX_CLAUSES = 16   # urcco_dev_recommend (include/urcco.h URCCO_REC_*)
 REC_MAX_NUM = 256
 REC_NO_BACKFILL = 1
 REC_STATS_LEN = 8
+REC_MAX_RULES = 16     # urcco_dev_recommend_rules (URCCO_REC_MAX_RULES, URCCO_RULE_*)
+RULE_ANY, RULE_NONE, RULE_RANGE = 0, 1, 2
 REC_LDS_LIMIT = 3072   # work bound w(q) up to which a query runs in the LDS class (csrc/cco_kernels.h)
 EXCH_SIZES = 4   # int64 words of a shard's record (include/urcco.h URCCO_EXCH_SIZES)
 STAGE_NAMES = ["column_counts", "downsample_flags", "downsample_scan", "downsample_compact", "transpose", "row_work", "binning",
@@ -107,6 +109,11 @@ class RecClause(C.Structure):
                 ("q_row_ptr", C.c_void_p), ("q_col_idx", C.c_void_p)]
 
 
+class RecRule(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("n_cols", C.c_int32), ("m_row_ptr", C.c_void_p), ("m_col_idx", C.c_void_p), ("q_row_ptr", C.c_void_p),
+                ("q_col_idx", C.c_void_p), ("item_value", C.c_void_p), ("q_lo", C.c_void_p), ("q_hi", C.c_void_p)]
+
+
 # every symbol include/urcco.h declares: (restype, argtypes)
 _p = C.c_void_p
 SYMBOLS = {
@@ -163,6 +170,8 @@ SYMBOLS = {
     "urcco_dev_compact_indicators": (C.c_int, [_p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p, _p]),
     "urcco_dev_pop_counts": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int32, C.c_int32, C.POINTER(C.c_int64), _p]),
     "urcco_dev_recommend": (C.c_int, [_p, C.c_int64, C.c_int32, C.POINTER(RecClause), C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p]),
+    "urcco_dev_recommend_rules": (C.c_int, [_p, C.c_int64, C.c_int32, C.POINTER(RecClause), C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p,
+                                            C.POINTER(RecRule), C.c_int32]),
     "urcco_dev_llr": (C.c_int, [_p, C.c_int64, _p, _p, _p, _p, _p]),
     "urcco_dev_u01": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p]),
     "urcco_dev_u01_rng": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, C.c_int32, _p]),

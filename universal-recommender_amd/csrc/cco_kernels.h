@@ -230,13 +230,29 @@ struct RecClause {
   int32_t n_cols;
   int32_t reserved;
 };
+// ---- eligibility rules of urcco_dev_recommend_rules (decision D16): every rule of a call must hold for (query, item) ----
+constexpr int REC_MAX_RULES = 16;
+constexpr int REC_RULE_ANY = 0;     // row `item` of M and the query's row share a column
+constexpr int REC_RULE_NONE = 1;    // they share none
+constexpr int REC_RULE_RANGE = 2;   // q_lo[q] <= item_value[item] < q_hi[q]; INT64_MIN = the item has no value and fails
+struct RecRule {
+  const int64_t* m_row_ptr;    // ANY / NONE: CSR of M (n_items x n_cols), order inside a row unspecified, duplicates allowed
+  const int32_t* m_col_idx;
+  const int64_t* q_row_ptr;    // ANY / NONE: CSR of the query rows (n_queries x n_cols), sorted unique columns
+  const int32_t* q_col_idx;
+  const int64_t* item_value;   // RANGE: [n_items]
+  const int64_t* q_lo;         // RANGE: [n_queries]
+  const int64_t* q_hi;
+  int32_t kind, n_cols;
+};
 struct RecArgs;  // cco_recommend.h
 int32_t recommend_global_blocks(int64_t n_queries, int32_t n_items, int n_cu);
-// ctr[4], list[n_queries], pos[n_items] (only with fill_order), g_state / g_m / g_list [g_blocks * n_items] words, g_score [g_blocks * n_items] doubles: scratch
+// ctr[5], list[n_queries], pos[n_items] (only with fill_order), g_state / g_m / g_list [g_blocks * n_items] words, g_score [g_blocks * n_items] doubles: scratch
 hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t n_items, const RecClause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
                             const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
                             int32_t* out_idx, double* out_score, int64_t* stats_dev, unsigned long long* ctr, int32_t* list, int32_t* pos, int32_t g_blocks,
-                            unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit = REC_LDS_LIMIT);
+                            unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit = REC_LDS_LIMIT, const RecRule* rules = nullptr,
+                            int32_t n_rules = 0);
 
 hipError_t launch_llr_test(hipStream_t st, int64_t n, const int64_t* a, const int64_t* b, const int64_t* ab, const int64_t* nu, double* out);
 hipError_t launch_u01_test(hipStream_t st, int64_t n, uint32_t seed, const int32_t* row, const int32_t* col, double* out, int rng32 = 0);

@@ -6,8 +6,10 @@
 //   rec_inverse_kernel   pos[fill_order[p]] = p: the backfill position of every item
 //   rec_work_kernel      w(q) = sum_c sum_{h in T_c(q)} len(column h of I_c) + exclusions of q: the upper bound of the distinct items the query
 //                        touches; w <= REC_LIMIT goes to the LDS class (list filled from the front), everything else to the global class (from the back)
-//   rec_rows_kernel<0>   LDS class: a block per query, an open-addressing table keyed by the item in LDS
-//   rec_rows_kernel<1>   global class: the same walk on a dense per-block accumulator of n_items slots in arena scratch, cleared through its touched lists
+//   rec_rows_kernel<0, R>  LDS class: a block per query, an open-addressing table keyed by the item in LDS
+//   rec_rows_kernel<1, R>  global class: the same walk on a dense per-block accumulator of n_items slots in arena scratch, cleared through its touched lists
+//   rec_rules_ok           R = true (urcco_dev_recommend_rules, decision D16): the per-(query, item) eligibility rules, evaluated wherever item_mask is consulted --
+//                          when an absent item is claimed (a rejected item becomes a tombstone) and per walked backfill position; R = false is the rule-free call
 // Both classes: exclusions enter first as tombstones, masked-out items become tombstones when they are first hit; clause by clause the hits raise a 32-bit
 // match counter per slot (the claiming lane appends the slot to the candidate list), then `score += boost * m; m = 0` is folded over the list -- the f64 sum
 // has the order of the clauses whatever the order of the hits.  Selection: an 8-bit radix select over the 96-bit key (score bits, ~position) finds the
@@ -37,7 +39,7 @@ struct RecArgs {
   const int32_t* fill_order;
   const int32_t* pos;         // nullable: backfill position per item (NULL: the item index)
   int32_t* list;              // [n_queries]: LDS-class queries from the front, global-class queries from the back
-  unsigned long long* ctr;    // [4]: queries of the LDS class, of the global class, table overflows, candidates
+  unsigned long long* ctr;    // [5]: queries of the LDS class, of the global class, table overflows, candidates, backfill steps (only counted under rules)
   int32_t* out_count;
   int32_t* out_idx;
   double* out_score;
@@ -47,7 +49,10 @@ struct RecArgs {
   int32_t* g_list;            // candidates from the front, tombstones from the back
   double* g_score;            // by candidate ordinal
   int32_t g_blocks;
+  int32_t n_rules;
+  RecRule r[REC_MAX_RULES];   // read by the <., true> instantiations only
 };
+static_assert(sizeof(RecArgs) <= 4096, "kernel arguments: the clause and rule tables travel by value");
 
 __global__ __launch_bounds__(256) void rec_inverse_kernel(int32_t n_items, const int32_t* __restrict__ fill_order, int32_t* __restrict__ pos) {
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n_items; p += (int64_t)gridDim.x * 256) {
@@ -81,14 +86,50 @@ __global__ __launch_bounds__(REC_THREADS) void rec_work_kernel(RecArgs a) {
 
 __device__ __forceinline__ unsigned rec_hash(unsigned item) { return (item * 2654435761u) >> (32 - REC_CAP_LOG2); }
 
+// Do all rules of the call hold for (q, item)?  item < n_items.  ANY / NONE: the entries of row `item` of the rule's matrix (any order, duplicates allowed, a
+// column outside 0..n_cols never matches) are looked up one by one in the query's sorted row; RANGE: lo <= value < hi, an item without a value fails.  Pure: a
+// plain per-lane loop over short rows (a handful of property values, at most k indicator entries), no atomics; the first failing rule ends it.
+template <bool RULES>
+__device__ __forceinline__ bool rec_rules_ok(const RecArgs& a, int64_t q, int32_t item) {
+  if (!RULES) return true;
+  for (int j = 0; j < a.n_rules; ++j) {
+    const RecRule& r = a.r[j];
+    if (r.kind == REC_RULE_RANGE) {
+      const int64_t v = r.item_value[item];
+      if (v == INT64_MIN || v < r.q_lo[q] || v >= r.q_hi[q]) return false;
+      continue;
+    }
+    const int64_t qb = r.q_row_ptr[q], qe = r.q_row_ptr[q + 1];
+    bool any = false;
+    if (qe > qb) {
+      const int64_t e = r.m_row_ptr[item + 1];
+      for (int64_t t = r.m_row_ptr[item]; t < e && !any; ++t) {
+        const int32_t col = r.m_col_idx[t];
+        if ((unsigned)col >= (unsigned)r.n_cols) continue;
+        int64_t lo = qb, hi = qe;
+        while (lo < hi) {
+          const int64_t mid = (lo + hi) >> 1;
+          if (r.q_col_idx[mid] < col) lo = mid + 1;
+          else hi = mid;
+        }
+        any = lo < qe && r.q_col_idx[lo] == col;
+      }
+    }
+    if (any != (r.kind == REC_RULE_ANY)) return false;
+  }
+  return true;
+}
+
 // Slot of `item` in the LDS table, or -1 when the item may not be returned (tombstone) or the table is full (err).  An absent item is
-// claimed -- as a candidate (*fresh = true) when `live` and the mask admit it, else as a tombstone.
-__device__ __forceinline__ int rec_lds_touch(unsigned* keys, unsigned item, bool live, const uint8_t* __restrict__ mask, bool* fresh, unsigned long long* err) {
+// claimed -- as a candidate (*fresh = true) when `live`, the mask and the rules admit it, else as a tombstone.
+template <bool RULES>
+__device__ __forceinline__ int rec_lds_touch(unsigned* keys, unsigned item, bool live, const uint8_t* __restrict__ mask, bool* fresh, unsigned long long* err,
+                                             const RecArgs& a, int64_t q) {
   unsigned h = rec_hash(item);
   for (int probe = 0; probe < REC_CAP; ++probe) {
     unsigned k = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (k == REC_EMPTY) {
-      const bool ok = live && (!mask || mask[item] != 0);
+      const bool ok = live && (!mask || mask[item] != 0) && rec_rules_ok<RULES>(a, q, (int32_t)item);
       k = atomicCAS(&keys[h], REC_EMPTY, ok ? item : (item | REC_TOMB));
       if (k == REC_EMPTY) {
         *fresh = ok;
@@ -113,7 +154,7 @@ __device__ __forceinline__ bool rec_lds_has(const unsigned* keys, unsigned item)
   return false;
 }
 
-template <bool DENSE>
+template <bool DENSE, bool RULES>
 __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
   __shared__ unsigned s_keys[DENSE ? 1 : REC_CAP];
   __shared__ unsigned s_m[DENSE ? 1 : REC_CAP];
@@ -154,7 +195,7 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
       if (DENSE) {
         unsigned st = __hip_atomic_load(&g_state[item], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         if (st == 0) {
-          const bool ok = !mask || mask[item] != 0;
+          const bool ok = (!mask || mask[item] != 0) && rec_rules_ok<RULES>(a, q, item);
           st = atomicCAS(&g_state[item], 0u, ok ? 1u : 2u);
           if (st == 0) {
             if (ok) {
@@ -170,7 +211,7 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
         if (st == 1) atomicAdd(&g_m[item], 1u);
       } else {
         bool fresh = false;
-        const int slot = rec_lds_touch(s_keys, (unsigned)item, true, mask, &fresh, &a.ctr[2]);
+        const int slot = rec_lds_touch<RULES>(s_keys, (unsigned)item, true, mask, &fresh, &a.ctr[2], a, q);
         if (slot < 0) return;
         if (fresh) {
           const unsigned j = atomicAdd(&s_ncand, 1u);
@@ -195,7 +236,7 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
           if (atomicCAS(&g_state[item], 0u, 2u) == 0) g_list[n_items - 1 - (int32_t)atomicAdd(&s_ntomb, 1u)] = item;
         } else {
           bool fresh = false;
-          (void)rec_lds_touch(s_keys, (unsigned)item, false, mask, &fresh, &a.ctr[2]);
+          (void)rec_lds_touch<RULES>(s_keys, (unsigned)item, false, mask, &fresh, &a.ctr[2], a, q);
         }
       }
       __syncthreads();
@@ -312,6 +353,7 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
 
     // ---- backfill: eligible items nothing hit, in fill order ----
     unsigned n_out = nw;
+    unsigned steps = 0;  // of 256 positions each (reported under rules: a rare filter makes the walk cross the catalogue)
     if (!(a.flags & REC_NO_BACKFILL)) {
       for (int64_t p0 = 0; p0 < n_items && n_out < (unsigned)num; p0 += REC_THREADS) {
         const int64_t p = p0 + tid;
@@ -321,7 +363,9 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
           item = a.fill_order ? a.fill_order[p] : (int32_t)p;
           ok = (unsigned)item < (unsigned)n_items && (!mask || mask[item] != 0);
           if (ok) ok = DENSE ? g_state[item] == 0 : !rec_lds_has(s_keys, (unsigned)item);
+          if (RULES && ok) ok = rec_rules_ok<RULES>(a, q, item);
         }
+        ++steps;
         const unsigned long long b = __ballot(ok ? 1 : 0);
         if (lane == 0) s_wcnt[wave] = (unsigned)__popcll(b);
         __syncthreads();
@@ -343,6 +387,7 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
     if (tid == 0) {
       a.out_count[q] = (int32_t)n_out;
       atomicAdd(&a.ctr[3], (unsigned long long)nc);
+      if (RULES) atomicAdd(&a.ctr[4], (unsigned long long)steps);
     }
     if (DENSE) {  // leave the accumulator as it was found
       for (unsigned j = tid; j < nc; j += REC_THREADS) g_state[g_list[j]] = 0;
@@ -355,7 +400,7 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
 
 __global__ void rec_stats_kernel(const unsigned long long* __restrict__ ctr, int64_t* __restrict__ stats) {
   const int t = threadIdx.x;
-  if (t < REC_STATS_LEN) stats[t] = t < 4 ? (int64_t)ctr[t] : 0;
+  if (t < REC_STATS_LEN) stats[t] = t < 5 ? (int64_t)ctr[t] : 0;
 }
 
 // resident blocks of the global class: 20 bytes of scratch per item and block (g_state, g_m, g_list: 4 each; g_score: 8), at most 512 MiB
@@ -369,17 +414,19 @@ int32_t recommend_global_blocks(int64_t n_queries, int32_t n_items, int n_cu) {
 hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t n_items, const RecClause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
                             const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
                             int32_t* out_idx, double* out_score, int64_t* stats_dev, unsigned long long* ctr, int32_t* list, int32_t* pos, int32_t g_blocks,
-                            unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit) {
+                            unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit, const RecRule* rules, int32_t n_rules) {
   RecArgs a;
   memset(&a, 0, sizeof(a));
   for (int c = 0; c < n_clauses; ++c) a.c[c] = clauses[c];
+  for (int j = 0; j < n_rules; ++j) a.r[j] = rules[j];
+  a.n_rules = n_rules;
   a.n_queries = n_queries; a.n_items = n_items; a.n_clauses = n_clauses; a.num = num; a.flags = flags;
   a.lds_limit = lds_limit < REC_LIMIT ? lds_limit : REC_LIMIT;
   a.excl_row_ptr = excl_row_ptr; a.excl_col_idx = excl_col_idx; a.item_mask = item_mask; a.fill_order = fill_order;
   a.pos = fill_order ? pos : nullptr;
   a.list = list; a.ctr = ctr; a.out_count = out_count; a.out_idx = out_idx; a.out_score = out_score;
   a.g_state = g_state; a.g_m = g_m; a.g_list = g_list; a.g_score = g_score; a.g_blocks = g_blocks;
-  hipError_t e = hipMemsetAsync(ctr, 0, 4 * sizeof(unsigned long long), st);
+  hipError_t e = hipMemsetAsync(ctr, 0, 5 * sizeof(unsigned long long), st);
   if (e != hipSuccess) return e;
   if (n_queries > 0) {
     if (fill_order && n_items > 0) {
@@ -394,8 +441,13 @@ hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t
     if (wb > (int64_t)n_cu * 8) wb = (int64_t)n_cu * 8;
     hipLaunchKernelGGL(rec_work_kernel, dim3((unsigned)wb), dim3(REC_THREADS), 0, st, a);
     const int64_t lb = n_queries < (int64_t)n_cu * 2 ? n_queries : (int64_t)n_cu * 2;  // the LDS table lets two blocks share a CU
-    hipLaunchKernelGGL((rec_rows_kernel<false>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
-    hipLaunchKernelGGL((rec_rows_kernel<true>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
+    if (n_rules > 0) {
+      hipLaunchKernelGGL((rec_rows_kernel<false, true>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<true, true>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
+    } else {
+      hipLaunchKernelGGL((rec_rows_kernel<false, false>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<true, false>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
+    }
   }
   if (stats_dev) hipLaunchKernelGGL(rec_stats_kernel, dim3(1), dim3(64), 0, st, ctr, stats_dev);
   return hipGetLastError();

@@ -683,9 +683,12 @@ int urcco_dev_pop_counts(urcco_session* s, int64_t n_events, const int32_t* item
   return URCCO_OK;
 }
 
-int urcco_dev_recommend(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
-                        const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
-                        int32_t* out_idx, double* out_score, int64_t* stats_dev) {
+}  // extern "C"
+
+// urcco_dev_recommend (n_rules == 0) and urcco_dev_recommend_rules
+static int recommend_call(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
+                          const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
+                          int32_t* out_idx, double* out_score, int64_t* stats_dev, const urcco_rec_rule* rules, int32_t n_rules) {
   if (!s || n_queries < 0 || n_queries > 0x7fffffffll || n_items < 0 || n_items == 0x7fffffff) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: bad argument");
   if (num < 1 || num > URCCO_REC_MAX_NUM) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: num must lie in 1..%d, got %d", URCCO_REC_MAX_NUM, num);
   if (n_clauses < 0 || n_clauses > URCCO_REC_MAX_CLAUSES || (n_clauses > 0 && !clauses))
@@ -701,6 +704,20 @@ int urcco_dev_recommend(urcco_session* s, int64_t n_queries, int32_t n_items, co
       return fail(URCCO_BAD_ARG, "urcco_dev_recommend: clause %d: bad matrix", c);
     cl[c] = urcco::RecClause{in.ind_col_ptr, in.ind_row_idx, in.q_row_ptr, in.q_col_idx, in.boost, in.n_cols, 0};
   }
+  if (n_rules < 0 || n_rules > URCCO_REC_MAX_RULES || (n_rules > 0 && !rules))
+    return fail(URCCO_BAD_ARG, "urcco_dev_recommend_rules: between 0 and %d rules, got %d", URCCO_REC_MAX_RULES, n_rules);
+  urcco::RecRule rl[URCCO_REC_MAX_RULES];
+  for (int j = 0; j < n_rules; ++j) {
+    const urcco_rec_rule& in = rules[j];
+    if (in.kind == URCCO_RULE_ANY || in.kind == URCCO_RULE_NONE) {
+      if (in.n_cols < 0 || !in.m_row_ptr || !in.m_col_idx || !in.q_row_ptr || !in.q_col_idx) return fail(URCCO_BAD_ARG, "urcco_dev_recommend_rules: rule %d: bad matrix", j);
+    } else if (in.kind == URCCO_RULE_RANGE) {
+      if (in.n_cols < 0 || !in.item_value || !in.q_lo || !in.q_hi) return fail(URCCO_BAD_ARG, "urcco_dev_recommend_rules: rule %d: a range needs item_value, q_lo and q_hi", j);
+    } else {
+      return fail(URCCO_BAD_ARG, "urcco_dev_recommend_rules: rule %d: unknown kind %d", j, in.kind);
+    }
+    rl[j] = urcco::RecRule{in.m_row_ptr, in.m_col_idx, in.q_row_ptr, in.q_col_idx, in.item_value, in.q_lo, in.q_hi, in.kind, in.n_cols};
+  }
   // URCCO_REC_LDS_LIMIT lowers the work bound up to which a query runs in the LDS class (read per call): small test shapes reach the global class with it
   int32_t lds_limit = urcco::REC_LDS_LIMIT;
   if (const char* e = getenv("URCCO_REC_LDS_LIMIT")) {
@@ -709,9 +726,9 @@ int urcco_dev_recommend(urcco_session* s, int64_t n_queries, int32_t n_items, co
   }
   const int32_t g_blocks = urcco::recommend_global_blocks(n_queries, n_items, s->n_cu);
   const size_t slice = (size_t)g_blocks * (size_t)(n_items > 0 ? n_items : 1);
-  URC(s->reserve(urcco_session::need(4, 8) + urcco_session::need((size_t)n_queries, 4) + urcco_session::need((size_t)n_items, 4) + 3 * urcco_session::need(slice, 4) +
+  URC(s->reserve(urcco_session::need(8, 8) + urcco_session::need((size_t)n_queries, 4) + urcco_session::need((size_t)n_items, 4) + 3 * urcco_session::need(slice, 4) +
                  urcco_session::need(slice, 8)));
-  unsigned long long* ctr = s->take<unsigned long long>(4);
+  unsigned long long* ctr = s->take<unsigned long long>(8);
   int32_t* list = s->take<int32_t>((size_t)n_queries);
   int32_t* pos = s->take<int32_t>((size_t)n_items);
   unsigned* g_state = s->take<unsigned>(slice);
@@ -719,8 +736,24 @@ int urcco_dev_recommend(urcco_session* s, int64_t n_queries, int32_t n_items, co
   int32_t* g_list = s->take<int32_t>(slice);
   double* g_score = s->take<double>(slice);
   HIPC(urcco::launch_recommend(s->stream, s->n_cu, n_queries, n_items, cl, n_clauses, excl_row_ptr, excl_col_idx, item_mask, fill_order, num, flags, out_count, out_idx,
-                               out_score, stats_dev, ctr, list, pos, g_blocks, g_state, g_m, g_list, g_score, lds_limit));
+                               out_score, stats_dev, ctr, list, pos, g_blocks, g_state, g_m, g_list, g_score, lds_limit, rl, n_rules));
   return URCCO_OK;
+}
+
+extern "C" {
+
+int urcco_dev_recommend(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
+                        const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
+                        int32_t* out_idx, double* out_score, int64_t* stats_dev) {
+  return recommend_call(s, n_queries, n_items, clauses, n_clauses, excl_row_ptr, excl_col_idx, item_mask, fill_order, num, flags, out_count, out_idx, out_score, stats_dev,
+                        nullptr, 0);
+}
+
+int urcco_dev_recommend_rules(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
+                              const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
+                              int32_t* out_idx, double* out_score, int64_t* stats_dev, const urcco_rec_rule* rules, int32_t n_rules) {
+  return recommend_call(s, n_queries, n_items, clauses, n_clauses, excl_row_ptr, excl_col_idx, item_mask, fill_order, num, flags, out_count, out_idx, out_score, stats_dev,
+                        rules, n_rules);
 }
 
 int urcco_dev_llr(urcco_session* s, int64_t n, const int64_t* with_a, const int64_t* with_b, const int64_t* with_ab, const int64_t* n_users,

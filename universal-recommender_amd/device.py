@@ -209,12 +209,15 @@ class DeviceSession:
         return DevIndicators(item_lo, item_hi, b.n_cols, k, c_rp, c_idx, c_llr, stats, b.row_ptr, b.col_idx)
 
     def recommend(self, n_queries: int, n_items: int, clauses, num: int, excl=None, item_mask: Optional[torch.Tensor] = None,
-                  fill_order: Optional[torch.Tensor] = None, flags: int = 0, stats: bool = True):
+                  fill_order: Optional[torch.Tensor] = None, flags: int = 0, stats: bool = True, rules=None):
         """urcco_dev_recommend: the top `num` of sum_c boost_c |T_c(q) ^ I_c(i)| per query row over the eligible items, in the order (score
         desc, backfill position asc).  clauses: (n_cols, boost, ind_col_ptr, ind_row_idx, q_row_ptr, q_col_idx) per should-clause, device
         tensors (the CSC of the indicator matrix, the CSR of the query terms); excl: (row_ptr, col_idx) of the exclusion CSR or None.
         Returns (count int32 [n_queries], idx int32 [n_queries, num], score float64 [n_queries, num], stats int64 [REC_STATS_LEN] or None);
-        only the first count[q] entries of a row are written.  Enqueues, does not synchronise."""
+        only the first count[q] entries of a row are written.  Enqueues, does not synchronise.
+        rules (urcco_dev_recommend_rules; None = the rule-free call): per rule (RULE_ANY | RULE_NONE, n_cols, m_row_ptr, m_col_idx, q_row_ptr, q_col_idx)
+        -- the CSR of the item x value matrix and of the query rows -- or (RULE_RANGE, item_value, q_lo, q_hi), int64 device tensors; an item is
+        eligible only when every rule holds for (query, item)."""
         arr = (_lib.RecClause * max(len(clauses), 1))()
         for c, (n_cols, boost, cp, ri, qrp, qci) in enumerate(clauses):
             arr[c].n_cols, arr[c].boost = int(n_cols), float(boost)
@@ -223,9 +226,20 @@ class DeviceSession:
         o_idx = self.empty(max(n_queries * num, 1), torch.int32)
         o_score = self.empty(max(n_queries * num, 1), torch.float64)
         st = self.empty(_lib.REC_STATS_LEN, torch.int64) if stats else None
-        self._check(self.lib.urcco_dev_recommend(self.handle, n_queries, n_items, arr, len(clauses), _ptr(excl[0]) if excl is not None else None,
-                                                _ptr(excl[1]) if excl is not None else None, _ptr(item_mask), _ptr(fill_order), num, flags,
-                                                _ptr(o_count), _ptr(o_idx), _ptr(o_score), _ptr(st)))
+        args = (self.handle, n_queries, n_items, arr, len(clauses), _ptr(excl[0]) if excl is not None else None, _ptr(excl[1]) if excl is not None else None,
+                _ptr(item_mask), _ptr(fill_order), num, flags, _ptr(o_count), _ptr(o_idx), _ptr(o_score), _ptr(st))
+        if rules is None:
+            self._check(self.lib.urcco_dev_recommend(*args))
+        else:
+            rl = (_lib.RecRule * max(len(rules), 1))()
+            for j, rule in enumerate(rules):
+                rl[j].kind = int(rule[0])
+                if rule[0] == _lib.RULE_RANGE:
+                    rl[j].item_value, rl[j].q_lo, rl[j].q_hi = (_ptr(t) for t in rule[1:4])
+                else:
+                    rl[j].n_cols = int(rule[1])
+                    rl[j].m_row_ptr, rl[j].m_col_idx, rl[j].q_row_ptr, rl[j].q_col_idx = (_ptr(t) for t in rule[2:6])
+            self._check(self.lib.urcco_dev_recommend_rules(*args, rl, len(rules)))
         n = max(n_queries, 0)
         return o_count[:n], o_idx[: n * max(num, 0)].view(n, -1) if n and num > 0 else o_idx[:0], o_score[: n * max(num, 0)].view(n, -1) if n and num > 0 else o_score[:0], st
 

@@ -8,8 +8,20 @@ against the indicator matrices the build left in HBM: an item has a positive sco
 the order among positives are this library's (decision D15 of DESIGN.md -- BM25's `_score` cannot be reproduced).  PyTorch is plumbing here
 (device memory, the argsort of the backfill ranks); the product and the top-k are hand-written HIP.
 
-Not served (NotImplementedError names the key): query `fields` (property boost / filter / exclude), `dateRange`, negative user / item bias
-(history used as a filter).  Items outside the primary event's item dictionary are never returned."""
+Business rules (decision D16; buildQueryMust / buildQueryMustNot / getBoostedMetadata / getFilteringDateRange, :684-727, :841-953) are served
+by a model built with item properties (`DeviceModel.from_indicators(..., properties=..., date_names=...)`): they become eligibility rules that
+urcco_dev_recommend_rules evaluates on the device per (query, item), inside the top-`num` cut and the backfill walk:
+    fields, bias > 0     one more should-clause over the property's item x value matrix, boost = bias, after the similar-item clauses (:653)
+    fields, bias < 0     ANY rule: the item holds one of the values          fields, bias == 0    NONE rule: the item holds none of them
+    dateRange            RANGE rule on the named date: after < date < before, a missing side open; an item without the date fails
+    no dateRange, availableDateName and expireDateName configured and held by the model: available <= now and expire > now, now = the query's
+                         currentDate, else `now_ms`, else the wall clock (the reference's `else if`: a dateRange replaces this rule, :877-948)
+    userBias < 0         one ANY rule per query event: the item's indicator list for the event holds one of the user's recent items -- not a
+                         should-clause; an event without history matches nothing, as an empty `terms` query does (:688-693)
+    itemBias < 0         the same with the query item's own indicator lists (:695-699)
+An unknown property name or value has no column: an ANY on it matches nothing, a NONE or a boost on it does nothing.  A model built WITHOUT
+properties raises NotImplementedError (naming the key) for all of these, as before.  Not served: engine.json-level `fields`.  Items outside the
+primary event's item dictionary are never returned."""
 from __future__ import annotations
 
 from dataclasses import dataclass
@@ -35,19 +47,43 @@ class _Correlator:
     host: Optional[Tuple[np.ndarray, np.ndarray]] = None   # (row_ptr, col_idx) on the host, fetched once
 
 
+@dataclass
+class _Property:
+    """A list-of-strings item property as an item x value 0/1 matrix on the device: CSR for the rules, CSC for boost clauses."""
+    name: str
+    n_cols: int
+    values: Dict[str, int]
+    row_ptr: torch.Tensor
+    col_idx: torch.Tensor
+    col_ptr: torch.Tensor
+    row_idx: torch.Tensor
+
+
+NO_VALUE = -(1 << 63)      # INT64_MIN: the item has no value for a RANGE rule
+OPEN_HI = (1 << 63) - 1
+
+
 class DeviceModel:
     """The indicator matrices of a built model in HBM, in the form urcco_dev_recommend reads (CSC), with their dictionaries."""
 
-    def __init__(self, sess: DeviceSession, item_ids: Optional[BiDictionary], n_items: int, correlators: List[_Correlator], fill_order: Optional[torch.Tensor]):
+    def __init__(self, sess: DeviceSession, item_ids: Optional[BiDictionary], n_items: int, correlators: List[_Correlator], fill_order: Optional[torch.Tensor],
+                 properties: Optional[Dict[str, _Property]] = None, dates: Optional[Dict[str, torch.Tensor]] = None):
         self.sess, self.item_ids, self.n_items, self.correlators, self.fill_order = sess, item_ids, n_items, correlators, fill_order
         self.by_name = {c.name: c for c in correlators}
+        self.properties = properties    # None: built without item properties -- batch_predict serves no business rules
+        self.dates = dates or {}        # date property -> int64 [n_items] epoch milliseconds, NO_VALUE where the item has none
 
     @staticmethod
     def from_indicators(sess: DeviceSession, correlators: Sequence[Tuple[str, object]], ranks: Optional[Dict[object, float]] = None,
-                        item_ids: Optional[BiDictionary] = None, column_ids: Optional[Dict[str, BiDictionary]] = None) -> "DeviceModel":
+                        item_ids: Optional[BiDictionary] = None, column_ids: Optional[Dict[str, BiDictionary]] = None,
+                        properties: Optional[Dict[object, Dict[str, object]]] = None, date_names: Sequence[str] = ()) -> "DeviceModel":
         """correlators: (event name, IndexedDataset | DevIndicators) per event type, the primary first -- URModel.coocurrenceMatrices or the device
         build's own output (then the dictionaries come through item_ids / column_ids; without them ids are the dense integers).
-        ranks: {item: rank} (popRank of calcAll's properties) -> the backfill order: rank desc, items without a rank last, then item index."""
+        ranks: {item: rank} (popRank of calcAll's properties) -> the backfill order: rank desc, items without a rank last, then item index.
+        properties: item -> {name: value} (URModel.propertiesMaps[0]) -> the business rules of batch_predict: every list-of-strings property becomes
+        an item x value matrix on the device, every name in date_names an int64 array of epoch milliseconds (URModel.extractJvalue parses the
+        strings).  Items outside the primary's dictionary and other properties are ignored.  None: no rules are served ({} serves the negative
+        biases alone)."""
         if not correlators:
             raise ValueError("a model needs at least the primary event's indicator matrix")
         out: List[_Correlator] = []
@@ -86,7 +122,10 @@ class DeviceModel:
                 if i is not None and 0 <= i < n_items:
                     r[i] = float(v)
             fill = torch.sort(-r.to(sess.device), stable=True).indices.to(torch.int32)
-        return DeviceModel(sess, item_ids, n_items, out, fill)
+        model = DeviceModel(sess, item_ids, n_items, out, fill)
+        if properties is not None:
+            model.properties, model.dates = _device_properties(sess, properties, date_names, n_items, model.item_index)
+        return model
 
     # ---- dictionaries ----
     def item_index(self, item) -> Optional[int]:
@@ -119,6 +158,36 @@ class DeviceModel:
         return ci[rp[i]:rp[i + 1]]
 
 
+def _device_properties(sess: DeviceSession, properties, date_names: Sequence[str], n_items: int, index_of):
+    from .ur_model import extractJvalue
+    lists: Dict[str, Tuple[Dict[str, int], List[Tuple[int, int]]]] = {}
+    dates = {name: np.full(n_items, NO_VALUE, np.int64) for name in date_names}
+    for item, fields in properties.items():
+        i = index_of(item)
+        if i is None:
+            continue
+        for name, value in fields.items():
+            if name in dates:
+                if isinstance(value, str):
+                    dates[name][i] = int(round(extractJvalue(date_names, name, value).timestamp() * 1000))
+            elif isinstance(value, (list, tuple)) and all(isinstance(v, str) for v in value):
+                values, pairs = lists.setdefault(name, ({}, []))
+                pairs += [(i, values.setdefault(v, len(values))) for v in value]
+    props = {}
+    for name, (values, pairs) in lists.items():
+        if not values:
+            continue
+        key = np.unique(np.array([i * len(values) + v for i, v in pairs], np.int64))
+        rp = np.zeros(n_items + 1, np.int64)
+        np.cumsum(np.bincount(key // len(values), minlength=n_items), out=rp[1:])
+        row_ptr = torch.from_numpy(rp).to(sess.device)
+        col_idx = torch.from_numpy((key % len(values)).astype(np.int32)).to(sess.device)
+        counts = sess.column_counts(col_idx, key.size, len(values), sess.empty(len(values), torch.int32))
+        cp, ri = sess.transpose(DevCsr(n_items, len(values), row_ptr, col_idx, key.size), counts)
+        props[name] = _Property(name, len(values), values, row_ptr, col_idx, cp, ri)
+    return props, {name: torch.from_numpy(v).to(sess.device) for name, v in dates.items()}
+
+
 def _csr(rows: List[np.ndarray], device) -> Tuple[torch.Tensor, torch.Tensor]:
     rp = np.zeros(len(rows) + 1, np.int64)
     np.cumsum([r.size for r in rows], out=rp[1:])
@@ -131,10 +200,19 @@ def _boost(bias: float) -> float:
     return float(bias) if bias > 0 and bias != 1 else 1.0
 
 
-def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history: Dict[str, Dict[str, List[str]]], item_mask=None) -> List[dict]:
+def _date_ms(text: str, what: str) -> int:
+    from .ur_algorithm import _iso_ms
+    ms = _iso_ms(text)
+    if ms is None:
+        raise ValueError(f"{what}: {text!r} is not an ISO-8601 date")
+    return ms
+
+
+def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history: Dict[str, Dict[str, List[str]]], item_mask=None, now_ms: Optional[int] = None) -> List[dict]:
     """URAlgorithm.predict for a list of query dicts: [{"itemScores": [{"item", "score"}, ...]}, ...] in the order of `queries`.
     history: user -> {event name: [item ids, oldest first]} (the event store's view of the user); item_mask: None, an array of n_items
-    flags or {item: bool} (the available / expire date filter evaluated for "now"; items not named are eligible)."""
+    flags or {item: bool} (any further filter of the caller's; items not named are eligible -- it applies on top of the rules); now_ms: "now" of the
+    available / expire rule for queries without `currentDate` (default: the wall clock)."""
     ap = algo.ap
     model_events = list(algo.modelEventNames)
     primary = model_events[0]
@@ -167,16 +245,45 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history: Di
     # ---- per query: clause terms, exclusions, and the key of the call it can share ----
     groups: Dict[tuple, List[int]] = {}
     plans = []
+    served = model.properties is not None
+    dated = served and ap.availableDateName is not None and ap.expireDateName is not None and ap.availableDateName in model.dates and ap.expireDateName in model.dates
     for n, q in enumerate(queries):
-        for key in ("fields", "dateRange"):
-            if q.get(key):
-                raise NotImplementedError(f"query key {key!r} is not served by batch_predict")
         user_bias = q.get("userBias", ap.userBias if ap.userBias is not None else 1.0)
         item_bias = q.get("itemBias", ap.itemBias if ap.itemBias is not None else 1.0)
-        if user_bias < 0:
-            raise NotImplementedError("negative userBias (user history as a filter) is not served by batch_predict")
-        if item_bias < 0:
-            raise NotImplementedError("negative itemBias (similar items as a filter) is not served by batch_predict")
+        if not served:
+            for key in ("fields", "dateRange"):
+                if q.get(key):
+                    raise NotImplementedError(f"query key {key!r} needs a model built with item properties")
+            if user_bias < 0:
+                raise NotImplementedError("negative userBias (user history as a filter) needs a model built with item properties ({} will do)")
+            if item_bias < 0:
+                raise NotImplementedError("negative itemBias (similar items as a filter) needs a model built with item properties ({} will do)")
+        # ---- rules: key -> the query's row of the rule (ANY / NONE: columns; RANGE: (lo, hi)); the key names the matrix ----
+        rules: Dict[tuple, object] = {}
+        seen: Dict[tuple, int] = {}
+        boosted = []
+        for f in (q.get("fields") or []):
+            name, bias = f["name"], float(f.get("bias", 1.0))
+            prop = model.properties.get(name)
+            cols = np.unique(np.array([prop.values[v] for v in f.get("values", []) if v in prop.values], np.int64)) if prop is not None else None
+            kind = "boost" if bias > 0 else "any" if bias < 0 else "none"
+            k = seen[(kind, name, bias)] = seen.get((kind, name, bias), -1) + 1
+            if bias > 0:                                                                        # getBoostedMetadata :842-849
+                if prop is not None:
+                    boosted.append(((name, bias, k), cols))
+            elif bias < 0:                                                                      # getFilteringMetadata :852-859
+                rules[("any", name, k) if prop is not None else ("never", k)] = cols if prop is not None else np.zeros(0, np.int64)
+            elif prop is not None:                                                              # getExcludingMetadata :862-869
+                rules[("none", name, k)] = cols
+        dr = q.get("dateRange")
+        if dr and (dr.get("after") or dr.get("before")):                                        # getFilteringDateRange :877-915
+            rules[("range", dr["name"])] = (_date_ms(dr["after"], "dateRange.after") + 1 if dr.get("after") else NO_VALUE,
+                                            _date_ms(dr["before"], "dateRange.before") if dr.get("before") else OPEN_HI)
+        elif dated:                                                                             # :916-948 -- only without a dateRange
+            import time
+            now = _date_ms(q["currentDate"], "currentDate") if q.get("currentDate") else int(now_ms) if now_ms is not None else int(time.time() * 1000)
+            rules[("range", ap.availableDateName)] = (NO_VALUE, now + 1)
+            rules[("range", ap.expireDateName, "expire")] = (now + 1, OPEN_HI)
         num = int(q.get("num", limit))
         start = int(q.get("from", 0))
         if num < 1 or start < 0:
@@ -194,7 +301,11 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history: Di
                 continue
             recent = list(reversed(events.get(ev, [])))[: max_items.get(ev, 100)]               # most recent first, capped, then distinct
             ids = [model.column_index(c, i) for i in dict.fromkeys(recent)]
-            terms[("user", ev)] = np.unique(np.array([i for i in ids if i is not None], np.int64))
+            ids = np.unique(np.array([i for i in ids if i is not None], np.int64))
+            if user_bias < 0:                                                                   # buildQueryMust :688-693: a filter per event, no should-clause
+                rules[("hist", ev)] = ids
+            else:
+                terms[("user", ev)] = ids
         for ev in q_events:                                                                     # getExcludedItems :741-767
             if ev in blacklist_events:
                 excl += [model.item_index(i) for i in events.get(ev, [])]
@@ -207,7 +318,10 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history: Di
                     ids = model.indicator_row(c, i)
                     if ids.size > max_query_events:
                         ids = ids[: max_query_events - 1]
-                    terms[("item", ev)] = np.unique(ids.astype(np.int64))
+                    if item_bias < 0:                                                           # :695-699
+                        rules[("sim", ev)] = np.unique(ids.astype(np.int64))
+                    else:
+                        terms[("item", ev)] = np.unique(ids.astype(np.int64))
             if not q.get("returnSelf", ap.returnSelf if ap.returnSelf is not None else False):
                 excl.append(i)
         if item_set:                                                                            # :645
@@ -218,29 +332,51 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history: Di
         set_bias = q.get("itemSetBias", 1.0)
         if set_bias is None or set_bias < 0:
             set_bias = 1.0
-        key = (_boost(user_bias), _boost(item_bias), _boost(set_bias), start + num)
+        for slot, cols in boosted:
+            terms[("field",) + slot] = cols
+        # a rule cannot be absent for one row of a call: queries share a call only when they carry the same rules and the same property clauses
+        key = (_boost(user_bias), _boost(item_bias), _boost(set_bias), start + num, tuple(slot for slot, _ in boosted), tuple(rules))
         groups.setdefault(key, []).append(n)
-        plans.append((terms, np.unique(np.array([i for i in excl if i is not None], np.int64)), start, num))
+        plans.append((terms, np.unique(np.array([i for i in excl if i is not None], np.int64)), start, num, rules))
 
     # ---- one call per group ----
     results: List[Optional[dict]] = [None] * len(queries)
     dev = model.sess.device
     empty = np.zeros(0, np.int64)
-    for (ub, ib, sb, fetch), members in groups.items():
-        slots = []
-        for kind, boost in (("user", ub), ("item", ib), ("set", sb)):
+    for (ub, ib, sb, fetch, field_slots, rule_keys), members in groups.items():
+        slots = []                                                                              # the reference's order (:653): history, similar items, metadata, item set
+        for kind, boost in (("user", ub), ("item", ib), ("field", None), ("set", sb)):
+            if kind == "field":
+                slots += [(("field",) + slot, model.properties[slot[0]], slot[1]) for slot in field_slots
+                          if any(plans[n][0][("field",) + slot].size for n in members)]
+                continue
             for ev in ([primary] if kind == "set" else model_events if kind == "item" else list(model.by_name)):
                 if any(plans[n][0].get((kind, ev), empty).size for n in members):
-                    slots.append((kind, ev, boost))
+                    slots.append(((kind, ev), model.by_name[ev], boost))
         if len(slots) > _lib.REC_MAX_CLAUSES:
             raise ValueError(f"a batch needs {len(slots)} clauses, more than the {_lib.REC_MAX_CLAUSES} one call serves")
+        if len(rule_keys) > _lib.REC_MAX_RULES:
+            raise ValueError(f"a batch needs {len(rule_keys)} rules, more than the {_lib.REC_MAX_RULES} one call serves")
         clauses = []
-        for kind, ev, boost in slots:
-            c = model.by_name[ev]
-            qrp, qci = _csr([plans[n][0].get((kind, ev), empty) for n in members], dev)
+        for slot, c, boost in slots:
+            qrp, qci = _csr([plans[n][0].get(slot, empty) for n in members], dev)
             clauses.append((c.n_cols, boost, c.col_ptr, c.row_idx, qrp, qci))
+        rules = None
+        if served:
+            rules = []
+            for rk in rule_keys:
+                if rk[0] == "range":
+                    value = model.dates.get(rk[1])
+                    if value is None:                                                           # no item holds the property: nothing passes
+                        value = model.dates[rk[1]] = torch.full((max(model.n_items, 1),), NO_VALUE, dtype=torch.int64, device=dev)
+                    lo, hi = (torch.tensor([plans[n][4][rk][side] for n in members], dtype=torch.int64).to(dev) for side in (0, 1))
+                    rules.append((_lib.RULE_RANGE, value, lo, hi))
+                else:
+                    m = model.properties[rk[1]] if rk[0] in ("any", "none") else model.by_name[rk[1]] if rk[0] in ("hist", "sim") else model.correlators[0]
+                    qrp, qci = _csr([plans[n][4][rk] for n in members], dev)
+                    rules.append((_lib.RULE_NONE if rk[0] == "none" else _lib.RULE_ANY, m.n_cols, m.row_ptr, m.col_idx, qrp, qci))
         excl = _csr([plans[n][1] for n in members], dev)
-        count, idx, score, _ = model.sess.recommend(len(members), model.n_items, clauses, fetch, excl, mask_t, model.fill_order, flags, stats=False)
+        count, idx, score, _ = model.sess.recommend(len(members), model.n_items, clauses, fetch, excl, mask_t, model.fill_order, flags, stats=False, rules=rules)
         model.sess.synchronize()
         count, idx, score = count.cpu().numpy(), idx.cpu().numpy(), score.cpu().numpy()
         for r, n in enumerate(members):
