@@ -329,6 +329,19 @@ enum {
 int urcco_session_set_timing(urcco_session* s, int32_t enable);
 /* the debug bits of urcco_context_set_debug, for this session only */
 int urcco_session_set_debug(urcco_session* s, int32_t flags);
+/* The expand tables of urcco_dev_cco_rows* (per CSC entry of A': the start of the user's B' row, and the prefix of the rows' lengths) are built in a
+ * NARROW form -- 32-bit starts, the prefix modulo 2^32 -- whenever the device finds that exact: B' holds fewer than 2^32 entries, no scan tile of the
+ * prefix sums to `limit` = 2^32 or more (a tile = 2048 consecutive CSC entries of A' in the order of a_row_idx; its sum = the B' row lengths of those
+ * entries' users), and the packed-count instantiations of the row kernels run.  Otherwise they are built wide
+ * (64-bit), as before.  Results do not depend on the form.
+ * urcco_session_expand_form: synchronises; *form_host = 0 when the session's last urcco_dev_cco_rows* call ran on narrow tables, else the reasons for
+ * the wide form: 1 | 2 (B' too large) | 4 (a tile sum reached the limit) | 8 (counts do not fit the packed words) | 16 (no packed B', or debug row kernels).
+ * urcco_session_set_expand_test: test hook -- lowers `limit` so that the wide form can be driven at toy size (0 restores 2^32), and starts the
+ * prefix at prefix_seed instead of 0 (just below 2^32: toy rows straddle the wrap of the narrow form).  (0, 0) is production.
+ * ABI: both entries are additions within ABI 305 (no existing entry changed a signature, an array's element type or a stride: the expand tables are
+ * internal scratch).  urcco_session_expand_form is a stable diagnostic; urcco_session_set_expand_test is TEST-ONLY and may change or go without notice. */
+int urcco_session_expand_form(urcco_session* s, int32_t* form_host);
+int urcco_session_set_expand_test(urcco_session* s, int64_t limit, int64_t prefix_seed);
 int urcco_session_get_timings(urcco_session* s, double* ms /*[URCCO_N_STAGES]*/, int64_t* launches /*[URCCO_N_STAGES]*/);
 /* bytes of device scratch currently held */
 int64_t urcco_session_scratch_bytes(const urcco_session* s);

@@ -143,15 +143,22 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_reduce_kernel(Load ld, int6
 // 35 us -- 0.7 ms per build of config 4 over its twenty scans); tiles at or beyond *n_live hold zeros and are not visited.
 constexpr int ST_THREADS = 1024;
 constexpr int ST_ITEMS = 8;
-static __global__ __launch_bounds__(ST_THREADS) void scan_tiles_kernel(int64_t* __restrict__ tile_sums, int64_t n_tiles, const int64_t* __restrict__ n_live) {
+// form.word (nullable; the expand scans): this block also reaches the verdict on the form of the build's expand tables (ExpandForm, cco_kernels.h) -- it is
+// the one place that sees every tile sum before the downsweep writes the prefix.
+static __global__ __launch_bounds__(ST_THREADS) void scan_tiles_kernel(int64_t* __restrict__ tile_sums, int64_t n_tiles, const int64_t* __restrict__ n_live,
+                                                                       ExpandForm form) {
   __shared__ long long s_wave[ST_THREADS / WAVE];
+  __shared__ int s_over;
+  if (threadIdx.x == 0) s_over = 0;
+  __syncthreads();  // (s_over is written again behind the loop, which may run no round at all)
+  bool over = false;
   const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
   int64_t live_tiles = n_tiles;
   if (n_live) {
     const int64_t lt = *n_live / SCAN_TILE + 1;  // tiles that can hold a non-zero sum
     if (lt < live_tiles) live_tiles = lt;
   }
-  long long carry = 0;
+  long long carry = form.seed;
   for (int64_t base = 0; base < live_tiles; base += ST_THREADS * ST_ITEMS) {  // block-uniform trip count
     const int64_t first = base + (int64_t)threadIdx.x * ST_ITEMS;
     long long x[ST_ITEMS];
@@ -160,6 +167,7 @@ static __global__ __launch_bounds__(ST_THREADS) void scan_tiles_kernel(int64_t* 
     for (int q = 0; q < ST_ITEMS; ++q) {
       x[q] = first + q < live_tiles ? tile_sums[first + q] : 0;
       sum += x[q];
+      over = over || (unsigned long long)x[q] >= form.limit;
     }
     long long inc = sum;
 #pragma unroll
@@ -188,6 +196,18 @@ static __global__ __launch_bounds__(ST_THREADS) void scan_tiles_kernel(int64_t* 
   // the prefix of a tile beyond the live ones is the total (the downsweep never reads them, but keep the table well-defined)
   for (int64_t t = live_tiles + threadIdx.x; t < n_tiles; t += ST_THREADS) tile_sums[t] = carry;
   if (threadIdx.x == 0) tile_sums[n_tiles] = carry;
+  if (form.word) {
+    if (over) s_over = 1;  // (every writer stores the same value)
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int f = form.host_narrow ? 0 : *form.word;  // FORM_PS64, when expand_prepare left it
+      if (form.host_narrow) s_over = 0;
+      if (s_over) f |= FORM_TILE;
+      if (form.pack_bad && *form.pack_bad != 0) f |= FORM_PACK;
+      if (form.host_wide) f |= FORM_HOST;
+      *form.word = f ? (f | FORM_WIDE) : 0;
+    }
+  }
 }
 
 template <typename Load>
@@ -291,7 +311,7 @@ static hipError_t launch_scan(hipStream_t st, Load ld, int64_t n, int64_t* out, 
   }
   const int64_t n_tiles = (n + SCAN_TILE - 1) / SCAN_TILE;
   if (!tile_sums_ready) hipLaunchKernelGGL((scan_reduce_kernel<Load>), dim3((unsigned)n_tiles), dim3(SCAN_THREADS), 0, st, ld, n, tile_sums, n_live);
-  hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(ST_THREADS), 0, st, tile_sums, n_tiles, n_live);
+  hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(ST_THREADS), 0, st, tile_sums, n_tiles, n_live, ExpandForm{nullptr, nullptr, 0, 0, ~0ull, 0});
   hipLaunchKernelGGL((scan_downsweep_kernel<Load>), dim3((unsigned)n_tiles), dim3(SCAN_THREADS), 0, st, ld, n, tile_sums, n_tiles, out, n_live);
   return hipGetLastError();
 }

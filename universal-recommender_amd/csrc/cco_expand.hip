@@ -161,6 +161,93 @@ hipError_t launch_xlx_hi_table(hipStream_t st, double* tab, const double* xlx_ta
 // w_i = wp[cp[i+1]] - wp[cp[i]] (exactly the cooccurrence pairs row i forms) drives binning and work-balanced item
 // ranges, and lanes find "their" pairs by searching that slice.
 // ============================================================================================
+// The scan that turns the lengths into the work prefix, in the form the build can use (ExpandForm, cco_kernels.h).  Always the tiled scan: its second
+// pass reaches the verdict, and its tile bases are what keeps every row's 64-bit work available beside a 32-bit prefix.  The downsweep writes
+//   narrow: wp as unsigned[cap + 1], the prefix modulo 2^32 -- half the bytes here and under every row kernel's reads, which only ever take differences
+//           inside one item row;
+//   wide:   wp as int64[cap + 1], and the 32-bit starts (when it was those that expand_prepare left) widened into pstart64 for the plain instantiations
+// into the same buffer, which is sized for the wide form.
+__global__ __launch_bounds__(SCAN_THREADS) void expand_downsweep_kernel(const int32_t* __restrict__ plen, int64_t n, const int64_t* __restrict__ tile_sums,
+                                                                        int64_t n_tiles, int64_t* __restrict__ out, const int64_t* __restrict__ n_live,
+                                                                        const int32_t* __restrict__ form, const unsigned* __restrict__ pstart32,
+                                                                        int64_t* __restrict__ pstart64) {
+  __shared__ long long s_wave[SCAN_THREADS / WAVE];
+  if ((int64_t)blockIdx.x * SCAN_TILE > *n_live) return;  // block-uniform; out[] beyond *n_live is never read
+  const int f = *form;  // grid-uniform
+  const LoadI32 ld{plen};
+  const int64_t first = (int64_t)blockIdx.x * SCAN_TILE + (int64_t)threadIdx.x * SCAN_ITEMS;
+  static_assert(SCAN_ITEMS == 8, "load8");
+  long long x[SCAN_ITEMS];
+  long long v = 0;
+  const bool interior = first + SCAN_ITEMS <= n;
+  if (interior) {
+    ld.load8(first, x);
+  } else {
+#pragma unroll
+    for (int q = 0; q < SCAN_ITEMS; ++q) x[q] = first + q < n ? ld(first + q) : 0;
+  }
+#pragma unroll
+  for (int q = 0; q < SCAN_ITEMS; ++q) v += x[q];
+  long long tot;
+  long long run = block_exclusive_scan(v, s_wave, &tot) + tile_sums[blockIdx.x];
+  if (f == 0) {
+    unsigned* out32 = reinterpret_cast<unsigned*>(out);
+    unsigned r = (unsigned)run;
+    if (interior && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {  // two 16-byte stores per thread
+      unsigned e[SCAN_ITEMS];
+#pragma unroll
+      for (int q = 0; q < SCAN_ITEMS; ++q) {
+        e[q] = r;
+        r += (unsigned)x[q];
+      }
+      *reinterpret_cast<uint4*>(out32 + first) = make_uint4(e[0], e[1], e[2], e[3]);
+      *reinterpret_cast<uint4*>(out32 + first + 4) = make_uint4(e[4], e[5], e[6], e[7]);
+    } else {
+#pragma unroll
+      for (int q = 0; q < SCAN_ITEMS; ++q) {
+        if (first + q < n) out32[first + q] = r;
+        r += (unsigned)x[q];
+      }
+    }
+    if (blockIdx.x == 0 && threadIdx.x == 0) out32[n] = (unsigned)tile_sums[n_tiles];
+    return;
+  }
+  if (interior && (reinterpret_cast<uintptr_t>(out) & 15) == 0) {  // four 16-byte stores per thread
+#pragma unroll
+    for (int q = 0; q < SCAN_ITEMS; q += 2) {
+      const long long e0 = run, e1 = run + x[q];
+      run = e1 + x[q + 1];
+      int4 w;
+      w.x = (int)(unsigned)e0; w.y = (int)(unsigned)((unsigned long long)e0 >> 32);
+      w.z = (int)(unsigned)e1; w.w = (int)(unsigned)((unsigned long long)e1 >> 32);
+      *reinterpret_cast<int4*>(out + first + q) = w;
+    }
+  } else {
+#pragma unroll
+    for (int q = 0; q < SCAN_ITEMS; ++q) {
+      const int64_t i = first + q;
+      if (i < n) out[i] = run;
+      run += x[q];
+    }
+  }
+  if (!(f & FORM_PS64) && pstart32 && pstart64) {  // (the rare form: no effort spent on vector accesses)
+#pragma unroll
+    for (int q = 0; q < SCAN_ITEMS; ++q)
+      if (first + q < n) pstart64[first + q] = (int64_t)pstart32[first + q];
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) out[n] = tile_sums[n_tiles];
+}
+static hipError_t expand_scan(hipStream_t st, const int32_t* plen, int64_t cap, int64_t* wp, int64_t* tile_sums, const int64_t* n_live, bool tile_sums_ready,
+                              const unsigned* pstart32, int64_t* pstart64, ExpandForm form) {
+  const int64_t n_tiles = cap > 0 ? (cap + SCAN_TILE - 1) / SCAN_TILE : 1;  // (cap == 0: one tile without elements -- wp[0] = 0 and the verdict are still due)
+  if (!tile_sums_ready || cap <= 0)
+    hipLaunchKernelGGL((scan_reduce_kernel<LoadI32>), dim3((unsigned)n_tiles), dim3(SCAN_THREADS), 0, st, LoadI32{plen}, cap, tile_sums, n_live);
+  hipLaunchKernelGGL(scan_tiles_kernel, dim3(1), dim3(ST_THREADS), 0, st, tile_sums, n_tiles, n_live, form);
+  hipLaunchKernelGGL(expand_downsweep_kernel, dim3((unsigned)n_tiles), dim3(SCAN_THREADS), 0, st, plen, cap, (const int64_t*)tile_sums, n_tiles, wp, n_live,
+                     (const int32_t*)form.word, pstart32, pstart64);
+  return hipGetLastError();
+}
+
 // 32-bit copy of B's row_ptr.  expand_prepare is bound by the fabric traffic of one random row_ptr gather per CSC entry of A'
 // (PMC: 415 MB per launch for 4.6M entries); a table of 4 B per user is half as large and stays closer to the L2s.
 __global__ __launch_bounds__(256) void narrow_row_ptr_kernel(const int64_t* __restrict__ rp, int64_t n, unsigned* __restrict__ out) {
@@ -170,11 +257,15 @@ __global__ __launch_bounds__(256) void narrow_row_ptr_kernel(const int64_t* __re
 // b_rp32: optional 32-bit copy of b_rp (n_rows_b + 1 entries); used when B holds fewer than 2^32 entries (read on the device)
 __global__ __launch_bounds__(256) void expand_prepare_kernel(const int64_t* __restrict__ a_cp, int32_t n_items_a, const int32_t* __restrict__ a_ri,
                                                              const int64_t* __restrict__ b_rp, const unsigned* __restrict__ b_rp32, int64_t n_rows_b,
-                                                             int64_t cap, int64_t* __restrict__ pstart, int32_t* __restrict__ plen) {
+                                                             int64_t cap, unsigned* __restrict__ pstart32, int64_t* __restrict__ pstart64,
+                                                             int32_t* __restrict__ plen, int32_t* __restrict__ form) {
   const int64_t nnz = a_cp[n_items_a];
   int64_t lim = (nnz / SCAN_TILE + 1) * SCAN_TILE;  // the scan skips tiles that start at or beyond nnz
   if (lim > cap) lim = cap;
   const bool narrow = b_rp32 != nullptr && b_rp[n_rows_b] < ((int64_t)1 << 32);
+  // the starts go out in the width B' needs (grid-uniform): 32 bits, or 64 with the form word told so (the scan then settles on the wide form)
+  // (pstart32 == pstart64 == nullptr: the caller wants the lengths alone -- urcco_dev_row_work)
+  if (!narrow && pstart64 && blockIdx.x == 0 && threadIdx.x == 0) *form = FORM_PS64;
   // Four grid-stride steps at a time: the four user ids are loaded first, then all eight row_ptr gathers are in flight
   // together (the kernel is a chain of two dependent random loads); every access stays coalesced across the wave.
   const int64_t stride = (int64_t)gridDim.x * 256;
@@ -203,7 +294,11 @@ __global__ __launch_bounds__(256) void expand_prepare_kernel(const int64_t* __re
     for (int q = 0; q < 4; ++q) {
       const int64_t p = p0 + q * stride;
       if (p < lim) {
-        pstart[p] = s[q];
+        if (narrow) {
+          if (pstart32) pstart32[p] = (unsigned)s[q];
+        } else if (pstart64) {
+          pstart64[p] = s[q];
+        }
         plen[p] = (int32_t)(e[q] - s[q]);
       }
     }
@@ -211,8 +306,10 @@ __global__ __launch_bounds__(256) void expand_prepare_kernel(const int64_t* __re
 }
 
 hipError_t launch_expand_prepare(hipStream_t st, int n_cu, const int64_t* a_col_ptr, int32_t n_items_a, const int32_t* a_row_idx,
-                                 const int64_t* b_row_ptr, unsigned* b_rp32_scratch, int64_t n_rows_b, int64_t cap, int64_t* pstart, int32_t* plen,
-                                 int64_t* wp, int64_t* tile_sums) {
+                                 const int64_t* b_row_ptr, unsigned* b_rp32_scratch, int64_t n_rows_b, int64_t cap, unsigned* pstart32, int64_t* pstart64,
+                                 int32_t* plen, int64_t* wp, int64_t* tile_sums, ExpandForm form) {
+  hipError_t e = hipMemsetAsync(form.word, 0, sizeof(int32_t), st);
+  if (e != hipSuccess) return e;
   if (cap > 0) {
     if (b_rp32_scratch) {
       int64_t nb = (n_rows_b + 1 + 255) / 256;
@@ -223,9 +320,9 @@ hipError_t launch_expand_prepare(hipStream_t st, int n_cu, const int64_t* a_col_
     const int64_t lim = (int64_t)n_cu * 16;
     if (blocks > lim) blocks = lim;
     hipLaunchKernelGGL(expand_prepare_kernel, dim3((unsigned)blocks), dim3(256), 0, st, a_col_ptr, n_items_a, a_row_idx, b_row_ptr,
-                       (const unsigned*)b_rp32_scratch, n_rows_b, cap, pstart, plen);
+                       (const unsigned*)b_rp32_scratch, n_rows_b, cap, pstart32, pstart64, plen, form.word);
   }
-  return launch_scan(st, LoadI32{plen}, cap, wp, tile_sums, a_col_ptr + n_items_a);
+  return expand_scan(st, plen, cap, wp, tile_sums, a_col_ptr + n_items_a, false, pstart32, pstart64, form);
 }
 
 // --------------------------------------------------------------------------------------------
@@ -238,7 +335,7 @@ struct __attribute__((packed, aligned(4))) Words4 { unsigned a, b, c, d; };
 struct __attribute__((packed, aligned(4))) Words2 { unsigned a, b; };
 struct ExpandMultiArgs {
   const int64_t* b_rp[EXPAND_MULTI_MAX];
-  int64_t* pstart[EXPAND_MULTI_MAX];
+  unsigned* pstart[EXPAND_MULTI_MAX];
   int32_t* plen[EXPAND_MULTI_MAX];
   int64_t* tsum[EXPAND_MULTI_MAX];  // nullable: the scan-tile sums of plen[d] (launch_expand_scan(..., tile_sums_ready = true))
   int n;
@@ -308,7 +405,7 @@ __global__ __launch_bounds__(256) void expand_prepare_multi_kernel(const int64_t
 #pragma unroll
           for (int d = 0; d < N; ++d) {
             const int32_t len = (int32_t)(v[q][N + d] - v[q][d]);
-            a.pstart[d][p] = (int64_t)v[q][d];
+            a.pstart[d][p] = v[q][d];
             a.plen[d][p] = len;
             sum[d] += (long long)len;
           }
@@ -335,7 +432,7 @@ __global__ __launch_bounds__(256) void expand_prepare_multi_kernel(const int64_t
 }
 // pstart[d][cap], plen[d][cap] for n <= EXPAND_MULTI_MAX event types (every B must hold fewer than 2^32 entries); T: (n_rows_b + 1) * n words of 32 bits
 hipError_t launch_expand_prepare_multi(hipStream_t st, int n_cu, const int64_t* a_col_ptr, int32_t n_items_a, const int32_t* a_row_idx, int n,
-                                       const int64_t* const* b_row_ptr, int64_t n_rows_b, int64_t cap, int64_t* const* pstart, int32_t* const* plen, void* T,
+                                       const int64_t* const* b_row_ptr, int64_t n_rows_b, int64_t cap, unsigned* const* pstart, int32_t* const* plen, void* T,
                                        int64_t* const* tsum) {
   if (n < 1 || n > EXPAND_MULTI_MAX) return hipErrorInvalidValue;
   if (cap <= 0) return hipSuccess;
@@ -370,26 +467,38 @@ hipError_t launch_expand_prepare_multi(hipStream_t st, int n_cu, const int64_t* 
 // wp = exclusive prefix of plen over cap entries (the second half of launch_expand_prepare, for lengths produced by the multi form)
 // tile_sums_ready: tile_sums already holds the sums of plen's scan tiles (expand_prepare_multi left them): the reduce pass is skipped
 hipError_t launch_expand_scan(hipStream_t st, const int64_t* a_col_ptr, int32_t n_items_a, const int32_t* plen, int64_t cap, int64_t* wp, int64_t* tile_sums,
-                              bool tile_sums_ready) {
-  return launch_scan(st, LoadI32{plen}, cap, wp, tile_sums, a_col_ptr + n_items_a, tile_sums_ready);
+                              bool tile_sums_ready, const unsigned* pstart32, int64_t* pstart64, ExpandForm form) {
+  hipError_t e = hipMemsetAsync(form.word, 0, sizeof(int32_t), st);  // (the multi form's starts are always 32-bit ones)
+  if (e != hipSuccess) return e;
+  return expand_scan(st, plen, cap, wp, tile_sums, a_col_ptr + n_items_a, tile_sums_ready, pstart32, pstart64, form);
 }
 
+// A row's pairs, in 64 bits whatever the form of the prefix.  Narrow form: W(p) = base + ((low word of W(p)) - (low word of base)), base = the scan's
+// exclusive prefix of p's tile -- exact because no tile's sum reaches 2^32 (FORM_TILE otherwise: the prefix is a wide one).
+__device__ __forceinline__ int64_t work_prefix_at(const int64_t* __restrict__ wp, const int64_t* __restrict__ tile_sums, bool narrow, int64_t p) {
+  if (!narrow) return wp[p];
+  const int64_t base = tile_sums[p / SCAN_TILE];
+  return base + (int64_t)(unsigned)(reinterpret_cast<const unsigned*>(wp)[p] - (unsigned)base);
+}
 __global__ __launch_bounds__(256) void row_work_kernel(int32_t item_lo, int32_t item_hi, const int64_t* __restrict__ a_cp,
-                                                       const int64_t* __restrict__ wp, int64_t* __restrict__ work) {
+                                                       const int64_t* __restrict__ wp, const int64_t* __restrict__ tile_sums, const int32_t* __restrict__ form,
+                                                       int64_t* __restrict__ work) {
   const int64_t n = (int64_t)item_hi - item_lo;
+  const bool narrow = *form == 0;  // grid-uniform
   for (int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x; t < n; t += (int64_t)gridDim.x * 256) {
     const int64_t i = item_lo + t;
-    work[t] = wp[a_cp[i + 1]] - wp[a_cp[i]];
+    work[t] = work_prefix_at(wp, tile_sums, narrow, a_cp[i + 1]) - work_prefix_at(wp, tile_sums, narrow, a_cp[i]);
   }
 }
 
-hipError_t launch_row_work(hipStream_t st, int n_cu, int32_t item_lo, int32_t item_hi, const int64_t* a_col_ptr, const int64_t* wp, int64_t* work) {
+hipError_t launch_row_work(hipStream_t st, int n_cu, int32_t item_lo, int32_t item_hi, const int64_t* a_col_ptr, const int64_t* wp, const int64_t* tile_sums,
+                           const int32_t* form, int64_t* work) {
   const int64_t n = (int64_t)item_hi - item_lo;
   if (n <= 0) return hipSuccess;
   int64_t blocks = (n + 255) / 256;
   const int64_t cap = (int64_t)n_cu * 8;
   if (blocks > cap) blocks = cap;
-  hipLaunchKernelGGL(row_work_kernel, dim3((unsigned)blocks), dim3(256), 0, st, item_lo, item_hi, a_col_ptr, wp, work);
+  hipLaunchKernelGGL(row_work_kernel, dim3((unsigned)blocks), dim3(256), 0, st, item_lo, item_hi, a_col_ptr, wp, tile_sums, form, work);
   return hipGetLastError();
 }
 

@@ -40,21 +40,43 @@ constexpr int32_t DBG_SELECT_DELAY = 131072;        // test hook: the first wave
 constexpr int32_t DBG_UNPACKED_COUNTS = 1048576;    // B' travels as plain columns, the row kernels gather the counts
 constexpr int32_t DBG_ROW_KERNELS = DBG_GATHER_ONLY | DBG_NO_LLR | DBG_NO_TOPK | DBG_NO_SELECT | DBG_NO_RANK | DBG_NO_COUNT_GATHER | DBG_SELECT_DELAY;
 
+// The form of a build's expand tables, decided on the device by the scan of the work prefix (launch_expand_prepare / launch_expand_scan).
+// *word == 0: narrow.  Otherwise wide, and the bits say why.
+constexpr int32_t FORM_WIDE = 1;        // set with every other bit
+constexpr int32_t FORM_PS64 = 2;        // B' holds 2^32 entries or more (or no 32-bit row pointers were made): expand_prepare wrote pstart64 itself
+constexpr int32_t FORM_TILE = 4;        // a scan tile's sum reached `limit`: the 64-bit prefix cannot be rebuilt from tile bases + low words
+constexpr int32_t FORM_PACK = 8;        // *pack_bad != 0: the plain instantiations run, and they read wide tables
+constexpr int32_t FORM_HOST = 16;       // the host asked for the plain instantiations (no packed B', or the DBG ones)
+constexpr unsigned long long NARROW_LIMIT = 1ull << 32;
+struct ExpandForm {
+  int32_t* word;               // [1]
+  const int32_t* pack_bad;     // nullable: the verdict of launch_pack_counts, final on the stream by the time the scan runs
+  int32_t host_wide;           // 1: FORM_HOST
+  int32_t host_narrow;         // 1: the host knows every condition of the narrow form holds (cco_rows_impl): the word is set to 0 without the device-side tests
+  unsigned long long limit;    // NARROW_LIMIT in production; a test lowers it to drive the wide form at toy size
+  long long seed;              // 0 in production: the prefix starts here (a test starts it just below 2^32, so that toy rows straddle the wrap of the narrow form)
+};
+
 struct CcoArgs {
   // row lists per bin
   const int32_t* bin_rows;   // item ids grouped by bin
   const int32_t* bin_off;    // [BIN_OFF_LEN] offsets into bin_rows
   // matrices
   const int64_t* a_col_ptr;  // CSC of A': users of item i are entries [a_col_ptr[i], a_col_ptr[i+1])
-  const int64_t* pstart;     // per CSC entry: start of that user's B' row in b_col_idx
-  const int64_t* wp;         // per CSC entry (+1): exclusive prefix of B' row lengths over the CSC
+  // The expand tables come in two forms; *form (ExpandForm) names the one this build holds, and with it the instantiation whose turn it is:
+  //   narrow (*form == 0, the PK instantiations): pstart32[p] and the work prefix as 32-bit words modulo 2^32 (wp read as unsigned[cap + 1])
+  //   wide   (*form != 0, the plain ones):        pstart64[p] and the work prefix as int64[cap + 1]
+  // (pstart64 and work are appended at the end: the fields ahead of them keep the offsets they had)
+  const unsigned* pstart32;  // per CSC entry: start of that user's B' row in b_col_idx
+  const int64_t* wp;         // per CSC entry (+1): exclusive prefix of B' row lengths over the CSC (a row kernel only ever takes differences inside one item row)
   const int32_t* b_col_idx;
   // Round 6: B' with the column's post-sampling count riding in the spare bits of the column word -- word = col | cB << (32 - count_bits) -- so that a
   // candidate's cB arrives with the pair that claims its accumulator slot instead of through one scattered 2-byte gather per candidate (more than half
-  // of the SpGEMM classes' line fills: profiles/r06_fetch_by_phase.txt).  Nullable; used while *pack_bad == 0 (every count fits its 32 - key bits).
+  // of the SpGEMM classes' line fills: profiles/r06_fetch_by_phase.txt).  Nullable; used while *form == 0 (every count fits its 32 - key bits -- the
+  // pack verdict is folded into the form word -- and the expand tables are narrow).
   const int32_t* b_packed;
-  const int32_t* pack_bad;   // [1] counts that do not fit the spare bits (then b_col_idx + the count gather serve the build)
-  int32_t pk_known;          // 1: the HOST knows b_packed is good (a sharded build learns it with the shard sizes): pack_bad is not read, one instantiation is launched
+  const int32_t* form;       // [1] see ExpandForm
+  int32_t pk_known;          // 1: the HOST knows the verdict -- packed words that are good AND narrow tables (cco_rows_impl): *form is not read, one instantiation is launched
   uint32_t b_col_mask;       // b_col_idx[e] & b_col_mask = the column (0xffffffff unless b_col_idx itself holds packed words: the rows a sharded build received)
   const int32_t* cnt_a;
   const int32_t* cnt_b;
@@ -88,6 +110,8 @@ struct CcoArgs {
   unsigned long long* g_cand_key;  // [GLOBAL_BIN_BLOCKS][n_cols_b]
   int32_t* g_cand_col;       // [GLOBAL_BIN_BLOCKS][n_cols_b]
   int32_t g_blocks;          // > 0: bin 6 runs on the dense global-accumulator kernel with this many resident blocks; 0: multi-pass LDS class
+  const int64_t* pstart64;   // the wide form's starts
+  const int64_t* work;       // [item_hi - item_lo] the rows' pairs in full (launch_row_work): what the multi-pass class sizes its passes by
 };
 
 hipError_t launch_column_counts(hipStream_t st, int n_cu, const int32_t* col_idx, int64_t nnz, int32_t n_cols, int32_t* counts);
@@ -189,15 +213,18 @@ hipError_t launch_narrow_counts(hipStream_t st, int n_cu, const int32_t* counts,
 // pstart[cap], plen[cap] (scratch), wp[cap + 1]; cap >= nnz(A'); tile_sums scratch as for scans over cap elements
 hipError_t launch_expand_prepare(hipStream_t st, int n_cu, const int64_t* a_col_ptr, int32_t n_items_a, const int32_t* a_row_idx,
                                  const int64_t* b_row_ptr, unsigned* b_rp32_scratch /* nullable: n_rows_b + 1 words */, int64_t n_rows_b, int64_t cap,
-                                 int64_t* pstart, int32_t* plen, int64_t* wp, int64_t* tile_sums);
+                                 unsigned* pstart32, int64_t* pstart64, int32_t* plen, int64_t* wp, int64_t* tile_sums, ExpandForm form);
 // the same for up to EXPAND_MULTI_MAX event types with ONE gather per CSC entry: T = scratch of n_rows_b * n * 8 bytes
 constexpr int EXPAND_MULTI_MAX = 8;
 hipError_t launch_expand_prepare_multi(hipStream_t st, int n_cu, const int64_t* a_col_ptr, int32_t n_items_a, const int32_t* a_row_idx, int n,
-                                       const int64_t* const* b_row_ptr, int64_t n_rows_b, int64_t cap, int64_t* const* pstart, int32_t* const* plen, void* T,
+                                       const int64_t* const* b_row_ptr, int64_t n_rows_b, int64_t cap, unsigned* const* pstart, int32_t* const* plen, void* T,
                                        int64_t* const* tsum /* nullable; tsum[d]: ceil(cap / 2048) + 2 words: the scan-tile sums of plen[d] */);
+// (pstart32: the starts the multi form left; pstart64: cap words of scratch they are widened into when the verdict is the wide form)
 hipError_t launch_expand_scan(hipStream_t st, const int64_t* a_col_ptr, int32_t n_items_a, const int32_t* plen, int64_t cap, int64_t* wp, int64_t* tile_sums,
-                              bool tile_sums_ready = false);
-hipError_t launch_row_work(hipStream_t st, int n_cu, int32_t item_lo, int32_t item_hi, const int64_t* a_col_ptr, const int64_t* wp, int64_t* work);
+                              bool tile_sums_ready, const unsigned* pstart32, int64_t* pstart64, ExpandForm form);
+// wp / tile_sums / form as the expand scan left them: in the narrow form a row's 64-bit work is rebuilt from the scan's tile bases and the low words
+hipError_t launch_row_work(hipStream_t st, int n_cu, int32_t item_lo, int32_t item_hi, const int64_t* a_col_ptr, const int64_t* wp, const int64_t* tile_sums,
+                           const int32_t* form, int64_t* work);
 
 // binning: tile_counts scratch [(ceil(n/BIN_TILE)+1) * BIN_COLS_HOST] int64;
 // bin_off[BIN_OFF_LEN] int32, bin_rows[n] int32, stats[STATS_LEN] int64.

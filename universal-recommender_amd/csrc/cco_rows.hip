@@ -601,13 +601,18 @@ constexpr int URCCO_G_CU = 2;
 // launch it); the production instantiation carries neither their branches nor the scalar register a.debug would occupy -- at eight waves
 // per SIMD a wave has 78 scalar registers and the one-wave class spilled 128 of them to vector lanes (round 5: 69 after this and the
 // single-check LLR).
-// PK: the instantiation for a B' with the columns' counts aboard (CcoArgs::b_packed).  Whether the counts fit is known on the DEVICE only (*pack_bad), so
+// PK: the instantiation for a B' with the columns' counts aboard (CcoArgs::b_packed).  Whether the counts fit is known on the DEVICE only (it is part of *form), so
 // the launcher enqueues both instantiations and the one whose turn it is not returns at once -- the price of keeping the other form's registers (the count
 // gather's pointers, the word masks as run-time values) out of each: as one kernel with a run-time switch the 256-thread class spilled and the 512-thread
 // class lost a wave per SIMD.
+template <bool NARROW> struct PStart { typedef int64_t type; };
+template <> struct PStart<true> { typedef unsigned type; };
 template <int T, int E, int U, bool MP = false, bool DBG = false, bool PK = false>
 __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T == 256 && E == 4096 ? URCCO_OCC_BS : (T == 512 ? 4 : 1)))) void cco_rows_kernel(CcoArgs a, int bin) {
-  if ((a.b_packed != nullptr && (a.pk_known != 0 || *a.pack_bad == 0)) != PK) return;  // grid-uniform
+  // (the same verdict names the form of the expand tables -- CcoArgs::form: this instantiation reads the narrow ones, the plain one the wide ones)
+  if ((a.b_packed != nullptr && (a.pk_known != 0 || *a.form == 0)) != PK) return;  // grid-uniform
+  using PS = typename PStart<PK>::type;  // a start of a B' row: 32 bits in the narrow form
+  constexpr int WS = PK ? 1 : 2;         // words between two entries of the work prefix
   const int dbg = DBG ? a.debug : 0;
   // the arguments the row loop's inner loops use, each in scalar registers of its own (URCCO_OWN_SGPRS)
   // B' with the columns' counts aboard while every count fits (CcoArgs::b_packed), else the plain column indices and the count gather (wave-uniform)
@@ -682,7 +687,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
   unsigned* tab = s_tab + team * E;
   unsigned* cand = tab + SH;  // insert phase: the row's candidate list -- (slot, column count) of every claimed slot, in the order the claims were made
   unsigned long long* share = s_share + (SHARE ? team * SHARE_WORDS : 0);
-  long long* ustart = SHARE ? reinterpret_cast<long long*>(share) : s_ustart + team * T;
+  PS* ustart = reinterpret_cast<PS*>(SHARE ? reinterpret_cast<long long*>(share) : s_ustart + team * T);  // (the region keeps its 64-bit size)
   unsigned* uoff = SHARE ? reinterpret_cast<unsigned*>(share + T) : s_uoff + team * (T + 1);
   unsigned* hist = SHARE ? reinterpret_cast<unsigned*>(share) : s_hist + team * NH * 128;
   unsigned* sel_res = s_selres + team * 4;
@@ -714,6 +719,9 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
   const int S = total_teams;
   auto pos_of = [&](int l) { return list_start + (l < list_n ? l : list_n - 1); };
   const unsigned* wp32 = reinterpret_cast<const unsigned*>(a.wp);  // low words: a chunk only uses differences between its own entries
+  const PS* pstart;  // (read off the argument block here: handing `a` to a helper by reference makes the compiler keep a copy of the block)
+  if constexpr (PK) pstart = a.pstart32;
+  else pstart = a.pstart64;
   const int lane3 = lane < 3 ? lane : 2;
   int idv = a.bin_rows[pos_of(li + lane3 * S)];  // lanes 0, 1, 2: ids of this row and the next two
   int64_t cs_c, ce_c;                             // this row's CSC bounds (scalars)
@@ -727,14 +735,14 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
   }
   // first-chunk operands of the row about to be processed (low words of the work prefix)
   unsigned pf_w0, pf_w1, pf_wp;
-  int64_t pf_start;
+  PS pf_start;
   {
     const int64_t c1 = cs_c + T < ce_c ? cs_c + T : ce_c;
     const int64_t pl = cs_c + tl < c1 ? cs_c + tl : c1 - 1;
-    pf_w0 = wp32[2 * cs_c];
-    pf_w1 = wp32[2 * c1];
-    pf_wp = wp32[2 * pl];
-    pf_start = a.pstart[pl];
+    pf_w0 = wp32[WS * cs_c];
+    pf_w1 = wp32[WS * c1];
+    pf_wp = wp32[WS * pl];
+    pf_start = pstart[pl];
   }
   URCCO_SETTLE(idv); URCCO_SETTLE(bnd_b); URCCO_SETTLE(pf_w0); URCCO_SETTLE(pf_w1); URCCO_SETTLE(pf_wp); URCCO_SETTLE(pf_start);
   int64_t cs_n = 0, ce_n = 0, bnd_c = 0;  // next row's bounds as scalars / the bounds two rows ahead in flight: rotated by the loop's increment
@@ -747,7 +755,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
     // this row's first-chunk operands leave their registers ...
     const unsigned row_w0 = uni(pf_w0), row_w1 = uni(pf_w1);
     const unsigned my_wp = pf_wp;
-    const int64_t my_start = pf_start;
+    const PS my_start = pf_start;
     // ... and the rows ahead take them
     int lz = lane;
     URCCO_OPAQUE(lz);  // (what derives from the lane here is recomputed per row: kept across the row loop it was spilled at 64 registers, and a scratch reload at
@@ -757,16 +765,16 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
     if (!MP) {  // (the multi-pass rows re-read every chunk once per pass: no prefetched first chunk)
       const int64_t c1 = cs_n + T < ce_n ? cs_n + T : ce_n;
       const int64_t pl = cs_n + tl < c1 ? cs_n + tl : c1 - 1;
-      pf_w0 = wp32[2 * cs_n];
-      pf_w1 = wp32[2 * c1];
-      pf_wp = wp32[2 * pl];
-      pf_start = a.pstart[pl];
+      pf_w0 = wp32[WS * cs_n];
+      pf_w1 = wp32[WS * c1];
+      pf_wp = wp32[WS * pl];
+      pf_start = pstart[pl];
     }
     // MP: number of passes 2^mp_s, current pass mp_q, entries of the running top k and which of its two buffers is current
     int mp_s = 0;
     unsigned mp_q = 0u, n_run = 0u, run_cur = 0u;
     if (MP) {
-      const long long w_row = (long long)(uni(a.wp[ce]) - uni(a.wp[cs]));
+      const long long w_row = (long long)uni(a.work[i - a.item_lo]);  // (the prefix itself may be the narrow one: differences modulo 2^32)
       const long long ca_row = a.cnt_a[i];
       const long long dd = w_row < (long long)a.n_cols_b ? w_row : (long long)a.n_cols_b;
       const long long cap = ((long long)E - 3ll * a.k - 2ll) / 3ll;  // distinct columns a pass may hold (packed counts + keys + survivors)
@@ -799,12 +807,12 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
     for (int64_t c0 = cs; c0 < ce; c0 += T) {  // team-uniform
       const int64_t c1 = c0 + T < ce ? c0 + T : ce;
       const bool pre = !MP && c0 == cs;  // the first chunk's operands were prefetched
-      const unsigned w0 = pre ? row_w0 : uni(wp32[2 * c0]);  // low words: the differences below are < 2^32
-      const unsigned total = (pre ? row_w1 : uni(wp32[2 * c1])) - w0;
+      const unsigned w0 = pre ? row_w0 : uni(wp32[WS * c0]);  // low words: the differences below are < 2^32
+      const unsigned total = (pre ? row_w1 : uni(wp32[WS * c1])) - w0;
       const int64_t p = c0 + tl;
       if (p < c1) {
-        ustart[tl] = pre ? my_start : a.pstart[p];
-        uoff[tl] = (pre ? my_wp : wp32[2 * p]) - w0;
+        ustart[tl] = pre ? my_start : pstart[p];
+        uoff[tl] = (pre ? my_wp : wp32[WS * p]) - w0;
       } else {
         uoff[tl] = total;
       }
@@ -830,7 +838,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
             lo = gt ? lo : mid + 1;
           }
           o = lo - 1;
-          pos = ustart[o] + (first - uoff[o]);
+          pos = (int64_t)ustart[o] + (first - uoff[o]);
           uend = uoff[o + 1];
         }
         // `per` is team-uniform: the loop counter and its bound live in the scalar unit.  G column gathers are issued
@@ -846,7 +854,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
             if (on[q]) {
               if (t >= uend) {  // next user with a non-empty B' row
                 do { ++o; } while (uoff[o + 1] <= t);
-                pos = ustart[o];
+                pos = (int64_t)ustart[o];
                 uend = uoff[o + 1];
               }
               jj[q] = (unsigned)b_col_idx[pos++];
@@ -1437,9 +1445,13 @@ __device__ __forceinline__ unsigned seg_max_popc(unsigned long long m) {
   return best;
 }
 
+__device__ __forceinline__ unsigned gather_start(unsigned v, unsigned src) { return wave_gather(v, src); }
+__device__ __forceinline__ int64_t gather_start(int64_t v, unsigned src) { return wave_gather64(v, src); }
 template <int L, bool DBG, bool PK = false>
 __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO - 2)) void cco_rows_micro_kernel(CcoArgs a) {
-  if ((a.b_packed != nullptr && (a.pk_known != 0 || *a.pack_bad == 0)) != PK) return;  // grid-uniform: the other instantiation's turn (see cco_rows_kernel)
+  if ((a.b_packed != nullptr && (a.pk_known != 0 || *a.form == 0)) != PK) return;  // grid-uniform: the other instantiation's turn (see cco_rows_kernel)
+  using PS = typename PStart<PK>::type;
+  constexpr int WS = PK ? 1 : 2;
   using G = MicroGeom<L>;
   constexpr int S = G::S;
   const int dbg = DBG ? a.debug : 0;
@@ -1447,7 +1459,9 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
   // VECTOR registers to scratch and ran 3 % slower, profiles/r05_sgpr_diet_variants_ab.log)
   const int32_t* bin_rows = a.bin_rows;
   const int64_t* a_col_ptr = a.a_col_ptr;
-  const int64_t* pstart = a.pstart;
+  const PS* pstart;  // (read off the argument block here: handing `a` to a helper by reference makes the compiler keep a copy of the block)
+  if constexpr (PK) pstart = a.pstart32;
+  else pstart = a.pstart64;
   // B' with the columns' counts aboard while every count fits (CcoArgs::b_packed): the lane that claims a column has the column's count in the
   // very word it inserted -- no gather; else the plain column indices and one scattered count gather per candidate (wave-uniform)
   constexpr bool packed = PK;
@@ -1509,7 +1523,7 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
   int64_t cs1 = a_col_ptr[i_n1], ce1 = a_col_ptr[i_n1 + 1];  // ... and CSC bounds
   // operands of the row about to be processed; wp[cs] is what the segment's first lane reads as its user's entry
   unsigned pf_w1, pf_wp;
-  int64_t pf_start;
+  PS pf_start;
   int pf_ca;  // as loaded: widened where it is used
   double pf_ent;
   int n_cur;  // users of the row about to be processed
@@ -1517,8 +1531,8 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
     const int64_t cs0 = a_col_ptr[i_cur], ce0 = a_col_ptr[i_cur + 1];
     n_cur = (int)(ce0 - cs0);
     const int64_t pl = sl < n_cur ? cs0 + sl : ce0 - 1;
-    pf_w1 = wp32[2 * ce0];
-    pf_wp = wp32[2 * pl];
+    pf_w1 = wp32[WS * ce0];
+    pf_wp = wp32[WS * pl];
     pf_start = pstart[pl];
     pf_ca = cnt_a[i_cur];
     pf_ent = ent_a[i_cur];
@@ -1538,7 +1552,7 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
     const bool owns_user = live && sl < n_cur;
     const long long ca = (long long)pf_ca;
     const double row_entropy = pf_ent;
-    const int64_t my_start = owns_user ? pf_start : 0;
+    const PS my_start = owns_user ? pf_start : (PS)0;
     const unsigned my_off = owns_user ? pf_wp - w0 : total;
     // ... and the rows ahead take them: id of row + 3, bounds of row + 2, operands of row + 1
     int i_n3 = row_at(li + 3 * stride);
@@ -1546,8 +1560,8 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
     n_cur = (int)(ce1 - cs1);
     {
       const int64_t pl = sl < n_cur ? cs1 + sl : ce1 - 1;
-      pf_w1 = wp32[2 * ce1];
-      pf_wp = wp32[2 * pl];
+      pf_w1 = wp32[WS * ce1];
+      pf_wp = wp32[WS * pl];
       pf_start = pstart[pl];
       pf_ca = cnt_a[i_n1];
       pf_ent = ent_a[i_n1];
@@ -1559,12 +1573,13 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
     if (owns_user) atomicMax(&marks[my_off], (unsigned)sl);  // my_off <= total <= L: marks has L + 2 words
     wave_sync();
     const unsigned o = seg_inclusive_max<L>(marks[sl]);
-    const int64_t base_o = wave_gather64(my_start - (int64_t)my_off, (unsigned)(seg * L) + o);  // B' position of pair p of user o: base + p
+    // B' position of pair p of user o: base + p (narrow form: in 32-bit wrap-around arithmetic -- base alone may be "negative", base + p is a position below 2^32)
+    const PS base_o = gather_start(my_start - (PS)my_off, (unsigned)(seg * L) + o);
     // ---- insert; the claiming lane owns the candidate
     unsigned slot = 0xffffffffu;
     unsigned jj = 0u;  // this lane's B' word: the column, and (packed) the column's count
     if ((unsigned)sl < total) {
-      jj = (unsigned)b_col_idx[base_o + sl];
+      jj = (unsigned)b_col_idx[base_o + (PS)sl];
       if (!(dbg & DBG_GATHER_ONLY)) {
         bool ok;
         slot = tab_insert_claim(tab, (jj & colmask) + 1u, cb, (unsigned)(G::TW - 1), 32 - G::LOG2TW, ident, &ok);
@@ -1693,6 +1708,11 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
 constexpr int GB_THREADS = 1024;
 constexpr int GSEL_K = 1024;  // survivors held in LDS by the radix-select form of the top-k
 
+__device__ __forceinline__ int64_t g_start(const unsigned* ps32, const int64_t* ps64, bool nar, int64_t p) { return nar ? (int64_t)ps32[p] : ps64[p]; }
+__device__ __forceinline__ int64_t g_len(const int64_t* wp, bool nar, int64_t p) {
+  const unsigned* w = reinterpret_cast<const unsigned*>(wp);
+  return nar ? (int64_t)(unsigned)(w[p + 1] - w[p]) : wp[p + 1] - wp[p];
+}
 __global__ __launch_bounds__(GB_THREADS) void cco_rows_global_kernel(CcoArgs a) {
   constexpr int NW = GB_THREADS / WAVE;
   __shared__ unsigned long long s_pkey[2][NW];
@@ -1713,19 +1733,20 @@ __global__ __launch_bounds__(GB_THREADS) void cco_rows_global_kernel(CcoArgs a) 
   const int G = 1 << a.g_log2;
   const int grp = threadIdx.x >> a.g_log2, gl = threadIdx.x & (G - 1), ngrp = GB_THREADS >> a.g_log2;
   const double xlx_n = *a.xlx_n;
+  const bool nar = *a.form == 0;  // the form of the expand tables (one body: these rows are rare and heavy)
   for (int li = blockIdx.x; li < list_n; li += gridDim.x) {  // block-uniform
     const int i = a.bin_rows[list_start + li];
     const int64_t cs = a.a_col_ptr[i], ce = a.a_col_ptr[i + 1];
     if (threadIdx.x == 0) s_ncand = 0;
     for (int64_t p = cs + grp; p < ce; p += ngrp) {
-      const int64_t s = a.pstart[p], e = s + (a.wp[p + 1] - a.wp[p]);
+      const int64_t s = g_start(a.pstart32, a.pstart64, nar, p), e = s + g_len(a.wp, nar, p);
       for (int64_t q = s + gl; q < e; q += G) atomicAdd(&cnt[(unsigned)a.b_col_idx[q] & a.b_col_mask], 1);
     }
     __syncthreads();
     const long long ca = a.cnt_a[i];
     const double row_entropy = a.ent_a[i];
     for (int64_t p = cs + grp; p < ce; p += ngrp) {
-      const int64_t s = a.pstart[p], e = s + (a.wp[p + 1] - a.wp[p]);
+      const int64_t s = g_start(a.pstart32, a.pstart64, nar, p), e = s + g_len(a.wp, nar, p);
       for (int64_t q = s + gl; q < e; q += G) {
         const int j = (int)((unsigned)a.b_col_idx[q] & a.b_col_mask);
         const long long k11 = atomicExch(&cnt[j], 0);  // exactly one lane claims (and clears) each column
@@ -1924,7 +1945,7 @@ hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, in
   // once.  The DBG instantiations exist for the plain form only (the ablation switches price the count gather among other things).
   CcoArgs plain = args;
   plain.b_packed = nullptr;
-  const bool both = args.b_packed != nullptr && !dbgk && !args.pk_known;  // (pk_known: the host knows the counts are aboard -- only that instantiation)
+  const bool both = args.b_packed != nullptr && !dbgk && !args.pk_known;  // (pk_known: the host knows the verdict -- packed and narrow -- only that instantiation)
 #define URCCO_LAUNCH_ROWS(TT, EE, UU, MPF, GRID, BLK, BINARG)                                                                      \
   do {                                                                                                                           \
     if (dbgk) hipLaunchKernelGGL((cco_rows_kernel<TT, EE, UU, MPF, true, false>), GRID, dim3(BLK), 0, st, plain, BINARG);          \

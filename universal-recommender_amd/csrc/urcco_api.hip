@@ -181,6 +181,7 @@ void urcco_session_destroy(urcco_session* s) {
   if (s->arena) (void)hipFree(s->arena);
   if (s->xlx_tab) (void)hipFree(s->xlx_tab);
   if (s->xlx_hi) (void)hipFree(s->xlx_hi);
+  if (s->form_word) (void)hipFree(s->form_word);
   if (s->g_counts) { (void)hipFree(s->g_counts); (void)hipFree(s->g_cand_key); (void)hipFree(s->g_cand_col); }
   s->collect();
   for (hipEvent_t e : s->free_events) (void)hipEventDestroy(e);
@@ -197,6 +198,21 @@ int urcco_session_synchronize(urcco_session* s) {
 int urcco_session_set_debug(urcco_session* s, int32_t flags) {
   if (!s) return fail(URCCO_BAD_ARG, "session is NULL");
   s->debug = flags;
+  return URCCO_OK;
+}
+
+int urcco_session_set_expand_test(urcco_session* s, int64_t limit, int64_t prefix_seed) {
+  if (!s || limit < 0 || prefix_seed < 0) return fail(URCCO_BAD_ARG, "urcco_session_set_expand_test: bad argument");
+  s->narrow_limit = limit == 0 ? urcco::NARROW_LIMIT : (unsigned long long)limit;
+  s->prefix_seed = prefix_seed;
+  return URCCO_OK;
+}
+
+int urcco_session_expand_form(urcco_session* s, int32_t* form_host) {
+  if (!s || !form_host) return fail(URCCO_BAD_ARG, "urcco_session_expand_form: bad argument");
+  if (!s->form_word || !s->form_valid) return fail(URCCO_BAD_ARG, "urcco_session_expand_form: no rows were built on this session");
+  HIPC(hipMemcpyAsync(form_host, s->form_word, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  HIPC(hipStreamSynchronize(s->stream));
   return URCCO_OK;
 }
 
@@ -325,15 +341,19 @@ int urcco_dev_row_work(urcco_session* s, int32_t item_lo, int32_t item_hi, int32
     return fail(URCCO_BAD_ARG, "urcco_dev_row_work: bad argument");
   const int64_t cap = nnz_a_bound;
   const int64_t n_tiles = (cap + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
-  URC(s->reserve(urcco_session::need((size_t)cap, 8) + urcco_session::need((size_t)cap, 4) + urcco_session::need((size_t)cap + 1, 8) +
-                 urcco_session::need((size_t)n_tiles + 2, 8)));
-  int64_t* pstart = s->take<int64_t>((size_t)cap);
+  URC(s->reserve(urcco_session::need((size_t)cap, 4) + urcco_session::need((size_t)cap + 1, 8) + urcco_session::need((size_t)n_tiles + 2, 8)));
+  if (!s->form_word) HIPC(hipMalloc((void**)&s->form_word, sizeof(int32_t)));
+  s->form_valid = false;
   int32_t* plen = s->take<int32_t>((size_t)cap);
   int64_t* wp = s->take<int64_t>((size_t)cap + 1);
   int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
+  int32_t* form = s->form_word;
   s->begin(URCCO_STAGE_ROW_WORK);
-  HIPC(urcco::launch_expand_prepare(s->stream, s->n_cu, a_col_ptr, n_items_a, a_row_idx, b_row_ptr, nullptr, 0, cap, pstart, plen, wp, tile_sums));
-  HIPC(urcco::launch_row_work(s->stream, s->n_cu, item_lo, item_hi, a_col_ptr, wp, work));
+  // (no row kernel follows: the lengths and their prefix alone, no starts -- the prefix in the narrow form unless a tile sum forbids it)
+  HIPC(urcco::launch_expand_prepare(s->stream, s->n_cu, a_col_ptr, n_items_a, a_row_idx, b_row_ptr, nullptr, 0, cap, nullptr, nullptr, plen, wp, tile_sums,
+                                    urcco::ExpandForm{form, nullptr, 0, 0, s->narrow_limit, s->prefix_seed}));
+  HIPC(urcco::launch_row_work(s->stream, s->n_cu, item_lo, item_hi, a_col_ptr, wp, tile_sums, form, work));
+  s->form_valid = true;
   s->end();
   return URCCO_OK;
 }
@@ -415,7 +435,7 @@ int partition_dev(urcco_session* s, int32_t n_items, const int64_t* work, int32_
 int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_items_a, const int64_t* a_col_ptr, const int32_t* a_row_idx, int64_t nnz_a_bound,
                   const int64_t* b_row_ptr, const int32_t* b_col_idx, int32_t n_cols_b, const int32_t* counts_a, const int32_t* counts_b, int64_t n_users,
                   int32_t exclude_self, int32_t k, int32_t has_min_llr, double min_llr, int32_t* out_count, int32_t* out_idx, double* out_llr, int64_t* stats_dev,
-                  const int64_t* pre_pstart, const int32_t* pre_plen, int64_t* pre_tile_sums, const int32_t* b_packed, const int32_t* pack_bad, bool pk_known) {
+                  const unsigned* pre_pstart, const int32_t* pre_plen, int64_t* pre_tile_sums, const int32_t* b_packed, const int32_t* pack_bad, bool pk_known, int64_t b_nnz_bound) {
   if (!s || item_lo < 0 || item_hi < item_lo || item_hi > n_items_a || n_cols_b < 0 || n_users < 0 || nnz_a_bound < 0 || !a_col_ptr || !b_row_ptr)
     return fail(URCCO_BAD_ARG, "urcco_dev_cco_rows: bad argument");
   if (k <= 0) return fail(URCCO_BAD_ARG, "maxInterestingElements must be positive, got %d", k);
@@ -451,16 +471,22 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
   const int64_t n_tiles = ((int64_t)n + urcco::BIN_TILE - 1) / urcco::BIN_TILE;
   const int64_t cap = nnz_a_bound;
   const int64_t p_tiles = (cap + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
-  URC(s->reserve(urcco_session::need((size_t)cap, 8) + urcco_session::need((size_t)cap, 4) + urcco_session::need((size_t)cap + 1, 8) +
+  if (!s->form_word) HIPC(hipMalloc((void**)&s->form_word, sizeof(int32_t)));
+  s->form_valid = false;
+  URC(s->reserve(urcco_session::need((size_t)cap, 8) + urcco_session::need((size_t)cap, 4) + (pre_pstart ? 0 : urcco_session::need((size_t)cap, 4)) + urcco_session::need((size_t)cap + 1, 8) +
                  urcco_session::need((size_t)p_tiles + 2, 8) +
                  urcco_session::need((size_t)n, 8) + urcco_session::need((size_t)(n_tiles + 1) * urcco::BIN_COLS_HOST, 8) +
                  urcco_session::need(urcco::BIN_OFF_LEN, 4) + urcco_session::need((size_t)n, 4) + urcco_session::need((size_t)n_items_a, 8) +
                  urcco_session::need((size_t)n_cols_b, 2) + urcco_session::need(1, 4) + urcco_session::need(urcco::CAND_SLOTS, 8) + urcco_session::need(1, 8) + urcco_session::need(URCCO_STATS_LEN, 8) +
                  urcco_session::need((size_t)n_users + 1, 4)));
-  int64_t* own_pstart = s->take<int64_t>((size_t)cap);
+  // the expand tables in the narrow form (32-bit starts; the work prefix as 32-bit words in the front half of wp) or, when the scan's verdict says so, in
+  // the wide one (pstart64; wp whole): cco_kernels.h, ExpandForm.  pstart64 is touched by the wide form alone.
+  int64_t* pstart64 = s->take<int64_t>((size_t)cap);
+  unsigned* own_pstart = pre_pstart ? nullptr : s->take<unsigned>((size_t)cap);
   int32_t* own_plen = s->take<int32_t>((size_t)cap);
-  const int64_t* pstart = pre_pstart ? pre_pstart : own_pstart;
+  const unsigned* pstart32 = pre_pstart ? pre_pstart : own_pstart;
   int64_t* wp = s->take<int64_t>((size_t)cap + 1);
+  int32_t* form = s->form_word;  // (the session's own word, not arena scratch: urcco_session_expand_form reads it after the call)
   int64_t* p_tile_sums = s->take<int64_t>((size_t)p_tiles + 2);
   int64_t* work = s->take<int64_t>((size_t)n);
   int64_t* tile_counts = s->take<int64_t>((size_t)(n_tiles + 1) * urcco::BIN_COLS_HOST);
@@ -474,12 +500,25 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
   int64_t* stats = stats_dev ? stats_dev : s->take<int64_t>(URCCO_STATS_LEN);
   unsigned* b_rp32 = s->take<unsigned>((size_t)n_users + 1);
 
+  // DBG_UNPACKED_COUNTS: the count gather of rounds 1-5 (A/B, tests).  pk_known: b_col_idx itself holds packed words (the rows a sharded build received
+  // travelled with their counts aboard -- the host learnt with the shard sizes that every count fits): no plain copy exists, every reader masks
+  const int32_t* packed = pk_known ? b_col_idx : ((b_packed && pack_bad && !(s->debug & urcco::DBG_UNPACKED_COUNTS)) ? b_packed : nullptr);
+  // the plain instantiations are the only ones that will run (no packed B', or the DBG ones): they read the wide form
+  const bool host_wide = packed == nullptr || (s->debug & urcco::DBG_ROW_KERNELS) != 0;
+  // pk_known builds: the host can know the whole verdict.  B' holds fewer than 2^32 entries (the shard sizes), and a row of B' holds distinct columns, so no
+  // tile of 2048 lengths sums to more than 2048 * n_cols_b.  (maxElementsPerRow is no bound: the down-sampling keeps entries at a RATE.)  Then only the packed
+  // instantiation of every class is enqueued and the scan sets the word without its tests.
+  const bool narrow_known = pk_known && !host_wide && b_nnz_bound >= 0 && b_nnz_bound < ((int64_t)1 << 32) &&
+                            (unsigned long long)n_cols_b * (unsigned long long)urcco::SCAN_TILE < s->narrow_limit;
+  const urcco::ExpandForm ef{form, pk_known ? nullptr : pack_bad, host_wide ? 1 : 0, narrow_known ? 1 : 0, s->narrow_limit, s->prefix_seed};
+  int64_t* tile_sums = (pre_pstart && pre_plen && pre_tile_sums) ? pre_tile_sums : p_tile_sums;
   s->begin(URCCO_STAGE_ROW_WORK);
   if (pre_pstart && pre_plen)
-    HIPC(urcco::launch_expand_scan(s->stream, a_col_ptr, n_items_a, pre_plen, cap, wp, pre_tile_sums ? pre_tile_sums : p_tile_sums, pre_tile_sums != nullptr));
+    HIPC(urcco::launch_expand_scan(s->stream, a_col_ptr, n_items_a, pre_plen, cap, wp, tile_sums, pre_tile_sums != nullptr, pre_pstart, pstart64, ef));
   else
-    HIPC(urcco::launch_expand_prepare(s->stream, s->n_cu, a_col_ptr, n_items_a, a_row_idx, b_row_ptr, b_rp32, n_users, cap, own_pstart, own_plen, wp, p_tile_sums));
-  HIPC(urcco::launch_row_work(s->stream, s->n_cu, item_lo, item_hi, a_col_ptr, wp, work));
+    HIPC(urcco::launch_expand_prepare(s->stream, s->n_cu, a_col_ptr, n_items_a, a_row_idx, b_row_ptr, b_rp32, n_users, cap, own_pstart, pstart64, own_plen, wp, tile_sums, ef));
+  HIPC(urcco::launch_row_work(s->stream, s->n_cu, item_lo, item_hi, a_col_ptr, wp, tile_sums, form, work));
+  s->form_valid = true;
   s->end();
   s->begin(URCCO_STAGE_BINNING);
   HIPC(hipMemsetAsync(stats, 0, sizeof(int64_t) * URCCO_STATS_LEN, s->stream));
@@ -492,12 +531,8 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
 
   urcco::CcoArgs a;
   a.bin_rows = bin_rows; a.bin_off = bin_off;
-  a.a_col_ptr = a_col_ptr; a.pstart = pstart; a.wp = wp; a.b_col_idx = b_col_idx;
-  // DBG_UNPACKED_COUNTS: the count gather of rounds 1-5 (A/B, tests).  pk_known: b_col_idx itself holds packed words (the rows a sharded build received
-  // travelled with their counts aboard -- the host learnt with the shard sizes that every count fits): no plain copy exists, every reader masks
-  a.b_packed = pk_known ? b_col_idx : ((b_packed && pack_bad && !(s->debug & urcco::DBG_UNPACKED_COUNTS)) ? b_packed : nullptr);
-  a.pack_bad = pack_bad;
-  a.pk_known = pk_known ? 1 : 0;
+  a.a_col_ptr = a_col_ptr; a.pstart32 = pstart32; a.pstart64 = pstart64; a.wp = wp; a.form = form; a.work = work; a.b_col_idx = b_col_idx;
+  a.b_packed = packed; a.pk_known = narrow_known ? 1 : 0;
   a.b_col_mask = pk_known ? (key_bits >= 32 ? 0xffffffffu : (1u << key_bits) - 1u) : 0xffffffffu;
   a.cnt_a = counts_a; a.cnt_b = counts_b; a.ent_a = ent_a; a.cnt_b16 = cnt_b16; a.cnt16_bad = cnt16_bad; a.xlx_n = xlx_n; a.xlx_tab = s->xlx_tab; a.xlx_hi = s->xlx_hi; a.col_ent = s->xlx_hi + urcco::XLX_TABLE_HOST; a.debug = s->debug;
   a.n_users = n_users; a.n_cols_b = n_cols_b; a.item_lo = item_lo; a.exclude_self = exclude_self ? 1 : 0; a.k = k;
@@ -544,7 +579,7 @@ int pack_counts(urcco_session* s, const int64_t* b_row_ptr, int64_t n_rows_b, co
 // Expand preparation of n secondaries in one pass over the CSC of A' (cco_expand.hip, expand_prepare_multi): pstart[d] / plen[d] hold
 // cap entries each.  The interleaved (start, length) table lives in the session's arena for the duration of the launch.
 int expand_multi(urcco_session* s, int n, const int64_t* a_col_ptr, int32_t n_items_a, const int32_t* a_row_idx, int64_t cap, const int64_t* const* b_row_ptr,
-                 int64_t n_users, int64_t* const* pstart, int32_t* const* plen, int64_t* const* tile_sums) {
+                 int64_t n_users, unsigned* const* pstart, int32_t* const* plen, int64_t* const* tile_sums) {
   if (!s || n < 1 || n > urcco::EXPAND_MULTI_MAX || !a_col_ptr || cap < 0) return fail(URCCO_BAD_ARG, "expand_multi: bad argument");
   URC(s->reserve(urcco_session::need(((size_t)n_users + 2) * (size_t)n, 4) + 256));
   void* T = s->take<unsigned>(((size_t)n_users + 2) * (size_t)n);  // n_users + 1 records of n starts (+ one record of slack: the last user's 2 n-word read)

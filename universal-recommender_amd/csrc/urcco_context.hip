@@ -199,7 +199,7 @@ struct EvState {
     HIPC(hipHostGetDevicePointer((void**)&h_verr_dev, h_verr, 0));
     return URCCO_OK;
   }
-  DBuf<int64_t> pre_pstart;     // this event type's share of the fused expand preparation (builds with >= 2 secondaries)
+  DBuf<unsigned> pre_pstart;    // this event type's share of the fused expand preparation (builds with >= 2 secondaries)
   DBuf<int32_t> pre_plen;
   DBuf<int64_t> pre_tsum;       // ... and the scan-tile sums of pre_plen the fused pass leaves (the expand scan then skips its reduce pass)
   // row-filtered exchange: the shard's row lengths masked per destination [W][rows] (int32 / as they travel when 16 bits do), their
@@ -570,7 +570,7 @@ int stage_rows(DevState& D, EvState& E, EvState& A, int d, const DsParams& pa, c
   URC(cco_rows_impl(E.s, D.item_lo, D.item_hi, (int32_t)pa.n_cols, D.a_cp[D.par].p, D.a_ri[D.par].p, a_nnz_bound, E.b_rp, E.b_ci, (int32_t)p.n_cols,
                     post_of(D, 0).p, post_of(D, d).p, n_users, d == 0 ? 1 : 0, p.k, p.has_min_llr, p.min_llr, E.o_count.p, E.o_idx.p, E.o_llr.p, E.stats.p,
                     pre_expanded ? E.pre_pstart.p : nullptr, pre_expanded ? E.pre_plen.p : nullptr, pre_expanded ? E.pre_tsum.p : nullptr,
-                    E.b_pk_known ? nullptr : E.b_pk.p, E.b_pk_known ? nullptr : E.pk_bad.p, E.b_pk_known));
+                    E.b_pk_known ? nullptr : E.b_pk.p, E.b_pk_known ? nullptr : E.pk_bad.p, E.b_pk_known, E.b_nnz_bound));
   URC(urcco_dev_compact_indicators(E.s, n, p.k, E.o_count.p, E.o_idx.p, E.o_llr.p, E.c_rp.p, E.c_idx.p, E.c_llr.p));
   HIPC(hipEventRecord(E.ev_done, E.s->stream));
   HIPC(hipEventRecord(E.ev_cons[D.par], E.s->stream));
@@ -657,7 +657,7 @@ int build_single(urcco_context* c, DevState& D, const std::vector<Shard>& sh, co
     EvState& L = D.ev[1];
     if (L.s != A.s) HIPC(hipStreamWaitEvent(L.s->stream, D.a_ready, 0));
     std::vector<const int64_t*> rp((size_t)(n_ds - f0));
-    std::vector<int64_t*> ps((size_t)(n_ds - f0));
+    std::vector<unsigned*> ps((size_t)(n_ds - f0));
     std::vector<int32_t*> pl((size_t)(n_ds - f0));
     std::vector<int64_t*> ts((size_t)(n_ds - f0));
     for (int d = f0; d < n_ds; ++d) {
@@ -1251,7 +1251,7 @@ int build_sharded(urcco_context* c, const std::vector<std::vector<Shard>>& sh, c
       EvState& L = D.ev[1];
       if (L.s != D.ev[0].s) HIPC(hipStreamWaitEvent(L.s->stream, D.a_ready, 0));
       std::vector<const int64_t*> rp((size_t)n_ds - 1);
-      std::vector<int64_t*> pst((size_t)n_ds - 1);
+      std::vector<unsigned*> pst((size_t)n_ds - 1);
       std::vector<int32_t*> pl((size_t)n_ds - 1);
       std::vector<int64_t*> ts((size_t)n_ds - 1);
       for (int d = 1; d < n_ds; ++d) {

@@ -90,15 +90,16 @@ namespace urcco_detail {
 int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_items_a, const int64_t* a_col_ptr, const int32_t* a_row_idx, int64_t nnz_a_bound,
                   const int64_t* b_row_ptr, const int32_t* b_col_idx, int32_t n_cols_b, const int32_t* counts_a, const int32_t* counts_b, int64_t n_users,
                   int32_t exclude_self, int32_t k, int32_t has_min_llr, double min_llr, int32_t* out_count, int32_t* out_idx, double* out_llr, int64_t* stats_dev,
-                  const int64_t* pre_pstart, const int32_t* pre_plen, int64_t* pre_tile_sums = nullptr /* the scan-tile sums of pre_plen, left by expand_multi */,
+                  const unsigned* pre_pstart, const int32_t* pre_plen, int64_t* pre_tile_sums = nullptr /* the scan-tile sums of pre_plen, left by expand_multi */,
                   const int32_t* b_packed = nullptr /* B' with the columns' counts aboard (launch_pack_counts) ... */, const int32_t* pack_bad = nullptr /* ... and its verdict */,
-                  bool pk_known = false /* b_col_idx itself holds such words and the host knows they are good (sharded builds) */);
+                  bool pk_known = false /* b_col_idx itself holds such words and the host knows they are good (sharded builds) */,
+                  int64_t b_nnz_bound = -1 /* pk_known: an upper bound of B' entries, if the host has one (with it the host can know the form of the expand tables) */);
 // B' with counts aboard for cco_rows_impl: out[e] = b_col_idx[e] | counts_b[b_col_idx[e]] << key bits, e < b_row_ptr[n_rows_b] (<= nnz_bound); bad[0] = counts that do not fit
 int pack_counts(urcco_session* s, const int64_t* b_row_ptr, int64_t n_rows_b, const int32_t* b_col_idx, int64_t nnz_bound, const int32_t* counts_b, int32_t n_cols_b,
                 int32_t* out, int32_t* bad);
 int partition_dev(urcco_session* s, int32_t n_items, const int64_t* work, int32_t n_parts, int32_t* bounds_dev, int32_t** bounds_out);
 int expand_multi(urcco_session* s, int n, const int64_t* a_col_ptr, int32_t n_items_a, const int32_t* a_row_idx, int64_t cap, const int64_t* const* b_row_ptr,
-                 int64_t n_users, int64_t* const* pstart, int32_t* const* plen, int64_t* const* tile_sums = nullptr /* [d]: expand_tile_words(cap) words */);
+                 int64_t n_users, unsigned* const* pstart, int32_t* const* plen, int64_t* const* tile_sums = nullptr /* [d]: expand_tile_words(cap) words */);
 inline size_t expand_tile_words(int64_t cap) { return (size_t)((cap + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE + 2); }
 }  // namespace urcco_detail
 
@@ -121,6 +122,10 @@ struct urcco_session {
   double* xlx_hi = nullptr;   // xLogX(N - d) for the N of the last build
   long long xlx_hi_n = -1;
   int debug = 0;              // urcco::DBG_* bits (urcco_session_set_debug)
+  unsigned long long narrow_limit = urcco::NARROW_LIMIT;  // urcco_session_set_expand_test (test hook): the tile sum from which the expand tables take the wide form
+  long long prefix_seed = 0;                              // ... and where the work prefix starts
+  int32_t* form_word = nullptr;                           // [1] the form of the expand tables of the session's last build (urcco::ExpandForm), allocated on first use
+  bool form_valid = false;                                // a cco_rows_impl has written it
   unsigned* marks = nullptr;  // URCCO_DEBUG_MARKS: pinned host words [0] last launch group begun, [1] last finished ((ordinal << 8) | stage)
   unsigned mark_seq = 0;
   int unordered_rows = 0;     // URCCO_FLAG_UNORDERED_ROWS of the owning context

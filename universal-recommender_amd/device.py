@@ -113,6 +113,16 @@ class DeviceSession:
     def set_debug(self, flags: int):
         self._check(self.lib.urcco_session_set_debug(self.handle, int(flags)))
 
+    def expand_form(self) -> int:
+        """0: the last cco_rows call of this session ran on narrow expand tables; else the reasons for the wide form (include/urcco.h); synchronises."""
+        f = C.c_int32(-1)
+        self._check(self.lib.urcco_session_expand_form(self.handle, C.byref(f)))
+        return int(f.value)
+
+    def set_expand_test(self, limit: int = 0, prefix_seed: int = 0):
+        """Test hook: the scan-tile sum from which the expand tables take the wide form (0: the production value, 2^32), and where the work prefix starts."""
+        self._check(self.lib.urcco_session_set_expand_test(self.handle, int(limit), int(prefix_seed)))
+
     def get_timings(self):
         """{stage name: (summed ms, launches)} since set_timing(True); synchronises."""
         ms = (C.c_double * _lib.N_STAGES)()
