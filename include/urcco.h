@@ -519,6 +519,56 @@ int urcco_dev_recommend_rules(urcco_session* s, int64_t n_queries, int32_t n_ite
                               int32_t num, int32_t flags, int32_t* out_count, int32_t* out_idx, double* out_score, int64_t* stats_dev,
                               const urcco_rec_rule* rules, int32_t n_rules);
 
+/* Device-resident user history: the event-store half of a batch of queries (getBiasedRecentUserActions, URAlgorithm.scala:795-839; getExcludedItems,
+ * :741-767), from event streams that already sit in HBM -- (user id, column id, time) per event and event type, dense ids as urcco_dev_dictionary_lookup
+ * yields them.  DESIGN.md decision D17.  For a query user u and event type e with cap max_items (the indicator's maxItemsPerUser):
+ *   events of u    the stream positions p of e's stream with users[p] == u; positions with users[p] < 0 (or >= n_users) belong to nobody
+ *   recency        the order (times_ms[p] desc, p desc): of two events with equal time the later stream position is the more recent (the reference
+ *                  leaves ties to the event store, `latest = true`, :809 -- this tie-break is this library's); times_ms == NULL: stream order is time order
+ *   window         the first min(n_u, max_items) events in that order.  Events with items[p] < 0 (an item outside the column dictionary) COUNT toward the
+ *                  cap and contribute no column: the reference counts `items.size` before any lookup (:830)
+ *   term row       the distinct items[p] of the window, ascending -- the form urcco_rec_clause.q_col_idx and the ANY / NONE rule rows need; duplicates
+ *                  inside the window make the row shorter than the cap (`distinct` after the cut)
+ *   exclusion row  of a query: the union over the event types flagged `blacklist` of col_map_e[items[p]] over ALL events of u (no cap, :743-752), united with
+ *                  the query's row of the caller's extra exclusion CSR (blacklistItems, the query item, the item set); ascending, distinct; entries outside
+ *                  0..n_items are dropped.  col_map_e (NULL = identity) maps e's column ids to the primary's item ids, -1 where the primary has none
+ *   unknown user   q_users[q] < 0 or >= n_users: empty term rows, the exclusion row is the extra row alone
+ * Everything is integer and the order is total: the rows are bit-identical from run to run, whatever order the index build's scatter produced.
+ *
+ * urcco_dev_history_index: out_pos[out_row_ptr[u] .. out_row_ptr[u + 1]) = the stream positions p with users[p] == u, order unspecified.
+ * urcco_dev_history_bounds: term_row_ptr of every type and excl_row_ptr receive the exclusive scans of upper bounds of the rows' lengths (min(n_u, max_items);
+ *   blacklist events + extra row).  The caller reads the 1 + n_types totals (term_row_ptr[n_queries], excl_row_ptr[n_queries]: its one synchronisation),
+ *   allocates term_col_idx / excl_col_idx of at least that many entries and states the sizes in term_capacity / excl_capacity.
+ * urcco_dev_history_rows: the same arguments, the row_ptr arrays as _bounds left them; on return they hold the final row starts and the col_idx arrays
+ *   the rows.  A capacity below the bound leaves the rows past it empty and counts them in stats[6].
+ * stats_dev (nullable, int64[URCCO_HIST_STATS_LEN]): (query, type) pairs served by [0] the wave class (<= 64 events), [1] the block class (<= 4096, keys in
+ *   LDS), [2] the global class; [3] pairs that ran the select (n_u > max_items); exclusion rows built by [4] one wave, [5] one block; [6] rows dropped
+ *   for lack of capacity (0 when the caller sized its buffers by the bounds); [7] 0.
+ * All three enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: n_events >= 2^31, n_types outside
+ * 1..URCCO_REC_MAX_CLAUSES, max_items < 1, n_queries * (n_types + 1) >= 2^31, a NULL the call needs, a half-NULL extra pair, a negative capacity.
+ * ABI: additions within ABI 305 -- the presence of the symbols is the feature test. */
+#define URCCO_HIST_STATS_LEN 8
+int urcco_dev_history_index(urcco_session* s, int64_t n_events, const int32_t* users, int64_t n_users,
+                            int64_t* out_row_ptr /* [n_users + 1] */, int32_t* out_pos /* capacity n_events */);
+
+typedef struct urcco_hist_event {
+  int32_t n_cols, max_items;          /* max_items >= 1 */
+  int32_t blacklist, reserved;        /* != 0: this type's events feed the exclusion rows */
+  const int64_t* idx_row_ptr; const int32_t* idx_pos;   /* urcco_dev_history_index of this stream */
+  const int32_t* items;               /* the stream: dense column id per event, < 0 = no column */
+  const int64_t* times_ms;            /* nullable: stream order is time order */
+  const int32_t* col_map;             /* nullable (identity): [n_cols] -> primary item id or -1 */
+  int64_t* term_row_ptr;              /* [n_queries + 1]: bounds after _bounds, final after _rows */
+  int32_t* term_col_idx;              /* _rows: capacity term_capacity; _bounds does not read it */
+  int64_t term_capacity;              /* _rows: entries of term_col_idx, >= the bound total the caller read after _bounds */
+} urcco_hist_event;
+
+int urcco_dev_history_bounds(urcco_session* s, int64_t n_queries, const int32_t* q_users, int64_t n_users, urcco_hist_event* events, int32_t n_types,
+                             const int64_t* extra_row_ptr, const int32_t* extra_col_idx /* nullable pair */, int64_t* excl_row_ptr /* [n_queries + 1] */);
+int urcco_dev_history_rows(urcco_session* s, int64_t n_queries, const int32_t* q_users, int64_t n_users, urcco_hist_event* events, int32_t n_types,
+                           const int64_t* extra_row_ptr, const int32_t* extra_col_idx, int32_t n_items,
+                           int64_t* excl_row_ptr, int32_t* excl_col_idx, int64_t excl_capacity, int64_t* stats_dev /* nullable */);
+
 /* Test hooks (device level): LLR of SimilarityAnalysis.logLikelihoodRatio evaluated by the device code for
  * n argument tuples; u01 of the down-sampling RNG.  All pointers device. */
 int urcco_dev_llr(urcco_session* s, int64_t n, const int64_t* with_a, const int64_t* with_b, const int64_t* with_ab,

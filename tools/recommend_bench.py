@@ -8,7 +8,12 @@ user's primary-event items as the blacklist, popularity as the backfill order, n
 --rules: the same problem once more through urcco_dev_recommend_rules under one category filter (an ANY rule on a value that about half of the
 catalogue holds) and one NONE rule (a value a ninth of it holds), its time printed next to the rule-free call's; the first measurement of that
 path belongs under profiles/ (DESIGN.md section 7a).
-usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--rules]"""
+--device-history: the event-store half of the same queries (decision D17).  The event matrices are unrolled into (user, item, time) streams on the
+device, indexed (urcco_dev_history_index), and the queries' term rows and exclusion rows built by urcco_dev_history_bounds + _rows (caps 500, the
+primary as the blacklist event); their device time (HIP events, the read of the bound totals in between included) is printed next to the wall time
+of the host planning of recommend.batch_predict's dict form for the same queries (per query and event type: reversed slice, dict.fromkeys, one
+dictionary lookup per item, np.unique) on this box.  --no-torch skips the torch comparison.
+usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--rules] [--device-history] [--no-torch]"""
 import argparse
 import os
 import sys
@@ -28,6 +33,8 @@ ap.add_argument("--chunk", type=int, default=2048)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--num", type=int, default=20)
 ap.add_argument("--rules", action="store_true", help="also time the call under an ANY and a NONE rule")
+ap.add_argument("--device-history", action="store_true", help="also time history_bounds + history_rows against the host planning loop")
+ap.add_argument("--no-torch", action="store_true", help="skip the torch comparison")
 args = ap.parse_args()
 
 assert torch.cuda.is_available(), "needs the GPU: there is no CPU path to time"
@@ -91,6 +98,51 @@ if args.rules:
     print(f"urcco_dev_recommend_rules (ANY on a value {float(half.float().mean()):.0%} of the items hold, NONE on a value a ninth hold): {min(ms_rules):.2f} ms best, "
           f"{sorted(ms_rules)[len(ms_rules) // 2]:.2f} ms median of {args.reps} ({[round(x, 2) for x in ms_rules]}) -- rule-free call above: {min(ms_hip):.2f} ms")
     print(f"  candidates {rs[3]} ({rs[3] / nq:.0f} per query, {st[3] / nq:.0f} without rules); backfill steps {rs[4]} ({rs[4] / nq:.2f} per query); full rows {int((r_count == num).sum())} / {nq}")
+
+if args.device_history:
+    import time
+
+    import numpy as np
+    CAP = 500
+    g = torch.Generator(device="cpu").manual_seed(2)
+    streams, host = [], []
+    for m in mats:
+        nnz = m.nnz_bound
+        users = torch.repeat_interleave(torch.arange(m.n_rows, device=dev, dtype=torch.int32), (m.row_ptr[1:] - m.row_ptr[:-1]))
+        perm = torch.randperm(nnz, generator=g).to(dev)                   # an event stream is not sorted by user
+        users, items = users[perm].contiguous(), m.col_idx[:nnz][perm].contiguous()
+        times = (1_600_000_000_000 + torch.randint(0, 30 * 86_400_000, (nnz,), generator=g)).to(dev)
+        rp, pos = sess.history_index(users, m.n_rows)
+        streams.append((m.n_cols, rp, pos, items, times))
+    specs = [(nc, CAP, t == 0, rp, pos, items, times, None) for t, (nc, rp, pos, items, times) in enumerate(streams)]
+    q_users = torch.arange(nq, dtype=torch.int32, device=dev)
+    ms_hist = []
+    for r in range(args.reps + 1):
+        rows, ex, info = sess.history_rows(q_users, cfg.n_users, specs, n_items, None, stats=True, timing=True)
+        if r:
+            ms_hist.append(info["ms"])
+    hs = info["stats"].cpu().tolist()
+    print(f"urcco_dev_history_bounds + _rows ({nq} queries x {len(mats)} event types, cap {CAP}): {min(ms_hist):.2f} ms best, {sorted(ms_hist)[len(ms_hist) // 2]:.2f} ms median "
+          f"of {args.reps} ({[round(x, 2) for x in ms_hist]})")
+    print(f"  pairs by class: wave {hs[0]}, block {hs[1]}, global {hs[2]}; ran the select {hs[3]}; exclusion rows: wave {hs[4]}, block {hs[5]}; term entries "
+          f"{[int(rp[-1].item()) for rp, _ in rows]}, exclusion entries {int(ex[0][-1].item())}")
+    # the host planning of the dict form for the same queries: the history as Python lists (built outside the timed part), ids through a dict per event type
+    h_rows = [(m.row_ptr[: nq + 1].cpu().numpy(), m.col_idx[: int(m.row_ptr[nq].item())].cpu().numpy()) for m in mats]
+    lists = [[[str(i) for i in ci[rp[u]:rp[u + 1]]] for u in range(nq)] for rp, ci in h_rows]
+    dicts = [{str(i): i for i in range(m.n_cols)} for m in mats]
+    t0 = time.perf_counter()
+    for u in range(nq):
+        for t in range(len(mats)):
+            recent = list(reversed(lists[t][u]))[:CAP]
+            ids = [dicts[t].get(i) for i in dict.fromkeys(recent)]
+            np.unique(np.array([i for i in ids if i is not None], np.int64))
+        np.unique(np.array([dicts[0].get(i) for i in lists[0][u]], np.int64))
+    host_ms = (time.perf_counter() - t0) * 1e3
+    print(f"host planning loop of the dict form, same queries (recommend.py, one thread): {host_ms:.0f} ms wall -- {host_ms / min(ms_hist):.0f}x the device calls")
+
+if args.no_torch:
+    sess.close()
+    sys.exit(0)
 
 # ---- the same with torch: per chunk of queries, sum_c boost_c * T_c[chunk] @ I_c' (sparse x sparse -> dense), key = score with the backfill position as tie break ----
 pos = torch.empty(n_items, dtype=torch.int64, device=dev)

@@ -32,6 +32,7 @@ REC_NO_BACKFILL = 1
 REC_STATS_LEN = 8
 REC_MAX_RULES = 16     # urcco_dev_recommend_rules (URCCO_REC_MAX_RULES, URCCO_RULE_*)
 RULE_ANY, RULE_NONE, RULE_RANGE = 0, 1, 2
+HIST_STATS_LEN = 8     # urcco_dev_history_rows (URCCO_HIST_STATS_LEN): pairs per class, selects, exclusion rows per class, overflows
 REC_LDS_LIMIT = 3072   # work bound w(q) up to which a query runs in the LDS class (csrc/cco_kernels.h)
 EXCH_SIZES = 4   # int64 words of a shard's record (include/urcco.h URCCO_EXCH_SIZES)
 STAGE_NAMES = ["column_counts", "downsample_flags", "downsample_scan", "downsample_compact", "transpose", "row_work", "binning",
@@ -114,6 +115,13 @@ class RecRule(C.Structure):
                 ("q_col_idx", C.c_void_p), ("item_value", C.c_void_p), ("q_lo", C.c_void_p), ("q_hi", C.c_void_p)]
 
 
+class HistEvent(C.Structure):
+    """urcco_hist_event: one event type of urcco_dev_history_bounds / _rows."""
+    _fields_ = [("n_cols", C.c_int32), ("max_items", C.c_int32), ("blacklist", C.c_int32), ("reserved", C.c_int32), ("idx_row_ptr", C.c_void_p),
+                ("idx_pos", C.c_void_p), ("items", C.c_void_p), ("times_ms", C.c_void_p), ("col_map", C.c_void_p), ("term_row_ptr", C.c_void_p),
+                ("term_col_idx", C.c_void_p), ("term_capacity", C.c_int64)]
+
+
 # every symbol include/urcco.h declares: (restype, argtypes)
 _p = C.c_void_p
 SYMBOLS = {
@@ -174,6 +182,9 @@ SYMBOLS = {
     "urcco_dev_recommend": (C.c_int, [_p, C.c_int64, C.c_int32, C.POINTER(RecClause), C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p]),
     "urcco_dev_recommend_rules": (C.c_int, [_p, C.c_int64, C.c_int32, C.POINTER(RecClause), C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p,
                                             C.POINTER(RecRule), C.c_int32]),
+    "urcco_dev_history_index": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p]),
+    "urcco_dev_history_bounds": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.POINTER(HistEvent), C.c_int32, _p, _p, _p]),
+    "urcco_dev_history_rows": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.POINTER(HistEvent), C.c_int32, _p, _p, C.c_int32, _p, _p, C.c_int64, _p]),
     "urcco_dev_llr": (C.c_int, [_p, C.c_int64, _p, _p, _p, _p, _p]),
     "urcco_dev_u01": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p]),
     "urcco_dev_u01_rng": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, C.c_int32, _p]),

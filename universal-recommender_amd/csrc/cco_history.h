@@ -1,0 +1,475 @@
+// Device-resident user history (decision D17 of DESIGN.md 7a; include/urcco.h urcco_dev_history_*): the event-store half of a
+// batch of queries.  Compiled into ingest_kernels.hip (it uses that file's grid helper and row compaction).
+//
+// What the reference reads from the event store per query (getBiasedRecentUserActions, URAlgorithm.scala:795-839: the most recent
+// maxItemsPerUser events per event type, then distinct; getExcludedItems, :741-767: every item of the blacklist events) is here
+//   index   stream positions by user: count per user -> scan -> scatter by cursor (order inside a user's segment unspecified)
+//   bounds  per (query, type) min(n_u, max_items), per query the blacklist events + the extra exclusion row: scans = raw row starts
+//   rows    per (query, type): the window = the min(n_u, max_items) largest keys (time, position) of the user's events -- found by an
+//           8-bit radix SELECT over the 96-bit keys when n_u > max_items, never by sorting the events -- then sort + unique of the
+//           window's columns; per query the same sort + unique tail over the mapped blacklist events and the extra row
+//   compact raw rows -> final CSR
+// Three classes by the number of events n_u of the (query, type), chosen on the device from the index:
+//   <= 64     one wave: keys in registers, rank by cross-lane compares, bitonic network + ballot unique in registers
+//   <= 4096   one block: keys in LDS, select with an LDS histogram per discriminating digit, window columns sorted in LDS
+//   larger    the same block code with the keys re-read from global memory per discriminating digit; the window is staged in its
+//             raw row (<= max_items entries) and sorted in LDS up to 4096 entries, in global memory beyond
+// A digit in which all keys of the user agree (the high bytes of millisecond times, every time byte without times) costs no pass:
+// one pass ORs key ^ key[0] over the events first.  Keys are unique (the position is part of them), so the order is total and the
+// rows do not depend on the order the index scatter left.  Wave = 64 lanes; wave primitives under wave-uniform control flow only.
+namespace urcco {
+
+namespace {
+constexpr int HS_SENT = 0x7fffffff;                       // "no column": sorts behind every id, dropped by the unique step
+constexpr unsigned long long HS_SIGN = 0x8000000000000000ull;  // int64 time -> order-preserving unsigned
+constexpr int HS_LDS = 4096;                              // events (keys) or window entries one block holds in LDS
+
+__device__ __forceinline__ int hs_user_events(const HistEvent& e, const int32_t* q_users, int64_t n_users, int64_t q, int64_t& seg) {
+  const int u = q_users[q];
+  if (u < 0 || u >= n_users) { seg = 0; return 0; }
+  seg = e.idx_row_ptr[u];
+  return (int)(e.idx_row_ptr[u + 1] - seg);
+}
+
+// an event's column as an exclusion: through the type's column map into the primary's items; HS_SENT = none
+__device__ __forceinline__ int hs_excl_id(const HistEvent& e, int item, int n_items) {
+  if (item < 0) return HS_SENT;
+  if (e.col_map) item = item < e.n_cols ? e.col_map[item] : -1;
+  return item >= 0 && item < n_items ? item : HS_SENT;
+}
+
+// one wave: sort the lanes' values, drop HS_SENT and duplicates, write the row; returns its length (all lanes)
+__device__ __forceinline__ int hs_wave_tail(int v, int lane, int32_t* __restrict__ dst) {
+  for (int k2 = 2; k2 <= IG_WAVE; k2 <<= 1) {
+    for (int j = k2 >> 1; j > 0; j >>= 1) {
+      const int o = __shfl_xor(v, j);
+      const bool keep_small = ((lane & j) == 0) == ((lane & k2) == 0);
+      if (keep_small ? o < v : o > v) v = o;
+    }
+  }
+  const int prev = __shfl_up(v, 1);
+  const bool fresh = v != HS_SENT && (lane == 0 || v != prev);
+  const unsigned long long m = __ballot(fresh);
+  if (fresh) dst[__popcll(m & ((1ull << lane) - 1ull))] = v;
+  return __popcll(m);
+}
+
+// one block: row[0..m) (global) -> sorted, duplicate-free, in place; returns the length (all threads).  s_v: HS_LDS ints of LDS.
+__device__ __forceinline__ int hs_block_tail(int32_t* __restrict__ row, int m, int* s_v) {
+  __shared__ int s_wsum[256 / IG_WAVE];
+  if (m <= 0) return 0;  // block-uniform
+  const int lane = threadIdx.x & (IG_WAVE - 1), wave = threadIdx.x / IG_WAVE;
+  int64_t P = 2;
+  while (P < m) P <<= 1;
+  const bool in_lds = m <= HS_LDS;
+  if (in_lds) {
+    for (int t = threadIdx.x; t < P; t += 256) s_v[t] = t < m ? row[t] : HS_SENT;
+    __syncthreads();
+    for (int k2 = 2; k2 <= P; k2 <<= 1) {
+      for (int j = k2 >> 1; j > 0; j >>= 1) {
+        for (int t = threadIdx.x; t < P; t += 256) {
+          const int u = t ^ j;
+          if (u > t) {
+            const int a = s_v[t], b = s_v[u];
+            const bool asc = (t & k2) == 0;
+            if (asc ? a > b : a < b) { s_v[t] = b; s_v[u] = a; }
+          }
+        }
+        __syncthreads();
+      }
+    }
+  } else {
+    // the ascending-only bitonic network over 2^ceil(log2 m) entries whose tail is +inf (ig_sort_rows_block_kernel): exchanges with the padding are skipped
+    for (int64_t k2 = 2; k2 <= P; k2 <<= 1) {
+      for (int64_t j = k2 >> 1; j > 0; j >>= 1) {
+        for (int64_t t = threadIdx.x; t < P; t += 256) {
+          const int64_t u = (j == (k2 >> 1)) ? (t ^ (k2 - 1)) : (t ^ j);
+          if (u > t && u < m) {
+            const int a = row[t], b = row[u];
+            if (a > b) { row[t] = b; row[u] = a; }
+          }
+        }
+        __syncthreads();
+      }
+    }
+  }
+  int carry = 0;
+  for (int base = 0; base < m; base += 256) {  // block-uniform
+    const int t = base + threadIdx.x;
+    int v = 0;
+    bool fresh = false;
+    if (t < m) {
+      v = in_lds ? s_v[t] : row[t];
+      const int pv = t == 0 ? 0 : (in_lds ? s_v[t - 1] : row[t - 1]);
+      fresh = t == 0 || v != pv;
+    }
+    const unsigned long long mk = __ballot(fresh);
+    if (lane == 0) s_wsum[wave] = __popcll(mk);
+    __syncthreads();
+    int before = 0, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 256 / IG_WAVE; ++w) {
+      const int c = s_wsum[w];
+      if (w < wave) before += c;
+      tot += c;
+    }
+    const int pos = carry + before + __popcll(mk & ((1ull << lane) - 1ull));
+    __syncthreads();  // every read of row[base .. base + 256) and of s_wsum precedes the writes below
+    if (fresh) row[pos] = v;  // pos <= t
+    carry += tot;
+    __syncthreads();
+  }
+  return carry;
+}
+}  // namespace
+
+// ---- index ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void hs_count_users_kernel(int64_t n, const int32_t* __restrict__ users, int64_t n_users, int32_t* __restrict__ cnt) {
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
+    const int u = users[p];
+    if (u >= 0 && u < n_users) atomicAdd(&cnt[u], 1);
+  }
+}
+
+__global__ __launch_bounds__(256) void hs_scatter_pos_kernel(int64_t n, const int32_t* __restrict__ users, int64_t n_users, const int64_t* __restrict__ row_ptr,
+                                                             int32_t* __restrict__ cursor, int32_t* __restrict__ out_pos) {
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
+    const int u = users[p];
+    if (u >= 0 && u < n_users) out_pos[row_ptr[u] + atomicAdd(&cursor[u], 1)] = (int32_t)p;
+  }
+}
+
+hipError_t launch_history_index(hipStream_t st, int n_cu, int64_t n, const int32_t* users, int64_t n_users, int32_t* cnt, int64_t* tile_sums,
+                                int64_t* out_row_ptr, int32_t* out_pos) {
+  if (n_users == 0) return hipMemsetAsync(out_row_ptr, 0, sizeof(int64_t), st);
+  hipError_t e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)n_users, st);
+  if (e != hipSuccess) return e;
+  if (n > 0) hipLaunchKernelGGL(hs_count_users_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, users, n_users, cnt);
+  e = launch_scan_i32(st, cnt, n_users, out_row_ptr, tile_sums);
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)n_users, st);  // now the scatter cursors
+  if (e != hipSuccess) return e;
+  if (n > 0) hipLaunchKernelGGL(hs_scatter_pos_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, users, n_users, out_row_ptr, cnt, out_pos);
+  return hipGetLastError();
+}
+
+// ---- bounds --------------------------------------------------------------------------------------------------------
+// bnd[t * n_queries + q] = min(n_u, max_items) of type t; bnd[n_types * n_queries + q] = blacklist events + the extra row's length
+__global__ __launch_bounds__(256) void hs_bounds_kernel(HistArgs a, int32_t* __restrict__ bnd) {
+  for (int64_t q = (int64_t)blockIdx.x * 256 + threadIdx.x; q < a.n_queries; q += (int64_t)gridDim.x * 256) {
+    int64_t excl = a.extra_row_ptr ? a.extra_row_ptr[q + 1] - a.extra_row_ptr[q] : 0;
+    for (int t = 0; t < a.n_types; ++t) {
+      int64_t seg;
+      const int n = hs_user_events(a.ev[t], a.q_users, a.n_users, q, seg);
+      bnd[(int64_t)t * a.n_queries + q] = n < a.ev[t].max_items ? n : a.ev[t].max_items;
+      if (a.ev[t].blacklist) excl += n;
+    }
+    bnd[(int64_t)a.n_types * a.n_queries + q] = excl > 0x7fffffffll ? 0x7fffffff : (int32_t)excl;  // saturated: the rows kernels never write past a raw row
+  }
+}
+
+hipError_t launch_history_bounds(hipStream_t st, int n_cu, const HistArgs& a, int32_t* bnd, int64_t* tile_sums, int64_t* const* term_row_ptr, int64_t* excl_row_ptr) {
+  if (a.n_queries == 0) {
+    for (int t = 0; t < a.n_types; ++t) {
+      const hipError_t e = hipMemsetAsync(term_row_ptr[t], 0, sizeof(int64_t), st);
+      if (e != hipSuccess) return e;
+    }
+    return hipMemsetAsync(excl_row_ptr, 0, sizeof(int64_t), st);
+  }
+  hipLaunchKernelGGL(hs_bounds_kernel, dim3(ig_grid(a.n_queries, n_cu)), dim3(256), 0, st, a, bnd);
+  for (int t = 0; t <= a.n_types; ++t) {
+    const hipError_t e = launch_scan_i32(st, bnd + (int64_t)t * a.n_queries, a.n_queries, t < a.n_types ? term_row_ptr[t] : excl_row_ptr, tile_sums);
+    if (e != hipSuccess) return e;
+  }
+  return hipGetLastError();
+}
+
+// ---- rows ----------------------------------------------------------------------------------------------------------
+// job j = t * n_queries + q; t == n_types is the exclusion row of query q.  ctr[0] = jobs left to the block kernel (big_list),
+// ctr[1 + HIST_STAT_*] = the statistics of include/urcco.h.
+// One wave per job of <= 64 events (exclusion rows: <= 64 raw entries); the others go on big_list.
+__global__ __launch_bounds__(256) void hs_rows_wave_kernel(HistArgs a) {
+  const int lane = threadIdx.x & (IG_WAVE - 1);
+  const int64_t n_waves = (int64_t)gridDim.x * (256 / IG_WAVE);
+  const int64_t n_jobs = a.n_queries * (a.n_types + 1);
+  unsigned n_term = 0, n_excl = 0, n_sel = 0, n_over = 0;
+  for (int64_t j = (int64_t)blockIdx.x * (256 / IG_WAVE) + threadIdx.x / IG_WAVE; j < n_jobs; j += n_waves) {  // wave-uniform
+    const int t = (int)(j / a.n_queries);
+    const int64_t q = j - (int64_t)t * a.n_queries;
+    if (t < a.n_types) {
+      const HistEvent& e = a.ev[t];
+      int64_t seg;
+      const int n = hs_user_events(e, a.q_users, a.n_users, q, seg);
+      if (e.raw_ptr[q + 1] > e.capacity) {  // the caller's buffers are smaller than the bounds: an empty row, counted
+        if (lane == 0) e.len[q] = 0;
+        ++n_over;
+        continue;
+      }
+      if (n > IG_WAVE) {
+        if (lane == 0) a.big_list[atomicAdd(&a.ctr[0], 1ull)] = (int32_t)j;
+        continue;
+      }
+      ++n_term;
+      unsigned p = 0;
+      unsigned long long tk = 0;
+      int item = -1;
+      if (lane < n) {
+        p = (unsigned)e.idx_pos[seg + lane];
+        tk = e.times_ms ? (unsigned long long)e.times_ms[p] ^ HS_SIGN : 0ull;
+        item = e.items[p];
+      }
+      bool in = lane < n;
+      if (n > e.max_items) {  // wave-uniform: rank = events of the user more recent than this lane's
+        ++n_sel;
+        int rank = 0;
+        for (int o = 0; o < n; ++o) {
+          const unsigned long long ot = __shfl(tk, o);
+          const unsigned op = __shfl(p, o);
+          rank += (ot > tk || (ot == tk && op > p)) ? 1 : 0;
+        }
+        in = in && rank < e.max_items;
+      }
+      const int len = hs_wave_tail(in && item >= 0 && item < e.n_cols ? item : HS_SENT, lane, e.tmp + e.raw_ptr[q]);
+      if (lane == 0) e.len[q] = len;
+    } else {
+      const int64_t s = a.excl_raw_ptr[q];
+      const int64_t L = a.excl_raw_ptr[q + 1] - s;
+      if (a.excl_raw_ptr[q + 1] > a.excl_capacity) {
+        if (lane == 0) a.excl_len[q] = 0;
+        ++n_over;
+        continue;
+      }
+      if (L > IG_WAVE) {
+        if (lane == 0) a.big_list[atomicAdd(&a.ctr[0], 1ull)] = (int32_t)j;
+        continue;
+      }
+      ++n_excl;
+      int v = HS_SENT;
+      int64_t base = 0;
+      for (int t2 = 0; t2 < a.n_types; ++t2) {
+        const HistEvent& e = a.ev[t2];
+        if (!e.blacklist) continue;
+        int64_t seg;
+        const int n = hs_user_events(e, a.q_users, a.n_users, q, seg);
+        if (lane >= base && lane < base + n) v = hs_excl_id(e, e.items[e.idx_pos[seg + lane - base]], a.n_items);
+        base += n;
+      }
+      if (a.extra_row_ptr) {
+        const int64_t xs = a.extra_row_ptr[q], xn = a.extra_row_ptr[q + 1] - xs;
+        if (lane >= base && lane < base + xn) {
+          const int x = a.extra_col_idx[xs + lane - base];
+          v = x >= 0 && x < a.n_items ? x : HS_SENT;
+        }
+      }
+      const int len = hs_wave_tail(v, lane, a.excl_tmp + s);
+      if (lane == 0) a.excl_len[q] = len;
+    }
+  }
+  if (lane == 0) {
+    if (n_term) atomicAdd(&a.ctr[1 + HIST_STAT_WAVE], (unsigned long long)n_term);
+    if (n_sel) atomicAdd(&a.ctr[1 + HIST_STAT_SELECT], (unsigned long long)n_sel);
+    if (n_excl) atomicAdd(&a.ctr[1 + HIST_STAT_EXCL_WAVE], (unsigned long long)n_excl);
+    if (n_over) atomicAdd(&a.ctr[1 + HIST_STAT_OVERFLOW], (unsigned long long)n_over);
+  }
+}
+
+// One block per job of big_list.
+__global__ __launch_bounds__(256) void hs_rows_block_kernel(HistArgs a) {
+  // keys of the LDS class: HS_LDS times (8 bytes), then HS_LDS positions; once the window is staged in its raw row the front is the sort buffer
+  __shared__ unsigned long long s_buf[HS_LDS + HS_LDS / 2];
+  __shared__ int s_hist[256];
+  __shared__ unsigned s_diff[3];
+  __shared__ int s_sel[2];
+  __shared__ int s_cnt;
+  unsigned long long* s_time = s_buf;
+  unsigned* s_pos = reinterpret_cast<unsigned*>(s_buf + HS_LDS);
+  int* s_v = reinterpret_cast<int*>(s_buf);
+  const int64_t n_big = (int64_t)a.ctr[0];
+  for (int64_t li = blockIdx.x; li < n_big; li += gridDim.x) {  // block-uniform
+    const int64_t j = a.big_list[li];
+    const int t = (int)(j / a.n_queries);
+    const int64_t q = j - (int64_t)t * a.n_queries;
+    if (threadIdx.x == 0) { s_cnt = 0; s_diff[0] = 0; s_diff[1] = 0; s_diff[2] = 0; }
+    int32_t* row;
+    int room;
+    if (t < a.n_types) {
+      const HistEvent& e = a.ev[t];
+      int64_t seg;
+      const int n = hs_user_events(e, a.q_users, a.n_users, q, seg);
+      row = e.tmp + e.raw_ptr[q];
+      room = (int)(e.raw_ptr[q + 1] - e.raw_ptr[q]);
+      const int K = e.max_items;
+      const bool in_lds = n <= HS_LDS;
+      const int32_t* __restrict__ ipos = e.idx_pos + seg;
+      const int64_t* __restrict__ times = e.times_ms;
+      if (in_lds)
+        for (int i = threadIdx.x; i < n; i += 256) {
+          const unsigned p = (unsigned)ipos[i];
+          s_pos[i] = p;
+          s_time[i] = times ? (unsigned long long)times[p] ^ HS_SIGN : 0ull;
+        }
+      __syncthreads();
+      auto key = [&](int i, unsigned long long& kt, unsigned& kp) {
+        if (in_lds) { kt = s_time[i]; kp = s_pos[i]; }
+        else { kp = (unsigned)ipos[i]; kt = times ? (unsigned long long)times[kp] ^ HS_SIGN : 0ull; }
+      };
+      unsigned long long thr_t = 0;
+      unsigned thr_p = 0;
+      const bool all = n <= K;  // block-uniform: no select
+      if (threadIdx.x == 0) {
+        atomicAdd(&a.ctr[1 + (in_lds ? HIST_STAT_BLOCK : HIST_STAT_GLOBAL)], 1ull);
+        if (!all) atomicAdd(&a.ctr[1 + HIST_STAT_SELECT], 1ull);
+      }
+      if (!all) {
+        // the K-th largest key: digits in which the user's keys differ, most significant first
+        unsigned long long t0;
+        unsigned p0;
+        key(0, t0, p0);
+        unsigned long long dt = 0;
+        unsigned dp = 0;
+        for (int i = threadIdx.x; i < n; i += 256) {
+          unsigned long long kt;
+          unsigned kp;
+          key(i, kt, kp);
+          dt |= kt ^ t0;
+          dp |= kp ^ p0;
+        }
+        if ((unsigned)dt) atomicOr(&s_diff[0], (unsigned)dt);
+        if ((unsigned)(dt >> 32)) atomicOr(&s_diff[1], (unsigned)(dt >> 32));
+        if (dp) atomicOr(&s_diff[2], dp);
+        __syncthreads();
+        dt = (unsigned long long)s_diff[0] | ((unsigned long long)s_diff[1] << 32);
+        dp = s_diff[2];
+        unsigned long long pre_t = 0, mask_t = 0;
+        unsigned pre_p = 0, mask_p = 0;
+        int remaining = K;
+        for (int d = 0; d < 12; ++d) {
+          const bool is_time = d < 8;
+          const int sh = is_time ? 56 - 8 * d : 24 - 8 * (d - 8);
+          const unsigned differ = is_time ? (unsigned)(dt >> sh) & 255u : (dp >> sh) & 255u;
+          int b;
+          if (!differ) {  // block-uniform: every key carries key[0]'s digit
+            b = is_time ? (int)((t0 >> sh) & 255u) : (int)((p0 >> sh) & 255u);
+          } else {
+            s_hist[threadIdx.x] = 0;
+            __syncthreads();
+            for (int i = threadIdx.x; i < n; i += 256) {
+              unsigned long long kt;
+              unsigned kp;
+              key(i, kt, kp);
+              if ((kt & mask_t) == pre_t && (kp & mask_p) == pre_p) atomicAdd(&s_hist[is_time ? (int)((kt >> sh) & 255u) : (int)((kp >> sh) & 255u)], 1);
+            }
+            __syncthreads();
+            if (threadIdx.x == 0) {
+              int cum = 0, bb = 255;
+              for (; bb > 0; --bb) {
+                const int c = s_hist[bb];
+                if (cum + c >= remaining) break;
+                cum += c;
+              }
+              s_sel[0] = bb;
+              s_sel[1] = remaining - cum;
+            }
+            __syncthreads();
+            b = s_sel[0];
+            remaining = s_sel[1];
+          }
+          if (is_time) { pre_t |= (unsigned long long)b << sh; mask_t |= 255ull << sh; }
+          else { pre_p |= (unsigned)b << sh; mask_p |= 255u << sh; }
+        }
+        thr_t = pre_t;
+        thr_p = pre_p;
+      }
+      // the window's columns -> the raw row (slots by an LDS counter: the sort below makes the order irrelevant)
+      for (int i = threadIdx.x; i < n; i += 256) {
+        unsigned long long kt;
+        unsigned kp;
+        key(i, kt, kp);
+        if (all || kt > thr_t || (kt == thr_t && kp >= thr_p)) {
+          const int item = e.items[kp];
+          if (item >= 0 && item < e.n_cols) {
+            const int slot = atomicAdd(&s_cnt, 1);
+            if (slot < room) row[slot] = item;
+          }
+        }
+      }
+    } else {
+      row = a.excl_tmp + a.excl_raw_ptr[q];
+      const int64_t room64 = a.excl_raw_ptr[q + 1] - a.excl_raw_ptr[q];
+      room = room64 > 0x7fffffffll ? 0x7fffffff : (int)room64;
+      if (threadIdx.x == 0) atomicAdd(&a.ctr[1 + HIST_STAT_EXCL_BLOCK], 1ull);
+      __syncthreads();
+      for (int t2 = 0; t2 < a.n_types; ++t2) {
+        const HistEvent& e = a.ev[t2];
+        if (!e.blacklist) continue;
+        int64_t seg;
+        const int n = hs_user_events(e, a.q_users, a.n_users, q, seg);
+        for (int i = threadIdx.x; i < n; i += 256) {
+          const int v = hs_excl_id(e, e.items[e.idx_pos[seg + i]], a.n_items);
+          if (v != HS_SENT) {
+            const int slot = atomicAdd(&s_cnt, 1);
+            if (slot < room) row[slot] = v;
+          }
+        }
+      }
+      if (a.extra_row_ptr) {
+        const int64_t xs = a.extra_row_ptr[q], xn = a.extra_row_ptr[q + 1] - xs;
+        for (int64_t i = threadIdx.x; i < xn; i += 256) {
+          const int x = a.extra_col_idx[xs + i];
+          if (x >= 0 && x < a.n_items) {
+            const int slot = atomicAdd(&s_cnt, 1);
+            if (slot < room) row[slot] = x;
+          }
+        }
+      }
+    }
+    __syncthreads();  // the raw row is complete (its writers are this block's threads), the keys in LDS are dead
+    const int m = s_cnt < room ? s_cnt : room;
+    const int len = hs_block_tail(row, m, s_v);
+    if (threadIdx.x == 0) {
+      if (t < a.n_types) a.ev[t].len[q] = len;
+      else a.excl_len[q] = len;
+    }
+    __syncthreads();
+  }
+}
+
+// a.ev[t].raw_ptr / tmp / len, a.excl_*, a.big_list, a.ctr: scratch.  term_row_ptr[t] / excl_row_ptr hold the bounds' scans on entry, the final row starts on return.
+hipError_t launch_history_rows(hipStream_t st, int n_cu, const HistArgs& a, int64_t* tile_sums, int64_t* const* term_row_ptr, int32_t* const* term_col_idx,
+                               int64_t* excl_row_ptr, int32_t* excl_col_idx, int64_t* stats_dev) {
+  hipError_t e = hipMemsetAsync(a.ctr, 0, sizeof(unsigned long long) * (1 + HIST_STATS_LEN), st);
+  if (e != hipSuccess) return e;
+  const int64_t nq = a.n_queries;
+  if (nq > 0) {
+    for (int t = 0; t <= a.n_types; ++t) {
+      e = hipMemcpyAsync(t < a.n_types ? a.ev[t].raw_ptr : a.excl_raw_ptr, t < a.n_types ? term_row_ptr[t] : excl_row_ptr,
+                         sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyDeviceToDevice, st);
+      if (e != hipSuccess) return e;
+    }
+    const int64_t n_jobs = nq * (a.n_types + 1);
+    hipLaunchKernelGGL(hs_rows_wave_kernel, dim3(ig_grid(n_jobs * IG_WAVE, n_cu)), dim3(256), 0, st, a);
+    const int64_t bgrid = n_jobs < (int64_t)n_cu * 8 ? n_jobs : (int64_t)n_cu * 8;
+    hipLaunchKernelGGL(hs_rows_block_kernel, dim3((unsigned)bgrid), dim3(256), 0, st, a);
+    const unsigned cgrid = ig_grid(nq * IG_WAVE, n_cu);
+    for (int t = 0; t <= a.n_types; ++t) {
+      const bool term = t < a.n_types;
+      int64_t* rp = term ? term_row_ptr[t] : excl_row_ptr;
+      e = launch_scan_i32(st, term ? a.ev[t].len : a.excl_len, nq, rp, tile_sums);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(ig_compact_rows_kernel, dim3(cgrid), dim3(256), 0, st, nq, term ? a.ev[t].raw_ptr : a.excl_raw_ptr, term ? a.ev[t].tmp : a.excl_tmp, rp,
+                         term ? term_col_idx[t] : excl_col_idx);
+    }
+  } else {
+    for (int t = 0; t <= a.n_types; ++t) {
+      e = hipMemsetAsync(t < a.n_types ? term_row_ptr[t] : excl_row_ptr, 0, sizeof(int64_t), st);
+      if (e != hipSuccess) return e;
+    }
+  }
+  if (stats_dev) {
+    e = hipMemcpyAsync(stats_dev, a.ctr + 1, sizeof(int64_t) * HIST_STATS_LEN, hipMemcpyDeviceToDevice, st);
+    if (e != hipSuccess) return e;
+  }
+  return hipGetLastError();
+}
+
+}  // namespace urcco

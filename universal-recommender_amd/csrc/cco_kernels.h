@@ -281,6 +281,43 @@ hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t
                             unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit = REC_LDS_LIMIT, const RecRule* rules = nullptr,
                             int32_t n_rules = 0);
 
+// ---- device-resident user history (cco_history.h, compiled into ingest_kernels.hip; decision D17) ----------------------
+constexpr int HIST_STATS_LEN = 8;   // == URCCO_HIST_STATS_LEN of include/urcco.h
+enum { HIST_STAT_WAVE = 0, HIST_STAT_BLOCK = 1, HIST_STAT_GLOBAL = 2, HIST_STAT_SELECT = 3, HIST_STAT_EXCL_WAVE = 4, HIST_STAT_EXCL_BLOCK = 5, HIST_STAT_OVERFLOW = 6 };
+struct HistEvent {
+  const int64_t* idx_row_ptr;  // the stream's positions by user (launch_history_index)
+  const int32_t* idx_pos;
+  const int32_t* items;        // the stream: column id per event, < 0 = none
+  const int64_t* times_ms;     // nullable: stream order is time order
+  const int32_t* col_map;      // nullable (identity): column id -> item id of the primary or -1
+  int64_t* raw_ptr;            // scratch [n_queries + 1]: the raw row starts (scan of the bounds)
+  int32_t* tmp;                // scratch [capacity]: the raw rows
+  int32_t* len;                // scratch [n_queries]: the rows' final lengths
+  int64_t capacity;            // entries of the caller's term_col_idx (and of tmp)
+  int32_t n_cols, max_items, blacklist, reserved;
+};
+struct HistArgs {
+  HistEvent ev[REC_MAX_CLAUSES];
+  int64_t n_queries, n_users;
+  const int32_t* q_users;
+  const int64_t* extra_row_ptr;  // nullable pair: the caller's own exclusions per query
+  const int32_t* extra_col_idx;
+  int64_t* excl_raw_ptr;         // scratch, as in HistEvent
+  int32_t* excl_tmp;
+  int32_t* excl_len;
+  int64_t excl_capacity;
+  int32_t* big_list;             // scratch [n_queries * (n_types + 1)]: jobs of more than one wave
+  unsigned long long* ctr;       // scratch [1 + HIST_STATS_LEN]
+  int32_t n_types, n_items;
+};
+// cnt [n_users], tile_sums: scratch
+hipError_t launch_history_index(hipStream_t st, int n_cu, int64_t n, const int32_t* users, int64_t n_users, int32_t* cnt, int64_t* tile_sums, int64_t* out_row_ptr,
+                                int32_t* out_pos);
+// bnd [(n_types + 1) * n_queries]: scratch; only the inputs of `a` are read
+hipError_t launch_history_bounds(hipStream_t st, int n_cu, const HistArgs& a, int32_t* bnd, int64_t* tile_sums, int64_t* const* term_row_ptr, int64_t* excl_row_ptr);
+hipError_t launch_history_rows(hipStream_t st, int n_cu, const HistArgs& a, int64_t* tile_sums, int64_t* const* term_row_ptr, int32_t* const* term_col_idx,
+                               int64_t* excl_row_ptr, int32_t* excl_col_idx, int64_t* stats_dev);
+
 hipError_t launch_llr_test(hipStream_t st, int64_t n, const int64_t* a, const int64_t* b, const int64_t* ab, const int64_t* nu, double* out);
 hipError_t launch_u01_test(hipStream_t st, int64_t n, uint32_t seed, const int32_t* row, const int32_t* col, double* out, int rng32 = 0);
 

@@ -720,6 +720,89 @@ int urcco_dev_pop_counts(urcco_session* s, int64_t n_events, const int32_t* item
 
 }  // extern "C"
 
+// urcco_dev_history_bounds / _rows: argument checks and the launch arguments; rows: also the output arrays
+static int history_args(const char* who, urcco_session* s, int64_t n_queries, const int32_t* q_users, int64_t n_users, const urcco_hist_event* events, int32_t n_types,
+                        const int64_t* extra_row_ptr, const int32_t* extra_col_idx, const int64_t* excl_row_ptr, bool rows, urcco::HistArgs* a) {
+  if (!s || n_queries < 0 || n_users < 0 || (n_queries > 0 && !q_users) || !excl_row_ptr) return fail(URCCO_BAD_ARG, "%s: bad argument", who);
+  if (n_types < 1 || n_types > URCCO_REC_MAX_CLAUSES || !events) return fail(URCCO_BAD_ARG, "%s: between 1 and %d event types, got %d", who, URCCO_REC_MAX_CLAUSES, n_types);
+  if (n_queries * (int64_t)(n_types + 1) > 0x7ffffff0ll) return fail(URCCO_BAD_ARG, "%s: too many queries", who);
+  if ((extra_row_ptr == nullptr) != (extra_col_idx == nullptr)) return fail(URCCO_BAD_ARG, "%s: the extra exclusion CSR needs both of its arrays", who);
+  *a = urcco::HistArgs{};
+  for (int t = 0; t < n_types; ++t) {
+    const urcco_hist_event& in = events[t];
+    if (in.max_items < 1) return fail(URCCO_BAD_ARG, "%s: event type %d: max_items must be >= 1, got %d", who, t, in.max_items);
+    if (in.n_cols < 0 || !in.idx_row_ptr || !in.idx_pos || !in.items || !in.term_row_ptr || (rows && (!in.term_col_idx || in.term_capacity < 0)))
+      return fail(URCCO_BAD_ARG, "%s: event type %d: bad argument", who, t);
+    urcco::HistEvent& e = a->ev[t];
+    e.idx_row_ptr = in.idx_row_ptr; e.idx_pos = in.idx_pos; e.items = in.items; e.times_ms = in.times_ms; e.col_map = in.col_map;
+    e.capacity = in.term_capacity; e.n_cols = in.n_cols; e.max_items = in.max_items; e.blacklist = in.blacklist != 0;
+  }
+  a->n_queries = n_queries; a->n_users = n_users; a->q_users = q_users; a->extra_row_ptr = extra_row_ptr; a->extra_col_idx = extra_col_idx; a->n_types = n_types;
+  return URCCO_OK;
+}
+
+extern "C" {
+
+int urcco_dev_history_index(urcco_session* s, int64_t n_events, const int32_t* users, int64_t n_users, int64_t* out_row_ptr, int32_t* out_pos) {
+  if (!s || n_events < 0 || n_events > 0x7fffffffll || n_users < 0 || n_users > 0x7ffffff0ll || !out_row_ptr || (n_events > 0 && (!users || !out_pos)))
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_index: bad argument (a stream holds fewer than 2^31 events)");
+  const int64_t n_tiles = (n_users + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
+  URC(s->reserve(urcco_session::need((size_t)n_users, 4) + urcco_session::need((size_t)n_tiles + 2, 8)));
+  int32_t* cnt = s->take<int32_t>((size_t)n_users);
+  int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
+  HIPC(urcco::launch_history_index(s->stream, s->n_cu, n_events, users, n_users, cnt, tile_sums, out_row_ptr, out_pos));
+  return URCCO_OK;
+}
+
+int urcco_dev_history_bounds(urcco_session* s, int64_t n_queries, const int32_t* q_users, int64_t n_users, urcco_hist_event* events, int32_t n_types,
+                             const int64_t* extra_row_ptr, const int32_t* extra_col_idx, int64_t* excl_row_ptr) {
+  urcco::HistArgs a;
+  URC(history_args("urcco_dev_history_bounds", s, n_queries, q_users, n_users, events, n_types, extra_row_ptr, extra_col_idx, excl_row_ptr, false, &a));
+  const int64_t n_tiles = (n_queries + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
+  URC(s->reserve(urcco_session::need((size_t)n_queries * (size_t)(n_types + 1), 4) + urcco_session::need((size_t)n_tiles + 2, 8)));
+  int32_t* bnd = s->take<int32_t>((size_t)n_queries * (size_t)(n_types + 1));
+  int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
+  int64_t* rp[URCCO_REC_MAX_CLAUSES];
+  for (int t = 0; t < n_types; ++t) rp[t] = events[t].term_row_ptr;
+  HIPC(urcco::launch_history_bounds(s->stream, s->n_cu, a, bnd, tile_sums, rp, excl_row_ptr));
+  return URCCO_OK;
+}
+
+int urcco_dev_history_rows(urcco_session* s, int64_t n_queries, const int32_t* q_users, int64_t n_users, urcco_hist_event* events, int32_t n_types,
+                           const int64_t* extra_row_ptr, const int32_t* extra_col_idx, int32_t n_items, int64_t* excl_row_ptr, int32_t* excl_col_idx,
+                           int64_t excl_capacity, int64_t* stats_dev) {
+  urcco::HistArgs a;
+  URC(history_args("urcco_dev_history_rows", s, n_queries, q_users, n_users, events, n_types, extra_row_ptr, extra_col_idx, excl_row_ptr, true, &a));
+  if (n_items < 0 || !excl_col_idx || excl_capacity < 0) return fail(URCCO_BAD_ARG, "urcco_dev_history_rows: bad argument");
+  const int64_t n_tiles = (n_queries + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
+  const size_t nq = (size_t)n_queries, n_jobs = nq * (size_t)(n_types + 1);
+  size_t bytes = urcco_session::need((size_t)n_tiles + 2, 8) + urcco_session::need(n_jobs, 4) + urcco_session::need(1 + URCCO_HIST_STATS_LEN, 8) +
+                 (size_t)(n_types + 1) * (urcco_session::need(nq + 1, 8) + urcco_session::need(nq, 4)) + urcco_session::need((size_t)excl_capacity, 4);
+  for (int t = 0; t < n_types; ++t) bytes += urcco_session::need((size_t)events[t].term_capacity, 4);
+  URC(s->reserve(bytes));
+  int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
+  a.big_list = s->take<int32_t>(n_jobs);
+  a.ctr = s->take<unsigned long long>(1 + URCCO_HIST_STATS_LEN);
+  int64_t* rp[URCCO_REC_MAX_CLAUSES];
+  int32_t* ci[URCCO_REC_MAX_CLAUSES];
+  for (int t = 0; t < n_types; ++t) {
+    a.ev[t].raw_ptr = s->take<int64_t>(nq + 1);
+    a.ev[t].len = s->take<int32_t>(nq);
+    a.ev[t].tmp = s->take<int32_t>((size_t)events[t].term_capacity);
+    rp[t] = events[t].term_row_ptr;
+    ci[t] = events[t].term_col_idx;
+  }
+  a.excl_raw_ptr = s->take<int64_t>(nq + 1);
+  a.excl_len = s->take<int32_t>(nq);
+  a.excl_tmp = s->take<int32_t>((size_t)excl_capacity);
+  a.excl_capacity = excl_capacity;
+  a.n_items = n_items;
+  HIPC(urcco::launch_history_rows(s->stream, s->n_cu, a, tile_sums, rp, ci, excl_row_ptr, excl_col_idx, stats_dev));
+  return URCCO_OK;
+}
+
+}  // extern "C"
+
 // urcco_dev_recommend (n_rules == 0) and urcco_dev_recommend_rules
 static int recommend_call(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
                           const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,

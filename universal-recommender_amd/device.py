@@ -253,6 +253,56 @@ class DeviceSession:
         n = max(n_queries, 0)
         return o_count[:n], o_idx[: n * max(num, 0)].view(n, -1) if n and num > 0 else o_idx[:0], o_score[: n * max(num, 0)].view(n, -1) if n and num > 0 else o_score[:0], st
 
+    def history_index(self, users: torch.Tensor, n_users: int):
+        """urcco_dev_history_index: the stream positions of every user's events.  users: int32 dense user id per event (< 0: nobody's).
+        Returns (row_ptr int64 [n_users + 1], pos int32 [n_events]); the order inside a user's segment is unspecified.  Does not synchronise."""
+        n = int(users.numel())
+        row_ptr = self.empty(n_users + 1, torch.int64)
+        pos = self.empty(max(n, 1), torch.int32)
+        self._check(self.lib.urcco_dev_history_index(self.handle, n, _ptr(users), n_users, _ptr(row_ptr), _ptr(pos)))
+        return row_ptr, pos
+
+    def history_rows(self, q_users: torch.Tensor, n_users: int, events, n_items: int, extra=None, stats: bool = False, timing: bool = False, keep_bounds: bool = False):
+        """urcco_dev_history_bounds + urcco_dev_history_rows: the user-history term rows and the exclusion rows of a batch of queries.
+        q_users: int32 [n_queries] dense user ids (< 0 or >= n_users: unknown).  events: per event type (n_cols, max_items, blacklist, idx_row_ptr, idx_pos,
+        items, times_ms | None, col_map | None), device tensors (idx_*: history_index of the stream).  extra: (row_ptr, col_idx) of the caller's own
+        exclusions per query, or None.  Returns (terms, excl, info): terms[t] = (row_ptr int64 [n_queries + 1], col_idx int32) sorted unique columns
+        of the most recent max_items events, excl = the same pair over the primary's items, info = {"bounds": [...], "stats": int64 tensor | None,
+        "ms": device time of the two calls | None, "bound_row_ptr": copies of the bounds' row_ptr arrays with keep_bounds (tests)}.  Reads the 1 + n_types bound totals between the two calls: one synchronisation."""
+        nq = int(q_users.numel())
+        arr = (_lib.HistEvent * max(len(events), 1))()
+        rps = []
+        for t, (n_cols, max_items, blacklist, irp, ipos, items, times, cmap) in enumerate(events):
+            rp = self.empty(nq + 1, torch.int64)
+            rps.append(rp)
+            arr[t].n_cols, arr[t].max_items, arr[t].blacklist = int(n_cols), int(max_items), int(bool(blacklist))
+            arr[t].idx_row_ptr, arr[t].idx_pos, arr[t].items, arr[t].times_ms, arr[t].col_map = _ptr(irp), _ptr(ipos), _ptr(items), _ptr(times), _ptr(cmap)
+            arr[t].term_row_ptr = _ptr(rp)
+        excl_rp = self.empty(nq + 1, torch.int64)
+        x_rp, x_ci = (_ptr(extra[0]), _ptr(extra[1])) if extra is not None else (None, None)
+        ev0 = ev1 = None
+        if timing and self.device.type == "cuda":
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record(self.torch_stream)
+        self._check(self.lib.urcco_dev_history_bounds(self.handle, nq, _ptr(q_users), n_users, arr, len(events), x_rp, x_ci, _ptr(excl_rp)))
+        totals = torch.stack([rp[nq] for rp in rps] + [excl_rp[nq]]).cpu().tolist()   # the one synchronisation
+        bound_rp = [rp.clone() for rp in rps + [excl_rp]] if keep_bounds else None
+        cis = []
+        for t, total in enumerate(totals[:-1]):
+            ci = self.empty(max(total, 1), torch.int32)
+            cis.append(ci)
+            arr[t].term_col_idx, arr[t].term_capacity = _ptr(ci), int(total)
+        excl_ci = self.empty(max(totals[-1], 1), torch.int32)
+        st = self.empty(_lib.HIST_STATS_LEN, torch.int64) if stats else None
+        self._check(self.lib.urcco_dev_history_rows(self.handle, nq, _ptr(q_users), n_users, arr, len(events), x_rp, x_ci, int(n_items), _ptr(excl_rp), _ptr(excl_ci),
+                                                   int(totals[-1]), _ptr(st)))
+        ms = None
+        if ev0 is not None:
+            ev1.record(self.torch_stream)
+            ev1.synchronize()
+            ms = ev0.elapsed_time(ev1)
+        return list(zip(rps, cis)), (excl_rp, excl_ci), {"bounds": totals, "stats": st, "ms": ms, "bound_row_ptr": bound_rp}
+
     def llr(self, with_a, with_b, with_ab, n_users) -> torch.Tensor:
         out = self.empty(with_a.numel(), torch.float64)
         self._check(self.lib.urcco_dev_llr(self.handle, with_a.numel(), _ptr(with_a), _ptr(with_b), _ptr(with_ab), _ptr(n_users), _ptr(out)))

@@ -208,9 +208,15 @@ def _date_ms(text: str, what: str) -> int:
     return ms
 
 
-def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history: Dict[str, Dict[str, List[str]]], item_mask=None, now_ms: Optional[int] = None) -> List[dict]:
+def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None) -> List[dict]:
     """URAlgorithm.predict for a list of query dicts: [{"itemScores": [{"item", "score"}, ...]}, ...] in the order of `queries`.
-    history: user -> {event name: [item ids, oldest first]} (the event store's view of the user); item_mask: None, an array of n_items
+    history: user -> {event name: [item ids, oldest first]} (the event store's view of the user), or a history.DeviceHistory: the event streams
+    resident on the device.  With a DeviceHistory the user-history term rows (the ("user", ev) clauses, or the ("hist", ev) ANY rules under
+    userBias < 0) and the blacklist events' part of the exclusions come from one urcco_dev_history_bounds + _rows call per group (decision D17);
+    blacklistItems, the query item and the item set go into that call as its extra exclusion rows.  Queries then share a call only when they name
+    the same event types, and a group in which any member names a user carries the user clause of EVERY event type of the query, also where all
+    its rows turn out empty (the dict form leaves such a clause out): an all-empty clause adds 0.0 * boost and leaves every score bit-identical,
+    but the 16-clause limit of a call can be reached earlier than with the dict form.  item_mask: None, an array of n_items
     flags or {item: bool} (any further filter of the caller's; items not named are eligible -- it applies on top of the rules); now_ms: "now" of the
     available / expire rule for queries without `currentDate` (default: the wall clock)."""
     ap = algo.ap
@@ -246,6 +252,8 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history: Di
     groups: Dict[tuple, List[int]] = {}
     plans = []
     served = model.properties is not None
+    from .history import DeviceHistory
+    dh = history if isinstance(history, DeviceHistory) else None
     dated = served and ap.availableDateName is not None and ap.expireDateName is not None and ap.availableDateName in model.dates and ap.expireDateName in model.dates
     for n, q in enumerate(queries):
         user_bias = q.get("userBias", ap.userBias if ap.userBias is not None else 1.0)
@@ -294,8 +302,13 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history: Di
         user, item, item_set = q.get("user"), q.get("item"), list(q.get("itemSet") or [])
         terms: Dict[tuple, np.ndarray] = {}
         excl: List[int] = []
-        events = history.get(user, {}) if user is not None else {}
-        for ev in q_events:                                                                     # getBiasedRecentUserActions :795-839
+        events = history.get(user, {}) if user is not None and dh is None else {}
+        hist_key = None
+        if dh is not None:                                                                      # the rows come from the device, per group (D17)
+            hist_key = (tuple(ev for ev in q_events if ev in dh.types and (ev in model.by_name or ev in blacklist_events)), user_bias < 0)
+            if user_bias < 0:
+                rules.update({("hist", ev): None if ev in dh.types else np.zeros(0, np.int64) for ev in q_events if ev in model.by_name})
+        for ev in (q_events if dh is None else ()):                                             # getBiasedRecentUserActions :795-839
             c = model.by_name.get(ev)
             if c is None:
                 continue
@@ -335,15 +348,26 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history: Di
         for slot, cols in boosted:
             terms[("field",) + slot] = cols
         # a rule cannot be absent for one row of a call: queries share a call only when they carry the same rules and the same property clauses
-        key = (_boost(user_bias), _boost(item_bias), _boost(set_bias), start + num, tuple(slot for slot, _ in boosted), tuple(rules))
+        key = (_boost(user_bias), _boost(item_bias), _boost(set_bias), start + num, tuple(slot for slot, _ in boosted), tuple(rules), hist_key)
         groups.setdefault(key, []).append(n)
-        plans.append((terms, np.unique(np.array([i for i in excl if i is not None], np.int64)), start, num, rules))
+        plans.append((terms, np.unique(np.array([i for i in excl if i is not None], np.int64)), start, num, rules, dh.user_index(user) if dh is not None else -1,
+                      user is not None))
 
     # ---- one call per group ----
     results: List[Optional[dict]] = [None] * len(queries)
     dev = model.sess.device
     empty = np.zeros(0, np.int64)
-    for (ub, ib, sb, fetch, field_slots, rule_keys), members in groups.items():
+    for (ub, ib, sb, fetch, field_slots, rule_keys, hist_key), members in groups.items():
+        hist_rows: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        excl = _csr([plans[n][1] for n in members], dev)
+        if hist_key is not None and hist_key[0]:                                                # one history call for the group
+            if len(hist_key[0]) > _lib.REC_MAX_CLAUSES:
+                raise ValueError(f"a batch names {len(hist_key[0])} event types, more than the {_lib.REC_MAX_CLAUSES} one history call serves")
+            specs = [(dh.types[ev].n_cols, max_items.get(ev, 100), ev in blacklist_events, dh.types[ev].idx_row_ptr, dh.types[ev].idx_pos, dh.types[ev].items,
+                      dh.types[ev].times, dh.types[ev].col_map) for ev in hist_key[0]]
+            q_users = torch.tensor([plans[n][5] for n in members], dtype=torch.int32).to(dev)
+            rows, excl, _ = model.sess.history_rows(q_users, dh.n_users, specs, model.n_items, excl)
+            hist_rows = {ev: r for ev, r in zip(hist_key[0], rows) if ev in model.by_name}
         slots = []                                                                              # the reference's order (:653): history, similar items, metadata, item set
         for kind, boost in (("user", ub), ("item", ib), ("field", None), ("set", sb)):
             if kind == "field":
@@ -351,6 +375,10 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history: Di
                           if any(plans[n][0][("field",) + slot].size for n in members)]
                 continue
             for ev in ([primary] if kind == "set" else model_events if kind == "item" else list(model.by_name)):
+                if kind == "user" and dh is not None:
+                    if ev in hist_rows and not hist_key[1] and any(plans[n][6] for n in members):
+                        slots.append(((kind, ev), model.by_name[ev], boost))
+                    continue
                 if any(plans[n][0].get((kind, ev), empty).size for n in members):
                     slots.append(((kind, ev), model.by_name[ev], boost))
         if len(slots) > _lib.REC_MAX_CLAUSES:
@@ -359,7 +387,7 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history: Di
             raise ValueError(f"a batch needs {len(rule_keys)} rules, more than the {_lib.REC_MAX_RULES} one call serves")
         clauses = []
         for slot, c, boost in slots:
-            qrp, qci = _csr([plans[n][0].get(slot, empty) for n in members], dev)
+            qrp, qci = hist_rows[slot[1]] if slot[0] == "user" and dh is not None else _csr([plans[n][0].get(slot, empty) for n in members], dev)
             clauses.append((c.n_cols, boost, c.col_ptr, c.row_idx, qrp, qci))
         rules = None
         if served:
@@ -373,9 +401,8 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history: Di
                     rules.append((_lib.RULE_RANGE, value, lo, hi))
                 else:
                     m = model.properties[rk[1]] if rk[0] in ("any", "none") else model.by_name[rk[1]] if rk[0] in ("hist", "sim") else model.correlators[0]
-                    qrp, qci = _csr([plans[n][4][rk] for n in members], dev)
+                    qrp, qci = hist_rows[rk[1]] if rk[0] == "hist" and rk[1] in hist_rows else _csr([plans[n][4][rk] for n in members], dev)
                     rules.append((_lib.RULE_NONE if rk[0] == "none" else _lib.RULE_ANY, m.n_cols, m.row_ptr, m.col_idx, qrp, qci))
-        excl = _csr([plans[n][1] for n in members], dev)
         count, idx, score, _ = model.sess.recommend(len(members), model.n_items, clauses, fetch, excl, mask_t, model.fill_order, flags, stats=False, rules=rules)
         model.sess.synchronize()
         count, idx, score = count.cpu().numpy(), idx.cpu().numpy(), score.cpu().numpy()

@@ -264,14 +264,15 @@ class URAlgorithm:
         return list(zip([n for n, _ in data.actions], res))                                    # :349
 
 
-    def batch_predict(self, model, queries: Sequence[dict], history: Dict[str, Dict[str, List[str]]], item_mask=None, now_ms: Optional[int] = None) -> List[dict]:
+    def batch_predict(self, model, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None) -> List[dict]:
         """URAlgorithm.predict (:484-535) for a batch of queries against a recommend.DeviceModel: user history, similar-item and itemSet
         queries, blacklists, backfill by rank and -- for a model built with item properties -- the business rules (fields, dateRange, available /
-        expire dates around now_ms, negative biases); see recommend.batch_predict for what is mirrored and what is left out."""
+        expire dates around now_ms, negative biases); see recommend.batch_predict for what is mirrored and what is left out.  history: the dict
+        user -> {event: [items, oldest first]} or a history.DeviceHistory (the event streams resident on the device)."""
         from .recommend import batch_predict
         return batch_predict(self, model, queries, history, item_mask, now_ms)
 
-    def predict(self, model, query: dict, history: Dict[str, Dict[str, List[str]]], item_mask=None, now_ms: Optional[int] = None) -> dict:
+    def predict(self, model, query: dict, history, item_mask=None, now_ms: Optional[int] = None) -> dict:
         return self.batch_predict(model, [query], history, item_mask, now_ms)[0]
 
     def train_events_on_device(self, trainingData, sess) -> List[Tuple[str, IndexedDataset]]:
