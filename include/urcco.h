@@ -540,7 +540,9 @@ int urcco_dev_recommend_rules(urcco_session* s, int64_t n_queries, int32_t n_ite
  *   blacklist events + extra row).  The caller reads the 1 + n_types totals (term_row_ptr[n_queries], excl_row_ptr[n_queries]: its one synchronisation),
  *   allocates term_col_idx / excl_col_idx of at least that many entries and states the sizes in term_capacity / excl_capacity.
  * urcco_dev_history_rows: the same arguments, the row_ptr arrays as _bounds left them; on return they hold the final row starts and the col_idx arrays
- *   the rows.  A capacity below the bound leaves the rows past it empty and counts them in stats[6].
+ *   the rows.  A capacity below a bound total: a row is written iff its bound ENDS within the capacity (row_ptr[q + 1] as _bounds left it <= capacity);
+ *   every other row of that array -- all rows behind the first one cut, those of bound 0 included -- is left empty and counted in stats[6], and
+ *   stats[0..5] count the written rows only.  Nothing is written at or past col_idx[capacity].
  * stats_dev (nullable, int64[URCCO_HIST_STATS_LEN]): (query, type) pairs served by [0] the wave class (<= 64 events), [1] the block class (<= 4096, keys in
  *   LDS), [2] the global class; [3] pairs that ran the select (n_u > max_items); exclusion rows built by [4] one wave, [5] one block; [6] rows dropped
  *   for lack of capacity (0 when the caller sized its buffers by the bounds); [7] 0.

@@ -1,5 +1,9 @@
 """urcco_dev_history_* on the MI355X against the numpy restatement of decision D17 (tests/history_ref.py): the problem and the checks of
-tests/test_sim_history.py, one larger shape, and batch_predict with a DeviceHistory against batch_predict with the dict."""
+tests/test_sim_history.py, one larger shape, and batch_predict with a DeviceHistory against batch_predict with the dict.
+
+The keys of the select, by byte, as in tests/test_sim_history.py: every time byte 0..7 alone, two bytes around uniform ones, the whole int64 domain and
+equal times (make_key_problem); the top position byte with a real index over 2^24 + 2^16 events (make_far_problem).  The capacity clause of
+include/urcco.h runs with 256 sentinel entries behind every buffer; DeviceHistory.from_streams with real times runs against the dict form."""
 import numpy as np
 import pytest
 import torch
@@ -50,6 +54,57 @@ def test_rows_do_not_depend_on_the_order_inside_the_index(gpu_session, problem, 
             assert all(np.array_equal(x, y) and np.array_equal(x, z) for x, y, z in zip(ra, rb, rc))
 
 
+@pytest.fixture(scope="module")
+def key_problem():
+    return H.make_key_problem()
+
+
+@pytest.fixture(scope="module")
+def key_dev(gpu_session, key_problem):
+    return H.DeviceProblem(gpu_session, key_problem)
+
+
+@pytest.mark.parametrize("cap", H.KEY_CAPS)
+def test_key_domain_rows_match_the_restatement(key_dev, cap):
+    stats, _, _ = H.check(key_dev, [cap, cap])
+    assert stats[0] > 0 and stats[1] > 0 and stats[2] > 0 and stats[3] > 0, stats
+
+
+def test_key_domain_rows_do_not_depend_on_the_index_order_or_the_job_before(gpu_session, key_problem, key_dev):
+    H.assert_key_edge_cases(key_problem)
+    other = H.DeviceProblem(gpu_session, key_problem, shuffle_index_seed=4)
+    byte0 = H.DeviceProblem(gpu_session, H.make_byte0_job())
+    for cap in (20, 150, 2048):
+        _, terms_a, excl_a = H.check(key_dev, [cap, 7])
+        stats, _, _ = H.check(byte0, [100])           # one job whose keys differ in the lowest time byte alone, between two runs over every byte
+        assert stats[1] == 1 and stats[3] == 1 and stats[0] + stats[2] == 0, stats
+        _, terms_b, excl_b = H.check(other, [cap, 7])
+        for ra, rb in zip(terms_a + [excl_a], terms_b + [excl_b]):
+            assert all(np.array_equal(x, y) for x, y in zip(ra, rb))
+
+
+def test_positions_beyond_2_24(gpu_session):
+    """One stream of 2^24 + 2^16 events indexed on the device; the five users' segments against np.flatnonzero, the rows (no times / equal times: the
+    top position digit decides) against the restatement over those users' events; caps below, at and above each user's events at or above 2^24."""
+    p = H.make_far_problem()
+    d = H.DeviceProblem(gpu_session, p, subset=range(p.n_users))
+    for s, (_, rp, pos, *_rest) in zip(p.streams, d.ev):
+        rp, rows = H.csr_rows(rp, pos)
+        assert rp[-1] == sum(n for n, _ in H.FAR_USERS) + 4 and rows[len(H.FAR_USERS)].size == 0
+        for u in range(len(H.FAR_USERS)):
+            assert np.array_equal(np.sort(rows[u]), d.by_user[0][u][::-1])       # without times: most recent first = positions descending
+    for cap in H.far_caps(p):
+        stats, terms, _ = H.check(d, [cap, cap])
+        assert stats[0] > 0 and stats[1] > 0 and stats[2] > 0 and stats[3] > 0, stats
+        assert np.array_equal(terms[0][3], terms[1][3])
+
+
+@pytest.mark.parametrize("cap", (5, 100))
+def test_capacity_below_the_bounds(dev, cap):
+    """256 sentinel entries behind every capacity: none is written."""
+    H.capacity_cases(dev, [cap] * 3, pad=256)
+
+
 def test_larger_shape(gpu_session):
     """20 000 users, 2 M events, one user with 300 000 of them, cap 500; 2 000 sampled queries (the heavy user among them)."""
     rng = np.random.default_rng(17)
@@ -95,3 +150,11 @@ def test_batch_predict_dict_against_device_history(gpu_session):
         for q, w, g in zip(qs, want, got):
             assert g == w, (blacklist, q)
     assert any(s["score"] > 0 for r in want for s in r["itemScores"])
+
+
+def test_batch_predict_dict_against_from_streams(gpu_session):
+    """DeviceHistory.from_streams -- integer user ids, shuffled events, int64 times with ties and negative values, one type without times -- gives
+    batch_predict the answers of the dict sorted by (time, position) on the host; users resolved by a dict and by their integer id."""
+    algo, model = H.predict_stack(gpu_session, 3000, 400, 250)
+    streams, history = H.make_stream_history(41, 120, 400, 250)
+    H.check_from_streams(gpu_session, algo, model, 120, streams, history)

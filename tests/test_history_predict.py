@@ -1,7 +1,9 @@
 """batch_predict with the user history resident on the device (history.DeviceHistory, decision D17) returns exactly the items and scores it
 returns with the dict form of `history`: the handmade fixture of tests/test_recommend_golden.py plus a synthetic user with more events than
-maxItemsPerUser, on the simulator session."""
+maxItemsPerUser, on the simulator session; and DeviceHistory.from_streams with real times (negative ones, ties) against the dict sorted on the host."""
 import pytest
+
+import history_ref as H
 
 from test_recommend_golden import _load
 
@@ -74,3 +76,11 @@ def test_device_history_gives_the_dicts_answers(sim_session, cap):
     scores = {s["item"]: s["score"] for s in res["itemScores"]}
     assert all(scores[s["item"]] == s["score"] for s in res_trimmed["itemScores"] if s["item"] in scores)
     assert {s["item"] for s in res_trimmed["itemScores"]} - set(scores) <= set(old)
+
+
+def test_from_streams_gives_the_dicts_answers(sim_session):
+    """Integer user ids, shuffled events, int64 times from the key families of tests/history_ref.py, one event type without times; caps 6 and 70 against
+    0..150 events per user; users resolved by a dict and by their integer id; the ValueErrors of from_streams."""
+    algo, model = H.predict_stack(sim_session, 400, 60, 40)
+    streams, history = H.make_stream_history(41, 60, 60, 40)
+    H.check_from_streams(sim_session, algo, model, 60, streams, history)

@@ -1,5 +1,11 @@
 """urcco_dev_history_index / _bounds / _rows on the host simulator (kernel LOGIC on the CPU) against the numpy restatement of decision D17
-(tests/history_ref.py): exact in every term row, exclusion row and final row_ptr, for caps on both sides of every class boundary."""
+(tests/history_ref.py): exact in every term row, exclusion row and final row_ptr, for caps on both sides of every class boundary.
+
+The keys of the select, by byte: make_problem's times differ in the lowest time byte alone; make_key_problem lets each time byte 0..7 be the only
+one that differs (positive and negative base, byte 7 across the sign bit), two bytes around uniform ones, the whole int64 domain with INT64_MIN / -1 /
+0 / INT64_MAX planted, and equal times; the position bytes 0..2 differ throughout, make_far_problem adds the top one (positions on both sides of 2^24).
+Clauses of include/urcco.h beyond the rows themselves: a capacity below the bound (served prefix, empty rows behind it, stats[6], stats[0..5] of the
+served rows only, nothing written past the capacity -- the guard-page rerun faults on it) and URCCO_BAD_ARG for a negative capacity."""
 import os
 import subprocess
 import sys
@@ -98,7 +104,7 @@ def test_bad_arguments(dev):
     lib = s.lib
     nq = dev.q_users.numel()
 
-    def call(events=None, n_types=None, extra=(None, None), rows=False):
+    def call(events=None, n_types=None, extra=(None, None), rows=False, term_capacity=0, excl_capacity=0):
         events = events if events is not None else dev.events([5] * 3)
         arr = (_lib.HistEvent * max(len(events), 17))()
         keep = []
@@ -107,12 +113,12 @@ def test_bad_arguments(dev):
             keep += [rp, ci]
             arr[t].n_cols, arr[t].max_items, arr[t].blacklist = n_cols, cap, int(bl)
             arr[t].idx_row_ptr, arr[t].idx_pos, arr[t].items = irp.data_ptr(), ipos.data_ptr(), items.data_ptr() if items is not None else None
-            arr[t].term_row_ptr, arr[t].term_col_idx = rp.data_ptr(), ci.data_ptr()
+            arr[t].term_row_ptr, arr[t].term_col_idx, arr[t].term_capacity = rp.data_ptr(), ci.data_ptr(), term_capacity
         xrp = s.empty(nq + 1, torch.int64)
         n = len(events) if n_types is None else n_types
         if rows:
             return lib.urcco_dev_history_rows(s.handle, nq, dev.q_users.data_ptr(), dev.p.n_users, arr, n, extra[0], extra[1], dev.p.n_items, xrp.data_ptr(),
-                                              xrp.data_ptr(), 0, None)
+                                              xrp.data_ptr(), excl_capacity, None)
         return lib.urcco_dev_history_bounds(s.handle, nq, dev.q_users.data_ptr(), dev.p.n_users, arr, n, extra[0], extra[1], xrp.data_ptr())
 
     ok = dev.events([5] * 3)
@@ -124,6 +130,9 @@ def test_bad_arguments(dev):
         assert call(events=[ok[0][:5] + (None,) + ok[0][6:]], rows=rows) == _lib.BAD_ARG                   # a NULL the call needs
         assert call(extra=(dev.extra[0].data_ptr(), None), rows=rows) == _lib.BAD_ARG                      # a half-NULL extra pair
         assert call(extra=(None, dev.extra[1].data_ptr()), rows=rows) == _lib.BAD_ARG
+    assert call(rows=True, term_capacity=-1) == _lib.BAD_ARG                                               # a negative capacity
+    assert call(rows=True, excl_capacity=-1) == _lib.BAD_ARG
+    assert call(events=ok[:2] + [ok[2]], rows=True, excl_capacity=-(1 << 40)) == _lib.BAD_ARG
     out = s.empty(4, torch.int64)
     assert lib.urcco_dev_history_index(s.handle, 1 << 31, out.data_ptr(), 1, out.data_ptr(), out.data_ptr()) == _lib.BAD_ARG   # n_events >= 2^31
     assert lib.urcco_dev_history_index(s.handle, 1, None, 1, out.data_ptr(), out.data_ptr()) == _lib.BAD_ARG
@@ -138,6 +147,75 @@ def test_no_queries_and_no_users(sim_session):
     d = H.DeviceProblem(sim_session, p)
     terms, excl, _ = sim_session.history_rows(d.q_users[:0], 0, d.events([3]), 4, d.extra)   # no queries at all
     assert terms[0][0].tolist() == [0] and excl[0].tolist() == [0]
+
+
+def test_restatement_orders_the_whole_int64_domain():
+    """user_positions over INT64_MIN, -1, 0, INT64_MAX (duplicated: ties by position) against sorted() on Python ints; the subset form agrees"""
+    rng = np.random.default_rng(1)
+    special = [H.I64_MIN, -1, 0, H.I64_MAX, H.I64_MIN + 1, H.I64_MAX - 1, 1]
+    times = np.array(special * 3 + [int(x) for x in rng.integers(-5, 5, 30)], np.int64)[rng.permutation(51)]
+    users = rng.integers(-1, 3, 51).astype(np.int32)
+    users[np.flatnonzero(np.isin(times, special[:4]))[::2]] = 1
+    s = H.Stream(4, users, np.zeros(51, np.int32), times, None, True)
+    got = H.user_positions(s, 3)
+    sub = H.user_positions_of(s, [1, 2])
+    for u in range(3):
+        want = sorted((int(q) for q in np.flatnonzero(users == u)), key=lambda q: (int(times[q]), q), reverse=True)
+        assert got[u].tolist() == want
+        assert u == 0 or sub[u].tolist() == want
+    assert {H.I64_MIN, -1, 0, H.I64_MAX} <= set(times[got[1]].tolist()) and sorted(sub) == [1, 2]
+    s.times = None
+    assert all(H.user_positions(s, 3)[u].tolist() == np.flatnonzero(users == u)[::-1].tolist() == H.user_positions_of(s, [u])[u].tolist() for u in range(3))
+
+
+@pytest.fixture(scope="module")
+def key_problem():
+    return H.make_key_problem()
+
+
+@pytest.fixture(scope="module")
+def key_dev(sim_session, key_problem):
+    return H.DeviceProblem(sim_session, key_problem)
+
+
+def test_key_problem_holds_the_edge_cases(key_problem):
+    H.assert_key_edge_cases(key_problem)
+
+
+@pytest.mark.parametrize("cap", H.KEY_CAPS)
+def test_key_domain_rows_match_the_restatement(key_dev, cap):
+    stats, _, _ = H.check(key_dev, [cap, cap])
+    assert stats[0] > 0 and stats[1] > 0 and stats[2] > 0 and stats[3] > 0, stats
+
+
+def test_key_domain_rows_do_not_depend_on_the_index_order_or_the_job_before(sim_session, key_problem, key_dev):
+    other = H.DeviceProblem(sim_session, key_problem, shuffle_index_seed=4)
+    assert not torch.equal(key_dev.ev[0][2], other.ev[0][2]), "the permuted index equals the built one"
+    byte0 = H.DeviceProblem(sim_session, H.make_byte0_job())
+    for cap in (20, 150, 2048):
+        _, terms_a, excl_a = H.check(key_dev, [cap, 7])
+        stats, _, _ = H.check(byte0, [100])           # one job whose keys differ in the lowest time byte alone, between two runs over every byte
+        assert stats[1] == 1 and stats[3] == 1 and stats[0] + stats[2] == 0, stats
+        _, terms_b, excl_b = H.check(other, [cap, 7])
+        for ra, rb in zip(terms_a + [excl_a], terms_b + [excl_b]):
+            assert all(np.array_equal(x, y) for x, y in zip(ra, rb))
+
+
+def test_positions_beyond_2_24(sim_session):
+    """The most significant position digit differs and decides (no times / equal times); caps below, at and above each user's number of events at or
+    above 2^24.  The index of the five users is built on the host: the simulator does not run the index kernels over 17 M events."""
+    p = H.make_far_problem()
+    d = H.DeviceProblem(sim_session, p, subset=range(p.n_users), host_index=True)
+    for cap in H.far_caps(p):
+        stats, terms, _ = H.check(d, [cap, cap])
+        assert stats[0] > 0 and stats[1] > 0 and stats[2] > 0 and stats[3] > 0, stats
+        assert np.array_equal(terms[0][3], terms[1][3])          # without times and with equal times: the same window
+
+
+@pytest.mark.parametrize("cap", (5, 100))
+def test_capacity_below_the_bounds(dev, cap):
+    """Buffers of exactly max(capacity, 1) entries: under HIPSIM_GUARD a write past them faults."""
+    H.capacity_cases(dev, [cap] * 3)
 
 
 def test_under_guard_pages():
