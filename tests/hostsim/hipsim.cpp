@@ -45,6 +45,12 @@ thread_local Idx tIdx, bIdx, bDim, gDim;
 thread_local int cur_device = 0;
 thread_local int last_error = 0;
 
+// ---- live-object counters ------------------------------------------------------------------------------
+namespace {
+std::atomic<long long> g_live[LIVE_KINDS];
+}  // namespace
+void live_add(int kind, long long delta) { g_live[kind].fetch_add(delta, std::memory_order_relaxed); }
+
 // ---- guard-page allocations (HIPSIM_GUARD=1) ------------------------------------------------------------
 bool guard_on() {
   static const bool on = [] { const char* e = getenv("HIPSIM_GUARD"); return e && *e && *e != '0'; }();
@@ -306,3 +312,5 @@ void launch(dim3 grid, dim3 block, const std::function<void()>& body) {
 // test-side allocations (tests/conftest.py wraps them as tensors for kernel inputs and outputs)
 extern "C" void* hipsim_guard_malloc(size_t n) { return hipsim::guard_alloc(n ? n : 1); }
 extern "C" void hipsim_guard_release(void* p) { if (p) (void)hipsim::guard_free(p); }
+// objects of `kind` (hipsim::LiveKind: 0 device allocations, 1 host allocations, 2 events, 3 streams) created and not yet destroyed
+extern "C" long long hipsim_live(int kind) { return kind >= 0 && kind < hipsim::LIVE_KINDS ? hipsim::g_live[kind].load() : -1; }

@@ -80,6 +80,19 @@ bool guard_free(void* p);                       // false: not a guarded allocati
 void arena_unguard(void* base, size_t cap);     // make the whole arena read/write again (its layout is about to change)
 char* arena_place(char* base, size_t off, size_t bytes, size_t* new_off);  // address of a sub-buffer ending at a guard page
 constexpr size_t GUARD_PAGE = 4096;
+// Live-object counters (tests/test_sim_resources.py): what the library has created and not yet given back, read through hipsim_live(kind).
+enum LiveKind { LIVE_DEVICE = 0, LIVE_HOST = 1, LIVE_EVENT = 2, LIVE_STREAM = 3, LIVE_KINDS = 4 };
+void live_add(int kind, long long delta);
+static inline void* raw_alloc(size_t n, int kind) {
+  void* p = guard_on() ? guard_alloc(n ? n : 1) : malloc(n ? n : 1);
+  if (p) live_add(kind, 1);
+  return p;
+}
+static inline void raw_free(void* p, int kind) {
+  if (!p) return;
+  live_add(kind, -1);
+  if (!guard_free(p)) free(p);
+}
 }  // namespace hipsim
 #define HIPSIM_HOST_BUILD 1
 
@@ -243,21 +256,21 @@ static inline unsigned __builtin_amdgcn_mbcnt_hi(unsigned mask, unsigned base) {
 static inline const char* hipGetErrorString(hipError_t e) { return e == hipSuccess ? "hipSuccess(sim)" : "hipError(sim)"; }
 static inline hipError_t hipGetLastError() { const int e = hipsim::last_error; hipsim::last_error = hipSuccess; return e; }
 static inline hipError_t hipPeekAtLastError() { return hipSuccess; }
-static inline hipError_t hipMalloc(void** p, size_t n) { *p = hipsim::guard_on() ? hipsim::guard_alloc(n ? n : 1) : malloc(n ? n : 1); return *p ? hipSuccess : hipErrorOutOfMemory; }
+static inline hipError_t hipMalloc(void** p, size_t n) { *p = hipsim::raw_alloc(n, hipsim::LIVE_DEVICE); return *p ? hipSuccess : hipErrorOutOfMemory; }
 template <typename T> static inline hipError_t hipMalloc(T** p, size_t n) { return hipMalloc((void**)p, n); }
-static inline hipError_t hipFree(void* p) { if (!p || !hipsim::guard_free(p)) free(p); return hipSuccess; }
+static inline hipError_t hipFree(void* p) { hipsim::raw_free(p, hipsim::LIVE_DEVICE); return hipSuccess; }
 enum { hipHostMallocDefault = 0, hipHostMallocPortable = 1, hipHostMallocMapped = 2, hipHostMallocCoherent = 0x40000000 };
 static inline hipError_t hipHostGetDevicePointer(void** dev, void* host, unsigned) { *dev = host; return hipSuccess; }
-static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { return hipMalloc(p, n); }
-static inline hipError_t hipHostFree(void* p) { return hipFree(p); }
+static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { *p = hipsim::raw_alloc(n, hipsim::LIVE_HOST); return *p ? hipSuccess : hipErrorOutOfMemory; }
+static inline hipError_t hipHostFree(void* p) { hipsim::raw_free(p, hipsim::LIVE_HOST); return hipSuccess; }
 static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t = nullptr) { if (n) memcpy(d, s, n); return hipSuccess; }
 static inline hipError_t hipMemset(void* d, int v, size_t n) { if (n) memset(d, v, n); return hipSuccess; }
 static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t = nullptr) { if (n) memset(d, v, n); return hipSuccess; }
 static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
 static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
-static inline hipError_t hipStreamCreate(hipStream_t* s) { *s = new hipsimStream{hipsim::cur_device}; return hipSuccess; }
-static inline hipError_t hipStreamDestroy(hipStream_t s) { delete static_cast<hipsimStream*>(s); return hipSuccess; }
+static inline hipError_t hipStreamCreate(hipStream_t* s) { *s = new hipsimStream{hipsim::cur_device}; hipsim::live_add(hipsim::LIVE_STREAM, 1); return hipSuccess; }
+static inline hipError_t hipStreamDestroy(hipStream_t s) { if (s) hipsim::live_add(hipsim::LIVE_STREAM, -1); delete static_cast<hipsimStream*>(s); return hipSuccess; }
 enum { hipStreamDefault = 0, hipStreamNonBlocking = 1 };
 static inline hipError_t hipDeviceGetStreamPriorityRange(int* least, int* greatest) { *least = 0; *greatest = 0; return hipSuccess; }
 static inline hipError_t hipStreamCreateWithPriority(hipStream_t* s, unsigned, int) { return hipStreamCreate(s); }
@@ -285,11 +298,11 @@ static inline hipError_t hipGetDeviceProperties(hipDeviceProp_t* p, int) {
   return hipSuccess;
 }
 template <typename F> static inline hipError_t hipOccupancyMaxActiveBlocksPerMultiprocessor(int* n, F, int, size_t) { *n = 2; return hipSuccess; }
-static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new hipsimEvent(); (*e)->device = hipsim::cur_device; return hipSuccess; }
+static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new hipsimEvent(); (*e)->device = hipsim::cur_device; hipsim::live_add(hipsim::LIVE_EVENT, 1); return hipSuccess; }
 enum { hipEventDefault = 0, hipEventDisableTiming = 2 };
 static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
 static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
-static inline hipError_t hipEventDestroy(hipEvent_t e) { delete e; return hipSuccess; }
+static inline hipError_t hipEventDestroy(hipEvent_t e) { if (e) hipsim::live_add(hipsim::LIVE_EVENT, -1); delete e; return hipSuccess; }
 static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t st = nullptr) {
   if (e->device != hipsim::stream_device(st)) return hipErrorInvalidHandle;  // an event belongs to the device it was created on
   e->t = std::chrono::steady_clock::now();

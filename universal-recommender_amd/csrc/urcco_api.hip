@@ -2,8 +2,6 @@
 // host-level one-shot entry points that stand in for Mahout's SimilarityAnalysis.cooccurrencesIDSs and
 // crossOccurrenceDownsampled (reference call sites: src/main/scala/URAlgorithm.scala:323-329, :343-346).
 // No CPU fallback: without a HIP device the compute entry points return URCCO_NO_DEVICE.
-#include <memory>
-
 #include "urcco_internal.h"
 
 using namespace urcco_detail;
@@ -178,15 +176,10 @@ void urcco_session_destroy(urcco_session* s) {
   (void)hipSetDevice(s->device);
   (void)hipStreamSynchronize(s->stream);
   debug_unregister(s);
-  if (s->arena) (void)hipFree(s->arena);
-  if (s->xlx_tab) (void)hipFree(s->xlx_tab);
-  if (s->xlx_hi) (void)hipFree(s->xlx_hi);
-  if (s->form_word) (void)hipFree(s->form_word);
-  if (s->g_counts) { (void)hipFree(s->g_counts); (void)hipFree(s->g_cand_key); (void)hipFree(s->g_cand_col); }
   s->collect();
   for (hipEvent_t e : s->free_events) (void)hipEventDestroy(e);
   if (s->own_stream) (void)hipStreamDestroy(s->stream);
-  delete s;
+  delete s;  // its device is current and its stream drained: the device buffers it owns free themselves
 }
 
 int urcco_session_synchronize(urcco_session* s) {
@@ -210,8 +203,8 @@ int urcco_session_set_expand_test(urcco_session* s, int64_t limit, int64_t prefi
 
 int urcco_session_expand_form(urcco_session* s, int32_t* form_host) {
   if (!s || !form_host) return fail(URCCO_BAD_ARG, "urcco_session_expand_form: bad argument");
-  if (!s->form_word || !s->form_valid) return fail(URCCO_BAD_ARG, "urcco_session_expand_form: no rows were built on this session");
-  HIPC(hipMemcpyAsync(form_host, s->form_word, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
+  if (!s->form_word.p || !s->form_valid) return fail(URCCO_BAD_ARG, "urcco_session_expand_form: no rows were built on this session");
+  HIPC(hipMemcpyAsync(form_host, s->form_word.p, sizeof(int32_t), hipMemcpyDeviceToHost, s->stream));
   HIPC(hipStreamSynchronize(s->stream));
   return URCCO_OK;
 }
@@ -233,17 +226,18 @@ int urcco_session_get_timings(urcco_session* s, double* ms, int64_t* launches) {
 
 int64_t urcco_session_scratch_bytes(const urcco_session* s) {
   if (!s) return 0;
-  return (int64_t)s->arena_cap + (int64_t)s->g_cap * 16;
+  return (int64_t)s->arena.cap + (int64_t)s->g_cap * 16;
 }
 
 int urcco_dev_column_counts(urcco_session* s, int64_t nnz, const int32_t* col_idx, int32_t n_cols, int32_t* counts) {
   if (!s || nnz < 0 || n_cols < 0 || (nnz > 0 && !col_idx) || (n_cols > 0 && !counts)) return fail(URCCO_BAD_ARG, "urcco_dev_column_counts: bad argument");
   if (n_cols == 0) return URCCO_OK;
   const int64_t ph_bytes = urcco::column_counts_scratch_bytes(nnz, n_cols);
-  if (ph_bytes > 0) URC(s->reserve((size_t)ph_bytes));
+  char* ph = nullptr;
+  if (ph_bytes > 0) URC(ArenaLayout(s).add(&ph, (size_t)ph_bytes).commit());
   s->begin(URCCO_STAGE_COLUMN_COUNTS);
   if (ph_bytes > 0)
-    HIPC(urcco::launch_column_counts_partitioned(s->stream, col_idx, nnz, nullptr, n_cols, counts, s->take<char>((size_t)ph_bytes)));
+    HIPC(urcco::launch_column_counts_partitioned(s->stream, col_idx, nnz, nullptr, n_cols, counts, ph));
   else
     HIPC(urcco::launch_column_counts(s->stream, s->n_cu, col_idx, nnz, n_cols, counts));
   s->end();
@@ -269,12 +263,13 @@ int urcco_dev_downsample(urcco_session* s, int64_t n_rows, const int64_t* row_pt
   const int64_t ds_tiles = (nnz + urcco::DS_TILE - 1) / urcco::DS_TILE;
   const size_t n_words = (size_t)ds_tiles * (urcco::DS_TILE / 64);
   const size_t thr_words = (size_t)n_cols + (size_t)n_cols / 8 + 2;  // 8-byte thresholds + their one-byte prefixes
-  URC(s->reserve(urcco_session::need(thr_words, 8) + urcco_session::need((size_t)ds_tiles + 1, 8) * 2 + urcco_session::need(n_words, 8) +
-                 (size_t)ph_bytes + 256));
-  unsigned long long* thresholds = s->take<unsigned long long>(thr_words);
-  int64_t* tile_rows = s->take<int64_t>((size_t)ds_tiles + 1);
-  int64_t* tile_count = s->take<int64_t>((size_t)ds_tiles + 1);
-  unsigned long long* flags = s->take<unsigned long long>(n_words);
+  ArenaLayout L(s);
+  unsigned long long *thresholds, *flags;
+  int64_t *tile_rows, *tile_count;
+  char* ph = nullptr;
+  L.add(&thresholds, thr_words).add(&tile_rows, (size_t)ds_tiles + 1).add(&tile_count, (size_t)ds_tiles + 1).add(&flags, n_words);
+  if (ph_bytes > 0) L.add(&ph, (size_t)ph_bytes);
+  URC(L.commit());
   s->begin(URCCO_STAGE_DOWNSAMPLE_FLAGS);
   HIPC(urcco::launch_downsample_flags(s->stream, s->n_cu, n_rows, row_ptr, col_idx, nnz, n_cols, raw_counts, thresholds, (uint32_t)seed,
                                       max_elements_per_row, row_rate_mode, row_base, tile_rows, flags, tile_count,
@@ -288,7 +283,7 @@ int urcco_dev_downsample(urcco_session* s, int64_t n_rows, const int64_t* row_pt
   s->end();
   if (ph_bytes > 0) {
     s->begin(URCCO_STAGE_COLUMN_COUNTS);
-    HIPC(urcco::launch_column_counts_partitioned(s->stream, out_col_idx, nnz, out_row_ptr + n_rows, n_cols, post_counts, s->take<char>((size_t)ph_bytes)));
+    HIPC(urcco::launch_column_counts_partitioned(s->stream, out_col_idx, nnz, out_row_ptr + n_rows, n_cols, post_counts, ph));
     s->end();
   }
   return URCCO_OK;
@@ -299,11 +294,14 @@ int urcco_dev_transpose(urcco_session* s, int64_t n_rows, const int64_t* row_ptr
   if (!s || n_rows < 0 || nnz < 0 || n_cols < 0 || !row_ptr || !out_col_ptr || (n_cols > 0 && !counts) || (nnz > 0 && (!col_idx || !out_row_idx)) ||
       col_lo < 0 || col_hi < col_lo || col_hi > n_cols)
     return fail(URCCO_BAD_ARG, "urcco_dev_transpose: bad argument");
-  const int64_t n_tiles = ((int64_t)n_cols + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
   const int64_t tr_bytes = urcco::transpose_scratch_bytes(n_rows, nnz, n_cols);
-  URC(s->reserve(urcco_session::need((size_t)n_cols, 4) + urcco_session::need((size_t)n_tiles + 2, 8) + (size_t)tr_bytes + 256));
-  int32_t* cursor = s->take<int32_t>((size_t)n_cols);
-  int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
+  ArenaLayout L(s);
+  int32_t* cursor;
+  int64_t* tile_sums;
+  char* tr = nullptr;  // the partitioned form's block, carved by its launcher
+  L.add(&cursor, (size_t)n_cols).add(&tile_sums, scan_tile_words(n_cols));
+  if (tr_bytes > 0) L.add(&tr, (size_t)tr_bytes);
+  URC(L.commit());
   s->begin(URCCO_STAGE_TRANSPOSE);
   HIPC(urcco::launch_scan_i32_range(s->stream, counts, n_cols, col_lo, col_hi, out_col_ptr, tile_sums));
   if (nnz > 0 && n_rows > 0) {
@@ -312,8 +310,7 @@ int urcco_dev_transpose(urcco_session* s, int64_t n_rows, const int64_t* row_ptr
     if (g > 6) g = 6;
     HIPC(hipMemsetAsync(cursor, 0, sizeof(int32_t) * (size_t)n_cols, s->stream));
     if (tr_bytes > 0) {
-      HIPC(urcco::launch_transpose_partitioned(s->stream, n_rows, row_ptr, col_idx, nnz, n_cols, out_col_ptr, cursor, out_row_idx, col_lo, col_hi,
-                                               s->take<char>((size_t)tr_bytes)));
+      HIPC(urcco::launch_transpose_partitioned(s->stream, n_rows, row_ptr, col_idx, nnz, n_cols, out_col_ptr, cursor, out_row_idx, col_lo, col_hi, tr));
     } else {
       HIPC(urcco::launch_transpose(s->stream, s->n_cu, n_rows, row_ptr, col_idx, g, out_col_ptr, cursor, out_row_idx, col_lo, col_hi));
     }
@@ -340,14 +337,12 @@ int urcco_dev_row_work(urcco_session* s, int32_t item_lo, int32_t item_hi, int32
   if (!s || item_lo < 0 || item_hi < item_lo || item_hi > n_items_a || nnz_a_bound < 0 || !a_col_ptr || !b_row_ptr || (item_hi > item_lo && !work))
     return fail(URCCO_BAD_ARG, "urcco_dev_row_work: bad argument");
   const int64_t cap = nnz_a_bound;
-  const int64_t n_tiles = (cap + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
-  URC(s->reserve(urcco_session::need((size_t)cap, 4) + urcco_session::need((size_t)cap + 1, 8) + urcco_session::need((size_t)n_tiles + 2, 8)));
-  if (!s->form_word) HIPC(hipMalloc((void**)&s->form_word, sizeof(int32_t)));
+  int32_t* plen;
+  int64_t *wp, *tile_sums;
+  URC(ArenaLayout(s).add(&plen, (size_t)cap).add(&wp, (size_t)cap + 1).add(&tile_sums, scan_tile_words(cap)).commit());
+  if (!s->form_word.p) URC(s->form_word.alloc(1));
   s->form_valid = false;
-  int32_t* plen = s->take<int32_t>((size_t)cap);
-  int64_t* wp = s->take<int64_t>((size_t)cap + 1);
-  int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
-  int32_t* form = s->form_word;
+  int32_t* form = s->form_word.p;
   s->begin(URCCO_STAGE_ROW_WORK);
   // (no row kernel follows: the lengths and their prefix alone, no starts -- the prefix in the narrow form unless a tile sum forbids it)
   HIPC(urcco::launch_expand_prepare(s->stream, s->n_cu, a_col_ptr, n_items_a, a_row_idx, b_row_ptr, nullptr, 0, cap, nullptr, nullptr, plen, wp, tile_sums,
@@ -375,10 +370,11 @@ int urcco_dev_merge_fragments(urcco_session* s, int32_t world, int32_t item_lo, 
     return fail(URCCO_BAD_ARG, "urcco_dev_merge_fragments: bad argument");
   const int32_t n_range = item_hi - item_lo;
   const int64_t n_runs = (int64_t)world * n_range;
-  const int64_t t_items = ((int64_t)n_items + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE, t_runs = (n_runs + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
-  URC(s->reserve(urcco_session::need((size_t)n_runs + 1, 8) + urcco_session::need((size_t)(t_items > t_runs ? t_items : t_runs) + 2, 8)));
-  int64_t* src_off = s->take<int64_t>((size_t)n_runs + 1);
-  int64_t* tile_sums = s->take<int64_t>((size_t)(t_items > t_runs ? t_items : t_runs) + 2);
+  int64_t *src_off, *tile_sums;
+  ArenaLayout L(s);
+  L.add(&src_off, (size_t)n_runs + 1);
+  L.add(&tile_sums, scan_tile_words(n_items > n_runs ? n_items : n_runs));  // shared by the scan over the items and the one over the runs
+  URC(L.commit());
   s->begin(URCCO_STAGE_TRANSPOSE);
   HIPC(urcco::launch_scan_i32_range(s->stream, counts, n_items, item_lo, item_hi, out_col_ptr, tile_sums));
   if (wire16) {
@@ -418,13 +414,14 @@ int urcco_dev_cco_rows_packed(urcco_session* s, int32_t item_lo, int32_t item_hi
 
 namespace urcco_detail {
 
-// bounds stay on the device: `bounds_dev` if given, else arena scratch returned through *bounds_out (valid until the session's next reserve)
+// bounds stay on the device: `bounds_dev` if given, else arena scratch returned through *bounds_out (valid until the session's next scratch layout)
 int partition_dev(urcco_session* s, int32_t n_items, const int64_t* work, int32_t n_parts, int32_t* bounds_dev, int32_t** bounds_out) {
-  const int64_t n_tiles = ((int64_t)n_items + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
-  URC(s->reserve(urcco_session::need((size_t)n_items + 1, 8) + urcco_session::need((size_t)n_tiles + 2, 8) + urcco_session::need((size_t)n_parts + 1, 4)));
-  int64_t* prefix = s->take<int64_t>((size_t)n_items + 1);
-  int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
-  int32_t* bounds = bounds_dev ? bounds_dev : s->take<int32_t>((size_t)n_parts + 1);
+  ArenaLayout L(s);
+  int64_t *prefix, *tile_sums;
+  int32_t* bounds = bounds_dev;
+  L.add(&prefix, (size_t)n_items + 1).add(&tile_sums, scan_tile_words(n_items));
+  if (!bounds_dev) L.add(&bounds, (size_t)n_parts + 1);
+  URC(L.commit());
   HIPC(urcco::launch_scan_i64(s->stream, work, n_items, prefix, tile_sums));
   HIPC(urcco::launch_partition(s->stream, n_items, prefix, n_parts, bounds));
   if (bounds_out) *bounds_out = bounds;
@@ -450,55 +447,47 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
     if (stats_dev) HIPC(hipMemsetAsync(stats_dev, 0, sizeof(int64_t) * URCCO_STATS_LEN, s->stream));
     return URCCO_OK;
   }
-  // packed LDS entry: key = col + 1 in the high bits, count in the low bits
-  int key_bits = 1;
-  while (((int64_t)1 << key_bits) <= (int64_t)n_cols_b) ++key_bits;  // values 1..n_cols_b
+  int key_bits = 0;  // packed LDS entry: key = col + 1 in the high bits, count in the low bits
+  URC(packed_key_bits(n_cols_b, &key_bits));
   const int count_bits = 32 - key_bits;
-  if (count_bits < 1) return fail(URCCO_BAD_ARG, "n_cols_b %d too large for the packed accumulator", n_cols_b);
   // bin 6 = the multi-pass LDS class; only a k beyond its running lists (or beyond any LDS table) falls back to the dense
   // global-accumulator kernel and pays for its n_cols x 16 B of scratch per resident block
   const bool dense_bin6 = k > urcco::MP_KMAX_HOST || 3ll * k + 5 > 32768ll;
   if (dense_bin6) URC(s->ensure_global_bin(n_cols_b));
-  if (!s->xlx_tab) {
-    HIPC(hipMalloc((void**)&s->xlx_tab, sizeof(double) * urcco::XLX_TABLE_HOST));
-    HIPC(urcco::launch_xlx_table(s->stream, s->xlx_tab));
+  if (!s->xlx_tab.p) {
+    URC(s->xlx_tab.alloc(urcco::XLX_TABLE_HOST));
+    HIPC(urcco::launch_xlx_table(s->stream, s->xlx_tab.p));
   }
-  if (!s->xlx_hi) HIPC(hipMalloc((void**)&s->xlx_hi, sizeof(double) * 2 * urcco::XLX_TABLE_HOST));  // xLogX(N - d), then columnEntropy(c)
+  if (!s->xlx_hi.p) URC(s->xlx_hi.alloc(2 * urcco::XLX_TABLE_HOST));  // xLogX(N - d), then columnEntropy(c)
   if (s->xlx_hi_n != n_users) {
-    HIPC(urcco::launch_xlx_hi_table(s->stream, s->xlx_hi, s->xlx_tab, n_users));
+    HIPC(urcco::launch_xlx_hi_table(s->stream, s->xlx_hi.p, s->xlx_tab.p, n_users));
     s->xlx_hi_n = n_users;
   }
   const int64_t n_tiles = ((int64_t)n + urcco::BIN_TILE - 1) / urcco::BIN_TILE;
   const int64_t cap = nnz_a_bound;
-  const int64_t p_tiles = (cap + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
-  if (!s->form_word) HIPC(hipMalloc((void**)&s->form_word, sizeof(int32_t)));
+  if (!s->form_word.p) URC(s->form_word.alloc(1));
   s->form_valid = false;
-  URC(s->reserve(urcco_session::need((size_t)cap, 8) + urcco_session::need((size_t)cap, 4) + (pre_pstart ? 0 : urcco_session::need((size_t)cap, 4)) + urcco_session::need((size_t)cap + 1, 8) +
-                 urcco_session::need((size_t)p_tiles + 2, 8) +
-                 urcco_session::need((size_t)n, 8) + urcco_session::need((size_t)(n_tiles + 1) * urcco::BIN_COLS_HOST, 8) +
-                 urcco_session::need(urcco::BIN_OFF_LEN, 4) + urcco_session::need((size_t)n, 4) + urcco_session::need((size_t)n_items_a, 8) +
-                 urcco_session::need((size_t)n_cols_b, 2) + urcco_session::need(1, 4) + urcco_session::need(urcco::CAND_SLOTS, 8) + urcco_session::need(1, 8) + urcco_session::need(URCCO_STATS_LEN, 8) +
-                 urcco_session::need((size_t)n_users + 1, 4)));
   // the expand tables in the narrow form (32-bit starts; the work prefix as 32-bit words in the front half of wp) or, when the scan's verdict says so, in
   // the wide one (pstart64; wp whole): cco_kernels.h, ExpandForm.  pstart64 is touched by the wide form alone.
-  int64_t* pstart64 = s->take<int64_t>((size_t)cap);
-  unsigned* own_pstart = pre_pstart ? nullptr : s->take<unsigned>((size_t)cap);
-  int32_t* own_plen = s->take<int32_t>((size_t)cap);
+  ArenaLayout L(s);
+  int64_t *pstart64, *wp, *p_tile_sums, *work, *tile_counts, *stats = stats_dev;
+  unsigned *own_pstart = nullptr, *b_rp32;
+  int32_t *own_plen, *bin_off, *bin_rows, *cnt16_bad;
+  double *ent_a, *xlx_n;
+  unsigned short* cnt_b16;
+  unsigned long long* cand;
+  L.add(&pstart64, (size_t)cap);
+  if (!pre_pstart) L.add(&own_pstart, (size_t)cap);
+  L.add(&own_plen, (size_t)cap).add(&wp, (size_t)cap + 1).add(&p_tile_sums, scan_tile_words(cap));
+  L.add(&work, (size_t)n).add(&tile_counts, (size_t)(n_tiles + 1) * urcco::BIN_COLS_HOST);  // binning
+  L.add(&bin_off, urcco::BIN_OFF_LEN).add(&bin_rows, (size_t)n);
+  L.add(&ent_a, (size_t)n_items_a).add(&cnt_b16, (size_t)n_cols_b).add(&cnt16_bad, 1);
+  L.add(&cand, urcco::CAND_SLOTS).add(&xlx_n, 1);
+  if (!stats_dev) L.add(&stats, URCCO_STATS_LEN);
+  L.add(&b_rp32, (size_t)n_users + 1);
+  URC(L.commit());
   const unsigned* pstart32 = pre_pstart ? pre_pstart : own_pstart;
-  int64_t* wp = s->take<int64_t>((size_t)cap + 1);
-  int32_t* form = s->form_word;  // (the session's own word, not arena scratch: urcco_session_expand_form reads it after the call)
-  int64_t* p_tile_sums = s->take<int64_t>((size_t)p_tiles + 2);
-  int64_t* work = s->take<int64_t>((size_t)n);
-  int64_t* tile_counts = s->take<int64_t>((size_t)(n_tiles + 1) * urcco::BIN_COLS_HOST);
-  int32_t* bin_off = s->take<int32_t>(urcco::BIN_OFF_LEN);
-  int32_t* bin_rows = s->take<int32_t>((size_t)n);
-  double* ent_a = s->take<double>((size_t)n_items_a);
-  unsigned short* cnt_b16 = s->take<unsigned short>((size_t)n_cols_b);
-  int32_t* cnt16_bad = s->take<int32_t>(1);
-  unsigned long long* cand = s->take<unsigned long long>(urcco::CAND_SLOTS);
-  double* xlx_n = s->take<double>(1);
-  int64_t* stats = stats_dev ? stats_dev : s->take<int64_t>(URCCO_STATS_LEN);
-  unsigned* b_rp32 = s->take<unsigned>((size_t)n_users + 1);
+  int32_t* form = s->form_word.p;  // (the session's own word, not arena scratch: urcco_session_expand_form reads it after the call)
 
   // DBG_UNPACKED_COUNTS: the count gather of rounds 1-5 (A/B, tests).  pk_known: b_col_idx itself holds packed words (the rows a sharded build received
   // travelled with their counts aboard -- the host learnt with the shard sizes that every count fits): no plain copy exists, every reader masks
@@ -534,7 +523,7 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
   a.a_col_ptr = a_col_ptr; a.pstart32 = pstart32; a.pstart64 = pstart64; a.wp = wp; a.form = form; a.work = work; a.b_col_idx = b_col_idx;
   a.b_packed = packed; a.pk_known = narrow_known ? 1 : 0;
   a.b_col_mask = pk_known ? (key_bits >= 32 ? 0xffffffffu : (1u << key_bits) - 1u) : 0xffffffffu;
-  a.cnt_a = counts_a; a.cnt_b = counts_b; a.ent_a = ent_a; a.cnt_b16 = cnt_b16; a.cnt16_bad = cnt16_bad; a.xlx_n = xlx_n; a.xlx_tab = s->xlx_tab; a.xlx_hi = s->xlx_hi; a.col_ent = s->xlx_hi + urcco::XLX_TABLE_HOST; a.debug = s->debug;
+  a.cnt_a = counts_a; a.cnt_b = counts_b; a.ent_a = ent_a; a.cnt_b16 = cnt_b16; a.cnt16_bad = cnt16_bad; a.xlx_n = xlx_n; a.xlx_tab = s->xlx_tab.p; a.xlx_hi = s->xlx_hi.p; a.col_ent = s->xlx_hi.p + urcco::XLX_TABLE_HOST; a.debug = s->debug;
   a.n_users = n_users; a.n_cols_b = n_cols_b; a.item_lo = item_lo; a.exclude_self = exclude_self ? 1 : 0; a.k = k;
   a.has_min_llr = has_min_llr ? 1 : 0; a.min_llr = min_llr; a.count_bits = count_bits;
   a.col_bytes = n_cols_b <= (1 << 8) ? 1 : (n_cols_b <= (1 << 16) ? 2 : (n_cols_b <= (1 << 24) ? 3 : 4));
@@ -544,7 +533,7 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
   a.err = reinterpret_cast<unsigned long long*>(stats + 1 + 4 * urcco::NBINS);
   a.cand = s->timing ? cand : nullptr;
   if (s->timing) HIPC(hipMemsetAsync(cand, 0, sizeof(unsigned long long) * urcco::CAND_SLOTS, s->stream));
-  a.g_counts = s->g_counts; a.g_cand_key = s->g_cand_key; a.g_cand_col = s->g_cand_col; a.g_blocks = dense_bin6 ? s->g_blocks : 0;
+  a.g_counts = s->g_counts.p; a.g_cand_key = s->g_cand_key.p; a.g_cand_col = s->g_cand_col.p; a.g_blocks = dense_bin6 ? s->g_blocks : 0;
   // Heaviest classes first (global, whole-CU, half-CU, ...): they have few, long rows and end raggedly; the fine-grained
   // one-wave and micro classes run last and finish sharply -- and, with a stream per event type, fill the heavy classes'
   // tails of the other event types instead of leaving a tail of their own.
@@ -561,14 +550,13 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
 int pack_counts(urcco_session* s, const int64_t* b_row_ptr, int64_t n_rows_b, const int32_t* b_col_idx, int64_t nnz_bound, const int32_t* counts_b, int32_t n_cols_b,
                 int32_t* out, int32_t* bad) {
   if (!s || !b_row_ptr || n_rows_b < 0 || nnz_bound < 0 || !out || !bad || (nnz_bound > 0 && (!b_col_idx || !counts_b))) return fail(URCCO_BAD_ARG, "pack_counts: bad argument");
-  int key_bits = 1;  // as cco_rows_impl: the bits of a (column + 1) key; the column itself fits them too
-  while (((int64_t)1 << key_bits) <= (int64_t)n_cols_b) ++key_bits;
+  int key_bits = 0;
+  URC(packed_key_bits(n_cols_b, &key_bits));
   const int count_bits = 32 - key_bits;
-  if (count_bits < 1) return fail(URCCO_BAD_ARG, "n_cols_b %d too large for the packed accumulator", n_cols_b);
   // the gathers read the 16-bit copy of the counts (half the table: 4 MB for a 2M-item catalogue) -- arena scratch, needed until the pack kernel has run
-  URC(s->reserve(urcco_session::need((size_t)n_cols_b + 8, 2) + urcco_session::need(1, 4) + 256));
-  unsigned short* c16 = s->take<unsigned short>((size_t)n_cols_b + 8);
-  int32_t* bad16 = s->take<int32_t>(1);
+  unsigned short* c16;
+  int32_t* bad16;
+  URC(ArenaLayout(s).add(&c16, (size_t)n_cols_b + 8).add(&bad16, 1).commit());
   s->begin(URCCO_STAGE_ENTROPY);
   HIPC(urcco::launch_narrow_counts(s->stream, s->n_cu, counts_b, n_cols_b, c16, bad16));
   HIPC(urcco::launch_pack_counts(s->stream, s->n_cu, b_col_idx, b_row_ptr + n_rows_b, nnz_bound, c16, bad16, count_bits, out, bad));
@@ -581,8 +569,9 @@ int pack_counts(urcco_session* s, const int64_t* b_row_ptr, int64_t n_rows_b, co
 int expand_multi(urcco_session* s, int n, const int64_t* a_col_ptr, int32_t n_items_a, const int32_t* a_row_idx, int64_t cap, const int64_t* const* b_row_ptr,
                  int64_t n_users, unsigned* const* pstart, int32_t* const* plen, int64_t* const* tile_sums) {
   if (!s || n < 1 || n > urcco::EXPAND_MULTI_MAX || !a_col_ptr || cap < 0) return fail(URCCO_BAD_ARG, "expand_multi: bad argument");
-  URC(s->reserve(urcco_session::need(((size_t)n_users + 2) * (size_t)n, 4) + 256));
-  void* T = s->take<unsigned>(((size_t)n_users + 2) * (size_t)n);  // n_users + 1 records of n starts (+ one record of slack: the last user's 2 n-word read)
+  unsigned* T;
+  // n_users + 1 records of n starts (+ one record of slack: the last user's 2 n-word read)
+  URC(ArenaLayout(s).add(&T, ((size_t)n_users + 2) * (size_t)n).commit());
   s->begin(URCCO_STAGE_ROW_WORK);
   HIPC(urcco::launch_expand_prepare_multi(s->stream, s->n_cu, a_col_ptr, n_items_a, a_row_idx, n, b_row_ptr, n_users, cap, pstart, plen, T, tile_sums));
   s->end();
@@ -597,9 +586,8 @@ int urcco_dev_compact_indicators(urcco_session* s, int32_t n_rows, int32_t k, co
                                  int64_t* out_row_ptr, int32_t* out_col_idx, double* out_llr) {
   if (!s || n_rows < 0 || k <= 0 || !out_row_ptr || (n_rows > 0 && (!count || !idx || !llr || !out_col_idx || !out_llr)))
     return fail(URCCO_BAD_ARG, "urcco_dev_compact_indicators: bad argument");
-  const int64_t n_tiles = ((int64_t)n_rows + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
-  URC(s->reserve(urcco_session::need((size_t)n_tiles + 2, 8)));
-  int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
+  int64_t* tile_sums;
+  URC(ArenaLayout(s).add(&tile_sums, scan_tile_words(n_rows)).commit());
   s->begin(URCCO_STAGE_COMPACT_INDICATORS);
   HIPC(urcco::launch_scan_i32(s->stream, count, n_rows, out_row_ptr, tile_sums));
   HIPC(urcco::launch_compact_indicators(s->stream, n_rows, k, count, idx, llr, out_row_ptr, out_col_idx, out_llr));
@@ -608,7 +596,10 @@ int urcco_dev_compact_indicators(urcco_session* s, int32_t n_rows, int32_t k, co
 }
 
 struct urcco_key_table {
-  urcco::KeyTable t{};
+  DBuf<unsigned long long> keys;
+  DBuf<unsigned> minpos, count;
+  DBuf<int32_t> id;
+  urcco::KeyTable t{};  // the kernels' view of the four arrays above
   int64_t capacity = 0;
   int device = 0;
 };
@@ -616,10 +607,6 @@ struct urcco_key_table {
 void urcco_key_table_destroy(urcco_key_table* table) {
   if (!table) return;
   (void)hipSetDevice(table->device);
-  if (table->t.keys) (void)hipFree(table->t.keys);
-  if (table->t.minpos) (void)hipFree(table->t.minpos);
-  if (table->t.count) (void)hipFree(table->t.count);
-  if (table->t.id) (void)hipFree(table->t.id);
   delete table;
 }
 
@@ -635,19 +622,18 @@ int urcco_dev_dictionary_build(urcco_session* s, int64_t n, const uint64_t* keys
   while (cap < 2 * n) cap <<= 1;
   tab->capacity = cap;
   tab->t.mask = (unsigned long long)cap - 1ull;
-  HIPC(hipMalloc((void**)&tab->t.keys, sizeof(unsigned long long) * (size_t)cap));
-  HIPC(hipMalloc((void**)&tab->t.minpos, sizeof(unsigned) * (size_t)cap));
-  HIPC(hipMalloc((void**)&tab->t.count, sizeof(unsigned) * (size_t)cap));
-  HIPC(hipMalloc((void**)&tab->t.id, sizeof(int32_t) * (size_t)cap));
+  URC(tab->keys.alloc((size_t)cap));
+  URC(tab->minpos.alloc((size_t)cap));
+  URC(tab->count.alloc((size_t)cap));
+  URC(tab->id.alloc((size_t)cap));
+  tab->t.keys = tab->keys.p; tab->t.minpos = tab->minpos.p; tab->t.count = tab->count.p; tab->t.id = tab->id.p;
   HIPC(hipMemsetAsync(tab->t.keys, 0xFF, sizeof(unsigned long long) * (size_t)cap, s->stream));
   HIPC(hipMemsetAsync(tab->t.minpos, 0xFF, sizeof(unsigned) * (size_t)cap, s->stream));
   HIPC(hipMemsetAsync(tab->t.count, 0, sizeof(unsigned) * (size_t)cap, s->stream));
   HIPC(hipMemsetAsync(tab->t.id, 0xFF, sizeof(int32_t) * (size_t)cap, s->stream));
-  const int64_t n_tiles = (n + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
-  URC(s->reserve(urcco_session::need((size_t)n, 4) + urcco_session::need((size_t)n + 1, 8) + urcco_session::need((size_t)n_tiles + 2, 8)));
-  int32_t* flag = s->take<int32_t>((size_t)n);
-  int64_t* prefix = s->take<int64_t>((size_t)n + 1);
-  int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
+  int32_t* flag;
+  int64_t *prefix, *tile_sums;
+  URC(ArenaLayout(s).add(&flag, (size_t)n).add(&prefix, (size_t)n + 1).add(&tile_sums, scan_tile_words(n)).commit());
   HIPC(urcco::launch_dictionary_build(s->stream, s->n_cu, tab->t, n, reinterpret_cast<const unsigned long long*>(keys), select, min_count, flag, prefix,
                                       tile_sums, first_pos));
   int64_t ids = 0;
@@ -669,8 +655,8 @@ int urcco_dev_dictionary_verify_against(urcco_session* s, const urcco_key_table*
                                         const uint64_t* check_keys, const uint64_t* dict_check_keys, const int64_t* first_pos, int64_t* n_mismatch) {
   if (!s || !table || n < 0 || !n_mismatch || (n > 0 && (!keys || !check_keys || !dict_check_keys || !first_pos)))
     return fail(URCCO_BAD_ARG, "urcco_dev_dictionary_verify: bad argument");
-  URC(s->reserve(urcco_session::need(1, 8)));
-  unsigned long long* err = s->take<unsigned long long>(1);
+  unsigned long long* err;
+  URC(ArenaLayout(s).add(&err, 1).commit());
   HIPC(urcco::launch_dictionary_verify(s->stream, s->n_cu, table->t, n, reinterpret_cast<const unsigned long long*>(keys), select,
                                        reinterpret_cast<const unsigned long long*>(check_keys), reinterpret_cast<const unsigned long long*>(dict_check_keys),
                                        first_pos, err));
@@ -690,13 +676,11 @@ int urcco_dev_csr_from_pairs(urcco_session* s, int64_t n, const int32_t* rows, c
                              int32_t* out_col_idx, int64_t* nnz) {
   if (!s || n < 0 || n_rows < 0 || !out_row_ptr || (n > 0 && (!rows || !cols || !out_col_idx)))
     return fail(URCCO_BAD_ARG, "urcco_dev_csr_from_pairs: bad argument");
-  const int64_t n_tiles = (n_rows + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
-  URC(s->reserve(urcco_session::need((size_t)n_rows, 4) + urcco_session::need((size_t)n_rows + 1, 8) + urcco_session::need((size_t)n, 4) +
-                 urcco_session::need((size_t)n_tiles + 2, 8)));
-  int32_t* cnt = s->take<int32_t>((size_t)n_rows);
-  int64_t* raw_ptr = s->take<int64_t>((size_t)n_rows + 1);
-  int32_t* tmp = s->take<int32_t>((size_t)n);
-  int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
+  int32_t *cnt, *tmp;
+  int64_t *raw_ptr, *tile_sums;
+  ArenaLayout L(s);
+  L.add(&cnt, (size_t)n_rows).add(&raw_ptr, (size_t)n_rows + 1).add(&tmp, (size_t)n).add(&tile_sums, scan_tile_words(n_rows));
+  URC(L.commit());
   HIPC(urcco::launch_csr_from_pairs(s->stream, s->n_cu, n, rows, cols, n_rows, cnt, raw_ptr, tmp, tile_sums, out_row_ptr, out_col_idx));
   if (nnz) {
     HIPC(hipMemcpyAsync(nnz, out_row_ptr + n_rows, sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
@@ -746,10 +730,9 @@ extern "C" {
 int urcco_dev_history_index(urcco_session* s, int64_t n_events, const int32_t* users, int64_t n_users, int64_t* out_row_ptr, int32_t* out_pos) {
   if (!s || n_events < 0 || n_events > 0x7fffffffll || n_users < 0 || n_users > 0x7ffffff0ll || !out_row_ptr || (n_events > 0 && (!users || !out_pos)))
     return fail(URCCO_BAD_ARG, "urcco_dev_history_index: bad argument (a stream holds fewer than 2^31 events)");
-  const int64_t n_tiles = (n_users + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
-  URC(s->reserve(urcco_session::need((size_t)n_users, 4) + urcco_session::need((size_t)n_tiles + 2, 8)));
-  int32_t* cnt = s->take<int32_t>((size_t)n_users);
-  int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
+  int32_t* cnt;
+  int64_t* tile_sums;
+  URC(ArenaLayout(s).add(&cnt, (size_t)n_users).add(&tile_sums, scan_tile_words(n_users)).commit());
   HIPC(urcco::launch_history_index(s->stream, s->n_cu, n_events, users, n_users, cnt, tile_sums, out_row_ptr, out_pos));
   return URCCO_OK;
 }
@@ -758,10 +741,9 @@ int urcco_dev_history_bounds(urcco_session* s, int64_t n_queries, const int32_t*
                              const int64_t* extra_row_ptr, const int32_t* extra_col_idx, int64_t* excl_row_ptr) {
   urcco::HistArgs a;
   URC(history_args("urcco_dev_history_bounds", s, n_queries, q_users, n_users, events, n_types, extra_row_ptr, extra_col_idx, excl_row_ptr, false, &a));
-  const int64_t n_tiles = (n_queries + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
-  URC(s->reserve(urcco_session::need((size_t)n_queries * (size_t)(n_types + 1), 4) + urcco_session::need((size_t)n_tiles + 2, 8)));
-  int32_t* bnd = s->take<int32_t>((size_t)n_queries * (size_t)(n_types + 1));
-  int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
+  int32_t* bnd;
+  int64_t* tile_sums;
+  URC(ArenaLayout(s).add(&bnd, (size_t)n_queries * (size_t)(n_types + 1)).add(&tile_sums, scan_tile_words(n_queries)).commit());
   int64_t* rp[URCCO_REC_MAX_CLAUSES];
   for (int t = 0; t < n_types; ++t) rp[t] = events[t].term_row_ptr;
   HIPC(urcco::launch_history_bounds(s->stream, s->n_cu, a, bnd, tile_sums, rp, excl_row_ptr));
@@ -774,27 +756,19 @@ int urcco_dev_history_rows(urcco_session* s, int64_t n_queries, const int32_t* q
   urcco::HistArgs a;
   URC(history_args("urcco_dev_history_rows", s, n_queries, q_users, n_users, events, n_types, extra_row_ptr, extra_col_idx, excl_row_ptr, true, &a));
   if (n_items < 0 || !excl_col_idx || excl_capacity < 0) return fail(URCCO_BAD_ARG, "urcco_dev_history_rows: bad argument");
-  const int64_t n_tiles = (n_queries + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE;
   const size_t nq = (size_t)n_queries, n_jobs = nq * (size_t)(n_types + 1);
-  size_t bytes = urcco_session::need((size_t)n_tiles + 2, 8) + urcco_session::need(n_jobs, 4) + urcco_session::need(1 + URCCO_HIST_STATS_LEN, 8) +
-                 (size_t)(n_types + 1) * (urcco_session::need(nq + 1, 8) + urcco_session::need(nq, 4)) + urcco_session::need((size_t)excl_capacity, 4);
-  for (int t = 0; t < n_types; ++t) bytes += urcco_session::need((size_t)events[t].term_capacity, 4);
-  URC(s->reserve(bytes));
-  int64_t* tile_sums = s->take<int64_t>((size_t)n_tiles + 2);
-  a.big_list = s->take<int32_t>(n_jobs);
-  a.ctr = s->take<unsigned long long>(1 + URCCO_HIST_STATS_LEN);
+  ArenaLayout L(s);
+  int64_t* tile_sums;
+  L.add(&tile_sums, scan_tile_words(n_queries)).add(&a.big_list, n_jobs).add(&a.ctr, 1 + URCCO_HIST_STATS_LEN);
   int64_t* rp[URCCO_REC_MAX_CLAUSES];
   int32_t* ci[URCCO_REC_MAX_CLAUSES];
   for (int t = 0; t < n_types; ++t) {
-    a.ev[t].raw_ptr = s->take<int64_t>(nq + 1);
-    a.ev[t].len = s->take<int32_t>(nq);
-    a.ev[t].tmp = s->take<int32_t>((size_t)events[t].term_capacity);
+    L.add(&a.ev[t].raw_ptr, nq + 1).add(&a.ev[t].len, nq).add(&a.ev[t].tmp, (size_t)events[t].term_capacity);
     rp[t] = events[t].term_row_ptr;
     ci[t] = events[t].term_col_idx;
   }
-  a.excl_raw_ptr = s->take<int64_t>(nq + 1);
-  a.excl_len = s->take<int32_t>(nq);
-  a.excl_tmp = s->take<int32_t>((size_t)excl_capacity);
+  L.add(&a.excl_raw_ptr, nq + 1).add(&a.excl_len, nq).add(&a.excl_tmp, (size_t)excl_capacity);
+  URC(L.commit());
   a.excl_capacity = excl_capacity;
   a.n_items = n_items;
   HIPC(urcco::launch_history_rows(s->stream, s->n_cu, a, tile_sums, rp, ci, excl_row_ptr, excl_col_idx, stats_dev));
@@ -844,15 +818,14 @@ static int recommend_call(urcco_session* s, int64_t n_queries, int32_t n_items, 
   }
   const int32_t g_blocks = urcco::recommend_global_blocks(n_queries, n_items, s->n_cu);
   const size_t slice = (size_t)g_blocks * (size_t)(n_items > 0 ? n_items : 1);
-  URC(s->reserve(urcco_session::need(8, 8) + urcco_session::need((size_t)n_queries, 4) + urcco_session::need((size_t)n_items, 4) + 3 * urcco_session::need(slice, 4) +
-                 urcco_session::need(slice, 8)));
-  unsigned long long* ctr = s->take<unsigned long long>(8);
-  int32_t* list = s->take<int32_t>((size_t)n_queries);
-  int32_t* pos = s->take<int32_t>((size_t)n_items);
-  unsigned* g_state = s->take<unsigned>(slice);
-  unsigned* g_m = s->take<unsigned>(slice);
-  int32_t* g_list = s->take<int32_t>(slice);
-  double* g_score = s->take<double>(slice);
+  ArenaLayout L(s);
+  unsigned long long* ctr;
+  int32_t *list, *pos, *g_list;
+  unsigned *g_state, *g_m;
+  double* g_score;
+  L.add(&ctr, 8).add(&list, (size_t)n_queries).add(&pos, (size_t)n_items);
+  L.add(&g_state, slice).add(&g_m, slice).add(&g_list, slice).add(&g_score, slice);  // the global class's per-block slices
+  URC(L.commit());
   HIPC(urcco::launch_recommend(s->stream, s->n_cu, n_queries, n_items, cl, n_clauses, excl_row_ptr, excl_col_idx, item_mask, fill_order, num, flags, out_count, out_idx,
                                out_score, stats_dev, ctr, list, pos, g_blocks, g_state, g_m, g_list, g_score, lds_limit, rl, n_rules));
   return URCCO_OK;
@@ -892,6 +865,5 @@ int urcco_dev_u01_rng(urcco_session* s, int64_t n, int32_t seed, const int32_t* 
   HIPC(urcco::launch_u01_test(s->stream, n, (uint32_t)seed, row, col, out, rng == URCCO_RNG_MIX32 ? 1 : 0));
   return URCCO_OK;
 }
-
 
 }  // extern "C"

@@ -86,33 +86,8 @@ int rccl_fail(Rccl* r, int code, const char* what) {
   } while (0)
 
 // ---------------------------------------------------------------------------------------------------------
-// buffers
+// buffers (device memory and events: the owning types of urcco_internal.h)
 // ---------------------------------------------------------------------------------------------------------
-template <typename T>
-struct DBuf {  // device buffer that only grows (hipFree synchronises the device: growth happens on the first builds only)
-  T* p = nullptr;
-  size_t cap = 0;
-  int ensure(size_t n) {
-    if (n <= cap && p) return URCCO_OK;
-    if (p) HIPC(hipFree(p));
-    p = nullptr;
-    cap = 0;
-    size_t want = n + n / 16 + 64;
-#ifdef HIPSIM_HOST_BUILD  // test-only host simulator: no slack, so that an overrun meets the guard page
-    if (hipsim::guard_on()) want = n ? n : 1;
-#endif
-    HIPC(hipMalloc((void**)&p, want * sizeof(T)));
-    cap = want;
-    if (debug_cfg().poison) debug_poison(p, want * sizeof(T), nullptr, false);
-    return URCCO_OK;
-  }
-  void release() {
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
 // Pinned host memory handed out as indicator arrays.  Process-wide: blocks may outlive the context that filled them
 // (the caller releases them with urcco_free_indicators whenever it is done).
 struct PinnedPool {
@@ -191,14 +166,7 @@ struct EvState {
                                 // receivers' f_ci then holds packed words: b_pk_known)
   bool b_pk_known = false;      // b_ci holds packed words and the host knows it (see cco_rows_impl)
   uint32_t b_col_mask = 0xffffffffu;  // b_ci[e] & b_col_mask = the column
-  unsigned long long* h_verr = nullptr;  // host-mapped pinned word the boundary check's result is STORED to by the GPU (host level, one GPU) ...
-  unsigned long long* h_verr_dev = nullptr;  // ... and its device address
-  int ensure_h_verr() {
-    if (h_verr) return URCCO_OK;
-    HIPC(hipHostMalloc((void**)&h_verr, sizeof(unsigned long long), hipHostMallocMapped | hipHostMallocCoherent));
-    HIPC(hipHostGetDevicePointer((void**)&h_verr_dev, h_verr, 0));
-    return URCCO_OK;
-  }
+  MappedWord h_verr;  // the boundary check's result is STORED here by the GPU (host level, one GPU)
   DBuf<unsigned> pre_pstart;    // this event type's share of the fused expand preparation (builds with >= 2 secondaries)
   DBuf<int32_t> pre_plen;
   DBuf<int64_t> pre_tsum;       // ... and the scan-tile sums of pre_plen the fused pass leaves (the expand scan then skips its reduce pass)
@@ -209,32 +177,13 @@ struct EvState {
   DBuf<unsigned short> mlen16;
   DBuf<int32_t> mlen_bad;
   DBuf<int64_t> moff, mtmp, to_nnz;
-  hipEvent_t ev_sampled = nullptr, ev_done = nullptr, ev_rp = nullptr;
-  hipEvent_t ev_cons[A_SETS] = {};  // ev_cons[q]: the A'B_d of the last build that used the primary's buffer set q has finished
+  Event ev_sampled, ev_done, ev_rp;
+  Event ev_cons[A_SETS];  // ev_cons[q]: the A'B_d of the last build that used the primary's buffer set q has finished
   bool cons_valid[A_SETS] = {};
   // facts of the current build
   const int64_t* b_rp = nullptr;  // the B this GPU multiplies with
   const int32_t* b_ci = nullptr;
   int64_t b_rows = 0, b_nnz_bound = 0;
-  void release() {
-    in_rp.release(); in_ci.release(); raw.release(); post.release(); s_rp.release(); s_ci.release(); deg.release(); f_deg.release();
-    deg16.release(); f_deg16.release();
-    f_rp.release(); f_ci.release(); sizes.release(); scan_tmp.release(); o_count.release(); o_idx.release(); o_llr.release(); c_rp.release();
-    c_idx.release(); c_llr.release(); stats.release(); verr.release(); b_pk.release(); pk_bad.release(); s_pk.release(); pre_pstart.release(); pre_plen.release(); pre_tsum.release();
-    mlen.release(); pack.release(); mlen16.release(); mlen_bad.release(); moff.release(); mtmp.release(); to_nnz.release();
-    if (h_verr) (void)hipHostFree(h_verr);
-    h_verr = nullptr;
-    h_verr_dev = nullptr;
-    if (ev_sampled) (void)hipEventDestroy(ev_sampled);
-    if (ev_done) (void)hipEventDestroy(ev_done);
-    if (ev_rp) (void)hipEventDestroy(ev_rp);
-    for (int q = 0; q < A_SETS; ++q) {
-      if (ev_cons[q]) (void)hipEventDestroy(ev_cons[q]);
-      ev_cons[q] = nullptr;
-      cons_valid[q] = false;
-    }
-    ev_sampled = ev_done = ev_rp = nullptr;
-  }
 };
 
 struct DevState {
@@ -260,11 +209,14 @@ struct DevState {
   DBuf<unsigned short> len16;
   DBuf<char> f_len;
   DBuf<unsigned long long> need;  // row-filtered exchange: per local user the ranks whose item range its row of A' touches
-  hipEvent_t need_ready = nullptr;
-  hipEvent_t a_ready = nullptr, in_ready = nullptr, b_expanded = nullptr;
+  Event need_ready;
+  Event a_ready, in_ready, b_expanded;
   Rccl::Comm comm = nullptr;
   int32_t item_lo = 0, item_hi = 0;
   int64_t a_ents = 0;  // entries of the primary's CSC over [item_lo, item_hi) (known exactly when it was merged from fragments)
+  DevState() = default;  DevState(DevState&&) = default;
+  // (urcco_context_destroy has made `device` current and drained every stream) the sessions first, then -- the members -- every buffer and event
+  ~DevState() { for (urcco_session* s : sessions) urcco_session_destroy(s); }
 };
 
 struct Shard {  // one device-resident user-range shard handed to the pipelines
@@ -516,16 +468,10 @@ int ensure_events(urcco_context* c, DevState& D, int n_ds) {
     EvState& E = D.ev[(size_t)d];
     E.s = sess_of(c, D, d);
     E.s->unordered_rows = (c->flags & URCCO_FLAG_UNORDERED_ROWS) ? 1 : 0;
-    if (!E.ev_sampled) HIPC(hipEventCreateWithFlags(&E.ev_sampled, hipEventDisableTiming));
-    if (!E.ev_done) HIPC(hipEventCreateWithFlags(&E.ev_done, hipEventDisableTiming));
-    for (int q = 0; q < A_SETS; ++q)
-      if (!E.ev_cons[q]) HIPC(hipEventCreateWithFlags(&E.ev_cons[q], hipEventDisableTiming));
-    if (!E.ev_rp) HIPC(hipEventCreateWithFlags(&E.ev_rp, hipEventDisableTiming));
+    for (Event* e : {&E.ev_sampled, &E.ev_done, &E.ev_rp}) URC(e->ensure());
+    for (Event& e : E.ev_cons) URC(e.ensure());
   }
-  if (!D.a_ready) HIPC(hipEventCreateWithFlags(&D.a_ready, hipEventDisableTiming));
-  if (!D.in_ready) HIPC(hipEventCreateWithFlags(&D.in_ready, hipEventDisableTiming));
-  if (!D.b_expanded) HIPC(hipEventCreateWithFlags(&D.b_expanded, hipEventDisableTiming));
-  if (!D.need_ready) HIPC(hipEventCreateWithFlags(&D.need_ready, hipEventDisableTiming));
+  for (Event* e : {&D.a_ready, &D.in_ready, &D.b_expanded, &D.need_ready}) URC(e->ensure());
   return URCCO_OK;
 }
 
@@ -603,7 +549,7 @@ struct InputGate {
     // the check's result was STORED to host-mapped memory by the last kernel of the staging chain (stage_event): waiting for the stream is all
     // it takes -- an 8-byte D2H copy here queued on the copy engine behind the other event types' results (round 6: 39 ms on config 4)
     HIPC(hipStreamSynchronize(E.s->stream));
-    const unsigned long long bad = E.h_verr ? *(volatile unsigned long long*)E.h_verr : 0ull;
+    const unsigned long long bad = E.h_verr.word ? *(volatile unsigned long long*)E.h_verr.word.get() : 0ull;
     if (bad)
       return fail(URCCO_BAD_ARG, "dataset %d: %llu invalid entries (row_ptr not monotone, or col_idx out of [0, n_cols) / not strictly increasing inside a row)", d, bad);
     if (trace) trace->mark("matrices landed and checked", d);
@@ -665,7 +611,7 @@ int build_single(urcco_context* c, DevState& D, const std::vector<Shard>& sh, co
       if (d > 0 && E.s != L.s) HIPC(hipStreamWaitEvent(L.s->stream, E.ev_sampled, 0));  // (the primary: a_ready, above)
       URC(E.pre_pstart.ensure((size_t)a_cap + 1));
       URC(E.pre_plen.ensure((size_t)a_cap + 1));
-      URC(E.pre_tsum.ensure(expand_tile_words(a_cap)));
+      URC(E.pre_tsum.ensure(scan_tile_words(a_cap)));
       ts[(size_t)(d - f0)] = E.pre_tsum.p;
       rp[(size_t)(d - f0)] = E.s_rp.p;
       ps[(size_t)(d - f0)] = E.pre_pstart.p;
@@ -1260,7 +1206,7 @@ int build_sharded(urcco_context* c, const std::vector<std::vector<Shard>>& sh, c
         if (E.s != L.s) HIPC(hipStreamWaitEvent(L.s->stream, E.ev_sampled, 0));
         URC(E.pre_pstart.ensure((size_t)D.a_ents + 1));
         URC(E.pre_plen.ensure((size_t)D.a_ents + 1));
-        URC(E.pre_tsum.ensure(expand_tile_words(D.a_ents)));
+        URC(E.pre_tsum.ensure(scan_tile_words(D.a_ents)));
         ts[(size_t)d - 1] = E.pre_tsum.p;
         rp[(size_t)d - 1] = E.b_rp;
         pst[(size_t)d - 1] = E.pre_pstart.p;
@@ -1424,20 +1370,13 @@ void urcco_context_destroy(urcco_context* c) {
   if (!c) return;
   CallerDevice restore;
   c->pending.reset();  // joins a builder thread of a staged build nobody finished
-  for (DevState& D : c->devs) {
+  // Nothing of a device is freed before that device is current and every stream of it is drained; then its DevState goes, and with it
+  // (~DevState, the owning members) its sessions, buffers and events.  The emulation stream, which its sessions only borrow, goes last.
+  for (DevState& slot : c->devs) {
+    DevState D = std::move(slot);  // goes at the end of this iteration
     (void)hipSetDevice(D.device);
     for (urcco_session* s : D.sessions) (void)hipStreamSynchronize(s->stream);
     if (D.comm && c->rccl) (void)c->rccl->CommDestroy(D.comm);
-    for (EvState& E : D.ev) E.release();
-    for (int q = 0; q < A_SETS; ++q) { D.a_cp[q].release(); D.a_ri[q].release(); D.a_post[q].release(); }
-    D.work.release(); D.bounds.release();
-    D.l_cnt.release(); D.l_ri.release(); D.len_bad.release(); D.f_ent.release(); D.l_cp.release(); D.rec.release(); D.len16.release(); D.f_len.release();
-    if (D.a_ready) (void)hipEventDestroy(D.a_ready);
-    if (D.in_ready) (void)hipEventDestroy(D.in_ready);
-    if (D.b_expanded) (void)hipEventDestroy(D.b_expanded);
-    if (D.need_ready) (void)hipEventDestroy(D.need_ready);
-    D.need.release();
-    for (urcco_session* s : D.sessions) urcco_session_destroy(s);
   }
   if (c->emu_stream) (void)hipStreamDestroy(c->emu_stream);
   c->rings.clear();
@@ -1720,7 +1659,7 @@ int urcco_context_stage(urcco_context* c, const urcco_dataset* datasets, int32_t
         URC(E.in_rp.ensure((size_t)rows + 1));
         URC(E.in_ci.ensure((size_t)nnz + 4));
         URC(E.verr.ensure(1));
-        URC(E.ensure_h_verr());
+        URC(E.h_verr.ensure());
         sh[(size_t)d][g] = Shard{rows, u0, nnz, E.in_rp.p, E.in_ci.p};
       }
     }
@@ -1739,7 +1678,7 @@ int urcco_context_stage(urcco_context* c, const urcco_dataset* datasets, int32_t
         gl = gl < 1 ? 1 : (gl > 6 ? 6 : gl);
         HIPC(urcco::launch_validate_csr(E.s->stream, D.n_cu, x.n_rows, E.in_rp.p, E.in_ci.p, x.nnz, (int32_t)m.n_cols, gl, e0, E.verr.p));
         HIPC(urcco::launch_rebase_i64(E.s->stream, D.n_cu, E.in_rp.p, x.n_rows + 1, e0));
-        HIPC(urcco::launch_publish_word(E.s->stream, E.verr.p, E.h_verr_dev));
+        HIPC(urcco::launch_publish_word(E.s->stream, E.verr.p, E.h_verr.dev));
         return URCCO_OK;
       });
     };

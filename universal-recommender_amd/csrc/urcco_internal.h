@@ -7,7 +7,10 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
+#include <type_traits>
+#include <utility>
 #include <vector>
 
 #include "../../include/urcco.h"
@@ -68,7 +71,7 @@ inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 //   URCCO_DEBUG_MARKS=1   flight recorder: every launch group of every session writes "begun" / "finished" marks (build ordinal, stage)
 //                         into pinned host memory, in stream order; a SIGABRT handler (the HSA runtime aborts the process on a GPU
 //                         memory fault) prints every session's last marks, so the launch groups in flight at the fault are known
-//   URCCO_DEBUG_POISON=1  every fresh device allocation of the library and the WHOLE scratch arena at every reserve() are filled with
+//   URCCO_DEBUG_POISON=1  every fresh device allocation of the library and the WHOLE scratch arena at every ArenaLayout::commit() are filled with
 //                         0x7f bytes (stream-ordered): a kernel that consumes memory nobody wrote meets an index ~2^31 elements away
 //                         (or a 64-bit offset beyond the address space) instead of a stale but plausible value
 struct DebugCfg { bool marks = false, poison = false; };
@@ -83,6 +86,78 @@ inline int ceil_log2_i64(int64_t v) {
   while (((int64_t)1 << l) < v) ++l;
   return l;
 }
+
+// words of scan-tile sums a tiled scan over n elements needs (the launch_scan_* family of cco_kernels.h)
+inline size_t scan_tile_words(int64_t n) { return (size_t)((n + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE + 2); }
+
+// packed accumulator entry: key = column + 1 in the high bits, count in the low ones.  *key_bits = the bits of a key (values 1..n_cols_b; the column
+// itself fits them too), the count keeps the other 32 - *key_bits
+inline int packed_key_bits(int32_t n_cols_b, int* key_bits) {
+  int b = 1;
+  while (((int64_t)1 << b) <= (int64_t)n_cols_b) ++b;
+  if (32 - b < 1) return fail(URCCO_BAD_ARG, "n_cols_b %d too large for the packed accumulator", n_cols_b);
+  *key_bits = b;
+  return URCCO_OK;
+}
+
+// ---- owners of device objects: move-only, released by their destructors, so a struct that holds them needs no release list.  What it does need:
+// its device is current and its streams are drained when it goes away (urcco_session_destroy, urcco_context_destroy) ----
+template <typename T>
+struct DBuf {  // device buffer that only grows (hipFree synchronises the device: growth happens on the first builds only)
+  T* p = nullptr;
+  size_t cap = 0;
+  DBuf() = default;
+  DBuf(DBuf&& o) noexcept : p(o.p), cap(o.cap) { o.p = nullptr; o.cap = 0; }
+  DBuf& operator=(DBuf&& o) noexcept { std::swap(p, o.p); std::swap(cap, o.cap); return *this; }  // (o frees what this held)
+  ~DBuf() { (void)release(); }
+  int release() {  // with hipFree's status, for the paths that can report it
+    const hipError_t e = p ? hipFree(p) : hipSuccess;
+    p = nullptr; cap = 0;
+    return e == hipSuccess ? URCCO_OK : hip_fail(e, "hipFree");
+  }
+  // Exactly n elements, whatever it held before; no growth slack and NO poison fill (fixed-size tables their owner sizes itself): else use ensure().
+  int alloc(size_t n) {
+    URC(release());
+    HIPC(hipMalloc((void**)&p, n * sizeof(T)));
+    cap = n;
+    return URCCO_OK;
+  }
+  int ensure(size_t n) {
+    if (n <= cap && p) return URCCO_OK;
+    size_t want = n + n / 16 + 64;
+#ifdef HIPSIM_HOST_BUILD  // test-only host simulator: no slack, so that an overrun meets the guard page
+    if (hipsim::guard_on()) want = n ? n : 1;
+#endif
+    URC(alloc(want));
+    if (debug_cfg().poison) debug_poison(p, want * sizeof(T), nullptr, false);
+    return URCCO_OK;
+  }
+};
+
+struct Event {  // an event without timing, created on first use under the device that is current then
+  struct Destroy { void operator()(hipEvent_t e) const { (void)hipEventDestroy(e); } };
+  std::unique_ptr<std::remove_pointer<hipEvent_t>::type, Destroy> e;
+  int ensure() {
+    hipEvent_t raw = nullptr;
+    if (!e) { HIPC(hipEventCreateWithFlags(&raw, hipEventDisableTiming)); e.reset(raw); }
+    return URCCO_OK;
+  }
+  operator hipEvent_t() const { return e.get(); }
+};
+
+struct MappedWord {  // one host-mapped, coherent pinned word the GPU stores to: `word` is the CPU's address of it, `dev` the GPU's
+  struct Free { void operator()(unsigned long long* p) const { (void)hipHostFree(p); } };
+  std::unique_ptr<unsigned long long, Free> word;
+  unsigned long long* dev = nullptr;
+  int ensure() {
+    unsigned long long* raw = nullptr;
+    if (word) return URCCO_OK;
+    HIPC(hipHostMalloc((void**)&raw, sizeof(*raw), hipHostMallocMapped | hipHostMallocCoherent));
+    word.reset(raw);
+    HIPC(hipHostGetDevicePointer((void**)&dev, raw, 0));
+    return URCCO_OK;
+  }
+};
 
 }  // namespace urcco_detail
 
@@ -100,8 +175,7 @@ int pack_counts(urcco_session* s, const int64_t* b_row_ptr, int64_t n_rows_b, co
                 int32_t* out, int32_t* bad);
 int partition_dev(urcco_session* s, int32_t n_items, const int64_t* work, int32_t n_parts, int32_t* bounds_dev, int32_t** bounds_out);
 int expand_multi(urcco_session* s, int n, const int64_t* a_col_ptr, int32_t n_items_a, const int32_t* a_row_idx, int64_t cap, const int64_t* const* b_row_ptr,
-                 int64_t n_users, unsigned* const* pstart, int32_t* const* plen, int64_t* const* tile_sums = nullptr /* [d]: expand_tile_words(cap) words */);
-inline size_t expand_tile_words(int64_t cap) { return (size_t)((cap + urcco::SCAN_TILE - 1) / urcco::SCAN_TILE + 2); }
+                 int64_t n_users, unsigned* const* pstart, int32_t* const* plen, int64_t* const* tile_sums = nullptr /* [d]: scan_tile_words(cap) words */);
 }  // namespace urcco_detail
 
 using namespace urcco_detail;
@@ -111,21 +185,19 @@ struct urcco_session {
   hipStream_t stream = nullptr;
   bool own_stream = false;
   int n_cu = 256;
-  char* arena = nullptr;
-  size_t arena_cap = 0;
-  size_t arena_off = 0;
+  DBuf<char> arena;  // stage scratch: laid out, grown and carved by ArenaLayout alone (below)
   // persistent zeroed dense counters + candidate scratch of the global-accumulator kernel
-  int32_t* g_counts = nullptr;
-  unsigned long long* g_cand_key = nullptr;
-  int32_t* g_cand_col = nullptr;
+  DBuf<int32_t> g_counts;
+  DBuf<unsigned long long> g_cand_key;
+  DBuf<int32_t> g_cand_col;
   int64_t g_cols = 0;
-  double* xlx_tab = nullptr;  // xLogX of small integers (N-independent), filled once
-  double* xlx_hi = nullptr;   // xLogX(N - d) for the N of the last build
+  DBuf<double> xlx_tab;  // xLogX of small integers (N-independent), filled once
+  DBuf<double> xlx_hi;   // xLogX(N - d) for the N of the last build
   long long xlx_hi_n = -1;
   int debug = 0;              // urcco::DBG_* bits (urcco_session_set_debug)
   unsigned long long narrow_limit = urcco::NARROW_LIMIT;  // urcco_session_set_expand_test (test hook): the tile sum from which the expand tables take the wide form
   long long prefix_seed = 0;                              // ... and where the work prefix starts
-  int32_t* form_word = nullptr;                           // [1] the form of the expand tables of the session's last build (urcco::ExpandForm), allocated on first use
+  DBuf<int32_t> form_word;                                // [1] the form of the expand tables of the session's last build (urcco::ExpandForm), allocated on first use
   bool form_valid = false;                                // a cco_rows_impl has written it
   unsigned* marks = nullptr;  // URCCO_DEBUG_MARKS: pinned host words [0] last launch group begun, [1] last finished ((ordinal << 8) | stage)
   unsigned mark_seq = 0;
@@ -181,51 +253,6 @@ struct urcco_session {
     recs.clear();
   }
 
-  int reserve(size_t bytes) {
-    arena_off = 0;
-#ifdef HIPSIM_HOST_BUILD  // test-only host simulator (tests/hostsim): sub-buffers end at guard pages under HIPSIM_GUARD=1
-    if (hipsim::guard_on()) {
-      hipsim::arena_unguard(arena, arena_cap);
-      bytes += 64 * hipsim::GUARD_PAGE;  // callers that reserve raw byte counts (one block carved by the launcher) do not go through need()
-    }
-#endif
-    if (bytes <= arena_cap) {
-      if (debug_cfg().poison) debug_poison(arena, arena_cap, stream, true);  // what the previous stage left behind is not an input of this one
-      return URCCO_OK;
-    }
-    if (arena) {
-      HIPC(hipStreamSynchronize(stream));
-      HIPC(hipFree(arena));
-      arena = nullptr;
-      arena_cap = 0;
-    }
-    const size_t want = align_up(bytes + bytes / 4, (size_t)1 << 20);
-    HIPC(hipMalloc((void**)&arena, want));
-    arena_cap = want;
-    if (debug_cfg().poison) debug_poison(arena, arena_cap, stream, true);
-    return URCCO_OK;
-  }
-  template <typename T>
-  T* take(size_t n) {
-#ifdef HIPSIM_HOST_BUILD
-    if (hipsim::guard_on()) {
-      T* q = reinterpret_cast<T*>(hipsim::arena_place(arena, arena_off, (n ? n : 1) * sizeof(T), &arena_off));
-      if (arena_off > arena_cap) { fprintf(stderr, "hipsim guard: arena overflow (%zu > %zu)\n", arena_off, arena_cap); abort(); }
-      return q;
-    }
-#endif
-    const size_t bytes = align_up((n ? n : 1) * sizeof(T), 256);
-    char* p = arena + arena_off;
-    arena_off += bytes;
-    return reinterpret_cast<T*>(p);
-  }
-  static size_t need(size_t n, size_t elem) {
-#ifdef HIPSIM_HOST_BUILD
-    if (hipsim::guard_on()) return align_up((n ? n : 1) * elem, hipsim::GUARD_PAGE) + 2 * hipsim::GUARD_PAGE;
-#endif
-    return align_up((n ? n : 1) * elem, 256);
-  }
-
   // Dense per-block counters of the global-accumulator class: g_blocks x n_cols_b x 16 B.  The block count shrinks with
   // the width of B so that the scratch stays within 1 GiB per session (4 GiB from 1M columns on: 128 blocks at 2M, 26 at 10M, never fewer
   // than 2): the class serves the rows no LDS table can hold -- a handful under a Zipf catalogue, thousands under config
@@ -239,7 +266,7 @@ struct urcco_session {
     if (blocks > urcco::GLOBAL_BIN_BLOCKS) blocks = urcco::GLOBAL_BIN_BLOCKS;
     if (blocks < 2) blocks = 2;
     const size_t n = (size_t)blocks * (size_t)n_cols_b;
-    if (n <= g_cap && g_counts) {
+    if (n <= g_cap && g_counts.p) {
       // the counters are zero between launches whatever the geometry (every claim walk restores them)
       g_blocks = (int)(g_cap / (size_t)(n_cols_b > 0 ? n_cols_b : 1) < (size_t)urcco::GLOBAL_BIN_BLOCKS ? g_cap / (size_t)(n_cols_b > 0 ? n_cols_b : 1)
                                                                                                          : (size_t)urcco::GLOBAL_BIN_BLOCKS);
@@ -247,12 +274,12 @@ struct urcco_session {
       return URCCO_OK;
     }
     HIPC(hipStreamSynchronize(stream));
-    if (g_counts) { HIPC(hipFree(g_counts)); HIPC(hipFree(g_cand_key)); HIPC(hipFree(g_cand_col)); }
-    g_counts = nullptr; g_cols = 0; g_cap = 0;
-    HIPC(hipMalloc((void**)&g_counts, n * sizeof(int32_t)));
-    HIPC(hipMalloc((void**)&g_cand_key, n * sizeof(unsigned long long)));
-    HIPC(hipMalloc((void**)&g_cand_col, n * sizeof(int32_t)));
-    HIPC(hipMemsetAsync(g_counts, 0, n * sizeof(int32_t), stream));
+    URC(g_counts.release()); URC(g_cand_key.release()); URC(g_cand_col.release());  // all three first: the new ones may not fit beside the old
+    g_cols = 0; g_cap = 0;
+    URC(g_counts.alloc(n));
+    URC(g_cand_key.alloc(n));
+    URC(g_cand_col.alloc(n));
+    HIPC(hipMemsetAsync(g_counts.p, 0, n * sizeof(int32_t), stream));
     g_cols = n_cols_b;
     g_cap = n;
     g_blocks = (int)blocks;
@@ -260,3 +287,64 @@ struct urcco_session {
   }
 };
 
+// The scratch of one stage, declared once: every buffer gives add() the pointer it will live in and its element count; commit() sums the entries, reserves
+// the session's arena for them -- what the previous stage carved is gone -- and only then hands out the addresses, in the order of the add() calls.  Until
+// commit() has returned URCCO_OK every declared pointer is NULL.  No heap allocation: CAPACITY entries, one more makes commit() fail with URCCO_INTERNAL.
+class ArenaLayout {
+ public:
+  static constexpr int CAPACITY = 64;
+  // the largest user is urcco_dev_history_rows: three buffers per event type, three for the exclusions, three shared ones
+  static_assert(CAPACITY >= 3 * URCCO_REC_MAX_CLAUSES + 6, "more event types need a larger ArenaLayout::CAPACITY (urcco_dev_history_rows)");
+
+  explicit ArenaLayout(urcco_session* s) : s_(s) {}
+  template <typename T>
+  ArenaLayout& add(T** out, size_t n) {
+    *out = nullptr;
+    if (n_ < CAPACITY) e_[n_] = Entry{out, (n ? n : 1) * sizeof(T), [](void* slot, char* p) { *static_cast<T**>(slot) = reinterpret_cast<T*>(p); }};
+    ++n_;
+    return *this;
+  }
+
+  // The arena is reused when it is large enough; else the stream is drained and a quarter more than asked, rounded up to 1 MiB, replaces it (URCCO_DEBUG_POISON: filled whole).
+  int commit() {
+    if (n_ > CAPACITY) return fail(URCCO_INTERNAL, "scratch layout: %d buffers, room for %d", n_, CAPACITY);
+    size_t bytes = 0, off = 0;
+    for (int i = 0; i < n_; ++i) bytes += slot_bytes(e_[i].bytes);
+    DBuf<char>& arena = s_->arena;
+#ifdef HIPSIM_HOST_BUILD
+    if (hipsim::guard_on()) hipsim::arena_unguard(arena.p, arena.cap);
+#endif
+    if (bytes > arena.cap) {
+      if (arena.p) HIPC(hipStreamSynchronize(s_->stream));
+      URC(arena.alloc(align_up(bytes + bytes / 4, (size_t)1 << 20)));
+    }
+    if (debug_cfg().poison) debug_poison(arena.p, arena.cap, s_->stream, true);
+    for (int i = 0; i < n_; ++i) e_[i].set(e_[i].slot, place(arena, &off, e_[i].bytes));
+    return URCCO_OK;
+  }
+
+ private:
+  struct Entry { void* slot; size_t bytes; void (*set)(void* slot, char* p); };
+  // Sub-buffers start 256-byte aligned.  Test-only host simulator (tests/hostsim) under HIPSIM_GUARD: each ends at a PROT_NONE page (mode 3: starts behind one).
+  static size_t slot_bytes(size_t bytes) {
+#ifdef HIPSIM_HOST_BUILD
+    if (hipsim::guard_on()) return align_up(bytes, hipsim::GUARD_PAGE) + 2 * hipsim::GUARD_PAGE;
+#endif
+    return align_up(bytes, 256);
+  }
+  static char* place(DBuf<char>& arena, size_t* off, size_t bytes) {
+#ifdef HIPSIM_HOST_BUILD
+    if (hipsim::guard_on()) {
+      char* q = hipsim::arena_place(arena.p, *off, bytes, off);
+      if (*off > arena.cap) { fprintf(stderr, "hipsim guard: arena overflow (%zu > %zu)\n", *off, arena.cap); abort(); }
+      return q;
+    }
+#endif
+    char* p = arena.p + *off;
+    *off += align_up(bytes, 256);
+    return p;
+  }
+  urcco_session* s_;
+  Entry e_[CAPACITY];
+  int n_ = 0;
+};
