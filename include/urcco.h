@@ -571,6 +571,44 @@ int urcco_dev_history_rows(urcco_session* s, int64_t n_queries, const int32_t* q
                            const int64_t* extra_row_ptr, const int32_t* extra_col_idx, int32_t n_items,
                            int64_t* excl_row_ptr, int32_t* excl_col_idx, int64_t excl_capacity, int64_t* stats_dev /* nullable */);
 
+/* Device-resident item queries: the model half of a batch of item queries ("people who liked this also liked": getBiasedSimilarItems,
+ * URAlgorithm.scala:770-792), cut from the indicator matrices where the build left them in HBM.  DESIGN.md decision D18.  For query q with item
+ * i = q_items[q] and event type e with cap max_terms (the reference's maxQueryEvents):
+ *   row            ind_col_idx[ind_row_ptr[i] .. ind_row_ptr[i + 1]) in stored order (strongest first for an ordered build), of length n
+ *   window         all n entries when n <= max_terms, otherwise the first max_terms - 1 (the reference's `slice(0, maxQueryEvents - 1)`, :782);
+ *                  max_terms == 1 with n > 1 therefore gives an empty window.  An entry outside 0..n_cols COUNTS toward the cut and contributes no column
+ *   term row       the distinct columns of the window, ascending -- the form urcco_rec_clause.q_col_idx and the ANY / NONE rule rows need; duplicates
+ *                  inside a row are legal (a model may be loaded from a caller's matrix) and make the term row shorter than the window
+ *   unknown item   q_items[q] < 0 or >= n_items: empty rows
+ * Exclusion rows stay with the caller: the query item (unless returnSelf) and blacklistItems are known on the host.
+ * Everything is integer: the rows are bit-identical from run to run.
+ *
+ * urcco_dev_item_bounds: term_row_ptr of every type receives the exclusive scan of the window lengths, upper bounds of the rows' lengths.  The caller reads
+ *   the n_types totals (term_row_ptr[n_queries]: its one synchronisation), allocates term_col_idx of at least that many entries and states the size in
+ *   term_capacity.
+ * urcco_dev_item_rows: the same arguments, the row_ptr arrays as _bounds left them; on return they hold the final row starts and the col_idx arrays
+ *   the rows.  A capacity below a bound total: a row is written iff its bound ENDS within the capacity (row_ptr[q + 1] as _bounds left it <= capacity);
+ *   every other row of that array -- all rows behind the first one cut, those of bound 0 included -- is left empty and counted in stats[6], and
+ *   stats[0..5] count the written rows only.  Nothing is written at or past col_idx[capacity].
+ * stats_dev (nullable, int64[URCCO_HIST_STATS_LEN]): (query, type) pairs served by [0] the wave class (window <= 64 entries), [1] the block class
+ *   (<= 4096, sorted in LDS), [2] the global class; [3] pairs whose row was cut (n > max_terms); [6] rows dropped for lack of capacity (0 when the caller
+ *   sized its buffers by the bounds); every other entry 0.
+ * Both enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: n_types outside
+ * 1..URCCO_REC_MAX_CLAUSES, max_terms < 1, n_cols < 0, n_queries * n_types >= 2^31, a NULL the call needs, a negative capacity.
+ * ABI: additions within ABI 305 -- the presence of the symbols is the feature test. */
+typedef struct urcco_item_event {
+  int32_t n_cols, max_terms;          /* max_terms >= 1: the reference's maxQueryEvents */
+  const int64_t* ind_row_ptr;         /* device: indicator CSR of this event type, n_items rows, as the build leaves it */
+  const int32_t* ind_col_idx;         /* order inside a row = stored order (strongest first for an ordered build) */
+  int64_t* term_row_ptr;              /* [n_queries + 1]: bounds after _bounds, final after _rows */
+  int32_t* term_col_idx;              /* _rows: capacity term_capacity; _bounds does not read it */
+  int64_t term_capacity;              /* _rows: entries of term_col_idx, >= the bound total the caller read after _bounds */
+} urcco_item_event;
+
+int urcco_dev_item_bounds(urcco_session* s, int64_t n_queries, const int32_t* q_items, int32_t n_items, urcco_item_event* events, int32_t n_types);
+int urcco_dev_item_rows(urcco_session* s, int64_t n_queries, const int32_t* q_items, int32_t n_items, urcco_item_event* events, int32_t n_types,
+                        int64_t* stats_dev /* nullable */);
+
 /* Test hooks (device level): LLR of SimilarityAnalysis.logLikelihoodRatio evaluated by the device code for
  * n argument tuples; u01 of the down-sampling RNG.  All pointers device. */
 int urcco_dev_llr(urcco_session* s, int64_t n, const int64_t* with_a, const int64_t* with_b, const int64_t* with_ab,

@@ -12,8 +12,12 @@ path belongs under profiles/ (DESIGN.md section 7a).
 device, indexed (urcco_dev_history_index), and the queries' term rows and exclusion rows built by urcco_dev_history_bounds + _rows (caps 500, the
 primary as the blacklist event); their device time (HIP events, the read of the bound totals in between included) is printed next to the wall time
 of the host planning of recommend.batch_predict's dict form for the same queries (per query and event type: reversed slice, dict.fromkeys, one
-dictionary lookup per item, np.unique) on this box.  --no-torch skips the torch comparison.
-usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--rules] [--device-history] [--no-torch]"""
+dictionary lookup per item, np.unique) on this box.
+--device-items: the model half of --queries item queries (decision D18), one per item from item 0 on (wrapping around the catalogue): the device time
+(HIP events, the read of the bound totals included) of urcco_dev_item_bounds + _rows over the model's indicator matrices, next to the wall time of the
+host planning recommend.batch_predict does for the same queries on this box -- the one-off copy of every indicator matrix to the host, printed on
+its own, then per query and event type a slice, an astype and np.unique, and the CSR of the rows.  --no-torch skips the torch comparison.
+usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--rules] [--device-history] [--device-items] [--no-torch]"""
 import argparse
 import os
 import sys
@@ -24,7 +28,7 @@ import torch  # noqa: E402
 
 from universal_recommender_amd import _lib, synth  # noqa: E402
 from universal_recommender_amd.device import DatasetParams, DevCsr, DeviceSession, cross_occurrence_device  # noqa: E402
-from universal_recommender_amd.recommend import DeviceModel  # noqa: E402
+from universal_recommender_amd.recommend import DeviceModel, _csr  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--users", type=int, default=1_000_000)
@@ -34,6 +38,7 @@ ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--num", type=int, default=20)
 ap.add_argument("--rules", action="store_true", help="also time the call under an ANY and a NONE rule")
 ap.add_argument("--device-history", action="store_true", help="also time history_bounds + history_rows against the host planning loop")
+ap.add_argument("--device-items", action="store_true", help="also time item_bounds + item_rows against the host planning loop of item queries")
 ap.add_argument("--no-torch", action="store_true", help="skip the torch comparison")
 args = ap.parse_args()
 
@@ -139,6 +144,46 @@ if args.device_history:
         np.unique(np.array([dicts[0].get(i) for i in lists[0][u]], np.int64))
     host_ms = (time.perf_counter() - t0) * 1e3
     print(f"host planning loop of the dict form, same queries (recommend.py, one thread): {host_ms:.0f} ms wall -- {host_ms / min(ms_hist):.0f}x the device calls")
+
+if args.device_items:
+    import time
+
+    import numpy as np
+    MQE = 5000                                                            # maxQueryEvents of five indicators at the default maxItemsPerUser: nothing is cut at k = 50
+    nqi = args.queries
+    q_items = (torch.arange(nqi, device=dev) % n_items).to(torch.int32)
+    specs = [(c.n_cols, MQE, c.row_ptr, c.col_idx) for c in model.correlators]
+    ms_items = []
+    for r in range(args.reps + 1):
+        rows, info = sess.item_rows(q_items, specs, stats=True, timing=True, n_items=n_items)
+        if r:
+            ms_items.append(info["ms"])
+    its = info["stats"].cpu().tolist()
+    print(f"urcco_dev_item_bounds + _rows ({nqi} item queries x {len(specs)} event types, maxQueryEvents {MQE}): {min(ms_items):.2f} ms best, "
+          f"{sorted(ms_items)[len(ms_items) // 2]:.2f} ms median of {args.reps} ({[round(x, 2) for x in ms_items]})")
+    print(f"  pairs by class: wave {its[0]}, block {its[1]}, global {its[2]}; cut {its[3]}; term entries {[int(rp[-1].item()) for rp, _ in rows]}")
+    # the host planning of recommend.batch_predict for the same queries: DeviceModel.indicator_row's copy of the matrices, then the per-query loop
+    for c in model.correlators:
+        c.host = None
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for c in model.correlators:
+        model.indicator_row(c, 0)
+    copy_ms = (time.perf_counter() - t0) * 1e3
+    q_host = q_items.cpu().tolist()
+    t0 = time.perf_counter()
+    planned = [[] for _ in model.correlators]
+    for i in q_host:
+        for t, c in enumerate(model.correlators):
+            ids = model.indicator_row(c, i)
+            if ids.size > MQE:
+                ids = ids[: MQE - 1]
+            planned[t].append(np.unique(ids.astype(np.int64)))
+    for p_rows in planned:                                                # the clause rows of the call, as batch_predict ships them
+        _csr(p_rows, dev)
+    torch.cuda.synchronize()
+    loop_ms = (time.perf_counter() - t0) * 1e3
+    print(f"host planning of the same item queries (recommend.py, one thread): matrices to the host once {copy_ms:.0f} ms wall, per-query loop {loop_ms:.0f} ms wall")
 
 if args.no_torch:
     sess.close()

@@ -122,6 +122,12 @@ class HistEvent(C.Structure):
                 ("term_col_idx", C.c_void_p), ("term_capacity", C.c_int64)]
 
 
+class ItemEvent(C.Structure):
+    """urcco_item_event: one event type of urcco_dev_item_bounds / _rows."""
+    _fields_ = [("n_cols", C.c_int32), ("max_terms", C.c_int32), ("ind_row_ptr", C.c_void_p), ("ind_col_idx", C.c_void_p), ("term_row_ptr", C.c_void_p),
+                ("term_col_idx", C.c_void_p), ("term_capacity", C.c_int64)]
+
+
 # every symbol include/urcco.h declares: (restype, argtypes)
 _p = C.c_void_p
 SYMBOLS = {
@@ -185,6 +191,8 @@ SYMBOLS = {
     "urcco_dev_history_index": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_bounds": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.POINTER(HistEvent), C.c_int32, _p, _p, _p]),
     "urcco_dev_history_rows": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.POINTER(HistEvent), C.c_int32, _p, _p, C.c_int32, _p, _p, C.c_int64, _p]),
+    "urcco_dev_item_bounds": (C.c_int, [_p, C.c_int64, _p, C.c_int32, C.POINTER(ItemEvent), C.c_int32]),
+    "urcco_dev_item_rows": (C.c_int, [_p, C.c_int64, _p, C.c_int32, C.POINTER(ItemEvent), C.c_int32, _p]),
     "urcco_dev_llr": (C.c_int, [_p, C.c_int64, _p, _p, _p, _p, _p]),
     "urcco_dev_u01": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p]),
     "urcco_dev_u01_rng": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, C.c_int32, _p]),

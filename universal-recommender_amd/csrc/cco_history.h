@@ -55,6 +55,9 @@ __device__ __forceinline__ int hs_wave_tail(int v, int lane, int32_t* __restrict
 }
 
 // one block: row[0..m) (global) -> sorted, duplicate-free, in place; returns the length (all threads).  s_v: HS_LDS ints of LDS.
+// STAGED (cco_items.h): the caller has put the m entries where the sort reads them -- s_v[0 .. 2^ceil(log2 m)), HS_SENT behind the m-th, when
+// m <= HS_LDS, else row[0..m) -- and HS_SENT among them marks an entry to drop; the result still goes to row.
+template <bool STAGED = false>
 __device__ __forceinline__ int hs_block_tail(int32_t* __restrict__ row, int m, int* s_v) {
   __shared__ int s_wsum[256 / IG_WAVE];
   if (m <= 0) return 0;  // block-uniform
@@ -63,7 +66,8 @@ __device__ __forceinline__ int hs_block_tail(int32_t* __restrict__ row, int m, i
   while (P < m) P <<= 1;
   const bool in_lds = m <= HS_LDS;
   if (in_lds) {
-    for (int t = threadIdx.x; t < P; t += 256) s_v[t] = t < m ? row[t] : HS_SENT;
+    if (!STAGED)
+      for (int t = threadIdx.x; t < P; t += 256) s_v[t] = t < m ? row[t] : HS_SENT;
     __syncthreads();
     for (int k2 = 2; k2 <= P; k2 <<= 1) {
       for (int j = k2 >> 1; j > 0; j >>= 1) {
@@ -101,7 +105,7 @@ __device__ __forceinline__ int hs_block_tail(int32_t* __restrict__ row, int m, i
     if (t < m) {
       v = in_lds ? s_v[t] : row[t];
       const int pv = t == 0 ? 0 : (in_lds ? s_v[t - 1] : row[t - 1]);
-      fresh = t == 0 || v != pv;
+      fresh = (t == 0 || v != pv) && (!STAGED || v != HS_SENT);
     }
     const unsigned long long mk = __ballot(fresh);
     if (lane == 0) s_wsum[wave] = __popcll(mk);

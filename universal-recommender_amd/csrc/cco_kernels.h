@@ -318,6 +318,28 @@ hipError_t launch_history_bounds(hipStream_t st, int n_cu, const HistArgs& a, in
 hipError_t launch_history_rows(hipStream_t st, int n_cu, const HistArgs& a, int64_t* tile_sums, int64_t* const* term_row_ptr, int32_t* const* term_col_idx,
                                int64_t* excl_row_ptr, int32_t* excl_col_idx, int64_t* stats_dev);
 
+// ---- device-resident item queries (cco_items.h, compiled into ingest_kernels.hip behind cco_history.h; decision D18) ----
+struct ItemEvent {
+  const int64_t* ind_row_ptr;  // the indicator CSR of the event type, n_items rows, as the build leaves it
+  const int32_t* ind_col_idx;
+  int64_t* raw_ptr;            // scratch [n_queries + 1]: the raw row starts (scan of the bounds)
+  int32_t* tmp;                // scratch [capacity]: the raw rows
+  int32_t* len;                // scratch [n_queries]: the rows' final lengths
+  int64_t capacity;            // entries of the caller's term_col_idx (and of tmp)
+  int32_t n_cols, max_terms;
+};
+struct ItemArgs {
+  ItemEvent ev[REC_MAX_CLAUSES];
+  int64_t n_queries;
+  const int32_t* q_items;
+  int32_t* big_list;             // scratch [n_queries * n_types]: jobs of more than one wave
+  unsigned long long* ctr;       // scratch [1]: the cursor of big_list
+  int32_t n_types, n_items;
+};
+// bnd [n_types * n_queries]: scratch; only the inputs of `a` are read
+hipError_t launch_item_bounds(hipStream_t st, int n_cu, const ItemArgs& a, int32_t* bnd, int64_t* tile_sums, int64_t* const* term_row_ptr);
+hipError_t launch_item_rows(hipStream_t st, int n_cu, const ItemArgs& a, int64_t* tile_sums, int64_t* const* term_row_ptr, int32_t* const* term_col_idx, int64_t* stats_dev);
+
 hipError_t launch_llr_test(hipStream_t st, int64_t n, const int64_t* a, const int64_t* b, const int64_t* ab, const int64_t* nu, double* out);
 hipError_t launch_u01_test(hipStream_t st, int64_t n, uint32_t seed, const int32_t* row, const int32_t* col, double* out, int rng32 = 0);
 

@@ -314,3 +314,4 @@ hipError_t launch_csr_from_pairs(hipStream_t st, int n_cu, int64_t n, const int3
 }  // namespace urcco
 
 #include "cco_history.h"  // device-resident user history: uses ig_grid and ig_compact_rows_kernel
+#include "cco_items.h"    // device-resident item queries: the tails of cco_history.h over the model's own indicator rows

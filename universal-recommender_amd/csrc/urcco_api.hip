@@ -777,6 +777,60 @@ int urcco_dev_history_rows(urcco_session* s, int64_t n_queries, const int32_t* q
 
 }  // extern "C"
 
+// urcco_dev_item_bounds / _rows: argument checks and the launch arguments
+static int item_args(const char* who, urcco_session* s, int64_t n_queries, const int32_t* q_items, int32_t n_items, const urcco_item_event* events, int32_t n_types,
+                     bool rows, urcco::ItemArgs* a) {
+  if (!s || n_queries < 0 || n_items < 0 || (n_queries > 0 && !q_items)) return fail(URCCO_BAD_ARG, "%s: bad argument", who);
+  if (n_types < 1 || n_types > URCCO_REC_MAX_CLAUSES || !events) return fail(URCCO_BAD_ARG, "%s: between 1 and %d event types, got %d", who, URCCO_REC_MAX_CLAUSES, n_types);
+  if (n_queries * (int64_t)n_types > 0x7ffffff0ll) return fail(URCCO_BAD_ARG, "%s: too many queries", who);
+  *a = urcco::ItemArgs{};
+  for (int t = 0; t < n_types; ++t) {
+    const urcco_item_event& in = events[t];
+    if (in.max_terms < 1) return fail(URCCO_BAD_ARG, "%s: event type %d: max_terms must be >= 1, got %d", who, t, in.max_terms);
+    if (in.n_cols < 0 || !in.ind_row_ptr || !in.ind_col_idx || !in.term_row_ptr || (rows && (!in.term_col_idx || in.term_capacity < 0)))
+      return fail(URCCO_BAD_ARG, "%s: event type %d: bad argument", who, t);
+    urcco::ItemEvent& e = a->ev[t];
+    e.ind_row_ptr = in.ind_row_ptr; e.ind_col_idx = in.ind_col_idx; e.capacity = in.term_capacity; e.n_cols = in.n_cols; e.max_terms = in.max_terms;
+  }
+  a->n_queries = n_queries; a->q_items = q_items; a->n_types = n_types; a->n_items = n_items;
+  return URCCO_OK;
+}
+
+extern "C" {
+
+int urcco_dev_item_bounds(urcco_session* s, int64_t n_queries, const int32_t* q_items, int32_t n_items, urcco_item_event* events, int32_t n_types) {
+  urcco::ItemArgs a;
+  URC(item_args("urcco_dev_item_bounds", s, n_queries, q_items, n_items, events, n_types, false, &a));
+  int32_t* bnd;
+  int64_t* tile_sums;
+  URC(ArenaLayout(s).add(&bnd, (size_t)n_queries * (size_t)n_types).add(&tile_sums, scan_tile_words(n_queries)).commit());
+  int64_t* rp[URCCO_REC_MAX_CLAUSES];
+  for (int t = 0; t < n_types; ++t) rp[t] = events[t].term_row_ptr;
+  HIPC(urcco::launch_item_bounds(s->stream, s->n_cu, a, bnd, tile_sums, rp));
+  return URCCO_OK;
+}
+
+int urcco_dev_item_rows(urcco_session* s, int64_t n_queries, const int32_t* q_items, int32_t n_items, urcco_item_event* events, int32_t n_types, int64_t* stats_dev) {
+  urcco::ItemArgs a;
+  URC(item_args("urcco_dev_item_rows", s, n_queries, q_items, n_items, events, n_types, true, &a));
+  const size_t nq = (size_t)n_queries;
+  ArenaLayout L(s);
+  int64_t* tile_sums;
+  L.add(&tile_sums, scan_tile_words(n_queries)).add(&a.big_list, nq * (size_t)n_types).add(&a.ctr, 1);
+  int64_t* rp[URCCO_REC_MAX_CLAUSES];
+  int32_t* ci[URCCO_REC_MAX_CLAUSES];
+  for (int t = 0; t < n_types; ++t) {
+    L.add(&a.ev[t].raw_ptr, nq + 1).add(&a.ev[t].len, nq).add(&a.ev[t].tmp, (size_t)events[t].term_capacity);
+    rp[t] = events[t].term_row_ptr;
+    ci[t] = events[t].term_col_idx;
+  }
+  URC(L.commit());
+  HIPC(urcco::launch_item_rows(s->stream, s->n_cu, a, tile_sums, rp, ci, stats_dev));
+  return URCCO_OK;
+}
+
+}  // extern "C"
+
 // urcco_dev_recommend (n_rules == 0) and urcco_dev_recommend_rules
 static int recommend_call(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
                           const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,

@@ -303,6 +303,44 @@ class DeviceSession:
             ms = ev0.elapsed_time(ev1)
         return list(zip(rps, cis)), (excl_rp, excl_ci), {"bounds": totals, "stats": st, "ms": ms, "bound_row_ptr": bound_rp}
 
+    def item_rows(self, q_items: torch.Tensor, specs, stats: bool = False, timing: bool = False, n_items: Optional[int] = None, keep_bounds: bool = False):
+        """urcco_dev_item_bounds + urcco_dev_item_rows: the term rows of a batch of item queries, cut from the indicator matrices on the device.
+        q_items: int32 [n_queries] dense item ids (< 0 or >= n_items: unknown, empty rows).  specs: per event type (n_cols, max_terms, ind_row_ptr,
+        ind_col_idx), device tensors: the indicator CSR as the build left it, one row per item.  n_items: the rows of the matrices (default: from the
+        first row_ptr).  Returns (rows, info): rows[t] = (row_ptr int64 [n_queries + 1], col_idx int32), the sorted distinct columns of the first
+        max_terms entries of the item's row (max_terms - 1 when the row is longer); info = {"bounds": [...], "stats": int64 tensor | None, "ms":
+        device time of the two calls | None, "bound_row_ptr": copies of the bounds' row_ptr arrays with keep_bounds (tests)}.  Reads the n_types bound
+        totals between the two calls: one synchronisation."""
+        nq = int(q_items.numel())
+        if n_items is None:
+            n_items = int(specs[0][2].numel()) - 1
+        arr = (_lib.ItemEvent * max(len(specs), 1))()
+        rps = []
+        for t, (n_cols, max_terms, irp, ici) in enumerate(specs):
+            rp = self.empty(nq + 1, torch.int64)
+            rps.append(rp)
+            arr[t].n_cols, arr[t].max_terms, arr[t].ind_row_ptr, arr[t].ind_col_idx, arr[t].term_row_ptr = int(n_cols), int(max_terms), _ptr(irp), _ptr(ici), _ptr(rp)
+        ev0 = ev1 = None
+        if timing and self.device.type == "cuda":
+            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            ev0.record(self.torch_stream)
+        self._check(self.lib.urcco_dev_item_bounds(self.handle, nq, _ptr(q_items), int(n_items), arr, len(specs)))
+        totals = torch.stack([rp[nq] for rp in rps]).cpu().tolist()   # the one synchronisation
+        bound_rp = [rp.clone() for rp in rps] if keep_bounds else None
+        cis = []
+        for t, total in enumerate(totals):
+            ci = self.empty(max(total, 1), torch.int32)
+            cis.append(ci)
+            arr[t].term_col_idx, arr[t].term_capacity = _ptr(ci), int(total)
+        st = self.empty(_lib.HIST_STATS_LEN, torch.int64) if stats else None
+        self._check(self.lib.urcco_dev_item_rows(self.handle, nq, _ptr(q_items), int(n_items), arr, len(specs), _ptr(st)))
+        ms = None
+        if ev0 is not None:
+            ev1.record(self.torch_stream)
+            ev1.synchronize()
+            ms = ev0.elapsed_time(ev1)
+        return list(zip(rps, cis)), {"bounds": totals, "stats": st, "ms": ms, "bound_row_ptr": bound_rp}
+
     def llr(self, with_a, with_b, with_ab, n_users) -> torch.Tensor:
         out = self.empty(with_a.numel(), torch.float64)
         self._check(self.lib.urcco_dev_llr(self.handle, with_a.numel(), _ptr(with_a), _ptr(with_b), _ptr(with_ab), _ptr(n_users), _ptr(out)))

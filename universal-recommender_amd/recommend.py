@@ -208,7 +208,30 @@ def _date_ms(text: str, what: str) -> int:
     return ms
 
 
-def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None) -> List[dict]:
+def _mask_tensor(model: DeviceModel, item_mask) -> Optional[torch.Tensor]:
+    """None, an array of n_items flags or {item: bool} -> uint8 [n_items] on the model's device"""
+    if item_mask is None:
+        return None
+    if isinstance(item_mask, dict):
+        m = np.ones(model.n_items, np.uint8)
+        for item, ok in item_mask.items():
+            i = model.item_index(item)
+            if i is not None:
+                m[i] = 1 if ok else 0
+        return torch.from_numpy(m).to(model.sess.device)
+    mask_t = torch.as_tensor(np.asarray(item_mask) != 0 if not torch.is_tensor(item_mask) else item_mask != 0).to(torch.uint8).to(model.sess.device)
+    if mask_t.numel() != model.n_items:
+        raise ValueError("item_mask needs one flag per item of the primary event")
+    return mask_t
+
+
+def _max_query_events(ap) -> int:
+    if ap.indicators:                                                                          # :203-211
+        return sum(i.maxItemsPerUser if i.maxItemsPerUser is not None else 100 for i in ap.indicators) * 10
+    return ap.maxQueryEvents if ap.maxQueryEvents is not None else 100
+
+
+def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host") -> List[dict]:
     """URAlgorithm.predict for a list of query dicts: [{"itemScores": [{"item", "score"}, ...]}, ...] in the order of `queries`.
     history: user -> {event name: [item ids, oldest first]} (the event store's view of the user), or a history.DeviceHistory: the event streams
     resident on the device.  With a DeviceHistory the user-history term rows (the ("user", ev) clauses, or the ("hist", ev) ANY rules under
@@ -218,7 +241,17 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
     its rows turn out empty (the dict form leaves such a clause out): an all-empty clause adds 0.0 * boost and leaves every score bit-identical,
     but the 16-clause limit of a call can be reached earlier than with the dict form.  item_mask: None, an array of n_items
     flags or {item: bool} (any further filter of the caller's; items not named are eligible -- it applies on top of the rules); now_ms: "now" of the
-    available / expire rule for queries without `currentDate` (default: the wall clock)."""
+    available / expire rule for queries without `currentDate` (default: the wall clock).
+    item_rows: "host" (default) plans the query item's own indicator lists one by one from a host copy of the matrices (DeviceModel.indicator_row; its
+    first use copies every indicator matrix back from the device).  "device" cuts them on the device (decision D18): the ("item", ev) clause rows, or the
+    ("sim", ev) ANY-rule rows under itemBias < 0, of a group come from one urcco_dev_item_bounds + _rows call per group over the group's dense item
+    ids (-1 for a member without a known item), with max_terms = maxQueryEvents; no matrix comes back to the host.  A group in which any member names a
+    known item then carries the item clause of EVERY event type of the model, also where all its rows turn out empty (the host route leaves such a
+    clause out): an all-empty clause adds 0.0 * boost, so every score stays bit-identical to the host route, but the 16-clause limit of a call can be
+    reached earlier."""
+    if item_rows not in ("host", "device"):
+        raise ValueError(f"item_rows must be 'host' or 'device', got {item_rows!r}")
+    dev_items = item_rows == "device"
     ap = algo.ap
     model_events = list(algo.modelEventNames)
     primary = model_events[0]
@@ -226,27 +259,14 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
         if ev not in model.by_name:
             raise ValueError(f"the model holds no indicator matrix for event {ev!r}")
     max_items = {i.name: (i.maxItemsPerUser if i.maxItemsPerUser is not None else 500) for i in ap.indicators} if ap.indicators else {e: 100 for e in model_events}
-    if ap.indicators:                                                                          # :203-211
-        max_query_events = sum(i.maxItemsPerUser if i.maxItemsPerUser is not None else 100 for i in ap.indicators) * 10
-    else:
-        max_query_events = ap.maxQueryEvents if ap.maxQueryEvents is not None else 100
+    max_query_events = _max_query_events(ap)
+    if dev_items and max_query_events < 1:
+        raise ValueError("item_rows='device' needs maxQueryEvents >= 1")
     limit = ap.num if ap.num is not None else 20
     blacklist_events = ap.blacklistEvents if ap.blacklistEvents is not None else [primary]      # :236
     flags = _lib.REC_NO_BACKFILL if algo.recsModel == "collabFiltering" else 0
 
-    mask_t = None
-    if item_mask is not None:
-        if isinstance(item_mask, dict):
-            m = np.ones(model.n_items, np.uint8)
-            for item, ok in item_mask.items():
-                i = model.item_index(item)
-                if i is not None:
-                    m[i] = 1 if ok else 0
-            mask_t = torch.from_numpy(m).to(model.sess.device)
-        else:
-            mask_t = torch.as_tensor(np.asarray(item_mask) != 0 if not torch.is_tensor(item_mask) else item_mask != 0).to(torch.uint8).to(model.sess.device)
-            if mask_t.numel() != model.n_items:
-                raise ValueError("item_mask needs one flag per item of the primary event")
+    mask_t = _mask_tensor(model, item_mask)
 
     # ---- per query: clause terms, exclusions, and the key of the call it can share ----
     groups: Dict[tuple, List[int]] = {}
@@ -323,9 +343,14 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
             if ev in blacklist_events:
                 excl += [model.item_index(i) for i in events.get(ev, [])]
         excl += [model.item_index(i) for i in (q.get("blacklistItems") or [])]
+        q_item = -1
         if item is not None:
             i = model.item_index(item)
-            if i is not None:                                                                   # getBiasedSimilarItems :770-792
+            if i is not None and dev_items:                                                     # the rows come from the device, per group (D18)
+                q_item = i
+                if item_bias < 0:
+                    rules.update({("sim", ev): None for ev in model_events})
+            elif i is not None:                                                                 # getBiasedSimilarItems :770-792
                 for ev in model_events:
                     c = model.by_name[ev]
                     ids = model.indicator_row(c, i)
@@ -351,7 +376,7 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
         key = (_boost(user_bias), _boost(item_bias), _boost(set_bias), start + num, tuple(slot for slot, _ in boosted), tuple(rules), hist_key)
         groups.setdefault(key, []).append(n)
         plans.append((terms, np.unique(np.array([i for i in excl if i is not None], np.int64)), start, num, rules, dh.user_index(user) if dh is not None else -1,
-                      user is not None))
+                      user is not None, q_item))
 
     # ---- one call per group ----
     results: List[Optional[dict]] = [None] * len(queries)
@@ -368,6 +393,14 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
             q_users = torch.tensor([plans[n][5] for n in members], dtype=torch.int32).to(dev)
             rows, excl, _ = model.sess.history_rows(q_users, dh.n_users, specs, model.n_items, excl)
             hist_rows = {ev: r for ev, r in zip(hist_key[0], rows) if ev in model.by_name}
+        item_dev: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        if dev_items and any(plans[n][7] >= 0 for n in members):                                # one item call for the group
+            if len(model_events) > _lib.REC_MAX_CLAUSES:
+                raise ValueError(f"the model has {len(model_events)} event types, more than the {_lib.REC_MAX_CLAUSES} one item call serves")
+            q_items = torch.tensor([plans[n][7] for n in members], dtype=torch.int32).to(dev)
+            rows, _ = model.sess.item_rows(q_items, [(model.by_name[ev].n_cols, max_query_events, model.by_name[ev].row_ptr, model.by_name[ev].col_idx)
+                                                     for ev in model_events], n_items=model.n_items)
+            item_dev = dict(zip(model_events, rows))
         slots = []                                                                              # the reference's order (:653): history, similar items, metadata, item set
         for kind, boost in (("user", ub), ("item", ib), ("field", None), ("set", sb)):
             if kind == "field":
@@ -379,6 +412,10 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
                     if ev in hist_rows and not hist_key[1] and any(plans[n][6] for n in members):
                         slots.append(((kind, ev), model.by_name[ev], boost))
                     continue
+                if kind == "item" and dev_items:                                                # under itemBias < 0 the rows are ANY rules, not clauses
+                    if ev in item_dev and ("sim", ev) not in rule_keys:
+                        slots.append(((kind, ev), model.by_name[ev], boost))
+                    continue
                 if any(plans[n][0].get((kind, ev), empty).size for n in members):
                     slots.append(((kind, ev), model.by_name[ev], boost))
         if len(slots) > _lib.REC_MAX_CLAUSES:
@@ -387,7 +424,8 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
             raise ValueError(f"a batch needs {len(rule_keys)} rules, more than the {_lib.REC_MAX_RULES} one call serves")
         clauses = []
         for slot, c, boost in slots:
-            qrp, qci = hist_rows[slot[1]] if slot[0] == "user" and dh is not None else _csr([plans[n][0].get(slot, empty) for n in members], dev)
+            qrp, qci = (hist_rows[slot[1]] if slot[0] == "user" and dh is not None else item_dev[slot[1]] if slot[0] == "item" and dev_items else
+                        _csr([plans[n][0].get(slot, empty) for n in members], dev))
             clauses.append((c.n_cols, boost, c.col_ptr, c.row_idx, qrp, qci))
         rules = None
         if served:
@@ -401,7 +439,8 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
                     rules.append((_lib.RULE_RANGE, value, lo, hi))
                 else:
                     m = model.properties[rk[1]] if rk[0] in ("any", "none") else model.by_name[rk[1]] if rk[0] in ("hist", "sim") else model.correlators[0]
-                    qrp, qci = hist_rows[rk[1]] if rk[0] == "hist" and rk[1] in hist_rows else _csr([plans[n][4][rk] for n in members], dev)
+                    qrp, qci = (hist_rows[rk[1]] if rk[0] == "hist" and rk[1] in hist_rows else item_dev[rk[1]] if rk[0] == "sim" and dev_items else
+                                _csr([plans[n][4][rk] for n in members], dev))
                     rules.append((_lib.RULE_NONE if rk[0] == "none" else _lib.RULE_ANY, m.n_cols, m.row_ptr, m.col_idx, qrp, qci))
         count, idx, score, _ = model.sess.recommend(len(members), model.n_items, clauses, fetch, excl, mask_t, model.fill_order, flags, stats=False, rules=rules)
         model.sess.synchronize()
@@ -410,3 +449,85 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
             start, num = plans[n][2], plans[n][3]
             results[n] = {"itemScores": [{"item": model.item_name(int(idx[r, j])), "score": float(score[r, j])} for j in range(start, min(int(count[r]), start + num))]}
     return results
+
+
+def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = None, item_bias: Optional[float] = None, return_self: Optional[bool] = None,
+                  chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None):
+    """The item-to-item table ("people who liked this also liked"): row n is what batch_predict answers to {"item": items[n]} -- the same items in the
+    same order with the same scores -- as three device tensors (count int32 [n], idx int32 [n, num], score float64 [n, num]); entries behind count[n]
+    are -1 / 0.0.  No Python work per item: the queries go `chunk` at a time through DeviceSession.item_rows (decision D18) and recommend, and no
+    matrix comes back to the host.
+    items: a sequence of item ids, a device int32 tensor of dense item ids, or None = every item of the model; an id the model does not know is served
+    as batch_predict serves an unknown item (the backfill alone).  num, item_bias, return_self: default to the algorithm's num (20), itemBias (1.0),
+    returnSelf (False).  item_bias > 0: one should-clause per event type of the model over the item's own indicator lists, boost = the bias;
+    item_bias < 0: the lists are ANY rules instead (a model built with item properties, {} will do).  The query item is excluded unless return_self.
+    Backfill, recsModel, item_mask and the available / expire date rule around now_ms are those of batch_predict."""
+    ap = algo.ap
+    sess, dev = model.sess, model.sess.device
+    model_events = list(algo.modelEventNames)
+    for ev in model_events:
+        if ev not in model.by_name:
+            raise ValueError(f"the model holds no indicator matrix for event {ev!r}")
+    if len(model_events) > _lib.REC_MAX_CLAUSES:
+        raise ValueError(f"the model has {len(model_events)} event types, more than the {_lib.REC_MAX_CLAUSES} one call serves")
+    num = int(num if num is not None else ap.num if ap.num is not None else 20)
+    if num < 1 or num > _lib.REC_MAX_NUM:
+        raise ValueError(f"num must lie in 1..{_lib.REC_MAX_NUM}, got {num}")
+    bias = float(item_bias if item_bias is not None else ap.itemBias if ap.itemBias is not None else 1.0)
+    keep_self = bool(return_self if return_self is not None else ap.returnSelf if ap.returnSelf is not None else False)
+    max_terms = _max_query_events(ap)
+    if max_terms < 1 or chunk < 1:
+        raise ValueError("similar_items needs maxQueryEvents >= 1 and chunk >= 1")
+    served = model.properties is not None
+    if bias < 0 and not served:
+        raise NotImplementedError("negative itemBias (similar items as a filter) needs a model built with item properties ({} will do)")
+    flags = _lib.REC_NO_BACKFILL if algo.recsModel == "collabFiltering" else 0
+    mask_t = _mask_tensor(model, item_mask)
+    if items is None:
+        q_all = torch.arange(model.n_items, dtype=torch.int32, device=dev)
+    elif torch.is_tensor(items):
+        if items.dtype != torch.int32 or items.dim() != 1:
+            raise ValueError("items as a tensor: dense item ids, int32, one dimension")
+        q_all = items.to(dev)
+    else:
+        idx_of = [model.item_index(i) for i in items]
+        q_all = torch.tensor([-1 if i is None else i for i in idx_of], dtype=torch.int32).to(dev)
+    n = int(q_all.numel())
+    dates = []
+    if served and ap.availableDateName is not None and ap.expireDateName is not None and ap.availableDateName in model.dates and ap.expireDateName in model.dates:
+        import time
+        now = int(now_ms) if now_ms is not None else int(time.time() * 1000)
+        dates = [(model.dates[ap.availableDateName], NO_VALUE, now + 1), (model.dates[ap.expireDateName], now + 1, OPEN_HI)]
+    specs = [(model.by_name[ev].n_cols, max_terms, model.by_name[ev].row_ptr, model.by_name[ev].col_idx) for ev in model_events]
+    count = torch.zeros(n, dtype=torch.int32, device=dev)
+    idx = torch.full((n, num), -1, dtype=torch.int32, device=dev)
+    score = torch.zeros((n, num), dtype=torch.float64, device=dev)
+    for lo in range(0, n, chunk):
+        q = q_all[lo:lo + chunk].contiguous()
+        m = int(q.numel())
+        known = (q >= 0) & (q < model.n_items)
+        rows, _ = sess.item_rows(q, specs, n_items=model.n_items)
+        if keep_self:
+            excl = (torch.zeros(m + 1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+        else:                                                                                   # one exclusion per known query item: the item itself
+            rp = torch.zeros(m + 1, dtype=torch.int64, device=dev)
+            rp[1:] = torch.cumsum(known, 0)
+            excl = (rp, torch.cat([q[known], torch.zeros(1, dtype=torch.int32, device=dev)]))
+        rules = None
+        if served:
+            rules = [(_lib.RULE_RANGE, value, torch.full((m,), lo_ms, dtype=torch.int64, device=dev), torch.full((m,), hi_ms, dtype=torch.int64, device=dev))
+                     for value, lo_ms, hi_ms in dates]
+        if bias < 0:
+            sim = [(_lib.RULE_ANY, model.by_name[ev].n_cols, model.by_name[ev].row_ptr, model.by_name[ev].col_idx, qrp, qci) for ev, (qrp, qci) in zip(model_events, rows)]
+            c, i, s, _ = sess.recommend(m, model.n_items, [], num, excl, mask_t, model.fill_order, flags, stats=False, rules=sim + rules)
+            if not bool(known.all()):                                                           # an unknown item carries no rule: the backfill alone
+                c2, i2, s2, _ = sess.recommend(m, model.n_items, [], num, excl, mask_t, model.fill_order, flags, stats=False, rules=rules)
+                c, i, s = torch.where(known, c, c2), torch.where(known[:, None], i, i2), torch.where(known[:, None], s, s2)
+        else:
+            clauses = [(model.by_name[ev].n_cols, _boost(bias), model.by_name[ev].col_ptr, model.by_name[ev].row_idx, qrp, qci) for ev, (qrp, qci) in zip(model_events, rows)]
+            c, i, s, _ = sess.recommend(m, model.n_items, clauses, num, excl, mask_t, model.fill_order, flags, stats=False, rules=rules)
+        live = torch.arange(num, device=dev)[None, :] < c[:, None]
+        count[lo:lo + m] = c
+        idx[lo:lo + m] = torch.where(live, i, idx[lo:lo + m])
+        score[lo:lo + m] = torch.where(live, s, score[lo:lo + m])
+    return count, idx, score

@@ -264,13 +264,21 @@ class URAlgorithm:
         return list(zip([n for n, _ in data.actions], res))                                    # :349
 
 
-    def batch_predict(self, model, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None) -> List[dict]:
+    def batch_predict(self, model, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host") -> List[dict]:
         """URAlgorithm.predict (:484-535) for a batch of queries against a recommend.DeviceModel: user history, similar-item and itemSet
         queries, blacklists, backfill by rank and -- for a model built with item properties -- the business rules (fields, dateRange, available /
         expire dates around now_ms, negative biases); see recommend.batch_predict for what is mirrored and what is left out.  history: the dict
-        user -> {event: [items, oldest first]} or a history.DeviceHistory (the event streams resident on the device)."""
+        user -> {event: [items, oldest first]} or a history.DeviceHistory (the event streams resident on the device).  item_rows="device": the query
+        items' own indicator lists are cut on the device instead of planned one by one from a host copy of the matrices."""
         from .recommend import batch_predict
-        return batch_predict(self, model, queries, history, item_mask, now_ms)
+        return batch_predict(self, model, queries, history, item_mask, now_ms, item_rows)
+
+    def similar_items(self, model, items=None, num: Optional[int] = None, item_bias: Optional[float] = None, return_self: Optional[bool] = None,
+                      chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None):
+        """The item-to-item table of `items` (None: every item of the model) as device tensors (count, idx, score): row n is what batch_predict
+        answers to {"item": items[n]}; see recommend.similar_items."""
+        from .recommend import similar_items
+        return similar_items(self, model, items, num, item_bias, return_self, chunk, item_mask, now_ms)
 
     def predict(self, model, query: dict, history, item_mask=None, now_ms: Optional[int] = None) -> dict:
         return self.batch_predict(model, [query], history, item_mask, now_ms)[0]
