@@ -17,18 +17,21 @@ namespace urcco {
 // item's interaction count and N only, so they are evaluated once per item, not once per cooccurrence.
 // ============================================================================================
 __global__ __launch_bounds__(256) void item_entropy_kernel(const int32_t* __restrict__ counts, int32_t n, long long n_users,
-                                                           double* __restrict__ ent, double* __restrict__ xlx_n) {
+                                                           double* __restrict__ ent, double* __restrict__ xlx_n, const unsigned short* __restrict__ mono,
+                                                           unsigned short* __restrict__ lim) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i < n) {
     const long long c = counts[i];
     ent[i] = entropy2(c, n_users - c);
+    if (mono) lim[i] = (c >= 0 && c < (long long)XLX_TABLE) ? mono[c] : (unsigned short)0;  // the row's prefilter limit (cco_rows.hip): rows beyond the table get no pruning
   }
   if (i == 0 && xlx_n) *xlx_n = x_log_x(n_users);
 }
 
-hipError_t launch_item_entropy(hipStream_t st, const int32_t* counts, int32_t n, long long n_users, double* ent, double* xlx_n) {
+hipError_t launch_item_entropy(hipStream_t st, const int32_t* counts, int32_t n, long long n_users, double* ent, double* xlx_n, const unsigned short* mono,
+                               unsigned short* lim) {
   const int blocks = n > 0 ? (n + 255) / 256 : 1;
-  hipLaunchKernelGGL(item_entropy_kernel, dim3(blocks), dim3(256), 0, st, counts, n, n_users, ent, xlx_n);
+  hipLaunchKernelGGL(item_entropy_kernel, dim3(blocks), dim3(256), 0, st, counts, n, n_users, ent, xlx_n, lim ? mono : nullptr, lim);
   return hipGetLastError();
 }
 

@@ -38,6 +38,9 @@ constexpr int32_t DBG_GATHERED_PRIMARY = 8192;      // the primary's CSC from a 
 constexpr int32_t DBG_UNFILTERED_EXCHANGE = 16384;  // several ranks: every row of B is exchanged
 constexpr int32_t DBG_SELECT_DELAY = 131072;        // test hook: the first wave of a multi-wave team dawdles before the select histogram
 constexpr int32_t DBG_UNPACKED_COUNTS = 1048576;    // B' travels as plain columns, the row kernels gather the counts
+// The k11 = 1 prefilter of the packed row kernels (cco_rows.hip).  Neither bit selects the DBG instantiations: the production kernels take them as arguments.
+constexpr int32_t DBG_NO_PREFILTER = 8388608;       // every distinct candidate is scored (A/B, and the tests' bit-for-bit comparison)
+constexpr int32_t DBG_COUNT_SCORED = 16777216;      // with stage timing on: stats[2 + 4 * NBINS] counts the candidates that were SCORED instead of the distinct ones
 constexpr int32_t DBG_ROW_KERNELS = DBG_GATHER_ONLY | DBG_NO_LLR | DBG_NO_TOPK | DBG_NO_SELECT | DBG_NO_RANK | DBG_NO_COUNT_GATHER | DBG_SELECT_DELAY;
 
 // The form of a build's expand tables, decided on the device by the scan of the work prefix (launch_expand_prepare / launch_expand_scan).
@@ -112,6 +115,7 @@ struct CcoArgs {
   int32_t g_blocks;          // > 0: bin 6 runs on the dense global-accumulator kernel with this many resident blocks; 0: multi-pass LDS class
   const int64_t* pstart64;   // the wide form's starts
   const int64_t* work;       // [item_hi - item_lo] the rows' pairs in full (launch_row_work): what the multi-pass class sizes its passes by
+  const unsigned short* pf_limit;  // nullable [n_items_a]: mono_limit[cA[i]] (launch_mono_limit, launch_item_entropy) -- the k11 = 1 prefilter of the packed row kernels; null: off
 };
 
 hipError_t launch_column_counts(hipStream_t st, int n_cu, const int32_t* col_idx, int64_t nnz, int32_t n_cols, int32_t* counts);
@@ -206,7 +210,11 @@ hipError_t launch_pack_counts(hipStream_t st, int n_cu, const int32_t* col_idx, 
                               const int32_t* bad16, int32_t count_bits, int32_t* out, int32_t* bad);
 hipError_t launch_xlx_table(hipStream_t st, double* tab);
 hipError_t launch_xlx_hi_table(hipStream_t st, double* tab /*[2 * XLX_TABLE_HOST]: xlx_hi, then col_ent*/, const double* xlx_tab, long long n_users);
-hipError_t launch_item_entropy(hipStream_t st, const int32_t* counts, int32_t n, long long n_users, double* ent, double* xlx_n);
+// mono (nullable): the monotone-limit table; then lim[i] = mono[counts[i]] (0 beyond the table) is written too
+hipError_t launch_item_entropy(hipStream_t st, const int32_t* counts, int32_t n, long long n_users, double* ent, double* xlx_n, const unsigned short* mono = nullptr,
+                               unsigned short* lim = nullptr);
+// mono[cA], cA < XLX_TABLE_HOST: up to which cB the LLR of a k11 = 1 candidate is verified to fall strictly and stay positive (cco_rows.hip, mono_limit_kernel); after launch_xlx_hi_table
+hipError_t launch_mono_limit(hipStream_t st, unsigned short* mono, const double* xlx_tab, const double* hi_tab, long long n_users);
 // out16[i] = counts[i] (low 16 bits); bad[0] = number of counts that do not fit
 hipError_t launch_narrow_counts(hipStream_t st, int n_cu, const int32_t* counts, int64_t n, unsigned short* out16, int32_t* bad);  // n: 64-bit (world x shard rows)
 

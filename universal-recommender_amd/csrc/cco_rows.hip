@@ -559,7 +559,9 @@ __device__ __forceinline__ unsigned team_exclusive_scan(unsigned v, unsigned* s_
     *total = wave_read_lane(inc, WAVE - 1);
     return inc - v;
   }
-  const int wave = (threadIdx.x % T) / WAVE;
+  int tz = (int)threadIdx.x;
+  URCCO_OPAQUE(tz);  // (the wave's slot address is formed at each call: kept across a row loop that scans twice per row it was spilled to scratch)
+  const int wave = (tz % T) / WAVE;
   if (lane == WAVE - 1) s_wsum[wave] = inc;
   __syncthreads();
   unsigned base = 0, tot = 0;
@@ -589,6 +591,9 @@ constexpr int URCCO_SEL_AMB_BLOCK = 128;
 constexpr int URCCO_G_BLOCK = 2;
 constexpr int URCCO_SEL_M_BLOCK = 128;  // capacity of the ambiguous set of the teams of several waves (>= URCCO_SEL_AMB_BLOCK)
 constexpr int URCCO_G_CU = 2;
+// The k11 = 1 prefilter (see the compaction of cco_rows_kernel), per class: compiled out of a class in which it does not pay.
+__host__ __device__ constexpr bool prefilter_class(int T, int E) { return T >= WAVE && E >= 1024; }
+constexpr unsigned PF_BINS = 256;  // bins of the count histogram: cB = 0 .. 254, the last one is the clamp bin and stays empty (a cut never falls in it)
 // MP ("multi-pass", bin 6): rows no single LDS table can hold -- a hot item of a skewed catalogue pairs with tens of thousands
 // of distinct columns -- or whose counts overflow the packed field.  Such a row is accumulated in P = 2^s passes over its
 // cooccurrence pairs: pass q keeps the columns with (col mod P) == q, keyed by col div P (so the key narrows by s bits and the
@@ -608,7 +613,8 @@ constexpr int URCCO_G_CU = 2;
 template <bool NARROW> struct PStart { typedef int64_t type; };
 template <> struct PStart<true> { typedef unsigned type; };
 template <int T, int E, int U, bool MP = false, bool DBG = false, bool PK = false>
-__global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T == 256 && E == 4096 ? URCCO_OCC_BS : (T == 512 ? 4 : 1)))) void cco_rows_kernel(CcoArgs a, int bin) {
+__global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T == 256 && E == 4096 ? URCCO_OCC_BS : (T == 512 ? 4 : 1)))) void cco_rows_kernel(CcoArgs a, int bin_arg) {
+  const int bin = bin_arg & 255;  // (bit 8: the statistics count the candidates that were SCORED -- DBG_COUNT_SCORED --, not the distinct ones)
   // (the same verdict names the form of the expand tables -- CcoArgs::form: this instantiation reads the narrow ones, the plain one the wide ones)
   if ((a.b_packed != nullptr && (a.pk_known != 0 || *a.form == 0)) != PK) return;  // grid-uniform
   using PS = typename PStart<PK>::type;  // a start of a B' row: 32 bits in the narrow form
@@ -696,6 +702,13 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
   unsigned long long* amb_key = SHARE ? share : s_ambkey + team * SEL_M;
   unsigned* amb_col = SHARE ? reinterpret_cast<unsigned*>(share + SEL_M) : s_ambcol + team * SEL_M;
   unsigned long long* sel_thr = s_selthr + team * 2;
+  // The prefilter's count histogram (PF_BINS 16-bit counters) lives in LDS that is dead between the expand and the select phase: the select's own
+  // histogram where that is an array of its own (zeroed at the top of a row), in the one-wave class the ustart | uoff region (zeroed behind the
+  // expand loop: a wave's LDS accesses execute in order), and in the 256-thread small-block class the half of the ustart region the 32-bit starts
+  // of the packed form leave unused -- so that it, too, can be zeroed at the top of the row and costs no barrier.
+  constexpr bool PF = PK && !MP && prefilter_class(T, E);
+  static_assert(!PF || !SHARE || T == WAVE || (sizeof(PS) == 4 && T * 4 + PF_BINS * 2 <= T * 8), "the histogram sits behind the 32-bit starts");
+  unsigned* pfh = (SHARE && T != WAVE) ? reinterpret_cast<unsigned*>(share) + T : hist;
   const int list_start = a.bin_off[bin];
   const int list_n = a.bin_off[bin + 1] - list_start;
   const int total_teams = gridDim.x * TEAMS;
@@ -802,6 +815,11 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
     for (int q = 0; q < SPT / 2; ++q) *reinterpret_cast<uint2*>(&tab[2 * (tl + q * T)]) = make_uint2(0u, 0u);
     unsigned n_cand = 0u;  // one-wave teams: length of the candidate list (wave-uniform)
     if (T != WAVE && tl == 0) s_ncand = 0u;
+    if (PF && T != WAVE) {
+      int tz = tl;
+      URCCO_OPAQUE(tz);  // (the address is formed here, not kept -- spilled -- across the row loop)
+      if (tz < (int)PF_BINS / 2) pfh[tz] = 0u;
+    }
     team_sync<T>();
     // ---- 2. expand + accumulate
     for (int64_t c0 = cs; c0 < ce; c0 += T) {  // team-uniform
@@ -916,6 +934,16 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
     // Thread tl moves candidates tl, tl + T, ...: list word -> slot -> packed word, every read of the table and of the list ahead of the first write.
     unsigned D = T == WAVE ? n_cand : uni(s_ncand);  // (teams of several waves: the expand loop's last barrier published it)
     if (D > CAND_CAP) D = CAND_CAP;                   // (an abandoned pass / a broken invariant: flagged above)
+    // The k11 = 1 PREFILTER.  For a fixed row (cA, N) the LLR of a candidate with k11 = 1 depends on its cB alone, and pf_limit[i] = mono_limit[cA]
+    // (mono_limit_kernel) says up to which cB the fp64 values the score phase would compare are strictly decreasing and positive.  The compaction counts
+    // the k11 = 1 candidates by cB; c* = the smallest count with k (+ 1 for the self pair) such candidates at or below it.  A k11 = 1 candidate x with
+    // c* < cB_x <= the limit is then outranked by >= k candidates y (k11 = 1, cB_y <= c*) with LLR(y) > LLR(x) strictly -- it is in no top k, and if
+    // those y fail llr > 0 or minLLR so does x -- and is NOT MOVED: the score, select and ranking phases run over the D' survivors.  Row lengths, ids,
+    // order and LLR bits are what they were (config 4: 96 % of the candidates hold k11 = 1 and 72 % of all are thrown away by the top-k cut).
+    unsigned pf_lim = 0u;  // this row's limit: loaded where the cut is found, in flight across the histogram reads and the prefix sum
+    if (PF) {
+      if (T == WAVE) *reinterpret_cast<uint2*>(&pfh[2 * lane]) = make_uint2(0u, 0u);
+    }
     {
       unsigned cw[CPT], cv[CPT];
 #pragma unroll
@@ -928,7 +956,60 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
           cv[q] = tab[cw[q] & 0xffffu];
         }
       }
+      const unsigned pf_need = (unsigned)a.k + (a.exclude_self ? 1u : 0u);  // (the self pair may be one of the counted: it is dropped by the score phase)
+      const bool pf_try = PF && a.pf_limit != nullptr && D > pf_need;      // team-uniform
+      if (PF && pf_try) {
+#pragma unroll
+        for (int q = 0; q < CPT; ++q) {
+          const unsigned cbq = cw[q] >> 16;
+          if ((cv[q] & cmask) == 1u && cbq < PF_BINS - 1u) atomicAdd(&pfh[cbq >> 1], 1u << (16 * (cbq & 1u)));  // (counts < 2^16: D is bounded by the table size; cv = 0 beyond D)
+        }
+      }
       team_sync<T>();  // every read of the table and the list precedes every write below (one wave: its LDS accesses execute in order -- wave_sync costs nothing there)
+      bool pf_cut = false;  // team-uniform: every wave reads the same histogram
+      unsigned cstar = 0u, lim = 0u;
+      if (PF && pf_try) {
+        // every wave finds the cut for itself: lane l owns bins 4 l .. 4 l + 3 (ascending: the count of everything at or below a bin is a prefix sum)
+        pf_lim = (unsigned)a.pf_limit[i];
+        int lq = lane;
+        URCCO_OPAQUE(lq);  // (the histogram addresses are formed here, not kept -- spilled -- across the row loop)
+        const unsigned w01 = pfh[2 * lq], w23 = pfh[2 * lq + 1];
+        const unsigned h0 = w01 & 0xffffu, h1 = w01 >> 16, h2 = w23 & 0xffffu, h3 = w23 >> 16;
+        const unsigned v4 = h0 + h1 + h2 + h3;
+        const unsigned S = wave_inclusive_sum(v4);
+        const unsigned long long ge = __ballot(S >= pf_need);
+        const int L = ge != 0ull ? __ffsll((unsigned long long)ge) - 1 : 0;
+        const unsigned below = S - v4;
+        const unsigned d = below + h0 >= pf_need ? 0u : (below + h0 + h1 >= pf_need ? 1u : (below + h0 + h1 + h2 >= pf_need ? 2u : 3u));
+        cstar = wave_read_lane(4u * (unsigned)lq + d, L);
+        lim = uni(pf_lim);
+        pf_cut = ge != 0ull && cstar < lim;  // (no k such candidates below the clamp bin: no cut; a limit at or below c*: nothing to drop)
+      }
+      if (PF && pf_cut) {
+        unsigned cnt = 0u;
+#pragma unroll
+        for (int q = 0; q < CPT; ++q) {
+          const unsigned t = (unsigned)tl + (unsigned)q * T;
+          const unsigned cbq = cw[q] >> 16;
+          const bool drop = (cv[q] & cmask) == 1u && cbq > cstar && cbq <= lim;
+          if (t < D && !drop) ++cnt;
+          else cv[q] = 0u;  // (an occupied slot's word is never 0)
+        }
+        unsigned Dn;
+        unsigned pos = team_exclusive_scan<T>(cnt, s_wsum, &Dn);
+        Dn = uni(Dn);
+        unsigned long long* kkn = reinterpret_cast<unsigned long long*>(tab + ((Dn + 1u) & ~1u));
+#pragma unroll
+        for (int q = 0; q < CPT; ++q) {
+          if (cv[q] != 0u) {
+            tab[pos] = cv[q];
+            kkn[pos] = (unsigned long long)(cw[q] >> 16);
+            ++pos;
+          }
+        }
+        if (!(bin_arg & 256)) cand_acc += D - Dn;  // (statistics: the distinct candidates, unless the scored ones are asked for)
+        D = Dn;
+      } else {
       unsigned long long* kk0 = reinterpret_cast<unsigned long long*>(tab + ((D + 1u) & ~1u));
       // (a multi-pass row's pass may hold more candidates than leave room for their keys: it is abandoned below -- and must not write key slots
       // beyond the table; found by the simulator's bounds-checked build)
@@ -940,6 +1021,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
           tab[t] = cv[q];
           if (fits) kk0[t] = (unsigned long long)(cw[q] >> 16);
         }
+      }
       }
     }
     team_sync<T>();
@@ -1015,8 +1097,10 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
     if (SKIP_SHARED) {
       wave_and_or_u64(kand, kor);
       if (lane == 0) {  // published by the barriers inside the scan below
-        s_kbits[2 * (tl / WAVE)] = kand;
-        s_kbits[2 * (tl / WAVE) + 1] = kor;
+        int tw = tl;
+        URCCO_OPAQUE(tw);  // (the address is formed here: hoisted out of the row loop it was spilled to scratch in the 256-thread small-block class)
+        s_kbits[2 * (tw / WAVE)] = kand;
+        s_kbits[2 * (tw / WAVE) + 1] = kor;
       }
     }
     unsigned C;
@@ -1896,6 +1980,38 @@ __global__ __launch_bounds__(GB_THREADS) void cco_rows_global_kernel(CcoArgs a) 
   }
 }
 
+// mono_limit[cA], cA < XLX_TABLE: the largest m such that the LLR of a candidate with k11 = 1 in a row of cA interactions -- evaluated by the very function
+// the row kernels score with, for the N of the build -- is > 0 and strictly greater than its value at cB + 1 for every 1 <= cB < m, every operand of
+// both inside the tables; 0 when that fails at the start.  In exact arithmetic the G statistic falls with cB while cA cB < N; the table makes that a
+// verified fact about the fp64 values that are compared, rounding and the round-off clamp included.  One block per cA; built with the per-N tables.
+__global__ __launch_bounds__(256) void mono_limit_kernel(unsigned short* __restrict__ mono, const double* __restrict__ xlx_tab, const double* __restrict__ xlx_hi,
+                                                         const double* __restrict__ col_ent, long long n_users) {
+  __shared__ unsigned s_min;
+  const unsigned ca = blockIdx.x;
+  if (threadIdx.x == 0) s_min = (unsigned)XLX_TABLE;
+  __syncthreads();
+  const double xlx_n = x_log_x(n_users);
+  const double row_entropy = (long long)ca <= n_users ? entropy2((long long)ca, n_users - (long long)ca) : 0.0;  // as item_entropy_kernel makes it
+  for (unsigned cb = 1u + threadIdx.x; cb < (unsigned)XLX_TABLE; cb += 256u) {
+    bool ok = llr_operands_in_tables(1u, (long long)ca, cb, n_users, col_ent) && llr_operands_in_tables(1u, (long long)ca, cb + 1u, n_users, col_ent);
+    if (ok) {
+      const double f0 = llr_from_tables(row_entropy, xlx_n, 1u, ca, cb, xlx_tab, xlx_hi, col_ent);
+      const double f1 = llr_from_tables(row_entropy, xlx_n, 1u, ca, cb + 1u, xlx_tab, xlx_hi, col_ent);
+      ok = f0 > f1 && f0 > 0.0;
+    }
+    if (!ok) {
+      atomicMin(&s_min, cb);
+      break;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) mono[ca] = (unsigned short)(s_min <= 1u ? 0u : s_min);
+}
+hipError_t launch_mono_limit(hipStream_t st, unsigned short* mono, const double* xlx_tab, const double* hi_tab /*xlx_hi, then col_ent*/, long long n_users) {
+  hipLaunchKernelGGL(mono_limit_kernel, dim3(XLX_TABLE), dim3(256), 0, st, mono, xlx_tab, hi_tab, hi_tab + XLX_TABLE, n_users);
+  return hipGetLastError();
+}
+
 // resident blocks per CU of each LDS-accumulator kernel (registers / LDS decide), so that the persistent grids fill
 // the chip exactly once
 static int blocks_per_cu(int bin) {
@@ -1941,6 +2057,7 @@ hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, in
     return dim3((unsigned)blocks);
   };
   const bool dbgk = (args.debug & DBG_ROW_KERNELS) != 0;  // the ablation / test switches live in the DBG instantiations only
+  const int scored = (args.debug & DBG_COUNT_SCORED) ? 256 : 0;  // rides on the kernels' bin argument (grid-uniform; the production instantiations do not read CcoArgs::debug)
   // A B' with counts aboard: BOTH instantiations are enqueued -- whether the counts fit is a device-side fact, the one whose turn it is not returns at
   // once.  The DBG instantiations exist for the plain form only (the ablation switches price the count gather among other things).
   CcoArgs plain = args;
@@ -1950,7 +2067,7 @@ hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, in
   do {                                                                                                                           \
     if (dbgk) hipLaunchKernelGGL((cco_rows_kernel<TT, EE, UU, MPF, true, false>), GRID, dim3(BLK), 0, st, plain, BINARG);          \
     else {                                                                                                                       \
-      if (both || args.pk_known) hipLaunchKernelGGL((cco_rows_kernel<TT, EE, UU, MPF, false, true>), GRID, dim3(BLK), 0, st, args, BINARG); \
+      if (both || args.pk_known) hipLaunchKernelGGL((cco_rows_kernel<TT, EE, UU, MPF, false, true>), GRID, dim3(BLK), 0, st, args, BINARG | scored); \
       if (!args.pk_known) hipLaunchKernelGGL((cco_rows_kernel<TT, EE, UU, MPF, false, false>), GRID, dim3(BLK), 0, st, args, BINARG); \
     }                                                                                                                            \
   } while (0)

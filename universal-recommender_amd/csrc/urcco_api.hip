@@ -458,9 +458,11 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
     URC(s->xlx_tab.alloc(urcco::XLX_TABLE_HOST));
     HIPC(urcco::launch_xlx_table(s->stream, s->xlx_tab.p));
   }
-  if (!s->xlx_hi.p) URC(s->xlx_hi.alloc(2 * urcco::XLX_TABLE_HOST));  // xLogX(N - d), then columnEntropy(c)
+  if (!s->xlx_hi.p) URC(s->xlx_hi.alloc(2 * urcco::XLX_TABLE_HOST + urcco::XLX_TABLE_HOST / 4));  // xLogX(N - d), then columnEntropy(c), then the 16-bit monotone limits
+  unsigned short* mono = reinterpret_cast<unsigned short*>(s->xlx_hi.p + 2 * urcco::XLX_TABLE_HOST);
   if (s->xlx_hi_n != n_users) {
     HIPC(urcco::launch_xlx_hi_table(s->stream, s->xlx_hi.p, s->xlx_tab.p, n_users));
+    HIPC(urcco::launch_mono_limit(s->stream, mono, s->xlx_tab.p, s->xlx_hi.p, n_users));
     s->xlx_hi_n = n_users;
   }
   const int64_t n_tiles = ((int64_t)n + urcco::BIN_TILE - 1) / urcco::BIN_TILE;
@@ -474,14 +476,14 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
   unsigned *own_pstart = nullptr, *b_rp32;
   int32_t *own_plen, *bin_off, *bin_rows, *cnt16_bad;
   double *ent_a, *xlx_n;
-  unsigned short* cnt_b16;
+  unsigned short *cnt_b16, *pf_limit;
   unsigned long long* cand;
   L.add(&pstart64, (size_t)cap);
   if (!pre_pstart) L.add(&own_pstart, (size_t)cap);
   L.add(&own_plen, (size_t)cap).add(&wp, (size_t)cap + 1).add(&p_tile_sums, scan_tile_words(cap));
   L.add(&work, (size_t)n).add(&tile_counts, (size_t)(n_tiles + 1) * urcco::BIN_COLS_HOST);  // binning
   L.add(&bin_off, urcco::BIN_OFF_LEN).add(&bin_rows, (size_t)n);
-  L.add(&ent_a, (size_t)n_items_a).add(&cnt_b16, (size_t)n_cols_b).add(&cnt16_bad, 1);
+  L.add(&ent_a, (size_t)n_items_a).add(&cnt_b16, (size_t)n_cols_b).add(&cnt16_bad, 1).add(&pf_limit, (size_t)n_items_a);
   L.add(&cand, urcco::CAND_SLOTS).add(&xlx_n, 1);
   if (!stats_dev) L.add(&stats, URCCO_STATS_LEN);
   L.add(&b_rp32, (size_t)n_users + 1);
@@ -514,7 +516,7 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
   HIPC(urcco::launch_binning(s->stream, item_lo, n, work, counts_a, n_cols_b, count_bits, k, tile_counts, bin_off, bin_rows, stats));
   s->end();
   s->begin(URCCO_STAGE_ENTROPY);
-  HIPC(urcco::launch_item_entropy(s->stream, counts_a, n_items_a, n_users, ent_a, xlx_n));
+  HIPC(urcco::launch_item_entropy(s->stream, counts_a, n_items_a, n_users, ent_a, xlx_n, mono, pf_limit));
   HIPC(urcco::launch_narrow_counts(s->stream, s->n_cu, counts_b, n_cols_b, cnt_b16, cnt16_bad));
   s->end();
 
@@ -524,6 +526,7 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
   a.b_packed = packed; a.pk_known = narrow_known ? 1 : 0;
   a.b_col_mask = pk_known ? (key_bits >= 32 ? 0xffffffffu : (1u << key_bits) - 1u) : 0xffffffffu;
   a.cnt_a = counts_a; a.cnt_b = counts_b; a.ent_a = ent_a; a.cnt_b16 = cnt_b16; a.cnt16_bad = cnt16_bad; a.xlx_n = xlx_n; a.xlx_tab = s->xlx_tab.p; a.xlx_hi = s->xlx_hi.p; a.col_ent = s->xlx_hi.p + urcco::XLX_TABLE_HOST; a.debug = s->debug;
+  a.pf_limit = (s->debug & urcco::DBG_NO_PREFILTER) ? nullptr : pf_limit;
   a.n_users = n_users; a.n_cols_b = n_cols_b; a.item_lo = item_lo; a.exclude_self = exclude_self ? 1 : 0; a.k = k;
   a.has_min_llr = has_min_llr ? 1 : 0; a.min_llr = min_llr; a.count_bits = count_bits;
   a.col_bytes = n_cols_b <= (1 << 8) ? 1 : (n_cols_b <= (1 << 16) ? 2 : (n_cols_b <= (1 << 24) ? 3 : 4));
