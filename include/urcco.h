@@ -521,6 +521,40 @@ int urcco_dev_recommend_rules(urcco_session* s, int64_t n_queries, int32_t n_ite
                               int32_t num, int32_t flags, int32_t* out_count, int32_t* out_idx, double* out_score, int64_t* stats_dev,
                               const urcco_rec_rule* rules, int32_t n_rules);
 
+/* Hold-out evaluation of a table of recommendations: hits, average precision and NDCG at up to URCCO_EVAL_MAX_KS cut-offs per query, and their sums over
+ * the queries -- the arithmetic of the reference's MAP@k tool (the query key `eventNames` exists "for indicator predictiveness testing with the MAP@k
+ * tool"; URAlgorithm.scala:401), without leaving the device.  DESIGN.md decision D19.  For query q:
+ *   c = min(max(rec_count[q], 0), num), r_j = rec_idx[q * num + j] for j < c -- nothing at or behind c is read; the entries are distinct (the caller's
+ *       duty, urcco_dev_recommend's guarantee), a repeated entry counts each time
+ *   T = the truth row (sorted unique, e.g. a history term row), t = |T|; rel_j = 1 iff r_j is in T (binary search); H(j) = rel_0 + ... + rel_j
+ *   for each k of ks, m = min(k, c):
+ *     hits[q, k] = H(m - 1), 0 when m = 0
+ *     ap[q, k]   = (sum over j < m with rel_j = 1 of (double)H(j) / (double)(j + 1)) / (double)min(k, t)
+ *     dcg[q, k]  = sum over j < m with rel_j = 1 of discount[j];   ideal[n] = discount[0] + ... + discount[n - 1];   ndcg[q, k] = dcg / ideal[min(k, t)]
+ *   every sum starts at 0.0 and runs in ascending j: one rounding per division and per add, no contraction.  The caller supplies the position weights
+ *   (1 / log2(j + 2) for the usual NDCG); the library never evaluates a logarithm.
+ *   t = 0: the query is NOT evaluated -- its outputs are 0 / 0.0 and it is counted in out_sums_i[1].
+ * Sums, kappa = the index of k in ks:
+ *   out_sums_i = [queries evaluated, queries not evaluated, sum_q hits[q, kappa] per kappa, #{q: hits[q, kappa] > 0} per kappa]
+ *   out_sums_f = [tree(ap[., kappa]) per kappa, tree(ndcg[., kappa]) per kappa]  (the second half zeros without discount)
+ *   tree(x) over all n_queries positions (not-evaluated ones hold +0.0): pad with +0.0 to the next power of two, then x[i] = x[2i] + x[2i + 1] until one
+ *   value is left -- in numpy `while x.size > 1: x = x[0::2] + x[1::2]`.  Every number is reproducible bit for bit; no float atomics are used.
+ * urcco_dev_tree_sum: out[c] = tree(x[., c]) for a row-major x [n, n_cols] -- the sums of per-query values gathered over several calls do not depend
+ *   on how the queries were split into calls.  n = 0 gives 0.0.
+ * Both enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG (rank_metrics): num outside
+ * 1..URCCO_REC_MAX_NUM, n_ks outside 1..URCCO_EVAL_MAX_KS, ks not strictly ascending or a k outside 1..num, n_queries * n_ks >= 2^31, a NULL array the call
+ * needs, discount / out_ndcg or out_sums_i / out_sums_f not both NULL or both non-NULL; (tree_sum): n < 0, n_cols outside 1..1024, n * n_cols >= 2^31, a NULL.
+ * n_queries == 0 is legal and writes zero sums.  ABI: additions within ABI 305 -- the presence of the symbols is the feature test. */
+#define URCCO_EVAL_MAX_KS 8
+int urcco_dev_rank_metrics(urcco_session* s, int64_t n_queries, int32_t num,
+                           const int32_t* rec_count, const int32_t* rec_idx,             /* device, as urcco_dev_recommend leaves them: rows strided by num */
+                           const int64_t* truth_row_ptr, const int32_t* truth_col_idx,   /* device CSR, n_queries rows, sorted unique */
+                           const int32_t* ks_host, int32_t n_ks,                         /* host: strictly ascending, each in 1..num */
+                           const double* discount,                                       /* device [num], nullable */
+                           int32_t* out_hits, double* out_ap, double* out_ndcg,          /* device [n_queries * n_ks], row-major by query; out_ndcg NULL iff discount NULL */
+                           int64_t* out_sums_i, double* out_sums_f);                     /* device, nullable pair: [2 + 2 * n_ks], [2 * n_ks] */
+int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double* x /* device [n * n_cols] */, double* out /* device [n_cols] */);
+
 /* Device-resident user history: the event-store half of a batch of queries (getBiasedRecentUserActions, URAlgorithm.scala:795-839; getExcludedItems,
  * :741-767), from event streams that already sit in HBM -- (user id, column id, time) per event and event type, dense ids as urcco_dev_dictionary_lookup
  * yields them.  DESIGN.md decision D17.  For a query user u and event type e with cap max_items (the indicator's maxItemsPerUser):

@@ -17,7 +17,12 @@ dictionary lookup per item, np.unique) on this box.
 (HIP events, the read of the bound totals included) of urcco_dev_item_bounds + _rows over the model's indicator matrices, next to the wall time of the
 host planning recommend.batch_predict does for the same queries on this box -- the one-off copy of every indicator matrix to the host, printed on
 its own, then per query and event type a slice, an astype and np.unique, and the CSR of the rows.  --no-torch skips the torch comparison.
-usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--rules] [--device-history] [--device-items] [--no-torch]"""
+--evaluate: hold-out evaluation of the model (decision D19) for the --queries users.  The training history is the users' rows of the event matrices as
+streams on the device; the held-out events are one more draw of the primary event by synth.py (same popularity, user ids beyond the trained ones, taken
+as the first --queries users').  Printed: the HIP-event time of urcco_dev_rank_metrics alone (ks = 1, 5, 10, 20, the sums included) over a table and truth
+rows built beforehand; the wall time of URAlgorithm.evaluate end to end (user_recommendations + truth rows + rank_metrics per chunk, the tree sums, one
+report); and, as a comparison point only, the HIP-event time of a torch.isin + cumsum restatement of the per-user hits on the same GPU.
+usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--rules] [--device-history] [--device-items] [--evaluate] [--no-torch]"""
 import argparse
 import os
 import sys
@@ -39,6 +44,7 @@ ap.add_argument("--num", type=int, default=20)
 ap.add_argument("--rules", action="store_true", help="also time the call under an ANY and a NONE rule")
 ap.add_argument("--device-history", action="store_true", help="also time history_bounds + history_rows against the host planning loop")
 ap.add_argument("--device-items", action="store_true", help="also time item_bounds + item_rows against the host planning loop of item queries")
+ap.add_argument("--evaluate", action="store_true", help="also time rank_metrics, evaluate end to end and a torch restatement of the hits")
 ap.add_argument("--no-torch", action="store_true", help="skip the torch comparison")
 args = ap.parse_args()
 
@@ -184,6 +190,57 @@ if args.device_items:
     torch.cuda.synchronize()
     loop_ms = (time.perf_counter() - t0) * 1e3
     print(f"host planning of the same item queries (recommend.py, one thread): matrices to the host once {copy_ms:.0f} ms wall, per-query loop {loop_ms:.0f} ms wall")
+
+if args.evaluate:
+    import dataclasses
+    import time
+
+    from universal_recommender_amd.evaluate import TRUTH_CAP, log2_discount
+    from universal_recommender_amd.history import DeviceHistory
+    from universal_recommender_amd.ur_algorithm import URAlgorithm, URAlgorithmParams
+    KS = (1, 5, 10, 20)
+    engine = {"algorithms": [{"name": "ur", "params": {"appName": "bench", "indexName": "bench", "typeName": "items", "num": num,
+                                                       "indicators": [{"name": n} for n in names]}}]}
+    algo = URAlgorithm(URAlgorithmParams.from_engine_json(engine), device=0, library=sess.lib)
+
+    def stream(rp, ci):          # the first nq rows of a CSR as (user, item) events
+        users = torch.repeat_interleave(torch.arange(nq, device=dev, dtype=torch.int32), rp[1: nq + 1] - rp[:nq])
+        return users, ci[: int(rp[nq].item())].contiguous(), None
+
+    train = DeviceHistory.from_streams(sess, model, {n: stream(m.row_ptr, m.col_idx) for n, m in zip(names, mats)}, n_users=nq)
+    _, _, h_rp, h_ci = synth.generate_device(dataclasses.replace(cfg, events=cfg.events[:1]), dev, user_lo=cfg.n_users, user_hi=cfg.n_users + nq)[0]
+    test = DeviceHistory.from_streams(sess, model, {names[0]: stream(h_rp, h_ci)}, n_users=nq)
+    q_users = torch.arange(nq, dtype=torch.int32, device=dev)
+    u_count, u_idx, _ = algo.user_recommendations(model, train, q_users, num)
+    ts = test.types[names[0]]
+    (truth,), _, _ = sess.history_rows(q_users, nq, [(ts.n_cols, TRUTH_CAP, False, ts.idx_row_ptr, ts.idx_pos, ts.items, ts.times, None)], n_items)
+    disc = torch.from_numpy(log2_discount(num)).to(dev)
+    (e_hits, _, _, e_si, _), ms_rank = timed(lambda: sess.rank_metrics(u_count, u_idx, truth[0], truth[1], KS, disc), args.reps)
+    si = e_si.cpu().tolist()
+    print(f"urcco_dev_rank_metrics ({nq} users, num = {num}, ks = {list(KS)}, {int(truth[0][-1].item())} truth entries, sums included): {min(ms_rank):.3f} ms best, "
+          f"{sorted(ms_rank)[len(ms_rank) // 2]:.3f} ms median of {args.reps} ({[round(x, 3) for x in ms_rank]})")
+    print(f"  evaluated {si[0]}, not evaluated {si[1]}, hits per k {si[2:2 + len(KS)]}, users with a hit per k {si[2 + len(KS):]}")
+    algo.evaluate(model, train, test, ks=KS, num=num)                       # warm
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    report = algo.evaluate(model, train, test, ks=KS, num=num)
+    torch.cuda.synchronize()
+    print(f"URAlgorithm.evaluate end to end, second call ({nq} users, chunk 65536): {(time.perf_counter() - t0) * 1e3:.1f} ms wall")
+    print(f"  precision {[round(x, 5) for x in report['precision']]}, hit rate {[round(x, 5) for x in report['hit_rate']]}, "
+          f"MAP {[round(x, 5) for x in report['map']]}, NDCG {[round(x, 5) for x in report['ndcg']]}")
+    ks_t = torch.tensor(KS, device=dev) - 1
+
+    def torch_hits():            # membership of (row, item) keys, then a running count along the row
+        live = torch.arange(num, device=dev)[None, :] < u_count[:, None]
+        rec_key = torch.arange(nq, device=dev)[:, None] * n_items + u_idx.to(torch.int64)
+        rows = torch.repeat_interleave(torch.arange(nq, device=dev), truth[0][1:] - truth[0][:-1])
+        truth_key = rows * n_items + truth[1][: rows.numel()].to(torch.int64)
+        rel = torch.isin(rec_key, truth_key) & live
+        return rel.cumsum(1)[:, ks_t].to(torch.int32)
+
+    t_hits, ms_isin = timed(torch_hits, args.reps)
+    print(f"torch.isin + cumsum restatement of the per-user hits alone (comparison point): {min(ms_isin):.3f} ms best ({[round(x, 3) for x in ms_isin]}); "
+          f"hits equal: {bool(torch.equal(t_hits, e_hits))}")
 
 if args.no_torch:
     sess.close()

@@ -32,6 +32,8 @@ REC_NO_BACKFILL = 1
 REC_STATS_LEN = 8
 REC_MAX_RULES = 16     # urcco_dev_recommend_rules (URCCO_REC_MAX_RULES, URCCO_RULE_*)
 RULE_ANY, RULE_NONE, RULE_RANGE = 0, 1, 2
+EVAL_MAX_KS = 8        # urcco_dev_rank_metrics (URCCO_EVAL_MAX_KS): cut-offs per call
+EVAL_TREE_BLOCK = 256  # positions one block of the tree sum reduces (csrc/cco_eval.h): beyond it a further pass runs over the partials
 HIST_STATS_LEN = 8     # urcco_dev_history_rows (URCCO_HIST_STATS_LEN): pairs per class, selects, exclusion rows per class, overflows
 REC_LDS_LIMIT = 3072   # work bound w(q) up to which a query runs in the LDS class (csrc/cco_kernels.h)
 EXCH_SIZES = 4   # int64 words of a shard's record (include/urcco.h URCCO_EXCH_SIZES)
@@ -188,6 +190,8 @@ SYMBOLS = {
     "urcco_dev_recommend": (C.c_int, [_p, C.c_int64, C.c_int32, C.POINTER(RecClause), C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p]),
     "urcco_dev_recommend_rules": (C.c_int, [_p, C.c_int64, C.c_int32, C.POINTER(RecClause), C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p,
                                             C.POINTER(RecRule), C.c_int32]),
+    "urcco_dev_rank_metrics": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p, _p, C.POINTER(C.c_int32), C.c_int32, _p, _p, _p, _p, _p, _p]),
+    "urcco_dev_tree_sum": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p]),
     "urcco_dev_history_index": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_bounds": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.POINTER(HistEvent), C.c_int32, _p, _p, _p]),
     "urcco_dev_history_rows": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.POINTER(HistEvent), C.c_int32, _p, _p, C.c_int32, _p, _p, C.c_int64, _p]),

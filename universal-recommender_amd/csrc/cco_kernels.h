@@ -289,6 +289,16 @@ hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t
                             unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit = REC_LDS_LIMIT, const RecRule* rules = nullptr,
                             int32_t n_rules = 0);
 
+// ---- hold-out evaluation (cco_eval.h, compiled into cco_misc.hip behind cco_recommend.h; decision D19) ----------------------
+constexpr int EVAL_MAX_KS = 8;        // == URCCO_EVAL_MAX_KS of include/urcco.h
+void tree_sum_scratch(int64_t n, int32_t n_cols, size_t* pa, size_t* pb);
+// pa, pb: scratch doubles as tree_sum_scratch sizes them
+hipError_t launch_tree_sum(hipStream_t st, const double* x, int64_t n, int32_t n_cols, double* out, double* pa, double* pb);
+// ks: host; ideal [num + 1] (only with discount), pa / pb (only with the sums; sized for n_queries x n_ks): scratch
+hipError_t launch_rank_metrics(hipStream_t st, int n_cu, int64_t n_queries, int32_t num, const int32_t* rec_count, const int32_t* rec_idx, const int64_t* truth_row_ptr,
+                               const int32_t* truth_col_idx, const int32_t* ks, int32_t n_ks, const double* discount, double* ideal, int32_t* out_hits, double* out_ap,
+                               double* out_ndcg, int64_t* out_sums_i, double* out_sums_f, double* pa, double* pb);
+
 // ---- device-resident user history (cco_history.h, compiled into ingest_kernels.hip; decision D17) ----------------------
 constexpr int HIST_STATS_LEN = 8;   // == URCCO_HIST_STATS_LEN of include/urcco.h
 enum { HIST_STAT_WAVE = 0, HIST_STAT_BLOCK = 1, HIST_STAT_GLOBAL = 2, HIST_STAT_SELECT = 3, HIST_STAT_EXCL_WAVE = 4, HIST_STAT_EXCL_BLOCK = 5, HIST_STAT_OVERFLOW = 6 };

@@ -904,6 +904,40 @@ int urcco_dev_recommend_rules(urcco_session* s, int64_t n_queries, int32_t n_ite
                         rules, n_rules);
 }
 
+int urcco_dev_rank_metrics(urcco_session* s, int64_t n_queries, int32_t num, const int32_t* rec_count, const int32_t* rec_idx, const int64_t* truth_row_ptr,
+                           const int32_t* truth_col_idx, const int32_t* ks_host, int32_t n_ks, const double* discount, int32_t* out_hits, double* out_ap, double* out_ndcg,
+                           int64_t* out_sums_i, double* out_sums_f) {
+  if (!s || n_queries < 0) return fail(URCCO_BAD_ARG, "urcco_dev_rank_metrics: bad argument");
+  if (num < 1 || num > URCCO_REC_MAX_NUM) return fail(URCCO_BAD_ARG, "urcco_dev_rank_metrics: num must lie in 1..%d, got %d", URCCO_REC_MAX_NUM, num);
+  if (n_ks < 1 || n_ks > URCCO_EVAL_MAX_KS || !ks_host) return fail(URCCO_BAD_ARG, "urcco_dev_rank_metrics: between 1 and %d cut-offs, got %d", URCCO_EVAL_MAX_KS, n_ks);
+  for (int x = 0; x < n_ks; ++x)
+    if (ks_host[x] < 1 || ks_host[x] > num || (x > 0 && ks_host[x] <= ks_host[x - 1]))
+      return fail(URCCO_BAD_ARG, "urcco_dev_rank_metrics: the cut-offs must ascend strictly inside 1..num");
+  if (n_queries * (int64_t)n_ks > 0x7fffffffll) return fail(URCCO_BAD_ARG, "urcco_dev_rank_metrics: too many queries");
+  if ((discount == nullptr) != (out_ndcg == nullptr)) return fail(URCCO_BAD_ARG, "urcco_dev_rank_metrics: discount and out_ndcg go together");
+  if ((out_sums_i == nullptr) != (out_sums_f == nullptr)) return fail(URCCO_BAD_ARG, "urcco_dev_rank_metrics: the sums need both of their arrays");
+  if (n_queries > 0 && (!rec_count || !rec_idx || !truth_row_ptr || !truth_col_idx || !out_hits || !out_ap))
+    return fail(URCCO_BAD_ARG, "urcco_dev_rank_metrics: an array is missing");
+  double *ideal, *pa, *pb;
+  size_t na = 0, nb = 0;
+  if (out_sums_f) urcco::tree_sum_scratch(n_queries, n_ks, &na, &nb);
+  URC(ArenaLayout(s).add(&ideal, (size_t)num + 1).add(&pa, na).add(&pb, nb).commit());
+  HIPC(urcco::launch_rank_metrics(s->stream, s->n_cu, n_queries, num, rec_count, rec_idx, truth_row_ptr, truth_col_idx, ks_host, n_ks, discount, ideal, out_hits, out_ap,
+                                  out_ndcg, out_sums_i, out_sums_f, pa, pb));
+  return URCCO_OK;
+}
+
+int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double* x, double* out) {
+  if (!s || n < 0 || n_cols < 1 || n_cols > 1024 || !out || (n > 0 && !x) || n * (int64_t)n_cols > 0x7fffffffll)
+    return fail(URCCO_BAD_ARG, "urcco_dev_tree_sum: bad argument");
+  double *pa, *pb;
+  size_t na, nb;
+  urcco::tree_sum_scratch(n, n_cols, &na, &nb);
+  URC(ArenaLayout(s).add(&pa, na).add(&pb, nb).commit());
+  HIPC(urcco::launch_tree_sum(s->stream, x, n, n_cols, out, pa, pb));
+  return URCCO_OK;
+}
+
 int urcco_dev_llr(urcco_session* s, int64_t n, const int64_t* with_a, const int64_t* with_b, const int64_t* with_ab, const int64_t* n_users,
                   double* out) {
   if (!s || n < 0) return fail(URCCO_BAD_ARG, "urcco_dev_llr: bad argument");

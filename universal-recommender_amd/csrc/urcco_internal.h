@@ -21,6 +21,7 @@ static_assert(urcco::REC_MAX_CLAUSES == URCCO_REC_MAX_CLAUSES && urcco::REC_MAX_
                   urcco::REC_RULE_NONE == URCCO_RULE_NONE && urcco::REC_RULE_RANGE == URCCO_RULE_RANGE,
               "include/urcco.h and cco_kernels.h agree on the recommendation call");
 static_assert(urcco::HIST_STATS_LEN == URCCO_HIST_STATS_LEN, "include/urcco.h and cco_kernels.h agree on the history calls");
+static_assert(urcco::EVAL_MAX_KS == URCCO_EVAL_MAX_KS, "include/urcco.h and cco_kernels.h agree on the evaluation call");
 
 struct urcco_session;
 namespace urcco_detail {

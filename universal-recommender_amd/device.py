@@ -253,6 +253,38 @@ class DeviceSession:
         n = max(n_queries, 0)
         return o_count[:n], o_idx[: n * max(num, 0)].view(n, -1) if n and num > 0 else o_idx[:0], o_score[: n * max(num, 0)].view(n, -1) if n and num > 0 else o_score[:0], st
 
+    def rank_metrics(self, count: torch.Tensor, idx: torch.Tensor, truth_row_ptr: torch.Tensor, truth_col_idx: torch.Tensor, ks, discount: Optional[torch.Tensor] = None,
+                     sums: bool = True, out=None):
+        """urcco_dev_rank_metrics (decision D19): hits, average precision and NDCG at the cut-offs `ks` of the recommendation table (count int32 [n], idx
+        int32 [n, num], as recommend leaves them) against the truth rows (row_ptr int64 [n + 1], col_idx int32 sorted unique per row, e.g. a history term
+        row).  ks: strictly ascending, each in 1..num.  discount: float64 [num] position weights of the DCG (None: no NDCG).
+        Returns (hits int32 [n, n_ks], ap float64 [n, n_ks], ndcg float64 [n, n_ks] | None, sums_i int64 [2 + 2 n_ks] | None, sums_f float64 [2 n_ks] | None):
+        sums_i = [evaluated, not evaluated, sum of hits per k, queries with a hit per k], sums_f = [tree sum of ap per k, of ndcg per k].
+        out: (hits, ap, ndcg | None) contiguous tensors to write into instead of fresh ones.  Enqueues, does not synchronise."""
+        n = int(count.numel())
+        num = int(idx.shape[1]) if idx.dim() == 2 else (int(idx.numel()) // n if n else 1)
+        ks = [int(k) for k in ks]
+        ks_arr = (C.c_int32 * max(len(ks), 1))(*ks)
+        if out is None:
+            out = (self.empty(max(n * len(ks), 1), torch.int32), self.empty(max(n * len(ks), 1), torch.float64),
+                   self.empty(max(n * len(ks), 1), torch.float64) if discount is not None else None)
+        hits, ap, ndcg = (t.view(-1) if t is not None else None for t in out)
+        s_i = self.empty(2 + 2 * len(ks), torch.int64) if sums else None
+        s_f = self.empty(max(2 * len(ks), 1), torch.float64) if sums else None
+        self._check(self.lib.urcco_dev_rank_metrics(self.handle, n, num, _ptr(count), _ptr(idx), _ptr(truth_row_ptr), _ptr(truth_col_idx), ks_arr, len(ks), _ptr(discount),
+                                                   _ptr(hits), _ptr(ap), _ptr(ndcg), _ptr(s_i), _ptr(s_f)))
+        shape = (n, len(ks))
+        return (hits[: n * len(ks)].view(shape), ap[: n * len(ks)].view(shape), ndcg[: n * len(ks)].view(shape) if ndcg is not None else None, s_i,
+                s_f[: 2 * len(ks)] if s_f is not None else None)
+
+    def tree_sum(self, x: torch.Tensor) -> torch.Tensor:
+        """urcco_dev_tree_sum: the pairwise sums of decision D19 over the rows of a contiguous float64 [n, n_cols] tensor, one per column: what
+        `while x.size > 1: x = x[0::2] + x[1::2]` leaves of each column padded with +0.0 to a power of two.  Enqueues, does not synchronise."""
+        n, n_cols = int(x.shape[0]), int(x.shape[1])
+        out = self.empty(n_cols, torch.float64)
+        self._check(self.lib.urcco_dev_tree_sum(self.handle, n, n_cols, _ptr(x), _ptr(out)))
+        return out
+
     def history_index(self, users: torch.Tensor, n_users: int):
         """urcco_dev_history_index: the stream positions of every user's events.  users: int32 dense user id per event (< 0: nobody's).
         Returns (row_ptr int64 [n_users + 1], pos int32 [n_events]); the order inside a user's segment is unspecified.  Does not synchronise."""

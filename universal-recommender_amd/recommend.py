@@ -531,3 +531,92 @@ def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = Non
         idx[lo:lo + m] = torch.where(live, i, idx[lo:lo + m])
         score[lo:lo + m] = torch.where(live, s, score[lo:lo + m])
     return count, idx, score
+
+
+def user_recommendations(algo, model: DeviceModel, history, users=None, num: Optional[int] = None, event_names: Optional[Sequence[str]] = None,
+                         user_bias: Optional[float] = None, chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None):
+    """The per-user table, the user-side twin of similar_items: row n is what batch_predict answers to {"user": users[n]} (with "eventNames", "num" and
+    "userBias" where given) over the same DeviceHistory -- the same items in the same order with the same scores -- as three device tensors (count
+    int32 [n], idx int32 [n, num], score float64 [n, num]); entries behind count[n] are -1 / 0.0.  No Python work per user: the queries go `chunk`
+    at a time through DeviceSession.history_rows (decision D17) and recommend.
+    history: a history.DeviceHistory.  users: None = every user id of the history, a device int32 tensor of dense user ids, or a sequence of users
+    resolved with DeviceHistory.user_index; a user the history does not know (an id < 0 or >= n_users) is served as batch_predict serves one: the
+    backfill alone, or nothing when the history is a filter.  num, user_bias: default to the algorithm's num (20) and userBias (1.0).  event_names:
+    the query's `eventNames`, default the model's event types.  user_bias > 0: one should-clause per event type over the user's recent items, boost
+    = the bias; user_bias < 0: the rows are ANY rules instead (a model built with item properties, {} will do) -- every query carries them, so an
+    unknown user or an event without history matches nothing, as in batch_predict.  The blacklist events' exclusions, backfill, recsModel, item_mask
+    and the available / expire date rule around now_ms are those of batch_predict."""
+    from .history import DeviceHistory
+    if not isinstance(history, DeviceHistory):
+        raise ValueError("user_recommendations needs a history.DeviceHistory (the event streams resident on the device)")
+    dh = history
+    ap = algo.ap
+    sess, dev = model.sess, model.sess.device
+    model_events = list(algo.modelEventNames)
+    primary = model_events[0]
+    for ev in model_events:
+        if ev not in model.by_name:
+            raise ValueError(f"the model holds no indicator matrix for event {ev!r}")
+    num = int(num if num is not None else ap.num if ap.num is not None else 20)
+    if num < 1 or num > _lib.REC_MAX_NUM:
+        raise ValueError(f"num must lie in 1..{_lib.REC_MAX_NUM}, got {num}")
+    if chunk < 1:
+        raise ValueError("user_recommendations needs chunk >= 1")
+    bias = float(user_bias if user_bias is not None else ap.userBias if ap.userBias is not None else 1.0)
+    served = model.properties is not None
+    if bias < 0 and not served:
+        raise NotImplementedError("negative userBias (user history as a filter) needs a model built with item properties ({} will do)")
+    max_items = {i.name: (i.maxItemsPerUser if i.maxItemsPerUser is not None else 500) for i in ap.indicators} if ap.indicators else {e: 100 for e in model_events}
+    blacklist_events = ap.blacklistEvents if ap.blacklistEvents is not None else [primary]
+    q_events = list(event_names or model_events)
+    hist_events = [ev for ev in q_events if ev in dh.types and (ev in model.by_name or ev in blacklist_events)]
+    if len(hist_events) > _lib.REC_MAX_CLAUSES:
+        raise ValueError(f"a batch names {len(hist_events)} event types, more than the {_lib.REC_MAX_CLAUSES} one history call serves")
+    flags = _lib.REC_NO_BACKFILL if algo.recsModel == "collabFiltering" else 0
+    mask_t = _mask_tensor(model, item_mask)
+    if users is None:
+        q_all = torch.arange(dh.n_users, dtype=torch.int32, device=dev)
+    elif torch.is_tensor(users):
+        if users.dtype != torch.int32 or users.dim() != 1:
+            raise ValueError("users as a tensor: dense user ids, int32, one dimension")
+        q_all = users.to(dev)
+    else:
+        q_all = torch.tensor([dh.user_index(u) for u in users], dtype=torch.int32).to(dev)
+    n = int(q_all.numel())
+    dates = []
+    if served and ap.availableDateName is not None and ap.expireDateName is not None and ap.availableDateName in model.dates and ap.expireDateName in model.dates:
+        import time
+        now = int(now_ms) if now_ms is not None else int(time.time() * 1000)
+        dates = [(model.dates[ap.availableDateName], NO_VALUE, now + 1), (model.dates[ap.expireDateName], now + 1, OPEN_HI)]
+    specs = [(dh.types[ev].n_cols, max_items.get(ev, 100), ev in blacklist_events, dh.types[ev].idx_row_ptr, dh.types[ev].idx_pos, dh.types[ev].items,
+              dh.types[ev].times, dh.types[ev].col_map) for ev in hist_events]
+    rule_events = list(dict.fromkeys(ev for ev in q_events if ev in model.by_name)) if bias < 0 else []
+    if len(rule_events) + len(dates) > _lib.REC_MAX_RULES:
+        raise ValueError(f"a batch needs {len(rule_events) + len(dates)} rules, more than the {_lib.REC_MAX_RULES} one call serves")
+    count = torch.zeros(n, dtype=torch.int32, device=dev)
+    idx = torch.full((n, num), -1, dtype=torch.int32, device=dev)
+    score = torch.zeros((n, num), dtype=torch.float64, device=dev)
+    for lo in range(0, n, chunk):
+        q = q_all[lo:lo + chunk].contiguous()
+        m = int(q.numel())
+        none = (torch.zeros(m + 1, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int32, device=dev))
+        hist_rows: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
+        excl = none
+        if specs:
+            rows, excl, _ = sess.history_rows(q, dh.n_users, specs, model.n_items)
+            hist_rows = {ev: r for ev, r in zip(hist_events, rows) if ev in model.by_name}
+        rules = None
+        if served:
+            rules = [(_lib.RULE_RANGE, value, torch.full((m,), lo_ms, dtype=torch.int64, device=dev), torch.full((m,), hi_ms, dtype=torch.int64, device=dev))
+                     for value, lo_ms, hi_ms in dates]
+        clauses = []
+        if bias < 0:                                                                            # a filter per event, no should-clause; an event without history matches nothing
+            rules = rules + [(_lib.RULE_ANY, model.by_name[ev].n_cols, model.by_name[ev].row_ptr, model.by_name[ev].col_idx) + hist_rows.get(ev, none) for ev in rule_events]
+        else:                                                                                   # the clauses in the model's order, as batch_predict lays them out
+            clauses = [(c.n_cols, _boost(bias), c.col_ptr, c.row_idx) + hist_rows[c.name] for c in model.correlators if c.name in hist_rows]
+        c, i, s, _ = sess.recommend(m, model.n_items, clauses, num, excl, mask_t, model.fill_order, flags, stats=False, rules=rules)
+        live = torch.arange(num, device=dev)[None, :] < c[:, None]
+        count[lo:lo + m] = c
+        idx[lo:lo + m] = torch.where(live, i, idx[lo:lo + m])
+        score[lo:lo + m] = torch.where(live, s, score[lo:lo + m])
+    return count, idx, score

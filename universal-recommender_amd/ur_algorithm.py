@@ -280,6 +280,20 @@ class URAlgorithm:
         from .recommend import similar_items
         return similar_items(self, model, items, num, item_bias, return_self, chunk, item_mask, now_ms)
 
+    def user_recommendations(self, model, history, users=None, num: Optional[int] = None, event_names=None, user_bias: Optional[float] = None,
+                             chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None):
+        """The per-user table of `users` (None: every user id of the history.DeviceHistory) as device tensors (count, idx, score): row n is what
+        batch_predict answers to {"user": users[n]} over the same history; see recommend.user_recommendations."""
+        from .recommend import user_recommendations
+        return user_recommendations(self, model, history, users, num, event_names, user_bias, chunk, item_mask, now_ms)
+
+    def evaluate(self, model, train, test, ks=(1, 5, 10, 20), num: Optional[int] = None, event_names=None, truth_event: Optional[str] = None,
+                 chunk: int = 65536, user_bias: Optional[float] = None, item_mask=None, now_ms: Optional[int] = None):
+        """Hold-out evaluation on the device (decision D19): precision, hit rate, MAP@k and NDCG@k of the recommendations over the `train` history
+        against the users' `truth_event` items in the `test` history; a list of event mixes gives a list of reports.  See evaluate.evaluate."""
+        from .evaluate import evaluate
+        return evaluate(self, model, train, test, ks, num, event_names, truth_event, chunk, user_bias, item_mask, now_ms)
+
     def predict(self, model, query: dict, history, item_mask=None, now_ms: Optional[int] = None) -> dict:
         return self.batch_predict(model, [query], history, item_mask, now_ms)[0]
 
