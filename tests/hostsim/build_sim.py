@@ -3,6 +3,7 @@
 The result (tests/hostsim/_build/liburcco_hostsim.so) exports the same C ABI as the product library but is
 never loaded by the package: only CPU tests that exercise kernel/host LOGIC load it explicitly.
 """
+import glob
 import os
 import subprocess
 import sys
@@ -13,8 +14,7 @@ CSRC = os.path.join(ROOT, "universal-recommender_amd", "csrc")
 OUT = os.path.join(HERE, "_build", "liburcco_hostsim.so")
 SOURCES = [os.path.join(CSRC, f) for f in ("cco_counts.hip", "cco_rowscan.hip", "cco_transpose.hip", "cco_expand.hip", "cco_rows.hip", "cco_misc.hip")] + [os.path.join(CSRC, "ingest_kernels.hip"), os.path.join(CSRC, "urcco_api.hip"), os.path.join(CSRC, "urcco_context.hip"), os.path.join(CSRC, "urcco_hash.hip"),
            os.path.join(HERE, "hipsim.cpp")]
-DEPS = SOURCES + [os.path.join(CSRC, "cco_kernels.h"), os.path.join(CSRC, "cco_common.h"), os.path.join(CSRC, "cco_device.h"), os.path.join(CSRC, "cco_recommend.h"), os.path.join(CSRC, "cco_history.h"), os.path.join(CSRC, "urcco_internal.h"),
-                  os.path.join(ROOT, "include", "urcco.h"), os.path.join(HERE, "include", "hip", "hip_runtime.h")]
+DEPS = SOURCES + glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(ROOT, "include", "urcco.h"), os.path.join(HERE, "include", "hip", "hip_runtime.h")]
 
 
 def build(force: bool = False) -> str:

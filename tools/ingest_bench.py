@@ -25,7 +25,7 @@ if sim:
     sess = DeviceSession(dev, _lib.load(build_sim.build()))
     sync = lambda: None
 else:
-    sess = DeviceSession(dev, _lib.load(_lib.DEFAULT_PATH))
+    sess = DeviceSession(dev, _lib.load(os.environ.get("URCCO_LIB", _lib.DEFAULT_PATH)))   # URCCO_LIB: A/B runs of two builds on one box
     sync = torch.cuda.synchronize
 
 cfg = synth.config3(scale)

@@ -1,5 +1,5 @@
 // Device-resident user history (decision D17 of DESIGN.md 7a; include/urcco.h urcco_dev_history_*): the event-store half of a
-// batch of queries.  Compiled into ingest_kernels.hip (it uses that file's grid helper and row compaction).
+// batch of queries.  Compiled into ingest_kernels.hip behind cco_sorted_rows.h (it uses that header's tails and host helpers, and the file's grid helper).
 //
 // What the reference reads from the event store per query (getBiasedRecentUserActions, URAlgorithm.scala:795-839: the most recent
 // maxItemsPerUser events per event type, then distinct; getExcludedItems, :741-767: every item of the blacklist events) is here
@@ -20,9 +20,7 @@
 namespace urcco {
 
 namespace {
-constexpr int HS_SENT = 0x7fffffff;                       // "no column": sorts behind every id, dropped by the unique step
 constexpr unsigned long long HS_SIGN = 0x8000000000000000ull;  // int64 time -> order-preserving unsigned
-constexpr int HS_LDS = 4096;                              // events (keys) or window entries one block holds in LDS
 
 __device__ __forceinline__ int hs_user_events(const HistEvent& e, const int32_t* q_users, int64_t n_users, int64_t q, int64_t& seg) {
   const int u = q_users[q];
@@ -31,99 +29,11 @@ __device__ __forceinline__ int hs_user_events(const HistEvent& e, const int32_t*
   return (int)(e.idx_row_ptr[u + 1] - seg);
 }
 
-// an event's column as an exclusion: through the type's column map into the primary's items; HS_SENT = none
+// an event's column as an exclusion: through the type's column map into the primary's items; SR_SENT = none
 __device__ __forceinline__ int hs_excl_id(const HistEvent& e, int item, int n_items) {
-  if (item < 0) return HS_SENT;
+  if (item < 0) return SR_SENT;
   if (e.col_map) item = item < e.n_cols ? e.col_map[item] : -1;
-  return item >= 0 && item < n_items ? item : HS_SENT;
-}
-
-// one wave: sort the lanes' values, drop HS_SENT and duplicates, write the row; returns its length (all lanes)
-__device__ __forceinline__ int hs_wave_tail(int v, int lane, int32_t* __restrict__ dst) {
-  for (int k2 = 2; k2 <= IG_WAVE; k2 <<= 1) {
-    for (int j = k2 >> 1; j > 0; j >>= 1) {
-      const int o = __shfl_xor(v, j);
-      const bool keep_small = ((lane & j) == 0) == ((lane & k2) == 0);
-      if (keep_small ? o < v : o > v) v = o;
-    }
-  }
-  const int prev = __shfl_up(v, 1);
-  const bool fresh = v != HS_SENT && (lane == 0 || v != prev);
-  const unsigned long long m = __ballot(fresh);
-  if (fresh) dst[__popcll(m & ((1ull << lane) - 1ull))] = v;
-  return __popcll(m);
-}
-
-// one block: row[0..m) (global) -> sorted, duplicate-free, in place; returns the length (all threads).  s_v: HS_LDS ints of LDS.
-// STAGED (cco_items.h): the caller has put the m entries where the sort reads them -- s_v[0 .. 2^ceil(log2 m)), HS_SENT behind the m-th, when
-// m <= HS_LDS, else row[0..m) -- and HS_SENT among them marks an entry to drop; the result still goes to row.
-template <bool STAGED = false>
-__device__ __forceinline__ int hs_block_tail(int32_t* __restrict__ row, int m, int* s_v) {
-  __shared__ int s_wsum[256 / IG_WAVE];
-  if (m <= 0) return 0;  // block-uniform
-  const int lane = threadIdx.x & (IG_WAVE - 1), wave = threadIdx.x / IG_WAVE;
-  int64_t P = 2;
-  while (P < m) P <<= 1;
-  const bool in_lds = m <= HS_LDS;
-  if (in_lds) {
-    if (!STAGED)
-      for (int t = threadIdx.x; t < P; t += 256) s_v[t] = t < m ? row[t] : HS_SENT;
-    __syncthreads();
-    for (int k2 = 2; k2 <= P; k2 <<= 1) {
-      for (int j = k2 >> 1; j > 0; j >>= 1) {
-        for (int t = threadIdx.x; t < P; t += 256) {
-          const int u = t ^ j;
-          if (u > t) {
-            const int a = s_v[t], b = s_v[u];
-            const bool asc = (t & k2) == 0;
-            if (asc ? a > b : a < b) { s_v[t] = b; s_v[u] = a; }
-          }
-        }
-        __syncthreads();
-      }
-    }
-  } else {
-    // the ascending-only bitonic network over 2^ceil(log2 m) entries whose tail is +inf (ig_sort_rows_block_kernel): exchanges with the padding are skipped
-    for (int64_t k2 = 2; k2 <= P; k2 <<= 1) {
-      for (int64_t j = k2 >> 1; j > 0; j >>= 1) {
-        for (int64_t t = threadIdx.x; t < P; t += 256) {
-          const int64_t u = (j == (k2 >> 1)) ? (t ^ (k2 - 1)) : (t ^ j);
-          if (u > t && u < m) {
-            const int a = row[t], b = row[u];
-            if (a > b) { row[t] = b; row[u] = a; }
-          }
-        }
-        __syncthreads();
-      }
-    }
-  }
-  int carry = 0;
-  for (int base = 0; base < m; base += 256) {  // block-uniform
-    const int t = base + threadIdx.x;
-    int v = 0;
-    bool fresh = false;
-    if (t < m) {
-      v = in_lds ? s_v[t] : row[t];
-      const int pv = t == 0 ? 0 : (in_lds ? s_v[t - 1] : row[t - 1]);
-      fresh = (t == 0 || v != pv) && (!STAGED || v != HS_SENT);
-    }
-    const unsigned long long mk = __ballot(fresh);
-    if (lane == 0) s_wsum[wave] = __popcll(mk);
-    __syncthreads();
-    int before = 0, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 256 / IG_WAVE; ++w) {
-      const int c = s_wsum[w];
-      if (w < wave) before += c;
-      tot += c;
-    }
-    const int pos = carry + before + __popcll(mk & ((1ull << lane) - 1ull));
-    __syncthreads();  // every read of row[base .. base + 256) and of s_wsum precedes the writes below
-    if (fresh) row[pos] = v;  // pos <= t
-    carry += tot;
-    __syncthreads();
-  }
-  return carry;
+  return item >= 0 && item < n_items ? item : SR_SENT;
 }
 }  // namespace
 
@@ -193,23 +103,23 @@ hipError_t launch_history_bounds(hipStream_t st, int n_cu, const HistArgs& a, in
 // ctr[1 + HIST_STAT_*] = the statistics of include/urcco.h.
 // One wave per job of <= 64 events (exclusion rows: <= 64 raw entries); the others go on big_list.
 __global__ __launch_bounds__(256) void hs_rows_wave_kernel(HistArgs a) {
-  const int lane = threadIdx.x & (IG_WAVE - 1);
-  const int64_t n_waves = (int64_t)gridDim.x * (256 / IG_WAVE);
+  const int lane = threadIdx.x & (SR_WAVE - 1);
+  const int64_t n_waves = (int64_t)gridDim.x * (256 / SR_WAVE);
   const int64_t n_jobs = a.n_queries * (a.n_types + 1);
   unsigned n_term = 0, n_excl = 0, n_sel = 0, n_over = 0;
-  for (int64_t j = (int64_t)blockIdx.x * (256 / IG_WAVE) + threadIdx.x / IG_WAVE; j < n_jobs; j += n_waves) {  // wave-uniform
+  for (int64_t j = (int64_t)blockIdx.x * (256 / SR_WAVE) + threadIdx.x / SR_WAVE; j < n_jobs; j += n_waves) {  // wave-uniform
     const int t = (int)(j / a.n_queries);
     const int64_t q = j - (int64_t)t * a.n_queries;
     if (t < a.n_types) {
       const HistEvent& e = a.ev[t];
       int64_t seg;
       const int n = hs_user_events(e, a.q_users, a.n_users, q, seg);
-      if (e.raw_ptr[q + 1] > e.capacity) {  // the caller's buffers are smaller than the bounds: an empty row, counted
-        if (lane == 0) e.len[q] = 0;
+      if (e.raw.raw_ptr[q + 1] > e.raw.capacity) {  // the caller's buffers are smaller than the bounds: an empty row, counted
+        if (lane == 0) e.raw.len[q] = 0;
         ++n_over;
         continue;
       }
-      if (n > IG_WAVE) {
+      if (n > SR_WAVE) {
         if (lane == 0) a.big_list[atomicAdd(&a.ctr[0], 1ull)] = (int32_t)j;
         continue;
       }
@@ -233,22 +143,22 @@ __global__ __launch_bounds__(256) void hs_rows_wave_kernel(HistArgs a) {
         }
         in = in && rank < e.max_items;
       }
-      const int len = hs_wave_tail(in && item >= 0 && item < e.n_cols ? item : HS_SENT, lane, e.tmp + e.raw_ptr[q]);
-      if (lane == 0) e.len[q] = len;
+      const int len = sr_wave_tail<true>(in && item >= 0 && item < e.n_cols ? item : SR_SENT, lane, SR_WAVE, e.raw.tmp + e.raw.raw_ptr[q]);
+      if (lane == 0) e.raw.len[q] = len;
     } else {
-      const int64_t s = a.excl_raw_ptr[q];
-      const int64_t L = a.excl_raw_ptr[q + 1] - s;
-      if (a.excl_raw_ptr[q + 1] > a.excl_capacity) {
-        if (lane == 0) a.excl_len[q] = 0;
+      const int64_t s = a.excl.raw_ptr[q];
+      const int64_t L = a.excl.raw_ptr[q + 1] - s;
+      if (a.excl.raw_ptr[q + 1] > a.excl.capacity) {
+        if (lane == 0) a.excl.len[q] = 0;
         ++n_over;
         continue;
       }
-      if (L > IG_WAVE) {
+      if (L > SR_WAVE) {
         if (lane == 0) a.big_list[atomicAdd(&a.ctr[0], 1ull)] = (int32_t)j;
         continue;
       }
       ++n_excl;
-      int v = HS_SENT;
+      int v = SR_SENT;
       int64_t base = 0;
       for (int t2 = 0; t2 < a.n_types; ++t2) {
         const HistEvent& e = a.ev[t2];
@@ -262,11 +172,11 @@ __global__ __launch_bounds__(256) void hs_rows_wave_kernel(HistArgs a) {
         const int64_t xs = a.extra_row_ptr[q], xn = a.extra_row_ptr[q + 1] - xs;
         if (lane >= base && lane < base + xn) {
           const int x = a.extra_col_idx[xs + lane - base];
-          v = x >= 0 && x < a.n_items ? x : HS_SENT;
+          v = x >= 0 && x < a.n_items ? x : SR_SENT;
         }
       }
-      const int len = hs_wave_tail(v, lane, a.excl_tmp + s);
-      if (lane == 0) a.excl_len[q] = len;
+      const int len = sr_wave_tail<true>(v, lane, SR_WAVE, a.excl.tmp + s);
+      if (lane == 0) a.excl.len[q] = len;
     }
   }
   if (lane == 0) {
@@ -279,14 +189,14 @@ __global__ __launch_bounds__(256) void hs_rows_wave_kernel(HistArgs a) {
 
 // One block per job of big_list.
 __global__ __launch_bounds__(256) void hs_rows_block_kernel(HistArgs a) {
-  // keys of the LDS class: HS_LDS times (8 bytes), then HS_LDS positions; once the window is staged in its raw row the front is the sort buffer
-  __shared__ unsigned long long s_buf[HS_LDS + HS_LDS / 2];
+  // keys of the LDS class: SR_LDS times (8 bytes), then SR_LDS positions; once the window is staged in its raw row the front is the sort buffer
+  __shared__ unsigned long long s_buf[SR_LDS + SR_LDS / 2];
   __shared__ int s_hist[256];
   __shared__ unsigned s_diff[3];
   __shared__ int s_sel[2];
   __shared__ int s_cnt;
   unsigned long long* s_time = s_buf;
-  unsigned* s_pos = reinterpret_cast<unsigned*>(s_buf + HS_LDS);
+  unsigned* s_pos = reinterpret_cast<unsigned*>(s_buf + SR_LDS);
   int* s_v = reinterpret_cast<int*>(s_buf);
   const int64_t n_big = (int64_t)a.ctr[0];
   for (int64_t li = blockIdx.x; li < n_big; li += gridDim.x) {  // block-uniform
@@ -300,10 +210,10 @@ __global__ __launch_bounds__(256) void hs_rows_block_kernel(HistArgs a) {
       const HistEvent& e = a.ev[t];
       int64_t seg;
       const int n = hs_user_events(e, a.q_users, a.n_users, q, seg);
-      row = e.tmp + e.raw_ptr[q];
-      room = (int)(e.raw_ptr[q + 1] - e.raw_ptr[q]);
+      row = e.raw.tmp + e.raw.raw_ptr[q];
+      room = (int)(e.raw.raw_ptr[q + 1] - e.raw.raw_ptr[q]);
       const int K = e.max_items;
-      const bool in_lds = n <= HS_LDS;
+      const bool in_lds = n <= SR_LDS;
       const int32_t* __restrict__ ipos = e.idx_pos + seg;
       const int64_t* __restrict__ times = e.times_ms;
       if (in_lds)
@@ -398,8 +308,8 @@ __global__ __launch_bounds__(256) void hs_rows_block_kernel(HistArgs a) {
         }
       }
     } else {
-      row = a.excl_tmp + a.excl_raw_ptr[q];
-      const int64_t room64 = a.excl_raw_ptr[q + 1] - a.excl_raw_ptr[q];
+      row = a.excl.tmp + a.excl.raw_ptr[q];
+      const int64_t room64 = a.excl.raw_ptr[q + 1] - a.excl.raw_ptr[q];
       room = room64 > 0x7fffffffll ? 0x7fffffff : (int)room64;
       if (threadIdx.x == 0) atomicAdd(&a.ctr[1 + HIST_STAT_EXCL_BLOCK], 1ull);
       __syncthreads();
@@ -410,7 +320,7 @@ __global__ __launch_bounds__(256) void hs_rows_block_kernel(HistArgs a) {
         const int n = hs_user_events(e, a.q_users, a.n_users, q, seg);
         for (int i = threadIdx.x; i < n; i += 256) {
           const int v = hs_excl_id(e, e.items[e.idx_pos[seg + i]], a.n_items);
-          if (v != HS_SENT) {
+          if (v != SR_SENT) {
             const int slot = atomicAdd(&s_cnt, 1);
             if (slot < room) row[slot] = v;
           }
@@ -429,45 +339,34 @@ __global__ __launch_bounds__(256) void hs_rows_block_kernel(HistArgs a) {
     }
     __syncthreads();  // the raw row is complete (its writers are this block's threads), the keys in LDS are dead
     const int m = s_cnt < room ? s_cnt : room;
-    const int len = hs_block_tail(row, m, s_v);
+    const int len = sr_block_tail(row, m, s_v);
     if (threadIdx.x == 0) {
-      if (t < a.n_types) a.ev[t].len[q] = len;
-      else a.excl_len[q] = len;
+      if (t < a.n_types) a.ev[t].raw.len[q] = len;
+      else a.excl.len[q] = len;
     }
     __syncthreads();
   }
 }
 
-// a.ev[t].raw_ptr / tmp / len, a.excl_*, a.big_list, a.ctr: scratch.  term_row_ptr[t] / excl_row_ptr hold the bounds' scans on entry, the final row starts on return.
+// a.ev[t].raw, a.excl, a.big_list, a.ctr: scratch.  term_row_ptr[t] / excl_row_ptr hold the bounds' scans on entry, the final row starts on return.
 hipError_t launch_history_rows(hipStream_t st, int n_cu, const HistArgs& a, int64_t* tile_sums, int64_t* const* term_row_ptr, int32_t* const* term_col_idx,
                                int64_t* excl_row_ptr, int32_t* excl_col_idx, int64_t* stats_dev) {
   hipError_t e = hipMemsetAsync(a.ctr, 0, sizeof(unsigned long long) * (1 + HIST_STATS_LEN), st);
   if (e != hipSuccess) return e;
   const int64_t nq = a.n_queries;
+  const int n_out = a.n_types + 1;
+  RowsOut out[REC_MAX_CLAUSES + 1];
+  for (int t = 0; t < a.n_types; ++t) out[t] = RowsOut{a.ev[t].raw, term_row_ptr[t], term_col_idx[t]};
+  out[a.n_types] = RowsOut{a.excl, excl_row_ptr, excl_col_idx};
+  e = sr_seed_raw_ptr(st, out, n_out, nq);
+  if (e != hipSuccess) return e;
   if (nq > 0) {
-    for (int t = 0; t <= a.n_types; ++t) {
-      e = hipMemcpyAsync(t < a.n_types ? a.ev[t].raw_ptr : a.excl_raw_ptr, t < a.n_types ? term_row_ptr[t] : excl_row_ptr,
-                         sizeof(int64_t) * (size_t)(nq + 1), hipMemcpyDeviceToDevice, st);
-      if (e != hipSuccess) return e;
-    }
-    const int64_t n_jobs = nq * (a.n_types + 1);
-    hipLaunchKernelGGL(hs_rows_wave_kernel, dim3(ig_grid(n_jobs * IG_WAVE, n_cu)), dim3(256), 0, st, a);
+    const int64_t n_jobs = nq * n_out;
+    hipLaunchKernelGGL(hs_rows_wave_kernel, dim3(ig_grid(n_jobs * SR_WAVE, n_cu)), dim3(256), 0, st, a);
     const int64_t bgrid = n_jobs < (int64_t)n_cu * 8 ? n_jobs : (int64_t)n_cu * 8;
     hipLaunchKernelGGL(hs_rows_block_kernel, dim3((unsigned)bgrid), dim3(256), 0, st, a);
-    const unsigned cgrid = ig_grid(nq * IG_WAVE, n_cu);
-    for (int t = 0; t <= a.n_types; ++t) {
-      const bool term = t < a.n_types;
-      int64_t* rp = term ? term_row_ptr[t] : excl_row_ptr;
-      e = launch_scan_i32(st, term ? a.ev[t].len : a.excl_len, nq, rp, tile_sums);
-      if (e != hipSuccess) return e;
-      hipLaunchKernelGGL(ig_compact_rows_kernel, dim3(cgrid), dim3(256), 0, st, nq, term ? a.ev[t].raw_ptr : a.excl_raw_ptr, term ? a.ev[t].tmp : a.excl_tmp, rp,
-                         term ? term_col_idx[t] : excl_col_idx);
-    }
-  } else {
-    for (int t = 0; t <= a.n_types; ++t) {
-      e = hipMemsetAsync(t < a.n_types ? term_row_ptr[t] : excl_row_ptr, 0, sizeof(int64_t), st);
-      if (e != hipSuccess) return e;
-    }
+    e = sr_finish_rows(st, n_cu, out, n_out, nq, tile_sums);
+    if (e != hipSuccess) return e;
   }
   if (stats_dev) {
     e = hipMemcpyAsync(stats_dev, a.ctr + 1, sizeof(int64_t) * HIST_STATS_LEN, hipMemcpyDeviceToDevice, st);

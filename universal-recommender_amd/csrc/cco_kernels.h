@@ -169,6 +169,13 @@ hipError_t launch_dictionary_lookup(hipStream_t st, int n_cu, KeyTable t, int64_
                                     int32_t* ids);
 hipError_t launch_dictionary_verify(hipStream_t st, int n_cu, KeyTable t, int64_t n, const unsigned long long* keys, const int32_t* select,
                                     const unsigned long long* check, const unsigned long long* ref_check, const int64_t* first_pos, unsigned long long* err);
+// Raw rows on their way to sorted, duplicate-free rows (cco_sorted_rows.h): the scratch of the CSR build, of every history and of every item event type
+struct RawRows {
+  int64_t* raw_ptr;  // [n_rows + 1]: the raw row starts (scan of the bounds)
+  int32_t* tmp;      // [capacity]: the raw rows
+  int32_t* len;      // [n_rows]: the rows' final lengths
+  int64_t capacity;  // entries of tmp (and of the caller's col_idx)
+};
 // cnt: int32[n_rows] scratch, raw_ptr: int64[n_rows + 1] scratch, tmp: int32[n] scratch
 hipError_t launch_csr_from_pairs(hipStream_t st, int n_cu, int64_t n, const int32_t* rows, const int32_t* cols, int64_t n_rows, int32_t* cnt,
                                  int64_t* raw_ptr, int32_t* tmp, int64_t* tile_sums, int64_t* out_row_ptr, int32_t* out_col_idx);
@@ -308,10 +315,7 @@ struct HistEvent {
   const int32_t* items;        // the stream: column id per event, < 0 = none
   const int64_t* times_ms;     // nullable: stream order is time order
   const int32_t* col_map;      // nullable (identity): column id -> item id of the primary or -1
-  int64_t* raw_ptr;            // scratch [n_queries + 1]: the raw row starts (scan of the bounds)
-  int32_t* tmp;                // scratch [capacity]: the raw rows
-  int32_t* len;                // scratch [n_queries]: the rows' final lengths
-  int64_t capacity;            // entries of the caller's term_col_idx (and of tmp)
+  RawRows raw;                 // scratch, n_queries rows; capacity = entries of the caller's term_col_idx
   int32_t n_cols, max_items, blacklist, reserved;
 };
 struct HistArgs {
@@ -320,10 +324,7 @@ struct HistArgs {
   const int32_t* q_users;
   const int64_t* extra_row_ptr;  // nullable pair: the caller's own exclusions per query
   const int32_t* extra_col_idx;
-  int64_t* excl_raw_ptr;         // scratch, as in HistEvent
-  int32_t* excl_tmp;
-  int32_t* excl_len;
-  int64_t excl_capacity;
+  RawRows excl;                  // scratch, as in HistEvent
   int32_t* big_list;             // scratch [n_queries * (n_types + 1)]: jobs of more than one wave
   unsigned long long* ctr;       // scratch [1 + HIST_STATS_LEN]
   int32_t n_types, n_items;
@@ -340,10 +341,7 @@ hipError_t launch_history_rows(hipStream_t st, int n_cu, const HistArgs& a, int6
 struct ItemEvent {
   const int64_t* ind_row_ptr;  // the indicator CSR of the event type, n_items rows, as the build leaves it
   const int32_t* ind_col_idx;
-  int64_t* raw_ptr;            // scratch [n_queries + 1]: the raw row starts (scan of the bounds)
-  int32_t* tmp;                // scratch [capacity]: the raw rows
-  int32_t* len;                // scratch [n_queries]: the rows' final lengths
-  int64_t capacity;            // entries of the caller's term_col_idx (and of tmp)
+  RawRows raw;                 // scratch, n_queries rows; capacity = entries of the caller's term_col_idx
   int32_t n_cols, max_terms;
 };
 struct ItemArgs {

@@ -17,7 +17,6 @@
 namespace urcco {
 
 namespace {
-constexpr int IG_WAVE = 64;
 constexpr unsigned long long IG_EMPTY = ~0ull;
 
 __device__ __forceinline__ unsigned long long ig_mix(unsigned long long x) {  // splitmix64 finaliser
@@ -148,10 +147,16 @@ hipError_t launch_dictionary_lookup(hipStream_t st, int n_cu, KeyTable t, int64_
   return hipGetLastError();
 }
 
+}  // namespace urcco
+
+#include "cco_sorted_rows.h"  // raw rows -> sorted, duplicate-free rows: the unit of the CSR build below, of cco_history.h and of cco_items.h
+
+namespace urcco {
+
 // ============================================================================================
 // (row, col) pairs -> binary CSR.  count per row (L2 atomics) -> scan -> scatter by cursor -> per row: sort ascending,
-// drop duplicates (rows of <= 64 raw entries: bitonic network in the registers of one wave; longer rows: one block,
-// bitonic in LDS up to 4096 entries, in global memory beyond) -> scan of the final lengths -> compaction.
+// drop duplicates (cco_sorted_rows.h: one wave for rows of <= 64 raw entries, one block for longer ones) -> scan of the
+// final lengths -> compaction.
 // ============================================================================================
 __global__ __launch_bounds__(256) void ig_count_rows_kernel(int64_t n, const int32_t* __restrict__ rows, const int32_t* __restrict__ cols,
                                                             int32_t* __restrict__ cnt) {
@@ -172,121 +177,31 @@ __global__ __launch_bounds__(256) void ig_scatter_rows_kernel(int64_t n, const i
 // Rows with more entries get len[r] = -1 (the block kernel takes them).
 __global__ __launch_bounds__(256) void ig_sort_rows_wave_kernel(int64_t n_rows, const int64_t* __restrict__ raw_ptr, int32_t* __restrict__ tmp,
                                                                 int32_t* __restrict__ len) {
-  const int lane = threadIdx.x & (IG_WAVE - 1);
-  const int64_t n_waves = (int64_t)gridDim.x * (256 / IG_WAVE);
-  for (int64_t r = (int64_t)blockIdx.x * (256 / IG_WAVE) + threadIdx.x / IG_WAVE; r < n_rows; r += n_waves) {  // wave-uniform
+  const int lane = threadIdx.x & (SR_WAVE - 1);
+  const int64_t n_waves = (int64_t)gridDim.x * (256 / SR_WAVE);
+  for (int64_t r = (int64_t)blockIdx.x * (256 / SR_WAVE) + threadIdx.x / SR_WAVE; r < n_rows; r += n_waves) {  // wave-uniform
     const int64_t s = raw_ptr[r];
     const int64_t L = raw_ptr[r + 1] - s;
-    if (L > IG_WAVE) {
+    if (L > SR_WAVE) {
       if (lane == 0) len[r] = -1;
       continue;
     }
-    int v = lane < L ? tmp[s + lane] : 0x7fffffff;
-    for (int k2 = 2; k2 <= IG_WAVE; k2 <<= 1) {
-      for (int j = k2 >> 1; j > 0; j >>= 1) {
-        const int o = __shfl_xor(v, j);
-        const bool keep_small = ((lane & j) == 0) == ((lane & k2) == 0);  // lower lane of an ascending block
-        if (keep_small ? o < v : o > v) v = o;
-      }
-    }
-    const int prev = __shfl_up(v, 1);
-    const bool fresh = lane < L && (lane == 0 || v != prev);
-    const unsigned long long m = __ballot(fresh);
-    if (fresh) tmp[s + __popcll(m & ((1ull << lane) - 1ull))] = v;
-    if (lane == 0) len[r] = __popcll(m);
+    const int n = sr_wave_tail<false>(lane < L ? tmp[s + lane] : SR_SENT, lane, (int)L, tmp + s);
+    if (lane == 0) len[r] = n;
   }
 }
-
-constexpr int IG_LDS_ROW = 4096;
 
 // one block per row with > 64 raw entries (grid-stride over all rows; the test is block-uniform)
 __global__ __launch_bounds__(256) void ig_sort_rows_block_kernel(int64_t n_rows, const int64_t* __restrict__ raw_ptr, int32_t* __restrict__ tmp,
                                                                  int32_t* __restrict__ len) {
-  __shared__ int s_v[IG_LDS_ROW];
-  __shared__ int s_wsum[256 / IG_WAVE];
-  __shared__ int s_total;
-  const int lane = threadIdx.x & (IG_WAVE - 1), wave = threadIdx.x / IG_WAVE;
+  __shared__ int s_v[SR_LDS];
   for (int64_t r = blockIdx.x; r < n_rows; r += gridDim.x) {
     const int64_t s = raw_ptr[r];
     const int64_t L = raw_ptr[r + 1] - s;
-    if (L <= IG_WAVE) continue;  // block-uniform
-    int64_t P = 1;
-    while (P < L) P <<= 1;
-    int* row = tmp + s;
-    const bool in_lds = L <= IG_LDS_ROW;
-    if (in_lds) {
-      for (int64_t t = threadIdx.x; t < P; t += 256) s_v[t] = t < L ? row[t] : 0x7fffffff;
-      __syncthreads();
-      for (int64_t k2 = 2; k2 <= P; k2 <<= 1) {
-        for (int64_t j = k2 >> 1; j > 0; j >>= 1) {
-          for (int64_t t = threadIdx.x; t < P; t += 256) {
-            const int64_t u = t ^ j;
-            if (u > t) {
-              const int a = s_v[t], b = s_v[u];
-              const bool asc = (t & k2) == 0;
-              if (asc ? a > b : a < b) { s_v[t] = b; s_v[u] = a; }
-            }
-          }
-          __syncthreads();
-        }
-      }
-    } else {
-      // In global memory, as P = 2^ceil(log2 L) entries whose tail [L, P) is +inf.  The ascending-only formulation of the
-      // bitonic network (partner = t ^ (k2 - 1) on the first step of a level, t ^ j afterwards; the smaller value always
-      // goes to the lower index) never moves a real value into the padding, so exchanges that touch it are skipped.
-      for (int64_t k2 = 2; k2 <= P; k2 <<= 1) {
-        for (int64_t j = k2 >> 1; j > 0; j >>= 1) {
-          for (int64_t t = threadIdx.x; t < P; t += 256) {
-            const int64_t u = (j == (k2 >> 1)) ? (t ^ (k2 - 1)) : (t ^ j);
-            if (u > t && u < L) {
-              const int a = row[t], b = row[u];
-              if (a > b) { row[t] = b; row[u] = a; }
-            }
-          }
-          __syncthreads();
-        }
-      }
-    }
-    // unique: keep an entry iff it differs from its predecessor; positions by block scan, chunk by chunk
-    int carry = 0;
-    for (int64_t base = 0; base < L; base += 256) {  // block-uniform
-      const int64_t t = base + threadIdx.x;
-      int v = 0, pv = 0;
-      bool fresh = false;
-      if (t < L) {
-        v = in_lds ? s_v[t] : row[t];
-        pv = t == 0 ? 0 : (in_lds ? s_v[t - 1] : row[t - 1]);
-        fresh = t == 0 || v != pv;
-      }
-      const unsigned long long m = __ballot(fresh);
-      if (lane == 0) s_wsum[wave] = __popcll(m);
-      __syncthreads();
-      int before = 0, tot = 0;
-#pragma unroll
-      for (int w = 0; w < 256 / IG_WAVE; ++w) {
-        const int c = s_wsum[w];
-        if (w < wave) before += c;
-        tot += c;
-      }
-      const int pos = carry + before + __popcll(m & ((1ull << lane) - 1ull));
-      __syncthreads();  // every read of row[base .. base+256) and of s_wsum precedes the writes below
-      if (fresh) row[pos] = v;  // pos <= t: in-place compaction towards the front, chunk by chunk
-      carry += tot;
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) len[r] = carry;
+    if (L <= SR_WAVE) continue;  // block-uniform
+    const int n = sr_block_tail(tmp + s, L, s_v);
+    if (threadIdx.x == 0) len[r] = n;
     __syncthreads();
-  }
-}
-
-__global__ __launch_bounds__(256) void ig_compact_rows_kernel(int64_t n_rows, const int64_t* __restrict__ raw_ptr, const int32_t* __restrict__ tmp,
-                                                              const int64_t* __restrict__ out_rp, int32_t* __restrict__ out_ci) {
-  const int lane = threadIdx.x & (IG_WAVE - 1);
-  const int64_t n_waves = (int64_t)gridDim.x * (256 / IG_WAVE);
-  for (int64_t r = (int64_t)blockIdx.x * (256 / IG_WAVE) + threadIdx.x / IG_WAVE; r < n_rows; r += n_waves) {
-    const int64_t s = raw_ptr[r], d = out_rp[r];
-    const int64_t L = out_rp[r + 1] - d;
-    for (int64_t t = lane; t < L; t += IG_WAVE) out_ci[d + t] = tmp[s + t];
   }
 }
 
@@ -301,17 +216,14 @@ hipError_t launch_csr_from_pairs(hipStream_t st, int n_cu, int64_t n, const int3
   e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)n_rows, st);  // now the scatter cursors
   if (e != hipSuccess) return e;
   if (n > 0) hipLaunchKernelGGL(ig_scatter_rows_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, rows, cols, raw_ptr, cnt, tmp);
-  const unsigned wgrid = ig_grid(n_rows * IG_WAVE, n_cu);
-  hipLaunchKernelGGL(ig_sort_rows_wave_kernel, dim3(wgrid), dim3(256), 0, st, n_rows, raw_ptr, tmp, cnt);  // cnt becomes the final lengths
+  const RowsOut out{RawRows{raw_ptr, tmp, cnt, n}, out_row_ptr, out_col_idx};  // cnt becomes the final lengths
+  hipLaunchKernelGGL(ig_sort_rows_wave_kernel, dim3(ig_grid(n_rows * SR_WAVE, n_cu)), dim3(256), 0, st, n_rows, raw_ptr, tmp, cnt);
   int64_t bgrid = n_rows < (int64_t)n_cu * 8 ? n_rows : (int64_t)n_cu * 8;
   hipLaunchKernelGGL(ig_sort_rows_block_kernel, dim3((unsigned)(bgrid < 1 ? 1 : bgrid)), dim3(256), 0, st, n_rows, raw_ptr, tmp, cnt);
-  e = launch_scan_i32(st, cnt, n_rows, out_row_ptr, tile_sums);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(ig_compact_rows_kernel, dim3(wgrid), dim3(256), 0, st, n_rows, raw_ptr, tmp, out_row_ptr, out_col_idx);
-  return hipGetLastError();
+  return sr_finish_rows(st, n_cu, &out, 1, n_rows, tile_sums);
 }
 
 }  // namespace urcco
 
-#include "cco_history.h"  // device-resident user history: uses ig_grid and ig_compact_rows_kernel
-#include "cco_items.h"    // device-resident item queries: the tails of cco_history.h over the model's own indicator rows
+#include "cco_history.h"  // device-resident user history: uses ig_grid and cco_sorted_rows.h
+#include "cco_items.h"    // device-resident item queries: the same over the model's own indicator rows

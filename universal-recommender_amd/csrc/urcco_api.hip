@@ -707,6 +707,12 @@ int urcco_dev_pop_counts(urcco_session* s, int64_t n_events, const int32_t* item
 
 }  // extern "C"
 
+// the scratch of n_rows raw rows (cco_sorted_rows.h) of `capacity` entries in all
+static void add_raw_rows(ArenaLayout& L, urcco::RawRows* r, size_t n_rows, int64_t capacity) {
+  L.add(&r->raw_ptr, n_rows + 1).add(&r->len, n_rows).add(&r->tmp, (size_t)capacity);
+  r->capacity = capacity;
+}
+
 // urcco_dev_history_bounds / _rows: argument checks and the launch arguments; rows: also the output arrays
 static int history_args(const char* who, urcco_session* s, int64_t n_queries, const int32_t* q_users, int64_t n_users, const urcco_hist_event* events, int32_t n_types,
                         const int64_t* extra_row_ptr, const int32_t* extra_col_idx, const int64_t* excl_row_ptr, bool rows, urcco::HistArgs* a) {
@@ -722,7 +728,7 @@ static int history_args(const char* who, urcco_session* s, int64_t n_queries, co
       return fail(URCCO_BAD_ARG, "%s: event type %d: bad argument", who, t);
     urcco::HistEvent& e = a->ev[t];
     e.idx_row_ptr = in.idx_row_ptr; e.idx_pos = in.idx_pos; e.items = in.items; e.times_ms = in.times_ms; e.col_map = in.col_map;
-    e.capacity = in.term_capacity; e.n_cols = in.n_cols; e.max_items = in.max_items; e.blacklist = in.blacklist != 0;
+    e.n_cols = in.n_cols; e.max_items = in.max_items; e.blacklist = in.blacklist != 0;
   }
   a->n_queries = n_queries; a->n_users = n_users; a->q_users = q_users; a->extra_row_ptr = extra_row_ptr; a->extra_col_idx = extra_col_idx; a->n_types = n_types;
   return URCCO_OK;
@@ -766,13 +772,12 @@ int urcco_dev_history_rows(urcco_session* s, int64_t n_queries, const int32_t* q
   int64_t* rp[URCCO_REC_MAX_CLAUSES];
   int32_t* ci[URCCO_REC_MAX_CLAUSES];
   for (int t = 0; t < n_types; ++t) {
-    L.add(&a.ev[t].raw_ptr, nq + 1).add(&a.ev[t].len, nq).add(&a.ev[t].tmp, (size_t)events[t].term_capacity);
+    add_raw_rows(L, &a.ev[t].raw, nq, events[t].term_capacity);
     rp[t] = events[t].term_row_ptr;
     ci[t] = events[t].term_col_idx;
   }
-  L.add(&a.excl_raw_ptr, nq + 1).add(&a.excl_len, nq).add(&a.excl_tmp, (size_t)excl_capacity);
+  add_raw_rows(L, &a.excl, nq, excl_capacity);
   URC(L.commit());
-  a.excl_capacity = excl_capacity;
   a.n_items = n_items;
   HIPC(urcco::launch_history_rows(s->stream, s->n_cu, a, tile_sums, rp, ci, excl_row_ptr, excl_col_idx, stats_dev));
   return URCCO_OK;
@@ -793,7 +798,7 @@ static int item_args(const char* who, urcco_session* s, int64_t n_queries, const
     if (in.n_cols < 0 || !in.ind_row_ptr || !in.ind_col_idx || !in.term_row_ptr || (rows && (!in.term_col_idx || in.term_capacity < 0)))
       return fail(URCCO_BAD_ARG, "%s: event type %d: bad argument", who, t);
     urcco::ItemEvent& e = a->ev[t];
-    e.ind_row_ptr = in.ind_row_ptr; e.ind_col_idx = in.ind_col_idx; e.capacity = in.term_capacity; e.n_cols = in.n_cols; e.max_terms = in.max_terms;
+    e.ind_row_ptr = in.ind_row_ptr; e.ind_col_idx = in.ind_col_idx; e.n_cols = in.n_cols; e.max_terms = in.max_terms;
   }
   a->n_queries = n_queries; a->q_items = q_items; a->n_types = n_types; a->n_items = n_items;
   return URCCO_OK;
@@ -823,7 +828,7 @@ int urcco_dev_item_rows(urcco_session* s, int64_t n_queries, const int32_t* q_it
   int64_t* rp[URCCO_REC_MAX_CLAUSES];
   int32_t* ci[URCCO_REC_MAX_CLAUSES];
   for (int t = 0; t < n_types; ++t) {
-    L.add(&a.ev[t].raw_ptr, nq + 1).add(&a.ev[t].len, nq).add(&a.ev[t].tmp, (size_t)events[t].term_capacity);
+    add_raw_rows(L, &a.ev[t].raw, nq, events[t].term_capacity);
     rp[t] = events[t].term_row_ptr;
     ci[t] = events[t].term_col_idx;
   }

@@ -303,37 +303,17 @@ class DeviceSession:
         "ms": device time of the two calls | None, "bound_row_ptr": copies of the bounds' row_ptr arrays with keep_bounds (tests)}.  Reads the 1 + n_types bound totals between the two calls: one synchronisation."""
         nq = int(q_users.numel())
         arr = (_lib.HistEvent * max(len(events), 1))()
-        rps = []
+        rps = [self.empty(nq + 1, torch.int64) for _ in range(len(events) + 1)]   # the last: the exclusion rows
         for t, (n_cols, max_items, blacklist, irp, ipos, items, times, cmap) in enumerate(events):
-            rp = self.empty(nq + 1, torch.int64)
-            rps.append(rp)
             arr[t].n_cols, arr[t].max_items, arr[t].blacklist = int(n_cols), int(max_items), int(bool(blacklist))
             arr[t].idx_row_ptr, arr[t].idx_pos, arr[t].items, arr[t].times_ms, arr[t].col_map = _ptr(irp), _ptr(ipos), _ptr(items), _ptr(times), _ptr(cmap)
-            arr[t].term_row_ptr = _ptr(rp)
-        excl_rp = self.empty(nq + 1, torch.int64)
+            arr[t].term_row_ptr = _ptr(rps[t])
         x_rp, x_ci = (_ptr(extra[0]), _ptr(extra[1])) if extra is not None else (None, None)
-        ev0 = ev1 = None
-        if timing and self.device.type == "cuda":
-            ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            ev0.record(self.torch_stream)
-        self._check(self.lib.urcco_dev_history_bounds(self.handle, nq, _ptr(q_users), n_users, arr, len(events), x_rp, x_ci, _ptr(excl_rp)))
-        totals = torch.stack([rp[nq] for rp in rps] + [excl_rp[nq]]).cpu().tolist()   # the one synchronisation
-        bound_rp = [rp.clone() for rp in rps + [excl_rp]] if keep_bounds else None
-        cis = []
-        for t, total in enumerate(totals[:-1]):
-            ci = self.empty(max(total, 1), torch.int32)
-            cis.append(ci)
-            arr[t].term_col_idx, arr[t].term_capacity = _ptr(ci), int(total)
-        excl_ci = self.empty(max(totals[-1], 1), torch.int32)
-        st = self.empty(_lib.HIST_STATS_LEN, torch.int64) if stats else None
-        self._check(self.lib.urcco_dev_history_rows(self.handle, nq, _ptr(q_users), n_users, arr, len(events), x_rp, x_ci, int(n_items), _ptr(excl_rp), _ptr(excl_ci),
-                                                   int(totals[-1]), _ptr(st)))
-        ms = None
-        if ev0 is not None:
-            ev1.record(self.torch_stream)
-            ev1.synchronize()
-            ms = ev0.elapsed_time(ev1)
-        return list(zip(rps, cis)), (excl_rp, excl_ci), {"bounds": totals, "stats": st, "ms": ms, "bound_row_ptr": bound_rp}
+        head = (self.handle, nq, _ptr(q_users), n_users, arr, len(events), x_rp, x_ci)
+        cis, info = self._bounded_rows(arr, len(events), nq, rps, stats, timing, keep_bounds,
+                                       lambda: self.lib.urcco_dev_history_bounds(*head, _ptr(rps[-1])),
+                                       lambda cis, totals, st: self.lib.urcco_dev_history_rows(*head, int(n_items), _ptr(rps[-1]), _ptr(cis[-1]), int(totals[-1]), _ptr(st)))
+        return list(zip(rps[:-1], cis[:-1])), (rps[-1], cis[-1]), info
 
     def item_rows(self, q_items: torch.Tensor, specs, stats: bool = False, timing: bool = False, n_items: Optional[int] = None, keep_bounds: bool = False):
         """urcco_dev_item_bounds + urcco_dev_item_rows: the term rows of a batch of item queries, cut from the indicator matrices on the device.
@@ -347,31 +327,36 @@ class DeviceSession:
         if n_items is None:
             n_items = int(specs[0][2].numel()) - 1
         arr = (_lib.ItemEvent * max(len(specs), 1))()
-        rps = []
+        rps = [self.empty(nq + 1, torch.int64) for _ in specs]
         for t, (n_cols, max_terms, irp, ici) in enumerate(specs):
-            rp = self.empty(nq + 1, torch.int64)
-            rps.append(rp)
-            arr[t].n_cols, arr[t].max_terms, arr[t].ind_row_ptr, arr[t].ind_col_idx, arr[t].term_row_ptr = int(n_cols), int(max_terms), _ptr(irp), _ptr(ici), _ptr(rp)
+            arr[t].n_cols, arr[t].max_terms, arr[t].ind_row_ptr, arr[t].ind_col_idx, arr[t].term_row_ptr = int(n_cols), int(max_terms), _ptr(irp), _ptr(ici), _ptr(rps[t])
+        head = (self.handle, nq, _ptr(q_items), int(n_items), arr, len(specs))
+        cis, info = self._bounded_rows(arr, len(specs), nq, rps, stats, timing, keep_bounds, lambda: self.lib.urcco_dev_item_bounds(*head),
+                                       lambda cis, totals, st: self.lib.urcco_dev_item_rows(*head, _ptr(st)))
+        return list(zip(rps, cis)), info
+
+    def _bounded_rows(self, arr, n_types, nq, rps, stats, timing, keep_bounds, bounds, rows):
+        """The two-call protocol of history_rows and item_rows.  bounds() leaves in every row_ptr of `rps` the scan of its rows' upper bounds; their
+        totals are read (the one synchronisation) and size the col_idx tensors, those of the first n_types go into the struct array `arr`;
+        rows(col_idx tensors, totals, stats tensor | None) fills them and rewrites the row_ptr.  Returns (col_idx tensors, info)."""
         ev0 = ev1 = None
         if timing and self.device.type == "cuda":
             ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             ev0.record(self.torch_stream)
-        self._check(self.lib.urcco_dev_item_bounds(self.handle, nq, _ptr(q_items), int(n_items), arr, len(specs)))
+        self._check(bounds())
         totals = torch.stack([rp[nq] for rp in rps]).cpu().tolist()   # the one synchronisation
         bound_rp = [rp.clone() for rp in rps] if keep_bounds else None
-        cis = []
-        for t, total in enumerate(totals):
-            ci = self.empty(max(total, 1), torch.int32)
-            cis.append(ci)
-            arr[t].term_col_idx, arr[t].term_capacity = _ptr(ci), int(total)
+        cis = [self.empty(max(total, 1), torch.int32) for total in totals]
+        for t in range(n_types):
+            arr[t].term_col_idx, arr[t].term_capacity = _ptr(cis[t]), int(totals[t])
         st = self.empty(_lib.HIST_STATS_LEN, torch.int64) if stats else None
-        self._check(self.lib.urcco_dev_item_rows(self.handle, nq, _ptr(q_items), int(n_items), arr, len(specs), _ptr(st)))
+        self._check(rows(cis, totals, st))
         ms = None
         if ev0 is not None:
             ev1.record(self.torch_stream)
             ev1.synchronize()
             ms = ev0.elapsed_time(ev1)
-        return list(zip(rps, cis)), {"bounds": totals, "stats": st, "ms": ms, "bound_row_ptr": bound_rp}
+        return cis, {"bounds": totals, "stats": st, "ms": ms, "bound_row_ptr": bound_rp}
 
     def llr(self, with_a, with_b, with_ab, n_users) -> torch.Tensor:
         out = self.empty(with_a.numel(), torch.float64)
