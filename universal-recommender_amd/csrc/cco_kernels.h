@@ -41,6 +41,9 @@ constexpr int32_t DBG_UNPACKED_COUNTS = 1048576;    // B' travels as plain colum
 // The k11 = 1 prefilter of the packed row kernels (cco_rows.hip).  Neither bit selects the DBG instantiations: the production kernels take them as arguments.
 constexpr int32_t DBG_NO_PREFILTER = 8388608;       // every distinct candidate is scored (A/B, and the tests' bit-for-bit comparison)
 constexpr int32_t DBG_COUNT_SCORED = 16777216;      // with stage timing on: stats[2 + 4 * NBINS] counts the candidates that were SCORED instead of the distinct ones
+// The direct ranking of the packed row kernels (cco_rows.hip, direct_limit).  As above: arguments of the production kernels.
+constexpr int32_t DBG_NO_DIRECT_RANK = 33554432;    // every row with more than k valid candidates goes through the select (A/B, and the tests' bit-for-bit comparison)
+constexpr int32_t DBG_COUNT_DIRECT = 67108864;      // with stage timing on: stats[2 + 4 * NBINS] counts the ROWS that were ranked directly instead of the candidates
 constexpr int32_t DBG_ROW_KERNELS = DBG_GATHER_ONLY | DBG_NO_LLR | DBG_NO_TOPK | DBG_NO_SELECT | DBG_NO_RANK | DBG_NO_COUNT_GATHER | DBG_SELECT_DELAY;
 
 // The form of a build's expand tables, decided on the device by the scan of the work prefix (launch_expand_prepare / launch_expand_scan).

@@ -593,6 +593,21 @@ constexpr int URCCO_SEL_M_BLOCK = 128;  // capacity of the ambiguous set of the 
 constexpr int URCCO_G_CU = 2;
 // The k11 = 1 prefilter (see the compaction of cco_rows_kernel), per class: compiled out of a class in which it does not pay.
 __host__ __device__ constexpr bool prefilter_class(int T, int E) { return T >= WAVE && E >= 1024; }
+// The DIRECT RANKING (see "5. top-k" of cco_rows_kernel), per class: a row of the instantiations that carry the prefilter whose C valid candidates number
+// more than k and at most this many is ranked at once, without a select.  At most the class's ambiguous-set capacity (SEL_M); 0 = compiled out of the class.
+// Teams of several waves: ranking m members costs 4 m ceil(m / 64) wave instructions over the team against the select's passes and barriers; 64, 96 and 128 were
+// measured on the same box (profiles/direct_rank_ab.log) and 128 covers every class's rows at no loss.  One wave: compiled OUT.  With the limit at one element per
+// lane (64: beyond it the ranking costs 8 C instructions) 30 % of the class's rows of config 4 qualified and the vector instructions per launch did not move
+// (426.5 -> 427.9 M; 3.96 -> 3.95 ms): a one-wave row with <= 64 valid candidates already leaves its select after the shared-byte sweep and ONE pass -- the cut
+// bin then holds at most SEL_AMB members and the merged finish ranks them -- while the branch cost the other rows 23 more spilled scalar registers.
+constexpr unsigned URCCO_DIRECT_WAVE = 0;
+constexpr unsigned URCCO_DIRECT_BS = 128;
+constexpr unsigned URCCO_DIRECT_B = 128;
+constexpr unsigned URCCO_DIRECT_H = 128;
+constexpr unsigned URCCO_DIRECT_C = 128;
+__host__ __device__ constexpr unsigned direct_limit(int T, int E) {
+  return !prefilter_class(T, E) ? 0u : (T == WAVE ? URCCO_DIRECT_WAVE : (T == 256 ? (E == 4096 ? URCCO_DIRECT_BS : URCCO_DIRECT_B) : (T == 512 ? URCCO_DIRECT_H : URCCO_DIRECT_C)));
+}
 constexpr unsigned PF_BINS = 256;  // bins of the count histogram: cB = 0 .. 254, the last one is the clamp bin and stays empty (a cut never falls in it)
 // MP ("multi-pass", bin 6): rows no single LDS table can hold -- a hot item of a skewed catalogue pairs with tens of thousands
 // of distinct columns -- or whose counts overflow the packed field.  Such a row is accumulated in P = 2^s passes over its
@@ -614,7 +629,8 @@ template <bool NARROW> struct PStart { typedef int64_t type; };
 template <> struct PStart<true> { typedef unsigned type; };
 template <int T, int E, int U, bool MP = false, bool DBG = false, bool PK = false>
 __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T == 256 && E == 4096 ? URCCO_OCC_BS : (T == 512 ? 4 : 1)))) void cco_rows_kernel(CcoArgs a, int bin_arg) {
-  const int bin = bin_arg & 255;  // (bit 8: the statistics count the candidates that were SCORED -- DBG_COUNT_SCORED --, not the distinct ones)
+  const int bin = bin_arg & 255;  // (bit 8: the statistics count the candidates that were SCORED -- DBG_COUNT_SCORED --, not the distinct ones;
+                                  // bit 9: no direct ranking -- DBG_NO_DIRECT_RANK --; bit 10: they count the ROWS that were ranked directly -- DBG_COUNT_DIRECT)
   // (the same verdict names the form of the expand tables -- CcoArgs::form: this instantiation reads the narrow ones, the plain one the wide ones)
   if ((a.b_packed != nullptr && (a.pk_known != 0 || *a.form == 0)) != PK) return;  // grid-uniform
   using PS = typename PStart<PK>::type;  // a start of a B' row: 32 bits in the narrow form
@@ -709,6 +725,8 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
   constexpr bool PF = PK && !MP && prefilter_class(T, E);
   static_assert(!PF || !SHARE || T == WAVE || (sizeof(PS) == 4 && T * 4 + PF_BINS * 2 <= T * 8), "the histogram sits behind the 32-bit starts");
   unsigned* pfh = (SHARE && T != WAVE) ? reinterpret_cast<unsigned*>(share) + T : hist;
+  constexpr unsigned DL = PF ? direct_limit(T, E) : 0u;  // the direct ranking: only the instantiations that carry the prefilter, 0 = none
+  static_assert(DL <= (unsigned)SEL_M, "a directly ranked row lives in the ambiguous-set arrays");
   const int list_start = a.bin_off[bin];
   const int list_n = a.bin_off[bin + 1] - list_start;
   const int total_teams = gridDim.x * TEAMS;
@@ -942,7 +960,11 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
     // order and LLR bits are what they were (config 4: 96 % of the candidates hold k11 = 1 and 72 % of all are thrown away by the top-k cut).
     unsigned pf_lim = 0u;  // this row's limit: loaded where the cut is found, in flight across the histogram reads and the prefix sum
     if (PF) {
-      if (T == WAVE) *reinterpret_cast<uint2*>(&pfh[2 * lane]) = make_uint2(0u, 0u);
+      if (T == WAVE) {
+        *reinterpret_cast<uint2*>(&pfh[2 * lane]) = make_uint2(0u, 0u);
+        wave_sync();  // (no instruction: the wave's LDS accesses execute in order.  It is there for the host simulator, whose lanes run one after the other between
+                      // two wave operations -- a lane's counts would be wiped by the lanes that zero their words after it, and the cut would be found too high)
+      }
     }
     {
       unsigned cw[CPT], cv[CPT];
@@ -1007,7 +1029,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
             ++pos;
           }
         }
-        if (!(bin_arg & 256)) cand_acc += D - Dn;  // (statistics: the distinct candidates, unless the scored ones are asked for)
+        if (!(bin_arg & (256 | 1024))) cand_acc += D - Dn;  // (statistics: the distinct candidates, unless the scored ones -- or the directly ranked rows -- are asked for)
         D = Dn;
       } else {
       unsigned long long* kk0 = reinterpret_cast<unsigned long long*>(tab + ((D + 1u) & ~1u));
@@ -1036,7 +1058,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
         goto mp_again;
       }
     }
-    cand_acc += D;
+    if (DL == 0u || !(bin_arg & 1024)) cand_acc += D;
     unsigned long long* kk = reinterpret_cast<unsigned long long*>(tab + ((D + 1u) & ~1u));
     // ---- 4. score candidates tl, tl + T, ... (dense); keys go to LDS behind the packed counts
     unsigned n_valid = 0;
@@ -1103,6 +1125,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
         s_kbits[2 * (tw / WAVE) + 1] = kor;
       }
     }
+    if (DL != 0u && T != WAVE && tl == 0) sel_res[1] = 0u;  // the length of a directly ranked row's set: published, like s_kbits, by the barriers inside the scan
     unsigned C;
     team_exclusive_scan<T>(n_valid, s_wsum, &C);
     C = uni(C);
@@ -1129,6 +1152,14 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
         unsigned need = (unsigned)a.k;
         if (a.col_bytes < 4) thr_ncol = 0xffffffffu << (8 * a.col_bytes);  // digits of ~col above the highest used byte are all ones
         int p0 = 0;  // first key byte that differs between candidates
+        // THE DIRECT RANKING.  Behind the prefilter a typical row keeps only slightly more than k valid candidates: the >= k with k11 = 1 at or below the
+        // cut count, the few with k11 >= 2, the few beyond the monotone limit.  When all C of them fit the ambiguous-set arrays the select decides nothing
+        // the final ranking does not decide anyway: the row enters the select's `merged` finish below at once, with "every valid candidate" as the set --
+        // the same ranking by the same 96-bit composite (key desc, column asc), ranks < k are the row --, and skips the shared-byte sweep, the zeroing of
+        // the histograms, every pass and every digit search.  (C > k, a class that carries the prefilter, ordered rows; bit 9 of the bin argument switches
+        // it off: the A/B and the tests' bit-for-bit comparison.)
+        const bool direct = DL != 0u && C <= DL && !a.unordered && !(bin_arg & 512);  // team-uniform
+        if (!direct) {
         if (!SKIP_SHARED) {
           // The classes that do not track the shared key bytes while they score (registers) find them here, with one cheap sweep over
           // the keys (an AND and an OR per key, no histogram, no atomics): the LLRs of a row share their sign / exponent byte, so the
@@ -1171,6 +1202,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
         }
         if (tl == 0) { sel_res[0] = 0u; sel_res[1] = 0u; }  // list length, ambiguous-set length
         team_sync<T>();
+        }
         const int first_col_pass = 8 + (3 - (a.col_bytes - 1));  // column digits above the highest used byte are constant: skip
         bool have_list = false;
         unsigned list_n = 0, prev_cnt = C;
@@ -1181,10 +1213,11 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
         int q = 0;
         for (int p = p0; p < 12; ++p) {  // team-uniform trip count (the breaks below are on values every thread agrees on)
           if (p >= 8 && p < first_col_pass) continue;
+          const int shk = p < 8 ? 56 - 8 * p : 0, shc = p < 8 ? 0 : 24 - 8 * (p - 8);
+          if (!direct) {  // (a directly ranked row runs no pass: it goes straight to the finish)
           unsigned* H = hist + (q % NH) * 128;
           const bool build = SEL_CAP > 0 && !have_list && !first_pass && prev_cnt <= (unsigned)SEL_CAP;  // this sweep also records the survivors
           const unsigned n_scan = have_list ? list_n : D;
-          const int shk = p < 8 ? 56 - 8 * p : 0, shc = p < 8 ? 0 : 24 - 8 * (p - 8);
           unsigned lst_n = 0u;  // (unused: only teams of several waves build a list)
           for (unsigned base = 0; base < n_scan; base += T) {  // scalar loop control, no divergent exits (claim_positions is a wave operation)
             const unsigned idx = base + (unsigned)tl;
@@ -1260,7 +1293,8 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
             if (NH == 1) team_sync<T>();  // the histogram just cleared is the next pass's target
             ++q;
           }
-          if (prev_cnt <= (unsigned)SEL_AMB) {  // team-uniform
+          }
+          if (direct || prev_cnt <= (unsigned)SEL_AMB) {  // team-uniform
             // finish: copy out the members of the cut bin (they match the prefix through digit p) ...
             // In the SHARE layout amb_key / amb_col OVERLAY the three rotating histograms.  Every wave has run the digit search above for
             // itself, at its own pace: a wave that arrives here first must not write the ambiguous set over histogram words a sibling has
@@ -1269,12 +1303,18 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
             // entries lost at the cut in ~1 build of 50 on config 4, now and then a garbage column and a wild store (the GPU memory
             // fault of profiles/r03_rocprofv3_stats_failure.txt; found by tools/race_hunt.py, profiles/r04_race_hunt.log).  prev_cnt is
             // team-uniform, so every wave takes the barrier.
-            if (SHARE && T != WAVE) team_sync<T>();
+            // A DIRECTLY RANKED row has touched no select histogram and needs no barrier here.  What its set overlays in the SHARE classes is the expand
+            // loop's ustart | uoff -- last read before the team barrier that ends the loop's last chunk -- and the prefilter's count histogram, which every
+            // wave reads for itself in the compaction's cut search: those reads are ordered before the first write of the set by the team barrier that
+            // CLOSES THE COMPACTION ("3.": the team_sync behind the moves of the packed words, ahead of the multi-pass test and the score phase), and again
+            // by the two barriers of the scan of n_valid and the one behind it.  The set's length word was zeroed ahead of that scan.  (One wave: its LDS
+            // accesses execute in program order.)
+            if (SHARE && T != WAVE && !direct) team_sync<T>();
             // Round 5: when the cut bin AND everything above it (k - need composites) fit the set, they are copied out together and ranked ONCE --
             // the best k of that ranking ARE the row, in output order.  (Before: the bin's members ranked among themselves for the exact threshold,
             // a sweep for the survivors, the survivors ranked again: two sweeps and two rankings, at four vector instructions per compared element,
             // in classes that are bound by vector issue.)  The sweep then covers every candidate: what lies above the bin is not in the index list.
-            const bool merged = !MP && !a.unordered && !(dbg & DBG_NO_RANK) && ((unsigned)a.k - need) + prev_cnt <= (unsigned)SEL_M;  // team-uniform
+            const bool merged = direct || (!MP && !a.unordered && !(dbg & DBG_NO_RANK) && ((unsigned)a.k - need) + prev_cnt <= (unsigned)SEL_M);  // team-uniform
             const unsigned n_scan2 = (have_list && !merged) ? list_n : D;
             unsigned amb_n = 0u;  // (one-wave teams: the length of the set)
             for (unsigned base = 0; base < n_scan2; base += T) {  // scalar loop control, no divergent exits: claim_positions is a wave operation
@@ -1286,7 +1326,8 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
                 const unsigned t = (have_list && !merged) ? (unsigned)lst[idx] : idx;
                 key = kk[t];
                 col = (unsigned)((int)(tab[t] >> cb) - 1);
-                if (merged) match = key != 0ull && (p < 8 ? (key >> shk) >= (thr_key >> shk) : (key > thr_key || (key == thr_key && (~col >> shc) >= (thr_ncol >> shc))));
+                if (direct) match = key != 0ull;  // every valid candidate: m = C
+                else if (merged) match = key != 0ull && (p < 8 ? (key >> shk) >= (thr_key >> shk) : (key > thr_key || (key == thr_key && (~col >> shc) >= (thr_ncol >> shc))));
                 else match = key != 0ull && (p < 8 ? (key >> shk) == (thr_key >> shk) : (key == thr_key && (~col >> shc) == (thr_ncol >> shc)));
               }
               const unsigned pos = claim_positions<T>(match, &sel_res[1], amb_n);
@@ -1322,6 +1363,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
               int kout = a.k;
               URCCO_OPAQUE(kout);  // (likewise: the hoisted vector copy of k was spilled, and reloaded behind the row's stores)
               if (tl == 0) a.out_count[i - a.item_lo] = kout;
+              if (direct && (bin_arg & 1024)) cand_acc += 1ull;  // (statistics: the rows ranked directly, when those are asked for)
               row_done = true;
               break;
             }
@@ -2031,7 +2073,7 @@ static int blocks_per_cu(int bin) {
   return cache[bin].load(std::memory_order_relaxed);
 }
 
-hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, int bin, int32_t n_rows) {
+hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args_in, int bin, int32_t n_rows) {
   // Persistent grids sized to the chip; each kernel reads its own row list length from bin_off on the device,
   // so no host synchronisation sits between binning and the SpGEMM.
   // Several times as many blocks as fit the chip: the later ones start as blocks of the first wave retire, which evens out the
@@ -2056,19 +2098,28 @@ hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, in
     if (blocks > cap) blocks = cap;
     return dim3((unsigned)blocks);
   };
-  const bool dbgk = (args.debug & DBG_ROW_KERNELS) != 0;  // the ablation / test switches live in the DBG instantiations only
-  const int scored = (args.debug & DBG_COUNT_SCORED) ? 256 : 0;  // rides on the kernels' bin argument (grid-uniform; the production instantiations do not read CcoArgs::debug)
+  const bool dbgk = (args_in.debug & DBG_ROW_KERNELS) != 0;  // the ablation / test switches live in the DBG instantiations only
+  // DBG_COUNT_DIRECT: the statistics word counts the rows the packed kernels ranked directly -- every kernel that has no direct ranking (the plain and DBG
+  // forms, the micro and multi-pass classes, a class it is compiled out of) runs without the word, so that no candidate count is mixed in
+  constexpr unsigned dl_of_bin[NBINS] = {0u, direct_limit(64, E0), direct_limit(256, E1S), direct_limit(256, E1), direct_limit(512, E2S), direct_limit(1024, E2), 0u};
+  const bool count_direct = (args_in.debug & DBG_COUNT_DIRECT) != 0;
+  CcoArgs args = args_in;
+  if (count_direct && dl_of_bin[bin] == 0u) args.cand = nullptr;
+  // ride on the kernels' bin argument (grid-uniform; the production instantiations do not read CcoArgs::debug)
+  const int scored = ((args.debug & DBG_COUNT_SCORED) ? 256 : 0) | ((args.debug & DBG_NO_DIRECT_RANK) ? 512 : 0) | (count_direct ? 1024 : 0);
   // A B' with counts aboard: BOTH instantiations are enqueued -- whether the counts fit is a device-side fact, the one whose turn it is not returns at
   // once.  The DBG instantiations exist for the plain form only (the ablation switches price the count gather among other things).
   CcoArgs plain = args;
   plain.b_packed = nullptr;
+  CcoArgs wide = args;  // the plain instantiation's turn when the tables are wide
+  if (count_direct) { plain.cand = nullptr; wide.cand = nullptr; }
   const bool both = args.b_packed != nullptr && !dbgk && !args.pk_known;  // (pk_known: the host knows the verdict -- packed and narrow -- only that instantiation)
 #define URCCO_LAUNCH_ROWS(TT, EE, UU, MPF, GRID, BLK, BINARG)                                                                      \
   do {                                                                                                                           \
     if (dbgk) hipLaunchKernelGGL((cco_rows_kernel<TT, EE, UU, MPF, true, false>), GRID, dim3(BLK), 0, st, plain, BINARG);          \
     else {                                                                                                                       \
       if (both || args.pk_known) hipLaunchKernelGGL((cco_rows_kernel<TT, EE, UU, MPF, false, true>), GRID, dim3(BLK), 0, st, args, BINARG | scored); \
-      if (!args.pk_known) hipLaunchKernelGGL((cco_rows_kernel<TT, EE, UU, MPF, false, false>), GRID, dim3(BLK), 0, st, args, BINARG); \
+      if (!args.pk_known) hipLaunchKernelGGL((cco_rows_kernel<TT, EE, UU, MPF, false, false>), GRID, dim3(BLK), 0, st, wide, BINARG); \
     }                                                                                                                            \
   } while (0)
 #define URCCO_LAUNCH_MICRO(LL, GRID)                                                                                  \
