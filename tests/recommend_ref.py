@@ -103,6 +103,32 @@ def make_problem(seed, n_items, n_queries, cols, boosts, k, hist_hi, hub_cols=()
     return p
 
 
+TIE_BOOST = 1.05
+
+
+def make_tie_problem(seed, n_items, n_listed, starts) -> Problem:
+    """Ties at the cut: one clause with one column (boost TIE_BOOST) that the first n_listed items of a random fill_order list and every query holds;
+    query q excludes the items at fill positions 0 .. starts[q] - 1 (in shuffled order); the mask is all ones.  Every candidate scores exactly TIE_BOOST,
+    so the whole cut is decided in the position digits of the selection key: with fill_order the rows are tie_rows(p, starts, num)."""
+    rng = np.random.default_rng(seed)
+    fill = rng.permutation(n_items).astype(np.int32)
+    listed = np.zeros(n_items, bool)
+    listed[fill[:n_listed]] = True
+    irp = np.zeros(n_items + 1, np.int64)
+    np.cumsum(listed, out=irp[1:])
+    nq = len(starts)
+    cl = Clause(1, TIE_BOOST, irp, np.zeros(n_listed, np.int32), np.arange(nq + 1, dtype=np.int64), np.zeros(nq, np.int32))
+    excl_rp, excl_ci = _rows_to_csr([rng.permutation(fill[:s]) for s in starts])
+    p = Problem(n_items, nq, [cl], excl_rp, excl_ci, np.ones(n_items, np.uint8), fill)
+    dense_matches(p)
+    return p
+
+
+def tie_rows(p: Problem, starts, num):
+    """What brute_force must give for a make_tie_problem with fill_order on (starts[q] + num <= n_listed): (idx [nq, num], score [nq, num])."""
+    return np.stack([p.fill_order[s:s + num] for s in starts]), np.full((len(starts), num), TIE_BOOST)
+
+
 def dense_matches(p: Problem):
     """m_c(q, i) = |T_c(q) ^ I_c(i)| for every clause: the integer product of the 0/1 matrices (kept sparse until the product is formed)."""
     p.m = []
@@ -218,3 +244,13 @@ def check(dp: DeviceProblem, num, use_excl=True, use_mask=True, use_fill=True, n
     assert (int(stats[0]), int(stats[1])) == (n_lds, dp.n_queries - n_lds), f"class split {stats[:2]} vs {(n_lds, dp.n_queries - n_lds)}"
     assert int(stats[3]) == r_cand and not stats[4:].any()
     return stats
+
+
+def check_ties(dp: DeviceProblem, starts, split, lds_limit=_lib.REC_LDS_LIMIT):
+    """A make_tie_problem through check for num = 1, 20, 256 with fill_order; the restatement's rows are tie_rows; split = (LDS, global) queries."""
+    for num in (1, 20, 256):
+        stats = check(dp, num, lds_limit=lds_limit)
+        assert (int(stats[0]), int(stats[1])) == split, stats
+        r_count, r_idx, r_score, _ = brute_force(dp.p, num, True, True, True, False)
+        idx, score = tie_rows(dp.p, starts, num)
+        assert (r_count == num).all() and np.array_equal(r_idx, idx) and np.array_equal(r_score, score)

@@ -51,6 +51,28 @@ def test_wide_catalogue_and_hub_columns(gpu_session):
     R.check(dp, 20, no_backfill=True)
 
 
+def test_ties_at_the_cut_global_class(gpu_session):
+    """Every candidate scores 1.05: the cut lies in the position digits alone.  70 000 items, all listed; the winners' positions start at 0, 250 and
+    65 530 and straddle the 2^8 and 2^16 boundaries, so the threshold's digits carry across bytes.  w = 70 000, 70 250, 135 530."""
+    starts = (0, 250, 65_530)
+    p = R.make_tie_problem(24, 70_000, 70_000, starts)
+    assert R.work_bound(p, True).tolist() == [70_000, 70_250, 135_530]
+    R.check_ties(R.DeviceProblem(gpu_session, p), starts, split=(0, 3))
+
+
+def test_ties_at_the_cut_lds_class(gpu_session):
+    """3 000 items, 2 800 listed: w = 2 800 and 3 050 <= REC_LDS_LIMIT, at most 3 050 of the 4 096 table slots in use.  Once more without fill_order:
+    position = item id."""
+    starts = (0, 250)
+    p = R.make_tie_problem(25, 3000, 2800, starts)
+    assert R.work_bound(p, True).tolist() == [2800, 3050] and _lib.REC_LDS_LIMIT == 3072
+    dp = R.DeviceProblem(gpu_session, p)
+    R.check_ties(dp, starts, split=(2, 0))
+    for num in (1, 20, 256):
+        stats = R.check(dp, num, use_fill=False)
+        assert (int(stats[0]), int(stats[1])) == (2, 0)
+
+
 def test_reversed_fill_order_half_masked_long_exclusions(gpu_session):
     p = R.make_problem(23, 3000, 500, cols=(3000, 5000, 40), boosts=(1.05, 20.0, 0.3), k=20, hist_hi=40, excl_hi=500, mask_frac=0.5, reverse_fill=True)
     assert np.diff(p.excl_rp).max() >= 400 and 0.4 < p.mask.mean() < 0.6 and p.fill_order[0] == 2999

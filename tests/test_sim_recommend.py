@@ -74,6 +74,40 @@ def test_largest_num_and_more_than_the_catalogue(dev, low_limit):
     R.check(dev, 256, use_excl=False, use_mask=False, use_fill=False, lds_limit=low_limit)
 
 
+TIE_STARTS = (0, 250)
+
+
+@pytest.fixture(scope="module")
+def tie_dev(sim_session):
+    # every candidate scores 1.05: the cut lies in the position digits alone.  3 000 items, 2 800 listed: w = 2 800 and 3 050
+    p = R.make_tie_problem(25, 3000, 2800, TIE_STARTS)
+    assert R.work_bound(p, True).tolist() == [2800, 3050]
+    return R.DeviceProblem(sim_session, p)
+
+
+def test_ties_at_the_cut_lds_class(tie_dev):
+    """Under the production limit both queries fit the LDS table (at most 3 050 of its 4 096 slots); once more without fill_order: position = item id."""
+    R.check_ties(tie_dev, TIE_STARTS, split=(2, 0))
+    stats = R.check(tie_dev, 20, use_fill=False)
+    assert (int(stats[0]), int(stats[1])) == (2, 0)
+
+
+def test_ties_at_the_cut_global_class(tie_dev, low_limit):
+    """The same queries under the lowered limit: the global class."""
+    R.check_ties(tie_dev, TIE_STARTS, split=(0, 2), lds_limit=low_limit)
+    stats = R.check(tie_dev, 20, use_fill=False, lds_limit=low_limit)
+    assert (int(stats[0]), int(stats[1])) == (0, 2)
+
+
+def test_ties_at_the_cut_wide_catalogue(sim_session):
+    """70 000 items, all listed (the global class under the production limit): the winners' positions start at 0, 250 and 65 530 and straddle the 2^8 and
+    2^16 boundaries, so the threshold's digits carry across bytes."""
+    starts = (0, 250, 65_530)
+    p = R.make_tie_problem(24, 70_000, 70_000, starts)
+    assert R.work_bound(p, True).tolist() == [70_000, 70_250, 135_530]
+    R.check_ties(R.DeviceProblem(sim_session, p), starts, split=(0, 3))
+
+
 def test_bad_arguments(dev):
     s = dev.sess
     ok = dev.clauses

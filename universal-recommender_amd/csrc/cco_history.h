@@ -1,5 +1,5 @@
 // Device-resident user history (decision D17 of DESIGN.md 7a; include/urcco.h urcco_dev_history_*): the event-store half of a
-// batch of queries.  Compiled into ingest_kernels.hip behind cco_sorted_rows.h (it uses that header's tails and host helpers, and the file's grid helper).
+// batch of queries.  Compiled into ingest_kernels.hip behind cco_sorted_rows.h and cco_select.h (it uses their tails, host helpers and select, and the file's grid helper).
 //
 // What the reference reads from the event store per query (getBiasedRecentUserActions, URAlgorithm.scala:795-839: the most recent
 // maxItemsPerUser events per event type, then distinct; getExcludedItems, :741-767: every item of the blacklist events) is here
@@ -14,8 +14,8 @@
 //   <= 4096   one block: keys in LDS, select with an LDS histogram per discriminating digit, window columns sorted in LDS
 //   larger    the same block code with the keys re-read from global memory per discriminating digit; the window is staged in its
 //             raw row (<= max_items entries) and sorted in LDS up to 4096 entries, in global memory beyond
-// A digit in which all keys of the user agree (the high bytes of millisecond times, every time byte without times) costs no pass:
-// one pass ORs key ^ key[0] over the events first.  Keys are unique (the position is part of them), so the order is total and the
+// The select is the unit of cco_select.h.  A digit in which all keys of the user agree (the high bytes of millisecond times, every time byte
+// without times) costs no pass: sel_differ ORs key ^ key[0] over the events first.  Keys are unique (the position is part of them), so the order is total and the
 // rows do not depend on the order the index scatter left.  Wave = 64 lanes; wave primitives under wave-uniform control flow only.
 namespace urcco {
 
@@ -187,13 +187,45 @@ __global__ __launch_bounds__(256) void hs_rows_wave_kernel(HistArgs a) {
   }
 }
 
+// The window of one (query, type) of n events -> its raw row, slots by the LDS counter *s_cnt (the sort that follows makes the order irrelevant).  Called by
+// the whole block behind the barrier that makes the LDS keys visible.  IN_LDS: the keys are s_time[i], s_pos[i]; else they are read through ipos from
+// global memory.  A template parameter and not a branch inside the accessors: the compiler merges the two loads of such a branch into one load through
+// a pointer chosen at run time, a flat load (cco_sorted_rows.h, sr_unique).
+template <bool IN_LDS>
+__device__ __forceinline__ void hs_window(const HistEvent& e, int n, const int32_t* __restrict__ ipos, const unsigned long long* s_time, const unsigned* s_pos,
+                                          SelScratch& s_select, int* s_cnt, int32_t* __restrict__ row, int room) {
+  const int64_t* __restrict__ times = e.times_ms;
+  auto key_p = [&](unsigned i) -> unsigned { return IN_LDS ? s_pos[i] : (unsigned)ipos[i]; };
+  auto key_t = [&](unsigned i) -> unsigned long long {
+    if (IN_LDS) return s_time[i];
+    return times ? (unsigned long long)times[(unsigned)ipos[i]] ^ HS_SIGN : 0ull;
+  };
+  const int K = e.max_items;
+  const bool all = n <= K;  // block-uniform: no select
+  SelKey thr{0ull, 0u};
+  if (!all) {  // the K-th largest key; digits in which all keys of the user agree take no pass
+    SelKey common;
+    const SelKey differ = sel_differ<256>((unsigned)n, key_t, key_p, s_select, common);
+    thr = sel_kth_largest<256>((unsigned)n, (unsigned)K, key_t, key_p, differ, common, s_select);
+  }
+  for (int i = threadIdx.x; i < n; i += 256) {
+    const unsigned long long kt = key_t((unsigned)i);
+    const unsigned kp = key_p((unsigned)i);
+    if (all || kt > thr.hi || (kt == thr.hi && kp >= thr.lo)) {
+      const int item = e.items[kp];
+      if (item >= 0 && item < e.n_cols) {
+        const int slot = atomicAdd(s_cnt, 1);
+        if (slot < room) row[slot] = item;
+      }
+    }
+  }
+}
+
 // One block per job of big_list.
 __global__ __launch_bounds__(256) void hs_rows_block_kernel(HistArgs a) {
   // keys of the LDS class: SR_LDS times (8 bytes), then SR_LDS positions; once the window is staged in its raw row the front is the sort buffer
   __shared__ unsigned long long s_buf[SR_LDS + SR_LDS / 2];
-  __shared__ int s_hist[256];
-  __shared__ unsigned s_diff[3];
-  __shared__ int s_sel[2];
+  __shared__ SelScratch s_select;
   __shared__ int s_cnt;
   unsigned long long* s_time = s_buf;
   unsigned* s_pos = reinterpret_cast<unsigned*>(s_buf + SR_LDS);
@@ -203,7 +235,7 @@ __global__ __launch_bounds__(256) void hs_rows_block_kernel(HistArgs a) {
     const int64_t j = a.big_list[li];
     const int t = (int)(j / a.n_queries);
     const int64_t q = j - (int64_t)t * a.n_queries;
-    if (threadIdx.x == 0) { s_cnt = 0; s_diff[0] = 0; s_diff[1] = 0; s_diff[2] = 0; }
+    if (threadIdx.x == 0) s_cnt = 0;
     int32_t* row;
     int room;
     if (t < a.n_types) {
@@ -212,7 +244,6 @@ __global__ __launch_bounds__(256) void hs_rows_block_kernel(HistArgs a) {
       const int n = hs_user_events(e, a.q_users, a.n_users, q, seg);
       row = e.raw.tmp + e.raw.raw_ptr[q];
       room = (int)(e.raw.raw_ptr[q + 1] - e.raw.raw_ptr[q]);
-      const int K = e.max_items;
       const bool in_lds = n <= SR_LDS;
       const int32_t* __restrict__ ipos = e.idx_pos + seg;
       const int64_t* __restrict__ times = e.times_ms;
@@ -223,90 +254,12 @@ __global__ __launch_bounds__(256) void hs_rows_block_kernel(HistArgs a) {
           s_time[i] = times ? (unsigned long long)times[p] ^ HS_SIGN : 0ull;
         }
       __syncthreads();
-      auto key = [&](int i, unsigned long long& kt, unsigned& kp) {
-        if (in_lds) { kt = s_time[i]; kp = s_pos[i]; }
-        else { kp = (unsigned)ipos[i]; kt = times ? (unsigned long long)times[kp] ^ HS_SIGN : 0ull; }
-      };
-      unsigned long long thr_t = 0;
-      unsigned thr_p = 0;
-      const bool all = n <= K;  // block-uniform: no select
       if (threadIdx.x == 0) {
         atomicAdd(&a.ctr[1 + (in_lds ? HIST_STAT_BLOCK : HIST_STAT_GLOBAL)], 1ull);
-        if (!all) atomicAdd(&a.ctr[1 + HIST_STAT_SELECT], 1ull);
+        if (n > e.max_items) atomicAdd(&a.ctr[1 + HIST_STAT_SELECT], 1ull);
       }
-      if (!all) {
-        // the K-th largest key: digits in which the user's keys differ, most significant first
-        unsigned long long t0;
-        unsigned p0;
-        key(0, t0, p0);
-        unsigned long long dt = 0;
-        unsigned dp = 0;
-        for (int i = threadIdx.x; i < n; i += 256) {
-          unsigned long long kt;
-          unsigned kp;
-          key(i, kt, kp);
-          dt |= kt ^ t0;
-          dp |= kp ^ p0;
-        }
-        if ((unsigned)dt) atomicOr(&s_diff[0], (unsigned)dt);
-        if ((unsigned)(dt >> 32)) atomicOr(&s_diff[1], (unsigned)(dt >> 32));
-        if (dp) atomicOr(&s_diff[2], dp);
-        __syncthreads();
-        dt = (unsigned long long)s_diff[0] | ((unsigned long long)s_diff[1] << 32);
-        dp = s_diff[2];
-        unsigned long long pre_t = 0, mask_t = 0;
-        unsigned pre_p = 0, mask_p = 0;
-        int remaining = K;
-        for (int d = 0; d < 12; ++d) {
-          const bool is_time = d < 8;
-          const int sh = is_time ? 56 - 8 * d : 24 - 8 * (d - 8);
-          const unsigned differ = is_time ? (unsigned)(dt >> sh) & 255u : (dp >> sh) & 255u;
-          int b;
-          if (!differ) {  // block-uniform: every key carries key[0]'s digit
-            b = is_time ? (int)((t0 >> sh) & 255u) : (int)((p0 >> sh) & 255u);
-          } else {
-            s_hist[threadIdx.x] = 0;
-            __syncthreads();
-            for (int i = threadIdx.x; i < n; i += 256) {
-              unsigned long long kt;
-              unsigned kp;
-              key(i, kt, kp);
-              if ((kt & mask_t) == pre_t && (kp & mask_p) == pre_p) atomicAdd(&s_hist[is_time ? (int)((kt >> sh) & 255u) : (int)((kp >> sh) & 255u)], 1);
-            }
-            __syncthreads();
-            if (threadIdx.x == 0) {
-              int cum = 0, bb = 255;
-              for (; bb > 0; --bb) {
-                const int c = s_hist[bb];
-                if (cum + c >= remaining) break;
-                cum += c;
-              }
-              s_sel[0] = bb;
-              s_sel[1] = remaining - cum;
-            }
-            __syncthreads();
-            b = s_sel[0];
-            remaining = s_sel[1];
-          }
-          if (is_time) { pre_t |= (unsigned long long)b << sh; mask_t |= 255ull << sh; }
-          else { pre_p |= (unsigned)b << sh; mask_p |= 255u << sh; }
-        }
-        thr_t = pre_t;
-        thr_p = pre_p;
-      }
-      // the window's columns -> the raw row (slots by an LDS counter: the sort below makes the order irrelevant)
-      for (int i = threadIdx.x; i < n; i += 256) {
-        unsigned long long kt;
-        unsigned kp;
-        key(i, kt, kp);
-        if (all || kt > thr_t || (kt == thr_t && kp >= thr_p)) {
-          const int item = e.items[kp];
-          if (item >= 0 && item < e.n_cols) {
-            const int slot = atomicAdd(&s_cnt, 1);
-            if (slot < room) row[slot] = item;
-          }
-        }
-      }
+      if (in_lds) hs_window<true>(e, n, ipos, s_time, s_pos, s_select, &s_cnt, row, room);
+      else hs_window<false>(e, n, ipos, s_time, s_pos, s_select, &s_cnt, row, room);
     } else {
       row = a.excl.tmp + a.excl.raw_ptr[q];
       const int64_t room64 = a.excl.raw_ptr[q + 1] - a.excl.raw_ptr[q];

@@ -9,6 +9,7 @@
 
 #include "cco_common.h"
 #include "cco_device.h"
+#include "cco_select.h"
 #include "cco_recommend.h"
 #include "cco_eval.h"
 

@@ -1,7 +1,7 @@
 // cco_recommend.h -- batch recommendations from a built CCO model (urcco_dev_recommend): per query row the top `num` of
 //   score(q, i) = sum over should-clauses c, in call order, of boost_c * | T_c(q) ^ I_c(i) |
 // over the eligible items, in the total order (score desc, backfill position asc), zero-score items as backfill (decision D15).
-// Included once, from cco_misc.hip (the CPU suite compiles a fixed list of translation units).
+// Included once, from cco_misc.hip behind cco_select.h (the CPU suite compiles a fixed list of translation units).
 //
 //   rec_inverse_kernel   pos[fill_order[p]] = p: the backfill position of every item
 //   rec_work_kernel      w(q) = sum_c sum_{h in T_c(q)} len(column h of I_c) + exclusions of q: the upper bound of the distinct items the query
@@ -12,8 +12,8 @@
 //                          when an absent item is claimed (a rejected item becomes a tombstone) and per walked backfill position; R = false is the rule-free call
 // Both classes: exclusions enter first as tombstones, masked-out items become tombstones when they are first hit; clause by clause the hits raise a 32-bit
 // match counter per slot (the claiming lane appends the slot to the candidate list), then `score += boost * m; m = 0` is folded over the list -- the f64 sum
-// has the order of the clauses whatever the order of the hits.  Selection: an 8-bit radix select over the 96-bit key (score bits, ~position) finds the
-// num-th best candidate, the (at most num) winners are ranked by counting; then the backfill walks fill_order from the front.
+// has the order of the clauses whatever the order of the hits.  Selection: the radix select of cco_select.h over the 96-bit key (score bits, ~position) finds
+// the num-th best candidate, the (at most num) winners are ranked by counting; then the backfill walks fill_order from the front.
 #pragma once
 
 namespace urcco {
@@ -160,8 +160,7 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
   __shared__ unsigned s_m[DENSE ? 1 : REC_CAP];
   __shared__ unsigned short s_cand[DENSE ? 1 : REC_LIMIT];  // slot of every candidate
   __shared__ double s_score[DENSE ? 1 : REC_LIMIT];         // by candidate ordinal
-  __shared__ unsigned s_hist[256];
-  __shared__ unsigned s_sel[3];                              // digit chosen, winners still to take below it, size of its bucket
+  __shared__ SelScratch s_select;
   __shared__ unsigned s_ncand, s_ntomb, s_nwin;
   __shared__ unsigned s_wcnt[REC_NW];
   __shared__ double s_wscore[REC_MAX_NUM];
@@ -279,53 +278,13 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
     auto item_pos = [&](int32_t item) -> int32_t { return pos_of ? pos_of[item] : item; };
 
     // ---- selection: threshold key (thi, tlo) = the num-th largest of (score bits, ~position); every candidate when there are no more than num ----
-    unsigned long long thi = 0ull;
-    unsigned tlo = 0u;
-    if (nc > (unsigned)num) {
-      unsigned need = (unsigned)num;
-      for (int d = 0; d < 12; ++d) {
-        s_hist[tid] = 0;
-        __syncthreads();
-        for (unsigned j = tid; j < nc; j += REC_THREADS) {
-          const unsigned long long hi = (unsigned long long)__double_as_longlong(cand_score(j));
-          unsigned digit;
-          if (d < 8) {
-            if (d > 0 && (hi >> (64 - 8 * d)) != (thi >> (64 - 8 * d))) continue;
-            digit = (unsigned)(hi >> (56 - 8 * d)) & 255u;
-          } else {
-            if (hi != thi) continue;
-            const unsigned lo = ~(unsigned)item_pos(cand_item(j));
-            if (d > 8 && (lo >> (32 - 8 * (d - 8))) != (tlo >> (32 - 8 * (d - 8)))) continue;
-            digit = (lo >> (24 - 8 * (d - 8))) & 255u;
-          }
-          atomicAdd(&s_hist[digit], 1u);
-        }
-        __syncthreads();
-        if (tid < WAVE) {  // wave 0: lane l owns digits 4 l .. 4 l + 3; `above` = candidates of the larger digits
-          unsigned h4[4], sum = 0;
-#pragma unroll
-          for (int x = 0; x < 4; ++x) { h4[x] = s_hist[4 * lane + x]; sum += h4[x]; }
-          unsigned v = sum;
-          for (int o = 1; o < WAVE; o <<= 1) {
-            const unsigned t = __shfl_down(v, (unsigned)o);
-            if (lane + o < WAVE) v += t;
-          }
-          unsigned above = v - sum;
-#pragma unroll
-          for (int x = 3; x >= 0; --x) {
-            if (above < need && need <= above + h4[x]) { s_sel[0] = (unsigned)(4 * lane + x); s_sel[1] = need - above; s_sel[2] = h4[x]; }
-            above += h4[x];
-          }
-        }
-        __syncthreads();
-        const unsigned digit = s_sel[0];
-        need = s_sel[1];
-        const bool whole = need == s_sel[2];  // the whole bucket wins: every lower digit of the threshold is 0
-        if (d < 8) thi |= (unsigned long long)digit << (56 - 8 * d);
-        else tlo |= digit << (24 - 8 * (d - 8));
-        if (whole) break;
-      }
-    }
+    SelKey thr{0ull, 0u};
+    if (nc > (unsigned)num)  // (differ = all ones: whether sel_differ's pass would pay here has not been measured)
+      thr = sel_kth_largest<REC_THREADS>(
+          nc, (unsigned)num, [&](unsigned j) { return (unsigned long long)__double_as_longlong(cand_score(j)); },
+          [&](unsigned j) { return ~(unsigned)item_pos(cand_item(j)); }, SelKey{~0ull, ~0u}, SelKey{0ull, 0u}, s_select);
+    const unsigned long long thi = thr.hi;
+    const unsigned tlo = thr.lo;
     // ---- winners (at most num: the keys are distinct), ranked by counting ----
     for (unsigned j = tid; j < nc; j += REC_THREADS) {
       const double sc = cand_score(j);
