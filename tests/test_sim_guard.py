@@ -16,6 +16,14 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
+# The fast cases of tests/test_sim_large_k.py (0.1 to 0.8 s each; the ones that run a thousand argmax sweeps are left out): tables filled up to their last
+# words at k = 169 .. 5460, the survivor arrays of the dense global kernel full at k = 1024, outputs of rows far longer than a wave.
+_LK = "tests/test_sim_large_k.py::"
+LARGE_K_FAST = [_LK + t for t in ("test_capacity_edges", "test_rows_between_the_edges", "test_rows_with_fewer_candidates_than_a_huge_k",
+                                  "test_dense_global_kernel_around_gsel_k[1024]", "test_k_beyond_every_table_and_every_row", "test_context_level[600-ordered]",
+                                  "test_context_level[600-unordered]", "test_context_level[1024-ordered]", "test_context_level[1024-unordered]")]
+
+
 def run_guarded(mode: str, files, **extra):
     env = dict(os.environ, HIPSIM_GUARD=mode, **extra)
     r = subprocess.run([sys.executable, "-m", "pytest", "-x", "-q", "-p", "no:cacheprovider", *files], cwd=ROOT, env=env, capture_output=True, text=True)
@@ -46,7 +54,7 @@ def test_guard_pages_catch_an_overrun(sim_lib):
 
 
 def test_kernels_and_context_under_guard_pages_aligned(sim_lib):
-    run_guarded("1", ["tests/test_sim_kernel_logic.py", "tests/test_sim_context.py"])
+    run_guarded("1", ["tests/test_sim_kernel_logic.py", "tests/test_sim_context.py"] + LARGE_K_FAST)
 
 
 def test_kernels_under_guard_pages_exact(sim_lib):
@@ -56,14 +64,14 @@ def test_kernels_under_guard_pages_exact(sim_lib):
 def test_kernels_and_context_with_a_guard_page_before_every_buffer(sim_lib):
     """HIPSIM_GUARD=3: buffers START at a page boundary behind a PROT_NONE page -- buffer[-1], prefix[t - 1] at t = 0, a sentinel -1 used
     as an index (the one fault address recorded on hardware was the last page below a 2 MiB boundary)."""
-    run_guarded("3", ["tests/test_sim_kernel_logic.py", "tests/test_sim_context.py"])
+    run_guarded("3", ["tests/test_sim_kernel_logic.py", "tests/test_sim_context.py"] + LARGE_K_FAST)
 
 
 def test_kernels_with_the_waves_of_a_block_scheduled_in_reverse(sim_lib):
     """HIPSIM_ORDER=reverse: between two rendezvous the highest wave of a block runs first.  The default ascending order hides a
     missing __syncthreads() whenever the producing wave has the lower index -- which is also how hardware mostly happens to
     schedule, i.e. the kind of bug that survives ordinary runs and strikes once in a while."""
-    run_guarded("1", ["tests/test_sim_kernel_logic.py", "tests/test_sim_properties.py"], HIPSIM_ORDER="reverse")
+    run_guarded("1", ["tests/test_sim_kernel_logic.py", "tests/test_sim_properties.py"] + LARGE_K_FAST, HIPSIM_ORDER="reverse")
 
 
 def test_kernels_with_lds_array_bounds_checked(sim_lib):

@@ -635,9 +635,9 @@ def test_row_scan_threshold_table_forms(sim_session):
 
 
 def test_global_class_ties_at_the_cut(sim_session):
-    """The global-accumulator class (here reached through the packed-count overflow: 3M columns leave 10 count bits, the
-    item has 1100 users) selects its top k by radix select over candidates in global scratch: 200 candidates with exactly
-    equal LLR, so the cut falls in the column digits (3 column bytes).  Exact ids."""
+    """Bin 6 reached through the packed-count overflow (3M columns leave 10 count bits, the item has 1100 users).  At k <= 256 -- every k
+    here -- bin 6 is the MULTI-PASS class (the dense global-accumulator kernel serves it only from k = 257 on: tests/large_k_cases.py): 200
+    candidates with exactly equal LLR, so the cut falls in the column digits (3 column bytes).  Exact ids."""
     n_users, n_b = 1300, 3_000_000
     a_rows = [np.array([0], np.int64) if u < 1100 else np.array([1], np.int64) for u in range(n_users)]
     cols = 70000 + 3 * np.arange(200)
@@ -649,7 +649,7 @@ def test_global_class_ties_at_the_cut(sim_session):
     a, b = csr(a_rows, 2), csr(b_rows, n_b)
     for k in (7, 50, 150):
         _, _, st = compare_with_oracle(sim_session, [a, b], [P(1000000, k), P(1000000, k)], 3, exact_ids=True)
-        assert st[1][0][7] > 0          # global class used
+        assert st[1][0][7] > 0          # bin 6 used
 
 
 def test_multipass_class_adversarial_low_bits_and_k_limits(sim_session):
