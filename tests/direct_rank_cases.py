@@ -6,11 +6,9 @@ import numpy as np
 
 from helpers import check_indicators, compare_with_oracle, run_device, sort_rows, to_dev, to_params
 from oracle import c_oracle as O
-from prefilter_cases import CLAMP_BIN, NO_PREFILTER, assert_bit_equal, crafted
+from prefilter_cases import CLAMP_BIN, assert_bit_equal, crafted
 from universal_recommender_amd import _lib
 
-NO_DIRECT_RANK = 33554432   # urcco::DBG_NO_DIRECT_RANK
-COUNT_DIRECT = 67108864     # urcco::DBG_COUNT_DIRECT
 N_BIG = 200_000             # users: cA cB << N for every candidate of the crafted rows
 # the accumulator classes that carry the prefilter (bin numbers of cco_kernels.h) -- direct_limit(T, E) of cco_rows.hip, 0 = compiled out of the class --
 # and the capacity of their ambiguous-set arrays (what the edges are taken around where a class has no direct ranking)
@@ -117,7 +115,7 @@ def run_pair(sess, mats, params, seed, run=run_device, bits=0):
     sess.set_debug(bits)
     try:
         on = run(sess, mats, params, seed)
-        sess.set_debug(bits | NO_DIRECT_RANK)
+        sess.set_debug(bits | _lib.DBG_NO_DIRECT_RANK)
         off = run(sess, mats, params, seed)
     finally:
         sess.set_debug(0)
@@ -128,7 +126,7 @@ def direct_rows(sess, mats, params, seed, run=run_device, bits=0):
     """stats[30] of every event type under COUNT_DIRECT: the rows that were ranked directly."""
     sess.set_timing(True)
     try:
-        sess.set_debug(bits | COUNT_DIRECT)
+        sess.set_debug(bits | _lib.DBG_COUNT_DIRECT)
         return [int(o.stats.cpu().numpy()[30]) for o in run(sess, mats, params, seed)]
     finally:
         sess.set_debug(0)
@@ -195,7 +193,7 @@ def counted(sess, mats, rows, k, limit_of, bits=0, params=None, valid_of=None):
     """check(), then COUNT_DIRECT of A'B against the model.  Returns the model's (class, C) per row."""
     params = params or [P(k), P(k)]
     check(sess, mats, params, bits=bits)
-    want, seen = model_direct(rows, k, limit_of, mats[1].n_cols, prefilter=not (bits & NO_PREFILTER), valid_of=valid_of)
+    want, seen = model_direct(rows, k, limit_of, mats[1].n_cols, prefilter=not (bits & _lib.DBG_NO_PREFILTER), valid_of=valid_of)
     got = direct_rows(sess, mats, params, 3, bits=bits)
     print(f"rows ranked directly: {got} (model {want}); (class, C) per row: {seen}")
     assert got[1] == want, (got, want, seen)
@@ -216,12 +214,12 @@ def case_no_prefilter(sess):
     not the micro class) and rows of the 256-thread / 4Ki class with D at and one beyond its limit (k11 = cA = 12: 12 D > 512 pairs)."""
     k = 50
     mats, rows = crafted(np.random.default_rng(3), [k + 1, 64, 65], ca=80, n_users=N_BIG)
-    _, seen = counted(sess, mats, rows, k, limit_fn(sess), bits=NO_PREFILTER)
+    _, seen = counted(sess, mats, rows, k, limit_fn(sess), bits=_lib.DBG_NO_PREFILTER)
     assert seen == [(1, k + 1), (1, 64), (1, 65)], seen
     lim = DIRECT_LIMIT[2] or SEL_M[2]
     rng = np.random.default_rng(4)
     mats, rows = general([lim, lim + 1, k + 1], 12, N_BIG, lambda D: np.full(D, 12), lambda D: rng.integers(12, 200, D))
-    _, seen = counted(sess, mats, rows, k, limit_fn(sess), bits=NO_PREFILTER)
+    _, seen = counted(sess, mats, rows, k, limit_fn(sess), bits=_lib.DBG_NO_PREFILTER)
     assert seen == [(2, lim), (2, lim + 1), (2, k + 1)], seen
 
 
@@ -229,7 +227,7 @@ def case_ties(sess):
     """Every candidate the same count (all LLRs bit-equal: the row is cut by column alone), then two count values whose boundary falls exactly at rank k;
     with the prefilter in front (which keeps a tie at the cut whole, and drops the second value's candidates) and without."""
     k = 50
-    for bits in (0, NO_PREFILTER):
+    for bits in (0, _lib.DBG_NO_PREFILTER):
         for cb_lo, cb_hi in ((7, 7), (3, 9)):
             def cb_of(rng, n, lo=cb_lo, hi=cb_hi):
                 return np.where(np.arange(n) < k, lo, hi)

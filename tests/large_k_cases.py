@@ -10,7 +10,6 @@ import numpy as np
 import test_sim_kernel_logic as logic
 from helpers import check_indicators, compare_with_oracle, run_device, sort_rows, to_dev, to_params
 from oracle import c_oracle as O
-from prefilter_cases import NO_PREFILTER
 from universal_recommender_amd import _lib
 
 TABLE_WORDS = (1024, 4096, 8192, 16384, 32768)   # E of the classes 1 .. 5 (cco_rows.hip: E0, E1S, E1, E2S, E2)
@@ -129,7 +128,7 @@ def case_edge(sess, E, family, which, k=None, repeat=False):
     w, ca = (D, 1) if family == "hashed" else (2 * D, 2)
     want = cls + 1 if which == "above" else cls
     assert class_of(w, ca, mats[1].n_cols, k) == want, (E, family, which, D, k)
-    bits = NO_PREFILTER if which == "edge_no_prefilter" else 0
+    bits = _lib.DBG_NO_PREFILTER if which == "edge_no_prefilter" else 0
     _, ref = checked(sess, mats, k, one_row(want), item_hi=1, exact_ids=True, bits=bits, repeat=repeat)
     n = int(lens_of(ref[1])[0])
     assert n == min(D, k), (n, D, k)             # the oracle's row: every candidate valid, so the row is cut exactly when D > k

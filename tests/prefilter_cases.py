@@ -8,9 +8,8 @@ import numpy as np
 import torch
 
 from oracle import c_oracle as O
+from universal_recommender_amd import _lib
 
-NO_PREFILTER = 8388608     # urcco::DBG_NO_PREFILTER
-COUNT_SCORED = 16777216    # urcco::DBG_COUNT_SCORED
 XLX_TABLE = 4096
 CLAMP_BIN = 255
 
@@ -117,7 +116,7 @@ def run_both(sess, mats, params, seed, run, bits=0):
     """The build with the prefilter and with it switched off: (on, off) outputs.  `run(sess, mats, params, seed)` -> per event type outputs."""
     sess.set_debug(bits)
     on = run(sess, mats, params, seed)
-    sess.set_debug(bits | NO_PREFILTER)
+    sess.set_debug(bits | _lib.DBG_NO_PREFILTER)
     try:
         off = run(sess, mats, params, seed)
     finally:
@@ -140,7 +139,7 @@ def scored_and_distinct(sess, mats, params, seed, run):
     """stats[30] of every event type: (candidates scored, distinct candidates) -- two builds with stage timing on."""
     sess.set_timing(True)
     try:
-        sess.set_debug(COUNT_SCORED)
+        sess.set_debug(_lib.DBG_COUNT_SCORED)
         scored = [int(o.stats.cpu().numpy()[30]) for o in run(sess, mats, params, seed)]
         sess.set_debug(0)
         distinct = [int(o.stats.cpu().numpy()[30]) for o in run(sess, mats, params, seed)]

@@ -33,6 +33,21 @@ def test_header_binding_and_library_agree():
     assert b"gfx950" in blob
 
 
+def test_debug_bits_of_the_binding_are_the_library_s():
+    """Every `constexpr int32_t DBG_... = ...;` of csrc/cco_kernels.h has its name and value in _lib, and _lib carries no other DBG_ name.
+    DBG_ROW_KERNELS is written as the OR of its parts in both places and is compared as the value that OR gives."""
+    from universal_recommender_amd import _lib
+    text = open(os.path.join(ROOT, "universal-recommender_amd", "csrc", "cco_kernels.h")).read()
+    header = {}
+    for name, expr in re.findall(r"^constexpr int32_t (DBG_[A-Z0-9_]+) = ([^;]+);", text, flags=re.M):
+        header[name] = 0
+        for part in expr.split("|"):    # a number, or names defined above
+            header[name] |= int(part) if part.strip().isdigit() else header[part.strip()]
+    assert len(header) >= 16 and "DBG_ROW_KERNELS" in header, sorted(header)
+    assert all(v > 0 and v & (v - 1) == 0 for n, v in header.items() if n != "DBG_ROW_KERNELS"), "every bit on its own"
+    assert {n: getattr(_lib, n) for n in dir(_lib) if n.startswith("DBG_")} == header
+
+
 def test_no_device_means_loud_failure_not_fallback():
     import torch
     if torch.cuda.is_available():

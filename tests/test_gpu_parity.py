@@ -285,9 +285,9 @@ def test_select_overlay_race_fixed(gpu_session):
     the rotating select histograms, and a wave that had finished its digit search wrote them while a sibling wave was still
     reading the counts.  debug 131072 makes that interleaving certain (the team's first wave sleeps before it reads the
     histogram); with the barrier in place the build must still equal the oracle row for row."""
-    from universal_recommender_amd import synth
+    from universal_recommender_amd import _lib, synth
     cfg = synth.config3(0.1)
-    gpu_session.set_debug(131072)
+    gpu_session.set_debug(_lib.DBG_SELECT_DELAY)
     try:
         _, _, stats = compare_with_oracle(gpu_session, select_race_workload(), [P(), P()], 77, exact_ids=True)   # every row consumes the overlaid words
         assert all(int(s[0][1 + 2]) == SELECT_RACE_ROWS_SMALL_BLOCK for s in stats), "the workload must put its rows into the 256-thread small-block class"

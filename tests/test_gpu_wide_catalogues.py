@@ -98,7 +98,7 @@ def test_whole_builds_at_wide_catalogues(gpu_session):
     try:
         first = snapshot(D.cross_occurrence_context(ctx, dev_mats, to_params(params), seed))
         assert_same_bits(snapshot(D.cross_occurrence_context(ctx, dev_mats, to_params(params), seed)), first, "context, second build")
-        ctx.set_debug(1048576)
+        ctx.set_debug(_lib.DBG_UNPACKED_COUNTS)
         assert_same_bits(snapshot(D.cross_occurrence_context(ctx, dev_mats, to_params(params), seed)), first, "context, count gather")
         ctx.set_debug(0)
         ctx_out = D.cross_occurrence_context(ctx, dev_mats, to_params(params), seed)

@@ -80,7 +80,7 @@ def context_reuse_case(lib, device):
     sess = DeviceSession(device, lib)
     ctx = Context(device, lib)
     try:
-        for flags, dbg in ((0, 0), (_lib.FLAG_SINGLE_STREAM, 0), (0, 1048576)):   # debug 1048576: B' without the counts aboard (one count gather per candidate)
+        for flags, dbg in ((0, 0), (_lib.FLAG_SINGLE_STREAM, 0), (0, _lib.DBG_UNPACKED_COUNTS)):   # B' without the counts aboard (one count gather per candidate)
             ctx.set_flags(flags)
             ctx.set_debug(dbg)
             for mats, ps in cases:
@@ -156,9 +156,9 @@ def test_one_process_drives_several_gpus(sim_lib, n_gpus, primary, monkeypatch):
     coll = sharded.TorchCollectives(n_gpus, list(range(n_gpus)))
     ctx = Context(torch.device("cpu"), sim_lib, n_gpus=n_gpus, collectives=coll)
     if primary == "gathered":
-        ctx.set_debug(8192)       # A/B path: the primary's CSC from a pass over the whole gathered A' instead of fragments
+        ctx.set_debug(_lib.DBG_GATHERED_PRIMARY)       # A/B path: the primary's CSC from a pass over the whole gathered A' instead of fragments
     if primary == "plain rows":
-        ctx.set_debug(1048576)    # the rows travel as plain column indices, the row kernels gather the counts (the form of rounds 1-5)
+        ctx.set_debug(_lib.DBG_UNPACKED_COUNTS)    # the rows travel as plain column indices, the row kernels gather the counts (the form of rounds 1-5)
     try:
         assert ctx.n_local == n_gpus
         cuts = [n_users * g // n_gpus for g in range(n_gpus + 1)]
@@ -329,7 +329,7 @@ def fused_expand_case(lib, device):
             ref = [r.to_host() for r in cross_occurrence_device(sess, [to_dev(m, device) for m in mats], to_params(ps), 5)]
             sess.synchronize()
             for flags in (0, _lib.FLAG_SINGLE_STREAM):
-                for debug in (0, 4096):
+                for debug in (0, _lib.DBG_UNFUSED_EXPAND):
                     ctx = Context(device, lib, flags=flags)
                     try:
                         ctx.set_debug(debug)
@@ -488,7 +488,7 @@ def test_row_filtered_exchange_volume_at_8_ranks(sim_lib, monkeypatch):
     generator at 1/100 (100K users, 5 event types), 8 simulated GPUs in one process, the collectives' log as the wire: with the
     row-filtered exchange (default) every rank receives <= 0.6 x what the all-gather form (debug 16384) delivers to it -- B' rows travel
     only to the ranks whose item range their user touches -- and both builds equal the oracle."""
-    from universal_recommender_amd import sharded, synth
+    from universal_recommender_amd import _lib, sharded, synth
     from universal_recommender_amd.device import Context
     W = 8
     monkeypatch.setenv("HIPSIM_DEVICE_COUNT", str(W))
@@ -501,7 +501,7 @@ def test_row_filtered_exchange_volume_at_8_ranks(sim_lib, monkeypatch):
     shards = [[to_dev(O.Csr(hi - lo, m.n_cols, m.row_ptr[lo:hi + 1] - m.row_ptr[lo], m.col_idx[m.row_ptr[lo]:m.row_ptr[hi]]), "cpu")
                for lo, hi in zip(cuts, cuts[1:])] for m in mats]
     received = {}
-    for mode, debug in (("filtered", 0), ("all-gather", 16384)):
+    for mode, debug in (("filtered", 0), ("all-gather", _lib.DBG_UNFILTERED_EXCHANGE)):
         coll = sharded.TorchCollectives(W, list(range(W)))
         ctx = Context(torch.device("cpu"), sim_lib, n_gpus=W, collectives=coll)
         try:

@@ -710,7 +710,7 @@ def test_select_ambiguous_set_overlays_the_histograms(sim_session):
     team one after the other between rendezvous, so it cannot interleave them as the race needs (the -m gpu test runs the same
     build with a wave delayed on hardware); here the logic of the path -- and of the barrier round 4 added -- is checked with exact ids, delay hook on."""
     from helpers import SELECT_RACE_ROWS_SMALL_BLOCK, select_race_workload
-    sim_session.set_debug(131072)
+    sim_session.set_debug(_lib.DBG_SELECT_DELAY)
     try:
         _, _, stats = compare_with_oracle(sim_session, select_race_workload(), [P(), P()], 77, exact_ids=True)
     finally:

@@ -37,6 +37,23 @@ EVAL_TREE_BLOCK = 256  # positions one block of the tree sum reduces (csrc/cco_e
 HIST_STATS_LEN = 8     # urcco_dev_history_rows (URCCO_HIST_STATS_LEN): pairs per class, selects, exclusion rows per class, overflows
 REC_LDS_LIMIT = 3072   # work bound w(q) up to which a query runs in the LDS class (csrc/cco_kernels.h)
 EXCH_SIZES = 4   # int64 words of a shard's record (include/urcco.h URCCO_EXCH_SIZES)
+# bits of urcco_session_set_debug / urcco_context_set_debug: the names and values of csrc/cco_kernels.h (tests/test_c_abi_surface.py compares them)
+DBG_GATHER_ONLY = 1
+DBG_NO_LLR = 2
+DBG_NO_TOPK = 4
+DBG_NO_SELECT = 8
+DBG_NO_RANK = 16
+DBG_NO_COUNT_GATHER = 512
+DBG_UNFUSED_EXPAND = 4096
+DBG_GATHERED_PRIMARY = 8192
+DBG_UNFILTERED_EXCHANGE = 16384
+DBG_SELECT_DELAY = 131072
+DBG_UNPACKED_COUNTS = 1048576
+DBG_NO_PREFILTER = 8388608
+DBG_COUNT_SCORED = 16777216
+DBG_NO_DIRECT_RANK = 33554432
+DBG_COUNT_DIRECT = 67108864
+DBG_ROW_KERNELS = DBG_GATHER_ONLY | DBG_NO_LLR | DBG_NO_TOPK | DBG_NO_SELECT | DBG_NO_RANK | DBG_NO_COUNT_GATHER | DBG_SELECT_DELAY
 STAGE_NAMES = ["column_counts", "downsample_flags", "downsample_scan", "downsample_compact", "transpose", "row_work", "binning",
                "entropy", "cco_rows_micro", "cco_rows_wave", "cco_rows_block_small", "cco_rows_block", "cco_rows_cu_half", "cco_rows_cu", "cco_rows_global", "compact_indicators", "exchange"]
 

@@ -24,7 +24,7 @@ constexpr int CAND_SLOTS = 64;           // words the row kernels spread their c
 constexpr int STATS_LEN = 32;            // [0] pairs, then NBINS each of rows / pairs / users / out entries per bin, [1 + 4 NBINS] table overflows,
                                          // [STATS_LEN - 1] rows binned into the micro class's two shared-wave sub-lists (0: the class ran as one list)
 
-// Bits of urcco_session_set_debug / urcco_context_set_debug (include/urcco.h documents them; bench.py and the tests pass the values).
+// Bits of urcco_session_set_debug / urcco_context_set_debug (include/urcco.h documents them; _lib.py carries the same names and values for the tests, bench.py passes the values).
 // SpGEMM row phases switched off (profiling only, results meaningless): the DBG instantiations of the row kernels.
 constexpr int32_t DBG_GATHER_ONLY = 1;
 constexpr int32_t DBG_NO_LLR = 2;
@@ -111,7 +111,7 @@ struct CcoArgs {
   double* out_llr;
   unsigned long long* err;   // stats[1 + 4 * NBINS]: LDS table overflows (must stay 0)
   unsigned long long* cand;  // nullable [CAND_SLOTS], zero on entry: distinct (row, column) candidates scored, spread over the slots (statistics)
-  // global-accumulator scratch (bin 3)
+  // global-accumulator scratch (bin 6 when k is beyond the multi-pass class: g_blocks > 0)
   int32_t* g_counts;         // [GLOBAL_BIN_BLOCKS][n_cols_b] zero on entry, zero on exit
   unsigned long long* g_cand_key;  // [GLOBAL_BIN_BLOCKS][n_cols_b]
   int32_t* g_cand_col;       // [GLOBAL_BIN_BLOCKS][n_cols_b]
@@ -249,7 +249,18 @@ hipError_t launch_row_work(hipStream_t st, int n_cu, int32_t item_lo, int32_t it
 hipError_t launch_binning(hipStream_t st, int32_t item_lo, int32_t n, const int64_t* work, const int32_t* cnt_a, int32_t n_cols_b,
                           int32_t count_bits, int32_t k, int64_t* tile_counts, int32_t* bin_off, int32_t* bin_rows, int64_t* stats);
 
-hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, int bin, int32_t n_rows /* item rows of the build: bounds the grids */);
+// Which instantiations of the row kernels one A'B call enqueues per LDS class, decided once on the host (cco_rows_impl); the kernels' first-line guard
+// states the same rule on the device.  The two host verdicts follow from it: ExpandForm::host_wide = no PK instantiation runs, ExpandForm::host_narrow =
+// CcoArgs::pk_known = PACKED.
+//   DEBUG           DBG_ROW_KERNELS: the DBG instantiations (they exist for the plain form only), b_packed = NULL
+//   PLAIN           no packed words (no copy, or DBG_UNPACKED_COUNTS on a plain B'): the plain instantiations
+//   DEVICE_DECIDES  packed words whose verdict -- do the counts fit, are the tables narrow -- is a device-side fact: the PK, then the plain instantiations; the
+//                   one whose turn it is not returns at once
+//   PACKED          words known good AND tables known narrow (cco_rows_impl): the PK instantiations alone
+enum class RowsPlan { DEBUG, PLAIN, DEVICE_DECIDES, PACKED };
+constexpr bool plan_runs_pk(RowsPlan p) { return p == RowsPlan::DEVICE_DECIDES || p == RowsPlan::PACKED; }
+constexpr bool plan_runs_plain(RowsPlan p) { return p == RowsPlan::PLAIN || p == RowsPlan::DEVICE_DECIDES; }
+hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, RowsPlan plan, int bin, int32_t n_rows /* item rows of the build: bounds the grids */);
 hipError_t launch_bin_out_stats(hipStream_t st, const int32_t* bin_rows, const int32_t* bin_off, int32_t item_lo, const int32_t* out_count,
                                 const unsigned long long* cand, int64_t* stats);
 

@@ -1827,7 +1827,7 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
 }
 
 // --------------------------------------------------------------------------------------------
-// Global-accumulator variant (bin 4): rows whose distinct columns cannot be bounded below an LDS table or
+// Global-accumulator variant (bin 6 when k is beyond the multi-pass class): rows whose distinct columns cannot be bounded below an LDS table or
 // whose counts overflow the packed entry.  One 1024-thread block per row; a dense int32 counter array per
 // resident block (zero on entry, restored to zero by the claim walk), candidates spilled to global scratch,
 // top-k by k strictly-descending argmax sweeps.  Correct for any row; only meant for the rare heavy ones.
@@ -2019,102 +2019,86 @@ hipError_t launch_mono_limit(hipStream_t st, unsigned short* mono, const double*
   return hipGetLastError();
 }
 
+// The accumulator classes as the host launches them, by bin: the team of T threads, its table of E words, the candidates a lane scores together (U), the
+// multi-pass form, and the grid as a multiple of the blocks that fit the chip.  (Bin 0 is the micro class: cco_rows_micro_kernel, four one-wave teams per block.)
+// Several times as many blocks as fit the chip: the later ones start as blocks of the first wave retire, which evens out the
+// classes' ragged ends -- rows are dealt out by a static stride, so a block's share of heavy rows is luck -- and lets short kernels
+// of the other event types' streams in: a grid that exactly fills the chip locks them out until it ends (measured: single-block
+// kernels of another stream waited 0.2 ms).
+// Round 2 (config 3): 2x, and 3x / 4x / 8x measured no better.  Round 5 (config 4 / 5, after the row kernels had lost a third of
+// their time): 8x for the four big classes and 4x for the 512/1024-thread classes = -0.55 / -0.8 ms per build, every class's own
+// time included (profiles/r05_grid_factors_ab.log); bounded by one row loop per 32 item rows of the build (small builds and the ranks of a sharded
+// build keep the 2x: a row loop's start-up -- three rows of prefetches -- is not free; at an eighth of config 4's rows 4x measured 0.12 ms
+// per rank slower than 2x).
+struct RowClass {
+  int block, teams, factor;  // threads per block (the kernels' BLOCK), row loops per block (TEAMS), grid = factor x the blocks that fit the chip
+  unsigned direct;           // the kernels' DL: 0 = the class has no direct ranking
+  void (*dbg)(CcoArgs, int), (*pk)(CcoArgs, int), (*plain)(CcoArgs, int);  // the three instantiations a RowsPlan chooses from
+};
+template <int T, int E, int U, bool MP = false>
+constexpr RowClass row_class(int factor) {
+  return {T < 256 ? 256 : T, (T < 256 ? 256 : T) / T, factor, MP ? 0u : direct_limit(T, E),
+          cco_rows_kernel<T, E, U, MP, true, false>, cco_rows_kernel<T, E, U, MP, false, true>, cco_rows_kernel<T, E, U, MP, false, false>};
+}
+constexpr RowClass ROW_CLASS[NBINS] = {{256, 4, 8, 0u, nullptr, nullptr, nullptr},  // micro: cco_rows_micro_kernel<L> per sub-list, four one-wave teams
+                                       row_class<64, E0, URCCO_U_WAVE>(8),         row_class<256, E1S, URCCO_U_BS>(8), row_class<256, E1, URCCO_U_B>(8),
+                                       row_class<512, E2S, URCCO_U_H>(4),          row_class<1024, E2, URCCO_U_C>(4),  row_class<1024, E2, URCCO_U_C, true>(2)};
+// the micro class's sub-lists of shared waves (two / four rows per wave and pass) hold a third of the class's passes each at most: smaller grids,
+// so that a wave still runs several passes behind its start-up (three rows of prefetches).
+constexpr int MICRO_FACTOR32 = 3, MICRO_FACTOR16 = 2;
+
 // resident blocks per CU of each LDS-accumulator kernel (registers / LDS decide), so that the persistent grids fill
 // the chip exactly once
 static int blocks_per_cu(int bin) {
-  static std::atomic<int> cache[7];  // zero-initialised; a racing first call computes the same value twice
+  static std::atomic<int> cache[NBINS];  // zero-initialised; a racing first call computes the same value twice
   if (cache[bin].load(std::memory_order_relaxed) == 0) {
     int n = 0;
-    hipError_t e = hipErrorUnknown;
-    if (bin == 0) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (cco_rows_micro_kernel<WAVE, false, false>), 256, 0);
-    if (bin == 1) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, cco_rows_kernel<64, E0, URCCO_U_WAVE>, 256, 0);
-    if (bin == 2) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, cco_rows_kernel<256, E1S, URCCO_U_BS>, 256, 0);
-    if (bin == 3) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, cco_rows_kernel<256, E1, URCCO_U_B>, 256, 0);
-    if (bin == 4) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, cco_rows_kernel<512, E2S, URCCO_U_H>, 512, 0);
-    if (bin == 5) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, cco_rows_kernel<1024, E2, URCCO_U_C>, 1024, 0);
-    if (bin == 6) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, cco_rows_kernel<1024, E2, URCCO_U_C, true>, 1024, 0);
+    const hipError_t e = bin == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (cco_rows_micro_kernel<WAVE, false, false>), ROW_CLASS[0].block, 0)
+                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ROW_CLASS[bin].plain, ROW_CLASS[bin].block, 0);
     cache[bin].store((e == hipSuccess && n > 0) ? n : 1, std::memory_order_relaxed);
   }
   return cache[bin].load(std::memory_order_relaxed);
 }
 
-hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args_in, int bin, int32_t n_rows) {
-  // Persistent grids sized to the chip; each kernel reads its own row list length from bin_off on the device,
+hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, RowsPlan plan, int bin, int32_t n_rows) {
+  // Persistent grids sized to the chip (ROW_CLASS); each kernel reads its own row list length from bin_off on the device,
   // so no host synchronisation sits between binning and the SpGEMM.
-  // Several times as many blocks as fit the chip: the later ones start as blocks of the first wave retire, which evens out the
-  // classes' ragged ends -- rows are dealt out by a static stride, so a block's share of heavy rows is luck -- and lets short kernels
-  // of the other event types' streams in: a grid that exactly fills the chip locks them out until it ends (measured: single-block
-  // kernels of another stream waited 0.2 ms).
-  // Round 2 (config 3): 2x, and 3x / 4x / 8x measured no better.  Round 5 (config 4 / 5, after the row kernels had lost a third of
-  // their time): 8x for the four big classes and 4x for the 512/1024-thread classes = -0.55 / -0.8 ms per build, every class's own
-  // time included (profiles/r05_grid_factors_ab.log); bounded by one row loop per 32 item rows of the build (small builds and the ranks of a sharded
-  // build keep the 2x: a row loop's start-up -- three rows of prefetches -- is not free; at an eighth of config 4's rows 4x measured 0.12 ms
-  // per rank slower than 2x).
-  static constexpr int factor[NBINS] = {8, 8, 8, 8, 4, 4, 2};
-  // the micro class's sub-lists of shared waves (two / four rows per wave and pass) hold a third of the class's passes each at most: smaller grids,
-  // so that a wave still runs several passes behind its start-up (three rows of prefetches).
-  constexpr int micro_factor32 = 3, micro_factor16 = 2;
-  auto grid = [&](int b, int f = 0) {
-    const long long fill = (long long)n_cu * blocks_per_cu(b);  // blocks resident at once
-    const long long teams = b <= 1 ? 4 : 1;                       // row loops per block (micro / one-wave classes: four one-wave teams)
-    long long cap = ((long long)n_rows + teams * 32 - 1) / (teams * 32);
+  const RowClass& c = ROW_CLASS[bin];
+  auto grid = [&](int factor) {
+    const long long fill = (long long)n_cu * blocks_per_cu(bin);  // blocks resident at once
+    long long cap = ((long long)n_rows + c.teams * 32 - 1) / (c.teams * 32);
     if (cap < 2 * fill) cap = 2 * fill;  // (as rounds 2-4)
-    long long blocks = fill * (f > 0 ? f : factor[b]);
+    long long blocks = fill * factor;
     if (blocks > cap) blocks = cap;
     return dim3((unsigned)blocks);
   };
-  const bool dbgk = (args_in.debug & DBG_ROW_KERNELS) != 0;  // the ablation / test switches live in the DBG instantiations only
+  // Two blocks: the PK instantiations' and the one of every kernel that reads plain words (the plain and DBG instantiations, the dense global kernel).
   // DBG_COUNT_DIRECT: the statistics word counts the rows the packed kernels ranked directly -- every kernel that has no direct ranking (the plain and DBG
   // forms, the micro and multi-pass classes, a class it is compiled out of) runs without the word, so that no candidate count is mixed in
-  constexpr unsigned dl_of_bin[NBINS] = {0u, direct_limit(64, E0), direct_limit(256, E1S), direct_limit(256, E1), direct_limit(512, E2S), direct_limit(1024, E2), 0u};
-  const bool count_direct = (args_in.debug & DBG_COUNT_DIRECT) != 0;
-  CcoArgs args = args_in;
-  if (count_direct && dl_of_bin[bin] == 0u) args.cand = nullptr;
-  // ride on the kernels' bin argument (grid-uniform; the production instantiations do not read CcoArgs::debug)
-  const int scored = ((args.debug & DBG_COUNT_SCORED) ? 256 : 0) | ((args.debug & DBG_NO_DIRECT_RANK) ? 512 : 0) | (count_direct ? 1024 : 0);
-  // A B' with counts aboard: BOTH instantiations are enqueued -- whether the counts fit is a device-side fact, the one whose turn it is not returns at
-  // once.  The DBG instantiations exist for the plain form only (the ablation switches price the count gather among other things).
-  CcoArgs plain = args;
-  plain.b_packed = nullptr;
-  CcoArgs wide = args;  // the plain instantiation's turn when the tables are wide
-  if (count_direct) { plain.cand = nullptr; wide.cand = nullptr; }
-  const bool both = args.b_packed != nullptr && !dbgk && !args.pk_known;  // (pk_known: the host knows the verdict -- packed and narrow -- only that instantiation)
-#define URCCO_LAUNCH_ROWS(TT, EE, UU, MPF, GRID, BLK, BINARG)                                                                      \
-  do {                                                                                                                           \
-    if (dbgk) hipLaunchKernelGGL((cco_rows_kernel<TT, EE, UU, MPF, true, false>), GRID, dim3(BLK), 0, st, plain, BINARG);          \
-    else {                                                                                                                       \
-      if (both || args.pk_known) hipLaunchKernelGGL((cco_rows_kernel<TT, EE, UU, MPF, false, true>), GRID, dim3(BLK), 0, st, args, BINARG | scored); \
-      if (!args.pk_known) hipLaunchKernelGGL((cco_rows_kernel<TT, EE, UU, MPF, false, false>), GRID, dim3(BLK), 0, st, wide, BINARG); \
-    }                                                                                                                            \
-  } while (0)
-#define URCCO_LAUNCH_MICRO(LL, GRID)                                                                                  \
-  do {                                                                                                                \
-    if (dbgk) hipLaunchKernelGGL((cco_rows_micro_kernel<LL, true, false>), GRID, dim3(256), 0, st, plain);              \
-    else {                                                                                                            \
-      if (both || args.pk_known) hipLaunchKernelGGL((cco_rows_micro_kernel<LL, false, true>), GRID, dim3(256), 0, st, args); \
-      if (!args.pk_known) hipLaunchKernelGGL((cco_rows_micro_kernel<LL, false, false>), GRID, dim3(256), 0, st, args);  \
-    }                                                                                                                 \
-  } while (0)
-  switch (bin) {
-    case 0:  // the class's three sub-lists, the rows that keep a wave to themselves first (each kernel reads its own list bounds on the device)
-      URCCO_LAUNCH_MICRO(64, grid(0));
-      if (micro_split_for(n_rows)) {  // (the same rule as the binning pass: without the split the two sub-lists are empty)
-        URCCO_LAUNCH_MICRO(32, grid(0, micro_factor32));
-        URCCO_LAUNCH_MICRO(16, grid(0, micro_factor16));
-      }
-      break;
-    case 1: URCCO_LAUNCH_ROWS(64, E0, URCCO_U_WAVE, false, grid(1), 256, 1); break;
-    case 2: URCCO_LAUNCH_ROWS(256, E1S, URCCO_U_BS, false, grid(2), 256, 2); break;
-    case 3: URCCO_LAUNCH_ROWS(256, E1, URCCO_U_B, false, grid(3), 256, 3); break;
-    case 4: URCCO_LAUNCH_ROWS(512, E2S, URCCO_U_H, false, grid(4), 512, 4); break;
-    case 5: URCCO_LAUNCH_ROWS(1024, E2, URCCO_U_C, false, grid(5), 1024, 5); break;
-    default:
-      if (args.g_blocks > 0) hipLaunchKernelGGL(cco_rows_global_kernel, dim3((unsigned)args.g_blocks), dim3(GB_THREADS), 0, st, plain);
-      else URCCO_LAUNCH_ROWS(1024, E2, URCCO_U_C, true, grid(6), 1024, 6);
-      break;
+  const bool count_direct = (args.debug & DBG_COUNT_DIRECT) != 0;
+  CcoArgs pk = args, plain = args;
+  if (count_direct && c.direct == 0u) pk.cand = nullptr;
+  if (count_direct) plain.cand = nullptr;
+  // ride on the PK kernels' bin argument (grid-uniform; the production instantiations do not read CcoArgs::debug)
+  const int pk_bits = ((args.debug & DBG_COUNT_SCORED) ? 256 : 0) | ((args.debug & DBG_NO_DIRECT_RANK) ? 512 : 0) | (count_direct ? 1024 : 0);
+  // what the plan enqueues of one class (or micro sub-list), given its DBG, PK and plain instantiation; bin_arg: the bin argument of cco_rows_kernel
+  auto enqueue = [&](auto dbg_kernel, auto pk_kernel, auto plain_kernel, int factor, auto... bin_arg) {
+    if (plan == RowsPlan::DEBUG) hipLaunchKernelGGL(dbg_kernel, grid(factor), dim3(c.block), 0, st, plain, bin_arg...);
+    if (plan_runs_pk(plan)) hipLaunchKernelGGL(pk_kernel, grid(factor), dim3(c.block), 0, st, pk, (bin_arg | pk_bits)...);
+    if (plan_runs_plain(plan)) hipLaunchKernelGGL(plain_kernel, grid(factor), dim3(c.block), 0, st, plain, bin_arg...);
+  };
+  if (bin == 0) {  // the class's three sub-lists, the rows that keep a wave to themselves first (each kernel reads its own list bounds on the device)
+    enqueue(cco_rows_micro_kernel<64, true, false>, cco_rows_micro_kernel<64, false, true>, cco_rows_micro_kernel<64, false, false>, c.factor);
+    if (micro_split_for(n_rows)) {  // (the same rule as the binning pass: without the split the two sub-lists are empty)
+      enqueue(cco_rows_micro_kernel<32, true, false>, cco_rows_micro_kernel<32, false, true>, cco_rows_micro_kernel<32, false, false>, MICRO_FACTOR32);
+      enqueue(cco_rows_micro_kernel<16, true, false>, cco_rows_micro_kernel<16, false, true>, cco_rows_micro_kernel<16, false, false>, MICRO_FACTOR16);
+    }
+  } else if (bin == NBINS - 1 && args.g_blocks > 0) {
+    plain.b_packed = nullptr;  // (the dense kernel reads plain words whatever the plan)
+    hipLaunchKernelGGL(cco_rows_global_kernel, dim3((unsigned)args.g_blocks), dim3(GB_THREADS), 0, st, plain);
+  } else {
+    enqueue(c.dbg, c.pk, c.plain, c.factor, bin);
   }
-#undef URCCO_LAUNCH_ROWS
-#undef URCCO_LAUNCH_MICRO
   return hipGetLastError();
 }
 

@@ -391,13 +391,13 @@ int urcco_dev_cco_rows(urcco_session* s, int32_t item_lo, int32_t item_hi, int32
                        const int32_t* a_row_idx, int64_t nnz_a_bound, const int64_t* b_row_ptr, const int32_t* b_col_idx, int32_t n_cols_b,
                        const int32_t* counts_a, const int32_t* counts_b, int64_t n_users, int32_t exclude_self, int32_t k,
                        int32_t has_min_llr, double min_llr, int32_t* out_count, int32_t* out_idx, double* out_llr, int64_t* stats_dev) {
-  return urcco_detail::cco_rows_impl(s, item_lo, item_hi, n_items_a, a_col_ptr, a_row_idx, nnz_a_bound, b_row_ptr, b_col_idx, n_cols_b, counts_a, counts_b, n_users,
-                                     exclude_self, k, has_min_llr, min_llr, out_count, out_idx, out_llr, stats_dev, nullptr, nullptr);
+  return urcco_dev_cco_rows_packed(s, item_lo, item_hi, n_items_a, a_col_ptr, a_row_idx, nnz_a_bound, b_row_ptr, b_col_idx, n_cols_b, counts_a, counts_b, n_users, exclude_self,
+                                   k, has_min_llr, min_llr, out_count, out_idx, out_llr, stats_dev, nullptr, nullptr);
 }
 
 int urcco_dev_pack_counts(urcco_session* s, int64_t n_rows_b, const int64_t* b_row_ptr, const int32_t* b_col_idx, int64_t nnz_b_bound, const int32_t* counts_b,
                           int32_t n_cols_b, int32_t* out_packed, int32_t* out_bad) {
-  return urcco_detail::pack_counts(s, b_row_ptr, n_rows_b, b_col_idx, nnz_b_bound, counts_b, n_cols_b, out_packed, out_bad);
+  return urcco_detail::pack_counts(s, BPrime(b_row_ptr, b_col_idx, n_rows_b, nnz_b_bound, n_cols_b, counts_b, false), out_packed, out_bad);
 }
 
 int urcco_dev_cco_rows_packed(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_items_a, const int64_t* a_col_ptr,
@@ -406,8 +406,14 @@ int urcco_dev_cco_rows_packed(urcco_session* s, int32_t item_lo, int32_t item_hi
                               int32_t has_min_llr, double min_llr, int32_t* out_count, int32_t* out_idx, double* out_llr, int64_t* stats_dev,
                               const int32_t* b_packed, const int32_t* pack_bad) {
   if ((b_packed == nullptr) != (pack_bad == nullptr)) return fail(URCCO_BAD_ARG, "urcco_dev_cco_rows_packed: b_packed and pack_bad come together");
-  return urcco_detail::cco_rows_impl(s, item_lo, item_hi, n_items_a, a_col_ptr, a_row_idx, nnz_a_bound, b_row_ptr, b_col_idx, n_cols_b, counts_a, counts_b, n_users,
-                                     exclude_self, k, has_min_llr, min_llr, out_count, out_idx, out_llr, stats_dev, nullptr, nullptr, nullptr, b_packed, pack_bad);
+  RowsCall c;
+  c.item_lo = item_lo; c.item_hi = item_hi; c.n_items_a = n_items_a;
+  c.a_col_ptr = a_col_ptr; c.a_row_idx = a_row_idx; c.nnz_a_bound = nnz_a_bound; c.counts_a = counts_a;
+  c.b = BPrime(b_row_ptr, b_col_idx, n_users, -1, n_cols_b, counts_b, false);
+  if (b_packed) c.b = c.b.with_copy(b_packed, pack_bad);
+  c.n_users = n_users; c.exclude_self = exclude_self; c.k = k; c.has_min_llr = has_min_llr; c.min_llr = min_llr;
+  c.out_count = out_count; c.out_idx = out_idx; c.out_llr = out_llr; c.stats_dev = stats_dev;
+  return urcco_detail::cco_rows_impl(s, c);
 }
 
 }  // extern "C"
@@ -428,23 +434,21 @@ int partition_dev(urcco_session* s, int32_t n_items, const int64_t* work, int32_
   return URCCO_OK;
 }
 
-// One secondary's share of a fused expand preparation (see urcco_expand_multi) may be handed in as pre_pstart / pre_plen.
-int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_items_a, const int64_t* a_col_ptr, const int32_t* a_row_idx, int64_t nnz_a_bound,
-                  const int64_t* b_row_ptr, const int32_t* b_col_idx, int32_t n_cols_b, const int32_t* counts_a, const int32_t* counts_b, int64_t n_users,
-                  int32_t exclude_self, int32_t k, int32_t has_min_llr, double min_llr, int32_t* out_count, int32_t* out_idx, double* out_llr, int64_t* stats_dev,
-                  const unsigned* pre_pstart, const int32_t* pre_plen, int64_t* pre_tile_sums, const int32_t* b_packed, const int32_t* pack_bad, bool pk_known, int64_t b_nnz_bound) {
-  if (!s || item_lo < 0 || item_hi < item_lo || item_hi > n_items_a || n_cols_b < 0 || n_users < 0 || nnz_a_bound < 0 || !a_col_ptr || !b_row_ptr)
+int cco_rows_impl(urcco_session* s, const RowsCall& c) {
+  const int32_t item_lo = c.item_lo, item_hi = c.item_hi, n_items_a = c.n_items_a, n_cols_b = c.b.n_cols, k = c.k;
+  const int64_t n_users = c.n_users;  // (the rows of B': c.b.n_rows)
+  if (!s || item_lo < 0 || item_hi < item_lo || item_hi > n_items_a || n_cols_b < 0 || n_users < 0 || c.nnz_a_bound < 0 || !c.a_col_ptr || !c.b.row_ptr)
     return fail(URCCO_BAD_ARG, "urcco_dev_cco_rows: bad argument");
   if (k <= 0) return fail(URCCO_BAD_ARG, "maxInterestingElements must be positive, got %d", k);
   const int32_t n = item_hi - item_lo;
   if (n == 0) {
-    if (stats_dev) HIPC(hipMemsetAsync(stats_dev, 0, sizeof(int64_t) * URCCO_STATS_LEN, s->stream));
+    if (c.stats_dev) HIPC(hipMemsetAsync(c.stats_dev, 0, sizeof(int64_t) * URCCO_STATS_LEN, s->stream));
     return URCCO_OK;
   }
-  if (!out_count || !out_idx || !out_llr || !counts_a || (n_cols_b > 0 && !counts_b)) return fail(URCCO_BAD_ARG, "urcco_dev_cco_rows: NULL buffer");
-  HIPC(hipMemsetAsync(out_count, 0, sizeof(int32_t) * (size_t)n, s->stream));
+  if (!c.out_count || !c.out_idx || !c.out_llr || !c.counts_a || (n_cols_b > 0 && !c.b.counts)) return fail(URCCO_BAD_ARG, "urcco_dev_cco_rows: NULL buffer");
+  HIPC(hipMemsetAsync(c.out_count, 0, sizeof(int32_t) * (size_t)n, s->stream));
   if (n_cols_b == 0 || n_users == 0) {
-    if (stats_dev) HIPC(hipMemsetAsync(stats_dev, 0, sizeof(int64_t) * URCCO_STATS_LEN, s->stream));
+    if (c.stats_dev) HIPC(hipMemsetAsync(c.stats_dev, 0, sizeof(int64_t) * URCCO_STATS_LEN, s->stream));
     return URCCO_OK;
   }
   int key_bits = 0;  // packed LDS entry: key = col + 1 in the high bits, count in the low bits
@@ -466,73 +470,73 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
     s->xlx_hi_n = n_users;
   }
   const int64_t n_tiles = ((int64_t)n + urcco::BIN_TILE - 1) / urcco::BIN_TILE;
-  const int64_t cap = nnz_a_bound;
+  const int64_t cap = c.nnz_a_bound;
   if (!s->form_word.p) URC(s->form_word.alloc(1));
   s->form_valid = false;
   // the expand tables in the narrow form (32-bit starts; the work prefix as 32-bit words in the front half of wp) or, when the scan's verdict says so, in
   // the wide one (pstart64; wp whole): cco_kernels.h, ExpandForm.  pstart64 is touched by the wide form alone.
   ArenaLayout L(s);
-  int64_t *pstart64, *wp, *p_tile_sums, *work, *tile_counts, *stats = stats_dev;
+  int64_t *pstart64, *wp, *p_tile_sums, *work, *tile_counts, *stats = c.stats_dev;
   unsigned *own_pstart = nullptr, *b_rp32;
   int32_t *own_plen, *bin_off, *bin_rows, *cnt16_bad;
   double *ent_a, *xlx_n;
   unsigned short *cnt_b16, *pf_limit;
   unsigned long long* cand;
   L.add(&pstart64, (size_t)cap);
-  if (!pre_pstart) L.add(&own_pstart, (size_t)cap);
+  if (!c.pre_pstart) L.add(&own_pstart, (size_t)cap);
   L.add(&own_plen, (size_t)cap).add(&wp, (size_t)cap + 1).add(&p_tile_sums, scan_tile_words(cap));
   L.add(&work, (size_t)n).add(&tile_counts, (size_t)(n_tiles + 1) * urcco::BIN_COLS_HOST);  // binning
   L.add(&bin_off, urcco::BIN_OFF_LEN).add(&bin_rows, (size_t)n);
   L.add(&ent_a, (size_t)n_items_a).add(&cnt_b16, (size_t)n_cols_b).add(&cnt16_bad, 1).add(&pf_limit, (size_t)n_items_a);
   L.add(&cand, urcco::CAND_SLOTS).add(&xlx_n, 1);
-  if (!stats_dev) L.add(&stats, URCCO_STATS_LEN);
+  if (!c.stats_dev) L.add(&stats, URCCO_STATS_LEN);
   L.add(&b_rp32, (size_t)n_users + 1);
   URC(L.commit());
-  const unsigned* pstart32 = pre_pstart ? pre_pstart : own_pstart;
+  const unsigned* pstart32 = c.pre_pstart ? c.pre_pstart : own_pstart;
   int32_t* form = s->form_word.p;  // (the session's own word, not arena scratch: urcco_session_expand_form reads it after the call)
 
-  // DBG_UNPACKED_COUNTS: the count gather of rounds 1-5 (A/B, tests).  pk_known: b_col_idx itself holds packed words (the rows a sharded build received
-  // travelled with their counts aboard -- the host learnt with the shard sizes that every count fits): no plain copy exists, every reader masks
-  const int32_t* packed = pk_known ? b_col_idx : ((b_packed && pack_bad && !(s->debug & urcco::DBG_UNPACKED_COUNTS)) ? b_packed : nullptr);
-  // the plain instantiations are the only ones that will run (no packed B', or the DBG ones): they read the wide form
-  const bool host_wide = packed == nullptr || (s->debug & urcco::DBG_ROW_KERNELS) != 0;
-  // pk_known builds: the host can know the whole verdict.  B' holds fewer than 2^32 entries (the shard sizes), and a row of B' holds distinct columns, so no
+  // The plan (urcco::RowsPlan), decided here once for the expand scan and for every class's launch.
+  // The packed words: B' itself when it is known good -- no plain copy exists, every reader masks -- else its packed copy, unless DBG_UNPACKED_COUNTS asks for
+  // the count gather of rounds 1-5 (A/B, tests).
+  const int32_t* packed = c.b.known_good() ? c.b.words : ((s->debug & urcco::DBG_UNPACKED_COUNTS) ? nullptr : c.b.packed());
+  // Known-good words: the host can know the whole verdict.  B' holds fewer than 2^32 entries (the shard sizes), and a row of B' holds distinct columns, so no
   // tile of 2048 lengths sums to more than 2048 * n_cols_b.  (maxElementsPerRow is no bound: the down-sampling keeps entries at a RATE.)  Then only the packed
   // instantiation of every class is enqueued and the scan sets the word without its tests.
-  const bool narrow_known = pk_known && !host_wide && b_nnz_bound >= 0 && b_nnz_bound < ((int64_t)1 << 32) &&
+  const bool narrow_known = c.b.known_good() && c.b.nnz_bound >= 0 && c.b.nnz_bound < ((int64_t)1 << 32) &&
                             (unsigned long long)n_cols_b * (unsigned long long)urcco::SCAN_TILE < s->narrow_limit;
-  const urcco::ExpandForm ef{form, pk_known ? nullptr : pack_bad, host_wide ? 1 : 0, narrow_known ? 1 : 0, s->narrow_limit, s->prefix_seed};
-  int64_t* tile_sums = (pre_pstart && pre_plen && pre_tile_sums) ? pre_tile_sums : p_tile_sums;
+  using urcco::RowsPlan;
+  const RowsPlan plan = (s->debug & urcco::DBG_ROW_KERNELS) ? RowsPlan::DEBUG : !packed ? RowsPlan::PLAIN : narrow_known ? RowsPlan::PACKED : RowsPlan::DEVICE_DECIDES;
+  const urcco::ExpandForm ef{form, c.b.pack_bad(), urcco::plan_runs_pk(plan) ? 0 : 1, plan == RowsPlan::PACKED ? 1 : 0, s->narrow_limit, s->prefix_seed};
+  int64_t* tile_sums = c.pre_pstart ? c.pre_tile_sums : p_tile_sums;
   s->begin(URCCO_STAGE_ROW_WORK);
-  if (pre_pstart && pre_plen)
-    HIPC(urcco::launch_expand_scan(s->stream, a_col_ptr, n_items_a, pre_plen, cap, wp, tile_sums, pre_tile_sums != nullptr, pre_pstart, pstart64, ef));
+  if (c.pre_pstart)
+    HIPC(urcco::launch_expand_scan(s->stream, c.a_col_ptr, n_items_a, c.pre_plen, cap, wp, tile_sums, true, c.pre_pstart, pstart64, ef));
   else
-    HIPC(urcco::launch_expand_prepare(s->stream, s->n_cu, a_col_ptr, n_items_a, a_row_idx, b_row_ptr, b_rp32, n_users, cap, own_pstart, pstart64, own_plen, wp, tile_sums, ef));
-  HIPC(urcco::launch_row_work(s->stream, s->n_cu, item_lo, item_hi, a_col_ptr, wp, tile_sums, form, work));
+    HIPC(urcco::launch_expand_prepare(s->stream, s->n_cu, c.a_col_ptr, n_items_a, c.a_row_idx, c.b.row_ptr, b_rp32, n_users, cap, own_pstart, pstart64, own_plen, wp, tile_sums, ef));
+  HIPC(urcco::launch_row_work(s->stream, s->n_cu, item_lo, item_hi, c.a_col_ptr, wp, tile_sums, form, work));
   s->form_valid = true;
   s->end();
   s->begin(URCCO_STAGE_BINNING);
   HIPC(hipMemsetAsync(stats, 0, sizeof(int64_t) * URCCO_STATS_LEN, s->stream));
-  HIPC(urcco::launch_binning(s->stream, item_lo, n, work, counts_a, n_cols_b, count_bits, k, tile_counts, bin_off, bin_rows, stats));
+  HIPC(urcco::launch_binning(s->stream, item_lo, n, work, c.counts_a, n_cols_b, count_bits, k, tile_counts, bin_off, bin_rows, stats));
   s->end();
   s->begin(URCCO_STAGE_ENTROPY);
-  HIPC(urcco::launch_item_entropy(s->stream, counts_a, n_items_a, n_users, ent_a, xlx_n, mono, pf_limit));
-  HIPC(urcco::launch_narrow_counts(s->stream, s->n_cu, counts_b, n_cols_b, cnt_b16, cnt16_bad));
+  HIPC(urcco::launch_item_entropy(s->stream, c.counts_a, n_items_a, n_users, ent_a, xlx_n, mono, pf_limit));
+  HIPC(urcco::launch_narrow_counts(s->stream, s->n_cu, c.b.counts, n_cols_b, cnt_b16, cnt16_bad));
   s->end();
 
   urcco::CcoArgs a;
   a.bin_rows = bin_rows; a.bin_off = bin_off;
-  a.a_col_ptr = a_col_ptr; a.pstart32 = pstart32; a.pstart64 = pstart64; a.wp = wp; a.form = form; a.work = work; a.b_col_idx = b_col_idx;
-  a.b_packed = packed; a.pk_known = narrow_known ? 1 : 0;
-  a.b_col_mask = pk_known ? (key_bits >= 32 ? 0xffffffffu : (1u << key_bits) - 1u) : 0xffffffffu;
-  a.cnt_a = counts_a; a.cnt_b = counts_b; a.ent_a = ent_a; a.cnt_b16 = cnt_b16; a.cnt16_bad = cnt16_bad; a.xlx_n = xlx_n; a.xlx_tab = s->xlx_tab.p; a.xlx_hi = s->xlx_hi.p; a.col_ent = s->xlx_hi.p + urcco::XLX_TABLE_HOST; a.debug = s->debug;
+  a.a_col_ptr = c.a_col_ptr; a.pstart32 = pstart32; a.pstart64 = pstart64; a.wp = wp; a.form = form; a.work = work; a.b_col_idx = c.b.words;
+  a.b_packed = urcco::plan_runs_pk(plan) ? packed : nullptr; a.pk_known = ef.host_narrow; a.b_col_mask = c.b.col_mask();
+  a.cnt_a = c.counts_a; a.cnt_b = c.b.counts; a.ent_a = ent_a; a.cnt_b16 = cnt_b16; a.cnt16_bad = cnt16_bad; a.xlx_n = xlx_n; a.xlx_tab = s->xlx_tab.p; a.xlx_hi = s->xlx_hi.p; a.col_ent = s->xlx_hi.p + urcco::XLX_TABLE_HOST; a.debug = s->debug;
   a.pf_limit = (s->debug & urcco::DBG_NO_PREFILTER) ? nullptr : pf_limit;
-  a.n_users = n_users; a.n_cols_b = n_cols_b; a.item_lo = item_lo; a.exclude_self = exclude_self ? 1 : 0; a.k = k;
-  a.has_min_llr = has_min_llr ? 1 : 0; a.min_llr = min_llr; a.count_bits = count_bits;
+  a.n_users = n_users; a.n_cols_b = n_cols_b; a.item_lo = item_lo; a.exclude_self = c.exclude_self ? 1 : 0; a.k = k;
+  a.has_min_llr = c.has_min_llr ? 1 : 0; a.min_llr = c.min_llr; a.count_bits = count_bits;
   a.col_bytes = n_cols_b <= (1 << 8) ? 1 : (n_cols_b <= (1 << 16) ? 2 : (n_cols_b <= (1 << 24) ? 3 : 4));
   a.unordered = s->unordered_rows ? 1 : 0;
   a.g_log2 = 4;  // 16 lanes stream one user's B' row: 64 B segments, matches the ~10-40 item rows the cut leaves
-  a.out_count = out_count; a.out_idx = out_idx; a.out_llr = out_llr;
+  a.out_count = c.out_count; a.out_idx = c.out_idx; a.out_llr = c.out_llr;
   a.err = reinterpret_cast<unsigned long long*>(stats + 1 + 4 * urcco::NBINS);
   a.cand = s->timing ? cand : nullptr;
   if (s->timing) HIPC(hipMemsetAsync(cand, 0, sizeof(unsigned long long) * urcco::CAND_SLOTS, s->stream));
@@ -543,26 +547,25 @@ int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_
   for (int step = 0; step < urcco::NBINS; ++step) {
     const int bin = urcco::NBINS - 1 - step;
     s->begin(URCCO_STAGE_CCO_BIN0 + bin);
-    HIPC(urcco::launch_cco_rows_bin(s->stream, s->n_cu, a, bin, n));
+    HIPC(urcco::launch_cco_rows_bin(s->stream, s->n_cu, a, plan, bin, n));
     s->end();
   }
-  if (s->timing) HIPC(urcco::launch_bin_out_stats(s->stream, bin_rows, bin_off, item_lo, out_count, cand, stats));
+  if (s->timing) HIPC(urcco::launch_bin_out_stats(s->stream, bin_rows, bin_off, item_lo, c.out_count, cand, stats));
   return URCCO_OK;
 }
 
-int pack_counts(urcco_session* s, const int64_t* b_row_ptr, int64_t n_rows_b, const int32_t* b_col_idx, int64_t nnz_bound, const int32_t* counts_b, int32_t n_cols_b,
-                int32_t* out, int32_t* bad) {
-  if (!s || !b_row_ptr || n_rows_b < 0 || nnz_bound < 0 || !out || !bad || (nnz_bound > 0 && (!b_col_idx || !counts_b))) return fail(URCCO_BAD_ARG, "pack_counts: bad argument");
+int pack_counts(urcco_session* s, const BPrime& b, int32_t* out, int32_t* bad) {
+  if (!s || !b.row_ptr || b.n_rows < 0 || b.nnz_bound < 0 || !out || !bad || (b.nnz_bound > 0 && (!b.words || !b.counts))) return fail(URCCO_BAD_ARG, "pack_counts: bad argument");
   int key_bits = 0;
-  URC(packed_key_bits(n_cols_b, &key_bits));
+  URC(packed_key_bits(b.n_cols, &key_bits));
   const int count_bits = 32 - key_bits;
   // the gathers read the 16-bit copy of the counts (half the table: 4 MB for a 2M-item catalogue) -- arena scratch, needed until the pack kernel has run
   unsigned short* c16;
   int32_t* bad16;
-  URC(ArenaLayout(s).add(&c16, (size_t)n_cols_b + 8).add(&bad16, 1).commit());
+  URC(ArenaLayout(s).add(&c16, (size_t)b.n_cols + 8).add(&bad16, 1).commit());
   s->begin(URCCO_STAGE_ENTROPY);
-  HIPC(urcco::launch_narrow_counts(s->stream, s->n_cu, counts_b, n_cols_b, c16, bad16));
-  HIPC(urcco::launch_pack_counts(s->stream, s->n_cu, b_col_idx, b_row_ptr + n_rows_b, nnz_bound, c16, bad16, count_bits, out, bad));
+  HIPC(urcco::launch_narrow_counts(s->stream, s->n_cu, b.counts, b.n_cols, c16, bad16));
+  HIPC(urcco::launch_pack_counts(s->stream, s->n_cu, b.words, b.row_ptr + b.n_rows, b.nnz_bound, c16, bad16, count_bits, out, bad));
   s->end();
   return URCCO_OK;
 }

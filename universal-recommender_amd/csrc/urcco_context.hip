@@ -160,12 +160,10 @@ struct EvState {
   DBuf<double> c_llr;
   DBuf<int64_t> stats;
   DBuf<unsigned long long> verr;
-  DBuf<int32_t> b_pk;           // B' with the columns' counts aboard (CcoArgs::b_packed): rebuilt per build from b_ci + the post-sampling counts ...
+  DBuf<int32_t> b_pk;           // B' with the columns' counts aboard (CcoArgs::b_packed): rebuilt per build from a plain b + the post-sampling counts ...
   DBuf<int32_t> pk_bad;         // ... and [1] counts that did not fit
   DBuf<int32_t> s_pk;           // sharded builds: this rank's own down-sampled shard with the counts aboard -- what it SENDS when every count fits (the
-                                // receivers' f_ci then holds packed words: b_pk_known)
-  bool b_pk_known = false;      // b_ci holds packed words and the host knows it (see cco_rows_impl)
-  uint32_t b_col_mask = 0xffffffffu;  // b_ci[e] & b_col_mask = the column
+                                // receivers' f_ci then holds packed words: a known-good BPrime)
   MappedWord h_verr;  // the boundary check's result is STORED here by the GPU (host level, one GPU)
   DBuf<unsigned> pre_pstart;    // this event type's share of the fused expand preparation (builds with >= 2 secondaries)
   DBuf<int32_t> pre_plen;
@@ -180,10 +178,7 @@ struct EvState {
   Event ev_sampled, ev_done, ev_rp;
   Event ev_cons[A_SETS];  // ev_cons[q]: the A'B_d of the last build that used the primary's buffer set q has finished
   bool cons_valid[A_SETS] = {};
-  // facts of the current build
-  const int64_t* b_rp = nullptr;  // the B this GPU multiplies with
-  const int32_t* b_ci = nullptr;
-  int64_t b_rows = 0, b_nnz_bound = 0;
+  BPrime b;  // fact of the current build: the B this GPU multiplies with (set_b_prime)
 };
 
 struct DevState {
@@ -493,8 +488,14 @@ int stage_downsample(urcco_context* c, DevState& D, int d, const Shard& sh, cons
                               E.s_ci.p, post_of(D, d).p);
 }
 
+// The B' event type d of this GPU multiplies with in the current build, with the event type's final post-sampling counts: plain columns (down-sampled here, or
+// received as such) or the packed words a sharded build received once the shard sizes said that every count fits
+void set_b_prime(DevState& D, int d, int64_t n_cols, bool packed_good, const int64_t* row_ptr, const int32_t* words, int64_t n_rows, int64_t nnz_bound) {
+  D.ev[(size_t)d].b = BPrime(row_ptr, words, n_rows, nnz_bound, (int32_t)n_cols, post_of(D, d).p, packed_good);
+}
+
 // A'B_d for the GPU's item range + strided -> CSR, on event d's stream
-int stage_rows(DevState& D, EvState& E, EvState& A, int d, const DsParams& pa, const DsParams& p, int64_t n_users, int64_t a_nnz_bound, bool pre_expanded = false) {
+int stage_rows(DevState& D, EvState& E, int d, const DsParams& pa, const DsParams& p, int64_t n_users, int64_t a_nnz_bound, bool pre_expanded = false) {
   const int32_t n = D.item_hi - D.item_lo;
   const size_t strided = (size_t)(n > 0 ? n : 1) * (size_t)p.k;
   URC(E.o_count.ensure((size_t)n + 1));
@@ -507,16 +508,21 @@ int stage_rows(DevState& D, EvState& E, EvState& A, int d, const DsParams& pa, c
   // B' with the columns' counts aboard (round 6): one pass over the matrix this GPU multiplies with, with the FINAL post-sampling counts (all-reduced in a
   // sharded build) -- the row kernels then read a candidate's cB off the word that claims its slot instead of gathering it
   // (a sharded build packs on the SENDING side -- a rank's own shard is 1 / W of the matrix, what it receives about half of it -- and learns with the
-  // shard sizes whether every count fits: the rows then arrive packed, b_pk_known)
-  if (!E.b_pk_known) {
-    URC(E.b_pk.ensure((size_t)E.b_nnz_bound + 4));
+  // shard sizes whether every count fits: the rows then arrive packed, a known-good BPrime)
+  RowsCall c;
+  c.b = E.b;
+  if (!E.b.known_good()) {
+    URC(E.b_pk.ensure((size_t)E.b.nnz_bound + 4));
     URC(E.pk_bad.ensure(1));
-    URC(pack_counts(E.s, E.b_rp, E.b_rows, E.b_ci, E.b_nnz_bound, post_of(D, d).p, (int32_t)p.n_cols, E.b_pk.p, E.pk_bad.p));
+    URC(pack_counts(E.s, E.b, E.b_pk.p, E.pk_bad.p));
+    c.b = E.b.with_copy(E.b_pk.p, E.pk_bad.p);
   }
-  URC(cco_rows_impl(E.s, D.item_lo, D.item_hi, (int32_t)pa.n_cols, D.a_cp[D.par].p, D.a_ri[D.par].p, a_nnz_bound, E.b_rp, E.b_ci, (int32_t)p.n_cols,
-                    post_of(D, 0).p, post_of(D, d).p, n_users, d == 0 ? 1 : 0, p.k, p.has_min_llr, p.min_llr, E.o_count.p, E.o_idx.p, E.o_llr.p, E.stats.p,
-                    pre_expanded ? E.pre_pstart.p : nullptr, pre_expanded ? E.pre_plen.p : nullptr, pre_expanded ? E.pre_tsum.p : nullptr,
-                    E.b_pk_known ? nullptr : E.b_pk.p, E.b_pk_known ? nullptr : E.pk_bad.p, E.b_pk_known, E.b_nnz_bound));
+  c.item_lo = D.item_lo; c.item_hi = D.item_hi; c.n_items_a = (int32_t)pa.n_cols;
+  c.a_col_ptr = D.a_cp[D.par].p; c.a_row_idx = D.a_ri[D.par].p; c.nnz_a_bound = a_nnz_bound; c.counts_a = post_of(D, 0).p;
+  c.n_users = n_users; c.exclude_self = d == 0 ? 1 : 0; c.k = p.k; c.has_min_llr = p.has_min_llr; c.min_llr = p.min_llr;
+  c.out_count = E.o_count.p; c.out_idx = E.o_idx.p; c.out_llr = E.o_llr.p; c.stats_dev = E.stats.p;
+  if (pre_expanded) { c.pre_pstart = E.pre_pstart.p; c.pre_plen = E.pre_plen.p; c.pre_tile_sums = E.pre_tsum.p; }
+  URC(cco_rows_impl(E.s, c));
   URC(urcco_dev_compact_indicators(E.s, n, p.k, E.o_count.p, E.o_idx.p, E.o_llr.p, E.c_rp.p, E.c_idx.p, E.c_llr.p));
   HIPC(hipEventRecord(E.ev_done, E.s->stream));
   HIPC(hipEventRecord(E.ev_cons[D.par], E.s->stream));
@@ -634,13 +640,8 @@ int build_single(urcco_context* c, DevState& D, const std::vector<Shard>& sh, co
     EvState& E = D.ev[(size_t)d];
     if (E.s != A.s) HIPC(hipStreamWaitEvent(E.s->stream, D.a_ready, 0));
     if (fuse && E.s != D.ev[1].s) HIPC(hipStreamWaitEvent(E.s->stream, D.b_expanded, 0));
-    E.b_rp = E.s_rp.p;
-    E.b_ci = E.s_ci.p;
-    E.b_pk_known = false;
-    E.b_col_mask = 0xffffffffu;
-    E.b_rows = sh[(size_t)d].n_rows;
-    E.b_nnz_bound = sh[(size_t)d].nnz;
-    URC(stage_rows(D, E, A, d, ps_[0], ps_[(size_t)d], n_users, sh[0].nnz, fuse));
+    set_b_prime(D, d, ps_[(size_t)d].n_cols, false, E.s_rp.p, E.s_ci.p, sh[(size_t)d].n_rows, sh[(size_t)d].nnz);
+    URC(stage_rows(D, E, d, ps_[0], ps_[(size_t)d], n_users, sh[0].nnz, fuse));
     if (gate && gate->trace) gate->trace->mark("chain enqueued", d);
     // (one enqueueing thread for everything -- URCCO_FLAG_SINGLE_STREAM: the downloads wait until every chain is enqueued, see below)
     if (threaded && gate && gate->after_chain) URC(gate->after_chain(d));
@@ -692,14 +693,9 @@ int build_single(urcco_context* c, DevState& D, const std::vector<Shard>& sh, co
   a_ok = st == URCCO_OK;
   a_recorded.set_value();  // also on failure: the workers must not wait forever
   auto rows_primary = [&]() -> int {
-    A.b_rp = A.s_rp.p;
-    A.b_ci = A.s_ci.p;
-    A.b_pk_known = false;
-    A.b_col_mask = 0xffffffffu;
-    A.b_rows = sh[0].n_rows;
-    A.b_nnz_bound = sh[0].nnz;
+    set_b_prime(D, 0, ps_[0].n_cols, false, A.s_rp.p, A.s_ci.p, sh[0].n_rows, sh[0].nnz);
     if (fold && A.s != D.ev[1].s) HIPC(hipStreamWaitEvent(A.s->stream, D.b_expanded, 0));
-    URC(stage_rows(D, A, A, 0, ps_[0], ps_[0], n_users, sh[0].nnz, fold));
+    URC(stage_rows(D, A, 0, ps_[0], ps_[0], n_users, sh[0].nnz, fold));
     if (gate && gate->trace) gate->trace->mark("chain enqueued", 0);
     return URCCO_OK;
   };
@@ -840,7 +836,7 @@ int input_phase(urcco_context* c, int d, const std::vector<std::vector<Shard>>& 
     if (!no_pack) {
       URC(E.s_pk.ensure((size_t)s.nnz + 4));
       URC(E.pk_bad.ensure(1));
-      URC(pack_counts(E.s, E.s_rp.p, s.n_rows, E.s_ci.p, s.nnz, post_of(D, d).p, (int32_t)p.n_cols, E.s_pk.p, E.pk_bad.p));
+      URC(pack_counts(E.s, BPrime(E.s_rp.p, E.s_ci.p, s.n_rows, s.nnz, (int32_t)p.n_cols, post_of(D, d).p, false), E.s_pk.p, E.pk_bad.p));
     }
   }
   std::vector<int64_t> off((size_t)c->world), cnt((size_t)c->world, 8 * XS);
@@ -900,12 +896,6 @@ int exchange_phase(urcco_context* c, int d, const std::vector<std::vector<Shard>
   for (int r = 0; r < W; ++r) deg16 = deg16 && sizes[(size_t)XS * r + 2] == 0;
   bool packed_ok = true;  // the rows travel with their counts aboard: every rank's verdict on the (same) count table (input_phase)
   for (int r = 0; r < W; ++r) packed_ok = packed_ok && sizes[(size_t)XS * r + 3] == 0;
-  uint32_t col_mask = 0xffffffffu;
-  if (packed_ok) {
-    int key_bits = 1;
-    while (((int64_t)1 << key_bits) <= ps[(size_t)d].n_cols) ++key_bits;
-    col_mask = key_bits >= 32 ? 0xffffffffu : (1u << key_bits) - 1u;
-  }
   const int64_t deg_bytes = deg16 ? 2 : 4;
   for (int r = 0; r < W; ++r) {
     off_r[(size_t)r] = rows * deg_bytes;
@@ -1045,17 +1035,9 @@ int exchange_phase(urcco_context* c, int d, const std::vector<std::vector<Shard>
     if (deg16) HIPC(urcco::launch_scan_u16(E.s->stream, E.f_deg16.p, rows, E.f_rp.p, E.scan_tmp.p));
     else HIPC(urcco::launch_scan_i32(E.s->stream, E.f_deg.p, rows, E.f_rp.p, E.scan_tmp.p));
     E.s->end();
-    E.b_rp = E.f_rp.p;
-    E.b_ci = E.f_ci.p;
-    E.b_pk_known = packed_ok;
-    E.b_col_mask = col_mask;
-    E.b_rows = rows;
-    E.b_nnz_bound = nnz;
-    if (filt) {
-      int64_t nnz_in = 0;
-      for (int p = 0; p < W; ++p) nnz_in += T[(size_t)p * W + D.rank];
-      E.b_nnz_bound = nnz_in;
-    }
+    int64_t held = 0;  // the entries this rank holds: what every rank sent it through the filtered exchange, else every rank's whole shard (= nnz)
+    for (int p = 0; p < W; ++p) held += filt ? T[(size_t)p * W + D.rank] : sizes[(size_t)XS * p + 1];
+    set_b_prime(D, d, ps[(size_t)d].n_cols, packed_ok, E.f_rp.p, E.f_ci.p, rows, held);
   }
   return URCCO_OK;
 }
@@ -1173,7 +1155,7 @@ int build_sharded(urcco_context* c, const std::vector<std::vector<Shard>>& sh, c
       URC(urcco_dev_transpose(A.s, n_users, A.f_rp.p, A.f_ci.p, a_nnz, n_items_a, post_of(D, 0).p, D.item_lo, D.item_hi, D.a_cp[D.par].p, D.a_ri[D.par].p));
     }
     HIPC(hipEventRecord(D.a_ready, A.s->stream));
-    return stage_rows(D, A, A, 0, ps[0], ps[0], n_users, D.a_ents);
+    return stage_rows(D, A, 0, ps[0], ps[0], n_users, D.a_ents);
   }));
   // ---- secondaries: every input phase is enqueued on its own stream (they run under A'A); then per event type the shard
   // sizes are read (the host waits for that stream's sampling only), the exchange is issued and A'B_d runs behind it
@@ -1208,7 +1190,7 @@ int build_sharded(urcco_context* c, const std::vector<std::vector<Shard>>& sh, c
         URC(E.pre_plen.ensure((size_t)D.a_ents + 1));
         URC(E.pre_tsum.ensure(scan_tile_words(D.a_ents)));
         ts[(size_t)d - 1] = E.pre_tsum.p;
-        rp[(size_t)d - 1] = E.b_rp;
+        rp[(size_t)d - 1] = E.b.row_ptr;
         pst[(size_t)d - 1] = E.pre_pstart.p;
         pl[(size_t)d - 1] = E.pre_plen.p;
       }
@@ -1219,7 +1201,7 @@ int build_sharded(urcco_context* c, const std::vector<std::vector<Shard>>& sh, c
       EvState& E = D.ev[(size_t)d];
       if (E.s != D.ev[0].s) HIPC(hipStreamWaitEvent(E.s->stream, D.a_ready, 0));
       if (fuse && D.a_ents > 0 && E.s != D.ev[1].s) HIPC(hipStreamWaitEvent(E.s->stream, D.b_expanded, 0));
-      URC(stage_rows(D, E, D.ev[0], d, ps[0], ps[(size_t)d], n_users, D.a_ents, fuse && D.a_ents > 0));
+      URC(stage_rows(D, E, d, ps[0], ps[(size_t)d], n_users, D.a_ents, fuse && D.a_ents > 0));
     }
     return URCCO_OK;
   }));
@@ -1576,8 +1558,8 @@ int urcco_context_build_device(urcco_context* c, const urcco_dev_dataset* datase
         urcco_dev_result& r = out[(size_t)d * L + g];
         r.item_lo = D.item_lo; r.item_hi = D.item_hi;
         r.row_ptr = E.c_rp.p; r.col_idx = E.c_idx.p; r.llr = E.c_llr.p; r.stats = E.stats.p;
-        r.sampled_row_ptr = E.b_rp; r.sampled_col_idx = E.b_ci; r.sampled_rows = E.b_rows;
-        r.sampled_col_mask = (int32_t)E.b_col_mask;
+        r.sampled_row_ptr = E.b.row_ptr; r.sampled_col_idx = E.b.words; r.sampled_rows = E.b.n_rows;
+        r.sampled_col_mask = (int32_t)E.b.col_mask();
         r.sampled_nnz_total = c->exchange() && (size_t)d < c->h_sizes.size() ? c->h_sizes[(size_t)d] : -1;
       }
     return URCCO_OK;

@@ -93,13 +93,47 @@ inline size_t scan_tile_words(int64_t n) { return (size_t)((n + urcco::SCAN_TILE
 
 // packed accumulator entry: key = column + 1 in the high bits, count in the low ones.  *key_bits = the bits of a key (values 1..n_cols_b; the column
 // itself fits them too), the count keeps the other 32 - *key_bits
-inline int packed_key_bits(int32_t n_cols_b, int* key_bits) {
+inline int key_bits_of(int64_t n_cols_b) {
   int b = 1;
-  while (((int64_t)1 << b) <= (int64_t)n_cols_b) ++b;
+  while (((int64_t)1 << b) <= n_cols_b) ++b;
+  return b;
+}
+inline int packed_key_bits(int32_t n_cols_b, int* key_bits) {
+  const int b = key_bits_of(n_cols_b);
   if (32 - b < 1) return fail(URCCO_BAD_ARG, "n_cols_b %d too large for the packed accumulator", n_cols_b);
   *key_bits = b;
   return URCCO_OK;
 }
+
+// B': the matrix a GPU multiplies A' with, as the row kernels take it.  What `words` hold comes in exactly three forms, and only the two members below set one:
+//   plain (the constructor, packed_good = false): column indices; the row kernels gather the columns' counts
+//   plain + packed copy (with_copy() of a plain one): column indices, and beside them the copy with the counts aboard that launch_pack_counts made (`packed`)
+//       with its device-side verdict (`pack_bad`): the device decides which of the two is read
+//   packed, known good (the constructor, packed_good = true): col | cB << key bits, and the HOST knows that every count fits (the rows a sharded build
+//       received travelled in that form); no plain copy exists, every reader masks.  nnz_bound is then one the host trusts (< 0: none)
+struct BPrime {
+  const int64_t* row_ptr = nullptr;
+  const int32_t *words = nullptr, *counts = nullptr;  // counts: the columns' post-sampling counts
+  int64_t n_rows = 0, nnz_bound = -1;
+  int32_t n_cols = 0;
+  BPrime() = default;
+  BPrime(const int64_t* rp, const int32_t* w, int64_t rows, int64_t bound, int32_t cols, const int32_t* cnt, bool packed_good)
+      : row_ptr(rp), words(w), counts(cnt), n_rows(rows), nnz_bound(bound), n_cols(cols), good_(packed_good) {}
+  BPrime with_copy(const int32_t* packed, const int32_t* pack_bad) const {  // (both non-NULL; a copy never comes with known-good words)
+    BPrime b(row_ptr, words, n_rows, nnz_bound, n_cols, counts, false);
+    b.packed_ = packed; b.pack_bad_ = pack_bad;
+    return b;
+  }
+  bool known_good() const { return good_; }
+  const int32_t* packed() const { return packed_; }      // NULL unless with_copy()
+  const int32_t* pack_bad() const { return pack_bad_; }  // ... and so is this
+  // words[e] & col_mask() = the column (CcoArgs::b_col_mask, urcco_dev_result::sampled_col_mask)
+  uint32_t col_mask() const { return good_ ? (1u << key_bits_of(n_cols)) - 1u : 0xffffffffu; }  // (a 32-bit n_cols has at most 31 key bits)
+
+ private:
+  bool good_ = false;
+  const int32_t *packed_ = nullptr, *pack_bad_ = nullptr;
+};
 
 // ---- owners of device objects: move-only, released by their destructors, so a struct that holds them needs no release list.  What it does need:
 // its device is current and its streams are drained when it goes away (urcco_session_destroy, urcco_context_destroy) ----
@@ -163,17 +197,24 @@ struct MappedWord {  // one host-mapped, coherent pinned word the GPU stores to:
 }  // namespace urcco_detail
 
 namespace urcco_detail {
-// urcco_dev_cco_rows with one secondary's share of a fused expand preparation handed in (both NULL: it prepares its own)
-int cco_rows_impl(urcco_session* s, int32_t item_lo, int32_t item_hi, int32_t n_items_a, const int64_t* a_col_ptr, const int32_t* a_row_idx, int64_t nnz_a_bound,
-                  const int64_t* b_row_ptr, const int32_t* b_col_idx, int32_t n_cols_b, const int32_t* counts_a, const int32_t* counts_b, int64_t n_users,
-                  int32_t exclude_self, int32_t k, int32_t has_min_llr, double min_llr, int32_t* out_count, int32_t* out_idx, double* out_llr, int64_t* stats_dev,
-                  const unsigned* pre_pstart, const int32_t* pre_plen, int64_t* pre_tile_sums = nullptr /* the scan-tile sums of pre_plen, left by expand_multi */,
-                  const int32_t* b_packed = nullptr /* B' with the columns' counts aboard (launch_pack_counts) ... */, const int32_t* pack_bad = nullptr /* ... and its verdict */,
-                  bool pk_known = false /* b_col_idx itself holds such words and the host knows they are good (sharded builds) */,
-                  int64_t b_nnz_bound = -1 /* pk_known: an upper bound of B' entries, if the host has one (with it the host can know the form of the expand tables) */);
-// B' with counts aboard for cco_rows_impl: out[e] = b_col_idx[e] | counts_b[b_col_idx[e]] << key bits, e < b_row_ptr[n_rows_b] (<= nnz_bound); bad[0] = counts that do not fit
-int pack_counts(urcco_session* s, const int64_t* b_row_ptr, int64_t n_rows_b, const int32_t* b_col_idx, int64_t nnz_bound, const int32_t* counts_b, int32_t n_cols_b,
-                int32_t* out, int32_t* bad);
+// One A'B call: urcco_dev_cco_rows, urcco_dev_cco_rows_packed and the contexts' stage_rows fill it by name.
+struct RowsCall {
+  int32_t item_lo = 0, item_hi = 0, n_items_a = 0;  // the item range of A', its CSC and its post-sampling counts
+  const int64_t* a_col_ptr = nullptr;
+  const int32_t *a_row_idx = nullptr, *counts_a = nullptr;
+  int64_t nnz_a_bound = 0, n_users = 0;
+  BPrime b;
+  int32_t exclude_self = 0, k = 0, has_min_llr = 0;
+  double min_llr = 0.0;
+  int32_t *out_count = nullptr, *out_idx = nullptr;  // strided by k
+  double* out_llr = nullptr;
+  int64_t* stats_dev = nullptr;  // nullable
+  // this event type's share of a fused expand preparation (expand_multi), with the scan-tile sums of plen: all three, or none (it prepares its own)
+  const unsigned* pre_pstart = nullptr; const int32_t* pre_plen = nullptr; int64_t* pre_tile_sums = nullptr;
+};
+int cco_rows_impl(urcco_session* s, const RowsCall& c);
+// The copy of a plain B' with the counts aboard (BPrime::with_copy): out[e] = words[e] | counts[words[e]] << key bits, e < row_ptr[n_rows] (<= nnz_bound); bad[0] = counts that do not fit
+int pack_counts(urcco_session* s, const BPrime& b, int32_t* out, int32_t* bad);
 int partition_dev(urcco_session* s, int32_t n_items, const int64_t* work, int32_t n_parts, int32_t* bounds_dev, int32_t** bounds_out);
 int expand_multi(urcco_session* s, int n, const int64_t* a_col_ptr, int32_t n_items_a, const int32_t* a_row_idx, int64_t cap, const int64_t* const* b_row_ptr,
                  int64_t n_users, unsigned* const* pstart, int32_t* const* plen, int64_t* const* tile_sums = nullptr /* [d]: scan_tile_words(cap) words */);
