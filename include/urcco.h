@@ -656,7 +656,7 @@ int urcco_dev_u01_rng(urcco_session* s, int64_t n, int32_t seed, const int32_t* 
 
 /* ---- DEVICE level: Preparator (reference src/main/scala/Preparator.scala:44-87, :102-158, :160-214) -------------
  * Dictionaries and binary CSR matrices from event streams of 64-bit keys resident in HBM (the host hashes its id
- * strings or passes integer ids; the value ~0 is reserved).  Dense ids follow FIRST APPEARANCE in the stream
+ * strings or passes integer ids; the value ~0, i.e. the integer id -1, is reserved).  Dense ids follow FIRST APPEARANCE in the stream
  * (oracle decision D8), so the host recovers the id -> string dictionary from `first_pos` alone. */
 typedef struct urcco_key_table urcco_key_table;
 
@@ -669,7 +669,10 @@ int urcco_hash_strings(const uint8_t* bytes, const int64_t* offsets, int64_t n, 
  * occur at least min_count times (`minEventsPerUser` counts RAW events, Preparator.scala:129-132); other keys get no id.
  * select (nullable, device int32[n]): positions with select[p] < 0 do not take part (events of dropped users,
  * Preparator.scala:173-179).  first_pos (device int64, capacity n): first_pos[id] = stream position of the id's first
- * occurrence.  *n_ids is written on the host (the call synchronises the stream). */
+ * occurrence.  *n_ids is written on the host (the call synchronises the stream).
+ * The key ~0 (2^64 - 1: the integer id -1) marks an empty slot of the table and is not a key: if a position that takes part holds it the
+ * call returns URCCO_BAD_ARG, the message names the reserved key, no table is handed out and *table stays NULL.  A position masked by
+ * select may hold it.  (urcco_dev_dictionary_lookup answers -1 for it, the verify calls skip it.) */
 int urcco_dev_dictionary_build(urcco_session* s, int64_t n, const uint64_t* keys, const int32_t* select, int32_t min_count,
                                int64_t* first_pos, urcco_key_table** table, int64_t* n_ids);
 /* ids[p] = dense id of keys[p], or -1 (key without id, or select[p] < 0).  No host synchronisation. */

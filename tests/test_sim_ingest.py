@@ -17,16 +17,23 @@ def key64(s: str) -> int:
     return v - (1 << 64) if v >= (1 << 63) else v   # as the int64 bit pattern
 
 
-def keys_tensor(strings, device):
-    return torch.tensor([key64(s) for s in strings], dtype=torch.int64, device=device)
+def on_device(sess, values):
+    """int64 values in a tensor of the session (under guard pages: one that ends at a guard page, conftest.sim_session)."""
+    a = np.asarray(values, dtype=np.int64)
+    t = sess.empty(a.size, torch.int64)
+    t.copy_(torch.from_numpy(a))
+    return t
+
+
+def keys_tensor(strings, sess):
+    return on_device(sess, [key64(s) for s in strings])
 
 
 def check_prepare(sess, actions, min_events):
     from universal_recommender_amd import ingest
-    dev = sess.device
     ref = PO.prepare(actions, min_events)
     nonempty = [(n, e) for (n, e) in actions if len(e) > 0]           # DataSource.scala:89 (the host drops them)
-    dev_actions = [(n, keys_tensor([u for u, _ in e], dev), keys_tensor([i for _, i in e], dev)) for (n, e) in nonempty]
+    dev_actions = [(n, keys_tensor([u for u, _ in e], sess), keys_tensor([i for _, i in e], sess)) for (n, e) in nonempty]
     got = ingest.prepare_device(sess, dev_actions, min_events)
     sess.synchronize()
     assert len(got.events) == len(ref)
@@ -217,8 +224,7 @@ def test_native_string_hash_known_answers_and_collision_check(sim_session, sim_l
         assert got2 == [xxhash.xxh64_intdigest(s.encode(), seed=CHECK_SEED) for s in strs]
     except ImportError:
         pass
-    dev = sim_session.device
-    t = lambda x: torch.from_numpy(np.asarray(x, np.int64)).to(dev)
+    t = lambda x: on_device(sim_session, x)
     users, items = [f"u{i % 7}" for i in range(40)], [f"i{i % 11}" for i in range(40)]
     uk, ik = hash_keys(users, 0, sim_lib), hash_keys(items, 0, sim_lib)
     uc, ic = hash_keys(users, CHECK_SEED, sim_lib), hash_keys(items, CHECK_SEED, sim_lib)

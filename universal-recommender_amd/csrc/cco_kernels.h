@@ -165,9 +165,10 @@ struct KeyTable {
   int32_t* id;               // [capacity] dense id (first-appearance order), -1 = none
   unsigned long long mask;
 };
-// flag: int32[n] scratch, prefix: int64[n + 1] scratch (prefix[n] = number of ids), first_pos: int64[>= ids] out
+// flag: int32[n] scratch, prefix: int64[n + 1] scratch (prefix[n] = number of ids), first_pos: int64[>= ids] out,
+// reserved: one word out = selected positions holding the reserved key ~0 (nothing was inserted for them: the caller refuses the build)
 hipError_t launch_dictionary_build(hipStream_t st, int n_cu, KeyTable t, int64_t n, const unsigned long long* keys, const int32_t* select,
-                                   int32_t min_count, int32_t* flag, int64_t* prefix, int64_t* tile_sums, int64_t* first_pos);
+                                   int32_t min_count, int32_t* flag, int64_t* prefix, int64_t* tile_sums, int64_t* first_pos, unsigned* reserved);
 hipError_t launch_dictionary_lookup(hipStream_t st, int n_cu, KeyTable t, int64_t n, const unsigned long long* keys, const int32_t* select,
                                     int32_t* ids);
 hipError_t launch_dictionary_verify(hipStream_t st, int n_cu, KeyTable t, int64_t n, const unsigned long long* keys, const int32_t* select,

@@ -7,7 +7,8 @@
 //                occur at least min_count times (`minEventsPerUser`, raw events, duplicates included: :129-132)
 //   lookup       ids of a stream against an existing dictionary (-1 = not in it: :173-179 drop such events)
 //   CSR build    (row id, column id) pairs -> rows with sorted, duplicate-free columns (`setQuick(col, 1.0)`: :146, :205)
-// Keys are 64-bit (the host hashes its strings, or passes integer ids); ~0 is reserved for "empty slot".
+// Keys are 64-bit (the host hashes its strings, or passes integer ids); ~0 is reserved for "empty slot": the insert pass counts
+// the selected positions that hold it and leaves the table alone for them, and the build is refused (urcco_api.hip).
 // First-appearance ids need no sort: every slot keeps the smallest position of its key (atomicMin); an event is a
 // "first" iff its position equals that minimum; the id of a key is the number of firsts before its own first -- one
 // exclusive scan over the stream.
@@ -42,11 +43,18 @@ __device__ __forceinline__ unsigned long long ig_find(const KeyTable& t, unsigne
 // two thirds of the whole ingest).  A key never changes once written, the position minimum only decreases and the count only
 // matters up to `need` (min_count), so each of the three is read first and the atomic issued only if it can still change
 // something; a stale read (L1 is not coherent with other CUs' atomics) costs one unnecessary atomic, never a wrong result.
+// reserved[0] counts the selected positions that hold IG_EMPTY itself: such a key cannot be told from a free slot (its CAS would "claim" the slot
+// without changing it, and the next real key to probe there would inherit its position minimum), so the table is not touched for it.
 __global__ __launch_bounds__(256) void ig_insert_kernel(KeyTable t, int64_t n, const unsigned long long* __restrict__ keys,
-                                                        const int32_t* __restrict__ select, unsigned need) {
+                                                        const int32_t* __restrict__ select, unsigned need, unsigned* __restrict__ reserved) {
+  unsigned n_reserved = 0;
   for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n; p += (int64_t)gridDim.x * 256) {
     if (select && select[p] < 0) continue;
     const unsigned long long key = keys[p];
+    if (key == IG_EMPTY) {
+      ++n_reserved;
+      continue;
+    }
     unsigned long long slot = ig_mix(key) & t.mask;
     for (;;) {
       unsigned long long cur = t.keys[slot];
@@ -59,6 +67,7 @@ __global__ __launch_bounds__(256) void ig_insert_kernel(KeyTable t, int64_t n, c
       slot = (slot + 1) & t.mask;
     }
   }
+  if (n_reserved) atomicAdd(reserved, n_reserved);
 }
 
 // flag[p] = 1 iff event p is the first appearance of a key that occurs at least min_count times
@@ -106,11 +115,13 @@ static unsigned ig_grid(int64_t n, int n_cu) {
 }
 
 hipError_t launch_dictionary_build(hipStream_t st, int n_cu, KeyTable t, int64_t n, const unsigned long long* keys, const int32_t* select,
-                                   int32_t min_count, int32_t* flag, int64_t* prefix, int64_t* tile_sums, int64_t* first_pos) {
+                                   int32_t min_count, int32_t* flag, int64_t* prefix, int64_t* tile_sums, int64_t* first_pos, unsigned* reserved) {
+  hipError_t e = hipMemsetAsync(reserved, 0, sizeof(unsigned), st);
+  if (e != hipSuccess) return e;
   if (n == 0) return hipMemsetAsync(prefix, 0, sizeof(int64_t), st);
-  hipLaunchKernelGGL(ig_insert_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, t, n, keys, select, (unsigned)(min_count < 1 ? 1 : min_count));
+  hipLaunchKernelGGL(ig_insert_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, t, n, keys, select, (unsigned)(min_count < 1 ? 1 : min_count), reserved);
   hipLaunchKernelGGL(ig_first_flags_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, t, n, keys, select, (unsigned)(min_count < 1 ? 1 : min_count), flag);
-  hipError_t e = launch_scan_i32(st, flag, n, prefix, tile_sums);
+  e = launch_scan_i32(st, flag, n, prefix, tile_sums);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(ig_assign_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, t, n, keys, flag, prefix, first_pos);
   return hipGetLastError();

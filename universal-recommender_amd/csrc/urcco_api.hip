@@ -639,12 +639,18 @@ int urcco_dev_dictionary_build(urcco_session* s, int64_t n, const uint64_t* keys
   HIPC(hipMemsetAsync(tab->t.id, 0xFF, sizeof(int32_t) * (size_t)cap, s->stream));
   int32_t* flag;
   int64_t *prefix, *tile_sums;
-  URC(ArenaLayout(s).add(&flag, (size_t)n).add(&prefix, (size_t)n + 1).add(&tile_sums, scan_tile_words(n)).commit());
+  unsigned* reserved;
+  URC(ArenaLayout(s).add(&flag, (size_t)n).add(&prefix, (size_t)n + 1).add(&tile_sums, scan_tile_words(n)).add(&reserved, 1).commit());
   HIPC(urcco::launch_dictionary_build(s->stream, s->n_cu, tab->t, n, reinterpret_cast<const unsigned long long*>(keys), select, min_count, flag, prefix,
-                                      tile_sums, first_pos));
+                                      tile_sums, first_pos, reserved));
   int64_t ids = 0;
+  unsigned n_reserved = 0;
   HIPC(hipMemcpyAsync(&ids, prefix + n, sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+  HIPC(hipMemcpyAsync(&n_reserved, reserved, sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
   HIPC(hipStreamSynchronize(s->stream));
+  if (n_reserved)  // (the table goes with `tab`; *table stays NULL)
+    return fail(URCCO_BAD_ARG, "urcco_dev_dictionary_build: %u selected position(s) hold the reserved key ~0 (2^64 - 1, the integer id -1): it marks an empty slot",
+                n_reserved);
   *n_ids = ids;
   *table = tab.release();
   return URCCO_OK;

@@ -45,7 +45,8 @@ class DevDictionary:
 
 
 def dictionary_build(sess: DeviceSession, keys: torch.Tensor, select: Optional[torch.Tensor] = None, min_count: int = 1) -> DevDictionary:
-    """keys: uint64 stream as an int64 tensor (bit pattern); select: int32[n], positions with a negative entry are ignored."""
+    """keys: uint64 stream as an int64 tensor (bit pattern); select: int32[n], positions with a negative entry are ignored.
+    The key ~0 (the int64 -1) is reserved: a selected position that holds it makes the build fail with BAD_ARG."""
     n = keys.numel()
     first_pos = sess.empty(max(n, 1), torch.int64)
     handle, n_ids = C.c_void_p(), C.c_int64()
@@ -72,11 +73,12 @@ def dictionary_verify(sess: DeviceSession, d: DevDictionary, keys: torch.Tensor,
     return int(bad.value)
 
 
-def dictionary_verify_against(sess: DeviceSession, d: DevDictionary, keys: torch.Tensor, check_keys: torch.Tensor, dict_check_keys: torch.Tensor) -> int:
+def dictionary_verify_against(sess: DeviceSession, d: DevDictionary, keys: torch.Tensor, check_keys: torch.Tensor, dict_check_keys: torch.Tensor,
+                              select: Optional[torch.Tensor] = None) -> int:
     """dictionary_verify for another stream looked up in `d`: its check keys against the check keys of the ids' first occurrences
     in the stream the dictionary was built from."""
     bad = C.c_int64()
-    sess._check(sess.lib.urcco_dev_dictionary_verify_against(sess.handle, d.handle, keys.numel(), _ptr(keys), None, _ptr(check_keys), _ptr(dict_check_keys),
+    sess._check(sess.lib.urcco_dev_dictionary_verify_against(sess.handle, d.handle, keys.numel(), _ptr(keys), _ptr(select), _ptr(check_keys), _ptr(dict_check_keys),
                                                              _ptr(d.first_pos) if d.n_ids else _ptr(sess.empty(1, torch.int64)), C.byref(bad)))
     return int(bad.value)
 
@@ -108,7 +110,9 @@ def prepare_device(sess: DeviceSession, actions: Sequence[Tuple[str, torch.Tenso
     """Preparator.prepare.  actions[d] = (event name, user keys, item keys[, user check keys, item check keys]) with the keys
     as int64 tensors (uint64 bit patterns) resident on the session's device; actions[0] is the primary event type.  With
     check keys (a second, independent hash of the same strings) every dictionary is verified: HashCollision if two
-    different strings were merged into one id."""
+    different strings were merged into one id.
+    The key ~0 is the dictionaries' "empty slot" value: integer ids must not be -1 (UrccoError BAD_ARG for a stream that holds it at a position
+    that takes part); preparator.hash_keys remaps the value for hashed strings."""
     if not actions:
         raise ValueError("need at least the primary event type")
     pu = actions[0][1]
