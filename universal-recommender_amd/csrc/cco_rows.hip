@@ -53,10 +53,23 @@ __device__ __forceinline__ int choose_bin(long long w, long long ca, int32_t n_c
 // at a time (see cco_rows_micro_kernel).  The binning works on INTERNAL bins (0, 1, 2 = the sub-lists, 3 .. = the other classes); towards
 // everything else the micro class stays one bin: bin_off[0 .. NBINS] as before, the sub-lists' starts behind it (bin_off[NBINS + 1], [NBINS + 2]).
 constexpr int MICRO_SUBS = 3;
-constexpr int IBINS = NBINS - 1 + MICRO_SUBS;
+// The one-wave class (bin 1) in three sub-lists, by the same mechanism: rows of <= 64 users and <= 128 pairs, rows of <= 64 users and <= 256 pairs -- they run in
+// the micro-shaped body of cco_rows_small_kernel, two / four pairs per lane --, then the rest of the class.  Internal bins MICRO_SUBS, MICRO_SUBS + 1 and
+// MICRO_SUBS + 2; the first starts at bin_off[1], the other two at bin_off[NBINS + 3] and bin_off[NBINS + 4].  Unsplit (a small build, or a k the fast tail of
+// that body cannot serve: SMALL_KMAX) the two sub-lists are empty and bin_off[NBINS + 4] == bin_off[1].
+constexpr int SMALL_SUBS = 2;
+constexpr int SMALL_P0 = 2, SMALL_P1 = 4;  // pairs per lane of the two sub-lists
+constexpr int SMALL_KMAX = WAVE - 1;       // the prefilter keeps >= k (+ 1 with a self pair) survivors whenever it cuts; the fast tail ranks <= 64, one per lane
+static_assert(SMALL_KMAX + 1 <= WAVE && SMALL_KMAX >= 1, "k + 1 survivors (a self pair among them) must fit the lanes of the fast tail");
+constexpr int IBINS = NBINS - 1 + MICRO_SUBS + SMALL_SUBS;
+constexpr int SPLIT_MICRO = 1, SPLIT_SMALL = 2;  // bits of the binning kernels' `split`
 __device__ __forceinline__ int micro_sub(long long w, long long ca) { return (w <= 16 && ca <= 16) ? 0 : ((w <= 32 && ca <= 32) ? 1 : 2); }
+__device__ __forceinline__ int small_sub(long long w, long long ca) { return ca > WAVE ? 2 : (w <= SMALL_P0 * WAVE ? 0 : (w <= SMALL_P1 * WAVE ? 1 : 2)); }
 __device__ __forceinline__ int internal_bin(int b, long long w, long long ca, int split) {
-  return b < 0 ? -1 : (b == 0 ? (split ? micro_sub(w, ca) : MICRO_SUBS - 1) : b + MICRO_SUBS - 1);
+  if (b < 0) return -1;
+  if (b == 0) return (split & SPLIT_MICRO) ? micro_sub(w, ca) : MICRO_SUBS - 1;
+  if (b == 1) return MICRO_SUBS + ((split & SPLIT_SMALL) ? small_sub(w, ca) : SMALL_SUBS);
+  return b + MICRO_SUBS - 1 + SMALL_SUBS;
 }
 // The micro class is split into its sub-lists only when the build has enough item rows for three launches to pay: a rank of a sharded build (an eighth
 // of config 4's rows) would start 16K waves per sub-list for a handful of passes each (emulated 8-rank build: 3.45 against 3.17 ms of SpGEMM per rank).
@@ -65,13 +78,17 @@ static bool micro_split_for(int32_t n_rows) {
   static const long long min_rows = [] { const char* e = getenv("URCCO_MICRO_SPLIT_ROWS"); return e && *e ? atoll(e) : 1000000ll; }();
   return (long long)n_rows >= min_rows;
 }
-__device__ __forceinline__ int internal_start(const int32_t* __restrict__ bin_off, int ib) {
-  return ib == 0 ? bin_off[0] : (ib < MICRO_SUBS ? bin_off[NBINS + ib] : bin_off[ib - (MICRO_SUBS - 1)]);
+// where the list of internal bin ib starts, as an index into bin_off
+__host__ __device__ constexpr int internal_off_index(int ib) {
+  return ib == 0 ? 0 : (ib < MICRO_SUBS ? NBINS + ib : (ib == MICRO_SUBS ? 1 : (ib <= MICRO_SUBS + SMALL_SUBS ? NBINS + ib - 1 : ib - (MICRO_SUBS - 1 + SMALL_SUBS))));
 }
+static_assert(internal_off_index(MICRO_SUBS + 1) == NBINS + 3 && internal_off_index(MICRO_SUBS + 2) == NBINS + 4 && internal_off_index(MICRO_SUBS + 3) == 2 &&
+              internal_off_index(IBINS - 1) == NBINS - 1, "bin_off layout");
+__device__ __forceinline__ int internal_start(const int32_t* __restrict__ bin_off, int ib) { return bin_off[internal_off_index(ib)]; }
 constexpr int BIN_THREADS = 256;
 constexpr int BIN_ITEMS = BIN_TILE / BIN_THREADS;  // 4
 constexpr int BIN_COLS = IBINS + 2 * NBINS + 1;    // per tile: rows per INTERNAL bin, pairs per bin, users per bin, total pairs
-static_assert(BIN_COLS == BIN_COLS_HOST && BIN_OFF_LEN == NBINS + MICRO_SUBS, "scratch sizes of the callers");
+static_assert(BIN_COLS == BIN_COLS_HOST && BIN_OFF_LEN == NBINS + MICRO_SUBS + SMALL_SUBS, "scratch sizes of the callers");
 
 __global__ __launch_bounds__(BIN_THREADS) void bin_count_kernel(int32_t item_lo, int32_t n, const int64_t* __restrict__ work,
                                                                 const int32_t* __restrict__ cnt_a, int32_t n_cols_b, int32_t count_bits, int32_t k,
@@ -166,10 +183,8 @@ __global__ __launch_bounds__(BS_THREADS) void bin_scan_kernel(int64_t* __restric
   __syncthreads();
   if (threadIdx.x == 0) {
     int32_t off = 0;
-    for (int ib = 0; ib < IBINS; ++ib) {  // list order = internal bin order: the micro sub-lists, then the other classes
-      if (ib == 0) bin_off[0] = off;
-      else if (ib < MICRO_SUBS) bin_off[NBINS + ib] = off;
-      else bin_off[ib - (MICRO_SUBS - 1)] = off;
+    for (int ib = 0; ib < IBINS; ++ib) {  // list order = internal bin order: the micro sub-lists, the one-wave class's, then the other classes
+      bin_off[internal_off_index(ib)] = off;
       off += (int32_t)s_tot[ib];
     }
     bin_off[NBINS] = off;
@@ -177,7 +192,8 @@ __global__ __launch_bounds__(BS_THREADS) void bin_scan_kernel(int64_t* __restric
       for (int k = 0; k < NBINS; ++k) {
         long long rows = 0;
         if (k == 0) for (int q = 0; q < MICRO_SUBS; ++q) rows += s_tot[q];
-        else rows = s_tot[k + MICRO_SUBS - 1];
+        else if (k == 1) for (int q = 0; q <= SMALL_SUBS; ++q) rows += s_tot[MICRO_SUBS + q];
+        else rows = s_tot[k + MICRO_SUBS - 1 + SMALL_SUBS];
         stats[1 + k] = rows;                                      // rows
         stats[1 + NBINS + k] = s_tot[IBINS + k];                  // pairs
         stats[1 + 2 * NBINS + k] = s_tot[IBINS + NBINS + k];      // users (sum of cA over the bin's rows)
@@ -223,7 +239,7 @@ hipError_t launch_binning(hipStream_t st, int32_t item_lo, int32_t n, const int6
     return e;
   }
   const int64_t n_tiles = ((int64_t)n + BIN_TILE - 1) / BIN_TILE;
-  const int split = micro_split_for(n) ? 1 : 0;
+  const int split = micro_split_for(n) ? (SPLIT_MICRO | (k <= SMALL_KMAX ? SPLIT_SMALL : 0)) : 0;
   hipLaunchKernelGGL(bin_count_kernel, dim3((unsigned)n_tiles), dim3(BIN_THREADS), 0, st, item_lo, n, work, cnt_a, n_cols_b, count_bits, k, tile_counts, split);
   hipLaunchKernelGGL(bin_scan_kernel, dim3(1), dim3(BS_THREADS), 0, st, tile_counts, n_tiles, bin_off, stats);
   hipLaunchKernelGGL(bin_scatter_kernel, dim3((unsigned)n_tiles), dim3(BIN_THREADS), 0, st, item_lo, n, work, cnt_a, n_cols_b, count_bits, k,
@@ -610,6 +626,31 @@ __host__ __device__ constexpr unsigned direct_limit(int T, int E) {
   return !prefilter_class(T, E) ? 0u : (T == WAVE ? URCCO_DIRECT_WAVE : (T == 256 ? (E == 4096 ? URCCO_DIRECT_BS : URCCO_DIRECT_B) : (T == 512 ? URCCO_DIRECT_H : URCCO_DIRECT_C)));
 }
 constexpr unsigned PF_BINS = 256;  // bins of the count histogram: cB = 0 .. 254, the last one is the clamp bin and stays empty (a cut never falls in it)
+// The three steps of the k11 = 1 prefilter (the rule is stated at the compaction of cco_rows_kernel), shared by every row body that carries it.
+// 1. a candidate is counted by its cB when k11 = 1 and cB lies below the clamp bin (16-bit counters, two per word)
+__device__ __forceinline__ void pf_count(unsigned* pfh, unsigned k11, unsigned cbq) {
+  if (k11 == 1u && cbq < PF_BINS - 1u) atomicAdd(&pfh[cbq >> 1], 1u << (16 * (cbq & 1u)));
+}
+// 2. the cut c* = the smallest count with `pf_need` counted candidates at or below it; every wave finds it for itself: lane l owns bins 4 l .. 4 l + 3
+//    (ascending: the count of everything at or below a bin is a prefix sum).  pf_lim: this row's limit as loaded (any lane's copy).  False: no cut -- no
+//    pf_need such candidates below the clamp bin, or a limit at or below c* (nothing to drop).  Wave-uniform result; every lane must be active.
+__device__ __forceinline__ bool pf_find_cut(const unsigned* pfh, int lane, unsigned pf_need, unsigned pf_lim, unsigned& cstar, unsigned& lim) {
+  int lq = lane;
+  URCCO_OPAQUE(lq);  // (the histogram addresses are formed here, not kept -- spilled -- across the row loop)
+  const unsigned w01 = pfh[2 * lq], w23 = pfh[2 * lq + 1];
+  const unsigned h0 = w01 & 0xffffu, h1 = w01 >> 16, h2 = w23 & 0xffffu, h3 = w23 >> 16;
+  const unsigned v4 = h0 + h1 + h2 + h3;
+  const unsigned S = wave_inclusive_sum(v4);
+  const unsigned long long ge = __ballot(S >= pf_need);
+  const int L = ge != 0ull ? __ffsll((unsigned long long)ge) - 1 : 0;
+  const unsigned below = S - v4;
+  const unsigned d = below + h0 >= pf_need ? 0u : (below + h0 + h1 >= pf_need ? 1u : (below + h0 + h1 + h2 >= pf_need ? 2u : 3u));
+  cstar = wave_read_lane(4u * (unsigned)lq + d, L);
+  lim = uni(pf_lim);
+  return ge != 0ull && cstar < lim;
+}
+// 3. a k11 = 1 candidate above the cut and inside the limit is in no top k
+__device__ __forceinline__ bool pf_drops(unsigned k11, unsigned cbq, unsigned cstar, unsigned lim) { return k11 == 1u && cbq > cstar && cbq <= lim; }
 // MP ("multi-pass", bin 6): rows no single LDS table can hold -- a hot item of a skewed catalogue pairs with tens of thousands
 // of distinct columns -- or whose counts overflow the packed field.  Such a row is accumulated in P = 2^s passes over its
 // cooccurrence pairs: pass q keeps the columns with (col mod P) == q, keyed by col div P (so the key narrows by s bits and the
@@ -728,10 +769,11 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
   unsigned* pfh = (SHARE && T != WAVE) ? reinterpret_cast<unsigned*>(share) + T : hist;
   constexpr unsigned DL = PF ? direct_limit(T, E) : 0u;  // the direct ranking: only the instantiations that carry the prefilter, 0 = none
   static_assert(DL <= (unsigned)SEL_M, "a directly ranked row lives in the ambiguous-set arrays");
-  const int list_start = a.bin_off[bin];
+  // (bit 11 of the bin argument, one-wave PK instantiation only: the class's sub-lists of small rows run in cco_rows_small_kernel -- this kernel takes the rest)
+  const int list_start = (T == WAVE && PK && !MP && (bin_arg & 2048)) ? a.bin_off[NBINS + MICRO_SUBS - 1 + SMALL_SUBS] : a.bin_off[bin];
   const int list_n = a.bin_off[bin + 1] - list_start;
   const int total_teams = gridDim.x * TEAMS;
-  bool ident = (long long)a.n_cols_b * 3 + (long long)a.k * 3 + 2 <= E && a.n_cols_b <= SH;  // the table spans every column of B: slots addressed by column
+  bool ident =(long long)a.n_cols_b * 3 + (long long)a.k * 3 + 2 <= E && a.n_cols_b <= SH;  // the table spans every column of B: slots addressed by column
   int cb = a.count_bits;                                                   // (MP: both follow the row's pass count)
   unsigned cmask = (1u << cb) - 1u;
   unsigned long long cand_acc = 0ull;  // distinct (row, column) candidates scored by this team (statistics)
@@ -984,37 +1026,22 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
       if (PF && pf_try) {
 #pragma unroll
         for (int q = 0; q < CPT; ++q) {
-          const unsigned cbq = cw[q] >> 16;
-          if ((cv[q] & cmask) == 1u && cbq < PF_BINS - 1u) atomicAdd(&pfh[cbq >> 1], 1u << (16 * (cbq & 1u)));  // (counts < 2^16: D is bounded by the table size; cv = 0 beyond D)
+          pf_count(pfh, cv[q] & cmask, cw[q] >> 16);  // (counts < 2^16: D is bounded by the table size; cv = 0 beyond D)
         }
       }
       team_sync<T>();  // every read of the table and the list precedes every write below (one wave: its LDS accesses execute in order -- wave_sync costs nothing there)
       bool pf_cut = false;  // team-uniform: every wave reads the same histogram
       unsigned cstar = 0u, lim = 0u;
       if (PF && pf_try) {
-        // every wave finds the cut for itself: lane l owns bins 4 l .. 4 l + 3 (ascending: the count of everything at or below a bin is a prefix sum)
         pf_lim = (unsigned)a.pf_limit[i];
-        int lq = lane;
-        URCCO_OPAQUE(lq);  // (the histogram addresses are formed here, not kept -- spilled -- across the row loop)
-        const unsigned w01 = pfh[2 * lq], w23 = pfh[2 * lq + 1];
-        const unsigned h0 = w01 & 0xffffu, h1 = w01 >> 16, h2 = w23 & 0xffffu, h3 = w23 >> 16;
-        const unsigned v4 = h0 + h1 + h2 + h3;
-        const unsigned S = wave_inclusive_sum(v4);
-        const unsigned long long ge = __ballot(S >= pf_need);
-        const int L = ge != 0ull ? __ffsll((unsigned long long)ge) - 1 : 0;
-        const unsigned below = S - v4;
-        const unsigned d = below + h0 >= pf_need ? 0u : (below + h0 + h1 >= pf_need ? 1u : (below + h0 + h1 + h2 >= pf_need ? 2u : 3u));
-        cstar = wave_read_lane(4u * (unsigned)lq + d, L);
-        lim = uni(pf_lim);
-        pf_cut = ge != 0ull && cstar < lim;  // (no k such candidates below the clamp bin: no cut; a limit at or below c*: nothing to drop)
+        pf_cut = pf_find_cut(pfh, lane, pf_need, pf_lim, cstar, lim);
       }
       if (PF && pf_cut) {
         unsigned cnt = 0u;
 #pragma unroll
         for (int q = 0; q < CPT; ++q) {
           const unsigned t = (unsigned)tl + (unsigned)q * T;
-          const unsigned cbq = cw[q] >> 16;
-          const bool drop = (cv[q] & cmask) == 1u && cbq > cstar && cbq <= lim;
+          const bool drop = pf_drops(cv[q] & cmask, cw[q] >> 16, cstar, lim);
           if (t < D && !drop) ++cnt;
           else cv[q] = 0u;  // (an occupied slot's word is never 0)
         }
@@ -1827,6 +1854,436 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
 }
 
 // --------------------------------------------------------------------------------------------
+// Small rows of the one-wave class (bin 1): <= 64 users and <= 64 P cooccurrence pairs, P = 2 or 4 -- the class's first two sub-lists (SMALL_SUBS).  The
+// general kernel charges such a row its whole machinery -- a chunk loop with LDS staging, a six-step binary search per lane, a candidate list, a compaction
+// sweep, the select -- for one or two wave-iterations of pairs.  This is the micro class's row body with P pairs per lane (packed B' only: a build whose
+// counts do not fit runs the whole class in the plain instantiation of cco_rows_kernel):
+//  * pair t = 64 r + lane in round r: neighbouring lanes read neighbouring B' words; a pair's user is the largest mark at or below it, the prefix maximum
+//    carried from round to round; the B' words of all P rounds are in flight before the first insert;
+//  * an accumulator of 512 words (>= twice the row's distinct columns), zero between rows: the lane that claims a column owns the candidate in registers,
+//    reads the finished count and clears the slot -- no candidate list, no compaction sweep;
+//  * the k11 = 1 prefilter of cco_rows_kernel (pf_count / pf_find_cut / pf_drops) over the lanes' candidates;
+//  * FAST TAIL: the survivors are numbered by ballots; when they are <= 64 each lane takes one and the row ends as a micro row does -- wave-level table-only LLR,
+//    ranking by counting over two / four replicas, in-place order, contiguous stores;
+//  * FALLBACK (more than 64 survivors: many ties at the cut, many k11 >= 2, counts beyond the histogram's clamp bin or the row's limit so that nothing is
+//    pruned, no prefilter -- 23 % of the body's rows on config 4): the survivors are staged in the accumulator (all zero by then, zeroed again behind the row),
+//    scored by rolled loops, cut by ONE radix digit of their keys (pf_find_cut over a histogram of the first byte in which the valid keys differ), and what
+//    is left, when it fits the lanes, goes through the same ranking tail; only a cut bin of more than 64 is ranked in full, every survivor against all.
+// Wave LDS layout (words): [0, 512) the accumulator -- in the fallback the staged packed words [256] | cB, then columns [256], then over the packed words the
+// digit histogram [128] and, behind the cut, the tail's list [3 x 68]; [512, 1024) by phase: the pair -> user marks [64 P + 2] | the prefilter's histogram [128],
+// the fast tail's staged survivors (packed word, cB) [2 x 64] behind it, its columns [68] and keys [68] behind those | the fallback's keys [256].  16 KiB per block.
+// flags: bit 8 -- the statistics count the candidates that were SCORED (DBG_COUNT_SCORED); bit 12 -- they count the ROWS of this body, + 2^32 per row that took
+// the fallback (DBG_COUNT_SMALL_WAVE).
+// --------------------------------------------------------------------------------------------
+constexpr int SMALL_TW = 512, SMALL_LOG2TW = 9;  // accumulator words per row
+constexpr int SMALL_LIST = WAVE + 4;             // the fast tail's columns / keys (with room for the padding of the ranking loops)
+constexpr int SMALL_WORDS = 2 * SMALL_TW;
+constexpr int SMALL_FACTOR = 4;                  // grid of a sub-list, as a multiple of the blocks that fit the chip (see ROW_CLASS)
+static_assert(2 * SMALL_P1 * WAVE <= SMALL_TW && SMALL_P1 * WAVE + 2 <= SMALL_TW && 3 * SMALL_LIST <= SMALL_TW / 2 && PF_BINS / 2 <= SMALL_TW / 2, "accumulator load <= 1/2; the marks and the fallback's keys fit the phase region, its staged words and columns the accumulator");
+static_assert(PF_BINS / 2 + 2 * WAVE + 3 * SMALL_LIST <= SMALL_TW && (PF_BINS / 2 + 2 * WAVE + SMALL_LIST) % 2 == 0, "fast tail arrays; 64-bit keys 8-byte aligned");
+template <int P>
+__global__ __launch_bounds__(256, URCCO_OCC_MICRO) void cco_rows_small_kernel(CcoArgs a, int flags) {
+  if (!(a.b_packed != nullptr && (a.pk_known != 0 || *a.form == 0))) return;  // grid-uniform: the plain instantiation of cco_rows_kernel has the whole class
+  static_assert(P == SMALL_P0 || P == SMALL_P1, "one instantiation per sub-list");
+  const int32_t* bin_rows = a.bin_rows;
+  const int64_t* a_col_ptr = a.a_col_ptr;
+  const unsigned* pstart = a.pstart32;
+  const int32_t* b_col_idx = a.b_packed;
+  const int cshift = 32 - a.count_bits;
+  const unsigned colmask = (1u << cshift) - 1u;
+  const int32_t* cnt_a = a.cnt_a;
+  const double* ent_a = a.ent_a;
+  const double* xlx_tab = a.xlx_tab;
+  const double* xlx_hi = a.xlx_hi;
+  const double* col_ent = a.col_ent;
+  int32_t* out_idx = a.out_idx;
+  double* out_llr = a.out_llr;
+  int32_t* out_count = a.out_count;
+  const long long n_users = a.n_users;
+  const bool has_pf = a.pf_limit != nullptr;
+  const unsigned short* lim_tab = has_pf ? a.pf_limit : reinterpret_cast<const unsigned short*>(a.cnt_a);  // (prefetched unconditionally: any readable table of >= n items)
+  constexpr int TEAMS = 256 / WAVE;
+  __shared__ __attribute__((aligned(16))) unsigned s_tab[TEAMS * SMALL_WORDS];
+  const int team = threadIdx.x / WAVE;
+  const int lane = threadIdx.x & (WAVE - 1);
+  unsigned* tab = s_tab + team * SMALL_WORDS;
+  unsigned* marks = tab + SMALL_TW;
+  unsigned* pfh = marks;
+  unsigned* st_v = marks + PF_BINS / 2;
+  unsigned* st_c = st_v + WAVE;
+  unsigned* cand = st_c + WAVE;
+  unsigned long long* kkm = reinterpret_cast<unsigned long long*>(cand + SMALL_LIST);
+  unsigned long long* fkeys = reinterpret_cast<unsigned long long*>(marks);
+  const int list_start = P == SMALL_P0 ? a.bin_off[1] : a.bin_off[NBINS + 3];
+  const int list_n = (P == SMALL_P0 ? a.bin_off[NBINS + 3] : a.bin_off[NBINS + 4]) - list_start;
+  const int total_teams = gridDim.x * TEAMS;
+  const bool ident = a.n_cols_b <= SMALL_TW;
+  const int cb = a.count_bits;
+  const unsigned cmask = (1u << cb) - 1u;
+  const double xlx_n = __longlong_as_double((long long)uni((int64_t)__double_as_longlong(*a.xlx_n)));  // (a scalar pair: as a loaded value it held two vector registers across the row loop)
+  const unsigned pf_need = (unsigned)a.k + (a.exclude_self ? 1u : 0u);
+  unsigned long long cand_acc = 0ull;
+
+  int li = blockIdx.x * TEAMS + team;
+  if (li >= list_n) return;  // (wave-level synchronisation only: a wave without rows may leave)
+  // The chain row id -> CSC bounds -> per-user operands, issued at the top of a row for the rows ahead and collected ahead of the row's stores (see
+  // cco_rows_micro_kernel), with the uniform links packed by lane as in cco_rows_kernel: one register carries the ids of this row and the next two, one pair
+  // both bounds of a row.  The row's own count, entropy and limit are loaded at the top of the row itself -- the wait for its B' words covers them.
+  const int stride = total_teams;
+  auto pos_of = [&](int l) { return list_start + (l < list_n ? l : list_n - 1); };
+  const unsigned* wp32 = reinterpret_cast<const unsigned*>(a.wp);
+  const int lane3 = lane < 3 ? lane : 2;
+  int idv = bin_rows[pos_of(li + lane3 * stride)];  // lanes 0, 1, 2: ids of this row and the next two
+  int64_t bnd_b;                                    // the next row's bounds: lane 0 start, lane 1 end
+  unsigned pf_w1, pf_wp, pf_start;
+  int n_cur;  // users of the row about to be processed (scalar)
+  {
+    const int id0 = (int)wave_read_lane((unsigned)idv, 0);
+    const int id1 = (int)wave_read_lane((unsigned)idv, 1);
+    const int64_t cs0 = uni(a_col_ptr[id0]), ce0 = uni(a_col_ptr[id0 + 1]);
+    bnd_b = a_col_ptr[id1 + (lane & 1)];
+    n_cur = (int)(ce0 - cs0);
+    const int64_t pl = lane < n_cur ? cs0 + lane : ce0 - 1;
+    pf_w1 = wp32[ce0];
+    pf_wp = wp32[pl];
+    pf_start = pstart[pl];
+  }
+  URCCO_SETTLE(idv); URCCO_SETTLE(bnd_b); URCCO_SETTLE(pf_w1); URCCO_SETTLE(pf_wp); URCCO_SETTLE(pf_start);
+#pragma unroll
+  for (int q = 0; q < SMALL_TW / WAVE; ++q) tab[lane + q * WAVE] = 0u;  // the accumulator: zero between rows (a candidate's owner clears its slot)
+  int64_t bnd_c = 0;  // the bounds two rows ahead, in flight: rotated by the loop's increment
+  for (; li < list_n; li += stride, bnd_b = bnd_c) {  // each wave runs its own row loop: wave-level sync only
+    const int i = (int)wave_read_lane((unsigned)idv, 0);
+    const int id2 = (int)wave_read_lane((unsigned)idv, 2);
+    const int64_t cs_n = wave_read_lane64(bnd_b, 0), ce_n = wave_read_lane64(bnd_b, 1);
+    // this row's operands leave their registers ...
+    const unsigned w0 = wave_read_lane(pf_wp, 0);  // wp[cs]
+    unsigned total = uni(pf_w1) - w0;              // <= 64 P by the binning rule
+    if (total > (unsigned)(P * WAVE) || n_cur > WAVE) {  // (cannot happen while the binning rule holds: reported, and the row left empty)
+      if (lane == 0) atomicAdd(a.err, 1ull);
+      total = 0u;
+    }
+    const bool owns_user = lane < n_cur;
+    const unsigned my_off = owns_user ? pf_wp - w0 : total;
+    const unsigned my_delta = (owns_user ? pf_start : 0u) - my_off;  // B' position of pair t of this lane's user: delta + t, in 32-bit wrap-around arithmetic
+    // ... and the rows ahead take them: ids up to row + 3, bounds of row + 2, operands of row + 1
+    int lz = lane;
+    URCCO_OPAQUE(lz);  // (what derives from the lane here is recomputed per row, not kept across the row loop)
+    idv = bin_rows[pos_of(li + (1 + (lz < 3 ? lz : 2)) * stride)];
+    bnd_c = a_col_ptr[id2 + (lz & 1)];
+    int iv = i;
+    URCCO_OPAQUE(iv);  // (vector loads: a scalar load would tie the LDS counter -- which the marks below wait on -- to a trip to memory)
+    const int row_ca = cnt_a[iv];
+    const double row_entropy = ent_a[iv];
+    const unsigned row_lim = lim_tab[iv];  // the row's monotone limit (16 bits, zero-extended by the load)
+    n_cur = (int)(ce_n - cs_n);
+    {
+      const int64_t pl = lz < n_cur ? cs_n + lz : ce_n - 1;
+      pf_w1 = wp32[ce_n];
+      pf_wp = wp32[pl];
+      pf_start = pstart[pl];
+    }
+    // ---- pair -> user: user u marks the first pair of its B' row with u (the LAST user of an offset is the one whose row is not empty)
+#pragma unroll
+    for (int r = 0; r < P; ++r) marks[lane + r * WAVE] = 0u;
+    if (lane < 2) marks[P * WAVE + lane] = 0u;
+    wave_sync();
+    if (owns_user && my_off <= total) atomicMax(&marks[my_off], (unsigned)lane);  // my_off <= total <= 64 P: marks has 64 P + 2 words
+    wave_sync();
+    unsigned jj[P];  // this lane's B' words: the column, and the column's count
+    unsigned carry = 0u;
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+      const unsigned m = wave_inclusive_max(marks[lane + r * WAVE]);
+      const unsigned o = m > carry ? m : carry;
+      carry = wave_read_lane(o, WAVE - 1);
+      const unsigned base_o = wave_gather(my_delta, o);
+      const unsigned t = (unsigned)(r * WAVE + lane);
+      jj[r] = 0u;
+      if (t < total) jj[r] = (unsigned)b_col_idx[base_o + t];
+    }
+    // ---- insert; the claiming lane owns the candidate
+    unsigned slot[P];
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+      slot[r] = 0xffffffffu;
+      if ((unsigned)(r * WAVE + lane) < total) {
+        bool ok;
+        slot[r] = tab_insert_claim(tab, (jj[r] & colmask) + 1u, cb, (unsigned)(SMALL_TW - 1), 32 - SMALL_LOG2TW, ident, &ok);
+        if (!ok) atomicAdd(a.err, 1ull);
+      }
+    }
+    wave_sync();
+    // the finished counts leave the accumulator and the slots are zero again: vv != 0 names a candidate (an occupied slot's word is never 0)
+    unsigned vv[P];
+    unsigned D = 0u;
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+      const bool is_cand = slot[r] != 0xffffffffu;
+      D += (unsigned)__popcll(__ballot(is_cand));
+      vv[r] = 0u;
+      if (is_cand) {
+        vv[r] = tab[slot[r]];
+        tab[slot[r]] = 0u;
+      }
+    }
+    // ---- the k11 = 1 prefilter (see cco_rows_kernel): what it drops is no candidate any more
+    if (has_pf && D > pf_need) {  // wave-uniform
+      unsigned zero = 0u;
+      URCCO_OPAQUE(zero);  // (made here: as a constant the pair of zeros was kept -- spilled to scratch -- across the row loop)
+      *reinterpret_cast<uint2*>(&pfh[2 * lane]) = make_uint2(zero, zero);  // (the marks are dead: every lane has read its own)
+      wave_sync();
+#pragma unroll
+      for (int r = 0; r < P; ++r)
+        if (vv[r] != 0u) pf_count(pfh, vv[r] & cmask, jj[r] >> cshift);
+      wave_sync();
+      unsigned cstar, lim;
+      if (pf_find_cut(pfh, lane, pf_need, row_lim, cstar, lim)) {
+#pragma unroll
+        for (int r = 0; r < P; ++r)
+          if (pf_drops(vv[r] & cmask, jj[r] >> cshift, cstar, lim)) vv[r] = 0u;
+      }
+      wave_sync();
+    }
+    // ---- the survivors, numbered by ballots in (round, lane) order
+    unsigned pos[P];
+    unsigned n_surv = 0u;
+#pragma unroll
+    for (int r = 0; r < P; ++r) {
+      const unsigned long long m = __ballot(vv[r] != 0u);
+      pos[r] = n_surv + lanes_below(m);
+      n_surv += (unsigned)__popcll(m);
+    }
+    if (!(flags & 4096)) cand_acc += (flags & 256) ? n_surv : D;
+    else cand_acc += n_surv <= (unsigned)WAVE ? 1ull : (1ull << 32) + 1ull;
+    const int64_t obase = ((int64_t)(i - a.item_lo)) * a.k;
+    auto settle_prefetch = [&]() {  // the next row's operands have had the row to arrive: collect them before the output stores
+      URCCO_SETTLE(idv); URCCO_SETTLE(bnd_c); URCCO_SETTLE(pf_w1); URCCO_SETTLE(pf_wp); URCCO_SETTLE(pf_start);
+    };
+    // the survivors' (packed word, cB) leave the registers for their numbered places: the fast tail's 64 behind the histogram, the fallback's <= 64 P in the
+    // accumulator -- zero again since the counts left it, and zeroed again below
+    const bool fast = n_surv <= (unsigned)WAVE;  // wave-uniform
+    {
+      unsigned* sv = fast ? st_v : tab;
+      unsigned* sc = fast ? st_c : tab + SMALL_TW / 2;
+#pragma unroll
+      for (int r = 0; r < P; ++r)
+        if (vv[r] != 0u) {
+          sv[pos[r]] = vv[r];
+          sc[pos[r]] = jj[r] >> cshift;
+        }
+    }
+    // Both paths end in ONE ranking tail over a list of <= 64 elements, one per lane (columns cand_l, keys kkm_l, padded for the ranking loops): the fast
+    // tail's survivors, or what the fallback's digit cut leaves of its valid candidates.
+    unsigned* cand_l = cand;
+    unsigned long long* kkm_l = kkm;
+    unsigned n_list = n_surv;
+    bool listed = true;  // wave-uniform: false = the fallback has ranked and stored the row itself
+    unsigned long long mk = 0ull;  // this lane's element of the list
+    int jc = 0;
+    if (fast) {
+      // ---- fast tail: one survivor per lane, scored as the micro class scores (cco_rows_micro_kernel, L = 64)
+      wave_sync();
+      const bool is_cand = (unsigned)lane < n_surv;
+      const unsigned v1 = is_cand ? st_v[lane] : 0u;
+      const unsigned cbj = is_cand ? st_c[lane] : 0u;
+      if (n_surv + (unsigned)lane < (unsigned)SMALL_LIST) {  // padding of the ranking loop's element list behind the survivors: sorts before nothing
+        unsigned zero = 0u;
+        URCCO_OPAQUE(zero);  // (as above)
+        *reinterpret_cast<uint2*>(&kkm[n_surv + (unsigned)lane]) = make_uint2(zero, zero);
+        cand[n_surv + (unsigned)lane] = 0xffffffffu;
+      }
+      jc = (int)(v1 >> cb) - 1;
+      const long long k11 = (long long)(v1 & cmask);
+      const bool in_tables = !is_cand || llr_operands_in_tables((unsigned)k11, (long long)row_ca, cbj, n_users, col_ent);
+      const bool all_in_tables = __ballot(!in_tables) == 0ull;  // wave-uniform: the straight-line table form (see llr_from_tables)
+      if (is_cand) {
+        if (!(a.exclude_self && jc == i)) {
+          const double llr = all_in_tables ? llr_from_tables(row_entropy, xlx_n, (unsigned)k11, (unsigned)row_ca, cbj, xlx_tab, xlx_hi, col_ent)
+                                           : llr_of(row_entropy, xlx_n, k11, (long long)row_ca, (long long)cbj, n_users, xlx_tab, xlx_hi, col_ent);
+          if (llr > 0.0 && (!a.has_min_llr || llr >= a.min_llr)) mk = (unsigned long long)__double_as_longlong(llr);
+        }
+        kkm[lane] = mk;
+        cand[lane] = (unsigned)jc;
+      }
+      wave_sync();
+    } else {
+      // ---- fallback: more survivors than lanes (<= 64 P).  Rolled loops over the staged survivors, 64 at a time.  1. each is scored, every operand tested
+      // on its own; its key goes to the phase region, its column takes the place of its cB.
+      unsigned* fcol = tab + SMALL_TW / 2;
+      wave_sync();
+      unsigned n_valid = 0u;
+      unsigned long long kand = ~0ull, kor = 0ull;  // over the valid keys: the leading bytes they share decide nothing
+#pragma unroll 1
+      for (unsigned base = 0; base < n_surv; base += WAVE) {  // scalar loop control
+        const unsigned x = base + (unsigned)lane;
+        unsigned long long key = 0ull;
+        if (x < n_surv) {
+          const unsigned v1 = tab[x], cbj = fcol[x];
+          const int j = (int)(v1 >> cb) - 1;
+          const long long k11 = (long long)(v1 & cmask);
+          if (!(a.exclude_self && j == i)) {
+            const double llr = llr_operands_in_tables((unsigned)k11, (long long)row_ca, cbj, n_users, col_ent)
+                                   ? llr_from_tables(row_entropy, xlx_n, (unsigned)k11, (unsigned)row_ca, cbj, xlx_tab, xlx_hi, col_ent)
+                                   : llr_of(row_entropy, xlx_n, k11, (long long)row_ca, (long long)cbj, n_users, xlx_tab, xlx_hi, col_ent);
+            if (llr > 0.0 && (!a.has_min_llr || llr >= a.min_llr)) key = (unsigned long long)__double_as_longlong(llr);
+          }
+          fkeys[x] = key;
+          fcol[x] = (unsigned)j;
+        }
+        if (key != 0ull) {
+          kand &= key;
+          kor |= key;
+        }
+        n_valid += (unsigned)__popcll(__ballot(key != 0ull));
+      }
+      // 2. THE DIGIT CUT: one pass of a radix select over the first key byte in which the valid keys differ.  The valid candidates are counted by that byte,
+      // the highest value first (255 - byte, so that "the count of everything at or above" is the ascending prefix sum the prefilter's cut search computes:
+      // pf_find_cut, without a limit); c* = the bin in which the k-th best key lies.  Every key of a higher bin is in the row, every key of a lower bin is
+      // outranked by >= k keys that are strictly greater, and the bin itself is kept whole: the final ranking by (key, column) cuts it.
+      wave_and_or_u64(kand, kor);
+      const unsigned long long kdiff = kand ^ kor;
+      const int shk = kdiff == 0ull ? 0 : 56 - 8 * (__clzll((long long)kdiff) >> 3);
+      bool cut = false;  // wave-uniform
+      unsigned cstar = 0u;
+      if (kdiff != 0ull && n_valid > (unsigned)a.k) {  // (all keys equal: the columns decide; no more than k valid: all of them are the row)
+        unsigned zero = 0u;
+        URCCO_OPAQUE(zero);
+        *reinterpret_cast<uint2*>(&tab[2 * lane]) = make_uint2(zero, zero);  // the histogram: over the staged packed words, which the scores no longer need
+        wave_sync();
+#pragma unroll 1
+        for (unsigned base = 0; base < n_surv; base += WAVE) {
+          const unsigned x = base + (unsigned)lane;
+          const unsigned long long key = x < n_surv ? fkeys[x] : 0ull;
+          const unsigned dg = 255u - ((unsigned)(key >> shk) & 255u);
+          if (key != 0ull) atomicAdd(&tab[dg >> 1], 1u << (16 * (dg & 1u)));  // (counts <= 256)
+        }
+        wave_sync();
+        unsigned nolim;
+        cut = pf_find_cut(tab, lane, (unsigned)a.k, 0xffffffffu, cstar, nolim);
+        wave_sync();
+      }
+      unsigned n_sel = 0u;
+#pragma unroll 1
+      for (unsigned base = 0; base < n_surv; base += WAVE) {
+        const unsigned x = base + (unsigned)lane;
+        const unsigned long long key = x < n_surv ? fkeys[x] : 0ull;
+        const bool sel = key != 0ull && (!cut || 255u - ((unsigned)(key >> shk) & 255u) <= cstar);
+        n_sel += (unsigned)__popcll(__ballot(sel));
+      }
+      if (n_sel <= (unsigned)WAVE) {  // wave-uniform
+        // 3a. what the cut leaves fits the lanes: it becomes the list of the ranking tail, in the accumulator's first words (the histogram is dead)
+        cand_l = tab;
+        kkm_l = reinterpret_cast<unsigned long long*>(tab + SMALL_LIST);
+        n_list = 0u;
+#pragma unroll 1
+        for (unsigned base = 0; base < n_surv; base += WAVE) {
+          const unsigned x = base + (unsigned)lane;
+          const unsigned long long key = x < n_surv ? fkeys[x] : 0ull;
+          const bool sel = key != 0ull && (!cut || 255u - ((unsigned)(key >> shk) & 255u) <= cstar);
+          const unsigned long long m = __ballot(sel);
+          if (sel) {
+            const unsigned at = n_list + lanes_below(m);
+            kkm_l[at] = key;
+            cand_l[at] = fcol[x];
+          }
+          n_list += (unsigned)__popcll(m);
+        }
+        if (n_list + (unsigned)lane < (unsigned)SMALL_LIST) {
+          unsigned zero = 0u;
+          URCCO_OPAQUE(zero);
+          *reinterpret_cast<uint2*>(&kkm_l[n_list + (unsigned)lane]) = make_uint2(zero, zero);
+          cand_l[n_list + (unsigned)lane] = 0xffffffffu;
+        }
+        wave_sync();
+        if ((unsigned)lane < n_list) {
+          mk = kkm_l[lane];
+          jc = (int)cand_l[lane];
+        }
+      } else {
+        // 3b. a cut bin too large for the lanes (many equal keys): every survivor is ranked against all of them and stored at its rank
+        listed = false;
+        const unsigned n_out = n_valid < (unsigned)a.k ? n_valid : (unsigned)a.k;
+        settle_prefetch();
+#pragma unroll 1
+        for (unsigned base = 0; base < n_surv; base += WAVE) {  // (every lane counts, survivor or not: the ranking loop is wave-uniform)
+          const unsigned x = base + (unsigned)lane;
+          const unsigned long long key = x < n_surv ? fkeys[x] : 0ull;
+          const unsigned mc = x < n_surv ? fcol[x] : 0u;
+          const unsigned rank = rank_by_counting_strided<1>(fkeys, fcol, 0u, n_surv, key, mc);
+          if (key != 0ull && rank < n_out) {  // (an invalid survivor's key is 0: it sorts behind every valid one)
+            out_idx[obase + rank] = (int)mc;
+            out_llr[obase + rank] = __longlong_as_double((long long)key);
+          }
+        }
+        if (lane == 0) out_count[i - a.item_lo] = (int)n_out;
+      }
+    }
+    if (listed) {  // wave-uniform
+      // ---- the micro class's tail (cco_rows_micro_kernel, L = 64) over the list
+      const unsigned long long valid_mask = __ballot(mk != 0ull);
+      const int n_valid = __popcll(valid_mask);
+      if (a.unordered && n_valid <= a.k) {  // every valid element is emitted: no ranking needed (wave-uniform)
+        settle_prefetch();
+        if (mk != 0ull) {
+          const unsigned opos = lanes_below(valid_mask);
+          out_idx[obase + opos] = jc;
+          out_llr[obase + opos] = __longlong_as_double((long long)mk);
+        }
+        if (lane == 0) out_count[i - a.item_lo] = n_valid;
+      } else {
+        // elements dense by lane, replicated while they fit twice / four times into the wave: replica q counts elements q, q + R, ...
+        unsigned rank;
+        unsigned long long rk;
+        unsigned rc;
+        unsigned ln = (unsigned)lane;
+        URCCO_OPAQUE(ln);  // the per-lane LDS addresses of the three forms are computed here, not kept across the row loop
+        if (n_list <= (unsigned)(WAVE / 4)) {  // wave-uniform
+          const unsigned c = ln & (unsigned)(WAVE / 4 - 1);
+          rk = kkm_l[c];
+          rc = cand_l[c];
+          rank = rank_by_counting_strided<4>(kkm_l, cand_l, ln / (unsigned)(WAVE / 4), (n_list + 3u) & ~3u, rk, rc);
+          rank += (unsigned)__shfl_xor((int)rank, WAVE / 4);
+          rank += (unsigned)__shfl_xor((int)rank, WAVE / 2);
+        } else if (n_list <= (unsigned)(WAVE / 2)) {
+          const unsigned c = ln & (unsigned)(WAVE / 2 - 1);
+          rk = kkm_l[c];
+          rc = cand_l[c];
+          rank = rank_by_counting_strided<2>(kkm_l, cand_l, ln / (unsigned)(WAVE / 2), (n_list + 1u) & ~1u, rk, rc);
+          rank += (unsigned)__shfl_xor((int)rank, WAVE / 2);
+        } else {
+          rk = kkm_l[ln];
+          rc = cand_l[ln];
+          rank = rank_by_counting_strided<1>(kkm_l, cand_l, 0u, n_list, rk, rc);
+        }
+        // the row is put in order in LDS (every lane has its element in registers: in place) and leaves as contiguous stores
+        wave_sync();
+        const unsigned n_out = (unsigned)(n_valid < a.k ? n_valid : a.k);
+        if ((unsigned)lane < n_list && rk != 0ull && rank < n_out) {
+          cand_l[rank] = rc;
+          kkm_l[rank] = rk;
+        }
+        wave_sync();
+        settle_prefetch();
+        if ((unsigned)lane < n_out) {
+          out_idx[obase + lane] = (int)cand_l[lane];
+          out_llr[obase + lane] = __longlong_as_double((long long)kkm_l[lane]);
+        }
+        if (lane == 0) out_count[i - a.item_lo] = (int)n_out;
+      }
+    }
+    if (!fast) {
+      wave_sync();
+#pragma unroll
+      for (int q = 0; q < SMALL_TW / WAVE; ++q) tab[lane + q * WAVE] = 0u;  // the accumulator is zero between rows
+    }
+    wave_sync();
+  }
+  // (one slot per block, the first lane found by counting: the thread id, kept for this line alone, was the one register the kernel spilled to scratch)
+  if (a.cand && cand_acc != 0ull && lanes_below(~0ull) == 0u) atomicAdd(&a.cand[blockIdx.x & (CAND_SLOTS - 1)], cand_acc);
+}
+
+// --------------------------------------------------------------------------------------------
 // Global-accumulator variant (bin 6 when k is beyond the multi-pass class): rows whose distinct columns cannot be bounded below an LDS table or
 // whose counts overflow the packed entry.  One 1024-thread block per row; a dense int32 counter array per
 // resident block (zero on entry, restored to zero by the claim walk), candidates spilled to global scratch,
@@ -2075,10 +2532,12 @@ hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, Ro
   // Two blocks: the PK instantiations' and the one of every kernel that reads plain words (the plain and DBG instantiations, the dense global kernel).
   // DBG_COUNT_DIRECT: the statistics word counts the rows the packed kernels ranked directly -- every kernel that has no direct ranking (the plain and DBG
   // forms, the micro and multi-pass classes, a class it is compiled out of) runs without the word, so that no candidate count is mixed in
-  const bool count_direct = (args.debug & DBG_COUNT_DIRECT) != 0;
-  CcoArgs pk = args, plain = args;
-  if (count_direct && c.direct == 0u) pk.cand = nullptr;
-  if (count_direct) plain.cand = nullptr;
+  // DBG_COUNT_SMALL_WAVE, likewise: the word counts the rows of cco_rows_small_kernel, and every other kernel runs without it
+  const bool count_direct = (args.debug & DBG_COUNT_DIRECT) != 0, count_small = (args.debug & DBG_COUNT_SMALL_WAVE) != 0;
+  CcoArgs pk = args, plain = args, small = args;
+  if ((count_direct && c.direct == 0u) || count_small) pk.cand = nullptr;
+  if (count_direct || count_small) plain.cand = nullptr;
+  if (count_direct) small.cand = nullptr;
   // ride on the PK kernels' bin argument (grid-uniform; the production instantiations do not read CcoArgs::debug)
   const int pk_bits = ((args.debug & DBG_COUNT_SCORED) ? 256 : 0) | ((args.debug & DBG_NO_DIRECT_RANK) ? 512 : 0) | (count_direct ? 1024 : 0);
   // what the plan enqueues of one class (or micro sub-list), given its DBG, PK and plain instantiation; bin_arg: the bin argument of cco_rows_kernel
@@ -2096,6 +2555,14 @@ hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, Ro
   } else if (bin == NBINS - 1 && args.g_blocks > 0) {
     plain.b_packed = nullptr;  // (the dense kernel reads plain words whatever the plan)
     hipLaunchKernelGGL(cco_rows_global_kernel, dim3((unsigned)args.g_blocks), dim3(GB_THREADS), 0, st, plain);
+  } else if (bin == 1 && plan_runs_pk(plan) && micro_split_for(n_rows) && args.k <= SMALL_KMAX && !(args.debug & DBG_NO_SMALL_WAVE)) {
+    // the class's two sub-lists of small rows in the micro-shaped body (the same rule as the binning pass: otherwise they are empty), the rest in the general
+    // kernel (bit 11 of its bin argument); the plain instantiation -- a build whose counts do not fit -- keeps the whole class
+    const int small_bits = ((args.debug & DBG_COUNT_SCORED) ? 256 : 0) | (count_small ? 4096 : 0);
+    hipLaunchKernelGGL(cco_rows_small_kernel<SMALL_P0>, grid(SMALL_FACTOR), dim3(c.block), 0, st, small, small_bits);
+    hipLaunchKernelGGL(cco_rows_small_kernel<SMALL_P1>, grid(SMALL_FACTOR), dim3(c.block), 0, st, small, small_bits);
+    hipLaunchKernelGGL(c.pk, grid(c.factor), dim3(c.block), 0, st, pk, bin | pk_bits | 2048);
+    if (plan_runs_plain(plan)) hipLaunchKernelGGL(c.plain, grid(c.factor), dim3(c.block), 0, st, plain, bin);
   } else {
     enqueue(c.dbg, c.pk, c.plain, c.factor, bin);
   }
