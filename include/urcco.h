@@ -525,6 +525,35 @@ int urcco_dev_recommend_rules(urcco_session* s, int64_t n_queries, int32_t n_ite
                               int32_t num, int32_t flags, int32_t* out_count, int32_t* out_idx, double* out_score, int64_t* stats_dev,
                               const urcco_rec_rule* rules, int32_t n_rules);
 
+/* urcco_dev_recommend_rules with per-term weights (DESIGN.md decision D20).  A clause c may carry a weight array w_c[h], one unsigned 32-bit integer per
+ * column h of I_c, in units of 2^-15; valid values are 1 .. URCCO_REC_WEIGHT_MAX (32.0), URCCO_REC_WEIGHT_ONE is 1.0.
+ *   M_c(q, i)   = sum over h in T_c(q) ^ I_c(i) of w_c[h]                                      exact integer
+ *   score(q, i) = ((0.0 + boost_0 ((double)M_0 2^-15)) + boost_1 ((double)M_1 2^-15)) + ...    f64, clauses in call order, no contraction
+ * The weights are accumulated with integer atomics and folded into the f64 score once per clause: ids and score bits stay reproducible bit for bit whatever
+ * the order of the hits.  A clause without an array (a NULL entry) behaves as w = URCCO_REC_WEIGHT_ONE throughout, and (double)(m 2^15) 2^-15 == m exactly:
+ * clause_weights == NULL, all entries NULL, or arrays that hold URCCO_REC_WEIGHT_ONE alone give the counts, ids, score bits and statistics of
+ * urcco_dev_recommend_rules.  Weights are >= 1, so an item has a positive score exactly when it has one there: eligibility, exclusions, the mask, the rules,
+ * the backfill, URCCO_REC_NO_BACKFILL and the total order (score desc, backfill position asc) are those of urcco_dev_recommend_rules.
+ * No counter overflows: a query whose work bound w(q) is at most 3072 runs on 32-bit counters and has at most 3072 hits, so M <= 3072 * 2^20 < 2^32; every
+ * other query counts in 64 bits (24 instead of 20 bytes of scratch per item and resident block).  That the values lie in 1 .. URCCO_REC_WEIGHT_MAX is the
+ * caller's duty, like fill_order being a permutation; the kernel clamps every weight it loads into that range (0 counts as 1, anything larger as the
+ * maximum), so a bad array gives other scores but cannot overflow a counter.  URCCO_BAD_ARG: as urcco_dev_recommend_rules. */
+#define URCCO_REC_WEIGHT_ONE (1 << 15)
+#define URCCO_REC_WEIGHT_MAX (1 << 20)
+int urcco_dev_recommend_weighted(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses,
+                                 const int64_t* excl_row_ptr, const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order,
+                                 int32_t num, int32_t flags, int32_t* out_count, int32_t* out_idx, double* out_score, int64_t* stats_dev,
+                                 const urcco_rec_rule* rules, int32_t n_rules,
+                                 const uint32_t* const* clause_weights /* nullable: HOST array [n_clauses] of device pointers [clause.n_cols], entries nullable */);
+
+/* Term weights by rarity for urcco_dev_recommend_weighted: for column h of a CSC, df = ind_col_ptr[h + 1] - ind_col_ptr[h] (a df above n_docs counts as n_docs),
+ *   idf = log(1 + (n_docs - df + 0.5) / (df + 0.5))   in f64 -- Lucene's BM25 idf, the term-rarity half of what the reference's Elasticsearch index computes;
+ *   out_weight[h] = clamp(llrint(idf * 2^15), 1, URCCO_REC_WEIGHT_MAX); a column nothing lists (df == 0) gets 1.
+ * BM25's length norm and per-shard statistics are not part of it.  n_docs is the caller's document count (Elasticsearch's: the items whose field is not empty).
+ * Enqueues on the session's stream.  URCCO_BAD_ARG: n_cols < 0, n_docs < 1, a NULL array with n_cols > 0. */
+int urcco_dev_idf_weights(urcco_session* s, int32_t n_cols, const int64_t* ind_col_ptr /* device, n_cols + 1 */, int64_t n_docs,
+                          uint32_t* out_weight /* device, [n_cols] */);
+
 /* Hold-out evaluation of a table of recommendations: hits, average precision and NDCG at up to URCCO_EVAL_MAX_KS cut-offs per query, and their sums over
  * the queries -- the arithmetic of the reference's MAP@k tool (the query key `eventNames` exists "for indicator predictiveness testing with the MAP@k
  * tool"; URAlgorithm.scala:401), without leaving the device.  DESIGN.md decision D19.  For query q:

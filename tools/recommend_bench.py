@@ -22,7 +22,10 @@ streams on the device; the held-out events are one more draw of the primary even
 as the first --queries users').  Printed: the HIP-event time of urcco_dev_rank_metrics alone (ks = 1, 5, 10, 20, the sums included) over a table and truth
 rows built beforehand; the wall time of URAlgorithm.evaluate end to end (user_recommendations + truth rows + rank_metrics per chunk, the tree sums, one
 report); and, as a comparison point only, the HIP-event time of a torch.isin + cumsum restatement of the per-user hits on the same GPU.
-usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--rules] [--device-history] [--device-items] [--evaluate] [--no-torch]"""
+--weights: the same problem once more through urcco_dev_recommend_weighted (decision D20) under the model's idf term weights (DeviceModel.term_weights:
+one urcco_dev_idf_weights call per event type, timed on its own), its time printed next to the unweighted call's of the same process; and once with arrays
+that hold WEIGHT_ONE alone, whose ids and score bits must be the unweighted call's.
+usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--rules] [--weights] [--device-history] [--device-items] [--evaluate] [--no-torch]"""
 import argparse
 import os
 import sys
@@ -42,6 +45,7 @@ ap.add_argument("--chunk", type=int, default=2048)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--num", type=int, default=20)
 ap.add_argument("--rules", action="store_true", help="also time the call under an ANY and a NONE rule")
+ap.add_argument("--weights", action="store_true", help="also time the weighted call under idf term weights")
 ap.add_argument("--device-history", action="store_true", help="also time history_bounds + history_rows against the host planning loop")
 ap.add_argument("--device-items", action="store_true", help="also time item_bounds + item_rows against the host planning loop of item queries")
 ap.add_argument("--evaluate", action="store_true", help="also time rank_metrics, evaluate end to end and a torch restatement of the hits")
@@ -109,6 +113,25 @@ if args.rules:
     print(f"urcco_dev_recommend_rules (ANY on a value {float(half.float().mean()):.0%} of the items hold, NONE on a value a ninth hold): {min(ms_rules):.2f} ms best, "
           f"{sorted(ms_rules)[len(ms_rules) // 2]:.2f} ms median of {args.reps} ({[round(x, 2) for x in ms_rules]}) -- rule-free call above: {min(ms_hip):.2f} ms")
     print(f"  candidates {rs[3]} ({rs[3] / nq:.0f} per query, {st[3] / nq:.0f} without rules); backfill steps {rs[4]} ({rs[4] / nq:.2f} per query); full rows {int((r_count == num).sum())} / {nq}")
+
+if args.weights:
+    _, ms_idf = timed(lambda: [sess.idf_weights(c.col_ptr, c.n_cols, n_items) for c in model.correlators], args.reps)
+    tw = model.term_weights("idf")
+    w_idf = [tw[c.name] for c in model.correlators]
+    (w_count, w_idx, w_score, w_stats), ms_w = timed(lambda: sess.recommend(nq, n_items, clauses, num, excl, None, fill, 0, weights=w_idf), args.reps)
+    ws = w_stats.cpu().tolist()
+    print(f"urcco_dev_idf_weights, {len(w_idf)} calls over {[c.n_cols for c in model.correlators]} columns: {min(ms_idf):.3f} ms best ({[round(x, 3) for x in ms_idf]}); "
+          f"weights per event type (min, max, in units of 2^-15): {[(int(w.view(torch.int32).min().item()), int(w.view(torch.int32).max().item())) for w in w_idf]}")
+    print(f"urcco_dev_recommend_weighted (idf weights on every clause): {min(ms_w):.2f} ms best, {sorted(ms_w)[len(ms_w) // 2]:.2f} ms median of {args.reps} "
+          f"({[round(x, 2) for x in ms_w]}) -- unweighted call above: {min(ms_hip):.2f} ms best, {sorted(ms_hip)[len(ms_hip) // 2]:.2f} ms median")
+    live = torch.arange(num, device=dev)[None, :] < count[:, None]
+    moved = ((w_idx != idx) & live).any(1)
+    print(f"  class split: {ws[0]} LDS, {ws[1]} global; candidates {ws[3]} (unweighted {st[3]}); counts equal: {bool(torch.equal(w_count, count))}; "
+          f"queries whose list differs from the unweighted one: {int(moved.sum())} / {nq}")
+    ones = [torch.full((c.n_cols,), _lib.REC_WEIGHT_ONE, dtype=torch.int32, device=dev).view(torch.uint32) for c in model.correlators]
+    o_count, o_idx, o_score, _ = sess.recommend(nq, n_items, clauses, num, excl, None, fill, 0, weights=ones)
+    print(f"  arrays of WEIGHT_ONE: counts, ids and score bits equal the unweighted call's: "
+          f"{bool(torch.equal(o_count, count) and torch.equal(torch.where(live, o_idx, 0), torch.where(live, idx, 0)) and torch.equal(torch.where(live, o_score, 0.0).view(torch.int64), torch.where(live, score, 0.0).view(torch.int64)))}")
 
 if args.device_history:
     import time

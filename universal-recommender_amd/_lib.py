@@ -32,6 +32,8 @@ REC_NO_BACKFILL = 1
 REC_STATS_LEN = 8
 REC_MAX_RULES = 16     # urcco_dev_recommend_rules (URCCO_REC_MAX_RULES, URCCO_RULE_*)
 RULE_ANY, RULE_NONE, RULE_RANGE = 0, 1, 2
+REC_WEIGHT_ONE = 1 << 15   # urcco_dev_recommend_weighted (URCCO_REC_WEIGHT_*): term weights are uint32 in units of 2^-15 ...
+REC_WEIGHT_MAX = 1 << 20   # ... from 1 to 32.0
 EVAL_MAX_KS = 8        # urcco_dev_rank_metrics (URCCO_EVAL_MAX_KS): cut-offs per call
 EVAL_TREE_BLOCK = 256  # positions one block of the tree sum reduces (csrc/cco_eval.h): beyond it a further pass runs over the partials
 HIST_STATS_LEN = 8     # urcco_dev_history_rows (URCCO_HIST_STATS_LEN): pairs per class, selects, exclusion rows per class, overflows
@@ -209,6 +211,9 @@ SYMBOLS = {
     "urcco_dev_recommend": (C.c_int, [_p, C.c_int64, C.c_int32, C.POINTER(RecClause), C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p]),
     "urcco_dev_recommend_rules": (C.c_int, [_p, C.c_int64, C.c_int32, C.POINTER(RecClause), C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p,
                                             C.POINTER(RecRule), C.c_int32]),
+    "urcco_dev_recommend_weighted": (C.c_int, [_p, C.c_int64, C.c_int32, C.POINTER(RecClause), C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p,
+                                               C.POINTER(RecRule), C.c_int32, C.POINTER(C.c_void_p)]),
+    "urcco_dev_idf_weights": (C.c_int, [_p, C.c_int32, _p, C.c_int64, _p]),
     "urcco_dev_rank_metrics": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p, _p, C.POINTER(C.c_int32), C.c_int32, _p, _p, _p, _p, _p, _p]),
     "urcco_dev_tree_sum": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p]),
     "urcco_dev_history_index": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p]),

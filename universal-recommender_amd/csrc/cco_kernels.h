@@ -282,6 +282,8 @@ constexpr int REC_MAX_NUM = 256;
 constexpr int REC_NO_BACKFILL = 1;
 constexpr int REC_STATS_LEN = 8;
 constexpr int REC_LDS_LIMIT = 3072;   // a query whose work bound w(q) (candidate touches + exclusions) is larger runs in the global-accumulator class
+constexpr int REC_WEIGHT_ONE = 1 << 15;  // term weights of urcco_dev_recommend_weighted (decision D20): unsigned integers in units of 2^-15 ...
+constexpr int REC_WEIGHT_MAX = 1 << 20;  // ... from 1 to 32.0
 struct RecClause {
   const int64_t* ind_col_ptr;  // CSC of the indicator matrix I_c (n_items x n_cols)
   const int32_t* ind_row_idx;
@@ -307,13 +309,15 @@ struct RecRule {
   int32_t kind, n_cols;
 };
 struct RecArgs;  // cco_recommend.h
-int32_t recommend_global_blocks(int64_t n_queries, int32_t n_items, int n_cu);
-// ctr[5], list[n_queries], pos[n_items] (only with fill_order), g_state / g_m / g_list [g_blocks * n_items] words, g_score [g_blocks * n_items] doubles: scratch
+int32_t recommend_global_blocks(int64_t n_queries, int32_t n_items, int n_cu, bool weighted = false);
+// ctr[5], list[n_queries], pos[n_items] (only with fill_order), g_state / g_m / g_list [g_blocks * n_items] words, g_score [g_blocks * n_items] doubles: scratch.
+// weights != NULL (host array [n_clauses] of device pointers, entries nullable): the weighted kernels; g_m64 [g_blocks * n_items] 64-bit words then takes g_m's place
 hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t n_items, const RecClause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
                             const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
                             int32_t* out_idx, double* out_score, int64_t* stats_dev, unsigned long long* ctr, int32_t* list, int32_t* pos, int32_t g_blocks,
                             unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit = REC_LDS_LIMIT, const RecRule* rules = nullptr,
-                            int32_t n_rules = 0);
+                            int32_t n_rules = 0, const uint32_t* const* weights = nullptr, unsigned long long* g_m64 = nullptr);
+hipError_t launch_idf_weights(hipStream_t st, int n_cu, int32_t n_cols, const int64_t* col_ptr, int64_t n_docs, uint32_t* out);
 
 // ---- hold-out evaluation (cco_eval.h, compiled into cco_misc.hip behind cco_recommend.h; decision D19) ----------------------
 constexpr int EVAL_MAX_KS = 8;        // == URCCO_EVAL_MAX_KS of include/urcco.h

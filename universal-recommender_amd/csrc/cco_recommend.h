@@ -14,6 +14,10 @@
 // match counter per slot (the claiming lane appends the slot to the candidate list), then `score += boost * m; m = 0` is folded over the list -- the f64 sum
 // has the order of the clauses whatever the order of the hits.  Selection: the radix select of cco_select.h over the 96-bit key (score bits, ~position) finds
 // the num-th best candidate, the (at most num) winners are ranked by counting; then the backfill walks fill_order from the front.
+//   rec_rows_kernel<., ., true>  W = true (urcco_dev_recommend_weighted, decision D20): a hit of term h raises the counter by the clause's integer weight w_c[h]
+//                          (units of 2^-15, 1 .. REC_WEIGHT_MAX; a clause without an array: REC_WEIGHT_ONE) and the fold adds boost * ((double)M * 2^-15); the LDS
+//                          class keeps its 32-bit counters, the global class counts in a 64-bit array of its own (g_m64) in place of g_m; W = false is the code above
+//   rec_idf_kernel         urcco_dev_idf_weights: w[h] = clamp(llrint(log(1 + (n_docs - df + 0.5) / (df + 0.5)) * 2^15), 1, REC_WEIGHT_MAX), a thread per column
 #pragma once
 
 namespace urcco {
@@ -24,6 +28,11 @@ constexpr int REC_CAP_LOG2 = 12;
 constexpr int REC_CAP = 1 << REC_CAP_LOG2;  // slots of the LDS table
 constexpr int REC_LIMIT = REC_LDS_LIMIT;    // most distinct items (candidates + tombstones) a query of the LDS class can hold: load factor 0.75
 static_assert(REC_LIMIT * 4 <= REC_CAP * 3 && REC_LIMIT <= 65536, "load factor of the LDS table; 16-bit slot numbers");
+// Weighted counters (D20) cannot overflow.  LDS class: w(q) <= REC_LIMIT bounds the hits of a query, so M <= REC_LIMIT * REC_WEIGHT_MAX = 3072 * 2^20 < 2^32 and
+// the 32-bit s_m stays (the kernel clamps every loaded weight to 1 .. REC_WEIGHT_MAX, so a bad array cannot break the bound).  Global class: no cap on the
+// terms, so its weighted form counts in 64 bits: fewer than 2^43 hits of at most 2^20 each.
+static_assert((unsigned long long)REC_LIMIT * (unsigned long long)REC_WEIGHT_MAX < (1ull << 32), "weighted 32-bit LDS match counters: REC_LIMIT hits of REC_WEIGHT_MAX each");
+constexpr double REC_WEIGHT_UNIT = 1.0 / (double)REC_WEIGHT_ONE;  // 2^-15, exact
 constexpr unsigned REC_EMPTY = 0xffffffffu; // (item ids are < 2^31 - 1)
 constexpr unsigned REC_TOMB = 0x80000000u;  // slot of an item that may not be returned
 static_assert(REC_MAX_NUM <= REC_THREADS, "one thread ranks one winner");
@@ -50,7 +59,10 @@ struct RecArgs {
   double* g_score;            // by candidate ordinal
   int32_t g_blocks;
   int32_t n_rules;
-  RecRule r[REC_MAX_RULES];   // read by the <., true> instantiations only
+  RecRule r[REC_MAX_RULES];   // read by the <., true, .> instantiations only
+  // read by the <., ., true> instantiations only (urcco_dev_recommend_weighted)
+  const uint32_t* w[REC_MAX_CLAUSES];  // per clause: [n_cols] term weights in units of 2^-15, or NULL = REC_WEIGHT_ONE throughout
+  unsigned long long* g_m64;           // global class: the 64-bit match counters, g_blocks slices of n_items, zero between queries (takes the place of g_m)
 };
 static_assert(sizeof(RecArgs) <= 4096, "kernel arguments: the clause and rule tables travel by value");
 
@@ -154,7 +166,7 @@ __device__ __forceinline__ bool rec_lds_has(const unsigned* keys, unsigned item)
   return false;
 }
 
-template <bool DENSE, bool RULES>
+template <bool DENSE, bool RULES, bool WEIGHTED>
 __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
   __shared__ unsigned s_keys[DENSE ? 1 : REC_CAP];
   __shared__ unsigned s_m[DENSE ? 1 : REC_CAP];
@@ -173,7 +185,8 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
   const uint8_t* __restrict__ mask = a.item_mask;
   const int32_t* __restrict__ pos_of = a.pos;
   unsigned* g_state = DENSE ? a.g_state + (size_t)blockIdx.x * (size_t)n_items : nullptr;
-  unsigned* g_m = DENSE ? a.g_m + (size_t)blockIdx.x * (size_t)n_items : nullptr;
+  unsigned* g_m = DENSE && !WEIGHTED ? a.g_m + (size_t)blockIdx.x * (size_t)n_items : nullptr;
+  unsigned long long* g_m64 = DENSE && WEIGHTED ? a.g_m64 + (size_t)blockIdx.x * (size_t)n_items : nullptr;
   int32_t* g_list = DENSE ? a.g_list + (size_t)blockIdx.x * (size_t)n_items : nullptr;
   double* g_score = DENSE ? a.g_score + (size_t)blockIdx.x * (size_t)n_items : nullptr;
   const long long n_mine = (long long)a.ctr[DENSE ? 1 : 0];
@@ -188,8 +201,8 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
     if (tid == 0) { s_ncand = 0; s_ntomb = 0; s_nwin = 0; }
     __syncthreads();
 
-    // one hit of a clause term on `item`
-    auto hit = [&](int32_t item) {
+    // one hit of a clause term of weight `wt` (WEIGHTED only) on `item`
+    auto hit = [&](int32_t item, unsigned wt) {
       if ((unsigned)item >= (unsigned)n_items) return;
       if (DENSE) {
         unsigned st = __hip_atomic_load(&g_state[item], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -207,7 +220,10 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
             st = ok ? 1u : 2u;
           }
         }
-        if (st == 1) atomicAdd(&g_m[item], 1u);
+        if (st == 1) {
+          if (WEIGHTED) atomicAdd(&g_m64[item], (unsigned long long)wt);
+          else atomicAdd(&g_m[item], 1u);
+        }
       } else {
         bool fresh = false;
         const int slot = rec_lds_touch<RULES>(s_keys, (unsigned)item, true, mask, &fresh, &a.ctr[2], a, q);
@@ -221,7 +237,7 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
             atomicAdd(&a.ctr[2], 1ull);
           }
         }
-        atomicAdd(&s_m[slot], 1u);
+        atomicAdd(&s_m[slot], WEIGHTED ? wt : 1u);
       }
     };
 
@@ -249,24 +265,33 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
         const int32_t h = cl.q_col_idx[tb + t];
         if ((unsigned)h >= (unsigned)cl.n_cols) continue;
         const int64_t s = cl.ind_col_ptr[h], e = cl.ind_col_ptr[h + 1];
+        unsigned wt = 1u;
+        if (WEIGHTED) {  // one load per term, uniform for whoever walks the column; clamped, so the 32-bit LDS counter holds whatever the array says
+          wt = a.w[c] ? a.w[c][h] : (unsigned)REC_WEIGHT_ONE;
+          wt = wt < 1u ? 1u : wt > (unsigned)REC_WEIGHT_MAX ? (unsigned)REC_WEIGHT_MAX : wt;
+        }
         if (e - s >= 2 * REC_THREADS) {
-          for (int64_t p = s + tid; p < e; p += REC_THREADS) hit(cl.ind_row_idx[p]);
+          for (int64_t p = s + tid; p < e; p += REC_THREADS) hit(cl.ind_row_idx[p], wt);
         } else if ((int)(t & (REC_NW - 1)) == wave) {
-          for (int64_t p = s + lane; p < e; p += WAVE) hit(cl.ind_row_idx[p]);
+          for (int64_t p = s + lane; p < e; p += WAVE) hit(cl.ind_row_idx[p], wt);
         }
       }
       __syncthreads();
       const unsigned nc = s_ncand < (unsigned)(DENSE ? n_items : REC_LIMIT) ? s_ncand : (unsigned)(DENSE ? n_items : REC_LIMIT);
       const double boost = cl.boost;
       for (unsigned j = tid; j < nc; j += REC_THREADS) {
-        if (DENSE) {
+        if (DENSE && WEIGHTED) {  // (the translation unit is compiled with -ffp-contract=off: product, then sum, one rounding each)
+          const int32_t item = g_list[j];
+          const unsigned long long m = g_m64[item];
+          if (m) { g_score[j] = g_score[j] + boost * ((double)m * REC_WEIGHT_UNIT); g_m64[item] = 0; }
+        } else if (DENSE) {
           const int32_t item = g_list[j];
           const unsigned m = g_m[item];
           if (m) { g_score[j] = g_score[j] + boost * (double)m; g_m[item] = 0; }
         } else {
           const unsigned slot = s_cand[j];
           const unsigned m = s_m[slot];
-          if (m) { s_score[j] = s_score[j] + boost * (double)m; s_m[slot] = 0; }
+          if (m) { s_score[j] = s_score[j] + boost * (WEIGHTED ? (double)m * REC_WEIGHT_UNIT : (double)m); s_m[slot] = 0; }
         }
       }
       __syncthreads();
@@ -362,9 +387,33 @@ __global__ void rec_stats_kernel(const unsigned long long* __restrict__ ctr, int
   if (t < REC_STATS_LEN) stats[t] = t < 5 ? (int64_t)ctr[t] : 0;
 }
 
-// resident blocks of the global class: 20 bytes of scratch per item and block (g_state, g_m, g_list: 4 each; g_score: 8), at most 512 MiB
-int32_t recommend_global_blocks(int64_t n_queries, int32_t n_items, int n_cu) {
-  int64_t blocks = ((int64_t)512 << 20) / ((int64_t)(n_items > 0 ? n_items : 1) * 20);
+// urcco_dev_idf_weights: a thread per column.  df = the column's length (clamped to 0 .. n_docs); Lucene's BM25 idf in f64, rounded to units of 2^-15.
+__global__ __launch_bounds__(256) void rec_idf_kernel(int32_t n_cols, const int64_t* __restrict__ col_ptr, int64_t n_docs, uint32_t* __restrict__ out) {
+  for (int64_t h = (int64_t)blockIdx.x * 256 + threadIdx.x; h < n_cols; h += (int64_t)gridDim.x * 256) {
+    int64_t df = col_ptr[h + 1] - col_ptr[h];
+    if (df > n_docs) df = n_docs;
+    long long w = 1;
+    if (df > 0) {
+      const double idf = log(1.0 + ((double)(n_docs - df) + 0.5) / ((double)df + 0.5));
+      w = llrint(idf * (double)REC_WEIGHT_ONE);
+      w = w < 1 ? 1 : w > (long long)REC_WEIGHT_MAX ? (long long)REC_WEIGHT_MAX : w;
+    }
+    out[h] = (uint32_t)w;
+  }
+}
+
+hipError_t launch_idf_weights(hipStream_t st, int n_cu, int32_t n_cols, const int64_t* col_ptr, int64_t n_docs, uint32_t* out) {
+  if (n_cols <= 0) return hipSuccess;
+  int64_t blocks = ((int64_t)n_cols + 255) / 256;
+  if (blocks > (int64_t)n_cu * 8) blocks = (int64_t)n_cu * 8;
+  hipLaunchKernelGGL(rec_idf_kernel, dim3((unsigned)blocks), dim3(256), 0, st, n_cols, col_ptr, n_docs, out);
+  return hipGetLastError();
+}
+
+// resident blocks of the global class: 20 bytes of scratch per item and block (g_state, g_m, g_list: 4 each; g_score: 8), at most 512 MiB; the weighted
+// call counts in g_m64 (8) in place of g_m: 24 bytes
+int32_t recommend_global_blocks(int64_t n_queries, int32_t n_items, int n_cu, bool weighted) {
+  int64_t blocks = ((int64_t)512 << 20) / ((int64_t)(n_items > 0 ? n_items : 1) * (weighted ? 24 : 20));
   if (blocks > 2 * (int64_t)n_cu) blocks = 2 * (int64_t)n_cu;
   if (blocks > n_queries) blocks = n_queries;
   return (int32_t)(blocks < 1 ? 1 : blocks);
@@ -373,12 +422,17 @@ int32_t recommend_global_blocks(int64_t n_queries, int32_t n_items, int n_cu) {
 hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t n_items, const RecClause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
                             const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
                             int32_t* out_idx, double* out_score, int64_t* stats_dev, unsigned long long* ctr, int32_t* list, int32_t* pos, int32_t g_blocks,
-                            unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit, const RecRule* rules, int32_t n_rules) {
+                            unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit, const RecRule* rules, int32_t n_rules,
+                            const uint32_t* const* weights, unsigned long long* g_m64) {
+  const bool weighted = weights != nullptr;  // then g_m64 is the counter array of the global class and g_m is not read
   RecArgs a;
   memset(&a, 0, sizeof(a));
   for (int c = 0; c < n_clauses; ++c) a.c[c] = clauses[c];
   for (int j = 0; j < n_rules; ++j) a.r[j] = rules[j];
   a.n_rules = n_rules;
+  if (weighted)
+    for (int c = 0; c < n_clauses; ++c) a.w[c] = weights[c];
+  a.g_m64 = g_m64;
   a.n_queries = n_queries; a.n_items = n_items; a.n_clauses = n_clauses; a.num = num; a.flags = flags;
   a.lds_limit = lds_limit < REC_LIMIT ? lds_limit : REC_LIMIT;
   a.excl_row_ptr = excl_row_ptr; a.excl_col_idx = excl_col_idx; a.item_mask = item_mask; a.fill_order = fill_order;
@@ -395,17 +449,23 @@ hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t
     }
     const size_t slice = (size_t)g_blocks * (size_t)(n_items > 0 ? n_items : 1);
     if ((e = hipMemsetAsync(g_state, 0, slice * sizeof(unsigned), st)) != hipSuccess) return e;
-    if ((e = hipMemsetAsync(g_m, 0, slice * sizeof(unsigned), st)) != hipSuccess) return e;
+    if ((e = weighted ? hipMemsetAsync(g_m64, 0, slice * sizeof(unsigned long long), st) : hipMemsetAsync(g_m, 0, slice * sizeof(unsigned), st)) != hipSuccess) return e;
     int64_t wb = (n_queries + REC_NW - 1) / REC_NW;
     if (wb > (int64_t)n_cu * 8) wb = (int64_t)n_cu * 8;
     hipLaunchKernelGGL(rec_work_kernel, dim3((unsigned)wb), dim3(REC_THREADS), 0, st, a);
     const int64_t lb = n_queries < (int64_t)n_cu * 2 ? n_queries : (int64_t)n_cu * 2;  // the LDS table lets two blocks share a CU
-    if (n_rules > 0) {
-      hipLaunchKernelGGL((rec_rows_kernel<false, true>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
-      hipLaunchKernelGGL((rec_rows_kernel<true, true>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
+    if (weighted && n_rules > 0) {
+      hipLaunchKernelGGL((rec_rows_kernel<false, true, true>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<true, true, true>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
+    } else if (weighted) {
+      hipLaunchKernelGGL((rec_rows_kernel<false, false, true>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<true, false, true>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
+    } else if (n_rules > 0) {
+      hipLaunchKernelGGL((rec_rows_kernel<false, true, false>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<true, true, false>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
     } else {
-      hipLaunchKernelGGL((rec_rows_kernel<false, false>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
-      hipLaunchKernelGGL((rec_rows_kernel<true, false>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<false, false, false>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<true, false, false>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
     }
   }
   if (stats_dev) hipLaunchKernelGGL(rec_stats_kernel, dim3(1), dim3(64), 0, st, ctr, stats_dev);

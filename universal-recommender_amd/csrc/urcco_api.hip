@@ -848,10 +848,11 @@ int urcco_dev_item_rows(urcco_session* s, int64_t n_queries, const int32_t* q_it
 
 }  // extern "C"
 
-// urcco_dev_recommend (n_rules == 0) and urcco_dev_recommend_rules
+// urcco_dev_recommend (n_rules == 0), urcco_dev_recommend_rules and urcco_dev_recommend_weighted (clause_weights != NULL)
 static int recommend_call(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
                           const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
-                          int32_t* out_idx, double* out_score, int64_t* stats_dev, const urcco_rec_rule* rules, int32_t n_rules) {
+                          int32_t* out_idx, double* out_score, int64_t* stats_dev, const urcco_rec_rule* rules, int32_t n_rules,
+                          const uint32_t* const* clause_weights) {
   if (!s || n_queries < 0 || n_queries > 0x7fffffffll || n_items < 0 || n_items == 0x7fffffff) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: bad argument");
   if (num < 1 || num > URCCO_REC_MAX_NUM) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: num must lie in 1..%d, got %d", URCCO_REC_MAX_NUM, num);
   if (n_clauses < 0 || n_clauses > URCCO_REC_MAX_CLAUSES || (n_clauses > 0 && !clauses))
@@ -887,18 +888,24 @@ static int recommend_call(urcco_session* s, int64_t n_queries, int32_t n_items, 
     const long v = atol(e);
     if (v >= 0 && v < lds_limit) lds_limit = (int32_t)v;
   }
-  const int32_t g_blocks = urcco::recommend_global_blocks(n_queries, n_items, s->n_cu);
+  // the weighted kernels run when a clause carries an array: without one every weight is WEIGHT_ONE, which the unweighted kernels compute bit for bit
+  bool weighted = false;
+  for (int c = 0; clause_weights && c < n_clauses; ++c) weighted = weighted || clause_weights[c] != nullptr;
+  const int32_t g_blocks = urcco::recommend_global_blocks(n_queries, n_items, s->n_cu, weighted);
   const size_t slice = (size_t)g_blocks * (size_t)(n_items > 0 ? n_items : 1);
   ArenaLayout L(s);
   unsigned long long* ctr;
   int32_t *list, *pos, *g_list;
   unsigned *g_state, *g_m;
   double* g_score;
+  unsigned long long* g_m64;
   L.add(&ctr, 8).add(&list, (size_t)n_queries).add(&pos, (size_t)n_items);
-  L.add(&g_state, slice).add(&g_m, slice).add(&g_list, slice).add(&g_score, slice);  // the global class's per-block slices
+  L.add(&g_state, slice).add(&g_m, weighted ? 1 : slice).add(&g_list, slice).add(&g_score, slice);  // the global class's per-block slices
+  L.add(&g_m64, weighted ? slice : 1);                                                               // ... the weighted call counts in 64 bits instead of g_m
   URC(L.commit());
   HIPC(urcco::launch_recommend(s->stream, s->n_cu, n_queries, n_items, cl, n_clauses, excl_row_ptr, excl_col_idx, item_mask, fill_order, num, flags, out_count, out_idx,
-                               out_score, stats_dev, ctr, list, pos, g_blocks, g_state, g_m, g_list, g_score, lds_limit, rl, n_rules));
+                               out_score, stats_dev, ctr, list, pos, g_blocks, g_state, g_m, g_list, g_score, lds_limit, rl, n_rules, weighted ? clause_weights : nullptr,
+                               g_m64));
   return URCCO_OK;
 }
 
@@ -908,14 +915,29 @@ int urcco_dev_recommend(urcco_session* s, int64_t n_queries, int32_t n_items, co
                         const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
                         int32_t* out_idx, double* out_score, int64_t* stats_dev) {
   return recommend_call(s, n_queries, n_items, clauses, n_clauses, excl_row_ptr, excl_col_idx, item_mask, fill_order, num, flags, out_count, out_idx, out_score, stats_dev,
-                        nullptr, 0);
+                        nullptr, 0, nullptr);
 }
 
 int urcco_dev_recommend_rules(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
                               const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
                               int32_t* out_idx, double* out_score, int64_t* stats_dev, const urcco_rec_rule* rules, int32_t n_rules) {
   return recommend_call(s, n_queries, n_items, clauses, n_clauses, excl_row_ptr, excl_col_idx, item_mask, fill_order, num, flags, out_count, out_idx, out_score, stats_dev,
-                        rules, n_rules);
+                        rules, n_rules, nullptr);
+}
+
+int urcco_dev_recommend_weighted(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
+                                 const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
+                                 int32_t* out_idx, double* out_score, int64_t* stats_dev, const urcco_rec_rule* rules, int32_t n_rules,
+                                 const uint32_t* const* clause_weights) {
+  return recommend_call(s, n_queries, n_items, clauses, n_clauses, excl_row_ptr, excl_col_idx, item_mask, fill_order, num, flags, out_count, out_idx, out_score, stats_dev,
+                        rules, n_rules, clause_weights);
+}
+
+int urcco_dev_idf_weights(urcco_session* s, int32_t n_cols, const int64_t* ind_col_ptr, int64_t n_docs, uint32_t* out_weight) {
+  if (!s || n_cols < 0 || n_docs < 1) return fail(URCCO_BAD_ARG, "urcco_dev_idf_weights: n_cols must be >= 0 and n_docs >= 1");
+  if (n_cols > 0 && (!ind_col_ptr || !out_weight)) return fail(URCCO_BAD_ARG, "urcco_dev_idf_weights: an array is missing");
+  HIPC(urcco::launch_idf_weights(s->stream, s->n_cu, n_cols, ind_col_ptr, n_docs, out_weight));
+  return URCCO_OK;
 }
 
 int urcco_dev_rank_metrics(urcco_session* s, int64_t n_queries, int32_t num, const int32_t* rec_count, const int32_t* rec_idx, const int64_t* truth_row_ptr,

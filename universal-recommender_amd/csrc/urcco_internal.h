@@ -18,7 +18,8 @@
 static_assert(urcco::EXCH_SIZES == URCCO_EXCH_SIZES && urcco::STATS_LEN == URCCO_STATS_LEN, "include/urcco.h and cco_kernels.h agree");
 static_assert(urcco::REC_MAX_CLAUSES == URCCO_REC_MAX_CLAUSES && urcco::REC_MAX_NUM == URCCO_REC_MAX_NUM && urcco::REC_NO_BACKFILL == URCCO_REC_NO_BACKFILL &&
                   urcco::REC_STATS_LEN == URCCO_REC_STATS_LEN && urcco::REC_MAX_RULES == URCCO_REC_MAX_RULES && urcco::REC_RULE_ANY == URCCO_RULE_ANY &&
-                  urcco::REC_RULE_NONE == URCCO_RULE_NONE && urcco::REC_RULE_RANGE == URCCO_RULE_RANGE,
+                  urcco::REC_RULE_NONE == URCCO_RULE_NONE && urcco::REC_RULE_RANGE == URCCO_RULE_RANGE &&
+                  urcco::REC_WEIGHT_ONE == URCCO_REC_WEIGHT_ONE && urcco::REC_WEIGHT_MAX == URCCO_REC_WEIGHT_MAX,
               "include/urcco.h and cco_kernels.h agree on the recommendation call");
 static_assert(urcco::HIST_STATS_LEN == URCCO_HIST_STATS_LEN, "include/urcco.h and cco_kernels.h agree on the history calls");
 static_assert(urcco::EVAL_MAX_KS == URCCO_EVAL_MAX_KS, "include/urcco.h and cco_kernels.h agree on the evaluation call");

@@ -219,7 +219,7 @@ class DeviceSession:
         return DevIndicators(item_lo, item_hi, b.n_cols, k, c_rp, c_idx, c_llr, stats, b.row_ptr, b.col_idx)
 
     def recommend(self, n_queries: int, n_items: int, clauses, num: int, excl=None, item_mask: Optional[torch.Tensor] = None,
-                  fill_order: Optional[torch.Tensor] = None, flags: int = 0, stats: bool = True, rules=None):
+                  fill_order: Optional[torch.Tensor] = None, flags: int = 0, stats: bool = True, rules=None, weights=None):
         """urcco_dev_recommend: the top `num` of sum_c boost_c |T_c(q) ^ I_c(i)| per query row over the eligible items, in the order (score
         desc, backfill position asc).  clauses: (n_cols, boost, ind_col_ptr, ind_row_idx, q_row_ptr, q_col_idx) per should-clause, device
         tensors (the CSC of the indicator matrix, the CSR of the query terms); excl: (row_ptr, col_idx) of the exclusion CSR or None.
@@ -227,7 +227,12 @@ class DeviceSession:
         only the first count[q] entries of a row are written.  Enqueues, does not synchronise.
         rules (urcco_dev_recommend_rules; None = the rule-free call): per rule (RULE_ANY | RULE_NONE, n_cols, m_row_ptr, m_col_idx, q_row_ptr, q_col_idx)
         -- the CSR of the item x value matrix and of the query rows -- or (RULE_RANGE, item_value, q_lo, q_hi), int64 device tensors; an item is
-        eligible only when every rule holds for (query, item)."""
+        eligible only when every rule holds for (query, item).
+        weights (urcco_dev_recommend_weighted, decision D20; None = the calls above): a list parallel to `clauses` of uint32 device tensors [n_cols] -- the
+        clause's term weights in units of 2^-15, 1 .. REC_WEIGHT_MAX, e.g. from idf_weights -- or None for a clause whose terms all weigh REC_WEIGHT_ONE;
+        the score is then sum_c boost_c * (sum of the weights of the shared terms) * 2^-15, still exact and independent of the order of the hits."""
+        if weights is not None and len(weights) != len(clauses):
+            raise ValueError("weights: one entry (a uint32 tensor or None) per clause")
         arr = (_lib.RecClause * max(len(clauses), 1))()
         for c, (n_cols, boost, cp, ri, qrp, qci) in enumerate(clauses):
             arr[c].n_cols, arr[c].boost = int(n_cols), float(boost)
@@ -238,9 +243,10 @@ class DeviceSession:
         st = self.empty(_lib.REC_STATS_LEN, torch.int64) if stats else None
         args = (self.handle, n_queries, n_items, arr, len(clauses), _ptr(excl[0]) if excl is not None else None, _ptr(excl[1]) if excl is not None else None,
                 _ptr(item_mask), _ptr(fill_order), num, flags, _ptr(o_count), _ptr(o_idx), _ptr(o_score), _ptr(st))
-        if rules is None:
+        if rules is None and weights is None:
             self._check(self.lib.urcco_dev_recommend(*args))
         else:
+            rules = rules or ()
             rl = (_lib.RecRule * max(len(rules), 1))()
             for j, rule in enumerate(rules):
                 rl[j].kind = int(rule[0])
@@ -249,9 +255,23 @@ class DeviceSession:
                 else:
                     rl[j].n_cols = int(rule[1])
                     rl[j].m_row_ptr, rl[j].m_col_idx, rl[j].q_row_ptr, rl[j].q_col_idx = (_ptr(t) for t in rule[2:6])
-            self._check(self.lib.urcco_dev_recommend_rules(*args, rl, len(rules)))
+            if weights is None:
+                self._check(self.lib.urcco_dev_recommend_rules(*args, rl, len(rules)))
+            else:
+                for c, w in enumerate(weights):
+                    if w is not None and (w.dtype != torch.uint32 or w.numel() < int(clauses[c][0])):
+                        raise ValueError(f"weights[{c}]: a uint32 tensor of at least n_cols = {int(clauses[c][0])} entries")
+                wp = (C.c_void_p * max(len(weights), 1))(*[_ptr(w) for w in weights])
+                self._check(self.lib.urcco_dev_recommend_weighted(*args, rl, len(rules), wp))
         n = max(n_queries, 0)
         return o_count[:n], o_idx[: n * max(num, 0)].view(n, -1) if n and num > 0 else o_idx[:0], o_score[: n * max(num, 0)].view(n, -1) if n and num > 0 else o_score[:0], st
+
+    def idf_weights(self, col_ptr: torch.Tensor, n_cols: int, n_docs: int) -> torch.Tensor:
+        """urcco_dev_idf_weights: uint32 [n_cols], clamp(llrint(log(1 + (n_docs - df + 0.5) / (df + 0.5)) * 2^15), 1, REC_WEIGHT_MAX) with df the length of
+        column h of the CSC whose column starts are col_ptr (int64 [n_cols + 1], device); a column nothing lists gets 1.  Enqueues, does not synchronise."""
+        out = self.empty(max(n_cols, 1), torch.uint32)
+        self._check(self.lib.urcco_dev_idf_weights(self.handle, n_cols, _ptr(col_ptr), n_docs, _ptr(out)))
+        return out[: max(n_cols, 0)]
 
     def rank_metrics(self, count: torch.Tensor, idx: torch.Tensor, truth_row_ptr: torch.Tensor, truth_col_idx: torch.Tensor, ks, discount: Optional[torch.Tensor] = None,
                      sums: bool = True, out=None):

@@ -40,7 +40,8 @@ def _report(ks, sums_i, tree_ap, tree_ndcg, per_user) -> dict:
 
 
 def evaluate(algo, model: DeviceModel, train, test, ks: Sequence[int] = (1, 5, 10, 20), num: Optional[int] = None, event_names=None,
-             truth_event: Optional[str] = None, chunk: int = 65536, user_bias: Optional[float] = None, item_mask=None, now_ms: Optional[int] = None):
+             truth_event: Optional[str] = None, chunk: int = 65536, user_bias: Optional[float] = None, item_mask=None, now_ms: Optional[int] = None,
+             term_weights=None):
     """Scores the model's recommendations for every user id of `train` (what user_recommendations answers over it, under `event_names` /
     `user_bias`) against the user's `truth_event` items in `test`.  train, test: DeviceHistory objects over ONE user id space.  truth_event:
     default the model's primary event; its stream in `test` carries the primary's item ids (no column map).  ks: strictly ascending cut-offs, at
@@ -49,13 +50,13 @@ def evaluate(algo, model: DeviceModel, train, test, ks: Sequence[int] = (1, 5, 1
     "hit_rate" (users with a hit / evaluated), "map", "ndcg" (the D19 tree sums / evaluated): a list per k, 0.0 when nobody was evaluated;
     "per_user": {"hits" int32, "ap", "ndcg" float64: device tensors [n_users, n_ks]}}.  event_names as a list of lists: one report per event mix,
     in a list -- the reference's predictiveness test of an indicator mix.  One synchronisation per chunk (the history calls' bound totals) and
-    one at the end."""
+    one at the end.  term_weights: passed to user_recommendations (decision D20) -- what the weights buy on a data set is measured by evaluating twice."""
     if not isinstance(train, DeviceHistory) or not isinstance(test, DeviceHistory):
         raise ValueError("evaluate needs two history.DeviceHistory objects, the training and the held-out events")
     if train.n_users != test.n_users or not (train.user_ids is test.user_ids or train.user_ids == test.user_ids):
         raise ValueError("train and test must share one user id space")
     if event_names is not None and len(event_names) and all(isinstance(e, (list, tuple)) for e in event_names):
-        return [evaluate(algo, model, train, test, ks, num, list(mix), truth_event, chunk, user_bias, item_mask, now_ms) for mix in event_names]
+        return [evaluate(algo, model, train, test, ks, num, list(mix), truth_event, chunk, user_bias, item_mask, now_ms, term_weights) for mix in event_names]
     ks = [int(k) for k in ks]
     if not 1 <= len(ks) <= _lib.EVAL_MAX_KS or ks[0] < 1 or any(b <= a for a, b in zip(ks, ks[1:])):
         raise ValueError(f"ks: between 1 and {_lib.EVAL_MAX_KS} strictly ascending cut-offs >= 1, got {ks}")
@@ -80,7 +81,7 @@ def evaluate(algo, model: DeviceModel, train, test, ks: Sequence[int] = (1, 5, 1
     truth_spec = [(st.n_cols, TRUTH_CAP, False, st.idx_row_ptr, st.idx_pos, st.items, st.times, None)]
     for lo in range(0, n, chunk):
         q = torch.arange(lo, min(lo + chunk, n), dtype=torch.int32, device=dev)
-        count, idx, _ = user_recommendations(algo, model, train, q, num, event_names, user_bias, chunk, item_mask, now_ms)
+        count, idx, _ = user_recommendations(algo, model, train, q, num, event_names, user_bias, chunk, item_mask, now_ms, term_weights)
         (truth,), _, _ = sess.history_rows(q, test.n_users, truth_spec, model.n_items)
         hi = lo + int(q.numel())
         _, _, _, s_i, _ = sess.rank_metrics(count, idx, truth[0], truth[1], ks, discount, sums=True, out=(hits[lo:hi], ap[lo:hi], ndcg[lo:hi]))

@@ -20,7 +20,14 @@ urcco_dev_recommend_rules evaluates on the device per (query, item), inside the 
                          should-clause; an event without history matches nothing, as an empty `terms` query does (:688-693)
     itemBias < 0         the same with the query item's own indicator lists (:695-699)
 An unknown property name or value has no column: an ANY on it matches nothing, a NONE or a boost on it does nothing.  A model built WITHOUT
-properties raises NotImplementedError (naming the key) for all of these, as before.  Not served: engine.json-level `fields`.  Items outside the
+properties raises NotImplementedError (naming the key) for all of these, as before.
+
+Term weights (decision D20): every entry point takes `term_weights`.  None scores every matching term 1 (D15, the calls above).  "idf" weighs a term by
+its rarity -- DeviceModel.term_weights: Lucene's BM25 idf of the term among the items whose field is not empty, as urcco_dev_idf_weights rounds it to
+units of 2^-15 -- and a dict {event or property name: uint32 device tensor, one weight per column} gives the caller's own.  Every should-clause then
+carries the array of its matrix (user history, similar items, item set: the event's; a boosted `fields` clause: the property's) and the call is
+urcco_dev_recommend_weighted; ANY / NONE rules are filters and carry no weight.  Ids and score bits stay reproducible.  It is NOT Elasticsearch's BM25:
+the length norm and the per-shard statistics are left out.  Not served: engine.json-level `fields`.  Items outside the
 primary event's item dictionary are never returned."""
 from __future__ import annotations
 
@@ -72,6 +79,7 @@ class DeviceModel:
         self.by_name = {c.name: c for c in correlators}
         self.properties = properties    # None: built without item properties -- batch_predict serves no business rules
         self.dates = dates or {}        # date property -> int64 [n_items] epoch milliseconds, NO_VALUE where the item has none
+        self._term_weights: Dict[str, Dict[str, torch.Tensor]] = {}   # term_weights(kind), built on first use
 
     @staticmethod
     def from_indicators(sess: DeviceSession, correlators: Sequence[Tuple[str, object]], ranks: Optional[Dict[object, float]] = None,
@@ -149,6 +157,22 @@ class DeviceModel:
             return None
         return i if 0 <= i < c.n_cols else None
 
+    def term_weights(self, kind: str = "idf") -> Dict[str, torch.Tensor]:
+        """{event name or list-of-strings property name: uint32 device tensor [n_cols]}: the term weights of decision D20 for every matrix a should-clause
+        can be built on, in units of 2^-15.  kind "idf": urcco_dev_idf_weights over the matrix's CSC with n_docs = the items whose row of the matrix is not
+        empty (Elasticsearch's doc count of the field; at least 1), read from the CSR row_ptr the model holds.  Built on first use and cached; where a
+        property shares its name with an event type, the event's array is the one under the name."""
+        if kind != "idf":
+            raise ValueError(f"term weights of kind {kind!r} are not known ('idf' is)")
+        if kind not in self._term_weights:
+            out: Dict[str, torch.Tensor] = {}
+            for m in list((self.properties or {}).values()) + list(self.correlators):
+                rp = m.row_ptr[: self.n_items + 1]
+                n_docs = int((rp[1:] > rp[:-1]).sum().item()) if self.n_items else 0
+                out[m.name] = self.sess.idf_weights(m.col_ptr, m.n_cols, max(n_docs, 1))
+            self._term_weights[kind] = out
+        return self._term_weights[kind]
+
     def indicator_row(self, c: _Correlator, i: int) -> np.ndarray:
         """Column indices of item i's indicator list for this event, strongest first (one read of the matrix per model)."""
         if c.host is None:
@@ -225,13 +249,32 @@ def _mask_tensor(model: DeviceModel, item_mask) -> Optional[torch.Tensor]:
     return mask_t
 
 
+def _term_weights(algo, model: DeviceModel, term_weights) -> Optional[Dict[str, torch.Tensor]]:
+    """None (the algorithm's termWeights parameter decides; absent: unweighted), "none", "idf" or {name: uint32 device tensor} -> None = the unweighted
+    calls, or the dict the clauses look their matrix's name up in (a name it does not hold: every term of that clause weighs 1.0)"""
+    if term_weights is None:
+        term_weights = getattr(algo.ap, "termWeights", None)
+    if term_weights is None or (isinstance(term_weights, str) and term_weights == "none"):
+        return None
+    if isinstance(term_weights, str):
+        return model.term_weights(term_weights)
+    if not isinstance(term_weights, dict):
+        raise ValueError("term_weights: None, 'none', 'idf' or a dict {event or property name: uint32 device tensor}")
+    sizes = {m.name: m.n_cols for m in list((model.properties or {}).values()) + list(model.correlators)}
+    for name, w in term_weights.items():
+        if not torch.is_tensor(w) or w.dtype != torch.uint32 or w.dim() != 1 or w.device != model.sess.device or w.numel() != sizes.get(name, w.numel()):
+            raise ValueError(f"term_weights[{name!r}]: a uint32 tensor on the model's device with one weight per column of the matrix")
+    return term_weights
+
+
 def _max_query_events(ap) -> int:
     if ap.indicators:                                                                          # :203-211
         return sum(i.maxItemsPerUser if i.maxItemsPerUser is not None else 100 for i in ap.indicators) * 10
     return ap.maxQueryEvents if ap.maxQueryEvents is not None else 100
 
 
-def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host") -> List[dict]:
+def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host",
+                  term_weights=None) -> List[dict]:
     """URAlgorithm.predict for a list of query dicts: [{"itemScores": [{"item", "score"}, ...]}, ...] in the order of `queries`.
     history: user -> {event name: [item ids, oldest first]} (the event store's view of the user), or a history.DeviceHistory: the event streams
     resident on the device.  With a DeviceHistory the user-history term rows (the ("user", ev) clauses, or the ("hist", ev) ANY rules under
@@ -248,7 +291,10 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
     ids (-1 for a member without a known item), with max_terms = maxQueryEvents; no matrix comes back to the host.  A group in which any member names a
     known item then carries the item clause of EVERY event type of the model, also where all its rows turn out empty (the host route leaves such a
     clause out): an all-empty clause adds 0.0 * boost, so every score stays bit-identical to the host route, but the 16-clause limit of a call can be
-    reached earlier."""
+    reached earlier.
+    term_weights: None (the algorithm's termWeights parameter, absent: every matching term scores 1 -- the calls are then the unweighted ones), "none",
+    "idf" (DeviceModel.term_weights) or {event or property name: uint32 device tensor}: decision D20, see the module's head."""
+    tw = _term_weights(algo, model, term_weights)
     if item_rows not in ("host", "device"):
         raise ValueError(f"item_rows must be 'host' or 'device', got {item_rows!r}")
     dev_items = item_rows == "device"
@@ -423,6 +469,7 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
         if len(rule_keys) > _lib.REC_MAX_RULES:
             raise ValueError(f"a batch needs {len(rule_keys)} rules, more than the {_lib.REC_MAX_RULES} one call serves")
         clauses = []
+        weights = None if tw is None else [tw.get(c.name) for _, c, _ in slots]                 # the clause's matrix names its array
         for slot, c, boost in slots:
             qrp, qci = (hist_rows[slot[1]] if slot[0] == "user" and dh is not None else item_dev[slot[1]] if slot[0] == "item" and dev_items else
                         _csr([plans[n][0].get(slot, empty) for n in members], dev))
@@ -442,7 +489,8 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
                     qrp, qci = (hist_rows[rk[1]] if rk[0] == "hist" and rk[1] in hist_rows else item_dev[rk[1]] if rk[0] == "sim" and dev_items else
                                 _csr([plans[n][4][rk] for n in members], dev))
                     rules.append((_lib.RULE_NONE if rk[0] == "none" else _lib.RULE_ANY, m.n_cols, m.row_ptr, m.col_idx, qrp, qci))
-        count, idx, score, _ = model.sess.recommend(len(members), model.n_items, clauses, fetch, excl, mask_t, model.fill_order, flags, stats=False, rules=rules)
+        count, idx, score, _ = model.sess.recommend(len(members), model.n_items, clauses, fetch, excl, mask_t, model.fill_order, flags, stats=False, rules=rules,
+                                                    weights=weights)
         model.sess.synchronize()
         count, idx, score = count.cpu().numpy(), idx.cpu().numpy(), score.cpu().numpy()
         for r, n in enumerate(members):
@@ -452,7 +500,7 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
 
 
 def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = None, item_bias: Optional[float] = None, return_self: Optional[bool] = None,
-                  chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None):
+                  chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None):
     """The item-to-item table ("people who liked this also liked"): row n is what batch_predict answers to {"item": items[n]} -- the same items in the
     same order with the same scores -- as three device tensors (count int32 [n], idx int32 [n, num], score float64 [n, num]); entries behind count[n]
     are -1 / 0.0.  No Python work per item: the queries go `chunk` at a time through DeviceSession.item_rows (decision D18) and recommend, and no
@@ -461,9 +509,10 @@ def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = Non
     as batch_predict serves an unknown item (the backfill alone).  num, item_bias, return_self: default to the algorithm's num (20), itemBias (1.0),
     returnSelf (False).  item_bias > 0: one should-clause per event type of the model over the item's own indicator lists, boost = the bias;
     item_bias < 0: the lists are ANY rules instead (a model built with item properties, {} will do).  The query item is excluded unless return_self.
-    Backfill, recsModel, item_mask and the available / expire date rule around now_ms are those of batch_predict."""
+    Backfill, recsModel, item_mask, the available / expire date rule around now_ms and term_weights are those of batch_predict."""
     ap = algo.ap
     sess, dev = model.sess, model.sess.device
+    tw = _term_weights(algo, model, term_weights)
     model_events = list(algo.modelEventNames)
     for ev in model_events:
         if ev not in model.by_name:
@@ -525,7 +574,8 @@ def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = Non
                 c, i, s = torch.where(known, c, c2), torch.where(known[:, None], i, i2), torch.where(known[:, None], s, s2)
         else:
             clauses = [(model.by_name[ev].n_cols, _boost(bias), model.by_name[ev].col_ptr, model.by_name[ev].row_idx, qrp, qci) for ev, (qrp, qci) in zip(model_events, rows)]
-            c, i, s, _ = sess.recommend(m, model.n_items, clauses, num, excl, mask_t, model.fill_order, flags, stats=False, rules=rules)
+            c, i, s, _ = sess.recommend(m, model.n_items, clauses, num, excl, mask_t, model.fill_order, flags, stats=False, rules=rules,
+                                        weights=None if tw is None else [tw.get(ev) for ev in model_events])
         live = torch.arange(num, device=dev)[None, :] < c[:, None]
         count[lo:lo + m] = c
         idx[lo:lo + m] = torch.where(live, i, idx[lo:lo + m])
@@ -534,7 +584,7 @@ def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = Non
 
 
 def user_recommendations(algo, model: DeviceModel, history, users=None, num: Optional[int] = None, event_names: Optional[Sequence[str]] = None,
-                         user_bias: Optional[float] = None, chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None):
+                         user_bias: Optional[float] = None, chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None):
     """The per-user table, the user-side twin of similar_items: row n is what batch_predict answers to {"user": users[n]} (with "eventNames", "num" and
     "userBias" where given) over the same DeviceHistory -- the same items in the same order with the same scores -- as three device tensors (count
     int32 [n], idx int32 [n, num], score float64 [n, num]); entries behind count[n] are -1 / 0.0.  No Python work per user: the queries go `chunk`
@@ -545,8 +595,9 @@ def user_recommendations(algo, model: DeviceModel, history, users=None, num: Opt
     the query's `eventNames`, default the model's event types.  user_bias > 0: one should-clause per event type over the user's recent items, boost
     = the bias; user_bias < 0: the rows are ANY rules instead (a model built with item properties, {} will do) -- every query carries them, so an
     unknown user or an event without history matches nothing, as in batch_predict.  The blacklist events' exclusions, backfill, recsModel, item_mask
-    and the available / expire date rule around now_ms are those of batch_predict."""
+    the available / expire date rule around now_ms and term_weights are those of batch_predict."""
     from .history import DeviceHistory
+    tw = _term_weights(algo, model, term_weights)
     if not isinstance(history, DeviceHistory):
         raise ValueError("user_recommendations needs a history.DeviceHistory (the event streams resident on the device)")
     dh = history
@@ -609,12 +660,13 @@ def user_recommendations(algo, model: DeviceModel, history, users=None, num: Opt
         if served:
             rules = [(_lib.RULE_RANGE, value, torch.full((m,), lo_ms, dtype=torch.int64, device=dev), torch.full((m,), hi_ms, dtype=torch.int64, device=dev))
                      for value, lo_ms, hi_ms in dates]
-        clauses = []
+        clauses, weights = [], None
         if bias < 0:                                                                            # a filter per event, no should-clause; an event without history matches nothing
             rules = rules + [(_lib.RULE_ANY, model.by_name[ev].n_cols, model.by_name[ev].row_ptr, model.by_name[ev].col_idx) + hist_rows.get(ev, none) for ev in rule_events]
         else:                                                                                   # the clauses in the model's order, as batch_predict lays them out
             clauses = [(c.n_cols, _boost(bias), c.col_ptr, c.row_idx) + hist_rows[c.name] for c in model.correlators if c.name in hist_rows]
-        c, i, s, _ = sess.recommend(m, model.n_items, clauses, num, excl, mask_t, model.fill_order, flags, stats=False, rules=rules)
+            weights = None if tw is None else [tw.get(c.name) for c in model.correlators if c.name in hist_rows]
+        c, i, s, _ = sess.recommend(m, model.n_items, clauses, num, excl, mask_t, model.fill_order, flags, stats=False, rules=rules, weights=weights)
         live = torch.arange(num, device=dev)[None, :] < c[:, None]
         count[lo:lo + m] = c
         idx[lo:lo + m] = torch.where(live, i, idx[lo:lo + m])

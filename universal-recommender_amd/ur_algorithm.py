@@ -135,6 +135,7 @@ class URAlgorithmParams:
     itemBias: Optional[float] = None
     blacklistEvents: Optional[List[str]] = None    # :236: None = the primary event, [] = no blacklist
     returnSelf: Optional[bool] = None              # :237
+    termWeights: Optional[str] = None              # additive key: the default of the query side's term_weights (decision D20): absent = every matching term scores 1, "idf"
 
     @staticmethod
     def from_engine_json(engine: dict, name: str = "ur") -> "URAlgorithmParams":
@@ -155,7 +156,7 @@ class URAlgorithmParams:
             indicators=None if inds is None else [IndicatorParams(i["name"], i.get("maxItemsPerUser"), i.get("maxCorrelatorsPerItem"),
                                                                   i.get("minLLR")) for i in inds],
             seed=p.get("seed"), num=p.get("num"), maxQueryEvents=p.get("maxQueryEvents"), userBias=p.get("userBias"), itemBias=p.get("itemBias"),
-            blacklistEvents=p.get("blacklistEvents"), returnSelf=p.get("returnSelf"))
+            blacklistEvents=p.get("blacklistEvents"), returnSelf=p.get("returnSelf"), termWeights=p.get("termWeights"))
 
 
 def _get_or_else(v, default):
@@ -264,38 +265,41 @@ class URAlgorithm:
         return list(zip([n for n, _ in data.actions], res))                                    # :349
 
 
-    def batch_predict(self, model, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host") -> List[dict]:
+    def batch_predict(self, model, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host",
+                      term_weights=None) -> List[dict]:
         """URAlgorithm.predict (:484-535) for a batch of queries against a recommend.DeviceModel: user history, similar-item and itemSet
         queries, blacklists, backfill by rank and -- for a model built with item properties -- the business rules (fields, dateRange, available /
         expire dates around now_ms, negative biases); see recommend.batch_predict for what is mirrored and what is left out.  history: the dict
         user -> {event: [items, oldest first]} or a history.DeviceHistory (the event streams resident on the device).  item_rows="device": the query
-        items' own indicator lists are cut on the device instead of planned one by one from a host copy of the matrices."""
+        items' own indicator lists are cut on the device instead of planned one by one from a host copy of the matrices.  term_weights (here and in the
+        methods below): None = the algorithm parameter termWeights (absent: every matching term scores 1), "none", "idf" or {event or property name:
+        uint32 device tensor} -- decision D20, see recommend.py."""
         from .recommend import batch_predict
-        return batch_predict(self, model, queries, history, item_mask, now_ms, item_rows)
+        return batch_predict(self, model, queries, history, item_mask, now_ms, item_rows, term_weights)
 
     def similar_items(self, model, items=None, num: Optional[int] = None, item_bias: Optional[float] = None, return_self: Optional[bool] = None,
-                      chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None):
+                      chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None):
         """The item-to-item table of `items` (None: every item of the model) as device tensors (count, idx, score): row n is what batch_predict
         answers to {"item": items[n]}; see recommend.similar_items."""
         from .recommend import similar_items
-        return similar_items(self, model, items, num, item_bias, return_self, chunk, item_mask, now_ms)
+        return similar_items(self, model, items, num, item_bias, return_self, chunk, item_mask, now_ms, term_weights)
 
     def user_recommendations(self, model, history, users=None, num: Optional[int] = None, event_names=None, user_bias: Optional[float] = None,
-                             chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None):
+                             chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None):
         """The per-user table of `users` (None: every user id of the history.DeviceHistory) as device tensors (count, idx, score): row n is what
         batch_predict answers to {"user": users[n]} over the same history; see recommend.user_recommendations."""
         from .recommend import user_recommendations
-        return user_recommendations(self, model, history, users, num, event_names, user_bias, chunk, item_mask, now_ms)
+        return user_recommendations(self, model, history, users, num, event_names, user_bias, chunk, item_mask, now_ms, term_weights)
 
     def evaluate(self, model, train, test, ks=(1, 5, 10, 20), num: Optional[int] = None, event_names=None, truth_event: Optional[str] = None,
-                 chunk: int = 65536, user_bias: Optional[float] = None, item_mask=None, now_ms: Optional[int] = None):
+                 chunk: int = 65536, user_bias: Optional[float] = None, item_mask=None, now_ms: Optional[int] = None, term_weights=None):
         """Hold-out evaluation on the device (decision D19): precision, hit rate, MAP@k and NDCG@k of the recommendations over the `train` history
         against the users' `truth_event` items in the `test` history; a list of event mixes gives a list of reports.  See evaluate.evaluate."""
         from .evaluate import evaluate
-        return evaluate(self, model, train, test, ks, num, event_names, truth_event, chunk, user_bias, item_mask, now_ms)
+        return evaluate(self, model, train, test, ks, num, event_names, truth_event, chunk, user_bias, item_mask, now_ms, term_weights)
 
-    def predict(self, model, query: dict, history, item_mask=None, now_ms: Optional[int] = None) -> dict:
-        return self.batch_predict(model, [query], history, item_mask, now_ms)[0]
+    def predict(self, model, query: dict, history, item_mask=None, now_ms: Optional[int] = None, term_weights=None) -> dict:
+        return self.batch_predict(model, [query], history, item_mask, now_ms, term_weights=term_weights)[0]
 
     def train_events_on_device(self, trainingData, sess) -> List[Tuple[str, IndexedDataset]]:
         """Preparator.prepare + URAlgorithm.calcAll without leaving the GPU in between: the event streams are hashed on
