@@ -605,6 +605,15 @@ int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double
  * Everything is integer and the order is total: the rows are bit-identical from run to run, whatever order the index build's scatter produced.
  *
  * urcco_dev_history_index: out_pos[out_row_ptr[u] .. out_row_ptr[u + 1]) = the stream positions p with users[p] == u, order unspecified.
+ * urcco_dev_history_append (DESIGN.md decision D21): the index of a stream that grew by a batch, from the old index and the batch's users alone.  The old
+ *   index (old_row_ptr [n_users_old + 1], old_pos) covers the stream positions 0 .. n_old; new_users[p] is the user of position n_old + p, p = 0 .. n_new;
+ *   n_users >= n_users_old is the user id space after the append.  The result is an index of the concatenated stream in the sense of _index: for every
+ *   user u the segment out_pos[out_row_ptr[u] .. out_row_ptr[u + 1]) holds FIRST u's old segment in its old order (empty for u >= n_users_old), THEN the
+ *   positions n_old + p with new_users[p] == u in unspecified order.  new_users[p] < 0 or >= n_users belongs to nobody.  out_row_ptr / out_pos must not
+ *   overlap old_row_ptr / old_pos (the old segments are copied at their new offsets; nothing else of the old index is read, no `users` array of the old
+ *   stream is needed).  n_new == 0 with n_users > n_users_old extends the id space only; n_old == 0, n_users_old == 0 with NULL old arrays is _index of
+ *   the batch.  old_row_ptr is needed when n_users_old > 0, old_pos when also n_old > 0, new_users when n_new > 0, out_pos when anything is written.
+ *   URCCO_BAD_ARG: n_old + n_new >= 2^31, n_users < n_users_old, a negative count, a NULL the call needs.
  * urcco_dev_history_bounds: term_row_ptr of every type and excl_row_ptr receive the exclusive scans of upper bounds of the rows' lengths (min(n_u, max_items);
  *   blacklist events + extra row).  The caller reads the 1 + n_types totals (term_row_ptr[n_queries], excl_row_ptr[n_queries]: its one synchronisation),
  *   allocates term_col_idx / excl_col_idx of at least that many entries and states the sizes in term_capacity / excl_capacity.
@@ -615,12 +624,18 @@ int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double
  * stats_dev (nullable, int64[URCCO_HIST_STATS_LEN]): (query, type) pairs served by [0] the wave class (<= 64 events), [1] the block class (<= 4096, keys in
  *   LDS), [2] the global class; [3] pairs that ran the select (n_u > max_items); exclusion rows built by [4] one wave, [5] one block; [6] rows dropped
  *   for lack of capacity (0 when the caller sized its buffers by the bounds); [7] 0.
- * All three enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: n_events >= 2^31, n_types outside
+ * All four enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: n_events >= 2^31, n_types outside
  * 1..URCCO_REC_MAX_CLAUSES, max_items < 1, n_queries * (n_types + 1) >= 2^31, a NULL the call needs, a half-NULL extra pair, a negative capacity.
  * ABI: additions within ABI 305 -- the presence of the symbols is the feature test. */
 #define URCCO_HIST_STATS_LEN 8
 int urcco_dev_history_index(urcco_session* s, int64_t n_events, const int32_t* users, int64_t n_users,
                             int64_t* out_row_ptr /* [n_users + 1] */, int32_t* out_pos /* capacity n_events */);
+int urcco_dev_history_append(urcco_session* s,
+                             int64_t n_old,                      /* events the old index covers: stream positions 0 .. n_old */
+                             int64_t n_users_old, const int64_t* old_row_ptr /* [n_users_old + 1] */, const int32_t* old_pos,
+                             int64_t n_new, const int32_t* new_users,        /* users of stream positions n_old .. n_old + n_new */
+                             int64_t n_users,                                /* >= n_users_old: the id space after the append */
+                             int64_t* out_row_ptr /* [n_users + 1] */, int32_t* out_pos /* capacity n_old + n_new */);
 
 typedef struct urcco_hist_event {
   int32_t n_cols, max_items;          /* max_items >= 1 */

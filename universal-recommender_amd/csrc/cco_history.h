@@ -4,6 +4,7 @@
 // What the reference reads from the event store per query (getBiasedRecentUserActions, URAlgorithm.scala:795-839: the most recent
 // maxItemsPerUser events per event type, then distinct; getExcludedItems, :741-767: every item of the blacklist events) is here
 //   index   stream positions by user: count per user -> scan -> scatter by cursor (order inside a user's segment unspecified)
+//   append  the index of the stream grown by a batch: old segments copied at their shifts, the batch scattered behind them (D21)
 //   bounds  per (query, type) min(n_u, max_items), per query the blacklist events + the extra exclusion row: scans = raw row starts
 //   rows    per (query, type): the window = the min(n_u, max_items) largest keys (time, position) of the user's events -- found by an
 //           8-bit radix SELECT over the 96-bit keys when n_u > max_items, never by sorting the events -- then sort + unique of the
@@ -64,6 +65,115 @@ hipError_t launch_history_index(hipStream_t st, int n_cu, int64_t n, const int32
   e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)n_users, st);  // now the scatter cursors
   if (e != hipSuccess) return e;
   if (n > 0) hipLaunchKernelGGL(hs_scatter_pos_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, users, n_users, out_row_ptr, cnt, out_pos);
+  return hipGetLastError();
+}
+
+// ---- append (decision D21) -----------------------------------------------------------------------------------------
+// The index of a stream that grew by a batch, from the old index and the batch's users alone.  add[u] = the batch's events of the users below u
+// (count -> scan, as in the index build): user u's old segment moves from old_row_ptr[u] to old_row_ptr[u] + add[u] unchanged, the batch's positions
+// n_old + p fill the gap behind it.  The copy is balanced by ENTRIES: a block takes HA_TILE consecutive entries of old_pos, whatever the users are,
+// finds the tile's first and last user with one binary search each, and every entry then finds its user among those -- in LDS when the tile touches
+// at most HA_LDS_USERS users (empty ones in between included), in global memory otherwise.  HA_LDS_USERS >= HA_TILE: a tile without empty users
+// touches at most HA_TILE of them, so users with one event each are staged too and only a tile that crosses a run of empty users searches global
+// memory.  A tile inside one user's segment is a coalesced copy at a constant shift; a run of empty users at a tile's edge costs the two searches that
+// step over it.  No atomics here: the batch's positions are scattered by cursor.
+constexpr int HA_TILE = 2048;       // old index entries per block and round: 8 per thread
+constexpr int HA_LDS_USERS = 2048;  // users of a tile whose segment starts and shifts are staged in LDS (16 KiB)
+static_assert(HA_LDS_USERS >= HA_TILE, "a tile of one-event users must fit the staging");
+
+namespace {
+// the largest u in [lo, hi) with rp[u] <= key; rp[lo] <= key < rp[hi] on entry: the user whose segment holds entry `key`, empty users stepped over
+__device__ __forceinline__ int64_t ha_user_of(const int64_t* __restrict__ rp, int64_t lo, int64_t hi, int64_t key) {
+  while (hi - lo > 1) {
+    const int64_t mid = lo + ((hi - lo) >> 1);
+    if (rp[mid] <= key) lo = mid;
+    else hi = mid;
+  }
+  return lo;
+}
+}  // namespace
+
+// out_row_ptr[u] = old_row_ptr[min(u, n_users_old)] + add[u] for u = 0 .. n_users: users beyond the old id space start where the old index ends
+__global__ __launch_bounds__(256) void hs_append_row_ptr_kernel(int64_t n_users, int64_t n_users_old, const int64_t* __restrict__ old_row_ptr,
+                                                                const int64_t* __restrict__ add, int64_t* __restrict__ out_row_ptr) {
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u <= n_users; u += (int64_t)gridDim.x * 256)
+    out_row_ptr[u] = (n_users_old > 0 ? old_row_ptr[u < n_users_old ? u : n_users_old] : 0) + add[u];
+}
+
+// out_pos[e + add[u(e)]] = old_pos[e] for every old entry e.  The entries are old_row_ptr[n_users_old] of them (read here: the host knows only the bound
+// n_old, which sizes the grid and caps the count).  A row_ptr that does not ascend gives a wrong index, never a write outside out_pos: every e is below
+// n_old and every shift is an add[u] of a user 0 .. n_users_old.
+__global__ __launch_bounds__(256) void hs_append_copy_kernel(int64_t n_old, int64_t n_users_old, const int64_t* __restrict__ old_row_ptr,
+                                                             const int32_t* __restrict__ old_pos, const int64_t* __restrict__ add, int32_t* __restrict__ out_pos) {
+  __shared__ int s_start[HA_LDS_USERS];  // segment starts relative to the tile's first entry; [0] = 0: the first user's segment may begin before the tile
+  __shared__ int s_add[HA_LDS_USERS];
+  __shared__ int64_t s_u[2];
+  int64_t n_e = old_row_ptr[n_users_old];
+  if (n_e > n_old) n_e = n_old;
+  for (int64_t e0 = (int64_t)blockIdx.x * HA_TILE; e0 < n_e; e0 += (int64_t)gridDim.x * HA_TILE) {  // block-uniform
+    const int n = (int)(n_e - e0 < HA_TILE ? n_e - e0 : HA_TILE);
+    if (threadIdx.x < 2) s_u[threadIdx.x] = ha_user_of(old_row_ptr, 0, n_users_old, threadIdx.x == 0 ? e0 : e0 + n - 1);
+    __syncthreads();
+    const int64_t u_lo = s_u[0], u_hi = s_u[1];
+    const int64_t span = u_hi - u_lo + 1;
+    if (span >= 1 && span <= HA_LDS_USERS) {  // block-uniform
+      for (int i = threadIdx.x; i < (int)span; i += 256) {
+        const int64_t r = old_row_ptr[u_lo + i] - e0;
+        s_start[i] = r < 0 ? 0 : (int)r;
+        s_add[i] = (int)add[u_lo + i];
+      }
+      __syncthreads();
+      for (int k = threadIdx.x; k < n; k += 256) {
+        int lo = 0, hi = (int)span;
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (s_start[mid] <= k) lo = mid;
+          else hi = mid;
+        }
+        out_pos[e0 + k + s_add[lo]] = old_pos[e0 + k];
+      }
+    } else {
+      for (int k = threadIdx.x; k < n; k += 256) {
+        const int64_t u = ha_user_of(old_row_ptr, u_lo, u_hi + 1, e0 + k);
+        out_pos[e0 + k + add[u]] = old_pos[e0 + k];
+      }
+    }
+    __syncthreads();  // s_u and the staged slice are free for the next tile
+  }
+}
+
+// the batch's positions behind the old segments: hs_scatter_pos_kernel with the base old end of u + add[u]
+__global__ __launch_bounds__(256) void hs_append_scatter_kernel(int64_t n_old, int64_t n_new, const int32_t* __restrict__ new_users, int64_t n_users,
+                                                                int64_t n_users_old, const int64_t* __restrict__ old_row_ptr, const int64_t* __restrict__ add,
+                                                                int32_t* __restrict__ cursor, int32_t* __restrict__ out_pos) {
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n_new; p += (int64_t)gridDim.x * 256) {
+    const int u = new_users[p];
+    if (u >= 0 && u < n_users) {
+      const int64_t old_end = n_users_old > 0 ? old_row_ptr[u + 1 < n_users_old ? u + 1 : n_users_old] : 0;
+      out_pos[old_end + add[u] + atomicAdd(&cursor[u], 1)] = (int32_t)(n_old + p);
+    }
+  }
+}
+
+// cnt [n_users], add [n_users + 1], tile_sums: scratch.  out_* must not overlap old_*.
+hipError_t launch_history_append(hipStream_t st, int n_cu, int64_t n_old, int64_t n_users_old, const int64_t* old_row_ptr, const int32_t* old_pos, int64_t n_new,
+                                 const int32_t* new_users, int64_t n_users, int32_t* cnt, int64_t* add, int64_t* tile_sums, int64_t* out_row_ptr, int32_t* out_pos) {
+  if (n_users == 0) return hipMemsetAsync(out_row_ptr, 0, sizeof(int64_t), st);
+  hipError_t e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)n_users, st);
+  if (e != hipSuccess) return e;
+  if (n_new > 0) hipLaunchKernelGGL(hs_count_users_kernel, dim3(ig_grid(n_new, n_cu)), dim3(256), 0, st, n_new, new_users, n_users, cnt);
+  e = launch_scan_i32(st, cnt, n_users, add, tile_sums);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(hs_append_row_ptr_kernel, dim3(ig_grid(n_users + 1, n_cu)), dim3(256), 0, st, n_users, n_users_old, old_row_ptr, add, out_row_ptr);
+  if (n_users_old > 0 && n_old > 0) {
+    const int64_t tiles = (n_old + HA_TILE - 1) / HA_TILE, cap = (int64_t)n_cu * 8;
+    hipLaunchKernelGGL(hs_append_copy_kernel, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(256), 0, st, n_old, n_users_old, old_row_ptr, old_pos, add, out_pos);
+  }
+  if (n_new > 0) {
+    e = hipMemsetAsync(cnt, 0, sizeof(int32_t) * (size_t)n_users, st);  // now the scatter cursors
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(hs_append_scatter_kernel, dim3(ig_grid(n_new, n_cu)), dim3(256), 0, st, n_old, n_new, new_users, n_users, n_users_old, old_row_ptr, add, cnt, out_pos);
+  }
   return hipGetLastError();
 }
 

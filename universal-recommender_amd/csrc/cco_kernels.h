@@ -355,6 +355,9 @@ struct HistArgs {
 // cnt [n_users], tile_sums: scratch
 hipError_t launch_history_index(hipStream_t st, int n_cu, int64_t n, const int32_t* users, int64_t n_users, int32_t* cnt, int64_t* tile_sums, int64_t* out_row_ptr,
                                 int32_t* out_pos);
+// the index of the stream grown by n_new events (decision D21): cnt [n_users], add [n_users + 1], tile_sums: scratch; out_* must not overlap old_*
+hipError_t launch_history_append(hipStream_t st, int n_cu, int64_t n_old, int64_t n_users_old, const int64_t* old_row_ptr, const int32_t* old_pos, int64_t n_new,
+                                 const int32_t* new_users, int64_t n_users, int32_t* cnt, int64_t* add, int64_t* tile_sums, int64_t* out_row_ptr, int32_t* out_pos);
 // bnd [(n_types + 1) * n_queries]: scratch; only the inputs of `a` are read
 hipError_t launch_history_bounds(hipStream_t st, int n_cu, const HistArgs& a, int32_t* bnd, int64_t* tile_sums, int64_t* const* term_row_ptr, int64_t* excl_row_ptr);
 hipError_t launch_history_rows(hipStream_t st, int n_cu, const HistArgs& a, int64_t* tile_sums, int64_t* const* term_row_ptr, int32_t* const* term_col_idx,

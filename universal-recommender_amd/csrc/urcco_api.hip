@@ -755,6 +755,20 @@ int urcco_dev_history_index(urcco_session* s, int64_t n_events, const int32_t* u
   return URCCO_OK;
 }
 
+int urcco_dev_history_append(urcco_session* s, int64_t n_old, int64_t n_users_old, const int64_t* old_row_ptr, const int32_t* old_pos, int64_t n_new,
+                             const int32_t* new_users, int64_t n_users, int64_t* out_row_ptr, int32_t* out_pos) {
+  if (!s || n_old < 0 || n_new < 0 || n_users_old < 0 || n_old > 0x7fffffffll - n_new || n_users < n_users_old || n_users > 0x7ffffff0ll)
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_append: bad argument (a stream holds fewer than 2^31 events, the user id space does not shrink)");
+  const bool copies = n_users_old > 0 && n_old > 0;
+  if (!out_row_ptr || (n_users_old > 0 && !old_row_ptr) || (copies && !old_pos) || (n_new > 0 && !new_users) || ((copies || n_new > 0) && !out_pos))
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_append: NULL argument");
+  int32_t* cnt;
+  int64_t *add, *tile_sums;
+  URC(ArenaLayout(s).add(&cnt, (size_t)n_users).add(&add, (size_t)n_users + 1).add(&tile_sums, scan_tile_words(n_users)).commit());
+  HIPC(urcco::launch_history_append(s->stream, s->n_cu, n_old, n_users_old, old_row_ptr, old_pos, n_new, new_users, n_users, cnt, add, tile_sums, out_row_ptr, out_pos));
+  return URCCO_OK;
+}
+
 int urcco_dev_history_bounds(urcco_session* s, int64_t n_queries, const int32_t* q_users, int64_t n_users, urcco_hist_event* events, int32_t n_types,
                              const int64_t* extra_row_ptr, const int32_t* extra_col_idx, int64_t* excl_row_ptr) {
   urcco::HistArgs a;

@@ -314,6 +314,21 @@ class DeviceSession:
         self._check(self.lib.urcco_dev_history_index(self.handle, n, _ptr(users), n_users, _ptr(row_ptr), _ptr(pos)))
         return row_ptr, pos
 
+    def history_append(self, old_row_ptr: Optional[torch.Tensor], old_pos: Optional[torch.Tensor], n_old: int, new_users: torch.Tensor, n_users: int, out=None):
+        """urcco_dev_history_append: the index of a stream that grew by the events of `new_users` (int32 dense user id of the stream positions n_old,
+        n_old + 1, ...), from its old index (old_row_ptr int64 [n_users_old + 1], old_pos; both None: no old index) without the old stream's user ids.
+        n_users >= n_users_old.  Returns (row_ptr int64 [n_users + 1], pos int32 [n_old + n_new]): per user the old segment as it was, then the new
+        positions in unspecified order.  out: (row_ptr, pos) tensors of at least those sizes to write into -- they must not share memory with the old
+        index; the returned tensors are views of them.  Does not synchronise."""
+        n_old, n_new, n_users = int(n_old), int(new_users.numel()), int(n_users)
+        n_users_old = int(old_row_ptr.numel()) - 1 if old_row_ptr is not None else 0
+        row_ptr, pos = out if out is not None else (self.empty(n_users + 1, torch.int64), self.empty(max(n_old + n_new, 1), torch.int32))
+        if row_ptr.numel() < n_users + 1 or pos.numel() < n_old + n_new:
+            raise ValueError("history_append: the output tensors are smaller than n_users + 1 / n_old + n_new")
+        self._check(self.lib.urcco_dev_history_append(self.handle, n_old, n_users_old, _ptr(old_row_ptr), _ptr(old_pos), n_new, _ptr(new_users), n_users,
+                                                      _ptr(row_ptr), _ptr(pos)))
+        return (row_ptr, pos) if out is None else (row_ptr[: n_users + 1], pos[: n_old + n_new])
+
     def history_rows(self, q_users: torch.Tensor, n_users: int, events, n_items: int, extra=None, stats: bool = False, timing: bool = False, keep_bounds: bool = False):
         """urcco_dev_history_bounds + urcco_dev_history_rows: the user-history term rows and the exclusion rows of a batch of queries.
         q_users: int32 [n_queries] dense user ids (< 0 or >= n_users: unknown).  events: per event type (n_cols, max_items, blacklist, idx_row_ptr, idx_pos,

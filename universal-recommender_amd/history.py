@@ -33,14 +33,25 @@ class _Stream:
     items: torch.Tensor                # int32 [n_events]: column id of the event type (primary item id for an event outside the model), < 0 = none
     times: Optional[torch.Tensor]      # int64 [n_events] epoch milliseconds; None: stream order is time order
     col_map: Optional[torch.Tensor]    # int32 [n_cols] -> primary item id or -1; None: identity
+    n_events: int = -1                 # events of the stream; -1: not stated (an empty stream holds one placeholder entry, so items.numel() does not say) -- append refuses
+    # DeviceHistory.append: the tensors above are exact-length views of these buffers (None: the tensor is its own buffer, no spare capacity)
+    items_buf: Optional[torch.Tensor] = None
+    times_buf: Optional[torch.Tensor] = None
+    idx_buf: Optional[Tuple[torch.Tensor, torch.Tensor]] = None     # (row_ptr, pos) the index lives in
+    idx_spare: Optional[Tuple[torch.Tensor, torch.Tensor]] = None   # the pair the next merge writes into: the index of before the last append
+
+
+GROWTH = 2     # DeviceHistory.append: a buffer that is too small is replaced by one of max(needed, GROWTH * its capacity) entries
 
 
 class DeviceHistory:
     """Event streams by user in HBM.  `types[event name]` = the stream of that event type; an event name outside the model may be present
-    (it can only feed exclusions: blacklistEvents), its column ids are then the primary's item ids."""
+    (it can only feed exclusions: blacklistEvents), its column ids are then the primary's item ids.  A history built by from_streams / from_dict keeps a
+    reference to the model (`model`): `append` takes the columns of an event name it does not hold yet from it."""
 
-    def __init__(self, sess: DeviceSession, n_users: int, user_ids, types: Dict[str, _Stream]):
+    def __init__(self, sess: DeviceSession, n_users: int, user_ids, types: Dict[str, _Stream], model=None):
         self.sess, self.n_users, self.user_ids, self.types = sess, int(n_users), user_ids, types
+        self.model = model     # the model the column maps came from: `append` needs it for an event name the history does not hold yet
 
     def user_index(self, user) -> int:
         """Dense id of a query's user, -1 when the history does not know it."""
@@ -79,20 +90,115 @@ class DeviceHistory:
             n_users = len(user_ids) if user_ids is not None else max([int(u.max().item()) + 1 for u, _, _ in streams.values() if u.numel()] + [0])
         types = {}
         for ev, (users, items, times) in streams.items():
-            if users.dtype != torch.int32 or items.dtype != torch.int32 or users.numel() != items.numel():
-                raise ValueError(f"stream {ev!r}: int32 user ids and item ids of one length expected")
-            if times is not None and (times.dtype != torch.int64 or times.numel() != users.numel()):
-                raise ValueError(f"stream {ev!r}: int64 times, one per event, expected")
+            DeviceHistory._check_stream(ev, users, items, times)
             n_cols, col_map = DeviceHistory._col_map(sess, model, ev)
             rp, pos = sess.history_index(users, n_users)
-            types[ev] = _Stream(n_cols, rp, pos, items if items.numel() else sess.empty(1, torch.int32), times, col_map)
-        return DeviceHistory(sess, n_users, user_ids, types)
+            types[ev] = _Stream(n_cols, rp, pos, items if items.numel() else sess.empty(1, torch.int32), times, col_map, n_events=int(items.numel()))
+        return DeviceHistory(sess, n_users, user_ids, types, model)
+
+    @staticmethod
+    def _check_stream(ev: str, users: torch.Tensor, items: torch.Tensor, times: Optional[torch.Tensor]):
+        if users.dtype != torch.int32 or items.dtype != torch.int32 or users.numel() != items.numel():
+            raise ValueError(f"stream {ev!r}: int32 user ids and item ids of one length expected")
+        if times is not None and (times.dtype != torch.int64 or times.numel() != users.numel()):
+            raise ValueError(f"stream {ev!r}: int64 times, one per event, expected")
+
+    def _grown(self, buf: Optional[torch.Tensor], live: Optional[torch.Tensor], n_live: int, need: int, dtype) -> torch.Tensor:
+        """A buffer of at least `need` entries whose first n_live are those of `live`: `buf` when it is large enough, else a new one, GROWTH times larger."""
+        if buf is None:
+            buf = live
+        if buf is not None and buf.numel() >= need:
+            return buf
+        new = self.sess.empty(max(need, GROWTH * (buf.numel() if buf is not None else 0), 1), dtype)
+        if n_live:
+            new[:n_live].copy_(live[:n_live])
+        return new
+
+    def append(self, streams: Dict[str, Tuple[torch.Tensor, torch.Tensor, Optional[torch.Tensor]]], user_ids=None, n_users: Optional[int] = None,
+               model=None) -> "DeviceHistory":
+        """New events behind the streams, in place (decision D21 of DESIGN.md; include/urcco.h urcco_dev_history_append); returns self.  streams: as
+        from_streams takes them, the event types with new events only; per type the items (and the times, iff the stream has times) are appended to
+        the stream and the index is replaced by the merge of the old index with the batch -- no index rebuild, and the user ids of the events
+        already held are not needed.  Every result afterwards is the one of from_streams over the concatenated streams with the final n_users.
+
+        n_users may grow, never shrink: default len(user_ids) when a new `user_ids` is given (it replaces the old one), else the larger of the old
+        size and the batch's largest id + 1 (one synchronisation, as in from_streams).  When it grows, the event types without new events get their
+        index extended; a type for which nothing changes costs no call.  An event name the history does not hold yet is added as from_streams adds
+        it (model: default the one the history was built from).
+
+        Memory: the stream tensors and the index live in buffers with spare capacity; one that is too small is replaced by one GROWTH (2) times
+        larger, so the cost of an append is the merge (one copy of the old index plus the batch), not a reallocation of the streams.  _Stream.items
+        / .times / .idx_* stay exact-length views.  The merge cannot run in place: every event type that was appended to keeps a second index
+        buffer, the one the next merge writes into.
+
+        ValueError -- nothing is modified before all streams passed: dtypes or lengths as in from_streams; times given for a stream that has none or
+        missing for one that has them; a shrinking n_users; a new event name without a model; a _Stream built by hand without n_events."""
+        model = model if model is not None else self.model
+        new_cols = {}      # the columns of the event names the history does not hold yet, resolved before anything is modified
+        for ev, (users, items, times) in streams.items():
+            self._check_stream(ev, users, items, times)
+            st = self.types.get(ev)
+            if st is None:
+                if model is None:
+                    raise ValueError(f"stream {ev!r}: the history does not hold this event type and was built without a model to take its columns from")
+                new_cols[ev] = self._col_map(self.sess, model, ev)
+            elif (times is None) != (st.times is None):
+                raise ValueError(f"stream {ev!r}: the stream {'has no times' if st.times is None else 'has times'}, the batch must agree")
+        if n_users is None:
+            n_users = len(user_ids) if user_ids is not None else max([int(u.max().item()) + 1 for u, _, _ in streams.values() if u.numel()] + [self.n_users])
+        n_users = int(n_users)
+        if n_users < self.n_users:
+            raise ValueError(f"n_users {n_users} is below the history's {self.n_users}: the user id space does not shrink")
+        for ev, st in self.types.items():      # a stream of unknown length (a _Stream built without n_events) cannot be appended to or extended
+            if st.n_events < 0 and (n_users != self.n_users or (ev in streams and streams[ev][0].numel())):
+                raise ValueError(f"stream {ev!r}: built without its number of events (_Stream.n_events)")
+        sess = self.sess
+        for ev in list(self.types) + [ev for ev in streams if ev not in self.types]:
+            st = self.types.get(ev)
+            users, items, times = streams.get(ev, (None, None, None))
+            n_new = int(users.numel()) if users is not None else 0
+            if st is None:
+                n_cols, col_map = new_cols[ev]
+                st = self.types[ev] = _Stream(n_cols, None, None, None, None, col_map, n_events=0)
+                have_times = times is not None
+            else:
+                have_times = st.times is not None
+                if n_new == 0 and n_users == self.n_users:
+                    continue
+            n_old = st.n_events
+            n = n_old + n_new
+            if n_new or st.items is None:
+                st.items_buf = self._grown(st.items_buf, st.items, n_old, n, torch.int32)
+                st.items_buf[n_old:n].copy_(items)
+                st.items = st.items_buf[:n] if n else st.items_buf[:1]      # an empty stream still has an array
+                if have_times:
+                    st.times_buf = self._grown(st.times_buf, st.times, n_old, n, torch.int64)
+                    st.times_buf[n_old:n].copy_(times)
+                    st.times = st.times_buf[:n] if n else st.times_buf[:1]
+            out = st.idx_spare
+            if out is None or out[0].numel() < n_users + 1 or out[1].numel() < n:
+                live = st.idx_buf if st.idx_buf is not None else (st.idx_row_ptr, st.idx_pos)
+                caps = [t.numel() if t is not None else 0 for t in live]      # the size of the live pair where that suffices, GROWTH times it where not
+                caps = [c if c >= need else max(need, GROWTH * c, 1) for c, need in zip(caps, (n_users + 1, n))]
+                out = (sess.empty(caps[0], torch.int64), sess.empty(caps[1], torch.int32))
+            rp, pos = sess.history_append(st.idx_row_ptr, st.idx_pos, n_old, users if users is not None else sess.empty(0, torch.int32), n_users, out)
+            st.idx_spare = st.idx_buf if st.idx_buf is not None else ((st.idx_row_ptr, st.idx_pos) if st.idx_row_ptr is not None else None)
+            st.idx_buf, st.idx_row_ptr, st.idx_pos, st.n_events = out, rp, pos if n else out[1][:1], n
+        self.n_users = n_users
+        if user_ids is not None:
+            self.user_ids = user_ids
+        return self
 
     @staticmethod
     def from_dict(sess: DeviceSession, model, history: Dict[str, Dict[str, List[str]]]) -> "DeviceHistory":
         """The dict form of batch_predict's `history` (user -> {event name: [item ids, oldest first]}) loaded onto the device: every user gets a
         dense id, the list order is the time order, an item outside the event's column dictionary gets the id -1."""
         user_ids = {u: i for i, u in enumerate(history)}
+        return DeviceHistory.from_streams(sess, model, DeviceHistory._dict_streams(sess, model, history, user_ids), user_ids)
+
+    @staticmethod
+    def _dict_streams(sess: DeviceSession, model, history: Dict[str, Dict[str, List[str]]], user_ids: Dict) -> Dict[str, Tuple[torch.Tensor, torch.Tensor, None]]:
+        """The streams of the dict form: per event name the users' lists one after the other, each in its own order; no times"""
         names: List[str] = []
         for events in history.values():
             names += [ev for ev in events if ev not in names]
@@ -106,4 +212,14 @@ class DeviceHistory:
                 items += [-1 if i is None else i for i in ids]
                 users += [user_ids[u]] * len(ids)
             streams[ev] = (torch.tensor(users, dtype=torch.int32).to(sess.device), torch.tensor(items, dtype=torch.int32).to(sess.device), None)
-        return DeviceHistory.from_streams(sess, model, streams, user_ids)
+        return streams
+
+    def append_dict(self, model, history: Dict[str, Dict[str, List[str]]]) -> "DeviceHistory":
+        """`append` for the dict form of from_dict (user -> {event name: [item ids, oldest first]}): the lists are appended in order behind what the
+        history holds of the user, a user it has not seen gets the next id.  Only for a history whose user_ids is a dict (from_dict's)."""
+        if not isinstance(self.user_ids, dict):
+            raise ValueError("append_dict needs a history whose user_ids is a dict (DeviceHistory.from_dict)")
+        user_ids = dict(self.user_ids)
+        for u in history:
+            user_ids.setdefault(u, len(user_ids))
+        return self.append(self._dict_streams(self.sess, model, history, user_ids), user_ids, model=model)
