@@ -614,6 +614,27 @@ int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double
  *   stream is needed).  n_new == 0 with n_users > n_users_old extends the id space only; n_old == 0, n_users_old == 0 with NULL old arrays is _index of
  *   the batch.  old_row_ptr is needed when n_users_old > 0, old_pos when also n_old > 0, new_users when n_new > 0, out_pos when anything is written.
  *   URCCO_BAD_ARG: n_old + n_new >= 2^31, n_users < n_users_old, a negative count, a NULL the call needs.
+ * urcco_dev_history_trim (DESIGN.md decision D22): a stream and its index without the events older than a cut-off and without the events of listed users,
+ *   from the stream and the index alone.
+ *   dropped by time   the event at stream position p when times_ms != NULL and times_ms[p] < min_time_ms: a signed compare, equality keeps the event,
+ *                     INT64_MIN keeps everything; min_time_ms is read only when times_ms != NULL
+ *   dropped by user   an event that an index entry of a user listed in drop_users names.  The ids may come in any order and may repeat; an id < 0 or
+ *                     >= n_users is ignored
+ *   nobody's events   a position that no index entry names is kept or dropped by the time rule alone: nothing reads it, and no `users` array exists to
+ *                     decide otherwise
+ *   stream output     K = the number of kept events, new_of[p] = the number of kept positions below p: out_items[0 .. K) and out_times[0 .. K) are the
+ *                     kept events in stream order
+ *   index output      KE = the number of kept index entries among the n_e = min(idx_row_ptr[n_users], n_events) entries (n_e is read on the device):
+ *                     out_pos[0 .. KE) are the kept entries in their old order, each renumbered to new_of[idx_pos[e]]; out_row_ptr[u] = the number of
+ *                     kept entries below idx_row_ptr[u].  So every user's segment is its old segment with the dropped entries removed and the order
+ *                     kept; the id space does not change, a dropped user keeps its id and has an empty segment
+ *   counts            out_counts[0] = K, out_counts[1] = KE
+ *   capacities        nothing is written at or past out_items[K], out_times[K], out_pos[KE] or out_row_ptr[n_users + 1]; a caller that does not know K
+ *                     sizes the three arrays by n_events.  out_* must not overlap the inputs: the compaction is not in place
+ *   malformed index   entries of idx_pos outside 0 .. n_events count as dropped, row starts are clamped into 0 .. n_e; whatever idx_row_ptr and idx_pos
+ *                     hold, the result may be wrong, but no access leaves the arrays
+ *   URCCO_BAD_ARG: n_events >= 2^31, a negative count, n_users > 0x7ffffff0, a NULL the call needs, out_times and times_ms not NULL together.  Needed:
+ *   items, idx_pos, out_items and out_pos only when n_events > 0; idx_row_ptr when n_users > 0; drop_users when n_drop > 0; out_row_ptr and out_counts always.
  * urcco_dev_history_bounds: term_row_ptr of every type and excl_row_ptr receive the exclusive scans of upper bounds of the rows' lengths (min(n_u, max_items);
  *   blacklist events + extra row).  The caller reads the 1 + n_types totals (term_row_ptr[n_queries], excl_row_ptr[n_queries]: its one synchronisation),
  *   allocates term_col_idx / excl_col_idx of at least that many entries and states the sizes in term_capacity / excl_capacity.
@@ -624,7 +645,7 @@ int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double
  * stats_dev (nullable, int64[URCCO_HIST_STATS_LEN]): (query, type) pairs served by [0] the wave class (<= 64 events), [1] the block class (<= 4096, keys in
  *   LDS), [2] the global class; [3] pairs that ran the select (n_u > max_items); exclusion rows built by [4] one wave, [5] one block; [6] rows dropped
  *   for lack of capacity (0 when the caller sized its buffers by the bounds); [7] 0.
- * All four enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: n_events >= 2^31, n_types outside
+ * All five enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: n_events >= 2^31, n_types outside
  * 1..URCCO_REC_MAX_CLAUSES, max_items < 1, n_queries * (n_types + 1) >= 2^31, a NULL the call needs, a half-NULL extra pair, a negative capacity.
  * ABI: additions within ABI 305 -- the presence of the symbols is the feature test. */
 #define URCCO_HIST_STATS_LEN 8
@@ -636,6 +657,14 @@ int urcco_dev_history_append(urcco_session* s,
                              int64_t n_new, const int32_t* new_users,        /* users of stream positions n_old .. n_old + n_new */
                              int64_t n_users,                                /* >= n_users_old: the id space after the append */
                              int64_t* out_row_ptr /* [n_users + 1] */, int32_t* out_pos /* capacity n_old + n_new */);
+int urcco_dev_history_trim(urcco_session* s,
+                           int64_t n_events, const int32_t* items, const int64_t* times_ms /* nullable */,
+                           int64_t n_users, const int64_t* idx_row_ptr /* [n_users + 1] */, const int32_t* idx_pos,
+                           int64_t min_time_ms,                          /* read only when times_ms != NULL */
+                           int64_t n_drop, const int32_t* drop_users,    /* device; nullable iff n_drop == 0 */
+                           int32_t* out_items, int64_t* out_times /* NULL iff times_ms NULL */,
+                           int64_t* out_row_ptr /* [n_users + 1] */, int32_t* out_pos,
+                           int64_t* out_counts /* device [2] */);
 
 typedef struct urcco_hist_event {
   int32_t n_cols, max_items;          /* max_items >= 1 */

@@ -5,6 +5,7 @@
 // maxItemsPerUser events per event type, then distinct; getExcludedItems, :741-767: every item of the blacklist events) is here
 //   index   stream positions by user: count per user -> scan -> scatter by cursor (order inside a user's segment unspecified)
 //   append  the index of the stream grown by a batch: old segments copied at their shifts, the batch scattered behind them (D21)
+//   trim    the stream and the index without the events before a cut-off and those of listed users: "kept" bitmaps, popcount scans, ranks (D22)
 //   bounds  per (query, type) min(n_u, max_items), per query the blacklist events + the extra exclusion row: scans = raw row starts
 //   rows    per (query, type): the window = the min(n_u, max_items) largest keys (time, position) of the user's events -- found by an
 //           8-bit radix SELECT over the 96-bit keys when n_u > max_items, never by sorting the events -- then sort + unique of the
@@ -174,6 +175,167 @@ hipError_t launch_history_append(hipStream_t st, int n_cu, int64_t n_old, int64_
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(hs_append_scatter_kernel, dim3(ig_grid(n_new, n_cu)), dim3(256), 0, st, n_old, n_new, new_users, n_users, n_users_old, old_row_ptr, add, cnt, out_pos);
   }
+  return hipGetLastError();
+}
+
+// ---- trim (decision D22) -------------------------------------------------------------------------------------------
+// A stream and its index without the events older than a cut-off and without the events of listed users, from the stream and the index alone.
+// Stream rule: dropping events keeps the survivors' order, so new_of[p] = the kept positions below p renumbers them and the recency key orders them
+// as before.  Index rule: a user's segment is contiguous, so the exclusive scan of "entry kept" over the index entries is the new place of every
+// entry AND the new start of every user: out_row_ptr[u] = rank(idx_row_ptr[u]).  No `users` array, no per-user atomic, no per-user launch.
+//   mark     D: one bit per stream position, zeroed; the segments of the listed users set the bits of their positions (atomicOr: the only atomics,
+//            proportional to the dropped users' entries; duplicates in the list set the same bits again)
+//   keep     S = time test passed and D clear, in place over D: one wave per word of 64 positions, the word is the wave's ballot, its popcount the count
+//   entries  I[e] = S bit of idx_pos[e] for the n_e = min(idx_row_ptr[n_users], n_events) entries (read here, as the append's copy kernel reads it)
+//   scans    launch_scan_i32 over the words' popcounts: word bases, the total behind the last word
+//   rank(x)  base[x >> 6] + popcount(word[x >> 6] below bit x & 63); x & 63 == 0 reads no word: x may be the array's length on a word boundary
+//   compact  kept position p -> out_items / out_times[rankS(p)]; kept entry e -> out_pos[rankI(e)] = rankS(idx_pos[e]); out_row_ptr[u] = rankI(start of u)
+// The mark is balanced by ENTRIES as far as one list entry goes: a listed user's segment is cut into chunks of HT_CHUNK entries that HT_SPLIT blocks
+// take in turn, so a user of 10^6 entries is 489 chunks over 32 blocks, about 128 atomics per thread; a user of up to HT_CHUNK entries costs one block
+// one round and 31 blocks two loads of row starts each.  Entries of idx_pos outside 0 .. n_events count as dropped, row starts are clamped into
+// 0 .. n_e: whatever the index holds, no access leaves the arrays.
+constexpr int HT_CHUNK = 2048;  // index entries of a listed user per block and round: 8 per thread
+constexpr int HT_SPLIT = 32;    // blocks that share one listed user's chunks
+
+namespace {
+// the entries of the index: what idx_row_ptr[n_users] says, at most n_events, never negative
+__device__ __forceinline__ int64_t ht_entries(const int64_t* __restrict__ idx_row_ptr, int64_t n_users, int64_t n_events) {
+  const int64_t n_e = n_users > 0 ? idx_row_ptr[n_users] : 0;
+  return n_e < 0 ? 0 : n_e < n_events ? n_e : n_events;
+}
+__device__ __forceinline__ int64_t ht_clamp(int64_t x, int64_t hi) { return x < 0 ? 0 : x < hi ? x : hi; }
+// set bits of `words` below x; x in 0 .. 64 * (number of words), base holds one more entry than there are words
+__device__ __forceinline__ int64_t ht_rank(const int64_t* __restrict__ base, const unsigned long long* __restrict__ words, int64_t x) {
+  const int b = (int)(x & 63);
+  return base[x >> 6] + (b ? __popcll(words[x >> 6] & ((1ull << b) - 1ull)) : 0);
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void ht_mark_kernel(int64_t n_events, int64_t n_users, const int64_t* __restrict__ idx_row_ptr, const int32_t* __restrict__ idx_pos,
+                                                      int64_t n_drop, const int32_t* __restrict__ drop_users, unsigned long long* __restrict__ bits) {
+  const int64_t n_e = ht_entries(idx_row_ptr, n_users, n_events);
+  for (int64_t j = blockIdx.x; j < n_drop * HT_SPLIT; j += gridDim.x) {  // block-uniform
+    const int u = drop_users[j / HT_SPLIT];
+    if (u < 0 || u >= n_users) continue;
+    const int64_t lo = ht_clamp(idx_row_ptr[u], n_e), hi = ht_clamp(idx_row_ptr[u + 1], n_e);
+    for (int64_t c = lo + (j % HT_SPLIT) * HT_CHUNK; c < hi; c += (int64_t)HT_SPLIT * HT_CHUNK) {
+      const int64_t end = c + HT_CHUNK < hi ? c + HT_CHUNK : hi;
+      for (int64_t e = c + threadIdx.x; e < end; e += 256) {
+        const int p = idx_pos[e];
+        if (p >= 0 && p < n_events) atomicOr(&bits[p >> 6], 1ull << (p & 63));
+      }
+    }
+  }
+}
+
+// bits: D on entry when has_drop (else not read), S on return; cnt[w] = popcount of word w.  Bits at and beyond n_events are 0.
+__global__ __launch_bounds__(256) void ht_keep_kernel(int64_t n_events, const int64_t* __restrict__ times_ms, int64_t min_time_ms, bool has_drop,
+                                                      unsigned long long* bits, int32_t* __restrict__ cnt) {
+  const int lane = threadIdx.x & (SR_WAVE - 1);
+  const int64_t n_words = (n_events + 63) >> 6, n_waves = (int64_t)gridDim.x * (256 / SR_WAVE);
+  for (int64_t w = (int64_t)blockIdx.x * (256 / SR_WAVE) + threadIdx.x / SR_WAVE; w < n_words; w += n_waves) {  // wave-uniform
+    const int64_t p = (w << 6) + lane;
+    const unsigned long long d = has_drop ? bits[w] : 0ull;
+    bool keep = p < n_events && !((d >> lane) & 1ull);
+    if (keep && times_ms) keep = times_ms[p] >= min_time_ms;
+    const unsigned long long word = __ballot(keep);
+    if (lane == 0) {
+      bits[w] = word;
+      cnt[w] = __popcll(word);
+    }
+  }
+}
+
+// I[e] = S bit of idx_pos[e]; words and counts for all ceil(n_events / 64) words, zero at and beyond n_e
+__global__ __launch_bounds__(256) void ht_entries_kernel(int64_t n_events, int64_t n_users, const int64_t* __restrict__ idx_row_ptr, const int32_t* __restrict__ idx_pos,
+                                                         const unsigned long long* __restrict__ s_bits, unsigned long long* __restrict__ i_bits,
+                                                         int32_t* __restrict__ cnt) {
+  const int lane = threadIdx.x & (SR_WAVE - 1);
+  const int64_t n_e = ht_entries(idx_row_ptr, n_users, n_events);
+  const int64_t n_words = (n_events + 63) >> 6, n_waves = (int64_t)gridDim.x * (256 / SR_WAVE);
+  for (int64_t w = (int64_t)blockIdx.x * (256 / SR_WAVE) + threadIdx.x / SR_WAVE; w < n_words; w += n_waves) {  // wave-uniform
+    const int64_t e = (w << 6) + lane;
+    bool keep = false;
+    if (e < n_e) {
+      const int p = idx_pos[e];
+      if (p >= 0 && p < n_events) keep = (s_bits[p >> 6] >> (p & 63)) & 1ull;
+    }
+    const unsigned long long word = __ballot(keep);
+    if (lane == 0) {
+      i_bits[w] = word;
+      cnt[w] = __popcll(word);
+    }
+  }
+}
+
+// kept position p -> slot rankS(p): the kept positions of a wave's 64 fill one contiguous run
+__global__ __launch_bounds__(256) void ht_compact_stream_kernel(int64_t n_events, const int32_t* __restrict__ items, const int64_t* __restrict__ times_ms,
+                                                                const unsigned long long* __restrict__ s_bits, const int64_t* __restrict__ s_base,
+                                                                int32_t* __restrict__ out_items, int64_t* __restrict__ out_times) {
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < n_events; p += (int64_t)gridDim.x * 256) {
+    const unsigned long long word = s_bits[p >> 6];
+    const int b = (int)(p & 63);
+    if (!((word >> b) & 1ull)) continue;
+    const int64_t dst = s_base[p >> 6] + __popcll(word & ((1ull << b) - 1ull));
+    out_items[dst] = items[p];
+    if (times_ms) out_times[dst] = times_ms[p];
+  }
+}
+
+__global__ __launch_bounds__(256) void ht_compact_index_kernel(int64_t n_events, int64_t n_users, const int64_t* __restrict__ idx_row_ptr, const int32_t* __restrict__ idx_pos,
+                                                               const unsigned long long* __restrict__ s_bits, const int64_t* __restrict__ s_base,
+                                                               const unsigned long long* __restrict__ i_bits, const int64_t* __restrict__ i_base,
+                                                               int32_t* __restrict__ out_pos) {
+  const int64_t n_e = ht_entries(idx_row_ptr, n_users, n_events);
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n_e; e += (int64_t)gridDim.x * 256) {
+    const unsigned long long word = i_bits[e >> 6];
+    const int b = (int)(e & 63);
+    if (!((word >> b) & 1ull)) continue;  // a kept entry names a position inside the stream: ht_entries_kernel tested it
+    out_pos[i_base[e >> 6] + __popcll(word & ((1ull << b) - 1ull))] = (int32_t)ht_rank(s_base, s_bits, idx_pos[e]);
+  }
+}
+
+// out_row_ptr[u] = rankI(start of u) for u = 0 .. n_users; the first thread writes the counts: the totals behind the last words
+__global__ __launch_bounds__(256) void ht_row_ptr_kernel(int64_t n_events, int64_t n_users, const int64_t* __restrict__ idx_row_ptr,
+                                                         const unsigned long long* __restrict__ i_bits, const int64_t* __restrict__ s_base,
+                                                         const int64_t* __restrict__ i_base, int64_t* __restrict__ out_row_ptr, int64_t* __restrict__ out_counts) {
+  const int64_t n_e = ht_entries(idx_row_ptr, n_users, n_events);
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u <= n_users; u += (int64_t)gridDim.x * 256)
+    out_row_ptr[u] = ht_rank(i_base, i_bits, n_users > 0 ? ht_clamp(idx_row_ptr[u], n_e) : 0);
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    const int64_t n_words = (n_events + 63) >> 6;
+    out_counts[0] = s_base[n_words];
+    out_counts[1] = i_base[n_words];
+  }
+}
+
+// a.s_bits, i_bits, s_cnt, i_cnt [ceil(n_events / 64)], s_base, i_base [that + 1], tile_sums: scratch.  out_* must not overlap the inputs.
+hipError_t launch_history_trim(hipStream_t st, int n_cu, const TrimArgs& a) {
+  const int64_t n = a.n_events, n_words = (n + 63) >> 6;
+  hipError_t e;
+  if (n > 0) {
+    const bool has_drop = a.n_drop > 0 && a.n_users > 0;
+    if (has_drop) {
+      e = hipMemsetAsync(a.s_bits, 0, sizeof(unsigned long long) * (size_t)n_words, st);
+      if (e != hipSuccess) return e;
+      const int64_t jobs = a.n_drop * HT_SPLIT, cap = (int64_t)n_cu * 8;
+      hipLaunchKernelGGL(ht_mark_kernel, dim3((unsigned)(jobs < cap ? jobs : cap)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.idx_pos, a.n_drop, a.drop_users,
+                         a.s_bits);
+    }
+    hipLaunchKernelGGL(ht_keep_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, a.times_ms, a.min_time_ms, has_drop, a.s_bits, a.s_cnt);
+    hipLaunchKernelGGL(ht_entries_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.idx_pos, a.s_bits, a.i_bits, a.i_cnt);
+  }
+  e = launch_scan_i32(st, a.s_cnt, n_words, a.s_base, a.tile_sums);
+  if (e != hipSuccess) return e;
+  e = launch_scan_i32(st, a.i_cnt, n_words, a.i_base, a.tile_sums);
+  if (e != hipSuccess) return e;
+  if (n > 0) {
+    hipLaunchKernelGGL(ht_compact_stream_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, a.items, a.times_ms, a.s_bits, a.s_base, a.out_items, a.out_times);
+    hipLaunchKernelGGL(ht_compact_index_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.idx_pos, a.s_bits, a.s_base, a.i_bits, a.i_base,
+                       a.out_pos);
+  }
+  hipLaunchKernelGGL(ht_row_ptr_kernel, dim3(ig_grid(a.n_users + 1, n_cu)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.i_bits, a.s_base, a.i_base, a.out_row_ptr,
+                     a.out_counts);
   return hipGetLastError();
 }
 

@@ -358,6 +358,25 @@ hipError_t launch_history_index(hipStream_t st, int n_cu, int64_t n, const int32
 // the index of the stream grown by n_new events (decision D21): cnt [n_users], add [n_users + 1], tile_sums: scratch; out_* must not overlap old_*
 hipError_t launch_history_append(hipStream_t st, int n_cu, int64_t n_old, int64_t n_users_old, const int64_t* old_row_ptr, const int32_t* old_pos, int64_t n_new,
                                  const int32_t* new_users, int64_t n_users, int32_t* cnt, int64_t* add, int64_t* tile_sums, int64_t* out_row_ptr, int32_t* out_pos);
+// a stream and its index without the events before min_time_ms and those of drop_users (decision D22; include/urcco.h urcco_dev_history_trim)
+struct TrimArgs {
+  int64_t n_events, n_users, n_drop, min_time_ms;
+  const int32_t* items;
+  const int64_t* times_ms;       // nullable: no time rule
+  const int64_t* idx_row_ptr;    // [n_users + 1]
+  const int32_t* idx_pos;
+  const int32_t* drop_users;     // [n_drop]
+  int32_t* out_items;
+  int64_t* out_times;            // NULL iff times_ms is
+  int64_t* out_row_ptr;          // [n_users + 1]
+  int32_t* out_pos;
+  int64_t* out_counts;           // [2]: kept events, kept index entries
+  unsigned long long *s_bits, *i_bits;  // scratch [ceil(n_events / 64)]: one bit per stream position / per index entry
+  int32_t *s_cnt, *i_cnt;               // scratch [ceil(n_events / 64)]: the words' popcounts
+  int64_t *s_base, *i_base;             // scratch [ceil(n_events / 64) + 1]: their exclusive scans
+  int64_t* tile_sums;                   // scratch: scan_tile_words(ceil(n_events / 64))
+};
+hipError_t launch_history_trim(hipStream_t st, int n_cu, const TrimArgs& a);
 // bnd [(n_types + 1) * n_queries]: scratch; only the inputs of `a` are read
 hipError_t launch_history_bounds(hipStream_t st, int n_cu, const HistArgs& a, int32_t* bnd, int64_t* tile_sums, int64_t* const* term_row_ptr, int64_t* excl_row_ptr);
 hipError_t launch_history_rows(hipStream_t st, int n_cu, const HistArgs& a, int64_t* tile_sums, int64_t* const* term_row_ptr, int32_t* const* term_col_idx,

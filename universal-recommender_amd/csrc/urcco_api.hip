@@ -769,6 +769,25 @@ int urcco_dev_history_append(urcco_session* s, int64_t n_old, int64_t n_users_ol
   return URCCO_OK;
 }
 
+int urcco_dev_history_trim(urcco_session* s, int64_t n_events, const int32_t* items, const int64_t* times_ms, int64_t n_users, const int64_t* idx_row_ptr,
+                           const int32_t* idx_pos, int64_t min_time_ms, int64_t n_drop, const int32_t* drop_users, int32_t* out_items, int64_t* out_times,
+                           int64_t* out_row_ptr, int32_t* out_pos, int64_t* out_counts) {
+  if (!s || n_events < 0 || n_events > 0x7fffffffll || n_users < 0 || n_users > 0x7ffffff0ll || n_drop < 0)
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_trim: bad argument (a stream holds fewer than 2^31 events)");
+  if (!out_row_ptr || !out_counts || (n_events > 0 && (!items || !idx_pos || !out_items || !out_pos)) || (n_users > 0 && !idx_row_ptr) || (n_drop > 0 && !drop_users))
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_trim: NULL argument");
+  if ((times_ms == nullptr) != (out_times == nullptr)) return fail(URCCO_BAD_ARG, "urcco_dev_history_trim: times_ms and out_times are both NULL or both given");
+  urcco::TrimArgs a{};
+  a.n_events = n_events; a.n_users = n_users; a.n_drop = n_drop; a.min_time_ms = min_time_ms;
+  a.items = items; a.times_ms = times_ms; a.idx_row_ptr = idx_row_ptr; a.idx_pos = idx_pos; a.drop_users = drop_users;
+  a.out_items = out_items; a.out_times = out_times; a.out_row_ptr = out_row_ptr; a.out_pos = out_pos; a.out_counts = out_counts;
+  const size_t n_words = (size_t)((n_events + 63) >> 6);
+  URC(ArenaLayout(s).add(&a.s_bits, n_words).add(&a.i_bits, n_words).add(&a.s_cnt, n_words).add(&a.i_cnt, n_words).add(&a.s_base, n_words + 1).add(&a.i_base, n_words + 1)
+          .add(&a.tile_sums, scan_tile_words((int64_t)n_words)).commit());
+  HIPC(urcco::launch_history_trim(s->stream, s->n_cu, a));
+  return URCCO_OK;
+}
+
 int urcco_dev_history_bounds(urcco_session* s, int64_t n_queries, const int32_t* q_users, int64_t n_users, urcco_hist_event* events, int32_t n_types,
                              const int64_t* extra_row_ptr, const int32_t* extra_col_idx, int64_t* excl_row_ptr) {
   urcco::HistArgs a;

@@ -329,6 +329,28 @@ class DeviceSession:
                                                       _ptr(row_ptr), _ptr(pos)))
         return (row_ptr, pos) if out is None else (row_ptr[: n_users + 1], pos[: n_old + n_new])
 
+    def history_trim(self, n_events: int, items: torch.Tensor, times: Optional[torch.Tensor], idx_row_ptr: torch.Tensor, idx_pos: torch.Tensor,
+                     min_time_ms: Optional[int] = None, drop_users: Optional[torch.Tensor] = None, out=None):
+        """urcco_dev_history_trim (decision D22): the stream (items int32, times int64 | None, n_events of them) and its index (idx_row_ptr int64
+        [n_users + 1], idx_pos) without the events with time < min_time_ms (None: no time rule) and without the events of the users in drop_users
+        (int32 dense ids in any order, repeats allowed, ids outside the id space ignored; None: nobody).  Returns (items, times | None, row_ptr, pos,
+        counts): tensors sized by n_events (row_ptr: n_users + 1) of which the first K (items, times) and KE (pos) entries are the result, and counts
+        int64 [2] = [K, KE] on the device.  out: (items, times | None, row_ptr, pos) tensors of at least those sizes to write into, returned as they
+        are; they must not share memory with the inputs.  Does not synchronise."""
+        n, n_users = int(n_events), int(idx_row_ptr.numel()) - 1
+        n_drop = int(drop_users.numel()) if drop_users is not None else 0
+        if out is None:
+            out = (self.empty(max(n, 1), torch.int32), self.empty(max(n, 1), torch.int64) if times is not None else None, self.empty(n_users + 1, torch.int64),
+                   self.empty(max(n, 1), torch.int32))
+        o_items, o_times, o_rp, o_pos = out
+        if o_items.numel() < n or o_pos.numel() < n or o_rp.numel() < n_users + 1 or (o_times is not None and o_times.numel() < n):
+            raise ValueError("history_trim: the output tensors are smaller than n_events / n_users + 1")
+        counts = self.empty(2, torch.int64)
+        self._check(self.lib.urcco_dev_history_trim(self.handle, n, _ptr(items), _ptr(times), n_users, _ptr(idx_row_ptr), _ptr(idx_pos),
+                                                    int(min_time_ms) if min_time_ms is not None and times is not None else -(1 << 63), n_drop,
+                                                    _ptr(drop_users) if n_drop else None, _ptr(o_items), _ptr(o_times), _ptr(o_rp), _ptr(o_pos), _ptr(counts)))
+        return o_items, o_times, o_rp, o_pos, counts
+
     def history_rows(self, q_users: torch.Tensor, n_users: int, events, n_items: int, extra=None, stats: bool = False, timing: bool = False, keep_bounds: bool = False):
         """urcco_dev_history_bounds + urcco_dev_history_rows: the user-history term rows and the exclusion rows of a batch of queries.
         q_users: int32 [n_queries] dense user ids (< 0 or >= n_users: unknown).  events: per event type (n_cols, max_items, blacklist, idx_row_ptr, idx_pos,

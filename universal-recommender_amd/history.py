@@ -52,6 +52,7 @@ class DeviceHistory:
     def __init__(self, sess: DeviceSession, n_users: int, user_ids, types: Dict[str, _Stream], model=None):
         self.sess, self.n_users, self.user_ids, self.types = sess, int(n_users), user_ids, types
         self.model = model     # the model the column maps came from: `append` needs it for an event name the history does not hold yet
+        self.last_trim: Dict[str, Tuple[int, int]] = {}     # `trim`: event -> (events before, events after) of the last call
 
     def user_index(self, user) -> int:
         """Dense id of a query's user, -1 when the history does not know it."""
@@ -187,6 +188,65 @@ class DeviceHistory:
         self.n_users = n_users
         if user_ids is not None:
             self.user_ids = user_ids
+        return self
+
+    def trim(self, before_ms: Optional[int] = None, drop_users=None, events: Optional[List[str]] = None) -> "DeviceHistory":
+        """Retention, in place (decision D22 of DESIGN.md; include/urcco.h urcco_dev_history_trim); returns self.  before_ms: the events with time <
+        before_ms leave the event types named in `events` (default: every type that has times) -- the reference's eventWindow.  drop_users: an
+        iterable of user keys (resolved through user_index, unknown ones ignored) or an int32 tensor of dense ids; their events leave EVERY event type,
+        whatever `events` says -- the event store's $delete of a user.  The users keep their ids: user_ids and n_users are unchanged, a dropped user
+        is answered like a user without events.  Every result afterwards is the one of from_streams over the filtered whole streams with the same
+        n_users; `append` works on as before.
+
+        A type for which neither rule applies costs no call.  One device-to-host read, of the counts of all types together.  The outputs of the
+        call become the stream's buffers, with the capacity the old ones had: their tail is the spare capacity the next append fills.  The index
+        pair of before becomes the spare pair.  `last_trim` = {event: (events before, events after)} of the types that were trimmed.
+
+        ValueError -- nothing is modified: `events` names a type the history does not hold, or, with before_ms, one without times; drop_users is a
+        tensor of another dtype; a _Stream built by hand without n_events."""
+        named = list(self.types) if events is None else list(events)
+        for ev in named:
+            if ev not in self.types:
+                raise ValueError(f"trim: the history holds no event type {ev!r}")
+            if before_ms is not None and events is not None and self.types[ev].times is None:
+                raise ValueError(f"trim: the stream {ev!r} has no times, before_ms cannot apply to it")
+        by_time = {ev for ev in named if self.types[ev].times is not None} if before_ms is not None else set()
+        sess = self.sess
+        drop = None
+        if isinstance(drop_users, torch.Tensor):
+            if drop_users.dtype != torch.int32:
+                raise ValueError("trim: drop_users as a tensor holds int32 dense user ids")
+            drop = drop_users.reshape(-1).to(sess.device) if drop_users.numel() else None
+        elif drop_users is not None:
+            ids = [i for i in (self.user_index(u) for u in drop_users) if i >= 0]
+            drop = torch.tensor(ids, dtype=torch.int32).to(sess.device) if ids else None
+        todo = [ev for ev in self.types if ev in by_time or drop is not None]
+        for ev in todo:
+            if self.types[ev].n_events < 0:
+                raise ValueError(f"stream {ev!r}: built without its number of events (_Stream.n_events)")
+        calls = []
+        for ev in todo:      # every call first, then the one read of the counts; the history changes only after both
+            st = self.types[ev]
+            n = st.n_events
+            if n == 0:
+                continue
+            spare = st.idx_spare
+            if spare is None or spare[0].numel() < self.n_users + 1 or spare[1].numel() < n:
+                live = st.idx_buf if st.idx_buf is not None else (st.idx_row_ptr, st.idx_pos)
+                spare = (sess.empty(max(live[0].numel(), self.n_users + 1), torch.int64), sess.empty(max(live[1].numel(), n), torch.int32))
+            out = (sess.empty((st.items_buf if st.items_buf is not None else st.items).numel(), torch.int32),
+                   sess.empty((st.times_buf if st.times_buf is not None else st.times).numel(), torch.int64) if st.times is not None else None, spare[0], spare[1])
+            calls.append((ev, out, sess.history_trim(n, st.items, st.times, st.idx_row_ptr, st.idx_pos, before_ms if ev in by_time else None, drop, out)[4]))
+        counts = torch.stack([c for _, _, c in calls]).cpu().tolist() if calls else []
+        self.last_trim = {ev: (0, 0) for ev in todo}
+        for (ev, (o_items, o_times, o_rp, o_pos), _), (k, _) in zip(calls, counts):
+            st = self.types[ev]
+            self.last_trim[ev] = (st.n_events, int(k))
+            st.idx_spare = st.idx_buf if st.idx_buf is not None else (st.idx_row_ptr, st.idx_pos)
+            st.items_buf, st.items = o_items, o_items[: max(k, 1)]      # an empty stream still has an array
+            if o_times is not None:
+                st.times_buf, st.times = o_times, o_times[: max(k, 1)]
+            st.idx_buf, st.idx_row_ptr, st.idx_pos, st.n_events = (o_rp, o_pos), o_rp[: self.n_users + 1], o_pos[: max(k, 1)], int(k)
         return self
 
     @staticmethod
