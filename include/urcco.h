@@ -294,6 +294,9 @@ int urcco_context_get_timings_gpu(urcco_context* ctx, int32_t local_gpu, double*
  *   67108864 COUNT_DIRECT     with stage timing on, stats[30] counts the rows that were ranked directly, not candidates
  *   134217728 NO_SMALL_WAVE   the one-wave class's rows of <= 64 users and <= 256 pairs stay in its general kernel (no micro-shaped body: cco_rows.hip)
  *   268435456 COUNT_SMALL_WAVE with stage timing on, stats[30] counts the rows that ran in that body, plus 2^32 per row that took its fallback
+ *   536870912 NO_BLOCK_SMALL_WAVE the rows of <= 128 users and <= 512 pairs that the same body takes with two users per lane -- the rest of the one-wave class,
+ *                             the first list of the small-block class -- stay in the general kernels
+ *   1073741824 COUNT_BLOCK_SMALL_WAVE with stage timing on, stats[30] counts the rows of those lists that ran in the body, plus 2^32 per row that took its fallback
  * Test hook: 131072 SELECT_DELAY = the first wave of every multi-wave team sleeps before it reads the select histogram
  * (tests/test_gpu_parity.py::test_select_overlay_race_fixed).
  * The row-kernel bits (1..16, 512, 131072) run the rows on separate instantiations that carry the switches. */

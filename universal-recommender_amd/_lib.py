@@ -57,6 +57,8 @@ DBG_NO_DIRECT_RANK = 33554432
 DBG_COUNT_DIRECT = 67108864
 DBG_NO_SMALL_WAVE = 134217728
 DBG_COUNT_SMALL_WAVE = 268435456
+DBG_NO_BLOCK_SMALL_WAVE = 536870912
+DBG_COUNT_BLOCK_SMALL_WAVE = 1073741824
 DBG_ROW_KERNELS = DBG_GATHER_ONLY | DBG_NO_LLR | DBG_NO_TOPK | DBG_NO_SELECT | DBG_NO_RANK | DBG_NO_COUNT_GATHER | DBG_SELECT_DELAY
 STAGE_NAMES = ["column_counts", "downsample_flags", "downsample_scan", "downsample_compact", "transpose", "row_work", "binning",
                "entropy", "cco_rows_micro", "cco_rows_wave", "cco_rows_block_small", "cco_rows_block", "cco_rows_cu_half", "cco_rows_cu", "cco_rows_global", "compact_indicators", "exchange"]

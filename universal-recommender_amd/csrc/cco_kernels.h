@@ -18,9 +18,10 @@ constexpr int DS_TILE = 4096;            // entries per down-sample tile (256 th
 constexpr int GLOBAL_BIN_BLOCKS = 128;    // persistent blocks of the global-accumulator kernel (upper bound)
 constexpr int BIN_TILE = 1024;           // items per binning tile
 constexpr int XLX_TABLE_HOST = 4096;     // entries of the small-integer xLogX table (== XLX_TABLE in cco_device.h)
-constexpr int BIN_COLS_HOST = 3 * NBINS + 5;  // int64 per binning tile (rows per internal bin -- the micro and the one-wave class have three sub-lists each --, pairs and users per bin, total)
-constexpr int BIN_OFF_LEN = NBINS + 5;        // bin_off: [0 .. NBINS] list offsets of the classes, then the starts of the micro class's second and third sub-list
-                                              // and of the one-wave class's second and third (its rows of <= 256 pairs, the rest: cco_rows.hip, SMALL_SUBS)
+constexpr int BIN_COLS_HOST = 3 * NBINS + 7;  // int64 per binning tile (rows per internal bin -- the micro class has three sub-lists, the one-wave class four, the small-block class two --, pairs and users per bin, total)
+constexpr int BIN_OFF_LEN = NBINS + 7;        // bin_off: [0 .. NBINS] list offsets of the classes, then the starts of the micro class's second and third sub-list,
+                                              // of the one-wave class's second, third and fourth (its rows of <= 256 pairs, of <= 128 users, the rest: cco_rows.hip, SMALL_SUBS)
+                                              // and of the small-block class's second (the rest behind its rows of <= 128 users and <= 512 pairs: BLOCK_SUBS)
 constexpr int CAND_SLOTS = 64;           // words the row kernels spread their candidate counts over (see CcoArgs::cand)
 constexpr int STATS_LEN = 32;            // [0] pairs, then NBINS each of rows / pairs / users / out entries per bin, [1 + 4 NBINS] table overflows,
                                          // [STATS_LEN - 1] rows binned into the micro class's two shared-wave sub-lists (0: the class ran as one list)
@@ -48,6 +49,10 @@ constexpr int32_t DBG_COUNT_DIRECT = 67108864;      // with stage timing on: sta
 // The micro-shaped body of the one-wave class's small rows (cco_rows.hip, cco_rows_small_kernel).  As above: arguments of the production kernels.
 constexpr int32_t DBG_NO_SMALL_WAVE = 134217728;    // the class's sub-lists of small rows stay in the general kernel (A/B, and the tests' bit-for-bit comparison)
 constexpr int32_t DBG_COUNT_SMALL_WAVE = 268435456; // with stage timing on: stats[2 + 4 * NBINS] counts the ROWS that ran in that body, + 2^32 per row that took its fallback
+// The same body with eight pairs and two users per lane: the one-wave class's rows of <= 128 users that those sub-lists leave, and the small-block class's rows
+// of <= 128 users and <= 512 pairs.  As above: arguments of the production kernels.
+constexpr int32_t DBG_NO_BLOCK_SMALL_WAVE = 536870912;     // these sub-lists run in the general kernels (A/B, and the tests' bit-for-bit comparison)
+constexpr int32_t DBG_COUNT_BLOCK_SMALL_WAVE = 1073741824; // with stage timing on: stats[2 + 4 * NBINS] counts the ROWS of these sub-lists that ran in that body, + 2^32 per row that took its fallback
 constexpr int32_t DBG_ROW_KERNELS = DBG_GATHER_ONLY | DBG_NO_LLR | DBG_NO_TOPK | DBG_NO_SELECT | DBG_NO_RANK | DBG_NO_COUNT_GATHER | DBG_SELECT_DELAY;
 
 // The form of a build's expand tables, decided on the device by the scan of the work prefix (launch_expand_prepare / launch_expand_scan).

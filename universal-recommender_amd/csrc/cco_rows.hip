@@ -56,20 +56,31 @@ constexpr int MICRO_SUBS = 3;
 // The one-wave class (bin 1) in three sub-lists, by the same mechanism: rows of <= 64 users and <= 128 pairs, rows of <= 64 users and <= 256 pairs -- they run in
 // the micro-shaped body of cco_rows_small_kernel, two / four pairs per lane --, then the rest of the class.  Internal bins MICRO_SUBS, MICRO_SUBS + 1 and
 // MICRO_SUBS + 2; the first starts at bin_off[1], the other two at bin_off[NBINS + 3] and bin_off[NBINS + 4].  Unsplit (a small build, or a k the fast tail of
-// that body cannot serve: SMALL_KMAX) the two sub-lists are empty and bin_off[NBINS + 4] == bin_off[1].
-constexpr int SMALL_SUBS = 2;
-constexpr int SMALL_P0 = 2, SMALL_P1 = 4;  // pairs per lane of the two sub-lists
+// that body cannot serve: SMALL_KMAX) the sub-lists are empty and the rest starts at bin_off[1].
+// A third sub-list of the one-wave class, behind those two: what is left of the class with <= 128 users (<= 290 pairs at k = 50, <= 512 always) runs in the
+// same body with eight pairs and TWO users per lane; the few rows beyond stay in the general kernel.  Internal bins MICRO_SUBS + 2 (start: bin_off[NBINS + 4])
+// and MICRO_SUBS + 3 (the rest, start: bin_off[NBINS + 5]).  And the small-block class (bin 2) in two lists: its rows of <= 128 users and <= 512 pairs -- that
+// body again --, then the rest, which starts at bin_off[NBINS + 6] (BLOCK_SUBS).
+constexpr int SMALL_SUBS = 3;
+constexpr int BLOCK_SUBS = 1;
+constexpr int SMALL_P0 = 2, SMALL_P1 = 4, SMALL_P2 = 8;  // pairs per lane of the sub-lists
+constexpr int SMALL_U2 = 2;                               // users per lane of the sub-lists that run with SMALL_P2
 constexpr int SMALL_KMAX = WAVE - 1;       // the prefilter keeps >= k (+ 1 with a self pair) survivors whenever it cuts; the fast tail ranks <= 64, one per lane
 static_assert(SMALL_KMAX + 1 <= WAVE && SMALL_KMAX >= 1, "k + 1 survivors (a self pair among them) must fit the lanes of the fast tail");
-constexpr int IBINS = NBINS - 1 + MICRO_SUBS + SMALL_SUBS;
+static_assert(SMALL_P2 * WAVE >= URCCO_WB1, "every row of the one-wave class fits eight pairs per lane");
+constexpr int IBINS = NBINS - 1 + MICRO_SUBS + SMALL_SUBS + BLOCK_SUBS;
 constexpr int SPLIT_MICRO = 1, SPLIT_SMALL = 2;  // bits of the binning kernels' `split`
 __device__ __forceinline__ int micro_sub(long long w, long long ca) { return (w <= 16 && ca <= 16) ? 0 : ((w <= 32 && ca <= 32) ? 1 : 2); }
-__device__ __forceinline__ int small_sub(long long w, long long ca) { return ca > WAVE ? 2 : (w <= SMALL_P0 * WAVE ? 0 : (w <= SMALL_P1 * WAVE ? 1 : 2)); }
+__device__ __forceinline__ int small_sub(long long w, long long ca) {
+  return ca > SMALL_U2 * WAVE ? 3 : ((ca > WAVE || w > SMALL_P1 * WAVE) ? 2 : (w <= SMALL_P0 * WAVE ? 0 : 1));
+}
+__device__ __forceinline__ int block_sub(long long w, long long ca) { return (ca <= SMALL_U2 * WAVE && w <= SMALL_P2 * WAVE) ? 0 : 1; }
 __device__ __forceinline__ int internal_bin(int b, long long w, long long ca, int split) {
   if (b < 0) return -1;
   if (b == 0) return (split & SPLIT_MICRO) ? micro_sub(w, ca) : MICRO_SUBS - 1;
   if (b == 1) return MICRO_SUBS + ((split & SPLIT_SMALL) ? small_sub(w, ca) : SMALL_SUBS);
-  return b + MICRO_SUBS - 1 + SMALL_SUBS;
+  if (b == 2) return MICRO_SUBS + SMALL_SUBS + 1 + ((split & SPLIT_SMALL) ? block_sub(w, ca) : BLOCK_SUBS);
+  return b + MICRO_SUBS - 1 + SMALL_SUBS + BLOCK_SUBS;
 }
 // The micro class is split into its sub-lists only when the build has enough item rows for three launches to pay: a rank of a sharded build (an eighth
 // of config 4's rows) would start 16K waves per sub-list for a handful of passes each (emulated 8-rank build: 3.45 against 3.17 ms of SpGEMM per rank).
@@ -80,15 +91,22 @@ static bool micro_split_for(int32_t n_rows) {
 }
 // where the list of internal bin ib starts, as an index into bin_off
 __host__ __device__ constexpr int internal_off_index(int ib) {
-  return ib == 0 ? 0 : (ib < MICRO_SUBS ? NBINS + ib : (ib == MICRO_SUBS ? 1 : (ib <= MICRO_SUBS + SMALL_SUBS ? NBINS + ib - 1 : ib - (MICRO_SUBS - 1 + SMALL_SUBS))));
+  constexpr int B2 = MICRO_SUBS + SMALL_SUBS + 1;  // the small-block class's first list
+  return ib == 0 ? 0
+                 : (ib < MICRO_SUBS ? NBINS + ib
+                                    : (ib == MICRO_SUBS ? 1
+                                                        : (ib < B2 ? NBINS + ib - 1
+                                                                   : (ib == B2 ? 2 : (ib <= B2 + BLOCK_SUBS ? NBINS + ib - 2 : ib - (MICRO_SUBS - 1 + SMALL_SUBS + BLOCK_SUBS))))));
 }
-static_assert(internal_off_index(MICRO_SUBS + 1) == NBINS + 3 && internal_off_index(MICRO_SUBS + 2) == NBINS + 4 && internal_off_index(MICRO_SUBS + 3) == 2 &&
-              internal_off_index(IBINS - 1) == NBINS - 1, "bin_off layout");
+constexpr int OFF_SMALL_P1 = NBINS + 3, OFF_SMALL_U2 = NBINS + 4, OFF_WAVE_REST = NBINS + 5, OFF_BLOCK_REST = NBINS + 6;  // the sub-lists' starts in bin_off
+static_assert(internal_off_index(MICRO_SUBS + 1) == OFF_SMALL_P1 && internal_off_index(MICRO_SUBS + 2) == OFF_SMALL_U2 && internal_off_index(MICRO_SUBS + 3) == OFF_WAVE_REST &&
+              internal_off_index(MICRO_SUBS + 4) == 2 && internal_off_index(MICRO_SUBS + 5) == OFF_BLOCK_REST && internal_off_index(MICRO_SUBS + 6) == 3 &&
+              internal_off_index(IBINS - 1) == NBINS - 1 && OFF_BLOCK_REST == BIN_OFF_LEN - 1, "bin_off layout");
 __device__ __forceinline__ int internal_start(const int32_t* __restrict__ bin_off, int ib) { return bin_off[internal_off_index(ib)]; }
 constexpr int BIN_THREADS = 256;
 constexpr int BIN_ITEMS = BIN_TILE / BIN_THREADS;  // 4
 constexpr int BIN_COLS = IBINS + 2 * NBINS + 1;    // per tile: rows per INTERNAL bin, pairs per bin, users per bin, total pairs
-static_assert(BIN_COLS == BIN_COLS_HOST && BIN_OFF_LEN == NBINS + MICRO_SUBS + SMALL_SUBS, "scratch sizes of the callers");
+static_assert(BIN_COLS == BIN_COLS_HOST && BIN_OFF_LEN == NBINS + MICRO_SUBS + SMALL_SUBS + BLOCK_SUBS, "scratch sizes of the callers");
 
 __global__ __launch_bounds__(BIN_THREADS) void bin_count_kernel(int32_t item_lo, int32_t n, const int64_t* __restrict__ work,
                                                                 const int32_t* __restrict__ cnt_a, int32_t n_cols_b, int32_t count_bits, int32_t k,
@@ -193,7 +211,8 @@ __global__ __launch_bounds__(BS_THREADS) void bin_scan_kernel(int64_t* __restric
         long long rows = 0;
         if (k == 0) for (int q = 0; q < MICRO_SUBS; ++q) rows += s_tot[q];
         else if (k == 1) for (int q = 0; q <= SMALL_SUBS; ++q) rows += s_tot[MICRO_SUBS + q];
-        else rows = s_tot[k + MICRO_SUBS - 1 + SMALL_SUBS];
+        else if (k == 2) for (int q = 0; q <= BLOCK_SUBS; ++q) rows += s_tot[MICRO_SUBS + SMALL_SUBS + 1 + q];
+        else rows = s_tot[k + MICRO_SUBS - 1 + SMALL_SUBS + BLOCK_SUBS];
         stats[1 + k] = rows;                                      // rows
         stats[1 + NBINS + k] = s_tot[IBINS + k];                  // pairs
         stats[1 + 2 * NBINS + k] = s_tot[IBINS + NBINS + k];      // users (sum of cA over the bin's rows)
@@ -770,7 +789,10 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
   constexpr unsigned DL = PF ? direct_limit(T, E) : 0u;  // the direct ranking: only the instantiations that carry the prefilter, 0 = none
   static_assert(DL <= (unsigned)SEL_M, "a directly ranked row lives in the ambiguous-set arrays");
   // (bit 11 of the bin argument, one-wave PK instantiation only: the class's sub-lists of small rows run in cco_rows_small_kernel -- this kernel takes the rest)
-  const int list_start = (T == WAVE && PK && !MP && (bin_arg & 2048)) ? a.bin_off[NBINS + MICRO_SUBS - 1 + SMALL_SUBS] : a.bin_off[bin];
+  // (with bit 13 as well it also takes the class's third sub-list, which lies just ahead of the rest -- DBG_NO_BLOCK_SMALL_WAVE; bit 11 of the small-block PK
+  // instantiation: the class's first list runs in that body, this kernel takes the rest)
+  const int list_start = (T == WAVE && PK && !MP && (bin_arg & 2048)) ? a.bin_off[(bin_arg & 8192) ? OFF_SMALL_U2 : OFF_WAVE_REST]
+                         : ((T == 256 && E == E1S && PK && !MP && (bin_arg & 2048)) ? a.bin_off[OFF_BLOCK_REST] : a.bin_off[bin]);
   const int list_n = a.bin_off[bin + 1] - list_start;
   const int total_teams = gridDim.x * TEAMS;
   bool ident =(long long)a.n_cols_b * 3 + (long long)a.k * 3 + 2 <= E && a.n_cols_b <= SH;  // the table spans every column of B: slots addressed by column
@@ -1872,19 +1894,31 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
 // Wave LDS layout (words): [0, 512) the accumulator -- in the fallback the staged packed words [256] | cB, then columns [256], then over the packed words the
 // digit histogram [128] and, behind the cut, the tail's list [3 x 68]; [512, 1024) by phase: the pair -> user marks [64 P + 2] | the prefilter's histogram [128],
 // the fast tail's staged survivors (packed word, cB) [2 x 64] behind it, its columns [68] and keys [68] behind those | the fallback's keys [256].  16 KiB per block.
+// <P = 8, UPL = 2>: the same body for rows of <= 128 users and <= 512 pairs -- what the two sub-lists leave of the one-wave class up to 128 users, and the
+// first list of the small-block class (bin 2), whose 256-thread kernel walked the one wave's worth of candidates such a row keeps with four waves behind block
+// barriers.  A lane holds pstart / wp of users lane and lane + 64, a mark carries a user index up to 127, and the pair -> user step gathers the user's delta
+// from lane (user & 63) of BOTH registers and selects by user >= 64.  Everything scales with P: wave LDS layout (words) [0, 1024) the accumulator (load
+// <= 1/2) -- in the fallback the staged packed words [512] | cB, then columns [512], the digit histogram [128] and the tail's list [3 x 68] over the packed
+// words --; [1024, 2048) by phase: marks [64 P + 2 = 514] | the prefilter's histogram [128], the fast tail's staged survivors [2 x 64], columns [68] and
+// keys [68] | the fallback's keys [512 of 64 bits].  32 KiB per block, five blocks per CU (77 VGPRs, no scratch).
 // flags: bit 8 -- the statistics count the candidates that were SCORED (DBG_COUNT_SCORED); bit 12 -- they count the ROWS of this body, + 2^32 per row that took
-// the fallback (DBG_COUNT_SMALL_WAVE).
+// the fallback (DBG_COUNT_SMALL_WAVE; for the eight-pair form DBG_COUNT_BLOCK_SMALL_WAVE); bit 13, eight-pair form -- the list is the small-block class's.
 // --------------------------------------------------------------------------------------------
-constexpr int SMALL_TW = 512, SMALL_LOG2TW = 9;  // accumulator words per row
+__host__ __device__ constexpr int small_log2tw(int P) { return P <= SMALL_P1 ? 9 : 10; }  // accumulator words per row: 512, or 1024 with eight pairs per lane
 constexpr int SMALL_LIST = WAVE + 4;             // the fast tail's columns / keys (with room for the padding of the ranking loops)
-constexpr int SMALL_WORDS = 2 * SMALL_TW;
 constexpr int SMALL_FACTOR = 4;                  // grid of a sub-list, as a multiple of the blocks that fit the chip (see ROW_CLASS)
-static_assert(2 * SMALL_P1 * WAVE <= SMALL_TW && SMALL_P1 * WAVE + 2 <= SMALL_TW && 3 * SMALL_LIST <= SMALL_TW / 2 && PF_BINS / 2 <= SMALL_TW / 2, "accumulator load <= 1/2; the marks and the fallback's keys fit the phase region, its staged words and columns the accumulator");
-static_assert(PF_BINS / 2 + 2 * WAVE + 3 * SMALL_LIST <= SMALL_TW && (PF_BINS / 2 + 2 * WAVE + SMALL_LIST) % 2 == 0, "fast tail arrays; 64-bit keys 8-byte aligned");
-template <int P>
-__global__ __launch_bounds__(256, URCCO_OCC_MICRO) void cco_rows_small_kernel(CcoArgs a, int flags) {
+constexpr int SMALL_OCC_P2 = 5;                  // blocks per CU of the eight-pair form: 32 KiB of LDS each
+template <int P, int UPL>
+__global__ __launch_bounds__(256, (P == SMALL_P2 ? SMALL_OCC_P2 : URCCO_OCC_MICRO)) void cco_rows_small_kernel(CcoArgs a, int flags) {
   if (!(a.b_packed != nullptr && (a.pk_known != 0 || *a.form == 0))) return;  // grid-uniform: the plain instantiation of cco_rows_kernel has the whole class
-  static_assert(P == SMALL_P0 || P == SMALL_P1, "one instantiation per sub-list");
+  static_assert(((P == SMALL_P0 || P == SMALL_P1) && UPL == 1) || (P == SMALL_P2 && UPL == SMALL_U2), "one instantiation per sub-list shape");
+  constexpr int LOG2TW = small_log2tw(P), TW = 1 << LOG2TW, WORDS = 2 * TW;
+  constexpr int MAX_USERS = UPL * WAVE;
+  static_assert(2 * P * WAVE <= TW && P * WAVE + 2 <= TW && 3 * SMALL_LIST <= TW / 2 && PF_BINS / 2 <= TW / 2,
+                "accumulator load <= 1/2; the marks and the fallback's keys (64 P of 64 bits) fit the phase region, its staged words and columns (64 P each) the accumulator");
+  static_assert(PF_BINS / 2 + 2 * WAVE + 3 * SMALL_LIST <= TW && (PF_BINS / 2 + 2 * WAVE + SMALL_LIST) % 2 == 0, "fast tail arrays; 64-bit keys 8-byte aligned");
+  static_assert(P * WAVE < 65536 && MAX_USERS <= 128, "the fallback's digit histogram and the prefilter's count 64 P candidates in 16-bit fields; a mark carries a user index");
+  static_assert((256 / WAVE) * WORDS * 4 <=160 * 1024 / (P == SMALL_P2 ? SMALL_OCC_P2 : URCCO_OCC_MICRO), "LDS per block at the occupancy the kernel is compiled for");
   const int32_t* bin_rows = a.bin_rows;
   const int64_t* a_col_ptr = a.a_col_ptr;
   const unsigned* pstart = a.pstart32;
@@ -1903,21 +1937,23 @@ __global__ __launch_bounds__(256, URCCO_OCC_MICRO) void cco_rows_small_kernel(Cc
   const bool has_pf = a.pf_limit != nullptr;
   const unsigned short* lim_tab = has_pf ? a.pf_limit : reinterpret_cast<const unsigned short*>(a.cnt_a);  // (prefetched unconditionally: any readable table of >= n items)
   constexpr int TEAMS = 256 / WAVE;
-  __shared__ __attribute__((aligned(16))) unsigned s_tab[TEAMS * SMALL_WORDS];
+  __shared__ __attribute__((aligned(16))) unsigned s_tab[TEAMS * WORDS];
   const int team = threadIdx.x / WAVE;
   const int lane = threadIdx.x & (WAVE - 1);
-  unsigned* tab = s_tab + team * SMALL_WORDS;
-  unsigned* marks = tab + SMALL_TW;
+  unsigned* tab = s_tab + team * WORDS;
+  unsigned* marks = tab + TW;
   unsigned* pfh = marks;
   unsigned* st_v = marks + PF_BINS / 2;
   unsigned* st_c = st_v + WAVE;
   unsigned* cand = st_c + WAVE;
   unsigned long long* kkm = reinterpret_cast<unsigned long long*>(cand + SMALL_LIST);
   unsigned long long* fkeys = reinterpret_cast<unsigned long long*>(marks);
-  const int list_start = P == SMALL_P0 ? a.bin_off[1] : a.bin_off[NBINS + 3];
-  const int list_n = (P == SMALL_P0 ? a.bin_off[NBINS + 3] : a.bin_off[NBINS + 4]) - list_start;
+  // the sub-list: by shape, and for the eight-pair form by bit 13 of the flags -- the small-block class's first list, else the one-wave class's third
+  const bool of_block = P == SMALL_P2 && (flags & 8192);
+  const int list_start = a.bin_off[P == SMALL_P0 ? 1 : (P == SMALL_P1 ? OFF_SMALL_P1 : (of_block ? 2 : OFF_SMALL_U2))];
+  const int list_n = a.bin_off[P == SMALL_P0 ? OFF_SMALL_P1 : (P == SMALL_P1 ? OFF_SMALL_U2 : (of_block ? OFF_BLOCK_REST : OFF_WAVE_REST))] - list_start;
   const int total_teams = gridDim.x * TEAMS;
-  const bool ident = a.n_cols_b <= SMALL_TW;
+  const bool ident = a.n_cols_b <= TW;
   const int cb = a.count_bits;
   const unsigned cmask = (1u << cb) - 1u;
   const double xlx_n = __longlong_as_double((long long)uni((int64_t)__double_as_longlong(*a.xlx_n)));  // (a scalar pair: as a loaded value it held two vector registers across the row loop)
@@ -1935,7 +1971,7 @@ __global__ __launch_bounds__(256, URCCO_OCC_MICRO) void cco_rows_small_kernel(Cc
   const int lane3 = lane < 3 ? lane : 2;
   int idv = bin_rows[pos_of(li + lane3 * stride)];  // lanes 0, 1, 2: ids of this row and the next two
   int64_t bnd_b;                                    // the next row's bounds: lane 0 start, lane 1 end
-  unsigned pf_w1, pf_wp, pf_start;
+  unsigned pf_w1, pf_wp[UPL], pf_start[UPL];  // (UPL users per lane: users lane, lane + 64)
   int n_cur;  // users of the row about to be processed (scalar)
   {
     const int id0 = (int)wave_read_lane((unsigned)idv, 0);
@@ -1943,29 +1979,39 @@ __global__ __launch_bounds__(256, URCCO_OCC_MICRO) void cco_rows_small_kernel(Cc
     const int64_t cs0 = uni(a_col_ptr[id0]), ce0 = uni(a_col_ptr[id0 + 1]);
     bnd_b = a_col_ptr[id1 + (lane & 1)];
     n_cur = (int)(ce0 - cs0);
-    const int64_t pl = lane < n_cur ? cs0 + lane : ce0 - 1;
     pf_w1 = wp32[ce0];
-    pf_wp = wp32[pl];
-    pf_start = pstart[pl];
-  }
-  URCCO_SETTLE(idv); URCCO_SETTLE(bnd_b); URCCO_SETTLE(pf_w1); URCCO_SETTLE(pf_wp); URCCO_SETTLE(pf_start);
 #pragma unroll
-  for (int q = 0; q < SMALL_TW / WAVE; ++q) tab[lane + q * WAVE] = 0u;  // the accumulator: zero between rows (a candidate's owner clears its slot)
+    for (int q = 0; q < UPL; ++q) {
+      const int64_t pl = lane + q * WAVE < n_cur ? cs0 + lane + q * WAVE : ce0 - 1;
+      pf_wp[q] = wp32[pl];
+      pf_start[q] = pstart[pl];
+    }
+  }
+  URCCO_SETTLE(idv); URCCO_SETTLE(bnd_b); URCCO_SETTLE(pf_w1);
+#pragma unroll
+  for (int q = 0; q < UPL; ++q) { URCCO_SETTLE(pf_wp[q]); URCCO_SETTLE(pf_start[q]); }
+#pragma unroll
+  for (int q = 0; q < TW / WAVE; ++q) tab[lane + q * WAVE] = 0u;  // the accumulator: zero between rows (a candidate's owner clears its slot)
   int64_t bnd_c = 0;  // the bounds two rows ahead, in flight: rotated by the loop's increment
   for (; li < list_n; li += stride, bnd_b = bnd_c) {  // each wave runs its own row loop: wave-level sync only
     const int i = (int)wave_read_lane((unsigned)idv, 0);
     const int id2 = (int)wave_read_lane((unsigned)idv, 2);
     const int64_t cs_n = wave_read_lane64(bnd_b, 0), ce_n = wave_read_lane64(bnd_b, 1);
     // this row's operands leave their registers ...
-    const unsigned w0 = wave_read_lane(pf_wp, 0);  // wp[cs]
-    unsigned total = uni(pf_w1) - w0;              // <= 64 P by the binning rule
-    if (total > (unsigned)(P * WAVE) || n_cur > WAVE) {  // (cannot happen while the binning rule holds: reported, and the row left empty)
+    const unsigned w0 = wave_read_lane(pf_wp[0], 0);  // wp[cs]
+    unsigned total = uni(pf_w1) - w0;                 // <= 64 P by the binning rule
+    if (total > (unsigned)(P * WAVE) || n_cur > MAX_USERS) {  // (cannot happen while the binning rule holds: reported, and the row left empty)
       if (lane == 0) atomicAdd(a.err, 1ull);
       total = 0u;
     }
-    const bool owns_user = lane < n_cur;
-    const unsigned my_off = owns_user ? pf_wp - w0 : total;
-    const unsigned my_delta = (owns_user ? pf_start : 0u) - my_off;  // B' position of pair t of this lane's user: delta + t, in 32-bit wrap-around arithmetic
+    bool owns_user[UPL];
+    unsigned my_off[UPL], my_delta[UPL];
+#pragma unroll
+    for (int q = 0; q < UPL; ++q) {
+      owns_user[q] = lane + q * WAVE < n_cur;
+      my_off[q] = owns_user[q] ? pf_wp[q] - w0 : total;
+      my_delta[q] = (owns_user[q] ? pf_start[q] : 0u) - my_off[q];  // B' position of pair t of this lane's user: delta + t, in 32-bit wrap-around arithmetic
+    }
     // ... and the rows ahead take them: ids up to row + 3, bounds of row + 2, operands of row + 1
     int lz = lane;
     URCCO_OPAQUE(lz);  // (what derives from the lane here is recomputed per row, not kept across the row loop)
@@ -1977,18 +2023,21 @@ __global__ __launch_bounds__(256, URCCO_OCC_MICRO) void cco_rows_small_kernel(Cc
     const double row_entropy = ent_a[iv];
     const unsigned row_lim = lim_tab[iv];  // the row's monotone limit (16 bits, zero-extended by the load)
     n_cur = (int)(ce_n - cs_n);
-    {
-      const int64_t pl = lz < n_cur ? cs_n + lz : ce_n - 1;
-      pf_w1 = wp32[ce_n];
-      pf_wp = wp32[pl];
-      pf_start = pstart[pl];
+    pf_w1 = wp32[ce_n];
+#pragma unroll
+    for (int q = 0; q < UPL; ++q) {
+      const int64_t pl = lz + q * WAVE < n_cur ? cs_n + lz + q * WAVE : ce_n - 1;
+      pf_wp[q] = wp32[pl];
+      pf_start[q] = pstart[pl];
     }
     // ---- pair -> user: user u marks the first pair of its B' row with u (the LAST user of an offset is the one whose row is not empty)
 #pragma unroll
     for (int r = 0; r < P; ++r) marks[lane + r * WAVE] = 0u;
     if (lane < 2) marks[P * WAVE + lane] = 0u;
     wave_sync();
-    if (owns_user && my_off <= total) atomicMax(&marks[my_off], (unsigned)lane);  // my_off <= total <= 64 P: marks has 64 P + 2 words
+#pragma unroll
+    for (int q = 0; q < UPL; ++q)
+      if (owns_user[q] && my_off[q] <= total) atomicMax(&marks[my_off[q]], (unsigned)(lane + q * WAVE));  // my_off <= total <= 64 P: marks has 64 P + 2 words
     wave_sync();
     unsigned jj[P];  // this lane's B' words: the column, and the column's count
     unsigned carry = 0u;
@@ -1997,7 +2046,15 @@ __global__ __launch_bounds__(256, URCCO_OCC_MICRO) void cco_rows_small_kernel(Cc
       const unsigned m = wave_inclusive_max(marks[lane + r * WAVE]);
       const unsigned o = m > carry ? m : carry;
       carry = wave_read_lane(o, WAVE - 1);
-      const unsigned base_o = wave_gather(my_delta, o);
+      unsigned base_o;  // the delta of user o: lane o & 63 holds it, in its register o / 64
+      if constexpr (UPL == 1) {
+        base_o = wave_gather(my_delta[0], o);
+      } else {
+        const unsigned src = o & (unsigned)(WAVE - 1);
+        const unsigned d0 = wave_gather(my_delta[0], src);
+        const unsigned d1 = wave_gather(my_delta[1], src);
+        base_o = o < (unsigned)WAVE ? d0 : d1;
+      }
       const unsigned t = (unsigned)(r * WAVE + lane);
       jj[r] = 0u;
       if (t < total) jj[r] = (unsigned)b_col_idx[base_o + t];
@@ -2009,7 +2066,7 @@ __global__ __launch_bounds__(256, URCCO_OCC_MICRO) void cco_rows_small_kernel(Cc
       slot[r] = 0xffffffffu;
       if ((unsigned)(r * WAVE + lane) < total) {
         bool ok;
-        slot[r] = tab_insert_claim(tab, (jj[r] & colmask) + 1u, cb, (unsigned)(SMALL_TW - 1), 32 - SMALL_LOG2TW, ident, &ok);
+        slot[r] = tab_insert_claim(tab, (jj[r] & colmask) + 1u, cb, (unsigned)(TW - 1), 32 - LOG2TW, ident, &ok);
         if (!ok) atomicAdd(a.err, 1ull);
       }
     }
@@ -2058,14 +2115,16 @@ __global__ __launch_bounds__(256, URCCO_OCC_MICRO) void cco_rows_small_kernel(Cc
     else cand_acc += n_surv <= (unsigned)WAVE ? 1ull : (1ull << 32) + 1ull;
     const int64_t obase = ((int64_t)(i - a.item_lo)) * a.k;
     auto settle_prefetch = [&]() {  // the next row's operands have had the row to arrive: collect them before the output stores
-      URCCO_SETTLE(idv); URCCO_SETTLE(bnd_c); URCCO_SETTLE(pf_w1); URCCO_SETTLE(pf_wp); URCCO_SETTLE(pf_start);
+      URCCO_SETTLE(idv); URCCO_SETTLE(bnd_c); URCCO_SETTLE(pf_w1);
+#pragma unroll
+      for (int q = 0; q < UPL; ++q) { URCCO_SETTLE(pf_wp[q]); URCCO_SETTLE(pf_start[q]); }
     };
     // the survivors' (packed word, cB) leave the registers for their numbered places: the fast tail's 64 behind the histogram, the fallback's <= 64 P in the
     // accumulator -- zero again since the counts left it, and zeroed again below
     const bool fast = n_surv <= (unsigned)WAVE;  // wave-uniform
     {
       unsigned* sv = fast ? st_v : tab;
-      unsigned* sc = fast ? st_c : tab + SMALL_TW / 2;
+      unsigned* sc = fast ? st_c : tab + TW / 2;
 #pragma unroll
       for (int r = 0; r < P; ++r)
         if (vv[r] != 0u) {
@@ -2110,7 +2169,7 @@ __global__ __launch_bounds__(256, URCCO_OCC_MICRO) void cco_rows_small_kernel(Cc
     } else {
       // ---- fallback: more survivors than lanes (<= 64 P).  Rolled loops over the staged survivors, 64 at a time.  1. each is scored, every operand tested
       // on its own; its key goes to the phase region, its column takes the place of its cB.
-      unsigned* fcol = tab + SMALL_TW / 2;
+      unsigned* fcol = tab + TW / 2;
       wave_sync();
       unsigned n_valid = 0u;
       unsigned long long kand = ~0ull, kor = 0ull;  // over the valid keys: the leading bytes they share decide nothing
@@ -2275,7 +2334,7 @@ __global__ __launch_bounds__(256, URCCO_OCC_MICRO) void cco_rows_small_kernel(Cc
     if (!fast) {
       wave_sync();
 #pragma unroll
-      for (int q = 0; q < SMALL_TW / WAVE; ++q) tab[lane + q * WAVE] = 0u;  // the accumulator is zero between rows
+      for (int q = 0; q < TW / WAVE; ++q) tab[lane + q * WAVE] = 0u;  // the accumulator is zero between rows
     }
     wave_sync();
   }
@@ -2521,8 +2580,8 @@ hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, Ro
   // Persistent grids sized to the chip (ROW_CLASS); each kernel reads its own row list length from bin_off on the device,
   // so no host synchronisation sits between binning and the SpGEMM.
   const RowClass& c = ROW_CLASS[bin];
-  auto grid = [&](int factor) {
-    const long long fill = (long long)n_cu * blocks_per_cu(bin);  // blocks resident at once
+  auto grid = [&](int factor, int per_cu = 0) {
+    const long long fill = (long long)n_cu * (per_cu > 0 ? per_cu : blocks_per_cu(bin));  // blocks resident at once
     long long cap = ((long long)n_rows + c.teams * 32 - 1) / (c.teams * 32);
     if (cap < 2 * fill) cap = 2 * fill;  // (as rounds 2-4)
     long long blocks = fill * factor;
@@ -2533,11 +2592,23 @@ hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, Ro
   // DBG_COUNT_DIRECT: the statistics word counts the rows the packed kernels ranked directly -- every kernel that has no direct ranking (the plain and DBG
   // forms, the micro and multi-pass classes, a class it is compiled out of) runs without the word, so that no candidate count is mixed in
   // DBG_COUNT_SMALL_WAVE, likewise: the word counts the rows of cco_rows_small_kernel, and every other kernel runs without it
+  // DBG_COUNT_BLOCK_SMALL_WAVE, likewise, for the launches of that kernel's eight-pair form (URCCO_COUNT_BLOCK_LIST = 1 / 2, read per call: only the one-wave
+  // class's list / only the small-block class's)
   const bool count_direct = (args.debug & DBG_COUNT_DIRECT) != 0, count_small = (args.debug & DBG_COUNT_SMALL_WAVE) != 0;
-  CcoArgs pk = args, plain = args, small = args;
-  if ((count_direct && c.direct == 0u) || count_small) pk.cand = nullptr;
-  if (count_direct || count_small) plain.cand = nullptr;
-  if (count_direct) small.cand = nullptr;
+  const bool count_block = (args.debug & DBG_COUNT_BLOCK_SMALL_WAVE) != 0;
+  CcoArgs pk = args, plain = args, small = args, small2 = args;
+  if ((count_direct && c.direct == 0u) || count_small || count_block) pk.cand = nullptr;
+  if (count_direct || count_small || count_block) plain.cand = nullptr;
+  if (count_direct || count_block) small.cand = nullptr;
+  if (count_direct || count_small) small2.cand = nullptr;
+  if (count_block) {
+    const char* only = getenv("URCCO_COUNT_BLOCK_LIST");
+    if (only && *only && atoi(only) != bin) small2.cand = nullptr;
+  }
+  // the sub-lists of the small-row body exist under the binning pass's own rule (launch_binning: otherwise they are empty), and only the packed form runs them
+  const bool small_split = plan_runs_pk(plan) && micro_split_for(n_rows) && args.k <= SMALL_KMAX;
+  const bool block_small = small_split && !(args.debug & DBG_NO_BLOCK_SMALL_WAVE);
+  const int small2_bits = ((args.debug & DBG_COUNT_SCORED) ? 256 : 0) | (count_block ? 4096 : 0);
   // ride on the PK kernels' bin argument (grid-uniform; the production instantiations do not read CcoArgs::debug)
   const int pk_bits = ((args.debug & DBG_COUNT_SCORED) ? 256 : 0) | ((args.debug & DBG_NO_DIRECT_RANK) ? 512 : 0) | (count_direct ? 1024 : 0);
   // what the plan enqueues of one class (or micro sub-list), given its DBG, PK and plain instantiation; bin_arg: the bin argument of cco_rows_kernel
@@ -2555,12 +2626,20 @@ hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, Ro
   } else if (bin == NBINS - 1 && args.g_blocks > 0) {
     plain.b_packed = nullptr;  // (the dense kernel reads plain words whatever the plan)
     hipLaunchKernelGGL(cco_rows_global_kernel, dim3((unsigned)args.g_blocks), dim3(GB_THREADS), 0, st, plain);
-  } else if (bin == 1 && plan_runs_pk(plan) && micro_split_for(n_rows) && args.k <= SMALL_KMAX && !(args.debug & DBG_NO_SMALL_WAVE)) {
-    // the class's two sub-lists of small rows in the micro-shaped body (the same rule as the binning pass: otherwise they are empty), the rest in the general
-    // kernel (bit 11 of its bin argument); the plain instantiation -- a build whose counts do not fit -- keeps the whole class
+  } else if (bin == 1 && small_split && !(args.debug & DBG_NO_SMALL_WAVE)) {
+    // the class's sub-lists of small rows in the micro-shaped body -- two / four pairs per lane, then eight pairs and two users per lane --, the rest in the
+    // general kernel (bit 11 of its bin argument; with bit 13 it takes the third sub-list as well: DBG_NO_BLOCK_SMALL_WAVE); the plain instantiation -- a build
+    // whose counts do not fit -- keeps the whole class.  (DBG_NO_SMALL_WAVE keeps all of them in the general kernel: its list is one piece.)
     const int small_bits = ((args.debug & DBG_COUNT_SCORED) ? 256 : 0) | (count_small ? 4096 : 0);
-    hipLaunchKernelGGL(cco_rows_small_kernel<SMALL_P0>, grid(SMALL_FACTOR), dim3(c.block), 0, st, small, small_bits);
-    hipLaunchKernelGGL(cco_rows_small_kernel<SMALL_P1>, grid(SMALL_FACTOR), dim3(c.block), 0, st, small, small_bits);
+    hipLaunchKernelGGL((cco_rows_small_kernel<SMALL_P0, 1>), grid(SMALL_FACTOR), dim3(c.block), 0, st, small, small_bits);
+    hipLaunchKernelGGL((cco_rows_small_kernel<SMALL_P1, 1>), grid(SMALL_FACTOR), dim3(c.block), 0, st, small, small_bits);
+    if (block_small) hipLaunchKernelGGL((cco_rows_small_kernel<SMALL_P2, SMALL_U2>), grid(SMALL_FACTOR, SMALL_OCC_P2), dim3(c.block), 0, st, small2, small2_bits);
+    hipLaunchKernelGGL(c.pk, grid(c.factor), dim3(c.block), 0, st, pk, bin | pk_bits | 2048 | (block_small ? 0 : 8192));
+    if (plan_runs_plain(plan)) hipLaunchKernelGGL(c.plain, grid(c.factor), dim3(c.block), 0, st, plain, bin);
+  } else if (bin == 2 && block_small && !count_direct) {
+    // the class's first list -- rows of <= 128 users and <= 512 pairs -- in the same body (bit 13 of its flags), the rest in the class's own kernel (bit 11).
+    // (DBG_COUNT_DIRECT: the whole class in its own kernel, which has the direct ranking.)
+    hipLaunchKernelGGL((cco_rows_small_kernel<SMALL_P2, SMALL_U2>), grid(SMALL_FACTOR, SMALL_OCC_P2), dim3(256), 0, st, small2, small2_bits | 8192);
     hipLaunchKernelGGL(c.pk, grid(c.factor), dim3(c.block), 0, st, pk, bin | pk_bits | 2048);
     if (plan_runs_plain(plan)) hipLaunchKernelGGL(c.plain, grid(c.factor), dim3(c.block), 0, st, plain, bin);
   } else {
