@@ -18,10 +18,23 @@ constexpr int DS_TILE = 4096;            // entries per down-sample tile (256 th
 constexpr int GLOBAL_BIN_BLOCKS = 128;    // persistent blocks of the global-accumulator kernel (upper bound)
 constexpr int BIN_TILE = 1024;           // items per binning tile
 constexpr int XLX_TABLE_HOST = 4096;     // entries of the small-integer xLogX table (== XLX_TABLE in cco_device.h)
-constexpr int BIN_COLS_HOST = 3 * NBINS + 7;  // int64 per binning tile (rows per internal bin -- the micro class has three sub-lists, the one-wave class four, the small-block class two --, pairs and users per bin, total)
-constexpr int BIN_OFF_LEN = NBINS + 7;        // bin_off: [0 .. NBINS] list offsets of the classes, then the starts of the micro class's second and third sub-list,
-                                              // of the one-wave class's second, third and fourth (its rows of <= 256 pairs, of <= 128 users, the rest: cco_rows.hip, SMALL_SUBS)
-                                              // and of the small-block class's second (the rest behind its rows of <= 128 users and <= 512 pairs: BLOCK_SUBS)
+// The ROW LISTS, in the order they lie in bin_rows: a class (public bin) is one list or a run of consecutive ones, each with a kernel body of its own
+// (cco_rows.hip: the binning pass fills them, launch_cco_rows_bin names the kernel of each).  A build that is not split keeps a class in its last list.
+enum RowList : int {
+  NO_LIST = -1,                                               // an empty indicator row
+  LIST_MICRO16, LIST_MICRO32, LIST_MICRO,                     // bin 0: <= 16 / <= 32 pairs and users (four / two rows share a wave), the rest of the class
+  LIST_WAVE_P128, LIST_WAVE_P256, LIST_WAVE_U128, LIST_WAVE,  // bin 1: <= 64 users and <= 128 / <= 256 pairs, <= 128 users (the small-row body), the rest
+  LIST_BLOCKS_U128, LIST_BLOCKS,                              // bin 2: <= 128 users and <= 512 pairs (the small-row body), the rest
+  LIST_BLOCK, LIST_HALF_CU, LIST_CU, LIST_MULTI_PASS,         // bins 3 .. 6
+  N_ROW_LISTS
+};
+// the first list of every public bin: bin b is the lists [first_list(b), first_list(b + 1))
+__host__ __device__ constexpr int first_list(int bin) {
+  constexpr int first[NBINS + 1] = {LIST_MICRO16, LIST_WAVE_P128, LIST_BLOCKS_U128, LIST_BLOCK, LIST_HALF_CU, LIST_CU, LIST_MULTI_PASS, N_ROW_LISTS};
+  return first[bin];
+}
+constexpr int BIN_COLS_HOST = N_ROW_LISTS + 2 * NBINS + 1;  // int64 per binning tile: rows per list, pairs and users per bin, total pairs
+constexpr int BIN_OFF_LEN = N_ROW_LISTS + 1;                // bin_off: the exclusive prefix of the lists' lengths -- list l is bin_rows[bin_off[l] .. bin_off[l + 1])
 constexpr int CAND_SLOTS = 64;           // words the row kernels spread their candidate counts over (see CcoArgs::cand)
 constexpr int STATS_LEN = 32;            // [0] pairs, then NBINS each of rows / pairs / users / out entries per bin, [1 + 4 NBINS] table overflows,
                                          // [STATS_LEN - 1] rows binned into the micro class's two shared-wave sub-lists (0: the class ran as one list)

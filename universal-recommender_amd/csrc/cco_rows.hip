@@ -49,38 +49,43 @@ __device__ __forceinline__ int choose_bin(long long w, long long ca, int32_t n_c
   return cap_bin > work_bin ? cap_bin : work_bin;
 }
 
-// Round 6: the micro class in three sub-lists by row size -- rows of <= 16 pairs and users share a wave four at a time, rows of <= 32 two
-// at a time (see cco_rows_micro_kernel).  The binning works on INTERNAL bins (0, 1, 2 = the sub-lists, 3 .. = the other classes); towards
-// everything else the micro class stays one bin: bin_off[0 .. NBINS] as before, the sub-lists' starts behind it (bin_off[NBINS + 1], [NBINS + 2]).
-constexpr int MICRO_SUBS = 3;
-// The one-wave class (bin 1) in three sub-lists, by the same mechanism: rows of <= 64 users and <= 128 pairs, rows of <= 64 users and <= 256 pairs -- they run in
-// the micro-shaped body of cco_rows_small_kernel, two / four pairs per lane --, then the rest of the class.  Internal bins MICRO_SUBS, MICRO_SUBS + 1 and
-// MICRO_SUBS + 2; the first starts at bin_off[1], the other two at bin_off[NBINS + 3] and bin_off[NBINS + 4].  Unsplit (a small build, or a k the fast tail of
-// that body cannot serve: SMALL_KMAX) the sub-lists are empty and the rest starts at bin_off[1].
-// A third sub-list of the one-wave class, behind those two: what is left of the class with <= 128 users (<= 290 pairs at k = 50, <= 512 always) runs in the
-// same body with eight pairs and TWO users per lane; the few rows beyond stay in the general kernel.  Internal bins MICRO_SUBS + 2 (start: bin_off[NBINS + 4])
-// and MICRO_SUBS + 3 (the rest, start: bin_off[NBINS + 5]).  And the small-block class (bin 2) in two lists: its rows of <= 128 users and <= 512 pairs -- that
-// body again --, then the rest, which starts at bin_off[NBINS + 6] (BLOCK_SUBS).
-constexpr int SMALL_SUBS = 3;
-constexpr int BLOCK_SUBS = 1;
-constexpr int SMALL_P0 = 2, SMALL_P1 = 4, SMALL_P2 = 8;  // pairs per lane of the sub-lists
-constexpr int SMALL_U2 = 2;                               // users per lane of the sub-lists that run with SMALL_P2
+// The ROW LISTS (RowList, cco_kernels.h).  The binning pass sorts the rows of a build into N_ROW_LISTS lists that lie one behind the other in bin_rows;
+// bin_off is the exclusive prefix of their lengths, so list l is bin_rows[bin_off[l] .. bin_off[l + 1]) and public bin b the lists first_list(b) ..
+// first_list(b + 1) - 1.  Towards everything else a class stays ONE bin (stats, rows_by_accumulator); the lists inside it exist for the row kernels:
+//   list              rows (of its bin, that no list in front of it took)     kernel body
+//   LIST_MICRO16      <= 16 pairs and users                                   cco_rows_micro_kernel<16>: four rows share a wave
+//   LIST_MICRO32      <= 32 pairs and users                                   cco_rows_micro_kernel<32>: two rows share a wave
+//   LIST_MICRO        the rest of bin 0                                       cco_rows_micro_kernel<64>
+//   LIST_WAVE_P128    <= 64 users, <= 128 pairs                               cco_rows_small_kernel<2, 1>: two pairs per lane
+//   LIST_WAVE_P256    <= 64 users, <= 256 pairs                               cco_rows_small_kernel<4, 1>: four pairs per lane
+//   LIST_WAVE_U128    <= 128 users (<= 290 pairs at k = 50, <= 512 always)    cco_rows_small_kernel<8, 2>: eight pairs and two users per lane
+//   LIST_WAVE         the rest of bin 1                                       cco_rows_kernel<64, E0>
+//   LIST_BLOCKS_U128  <= 128 users, <= 512 pairs                              cco_rows_small_kernel<8, 2>
+//   LIST_BLOCKS       the rest of bin 2                                       cco_rows_kernel<256, E1S>
+//   LIST_BLOCK .. LIST_MULTI_PASS: bins 3 .. 6, one list each                 cco_rows_kernel<256, E1>, <512, E2S>, <1024, E2>, <1024, E2, MP> (or the dense global kernel)
+// A launch covers a contiguous run of lists [first, end), named in its `int` argument (list_span): a general kernel that takes over the lists in front of its
+// own (a debug bit, or the plain form of a build whose counts do not fit) simply starts earlier.  A class is split only under `split`: SPLIT_MICRO for a
+// build with enough item rows for the extra launches to pay (micro_split_for), SPLIT_SMALL when in addition the fast tail of the small-row body can serve k
+// (SMALL_KMAX); unsplit, the lists in front stay empty and the class's last list holds all of it.
+constexpr int SMALL_P0 = 2, SMALL_P1 = 4, SMALL_P2 = 8;  // pairs per lane of the small-row body's lists
+constexpr int SMALL_U2 = 2;                               // users per lane of the lists that run with SMALL_P2
 constexpr int SMALL_KMAX = WAVE - 1;       // the prefilter keeps >= k (+ 1 with a self pair) survivors whenever it cuts; the fast tail ranks <= 64, one per lane
 static_assert(SMALL_KMAX + 1 <= WAVE && SMALL_KMAX >= 1, "k + 1 survivors (a self pair among them) must fit the lanes of the fast tail");
 static_assert(SMALL_P2 * WAVE >= URCCO_WB1, "every row of the one-wave class fits eight pairs per lane");
-constexpr int IBINS = NBINS - 1 + MICRO_SUBS + SMALL_SUBS + BLOCK_SUBS;
 constexpr int SPLIT_MICRO = 1, SPLIT_SMALL = 2;  // bits of the binning kernels' `split`
+// which list of its class a row belongs to, counted from the class's first
 __device__ __forceinline__ int micro_sub(long long w, long long ca) { return (w <= 16 && ca <= 16) ? 0 : ((w <= 32 && ca <= 32) ? 1 : 2); }
 __device__ __forceinline__ int small_sub(long long w, long long ca) {
   return ca > SMALL_U2 * WAVE ? 3 : ((ca > WAVE || w > SMALL_P1 * WAVE) ? 2 : (w <= SMALL_P0 * WAVE ? 0 : 1));
 }
 __device__ __forceinline__ int block_sub(long long w, long long ca) { return (ca <= SMALL_U2 * WAVE && w <= SMALL_P2 * WAVE) ? 0 : 1; }
-__device__ __forceinline__ int internal_bin(int b, long long w, long long ca, int split) {
-  if (b < 0) return -1;
-  if (b == 0) return (split & SPLIT_MICRO) ? micro_sub(w, ca) : MICRO_SUBS - 1;
-  if (b == 1) return MICRO_SUBS + ((split & SPLIT_SMALL) ? small_sub(w, ca) : SMALL_SUBS);
-  if (b == 2) return MICRO_SUBS + SMALL_SUBS + 1 + ((split & SPLIT_SMALL) ? block_sub(w, ca) : BLOCK_SUBS);
-  return b + MICRO_SUBS - 1 + SMALL_SUBS + BLOCK_SUBS;
+static_assert(LIST_MICRO - LIST_MICRO16 == 2 && LIST_WAVE - LIST_WAVE_P128 == 3 && LIST_BLOCKS - LIST_BLOCKS_U128 == 1, "micro_sub / small_sub / block_sub number the lists of their class");
+__device__ __forceinline__ RowList internal_bin(int b, long long w, long long ca, int split) {
+  if (b < 0) return NO_LIST;
+  if (b == 0) return (split & SPLIT_MICRO) ? (RowList)(LIST_MICRO16 + micro_sub(w, ca)) : LIST_MICRO;
+  if (b == 1) return (split & SPLIT_SMALL) ? (RowList)(LIST_WAVE_P128 + small_sub(w, ca)) : LIST_WAVE;
+  if (b == 2) return (split & SPLIT_SMALL) ? (RowList)(LIST_BLOCKS_U128 + block_sub(w, ca)) : LIST_BLOCKS;
+  return (RowList)first_list(b);
 }
 // The micro class is split into its sub-lists only when the build has enough item rows for three launches to pay: a rank of a sharded build (an eighth
 // of config 4's rows) would start 16K waves per sub-list for a handful of passes each (emulated 8-rank build: 3.45 against 3.17 ms of SpGEMM per rank).
@@ -89,24 +94,18 @@ static bool micro_split_for(int32_t n_rows) {
   static const long long min_rows = [] { const char* e = getenv("URCCO_MICRO_SPLIT_ROWS"); return e && *e ? atoll(e) : 1000000ll; }();
   return (long long)n_rows >= min_rows;
 }
-// where the list of internal bin ib starts, as an index into bin_off
-__host__ __device__ constexpr int internal_off_index(int ib) {
-  constexpr int B2 = MICRO_SUBS + SMALL_SUBS + 1;  // the small-block class's first list
-  return ib == 0 ? 0
-                 : (ib < MICRO_SUBS ? NBINS + ib
-                                    : (ib == MICRO_SUBS ? 1
-                                                        : (ib < B2 ? NBINS + ib - 1
-                                                                   : (ib == B2 ? 2 : (ib <= B2 + BLOCK_SUBS ? NBINS + ib - 2 : ib - (MICRO_SUBS - 1 + SMALL_SUBS + BLOCK_SUBS))))));
-}
-constexpr int OFF_SMALL_P1 = NBINS + 3, OFF_SMALL_U2 = NBINS + 4, OFF_WAVE_REST = NBINS + 5, OFF_BLOCK_REST = NBINS + 6;  // the sub-lists' starts in bin_off
-static_assert(internal_off_index(MICRO_SUBS + 1) == OFF_SMALL_P1 && internal_off_index(MICRO_SUBS + 2) == OFF_SMALL_U2 && internal_off_index(MICRO_SUBS + 3) == OFF_WAVE_REST &&
-              internal_off_index(MICRO_SUBS + 4) == 2 && internal_off_index(MICRO_SUBS + 5) == OFF_BLOCK_REST && internal_off_index(MICRO_SUBS + 6) == 3 &&
-              internal_off_index(IBINS - 1) == NBINS - 1 && OFF_BLOCK_REST == BIN_OFF_LEN - 1, "bin_off layout");
-__device__ __forceinline__ int internal_start(const int32_t* __restrict__ bin_off, int ib) { return bin_off[internal_off_index(ib)]; }
+// A launch's `int` argument: the run of lists it covers in the low 16 bits, the run-time switches of the production kernels (which do not read
+// CcoArgs::debug) above them.  One meaning per bit, whichever kernel reads it.
+__host__ __device__ constexpr int list_span(int first, int end) { return first | (end << 8); }
+__device__ __forceinline__ int span_start(const int32_t* __restrict__ bin_off, int arg) { return bin_off[arg & 255]; }
+__device__ __forceinline__ int span_end(const int32_t* __restrict__ bin_off, int arg) { return bin_off[(arg >> 8) & 255]; }
+constexpr int ROWS_COUNT_SCORED = 1 << 16;  // the statistics count the candidates that were SCORED, not the distinct ones (DBG_COUNT_SCORED)
+constexpr int ROWS_NO_DIRECT = 1 << 17;     // no direct ranking (DBG_NO_DIRECT_RANK)
+constexpr int ROWS_COUNT_DIRECT = 1 << 18;  // the statistics count the ROWS that were ranked directly (DBG_COUNT_DIRECT)
+constexpr int ROWS_COUNT_BODY = 1 << 19;    // the statistics count the ROWS of the small-row body, + 2^32 per row that took its fallback (DBG_COUNT_SMALL_WAVE, DBG_COUNT_BLOCK_SMALL_WAVE)
 constexpr int BIN_THREADS = 256;
 constexpr int BIN_ITEMS = BIN_TILE / BIN_THREADS;  // 4
-constexpr int BIN_COLS = IBINS + 2 * NBINS + 1;    // per tile: rows per INTERNAL bin, pairs per bin, users per bin, total pairs
-static_assert(BIN_COLS == BIN_COLS_HOST && BIN_OFF_LEN == NBINS + MICRO_SUBS + SMALL_SUBS + BLOCK_SUBS, "scratch sizes of the callers");
+constexpr int BIN_COLS = BIN_COLS_HOST;            // per tile: rows per list, pairs per bin, users per bin, total pairs
 
 __global__ __launch_bounds__(BIN_THREADS) void bin_count_kernel(int32_t item_lo, int32_t n, const int64_t* __restrict__ work,
                                                                 const int32_t* __restrict__ cnt_a, int32_t n_cols_b, int32_t count_bits, int32_t k,
@@ -114,10 +113,10 @@ __global__ __launch_bounds__(BIN_THREADS) void bin_count_kernel(int32_t item_lo,
   __shared__ long long s_acc[BIN_COLS];
   if (threadIdx.x < BIN_COLS) s_acc[threadIdx.x] = 0;
   __syncthreads();
-  int c[IBINS];
+  int c[N_ROW_LISTS];
   long long pw[NBINS], pu[NBINS];
 #pragma unroll
-  for (int k = 0; k < IBINS; ++k) c[k] = 0;
+  for (int k = 0; k < N_ROW_LISTS; ++k) c[k] = 0;
 #pragma unroll
   for (int k = 0; k < NBINS; ++k) { pw[k] = 0; pu[k] = 0; }
   long long pairs = 0;
@@ -129,9 +128,9 @@ __global__ __launch_bounds__(BIN_THREADS) void bin_count_kernel(int32_t item_lo,
       const long long ca = cnt_a[item_lo + t];
       pairs += w;
       const int b = choose_bin(w, ca, n_cols_b, count_bits, k);
-      const int ib = internal_bin(b, w, ca, split);
+      const RowList l = internal_bin(b, w, ca, split);
 #pragma unroll
-      for (int k = 0; k < IBINS; ++k) c[k] += (ib == k);
+      for (int k = 0; k < N_ROW_LISTS; ++k) c[k] += (l == k);
 #pragma unroll
       for (int k = 0; k < NBINS; ++k) {
         pw[k] += (b == k) ? w : 0;
@@ -140,28 +139,28 @@ __global__ __launch_bounds__(BIN_THREADS) void bin_count_kernel(int32_t item_lo,
     }
   }
 #pragma unroll
-  for (int k = 0; k < IBINS; ++k)
+  for (int k = 0; k < N_ROW_LISTS; ++k)
     if (c[k]) atomicAdd((unsigned long long*)&s_acc[k], (unsigned long long)c[k]);
 #pragma unroll
   for (int k = 0; k < NBINS; ++k)
     if (pu[k]) {
-      atomicAdd((unsigned long long*)&s_acc[IBINS + k], (unsigned long long)pw[k]);
-      atomicAdd((unsigned long long*)&s_acc[IBINS + NBINS + k], (unsigned long long)pu[k]);
+      atomicAdd((unsigned long long*)&s_acc[N_ROW_LISTS + k], (unsigned long long)pw[k]);
+      atomicAdd((unsigned long long*)&s_acc[N_ROW_LISTS + NBINS + k], (unsigned long long)pu[k]);
     }
-  if (pairs) atomicAdd((unsigned long long*)&s_acc[IBINS + 2 * NBINS], (unsigned long long)pairs);
+  if (pairs) atomicAdd((unsigned long long*)&s_acc[N_ROW_LISTS + 2 * NBINS], (unsigned long long)pairs);
   __syncthreads();
   if (threadIdx.x < BIN_COLS) tile_counts[(int64_t)blockIdx.x * BIN_COLS + threadIdx.x] = s_acc[threadIdx.x];
 }
 
 // single block: per-column exclusive scan over the tiles (in place), totals -> bin_off / stats.  One wave per column of
-// the tile table (rows per internal bin, pairs / users per bin, total pairs), 16 columns at a time.
+// the tile table (rows per list, pairs / users per bin, total pairs), 16 columns at a time.
 constexpr int BS_THREADS = 1024;
 __global__ __launch_bounds__(BS_THREADS) void bin_scan_kernel(int64_t* __restrict__ tile_counts, int64_t n_tiles, int32_t* __restrict__ bin_off,
                                                               int64_t* __restrict__ stats) {
   __shared__ long long s_tot[BIN_COLS];
   const int lane = threadIdx.x & (WAVE - 1), wave = threadIdx.x / WAVE;
   for (int k = wave; k < BIN_COLS; k += BS_THREADS / WAVE) {  // wave-uniform
-    if (k >= IBINS) {
+    if (k >= N_ROW_LISTS) {
       // pairs / users / total columns: only their TOTALS are used (statistics) -- a plain sum, every lane four loads deep, one reduction at the
       // end (rounds 1-4 ran the same carried shuffle scan over all 22 columns and wrote 15 prefixes nobody read: 54 us per event type)
       long long acc = 0;
@@ -201,24 +200,21 @@ __global__ __launch_bounds__(BS_THREADS) void bin_scan_kernel(int64_t* __restric
   __syncthreads();
   if (threadIdx.x == 0) {
     int32_t off = 0;
-    for (int ib = 0; ib < IBINS; ++ib) {  // list order = internal bin order: the micro sub-lists, the one-wave class's, then the other classes
-      bin_off[internal_off_index(ib)] = off;
-      off += (int32_t)s_tot[ib];
+    for (int l = 0; l < N_ROW_LISTS; ++l) {  // the exclusive prefix in list order
+      bin_off[l] = off;
+      off += (int32_t)s_tot[l];
     }
-    bin_off[NBINS] = off;
+    bin_off[N_ROW_LISTS] = off;
     if (stats) {
       for (int k = 0; k < NBINS; ++k) {
         long long rows = 0;
-        if (k == 0) for (int q = 0; q < MICRO_SUBS; ++q) rows += s_tot[q];
-        else if (k == 1) for (int q = 0; q <= SMALL_SUBS; ++q) rows += s_tot[MICRO_SUBS + q];
-        else if (k == 2) for (int q = 0; q <= BLOCK_SUBS; ++q) rows += s_tot[MICRO_SUBS + SMALL_SUBS + 1 + q];
-        else rows = s_tot[k + MICRO_SUBS - 1 + SMALL_SUBS + BLOCK_SUBS];
+        for (int l = first_list(k); l < first_list(k + 1); ++l) rows += s_tot[l];
         stats[1 + k] = rows;                                      // rows
-        stats[1 + NBINS + k] = s_tot[IBINS + k];                  // pairs
-        stats[1 + 2 * NBINS + k] = s_tot[IBINS + NBINS + k];      // users (sum of cA over the bin's rows)
+        stats[1 + NBINS + k] = s_tot[N_ROW_LISTS + k];                  // pairs
+        stats[1 + 2 * NBINS + k] = s_tot[N_ROW_LISTS + NBINS + k];      // users (sum of cA over the bin's rows)
       }
-      stats[0] = s_tot[IBINS + 2 * NBINS];
-      stats[STATS_LEN - 1] = s_tot[0] + s_tot[1];                 // rows of the two shared-wave sub-lists: 0 = the micro class ran as one list
+      stats[0] = s_tot[N_ROW_LISTS + 2 * NBINS];
+      stats[STATS_LEN - 1] = s_tot[LIST_MICRO16] + s_tot[LIST_MICRO32];  // rows of the two shared-wave sub-lists: 0 = the micro class ran as one list
     }
   }
 }
@@ -228,22 +224,22 @@ __global__ __launch_bounds__(BIN_THREADS) void bin_scatter_kernel(int32_t item_l
                                                                   const int64_t* __restrict__ tile_counts, const int32_t* __restrict__ bin_off,
                                                                   int32_t* __restrict__ bin_rows, int split) {
   __shared__ long long s_wave[SCAN_THREADS / WAVE];
-  int b[BIN_ITEMS];
+  int b[BIN_ITEMS];  // the items' lists
 #pragma unroll
   for (int q = 0; q < BIN_ITEMS; ++q) {
     const int64_t t = (int64_t)blockIdx.x * BIN_TILE + (int64_t)threadIdx.x * BIN_ITEMS + q;
-    b[q] = -1;
+    b[q] = NO_LIST;
     if (t < n) {
       const long long w = work[t], ca = cnt_a[item_lo + t];
       b[q] = internal_bin(choose_bin(w, ca, n_cols_b, count_bits, k), w, ca, split);
     }
   }
-  for (int k = 0; k < IBINS; ++k) {  // block-uniform: one block scan per internal bin
+  for (int k = 0; k < N_ROW_LISTS; ++k) {  // block-uniform: one block scan per list
     int c = 0;
 #pragma unroll
     for (int q = 0; q < BIN_ITEMS; ++q) c += (b[q] == k);
     long long tot;
-    long long pos = block_exclusive_scan(c, s_wave, &tot) + tile_counts[(int64_t)blockIdx.x * BIN_COLS + k] + internal_start(bin_off, k);
+    long long pos = block_exclusive_scan(c, s_wave, &tot) + tile_counts[(int64_t)blockIdx.x * BIN_COLS + k] + bin_off[k];
 #pragma unroll
     for (int q = 0; q < BIN_ITEMS; ++q)
       if (b[q] == k) bin_rows[pos++] = item_lo + (int32_t)((int64_t)blockIdx.x * BIN_TILE + (int64_t)threadIdx.x * BIN_ITEMS + q);
@@ -328,6 +324,18 @@ __device__ __forceinline__ double llr_of(double row_entropy, double xlx_n, long 
                                          const double* __restrict__ xlx_tab, const double* __restrict__ xlx_hi, const double* __restrict__ col_ent) {
   return llr_from_entropies_tab(row_entropy, column_entropy_of(cb, xlx_n, n_users, xlx_tab, xlx_hi, col_ent), xlx_n, k11, ca - k11, cb - k11, n_users - ca - cb + k11, xlx_tab,
                                 n_users, xlx_hi);
+}
+
+// One candidate's key: the bits of its LLR, or 0 -- the self pair of A'A, an LLR that is not positive or lies below minLLR.  in_tables: the table form, as
+// the CALLER chose it (wave-uniform at a straight-line site, see llr_from_tables; per lane elsewhere).  (cco_rows_kernel and cco_rows_micro_kernel, which
+// also carry the DBG ablations here, keep this step written out: through the helper their registers moved -- DESIGN.md, "Row lists".)
+__device__ __forceinline__ unsigned long long score_key(bool self_pair, bool in_tables, double row_entropy, double xlx_n, long long k11, long long ca, long long cb, long long n_users,
+                                                        const double* __restrict__ xlx_tab, const double* __restrict__ xlx_hi, const double* __restrict__ col_ent,
+                                                        int has_min_llr, double min_llr) {
+  if (self_pair) return 0ull;
+  const double llr = in_tables ? llr_from_tables(row_entropy, xlx_n, (unsigned)k11, (unsigned)ca, (unsigned)cb, xlx_tab, xlx_hi, col_ent)
+                               : llr_of(row_entropy, xlx_n, k11, ca, cb, n_users, xlx_tab, xlx_hi, col_ent);
+  return (llr > 0.0 && (!has_min_llr || llr >= min_llr)) ? (unsigned long long)__double_as_longlong(llr) : 0ull;
 }
 
 // r += [(ka, ca) sorts before (mk, mc)] -- key desc, column asc -- as the final borrow of a three-word subtraction chain: [ca < mc] enters
@@ -689,9 +697,11 @@ __device__ __forceinline__ bool pf_drops(unsigned k11, unsigned cbq, unsigned cs
 template <bool NARROW> struct PStart { typedef int64_t type; };
 template <> struct PStart<true> { typedef unsigned type; };
 template <int T, int E, int U, bool MP = false, bool DBG = false, bool PK = false>
-__global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T == 256 && E == 4096 ? URCCO_OCC_BS : (T == 512 ? 4 : 1)))) void cco_rows_kernel(CcoArgs a, int bin_arg) {
-  const int bin = bin_arg & 255;  // (bit 8: the statistics count the candidates that were SCORED -- DBG_COUNT_SCORED --, not the distinct ones;
-                                  // bit 9: no direct ranking -- DBG_NO_DIRECT_RANK --; bit 10: they count the ROWS that were ranked directly -- DBG_COUNT_DIRECT)
+__global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T == 256 && E == 4096 ? URCCO_OCC_BS : (T == 512 ? 4 : 1)))) void cco_rows_kernel(CcoArgs a, int flags) {  // flags: the launch's lists (list_span) and the ROWS_* switches
+  // the launch's rows (the lists of the class that run in cco_rows_small_kernel lie in front of them).  Read ahead of everything else: behind the argument
+  // pointers below, where the scalar registers are scarcest, the two loads cost the plain one-wave instantiation one more spilled vector register
+  const int list_start = span_start(a.bin_off, flags);
+  const int list_n = span_end(a.bin_off, flags) - list_start;
   // (the same verdict names the form of the expand tables -- CcoArgs::form: this instantiation reads the narrow ones, the plain one the wide ones)
   if ((a.b_packed != nullptr && (a.pk_known != 0 || *a.form == 0)) != PK) return;  // grid-uniform
   using PS = typename PStart<PK>::type;  // a start of a B' row: 32 bits in the narrow form
@@ -788,12 +798,6 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
   unsigned* pfh = (SHARE && T != WAVE) ? reinterpret_cast<unsigned*>(share) + T : hist;
   constexpr unsigned DL = PF ? direct_limit(T, E) : 0u;  // the direct ranking: only the instantiations that carry the prefilter, 0 = none
   static_assert(DL <= (unsigned)SEL_M, "a directly ranked row lives in the ambiguous-set arrays");
-  // (bit 11 of the bin argument, one-wave PK instantiation only: the class's sub-lists of small rows run in cco_rows_small_kernel -- this kernel takes the rest)
-  // (with bit 13 as well it also takes the class's third sub-list, which lies just ahead of the rest -- DBG_NO_BLOCK_SMALL_WAVE; bit 11 of the small-block PK
-  // instantiation: the class's first list runs in that body, this kernel takes the rest)
-  const int list_start = (T == WAVE && PK && !MP && (bin_arg & 2048)) ? a.bin_off[(bin_arg & 8192) ? OFF_SMALL_U2 : OFF_WAVE_REST]
-                         : ((T == 256 && E == E1S && PK && !MP && (bin_arg & 2048)) ? a.bin_off[OFF_BLOCK_REST] : a.bin_off[bin]);
-  const int list_n = a.bin_off[bin + 1] - list_start;
   const int total_teams = gridDim.x * TEAMS;
   bool ident =(long long)a.n_cols_b * 3 + (long long)a.k * 3 + 2 <= E && a.n_cols_b <= SH;  // the table spans every column of B: slots addressed by column
   int cb = a.count_bits;                                                   // (MP: both follow the row's pass count)
@@ -1079,7 +1083,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
             ++pos;
           }
         }
-        if (!(bin_arg & (256 | 1024))) cand_acc += D - Dn;  // (statistics: the distinct candidates, unless the scored ones -- or the directly ranked rows -- are asked for)
+        if (!(flags & (ROWS_COUNT_SCORED | ROWS_COUNT_DIRECT))) cand_acc += D - Dn;  // (statistics: the distinct candidates, unless the scored ones -- or the directly ranked rows -- are asked for)
         D = Dn;
       } else {
       unsigned long long* kk0 = reinterpret_cast<unsigned long long*>(tab + ((D + 1u) & ~1u));
@@ -1108,7 +1112,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
         goto mp_again;
       }
     }
-    if (DL == 0u || !(bin_arg & 1024)) cand_acc += D;
+    if (DL == 0u || !(flags & ROWS_COUNT_DIRECT)) cand_acc += D;
     unsigned long long* kk = reinterpret_cast<unsigned long long*>(tab + ((D + 1u) & ~1u));
     // ---- 4. score candidates tl, tl + T, ... (dense); keys go to LDS behind the packed counts
     unsigned n_valid = 0;
@@ -1206,9 +1210,9 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
         // cut count, the few with k11 >= 2, the few beyond the monotone limit.  When all C of them fit the ambiguous-set arrays the select decides nothing
         // the final ranking does not decide anyway: the row enters the select's `merged` finish below at once, with "every valid candidate" as the set --
         // the same ranking by the same 96-bit composite (key desc, column asc), ranks < k are the row --, and skips the shared-byte sweep, the zeroing of
-        // the histograms, every pass and every digit search.  (C > k, a class that carries the prefilter, ordered rows; bit 9 of the bin argument switches
+        // the histograms, every pass and every digit search.  (C > k, a class that carries the prefilter, ordered rows; ROWS_NO_DIRECT switches
         // it off: the A/B and the tests' bit-for-bit comparison.)
-        const bool direct = DL != 0u && C <= DL && !a.unordered && !(bin_arg & 512);  // team-uniform
+        const bool direct = DL != 0u && C <= DL && !a.unordered && !(flags & ROWS_NO_DIRECT);  // team-uniform
         if (!direct) {
         if (!SKIP_SHARED) {
           // The classes that do not track the shared key bytes while they score (registers) find them here, with one cheap sweep over
@@ -1413,7 +1417,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
               int kout = a.k;
               URCCO_OPAQUE(kout);  // (likewise: the hoisted vector copy of k was spilled, and reloaded behind the row's stores)
               if (tl == 0) a.out_count[i - a.item_lo] = kout;
-              if (direct && (bin_arg & 1024)) cand_acc += 1ull;  // (statistics: the rows ranked directly, when those are asked for)
+              if (direct && (flags & ROWS_COUNT_DIRECT)) cand_acc += 1ull;  // (statistics: the rows ranked directly, when those are asked for)
               row_done = true;
               break;
             }
@@ -1572,7 +1576,7 @@ __global__ __launch_bounds__((T < 256 ? 256 : T), (T == 64 ? URCCO_OCC_WAVE : (T
 //  * few candidates are ranked by two or four replicas of the candidates that each count every second (fourth) element.
 // Round 6: S ROWS PER WAVE.  The average micro row of config 4 holds 33 pairs -- half of the wave's lanes idled through ~310 vector
 // instructions --, 61 % of the class's rows hold <= 32 pairs and users and 33 % <= 16.  The binning pass sorts the class into three
-// sub-lists (bin_off[NBINS + 1], [NBINS + 2]); rows of the first share a wave four at a time (S = 4, 16 lanes and 64 accumulator words
+// lists (LIST_MICRO16, LIST_MICRO32, LIST_MICRO); rows of the first share a wave four at a time (S = 4, 16 lanes and 64 accumulator words
 // each), rows of the second two at a time, the rest keep a wave to themselves.  A sub-row is a SEGMENT of L = 64 / S lanes: everything
 // per row (ids, bounds, operands, counts, entropy, output base) is a per-lane value that is uniform inside a segment; prefix maxima
 // stop at segment boundaries (the DPP row broadcasts that would cross them are left out), ballots are masked to the segment, lane
@@ -1621,10 +1625,69 @@ __device__ __forceinline__ unsigned seg_max_popc(unsigned long long m) {
   return best;
 }
 
+// THE RANKING TAIL of the micro-shaped row bodies (cco_rows_micro_kernel<L>; cco_rows_small_kernel with L = WAVE): a row's n <= L elements, one per lane of its
+// segment of L lanes -- columns `cand`, keys `kkm`, padded behind the n elements for the ranking loops; this lane's own in (mk, col), mk = 0: none, or not
+// valid -- become the row's output.  valid_seg: the lanes of the segment with a valid element; n_max: the largest n of the wave's rows (wave-uniform: the loop
+// bounds); emit_all (wave-uniform): unordered rows whose valid elements all fit k.  settle_prefetch: the caller's prefetches for the rows ahead are collected
+// ahead of the row's stores.
+template <int L, class Settle>
+__device__ __forceinline__ void rank_tail(unsigned* cand, unsigned long long* kkm, unsigned n, unsigned n_max, unsigned long long mk, int col, unsigned long long valid_seg,
+                                          bool emit_all, int k, int sl, bool counts, int32_t* out_idx, double* out_llr, int64_t obase, int32_t* out_count, Settle settle_prefetch) {
+  const int n_valid = __popcll(valid_seg);
+  if (emit_all) {  // every valid element is emitted: no ranking needed (wave-uniform)
+    settle_prefetch();
+    if (mk != 0ull) {
+      const unsigned opos = lanes_below(valid_seg);
+      out_idx[obase + opos] = col;
+      out_llr[obase + opos] = __longlong_as_double((long long)mk);
+    }
+    if (counts) *out_count = n_valid;
+    return;
+  }
+  // elements dense by lane, replicated while they fit twice / four times into the row's segment: replica q counts elements q, q + R, ...
+  unsigned rank;
+  unsigned long long rk;
+  unsigned rc;
+  unsigned ln = (unsigned)sl;
+  URCCO_OPAQUE(ln);  // the per-lane LDS addresses of the three forms are computed here, not kept across the row loop
+  if (n_max <= (unsigned)(L / 4)) {  // wave-uniform
+    const unsigned c = ln & (unsigned)(L / 4 - 1);
+    rk = kkm[c];
+    rc = cand[c];
+    rank = rank_by_counting_strided<4>(kkm, cand, ln / (unsigned)(L / 4), (n_max + 3u) & ~3u, rk, rc);
+    rank += (unsigned)__shfl_xor((int)rank, L / 4);
+    rank += (unsigned)__shfl_xor((int)rank, L / 2);
+  } else if (n_max <= (unsigned)(L / 2)) {
+    const unsigned c = ln & (unsigned)(L / 2 - 1);
+    rk = kkm[c];
+    rc = cand[c];
+    rank = rank_by_counting_strided<2>(kkm, cand, ln / (unsigned)(L / 2), (n_max + 1u) & ~1u, rk, rc);
+    rank += (unsigned)__shfl_xor((int)rank, L / 2);
+  } else {
+    rk = kkm[ln];
+    rc = cand[ln];
+    rank = rank_by_counting_strided<1>(kkm, cand, 0u, n_max, rk, rc);
+  }
+  // the row is put in order in LDS (every lane has its element in registers: in place) and leaves as contiguous stores
+  wave_sync();
+  const unsigned n_out = (unsigned)(n_valid < k ? n_valid : k);
+  if ((unsigned)sl < n && rk != 0ull && rank < n_out) {
+    cand[rank] = rc;
+    kkm[rank] = rk;
+  }
+  wave_sync();
+  settle_prefetch();
+  if ((unsigned)sl < n_out) {
+    out_idx[obase + sl] = (int)cand[sl];
+    out_llr[obase + sl] = __longlong_as_double((long long)kkm[sl]);
+  }
+  if (counts) *out_count = (int)n_out;
+}
+
 __device__ __forceinline__ unsigned gather_start(unsigned v, unsigned src) { return wave_gather(v, src); }
 __device__ __forceinline__ int64_t gather_start(int64_t v, unsigned src) { return wave_gather64(v, src); }
 template <int L, bool DBG, bool PK = false>
-__global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO - 2)) void cco_rows_micro_kernel(CcoArgs a) {
+__global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO - 2)) void cco_rows_micro_kernel(CcoArgs a, int flags) {  // flags: the launch's lists (list_span)
   if ((a.b_packed != nullptr && (a.pk_known != 0 || *a.form == 0)) != PK) return;  // grid-uniform: the other instantiation's turn (see cco_rows_kernel)
   using PS = typename PStart<PK>::type;
   constexpr int WS = PK ? 1 : 2;
@@ -1666,9 +1729,8 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
   unsigned* cand = tab_w + 256 + seg * G::ROW_WORDS;
   unsigned long long* kkm = reinterpret_cast<unsigned long long*>(cand + G::LIST);
   unsigned* marks = cand + 3 * G::LIST;
-  // this instantiation's sub-list of the class: rows of <= 16 / <= 32 / <= 64 pairs and users (bin_off, see the binning pass)
-  const int list_start = L == 16 ? a.bin_off[0] : a.bin_off[NBINS + (L == 32 ? 1 : 2)];
-  const int list_n = (L == 16 ? a.bin_off[NBINS + 1] : (L == 32 ? a.bin_off[NBINS + 2] : a.bin_off[1])) - list_start;
+  const int list_start = span_start(a.bin_off, flags);  // the launch's list of the class: rows of <= 16 / <= 32 / <= 64 pairs and users (see the binning pass)
+  const int list_n = span_end(a.bin_off, flags) - list_start;
   const int n_groups = (list_n + S - 1) / S;  // a wave takes S consecutive rows of the list at a time
   const int total_teams = gridDim.x * TEAMS;
   const bool ident = a.n_cols_b <= G::TW;
@@ -1807,61 +1869,14 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
     }
     wave_sync();
     const unsigned long long valid_mask = __ballot(mk != 0ull);
-    const int n_valid = __popcll(valid_mask & seg_mask);
     const bool all_fit_k = (int)seg_max_popc<L>(valid_mask) <= a.k;  // wave-uniform
     auto settle_prefetch = [&]() {  // the next row's operands have had the score phase to arrive: collect them before the output stores
       URCCO_SETTLE(pf_w1); URCCO_SETTLE(pf_wp); URCCO_SETTLE(pf_start); URCCO_SETTLE(pf_ca); URCCO_SETTLE(pf_ent);
       URCCO_SETTLE(cs2); URCCO_SETTLE(ce2); URCCO_SETTLE(i_n3);
     };
-    if (a.unordered && all_fit_k && !(dbg & DBG_NO_TOPK)) {  // every candidate is emitted: no ranking needed (wave-uniform)
-      const int64_t obase = ((int64_t)(i - a.item_lo)) * a.k;
-      settle_prefetch();
-      if (mk != 0ull) {
-        const unsigned opos = lanes_below(valid_mask & seg_mask);
-        out_idx[obase + opos] = (int)(vv >> cb) - 1;
-        out_llr[obase + opos] = __longlong_as_double((long long)mk);
-      }
-      if (sl == 0 && live) out_count[i - a.item_lo] = n_valid;
-    } else if (!(dbg & DBG_NO_TOPK)) {
-      const int64_t obase = ((int64_t)(i - a.item_lo)) * a.k;
-      // candidates dense by lane, replicated while they fit twice / four times into the row's segment: replica q counts elements q, q + R, ...
-      unsigned rank;
-      unsigned long long rk;
-      unsigned rc;
-      unsigned ln = (unsigned)sl;
-      URCCO_OPAQUE(ln);  // the per-lane LDS addresses of the three forms are computed here, not kept across the row loop
-      if (D_max <= (unsigned)(L / 4)) {  // wave-uniform
-        const unsigned c = ln & (unsigned)(L / 4 - 1);
-        rk = kkm[c];
-        rc = cand[c];
-        rank = rank_by_counting_strided<4>(kkm, cand, ln / (unsigned)(L / 4), (D_max + 3u) & ~3u, rk, rc);
-        rank += (unsigned)__shfl_xor((int)rank, L / 4);
-        rank += (unsigned)__shfl_xor((int)rank, L / 2);
-      } else if (D_max <= (unsigned)(L / 2)) {
-        const unsigned c = ln & (unsigned)(L / 2 - 1);
-        rk = kkm[c];
-        rc = cand[c];
-        rank = rank_by_counting_strided<2>(kkm, cand, ln / (unsigned)(L / 2), (D_max + 1u) & ~1u, rk, rc);
-        rank += (unsigned)__shfl_xor((int)rank, L / 2);
-      } else {
-        rk = kkm[ln];
-        rc = cand[ln];
-        rank = rank_by_counting_strided<1>(kkm, cand, 0u, D_max, rk, rc);
-      }
-      // the row is put in order in LDS (every lane has its element in registers: in place) and leaves as contiguous stores
-      wave_sync();
-      const unsigned n_out = (unsigned)(n_valid < a.k ? n_valid : a.k);
-      if ((unsigned)sl < D && rk != 0ull && rank < n_out) {
-        cand[rank] = rc;
-        kkm[rank] = rk;
-      }
-      wave_sync();
-      settle_prefetch();
-      if ((unsigned)sl < n_out) {
-        out_idx[obase + sl] = (int)cand[sl];
-        out_llr[obase + sl] = __longlong_as_double((long long)kkm[sl]);
-      }
-      if (sl == 0 && live) out_count[i - a.item_lo] = (int)n_out;
+    if (!(dbg & DBG_NO_TOPK)) {
+      rank_tail<L>(cand, kkm, D, D_max, mk, (int)(vv >> cb) - 1, valid_mask & seg_mask, a.unordered && all_fit_k, a.k, sl, sl == 0 && live, out_idx, out_llr,
+                   ((int64_t)(i - a.item_lo)) * a.k, out_count + (i - a.item_lo), settle_prefetch);
     } else {
       settle_prefetch();
     }
@@ -1876,7 +1891,7 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
 }
 
 // --------------------------------------------------------------------------------------------
-// Small rows of the one-wave class (bin 1): <= 64 users and <= 64 P cooccurrence pairs, P = 2 or 4 -- the class's first two sub-lists (SMALL_SUBS).  The
+// Small rows of the one-wave class (bin 1): <= 64 users and <= 64 P cooccurrence pairs, P = 2 or 4 -- the class's first two lists (LIST_WAVE_P128, LIST_WAVE_P256).  The
 // general kernel charges such a row its whole machinery -- a chunk loop with LDS staging, a six-step binary search per lane, a candidate list, a compaction
 // sweep, the select -- for one or two wave-iterations of pairs.  This is the micro class's row body with P pairs per lane (packed B' only: a build whose
 // counts do not fit runs the whole class in the plain instantiation of cco_rows_kernel):
@@ -1901,8 +1916,7 @@ __global__ __launch_bounds__(256, (L == WAVE ? URCCO_OCC_MICRO : URCCO_OCC_MICRO
 // <= 1/2) -- in the fallback the staged packed words [512] | cB, then columns [512], the digit histogram [128] and the tail's list [3 x 68] over the packed
 // words --; [1024, 2048) by phase: marks [64 P + 2 = 514] | the prefilter's histogram [128], the fast tail's staged survivors [2 x 64], columns [68] and
 // keys [68] | the fallback's keys [512 of 64 bits].  32 KiB per block, five blocks per CU (77 VGPRs, no scratch).
-// flags: bit 8 -- the statistics count the candidates that were SCORED (DBG_COUNT_SCORED); bit 12 -- they count the ROWS of this body, + 2^32 per row that took
-// the fallback (DBG_COUNT_SMALL_WAVE; for the eight-pair form DBG_COUNT_BLOCK_SMALL_WAVE); bit 13, eight-pair form -- the list is the small-block class's.
+// flags: the launch's list (list_span: the eight-pair form serves LIST_WAVE_U128 and LIST_BLOCKS_U128), ROWS_COUNT_SCORED and ROWS_COUNT_BODY.
 // --------------------------------------------------------------------------------------------
 __host__ __device__ constexpr int small_log2tw(int P) { return P <= SMALL_P1 ? 9 : 10; }  // accumulator words per row: 512, or 1024 with eight pairs per lane
 constexpr int SMALL_LIST = WAVE + 4;             // the fast tail's columns / keys (with room for the padding of the ranking loops)
@@ -1948,10 +1962,8 @@ __global__ __launch_bounds__(256, (P == SMALL_P2 ? SMALL_OCC_P2 : URCCO_OCC_MICR
   unsigned* cand = st_c + WAVE;
   unsigned long long* kkm = reinterpret_cast<unsigned long long*>(cand + SMALL_LIST);
   unsigned long long* fkeys = reinterpret_cast<unsigned long long*>(marks);
-  // the sub-list: by shape, and for the eight-pair form by bit 13 of the flags -- the small-block class's first list, else the one-wave class's third
-  const bool of_block = P == SMALL_P2 && (flags & 8192);
-  const int list_start = a.bin_off[P == SMALL_P0 ? 1 : (P == SMALL_P1 ? OFF_SMALL_P1 : (of_block ? 2 : OFF_SMALL_U2))];
-  const int list_n = a.bin_off[P == SMALL_P0 ? OFF_SMALL_P1 : (P == SMALL_P1 ? OFF_SMALL_U2 : (of_block ? OFF_BLOCK_REST : OFF_WAVE_REST))] - list_start;
+  const int list_start = span_start(a.bin_off, flags);
+  const int list_n = span_end(a.bin_off, flags) - list_start;
   const int total_teams = gridDim.x * TEAMS;
   const bool ident = a.n_cols_b <= TW;
   const int cb = a.count_bits;
@@ -2111,7 +2123,7 @@ __global__ __launch_bounds__(256, (P == SMALL_P2 ? SMALL_OCC_P2 : URCCO_OCC_MICR
       pos[r] = n_surv + lanes_below(m);
       n_surv += (unsigned)__popcll(m);
     }
-    if (!(flags & 4096)) cand_acc += (flags & 256) ? n_surv : D;
+    if (!(flags & ROWS_COUNT_BODY)) cand_acc += (flags & ROWS_COUNT_SCORED) ? n_surv : D;
     else cand_acc += n_surv <= (unsigned)WAVE ? 1ull : (1ull << 32) + 1ull;
     const int64_t obase = ((int64_t)(i - a.item_lo)) * a.k;
     auto settle_prefetch = [&]() {  // the next row's operands have had the row to arrive: collect them before the output stores
@@ -2157,11 +2169,7 @@ __global__ __launch_bounds__(256, (P == SMALL_P2 ? SMALL_OCC_P2 : URCCO_OCC_MICR
       const bool in_tables = !is_cand || llr_operands_in_tables((unsigned)k11, (long long)row_ca, cbj, n_users, col_ent);
       const bool all_in_tables = __ballot(!in_tables) == 0ull;  // wave-uniform: the straight-line table form (see llr_from_tables)
       if (is_cand) {
-        if (!(a.exclude_self && jc == i)) {
-          const double llr = all_in_tables ? llr_from_tables(row_entropy, xlx_n, (unsigned)k11, (unsigned)row_ca, cbj, xlx_tab, xlx_hi, col_ent)
-                                           : llr_of(row_entropy, xlx_n, k11, (long long)row_ca, (long long)cbj, n_users, xlx_tab, xlx_hi, col_ent);
-          if (llr > 0.0 && (!a.has_min_llr || llr >= a.min_llr)) mk = (unsigned long long)__double_as_longlong(llr);
-        }
+        mk = score_key(a.exclude_self && jc == i, all_in_tables, row_entropy, xlx_n, k11, (long long)row_ca, (long long)cbj, n_users, xlx_tab, xlx_hi, col_ent, a.has_min_llr, a.min_llr);
         kkm[lane] = mk;
         cand[lane] = (unsigned)jc;
       }
@@ -2181,12 +2189,8 @@ __global__ __launch_bounds__(256, (P == SMALL_P2 ? SMALL_OCC_P2 : URCCO_OCC_MICR
           const unsigned v1 = tab[x], cbj = fcol[x];
           const int j = (int)(v1 >> cb) - 1;
           const long long k11 = (long long)(v1 & cmask);
-          if (!(a.exclude_self && j == i)) {
-            const double llr = llr_operands_in_tables((unsigned)k11, (long long)row_ca, cbj, n_users, col_ent)
-                                   ? llr_from_tables(row_entropy, xlx_n, (unsigned)k11, (unsigned)row_ca, cbj, xlx_tab, xlx_hi, col_ent)
-                                   : llr_of(row_entropy, xlx_n, k11, (long long)row_ca, (long long)cbj, n_users, xlx_tab, xlx_hi, col_ent);
-            if (llr > 0.0 && (!a.has_min_llr || llr >= a.min_llr)) key = (unsigned long long)__double_as_longlong(llr);
-          }
+          key = score_key(a.exclude_self && j == i, llr_operands_in_tables((unsigned)k11, (long long)row_ca, cbj, n_users, col_ent), row_entropy, xlx_n, k11, (long long)row_ca,
+                          (long long)cbj, n_users, xlx_tab, xlx_hi, col_ent, a.has_min_llr, a.min_llr);
           fkeys[x] = key;
           fcol[x] = (unsigned)j;
         }
@@ -2278,58 +2282,10 @@ __global__ __launch_bounds__(256, (P == SMALL_P2 ? SMALL_OCC_P2 : URCCO_OCC_MICR
         if (lane == 0) out_count[i - a.item_lo] = (int)n_out;
       }
     }
-    if (listed) {  // wave-uniform
-      // ---- the micro class's tail (cco_rows_micro_kernel, L = 64) over the list
+    if (listed) {  // wave-uniform: the micro class's tail over the list
       const unsigned long long valid_mask = __ballot(mk != 0ull);
-      const int n_valid = __popcll(valid_mask);
-      if (a.unordered && n_valid <= a.k) {  // every valid element is emitted: no ranking needed (wave-uniform)
-        settle_prefetch();
-        if (mk != 0ull) {
-          const unsigned opos = lanes_below(valid_mask);
-          out_idx[obase + opos] = jc;
-          out_llr[obase + opos] = __longlong_as_double((long long)mk);
-        }
-        if (lane == 0) out_count[i - a.item_lo] = n_valid;
-      } else {
-        // elements dense by lane, replicated while they fit twice / four times into the wave: replica q counts elements q, q + R, ...
-        unsigned rank;
-        unsigned long long rk;
-        unsigned rc;
-        unsigned ln = (unsigned)lane;
-        URCCO_OPAQUE(ln);  // the per-lane LDS addresses of the three forms are computed here, not kept across the row loop
-        if (n_list <= (unsigned)(WAVE / 4)) {  // wave-uniform
-          const unsigned c = ln & (unsigned)(WAVE / 4 - 1);
-          rk = kkm_l[c];
-          rc = cand_l[c];
-          rank = rank_by_counting_strided<4>(kkm_l, cand_l, ln / (unsigned)(WAVE / 4), (n_list + 3u) & ~3u, rk, rc);
-          rank += (unsigned)__shfl_xor((int)rank, WAVE / 4);
-          rank += (unsigned)__shfl_xor((int)rank, WAVE / 2);
-        } else if (n_list <= (unsigned)(WAVE / 2)) {
-          const unsigned c = ln & (unsigned)(WAVE / 2 - 1);
-          rk = kkm_l[c];
-          rc = cand_l[c];
-          rank = rank_by_counting_strided<2>(kkm_l, cand_l, ln / (unsigned)(WAVE / 2), (n_list + 1u) & ~1u, rk, rc);
-          rank += (unsigned)__shfl_xor((int)rank, WAVE / 2);
-        } else {
-          rk = kkm_l[ln];
-          rc = cand_l[ln];
-          rank = rank_by_counting_strided<1>(kkm_l, cand_l, 0u, n_list, rk, rc);
-        }
-        // the row is put in order in LDS (every lane has its element in registers: in place) and leaves as contiguous stores
-        wave_sync();
-        const unsigned n_out = (unsigned)(n_valid < a.k ? n_valid : a.k);
-        if ((unsigned)lane < n_list && rk != 0ull && rank < n_out) {
-          cand_l[rank] = rc;
-          kkm_l[rank] = rk;
-        }
-        wave_sync();
-        settle_prefetch();
-        if ((unsigned)lane < n_out) {
-          out_idx[obase + lane] = (int)cand_l[lane];
-          out_llr[obase + lane] = __longlong_as_double((long long)kkm_l[lane]);
-        }
-        if (lane == 0) out_count[i - a.item_lo] = (int)n_out;
-      }
+      rank_tail<WAVE>(cand_l, kkm_l, n_list, n_list, mk, jc, valid_mask, a.unordered && __popcll(valid_mask) <= a.k, a.k, lane, lane == 0, out_idx, out_llr, obase,
+                      out_count + (i - a.item_lo), settle_prefetch);
     }
     if (!fast) {
       wave_sync();
@@ -2356,7 +2312,7 @@ __device__ __forceinline__ int64_t g_len(const int64_t* wp, bool nar, int64_t p)
   const unsigned* w = reinterpret_cast<const unsigned*>(wp);
   return nar ? (int64_t)(unsigned)(w[p + 1] - w[p]) : wp[p + 1] - wp[p];
 }
-__global__ __launch_bounds__(GB_THREADS) void cco_rows_global_kernel(CcoArgs a) {
+__global__ __launch_bounds__(GB_THREADS) void cco_rows_global_kernel(CcoArgs a, int flags) {  // flags: the launch's list (list_span)
   constexpr int NW = GB_THREADS / WAVE;
   __shared__ unsigned long long s_pkey[2][NW];
   __shared__ int s_pcol[2][NW];
@@ -2365,9 +2321,8 @@ __global__ __launch_bounds__(GB_THREADS) void cco_rows_global_kernel(CcoArgs a) 
   __shared__ int s_nsel;
   __shared__ unsigned long long s_selk[GSEL_K];
   __shared__ unsigned s_selc[GSEL_K];
-  const int bin = NBINS - 1;
-  const int list_start = a.bin_off[bin];
-  const int list_n = a.bin_off[bin + 1] - list_start;
+  const int list_start = span_start(a.bin_off, flags);
+  const int list_n = span_end(a.bin_off, flags) - list_start;
   int32_t* cnt = a.g_counts + (int64_t)blockIdx.x * a.n_cols_b;
   unsigned long long* ckey = a.g_cand_key + (int64_t)blockIdx.x * a.n_cols_b;
   int32_t* ccol = a.g_cand_col + (int64_t)blockIdx.x * a.n_cols_b;
@@ -2393,12 +2348,10 @@ __global__ __launch_bounds__(GB_THREADS) void cco_rows_global_kernel(CcoArgs a) 
         const int j = (int)((unsigned)a.b_col_idx[q] & a.b_col_mask);
         const long long k11 = atomicExch(&cnt[j], 0);  // exactly one lane claims (and clears) each column
         if (k11 > 0 && !(a.exclude_self && j == i)) {
-          const long long cbj = a.cnt_b[j];
-          const double llr = llr_from_entropies_tab(row_entropy, column_entropy_of(cbj, xlx_n, a.n_users, a.xlx_tab, a.xlx_hi, a.col_ent), xlx_n, k11, ca - k11, cbj - k11,
-                                                    a.n_users - ca - cbj + k11, a.xlx_tab, a.n_users, a.xlx_hi);
-          if (llr > 0.0 && (!a.has_min_llr || llr >= a.min_llr)) {
+          const unsigned long long key = score_key(false, false, row_entropy, xlx_n, k11, ca, (long long)a.cnt_b[j], a.n_users, a.xlx_tab, a.xlx_hi, a.col_ent, a.has_min_llr, a.min_llr);
+          if (key != 0ull) {
             const int pos = atomicAdd(&s_ncand, 1);
-            ckey[pos] = (unsigned long long)__double_as_longlong(llr);
+            ckey[pos] = key;
             ccol[pos] = j;
           }
         }
@@ -2546,22 +2499,29 @@ hipError_t launch_mono_limit(hipStream_t st, unsigned short* mono, const double*
 // time included (profiles/r05_grid_factors_ab.log); bounded by one row loop per 32 item rows of the build (small builds and the ranks of a sharded
 // build keep the 2x: a row loop's start-up -- three rows of prefetches -- is not free; at an eighth of config 4's rows 4x measured 0.12 ms
 // per rank slower than 2x).
+using RowKernel = void (*)(CcoArgs, int);  // every row kernel: the arguments of the call, then the launch's lists and switches (list_span | ROWS_*)
 struct RowClass {
   int block, teams, factor;  // threads per block (the kernels' BLOCK), row loops per block (TEAMS), grid = factor x the blocks that fit the chip
   unsigned direct;           // the kernels' DL: 0 = the class has no direct ranking
-  void (*dbg)(CcoArgs, int), (*pk)(CcoArgs, int), (*plain)(CcoArgs, int);  // the three instantiations a RowsPlan chooses from
+  RowKernel dbg, pk, plain;  // the three instantiations a RowsPlan chooses from
 };
 template <int T, int E, int U, bool MP = false>
 constexpr RowClass row_class(int factor) {
   return {T < 256 ? 256 : T, (T < 256 ? 256 : T) / T, factor, MP ? 0u : direct_limit(T, E),
           cco_rows_kernel<T, E, U, MP, true, false>, cco_rows_kernel<T, E, U, MP, false, true>, cco_rows_kernel<T, E, U, MP, false, false>};
 }
-constexpr RowClass ROW_CLASS[NBINS] = {{256, 4, 8, 0u, nullptr, nullptr, nullptr},  // micro: cco_rows_micro_kernel<L> per sub-list, four one-wave teams
+template <int L>
+constexpr RowClass micro_class(int factor) {  // four one-wave teams
+  return {256, 4, factor, 0u, cco_rows_micro_kernel<L, true, false>, cco_rows_micro_kernel<L, false, true>, cco_rows_micro_kernel<L, false, false>};
+}
+constexpr RowClass ROW_CLASS[NBINS] = {micro_class<64>(8),                          // (LIST_MICRO; the lists of shared waves: MICRO_SHARED)
                                        row_class<64, E0, URCCO_U_WAVE>(8),         row_class<256, E1S, URCCO_U_BS>(8), row_class<256, E1, URCCO_U_B>(8),
                                        row_class<512, E2S, URCCO_U_H>(4),          row_class<1024, E2, URCCO_U_C>(4),  row_class<1024, E2, URCCO_U_C, true>(2)};
-// the micro class's sub-lists of shared waves (two / four rows per wave and pass) hold a third of the class's passes each at most: smaller grids,
+static_assert(ROW_CLASS[NBINS - 1].block == GB_THREADS, "the dense global kernel is launched with the multi-pass class's block");
+// the micro class's lists of shared waves (two / four rows per wave and pass) hold a third of the class's passes each at most: smaller grids,
 // so that a wave still runs several passes behind its start-up (three rows of prefetches).
 constexpr int MICRO_FACTOR32 = 3, MICRO_FACTOR16 = 2;
+constexpr RowClass MICRO_SHARED[2] = {micro_class<32>(MICRO_FACTOR32), micro_class<16>(MICRO_FACTOR16)};
 
 // resident blocks per CU of each LDS-accumulator kernel (registers / LDS decide), so that the persistent grids fill
 // the chip exactly once
@@ -2569,18 +2529,105 @@ static int blocks_per_cu(int bin) {
   static std::atomic<int> cache[NBINS];  // zero-initialised; a racing first call computes the same value twice
   if (cache[bin].load(std::memory_order_relaxed) == 0) {
     int n = 0;
-    const hipError_t e = bin == 0 ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, (cco_rows_micro_kernel<WAVE, false, false>), ROW_CLASS[0].block, 0)
-                                  : hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ROW_CLASS[bin].plain, ROW_CLASS[bin].block, 0);
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, ROW_CLASS[bin].plain, ROW_CLASS[bin].block, 0);
     cache[bin].store((e == hipSuccess && n > 0) ? n : 1, std::memory_order_relaxed);
   }
   return cache[bin].load(std::memory_order_relaxed);
+}
+
+// One launch of a bin: the kernel, the lists [first, end) it covers, its ROWS_* switches, the grid as a multiple of the blocks that fit the chip (0: the
+// dense kernel's own CcoArgs::g_blocks), the blocks per CU it is compiled for (0: ask the runtime about the class's kernel), and what it is to the statistics.
+enum class LaunchKind { GENERAL_PK, GENERAL_PLAIN /* and DBG */, MICRO, SMALL_BODY, EIGHT_PAIR_BODY, DENSE_GLOBAL };
+struct RowLaunch {
+  RowKernel kernel;
+  int first, end, flags, factor, per_cu;
+  LaunchKind kind;
+};
+constexpr int MAX_BIN_LAUNCHES = 6;  // bin 0 under DEVICE_DECIDES: three lists in two forms
+
+// The arguments of one launch: the call's, with the statistics word (CcoArgs::cand, stats[2 + 4 * NBINS] while stage timing is on) taken from every launch
+// that must not add to it under the call's DBG_COUNT_* bit -- a bit that makes the word count the ROWS of some kernel silences every other kernel, so that no
+// candidate count is mixed in.  The launches that keep the word:
+//   debug bit                     general PK                      general plain, DBG, micro, dense global   small-row body   eight-pair body
+//   none of the three             yes                             yes                                       yes              yes
+//   DBG_COUNT_DIRECT              a class with a direct ranking   no                                        no               no
+//   DBG_COUNT_SMALL_WAVE          no                              no                                        yes              no
+//   DBG_COUNT_BLOCK_SMALL_WAVE    no                              no                                        no               yes *
+// (a row: that bit set, alone or with others -- with several set a launch keeps the word only if every set bit's row says yes.)
+// * URCCO_COUNT_BLOCK_LIST = 1 / 2 (read per call): only the eight-pair launch of that bin -- the one-wave class's list / the small-block class's.
+static CcoArgs launch_args(const CcoArgs& args, LaunchKind kind, int bin) {
+  const bool direct = (args.debug & DBG_COUNT_DIRECT) != 0, small = (args.debug & DBG_COUNT_SMALL_WAVE) != 0, block = (args.debug & DBG_COUNT_BLOCK_SMALL_WAVE) != 0;
+  bool counts;
+  switch (kind) {
+    case LaunchKind::GENERAL_PK: counts = !(small || block) && (!direct || ROW_CLASS[bin].direct != 0u); break;
+    case LaunchKind::SMALL_BODY: counts = !(direct || block); break;
+    case LaunchKind::EIGHT_PAIR_BODY: {
+      const char* only = block ? getenv("URCCO_COUNT_BLOCK_LIST") : nullptr;
+      counts = !(direct || small) && !(only && *only && atoi(only) != bin);
+      break;
+    }
+    default: counts = !(direct || small || block);
+  }
+  CcoArgs a = args;
+  if (!counts) a.cand = nullptr;
+  if (kind == LaunchKind::DENSE_GLOBAL) a.b_packed = nullptr;  // (the dense kernel reads plain words whatever the plan)
+  return a;
+}
+
+// The launches of one bin under the plan and the call's debug bits, in the order they are enqueued.  Returns their number (<= MAX_BIN_LAUNCHES).
+static int bin_launches(const CcoArgs& args, RowsPlan plan, int bin, int32_t n_rows, RowLaunch* out) {
+  int n = 0;
+  const int first = first_list(bin), end = first_list(bin + 1);
+  const bool count_direct = (args.debug & DBG_COUNT_DIRECT) != 0;
+  const int scored = (args.debug & DBG_COUNT_SCORED) ? ROWS_COUNT_SCORED : 0;
+  // the switches ride on the production kernels' argument (grid-uniform; they do not read CcoArgs::debug)
+  const int pk_flags = scored | ((args.debug & DBG_NO_DIRECT_RANK) ? ROWS_NO_DIRECT : 0) | (count_direct ? ROWS_COUNT_DIRECT : 0);
+  // what the plan enqueues of one class (or micro list): its DBG, PK and plain instantiation over [lo, hi) -- the PK one from pk_lo on, behind the lists that
+  // run in the small-row body (a build whose counts do not fit runs all of them in the plain instantiation)
+  auto general = [&](const RowClass& c, int lo, int pk_lo, int hi) {
+    const LaunchKind pk_kind = bin == 0 ? LaunchKind::MICRO : LaunchKind::GENERAL_PK, kind = bin == 0 ? LaunchKind::MICRO : LaunchKind::GENERAL_PLAIN;
+    if (plan == RowsPlan::DEBUG) out[n++] = {c.dbg, lo, hi, 0, c.factor, 0, kind};
+    if (plan_runs_pk(plan)) out[n++] = {c.pk, pk_lo, hi, pk_flags, c.factor, 0, pk_kind};
+    if (plan_runs_plain(plan)) out[n++] = {c.plain, lo, hi, 0, c.factor, 0, kind};
+  };
+  auto body = [&](RowKernel kernel, int list, int count_bit, int per_cu, LaunchKind kind) {
+    out[n++] = {kernel, list, list + 1, scored | ((args.debug & count_bit) ? ROWS_COUNT_BODY : 0), SMALL_FACTOR, per_cu, kind};
+  };
+  // the lists of the small-row body exist under the binning pass's own rule (launch_binning: otherwise they are empty), and only the packed form runs them
+  const bool small_split = plan_runs_pk(plan) && micro_split_for(n_rows) && args.k <= SMALL_KMAX;
+  const bool block_small = small_split && !(args.debug & DBG_NO_BLOCK_SMALL_WAVE);
+  if (bin == 0) {  // the rows that keep a wave to themselves first
+    general(ROW_CLASS[0], LIST_MICRO, LIST_MICRO, end);
+    if (micro_split_for(n_rows)) {  // (the same rule as the binning pass: without the split the two lists are empty)
+      general(MICRO_SHARED[0], LIST_MICRO32, LIST_MICRO32, LIST_MICRO);
+      general(MICRO_SHARED[1], LIST_MICRO16, LIST_MICRO16, LIST_MICRO32);
+    }
+  } else if (bin == NBINS - 1 && args.g_blocks > 0) {
+    out[n++] = {cco_rows_global_kernel, first, end, 0, 0, 0, LaunchKind::DENSE_GLOBAL};
+  } else {
+    int pk_lo = first;  // the general PK kernel starts behind the lists that ran in the small-row body
+    if (bin == 1 && small_split && !(args.debug & DBG_NO_SMALL_WAVE)) {
+      body(cco_rows_small_kernel<SMALL_P0, 1>, LIST_WAVE_P128, DBG_COUNT_SMALL_WAVE, 0, LaunchKind::SMALL_BODY);
+      body(cco_rows_small_kernel<SMALL_P1, 1>, LIST_WAVE_P256, DBG_COUNT_SMALL_WAVE, 0, LaunchKind::SMALL_BODY);
+      pk_lo = LIST_WAVE_U128;
+      if (block_small) {  // (DBG_NO_BLOCK_SMALL_WAVE: the general kernel takes this list as well)
+        body(cco_rows_small_kernel<SMALL_P2, SMALL_U2>, LIST_WAVE_U128, DBG_COUNT_BLOCK_SMALL_WAVE, SMALL_OCC_P2, LaunchKind::EIGHT_PAIR_BODY);
+        pk_lo = LIST_WAVE;
+      }
+    } else if (bin == 2 && block_small && !count_direct) {  // (DBG_COUNT_DIRECT: the whole class in its own kernel, which has the direct ranking)
+      body(cco_rows_small_kernel<SMALL_P2, SMALL_U2>, LIST_BLOCKS_U128, DBG_COUNT_BLOCK_SMALL_WAVE, SMALL_OCC_P2, LaunchKind::EIGHT_PAIR_BODY);
+      pk_lo = LIST_BLOCKS;
+    }
+    general(ROW_CLASS[bin], first, pk_lo, end);
+  }
+  return n;
 }
 
 hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, RowsPlan plan, int bin, int32_t n_rows) {
   // Persistent grids sized to the chip (ROW_CLASS); each kernel reads its own row list length from bin_off on the device,
   // so no host synchronisation sits between binning and the SpGEMM.
   const RowClass& c = ROW_CLASS[bin];
-  auto grid = [&](int factor, int per_cu = 0) {
+  auto grid = [&](int factor, int per_cu) {
     const long long fill = (long long)n_cu * (per_cu > 0 ? per_cu : blocks_per_cu(bin));  // blocks resident at once
     long long cap = ((long long)n_rows + c.teams * 32 - 1) / (c.teams * 32);
     if (cap < 2 * fill) cap = 2 * fill;  // (as rounds 2-4)
@@ -2588,62 +2635,12 @@ hipError_t launch_cco_rows_bin(hipStream_t st, int n_cu, const CcoArgs& args, Ro
     if (blocks > cap) blocks = cap;
     return dim3((unsigned)blocks);
   };
-  // Two blocks: the PK instantiations' and the one of every kernel that reads plain words (the plain and DBG instantiations, the dense global kernel).
-  // DBG_COUNT_DIRECT: the statistics word counts the rows the packed kernels ranked directly -- every kernel that has no direct ranking (the plain and DBG
-  // forms, the micro and multi-pass classes, a class it is compiled out of) runs without the word, so that no candidate count is mixed in
-  // DBG_COUNT_SMALL_WAVE, likewise: the word counts the rows of cco_rows_small_kernel, and every other kernel runs without it
-  // DBG_COUNT_BLOCK_SMALL_WAVE, likewise, for the launches of that kernel's eight-pair form (URCCO_COUNT_BLOCK_LIST = 1 / 2, read per call: only the one-wave
-  // class's list / only the small-block class's)
-  const bool count_direct = (args.debug & DBG_COUNT_DIRECT) != 0, count_small = (args.debug & DBG_COUNT_SMALL_WAVE) != 0;
-  const bool count_block = (args.debug & DBG_COUNT_BLOCK_SMALL_WAVE) != 0;
-  CcoArgs pk = args, plain = args, small = args, small2 = args;
-  if ((count_direct && c.direct == 0u) || count_small || count_block) pk.cand = nullptr;
-  if (count_direct || count_small || count_block) plain.cand = nullptr;
-  if (count_direct || count_block) small.cand = nullptr;
-  if (count_direct || count_small) small2.cand = nullptr;
-  if (count_block) {
-    const char* only = getenv("URCCO_COUNT_BLOCK_LIST");
-    if (only && *only && atoi(only) != bin) small2.cand = nullptr;
-  }
-  // the sub-lists of the small-row body exist under the binning pass's own rule (launch_binning: otherwise they are empty), and only the packed form runs them
-  const bool small_split = plan_runs_pk(plan) && micro_split_for(n_rows) && args.k <= SMALL_KMAX;
-  const bool block_small = small_split && !(args.debug & DBG_NO_BLOCK_SMALL_WAVE);
-  const int small2_bits = ((args.debug & DBG_COUNT_SCORED) ? 256 : 0) | (count_block ? 4096 : 0);
-  // ride on the PK kernels' bin argument (grid-uniform; the production instantiations do not read CcoArgs::debug)
-  const int pk_bits = ((args.debug & DBG_COUNT_SCORED) ? 256 : 0) | ((args.debug & DBG_NO_DIRECT_RANK) ? 512 : 0) | (count_direct ? 1024 : 0);
-  // what the plan enqueues of one class (or micro sub-list), given its DBG, PK and plain instantiation; bin_arg: the bin argument of cco_rows_kernel
-  auto enqueue = [&](auto dbg_kernel, auto pk_kernel, auto plain_kernel, int factor, auto... bin_arg) {
-    if (plan == RowsPlan::DEBUG) hipLaunchKernelGGL(dbg_kernel, grid(factor), dim3(c.block), 0, st, plain, bin_arg...);
-    if (plan_runs_pk(plan)) hipLaunchKernelGGL(pk_kernel, grid(factor), dim3(c.block), 0, st, pk, (bin_arg | pk_bits)...);
-    if (plan_runs_plain(plan)) hipLaunchKernelGGL(plain_kernel, grid(factor), dim3(c.block), 0, st, plain, bin_arg...);
-  };
-  if (bin == 0) {  // the class's three sub-lists, the rows that keep a wave to themselves first (each kernel reads its own list bounds on the device)
-    enqueue(cco_rows_micro_kernel<64, true, false>, cco_rows_micro_kernel<64, false, true>, cco_rows_micro_kernel<64, false, false>, c.factor);
-    if (micro_split_for(n_rows)) {  // (the same rule as the binning pass: without the split the two sub-lists are empty)
-      enqueue(cco_rows_micro_kernel<32, true, false>, cco_rows_micro_kernel<32, false, true>, cco_rows_micro_kernel<32, false, false>, MICRO_FACTOR32);
-      enqueue(cco_rows_micro_kernel<16, true, false>, cco_rows_micro_kernel<16, false, true>, cco_rows_micro_kernel<16, false, false>, MICRO_FACTOR16);
-    }
-  } else if (bin == NBINS - 1 && args.g_blocks > 0) {
-    plain.b_packed = nullptr;  // (the dense kernel reads plain words whatever the plan)
-    hipLaunchKernelGGL(cco_rows_global_kernel, dim3((unsigned)args.g_blocks), dim3(GB_THREADS), 0, st, plain);
-  } else if (bin == 1 && small_split && !(args.debug & DBG_NO_SMALL_WAVE)) {
-    // the class's sub-lists of small rows in the micro-shaped body -- two / four pairs per lane, then eight pairs and two users per lane --, the rest in the
-    // general kernel (bit 11 of its bin argument; with bit 13 it takes the third sub-list as well: DBG_NO_BLOCK_SMALL_WAVE); the plain instantiation -- a build
-    // whose counts do not fit -- keeps the whole class.  (DBG_NO_SMALL_WAVE keeps all of them in the general kernel: its list is one piece.)
-    const int small_bits = ((args.debug & DBG_COUNT_SCORED) ? 256 : 0) | (count_small ? 4096 : 0);
-    hipLaunchKernelGGL((cco_rows_small_kernel<SMALL_P0, 1>), grid(SMALL_FACTOR), dim3(c.block), 0, st, small, small_bits);
-    hipLaunchKernelGGL((cco_rows_small_kernel<SMALL_P1, 1>), grid(SMALL_FACTOR), dim3(c.block), 0, st, small, small_bits);
-    if (block_small) hipLaunchKernelGGL((cco_rows_small_kernel<SMALL_P2, SMALL_U2>), grid(SMALL_FACTOR, SMALL_OCC_P2), dim3(c.block), 0, st, small2, small2_bits);
-    hipLaunchKernelGGL(c.pk, grid(c.factor), dim3(c.block), 0, st, pk, bin | pk_bits | 2048 | (block_small ? 0 : 8192));
-    if (plan_runs_plain(plan)) hipLaunchKernelGGL(c.plain, grid(c.factor), dim3(c.block), 0, st, plain, bin);
-  } else if (bin == 2 && block_small && !count_direct) {
-    // the class's first list -- rows of <= 128 users and <= 512 pairs -- in the same body (bit 13 of its flags), the rest in the class's own kernel (bit 11).
-    // (DBG_COUNT_DIRECT: the whole class in its own kernel, which has the direct ranking.)
-    hipLaunchKernelGGL((cco_rows_small_kernel<SMALL_P2, SMALL_U2>), grid(SMALL_FACTOR, SMALL_OCC_P2), dim3(256), 0, st, small2, small2_bits | 8192);
-    hipLaunchKernelGGL(c.pk, grid(c.factor), dim3(c.block), 0, st, pk, bin | pk_bits | 2048);
-    if (plan_runs_plain(plan)) hipLaunchKernelGGL(c.plain, grid(c.factor), dim3(c.block), 0, st, plain, bin);
-  } else {
-    enqueue(c.dbg, c.pk, c.plain, c.factor, bin);
+  RowLaunch launches[MAX_BIN_LAUNCHES];
+  const int n = bin_launches(args, plan, bin, n_rows, launches);
+  for (int q = 0; q < n; ++q) {
+    const RowLaunch& l = launches[q];
+    hipLaunchKernelGGL(l.kernel, l.factor > 0 ? grid(l.factor, l.per_cu) : dim3((unsigned)args.g_blocks), dim3(c.block), 0, st, launch_args(args, l.kind, bin),
+                       list_span(l.first, l.end) | l.flags);
   }
   return hipGetLastError();
 }
@@ -2660,7 +2657,7 @@ __global__ __launch_bounds__(256) void bin_out_stats_kernel(const int32_t* __res
     stats[2 + 4 * NBINS] = c;
   }
   long long v = 0;
-  for (int t = bin_off[bin] + blockIdx.y * 256 + threadIdx.x; t < bin_off[bin + 1]; t += 256 * gridDim.y) v += out_count[bin_rows[t] - item_lo];
+  for (int t = bin_off[first_list(bin)] + blockIdx.y * 256 + threadIdx.x; t < bin_off[first_list(bin + 1)]; t += 256 * gridDim.y) v += out_count[bin_rows[t] - item_lo];
   long long tot;
   block_exclusive_scan(v, s_wave, &tot);
   if (threadIdx.x == 0 && tot) atomicAdd((unsigned long long*)&stats[1 + 3 * NBINS + bin], (unsigned long long)tot);
