@@ -638,6 +638,31 @@ int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double
  *                     hold, the result may be wrong, but no access leaves the arrays
  *   URCCO_BAD_ARG: n_events >= 2^31, a negative count, n_users > 0x7ffffff0, a NULL the call needs, out_times and times_ms not NULL together.  Needed:
  *   items, idx_pos, out_items and out_pos only when n_events > 0; idx_row_ptr when n_users > 0; drop_users when n_drop > 0; out_row_ptr and out_counts always.
+ * urcco_dev_history_users / urcco_dev_history_matrix (DESIGN.md decision D23): the Preparator's output -- which users train, and one event type's user x
+ *   column matrix with sorted, duplicate-free rows -- from the stream and the index alone; no `users` array exists after an append or a trim.
+ *   window            the event at stream position p is in the window when times_ms == NULL, or when t_lo <= times_ms[p] and (t_hi == INT64_MAX or
+ *                     times_ms[p] < t_hi): signed compares, the start inclusive, the end exclusive as in urcco_dev_pop_counts, INT64_MAX = no end.  With
+ *                     times_ms == NULL any window other than (INT64_MIN, INT64_MAX) is URCCO_BAD_ARG
+ *   _users            c[u] = the number of u's index entries whose position is in the window, whatever item the event carries (the Preparator's
+ *                     minEventsPerUser counts events).  out_row_of[u] = the number of users v < u with c[v] >= min_events when c[u] >= min_events, else
+ *                     -1; out_n_rows[0] = the number of kept users.  The counting is balanced by index entries, not by users: one user may own a
+ *                     quarter of the stream
+ *   _matrix           row row_of[u] of the result holds the distinct items[p], ascending, with 0 <= items[p] < n_cols, over u's index entries whose p is
+ *                     in the window.  row_of == NULL is the identity and needs n_rows == n_users.  A user with row_of[u] < 0 contributes nothing, one
+ *                     with row_of[u] >= n_rows is ignored; a row that no user names is empty.  That row_of ascends over the users it keeps and names no
+ *                     row twice is the caller's duty (_users' output does).  out_row_ptr and out_col_idx[0 .. nnz) are then, bit for bit, the arrays
+ *                     urcco_dev_csr_from_pairs gives for the pairs (row_of[user], item) of the kept events; out_nnz[0] = nnz = out_row_ptr[n_rows]
+ *   capacity          the raw entries of a user are its index segment, so idx_row_ptr is the prefix of the rows' upper bounds: user u's row is written iff
+ *                     idx_row_ptr[u + 1] <= capacity (the bound of its END, over ALL users below it, kept or not); every other row is left empty.
+ *                     Nothing is written at or past out_col_idx[capacity] or out_row_ptr[n_rows + 1].  A caller that sizes by n_events never loses a row
+ *   classes           by the raw entries m of the user: m <= 64 one wave, m <= 4096 one block sorting in LDS, larger a column bitmap of ceil(n_cols / 32)
+ *                     words in arena scratch per block of that class -- one atomic bit set per kept entry, one walk over the words, no sort.  The
+ *                     bitmaps of one call take at most 8 MiB (64 blocks at most; one block when a single bitmap is larger than that)
+ *   malformed index   entries of idx_pos outside 0 .. n_events are dropped, row starts are clamped into 0 .. min(idx_row_ptr[n_users], n_events); whatever
+ *                     idx_row_ptr, idx_pos and row_of hold, the result may be wrong, but no access leaves the arrays
+ *   URCCO_BAD_ARG: n_events >= 2^31, a negative count or capacity, n_users or n_rows > 0x7ffffff0, min_events < 1, n_cols < 1, a window without times_ms,
+ *   row_of == NULL with n_rows != n_users, a NULL the call needs.  Needed: idx_pos (and items) only when n_events > 0; idx_row_ptr (and out_row_of) when
+ *   n_users > 0; out_col_idx when capacity > 0; out_n_rows, out_row_ptr and out_nnz always.
  * urcco_dev_history_bounds: term_row_ptr of every type and excl_row_ptr receive the exclusive scans of upper bounds of the rows' lengths (min(n_u, max_items);
  *   blacklist events + extra row).  The caller reads the 1 + n_types totals (term_row_ptr[n_queries], excl_row_ptr[n_queries]: its one synchronisation),
  *   allocates term_col_idx / excl_col_idx of at least that many entries and states the sizes in term_capacity / excl_capacity.
@@ -648,7 +673,7 @@ int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double
  * stats_dev (nullable, int64[URCCO_HIST_STATS_LEN]): (query, type) pairs served by [0] the wave class (<= 64 events), [1] the block class (<= 4096, keys in
  *   LDS), [2] the global class; [3] pairs that ran the select (n_u > max_items); exclusion rows built by [4] one wave, [5] one block; [6] rows dropped
  *   for lack of capacity (0 when the caller sized its buffers by the bounds); [7] 0.
- * All five enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: n_events >= 2^31, n_types outside
+ * All seven enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: n_events >= 2^31, n_types outside
  * 1..URCCO_REC_MAX_CLAUSES, max_items < 1, n_queries * (n_types + 1) >= 2^31, a NULL the call needs, a half-NULL extra pair, a negative capacity.
  * ABI: additions within ABI 305 -- the presence of the symbols is the feature test. */
 #define URCCO_HIST_STATS_LEN 8
@@ -668,6 +693,18 @@ int urcco_dev_history_trim(urcco_session* s,
                            int32_t* out_items, int64_t* out_times /* NULL iff times_ms NULL */,
                            int64_t* out_row_ptr /* [n_users + 1] */, int32_t* out_pos,
                            int64_t* out_counts /* device [2] */);
+/* which users train, and under which row number */
+int urcco_dev_history_users(urcco_session* s, int64_t n_events, const int64_t* times_ms /* nullable */,
+                            int64_t n_users, const int64_t* idx_row_ptr /* [n_users + 1] */, const int32_t* idx_pos,
+                            int64_t t_lo, int64_t t_hi, int32_t min_events,
+                            int32_t* out_row_of /* [n_users] */, int64_t* out_n_rows /* device [1] */);
+/* one event type's user x column matrix */
+int urcco_dev_history_matrix(urcco_session* s, int64_t n_events, const int32_t* items, const int64_t* times_ms /* nullable */,
+                             int64_t n_users, const int64_t* idx_row_ptr /* [n_users + 1] */, const int32_t* idx_pos,
+                             int64_t t_lo, int64_t t_hi, int32_t n_cols,
+                             const int32_t* row_of /* nullable: identity, n_rows == n_users */, int64_t n_rows,
+                             int64_t* out_row_ptr /* [n_rows + 1] */, int32_t* out_col_idx, int64_t capacity,
+                             int64_t* out_nnz /* device [1] */);
 
 typedef struct urcco_hist_event {
   int32_t n_cols, max_items;          /* max_items >= 1 */

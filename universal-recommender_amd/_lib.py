@@ -221,6 +221,8 @@ SYMBOLS = {
     "urcco_dev_history_index": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_append": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_trim": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p]),
+    "urcco_dev_history_users": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, C.c_int32, _p, _p]),
+    "urcco_dev_history_matrix": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, C.c_int32, _p, C.c_int64, _p, _p, C.c_int64, _p]),
     "urcco_dev_history_bounds": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.POINTER(HistEvent), C.c_int32, _p, _p, _p]),
     "urcco_dev_history_rows": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.POINTER(HistEvent), C.c_int32, _p, _p, C.c_int32, _p, _p, C.c_int64, _p]),
     "urcco_dev_item_bounds": (C.c_int, [_p, C.c_int64, _p, C.c_int32, C.POINTER(ItemEvent), C.c_int32]),

@@ -6,6 +6,7 @@
 //   index   stream positions by user: count per user -> scan -> scatter by cursor (order inside a user's segment unspecified)
 //   append  the index of the stream grown by a batch: old segments copied at their shifts, the batch scattered behind them (D21)
 //   trim    the stream and the index without the events before a cut-off and those of listed users: "kept" bitmaps, popcount scans, ranks (D22)
+//   matrix  the Preparator's output from the index: the users that train, per event type the user x column CSR; heavy users through a column bitmap (D23)
 //   bounds  per (query, type) min(n_u, max_items), per query the blacklist events + the extra exclusion row: scans = raw row starts
 //   rows    per (query, type): the window = the min(n_u, max_items) largest keys (time, position) of the user's events -- found by an
 //           8-bit radix SELECT over the 96-bit keys when n_u > max_items, never by sorting the events -- then sort + unique of the
@@ -336,6 +337,251 @@ hipError_t launch_history_trim(hipStream_t st, int n_cu, const TrimArgs& a) {
   }
   hipLaunchKernelGGL(ht_row_ptr_kernel, dim3(ig_grid(a.n_users + 1, n_cu)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.i_bits, a.s_base, a.i_base, a.out_row_ptr,
                      a.out_counts);
+  return hipGetLastError();
+}
+
+// ---- matrices (decision D23) ---------------------------------------------------------------------------------------
+// The Preparator's output from the index and the item stream alone: which users train (users), and per event type the user x column matrix whose rows are
+// the users' distinct in-window columns, ascending (matrix) -- the arrays launch_csr_from_pairs gives for the pairs (row_of[user], item), without a `users` array.
+//   users   I[e] = "the position of index entry e is in the window" as in the trim (one wave per word of 64 entries: balanced by ENTRIES), popcount scan,
+//           c[u] = rankI(end of u) - rankI(start of u), keep[u] = c[u] >= min_events, scan of keep = the row numbers
+//   matrix  the raw row of user u is tmp[lo .. hi), lo / hi = u's clamped row starts: idx_row_ptr is the prefix of the raw lengths, no bounds pass.
+//           Three classes by the raw entries m = hi - lo, chosen on the device:
+//             <= 64     sr_wave_tail<true>: a lane per entry, entries outside the window or the columns are SR_SENT
+//             <= 4096   sr_block_tail<true>: the gathered columns staged in LDS
+//             larger    column bitmap: a block owns ceil(n_cols / 32) words of scratch, all zero between rows; one atomicOr per kept entry, then one walk
+//                       over the words that takes each word with atomicExch(.., 0) -- reading it and leaving the bitmap zero for the block's next row in
+//                       one access -- and writes its set bits as columns at the offsets a block scan of the popcounts gives, 256 words at a time.  No
+//                       sort: the row is ascending and distinct by construction.  Every access to a bitmap is an atomic (performed at L2), so no line of
+//                       it is ever held in a CU's L1.  HM_BITMAP_BUDGET bytes bound the bitmaps of a launch: min(HM_BITMAP_BLOCKS, budget / bitmap) blocks
+//           then the scan of the lengths and the compaction of the raw rows' fronts into the caller's CSR
+// A row is written iff hi <= capacity; row r's place in the result ends at or before its raw end, so nothing is written at or past out_col_idx[capacity].
+// Whatever idx_row_ptr, idx_pos and row_of hold, no access leaves the arrays: entries outside the stream are dropped, row starts clamped into 0 .. n_e,
+// row numbers outside 0 .. n_rows skipped, and the compaction checks both ends (segments that overlap, or two users of one row, can sum to more than n_e).
+namespace {
+constexpr long long HM_OPEN = 0x7fffffffffffffffll;  // t_hi == INT64_MAX: no upper end
+
+__device__ __forceinline__ bool hm_in_window(const int64_t* __restrict__ times, int p, int64_t t_lo, int64_t t_hi) {
+  if (!times) return true;
+  const int64_t t = times[p];
+  return t >= t_lo && (t_hi == HM_OPEN || t < t_hi);
+}
+
+// the column index entry `p` gives its user's row, SR_SENT when it gives none
+__device__ __forceinline__ int hm_column(const MatrixArgs& a, int p) {
+  if (p < 0 || p >= a.n_events) return SR_SENT;
+  if (!hm_in_window(a.times_ms, p, a.t_lo, a.t_hi)) return SR_SENT;
+  const int item = a.items[p];
+  return item >= 0 && item < a.n_cols ? item : SR_SENT;
+}
+
+// user u's row number, -1: none; its raw row [lo, hi)
+__device__ __forceinline__ int64_t hm_row(const MatrixArgs& a, int64_t u, int64_t n_e, int64_t& lo, int64_t& hi) {
+  lo = ht_clamp(a.idx_row_ptr[u], n_e);
+  hi = ht_clamp(a.idx_row_ptr[u + 1], n_e);
+  const int64_t r = a.row_of ? a.row_of[u] : u;
+  return r >= 0 && r < a.n_rows ? r : -1;
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void hu_flags_kernel(UsersArgs a) {
+  const int lane = threadIdx.x & (SR_WAVE - 1);
+  const int64_t n_e = ht_entries(a.idx_row_ptr, a.n_users, a.n_events);
+  const int64_t n_words = (a.n_events + 63) >> 6, n_waves = (int64_t)gridDim.x * (256 / SR_WAVE);
+  for (int64_t w = (int64_t)blockIdx.x * (256 / SR_WAVE) + threadIdx.x / SR_WAVE; w < n_words; w += n_waves) {  // wave-uniform
+    const int64_t e = (w << 6) + lane;
+    bool in = false;
+    if (e < n_e) {
+      const int p = a.idx_pos[e];
+      if (p >= 0 && p < a.n_events) in = hm_in_window(a.times_ms, p, a.t_lo, a.t_hi);
+    }
+    const unsigned long long word = __ballot(in);
+    if (lane == 0) {
+      a.i_bits[w] = word;
+      a.i_cnt[w] = __popcll(word);
+    }
+  }
+}
+
+__global__ __launch_bounds__(256) void hu_keep_kernel(UsersArgs a) {
+  const int64_t n_e = ht_entries(a.idx_row_ptr, a.n_users, a.n_events);
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < a.n_users; u += (int64_t)gridDim.x * 256) {
+    const int64_t c = ht_rank(a.i_base, a.i_bits, ht_clamp(a.idx_row_ptr[u + 1], n_e)) - ht_rank(a.i_base, a.i_bits, ht_clamp(a.idx_row_ptr[u], n_e));
+    a.keep[u] = c >= a.min_events ? 1 : 0;
+  }
+}
+
+__global__ __launch_bounds__(256) void hu_row_of_kernel(UsersArgs a) {
+  for (int64_t u = (int64_t)blockIdx.x * 256 + threadIdx.x; u < a.n_users; u += (int64_t)gridDim.x * 256)
+    a.out_row_of[u] = a.keep[u] ? (int32_t)a.prefix[u] : -1;
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.out_n_rows[0] = a.prefix[a.n_users];
+}
+
+hipError_t launch_history_users(hipStream_t st, int n_cu, const UsersArgs& a) {
+  if (a.n_users == 0) return hipMemsetAsync(a.out_n_rows, 0, sizeof(int64_t), st);
+  const int64_t n_words = (a.n_events + 63) >> 6;
+  if (a.n_events > 0) hipLaunchKernelGGL(hu_flags_kernel, dim3(ig_grid(a.n_events, n_cu)), dim3(256), 0, st, a);
+  hipError_t e = launch_scan_i32(st, a.i_cnt, n_words, a.i_base, a.tile_sums);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(hu_keep_kernel, dim3(ig_grid(a.n_users, n_cu)), dim3(256), 0, st, a);
+  e = launch_scan_i32(st, a.keep, a.n_users, a.prefix, a.tile_sums);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(hu_row_of_kernel, dim3(ig_grid(a.n_users, n_cu)), dim3(256), 0, st, a);
+  return hipGetLastError();
+}
+
+// One wave per user of <= 64 raw entries; the others go on the list: up to SR_LDS entries from the front (ctr[0]), heavier ones from the back (ctr[1]).
+__global__ __launch_bounds__(256) void hm_rows_wave_kernel(MatrixArgs a) {
+  const int lane = threadIdx.x & (SR_WAVE - 1);
+  const int64_t n_waves = (int64_t)gridDim.x * (256 / SR_WAVE);
+  const int64_t n_e = ht_entries(a.idx_row_ptr, a.n_users, a.n_events);
+  for (int64_t u = (int64_t)blockIdx.x * (256 / SR_WAVE) + threadIdx.x / SR_WAVE; u < a.n_users; u += n_waves) {  // wave-uniform
+    int64_t lo, hi;
+    const int64_t r = hm_row(a, u, n_e, lo, hi);
+    const int64_t m = hi - lo;
+    if (r < 0 || m <= 0 || hi > a.capacity) continue;  // no row, or one that stays empty: len[r] is 0
+    if (m > SR_WAVE) {
+      if (lane == 0) {
+        if (m <= SR_LDS) a.list[atomicAdd(&a.ctr[0], 1ull)] = (int32_t)u;
+        else a.list[a.n_users - 1 - (int64_t)atomicAdd(&a.ctr[1], 1ull)] = (int32_t)u;
+      }
+      continue;
+    }
+    const int v = lane < m ? hm_column(a, a.idx_pos[lo + lane]) : SR_SENT;
+    const int len = sr_wave_tail<true>(v, lane, SR_WAVE, a.tmp + lo);
+    if (lane == 0) {
+      a.len[r] = len;
+      a.raw_start[r] = (int32_t)lo;
+    }
+  }
+}
+
+// One block per listed user of 65 .. SR_LDS raw entries.
+__global__ __launch_bounds__(256) void hm_rows_block_kernel(MatrixArgs a) {
+  __shared__ int s_v[SR_LDS];
+  const int64_t n_e = ht_entries(a.idx_row_ptr, a.n_users, a.n_events);
+  const int64_t n_big = (int64_t)a.ctr[0];
+  for (int64_t li = blockIdx.x; li < n_big; li += gridDim.x) {  // block-uniform
+    const int64_t u = a.list[li];
+    int64_t lo, hi;
+    const int64_t r = hm_row(a, u, n_e, lo, hi);
+    const int m = (int)(hi - lo);  // 65 .. SR_LDS: the wave kernel listed the user
+    int P = 2;
+    while (P < m) P <<= 1;
+    for (int i = threadIdx.x; i < P; i += 256) s_v[i] = i < m ? hm_column(a, a.idx_pos[lo + i]) : SR_SENT;
+    __syncthreads();  // the staged row is complete
+    const int len = sr_block_tail<true>(a.tmp + lo, m, s_v);
+    if (threadIdx.x == 0) {
+      a.len[r] = len;
+      a.raw_start[r] = (int32_t)lo;
+    }
+    __syncthreads();
+  }
+}
+
+// The listed users of more than SR_LDS raw entries, dealt to the grid's blocks; block b owns bitmap b, zero on entry and between its rows.
+__global__ __launch_bounds__(256) void hm_rows_bitmap_kernel(MatrixArgs a) {
+  __shared__ int s_wsum[256 / SR_WAVE];
+  const int lane = threadIdx.x & (SR_WAVE - 1), wave = threadIdx.x / SR_WAVE;
+  const int n_words = (int)(((int64_t)a.n_cols + 31) >> 5);
+  unsigned* bm = a.bitmaps + (int64_t)blockIdx.x * n_words;
+  const int64_t n_e = ht_entries(a.idx_row_ptr, a.n_users, a.n_events);
+  const int64_t n_heavy = (int64_t)a.ctr[1];
+  for (int64_t li = blockIdx.x; li < n_heavy; li += gridDim.x) {  // block-uniform
+    const int64_t u = a.list[a.n_users - 1 - li];
+    int64_t lo, hi;
+    const int64_t r = hm_row(a, u, n_e, lo, hi);
+    for (int64_t e = lo + threadIdx.x; e < hi; e += 256 * 4) {  // four independent gather chains per thread in flight
+      int c[4];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) c[k] = e + k * 256 < hi ? hm_column(a, a.idx_pos[e + k * 256]) : SR_SENT;
+#pragma unroll
+      for (int k = 0; k < 4; ++k)
+        if (c[k] != SR_SENT) atomicOr(&bm[c[k] >> 5], 1u << (c[k] & 31));
+    }
+    __threadfence();  // this thread's bit sets are performed ...
+    __syncthreads();  // ... and so are everybody's: the walk may take the words
+    int32_t* __restrict__ row = a.tmp + lo;  // distinct columns <= kept entries <= hi - lo: the walk stays inside the raw row
+    int carry = 0;
+    for (int w0 = 0; w0 < n_words; w0 += 256) {  // block-uniform
+      const int w = w0 + (int)threadIdx.x;
+      unsigned word = w < n_words ? atomicExch(&bm[w], 0u) : 0u;
+      const int c = __popc(word);
+      int incl = c;
+      for (int o = 1; o < SR_WAVE; o <<= 1) {  // inclusive wave scan of the popcounts
+        const int below = __shfl_up(incl, o);
+        if (lane >= o) incl += below;
+      }
+      if (lane == SR_WAVE - 1) s_wsum[wave] = incl;
+      __syncthreads();
+      int before = 0, tot = 0;
+#pragma unroll
+      for (int k = 0; k < 256 / SR_WAVE; ++k) {
+        const int s = s_wsum[k];
+        if (k < wave) before += s;
+        tot += s;
+      }
+      int pos = carry + before + incl - c;
+      while (word) {
+        row[pos++] = (w << 5) + __ffsll((unsigned long long)word) - 1;
+        word &= word - 1u;
+      }
+      carry += tot;
+      __syncthreads();  // s_wsum is free; behind the last round: every word is zero again before the next row sets bits
+    }
+    if (threadIdx.x == 0) {
+      a.len[r] = carry;
+      a.raw_start[r] = (int32_t)lo;
+    }
+  }
+}
+
+// row r of the result = the front of its raw row; one wave per row.  Both ends are checked: see the section's head.
+__global__ __launch_bounds__(256) void hm_compact_kernel(MatrixArgs a) {
+  const int lane = threadIdx.x & (SR_WAVE - 1);
+  const int64_t n_waves = (int64_t)gridDim.x * (256 / SR_WAVE);
+  for (int64_t r = (int64_t)blockIdx.x * (256 / SR_WAVE) + threadIdx.x / SR_WAVE; r < a.n_rows; r += n_waves) {
+    const int64_t s = a.raw_start[r], d = a.out_row_ptr[r];
+    const int64_t L = a.out_row_ptr[r + 1] - d;
+    for (int64_t t = lane; t < L; t += SR_WAVE)
+      if (s + t < a.n_events && d + t < a.capacity) a.out_col_idx[d + t] = a.tmp[s + t];
+  }
+  if (blockIdx.x == 0 && threadIdx.x == 0) a.out_nnz[0] = a.out_row_ptr[a.n_rows];
+}
+
+int32_t history_bitmap_blocks(int32_t n_cols, int64_t budget_bytes) {
+  const int64_t bytes = (((int64_t)n_cols + 31) >> 5) * (int64_t)sizeof(unsigned);
+  const int64_t b = budget_bytes / (bytes > 0 ? bytes : 1);
+  return (int32_t)(b < 1 ? 1 : b < HM_BITMAP_BLOCKS ? b : HM_BITMAP_BLOCKS);
+}
+
+hipError_t launch_history_matrix(hipStream_t st, int n_cu, const MatrixArgs& a) {
+  hipError_t e;
+  if (a.n_rows == 0) {
+    e = hipMemsetAsync(a.out_row_ptr, 0, sizeof(int64_t), st);
+    return e != hipSuccess ? e : hipMemsetAsync(a.out_nnz, 0, sizeof(int64_t), st);
+  }
+  e = hipMemsetAsync(a.len, 0, sizeof(int32_t) * (size_t)a.n_rows, st);
+  if (e != hipSuccess) return e;
+  e = hipMemsetAsync(a.raw_start, 0, sizeof(int32_t) * (size_t)a.n_rows, st);
+  if (e != hipSuccess) return e;
+  if (a.n_users > 0 && a.n_events > 0) {
+    e = hipMemsetAsync(a.ctr, 0, sizeof(unsigned long long) * 2, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(hm_rows_wave_kernel, dim3(ig_grid(a.n_users * SR_WAVE, n_cu)), dim3(256), 0, st, a);
+    if (a.n_events > SR_WAVE) {
+      const int64_t bgrid = a.n_users < (int64_t)n_cu * 8 ? a.n_users : (int64_t)n_cu * 8;
+      hipLaunchKernelGGL(hm_rows_block_kernel, dim3((unsigned)bgrid), dim3(256), 0, st, a);
+    }
+    if (a.bm_blocks > 0) {
+      e = hipMemsetAsync(a.bitmaps, 0, sizeof(unsigned) * (size_t)a.bm_blocks * (size_t)(((int64_t)a.n_cols + 31) >> 5), st);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(hm_rows_bitmap_kernel, dim3((unsigned)a.bm_blocks), dim3(256), 0, st, a);
+    }
+  }
+  e = launch_scan_i32(st, a.len, a.n_rows, a.out_row_ptr, a.tile_sums);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(hm_compact_kernel, dim3(ig_grid(a.n_rows * SR_WAVE, n_cu)), dim3(256), 0, st, a);
   return hipGetLastError();
 }
 

@@ -395,6 +395,46 @@ struct TrimArgs {
   int64_t* tile_sums;                   // scratch: scan_tile_words(ceil(n_events / 64))
 };
 hipError_t launch_history_trim(hipStream_t st, int n_cu, const TrimArgs& a);
+// the users that train and their row numbers, one event type's user x column matrix (decision D23; include/urcco.h urcco_dev_history_users / _matrix)
+constexpr int64_t HM_BITMAP_BUDGET = 8ll << 20;  // bytes of arena the column bitmaps of one _matrix launch may take
+constexpr int HM_BITMAP_BLOCKS = 64;             // blocks of the bitmap class at most: one bitmap each
+int32_t history_bitmap_blocks(int32_t n_cols, int64_t budget_bytes);  // min(HM_BITMAP_BLOCKS, budget / bytes of one bitmap), at least 1
+struct UsersArgs {
+  int64_t n_events, n_users, t_lo, t_hi;
+  const int64_t* times_ms;       // nullable: every event is in the window
+  const int64_t* idx_row_ptr;    // [n_users + 1]
+  const int32_t* idx_pos;
+  int32_t min_events;
+  int32_t* out_row_of;           // [n_users]
+  int64_t* out_n_rows;           // [1]
+  unsigned long long* i_bits;    // scratch [ceil(n_events / 64)]: one bit per index entry, "its position is in the window"
+  int32_t* i_cnt;                // scratch [ceil(n_events / 64)]: the words' popcounts
+  int64_t* i_base;               // scratch [ceil(n_events / 64) + 1]: their exclusive scan
+  int32_t* keep;                 // scratch [n_users]: 1 = the user trains
+  int64_t* prefix;               // scratch [n_users + 1]: its exclusive scan
+  int64_t* tile_sums;            // scratch: scan_tile_words(max(ceil(n_events / 64), n_users))
+};
+hipError_t launch_history_users(hipStream_t st, int n_cu, const UsersArgs& a);
+struct MatrixArgs {
+  int64_t n_events, n_users, n_rows, t_lo, t_hi, capacity;
+  const int32_t* items;
+  const int64_t* times_ms;       // nullable
+  const int64_t* idx_row_ptr;    // [n_users + 1]: also the raw row starts
+  const int32_t* idx_pos;
+  const int32_t* row_of;         // nullable: identity
+  int32_t n_cols, bm_blocks;     // bm_blocks: blocks of the bitmap class; 0 = no user can be that heavy (n_events <= 4096)
+  int64_t* out_row_ptr;          // [n_rows + 1]
+  int32_t* out_col_idx;          // [capacity]
+  int64_t* out_nnz;              // [1]
+  int32_t* tmp;                  // scratch [n_events]: the raw rows, user u's at its clamped index segment
+  int32_t* len;                  // scratch [n_rows]: the rows' final lengths
+  int32_t* raw_start;            // scratch [n_rows]: where in tmp the row lies
+  int32_t* list;                 // scratch [n_users]: users of 65 .. 4096 raw entries from the front, heavier ones from the back
+  unsigned long long* ctr;       // scratch [2]: their numbers
+  unsigned* bitmaps;             // scratch [bm_blocks * ceil(n_cols / 32)]
+  int64_t* tile_sums;            // scratch: scan_tile_words(n_rows)
+};
+hipError_t launch_history_matrix(hipStream_t st, int n_cu, const MatrixArgs& a);
 // bnd [(n_types + 1) * n_queries]: scratch; only the inputs of `a` are read
 hipError_t launch_history_bounds(hipStream_t st, int n_cu, const HistArgs& a, int32_t* bnd, int64_t* tile_sums, int64_t* const* term_row_ptr, int64_t* excl_row_ptr);
 hipError_t launch_history_rows(hipStream_t st, int n_cu, const HistArgs& a, int64_t* tile_sums, int64_t* const* term_row_ptr, int32_t* const* term_col_idx,

@@ -788,6 +788,54 @@ int urcco_dev_history_trim(urcco_session* s, int64_t n_events, const int32_t* it
   return URCCO_OK;
 }
 
+// the window of urcco_dev_history_users / _matrix: without times only the open one
+static bool history_window_ok(const int64_t* times_ms, int64_t t_lo, int64_t t_hi) { return times_ms || (t_lo == INT64_MIN && t_hi == INT64_MAX); }
+
+int urcco_dev_history_users(urcco_session* s, int64_t n_events, const int64_t* times_ms, int64_t n_users, const int64_t* idx_row_ptr, const int32_t* idx_pos, int64_t t_lo,
+                            int64_t t_hi, int32_t min_events, int32_t* out_row_of, int64_t* out_n_rows) {
+  if (!s || n_events < 0 || n_events > 0x7fffffffll || n_users < 0 || n_users > 0x7ffffff0ll)
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_users: bad argument (a stream holds fewer than 2^31 events)");
+  if (min_events < 1) return fail(URCCO_BAD_ARG, "urcco_dev_history_users: min_events must be >= 1, got %d", min_events);
+  if (!history_window_ok(times_ms, t_lo, t_hi)) return fail(URCCO_BAD_ARG, "urcco_dev_history_users: a window needs times_ms");
+  if (!out_n_rows || (n_users > 0 && (!idx_row_ptr || !out_row_of)) || (n_events > 0 && !idx_pos)) return fail(URCCO_BAD_ARG, "urcco_dev_history_users: NULL argument");
+  urcco::UsersArgs a{};
+  a.n_events = n_events; a.n_users = n_users; a.t_lo = t_lo; a.t_hi = t_hi; a.times_ms = times_ms; a.idx_row_ptr = idx_row_ptr; a.idx_pos = idx_pos;
+  a.min_events = min_events; a.out_row_of = out_row_of; a.out_n_rows = out_n_rows;
+  const size_t n_words = (size_t)((n_events + 63) >> 6);
+  URC(ArenaLayout(s).add(&a.i_bits, n_words).add(&a.i_cnt, n_words).add(&a.i_base, n_words + 1).add(&a.keep, (size_t)n_users).add(&a.prefix, (size_t)n_users + 1)
+          .add(&a.tile_sums, scan_tile_words(std::max((int64_t)n_words, n_users))).commit());
+  HIPC(urcco::launch_history_users(s->stream, s->n_cu, a));
+  return URCCO_OK;
+}
+
+int urcco_dev_history_matrix(urcco_session* s, int64_t n_events, const int32_t* items, const int64_t* times_ms, int64_t n_users, const int64_t* idx_row_ptr,
+                             const int32_t* idx_pos, int64_t t_lo, int64_t t_hi, int32_t n_cols, const int32_t* row_of, int64_t n_rows, int64_t* out_row_ptr,
+                             int32_t* out_col_idx, int64_t capacity, int64_t* out_nnz) {
+  if (!s || n_events < 0 || n_events > 0x7fffffffll || n_users < 0 || n_users > 0x7ffffff0ll || n_rows < 0 || n_rows > 0x7ffffff0ll || capacity < 0)
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_matrix: bad argument (a stream holds fewer than 2^31 events)");
+  if (n_cols < 1) return fail(URCCO_BAD_ARG, "urcco_dev_history_matrix: n_cols must be >= 1, got %d", n_cols);
+  if (!row_of && n_rows != n_users) return fail(URCCO_BAD_ARG, "urcco_dev_history_matrix: without row_of every user has a row: n_rows must be n_users");
+  if (!history_window_ok(times_ms, t_lo, t_hi)) return fail(URCCO_BAD_ARG, "urcco_dev_history_matrix: a window needs times_ms");
+  if (!out_row_ptr || !out_nnz || (n_users > 0 && !idx_row_ptr) || (n_events > 0 && (!items || !idx_pos)) || (capacity > 0 && !out_col_idx))
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_matrix: NULL argument");
+  urcco::MatrixArgs a{};
+  a.n_events = n_events; a.n_users = n_users; a.n_rows = n_rows; a.t_lo = t_lo; a.t_hi = t_hi; a.capacity = capacity;
+  a.items = items; a.times_ms = times_ms; a.idx_row_ptr = idx_row_ptr; a.idx_pos = idx_pos; a.row_of = row_of; a.n_cols = n_cols;
+  a.out_row_ptr = out_row_ptr; a.out_col_idx = out_col_idx; a.out_nnz = out_nnz;
+  // URCCO_HM_BITMAP_BUDGET lowers the bytes the bitmaps of the heavy-row class may take (read per call): with few bytes one block serves many heavy rows
+  int64_t budget = urcco::HM_BITMAP_BUDGET;
+  if (const char* e = getenv("URCCO_HM_BITMAP_BUDGET")) {
+    const long long v = atoll(e);
+    if (v >= 0 && v < budget) budget = v;
+  }
+  a.bm_blocks = n_events > 4096 && n_users > 0 ? urcco::history_bitmap_blocks(n_cols, budget) : 0;  // 4096 = SR_LDS: no raw row of a shorter stream is heavy
+  const size_t bm_words = (size_t)a.bm_blocks * (size_t)(((int64_t)n_cols + 31) >> 5);
+  URC(ArenaLayout(s).add(&a.tmp, (size_t)n_events).add(&a.len, (size_t)n_rows).add(&a.raw_start, (size_t)n_rows).add(&a.list, (size_t)n_users).add(&a.ctr, 2)
+          .add(&a.bitmaps, bm_words).add(&a.tile_sums, scan_tile_words(n_rows)).commit());
+  HIPC(urcco::launch_history_matrix(s->stream, s->n_cu, a));
+  return URCCO_OK;
+}
+
 int urcco_dev_history_bounds(urcco_session* s, int64_t n_queries, const int32_t* q_users, int64_t n_users, urcco_hist_event* events, int32_t n_types,
                              const int64_t* extra_row_ptr, const int32_t* extra_col_idx, int64_t* excl_row_ptr) {
   urcco::HistArgs a;

@@ -351,6 +351,41 @@ class DeviceSession:
                                                     _ptr(drop_users) if n_drop else None, _ptr(o_items), _ptr(o_times), _ptr(o_rp), _ptr(o_pos), _ptr(counts)))
         return o_items, o_times, o_rp, o_pos, counts
 
+    @staticmethod
+    def _window(after_ms: Optional[int], before_ms: Optional[int]):
+        return (-(1 << 63) if after_ms is None else int(after_ms), (1 << 63) - 1 if before_ms is None else int(before_ms))
+
+    def history_users(self, n_events: int, times: Optional[torch.Tensor], idx_row_ptr: torch.Tensor, idx_pos: torch.Tensor, after_ms: Optional[int] = None,
+                      before_ms: Optional[int] = None, min_events: int = 1):
+        """urcco_dev_history_users (decision D23): which users of a stream's index train.  A user counts its index entries whose event lies in the window
+        after_ms <= time < before_ms (None: open; a window needs `times`), whatever item the event carries.  Returns (row_of int32 [n_users]: the number of
+        kept users below u when u has at least min_events such events, else -1; n_rows int64 [1] on the device).  Does not synchronise."""
+        n_users = int(idx_row_ptr.numel()) - 1
+        row_of = self.empty(max(n_users, 1), torch.int32)
+        n_rows = self.empty(1, torch.int64)
+        t_lo, t_hi = self._window(after_ms, before_ms)
+        self._check(self.lib.urcco_dev_history_users(self.handle, int(n_events), _ptr(times), n_users, _ptr(idx_row_ptr), _ptr(idx_pos), t_lo, t_hi, int(min_events),
+                                                     _ptr(row_of), _ptr(n_rows)))
+        return row_of[:n_users], n_rows
+
+    def history_matrix(self, n_events: int, items: torch.Tensor, times: Optional[torch.Tensor], idx_row_ptr: torch.Tensor, idx_pos: torch.Tensor, n_cols: int,
+                       row_of: Optional[torch.Tensor] = None, n_rows: Optional[int] = None, after_ms: Optional[int] = None, before_ms: Optional[int] = None,
+                       capacity: Optional[int] = None):
+        """urcco_dev_history_matrix (decision D23): the user x column matrix of one event type from its stream (items int32, times int64 | None) and its
+        index: row row_of[u] (None: u itself, n_rows = n_users) holds the distinct items of u's events in the window, ascending, those outside
+        0 .. n_cols dropped.  Returns (row_ptr int64 [n_rows + 1], col_idx int32 [capacity], nnz int64 [1] on the device); capacity defaults to n_events,
+        with which no row is lost.  Does not synchronise."""
+        n, n_users = int(n_events), int(idx_row_ptr.numel()) - 1
+        n_rows = n_users if n_rows is None else int(n_rows)
+        capacity = n if capacity is None else int(capacity)
+        row_ptr = self.empty(n_rows + 1, torch.int64)
+        col_idx = self.empty(max(capacity, 1), torch.int32)
+        nnz = self.empty(1, torch.int64)
+        t_lo, t_hi = self._window(after_ms, before_ms)
+        self._check(self.lib.urcco_dev_history_matrix(self.handle, n, _ptr(items), _ptr(times), n_users, _ptr(idx_row_ptr), _ptr(idx_pos), t_lo, t_hi, int(n_cols),
+                                                      _ptr(row_of), n_rows, _ptr(row_ptr), _ptr(col_idx), capacity, _ptr(nnz)))
+        return row_ptr, col_idx, nnz
+
     def history_rows(self, q_users: torch.Tensor, n_users: int, events, n_items: int, extra=None, stats: bool = False, timing: bool = False, keep_bounds: bool = False):
         """urcco_dev_history_bounds + urcco_dev_history_rows: the user-history term rows and the exclusion rows of a batch of queries.
         q_users: int32 [n_queries] dense user ids (< 0 or >= n_users: unknown).  events: per event type (n_cols, max_items, blacklist, idx_row_ptr, idx_pos,

@@ -249,6 +249,42 @@ class DeviceHistory:
             st.idx_buf, st.idx_row_ptr, st.idx_pos, st.n_events = (o_rp, o_pos), o_rp[: self.n_users + 1], o_pos[: max(k, 1)], int(k)
         return self
 
+    def matrices(self, events: List[str], after_ms: Optional[int] = None, before_ms: Optional[int] = None, min_events_per_user: int = 1):
+        """The Preparator's output from the resident streams (decision D23 of DESIGN.md; include/urcco.h urcco_dev_history_users / _matrix): one user x
+        column matrix per event type of `events`, rows sorted and duplicate-free, over the events with after_ms <= time < before_ms (None: open).
+        events[0] is the primary: the users with at least min_events_per_user of ITS events in the window (whatever their items) are the rows, numbered in
+        ascending user id; the other types keep those users' events only.  Returns (row_of int32 [n_users] on the device: a user's row or -1, n_rows,
+        {event: DevCsr}): every matrix has n_rows rows and the stream's n_cols columns -- what device.cross_occurrence_device takes.  The history itself is
+        not modified.  Two device-to-host reads: n_rows, then the nnz of all matrices together.
+
+        ValueError: `events` is empty or names a type the history does not hold; a window and a stream without times; min_events_per_user < 1; a
+        _Stream built by hand without n_events."""
+        from .device import DevCsr
+        events = list(events)
+        if not events:
+            raise ValueError("matrices: at least the primary event type is needed")
+        if int(min_events_per_user) < 1:
+            raise ValueError(f"matrices: min_events_per_user must be >= 1, got {min_events_per_user}")
+        for ev in events:
+            st = self.types.get(ev)
+            if st is None:
+                raise ValueError(f"matrices: the history holds no event type {ev!r}")
+            if st.n_events < 0:
+                raise ValueError(f"stream {ev!r}: built without its number of events (_Stream.n_events)")
+            if st.times is None and (after_ms is not None or before_ms is not None):
+                raise ValueError(f"matrices: the stream {ev!r} has no times, a window cannot apply to it")
+        sess = self.sess
+        p = self.types[events[0]]
+        row_of, n_rows_dev = sess.history_users(p.n_events, p.times, p.idx_row_ptr, p.idx_pos, after_ms, before_ms, int(min_events_per_user))
+        n_rows = int(n_rows_dev.item())      # the first read: it sizes every row_ptr
+        calls = {}
+        for ev in events:
+            if ev not in calls:
+                st = self.types[ev]
+                calls[ev] = sess.history_matrix(st.n_events, st.items, st.times, st.idx_row_ptr, st.idx_pos, st.n_cols, row_of, n_rows, after_ms, before_ms)
+        nnz = torch.cat([c[2] for c in calls.values()]).cpu().tolist()      # the second read
+        return row_of, n_rows, {ev: DevCsr(n_rows, self.types[ev].n_cols, rp, ci, int(k)) for (ev, (rp, ci, _)), k in zip(calls.items(), nnz)}
+
     @staticmethod
     def from_dict(sess: DeviceSession, model, history: Dict[str, Dict[str, List[str]]]) -> "DeviceHistory":
         """The dict form of batch_predict's `history` (user -> {event name: [item ids, oldest first]}) loaded onto the device: every user gets a

@@ -136,6 +136,7 @@ class URAlgorithmParams:
     blacklistEvents: Optional[List[str]] = None    # :236: None = the primary event, [] = no blacklist
     returnSelf: Optional[bool] = None              # :237
     termWeights: Optional[str] = None              # additive key: the default of the query side's term_weights (decision D20): absent = every matching term scores 1, "idf"
+    minEventsPerUser: Optional[int] = None         # additive key: the datasource's minEventsPerUser for train_from_history, which has no DataSource in front of it; absent = 1
 
     @staticmethod
     def from_engine_json(engine: dict, name: str = "ur") -> "URAlgorithmParams":
@@ -156,7 +157,8 @@ class URAlgorithmParams:
             indicators=None if inds is None else [IndicatorParams(i["name"], i.get("maxItemsPerUser"), i.get("maxCorrelatorsPerItem"),
                                                                   i.get("minLLR")) for i in inds],
             seed=p.get("seed"), num=p.get("num"), maxQueryEvents=p.get("maxQueryEvents"), userBias=p.get("userBias"), itemBias=p.get("itemBias"),
-            blacklistEvents=p.get("blacklistEvents"), returnSelf=p.get("returnSelf"), termWeights=p.get("termWeights"))
+            blacklistEvents=p.get("blacklistEvents"), returnSelf=p.get("returnSelf"), termWeights=p.get("termWeights"),
+            minEventsPerUser=p.get("minEventsPerUser"))
 
 
 def _get_or_else(v, default):
@@ -306,7 +308,7 @@ class URAlgorithm:
         the host, dictionaries and matrices are built in HBM (Preparator.prepare_on_device) and those device matrices go
         straight into the CCO build (device.cross_occurrence_device); only the indicator rows come back.  Same model as
         `train(Preparator().prepare(trainingData))`."""
-        from .device import DatasetParams, cross_occurrence_device
+        from .device import cross_occurrence_device
         from .preparator import Preparator
         from .similarity_analysis import _seed_to_int
         if self.recsModel not in ("all", "collabFiltering"):
@@ -314,15 +316,7 @@ class URAlgorithm:
         ap = self.ap
         pd, dp = Preparator().prepare_on_device(trainingData, sess, keep_on_device=True)
         seed = ap.seed if ap.seed is not None else int(time.time() * 1000)
-        if not ap.indicators:
-            params = [DatasetParams(_get_or_else(ap.maxEventsPerEventType, DefaultURAlgoParams.MaxEventsPerEventType),
-                                    _get_or_else(ap.maxCorrelatorsPerEventType, DefaultURAlgoParams.MaxCorrelatorsPerEventType), None) for _ in dp.events]
-        else:
-            if len(ap.indicators) < len(dp.events):
-                raise IndexError("indicators(i) is matched to the event matrices by position (URAlgorithm.scala:334-340)")
-            params = [DatasetParams(_get_or_else(ap.indicators[i].maxItemsPerUser, DefaultURAlgoParams.MaxEventsPerEventType),
-                                    _get_or_else(ap.indicators[i].maxCorrelatorsPerItem, DefaultURAlgoParams.MaxCorrelatorsPerEventType),
-                                    ap.indicators[i].minLLR) for i in range(len(dp.events))]
+        params = self._dataset_params(len(dp.events))
         res = cross_occurrence_device(sess, [ev.matrix for ev in dp.events], params, _seed_to_int(seed))
         sess.synchronize()
         primary = pd.actions[0][1]
@@ -331,6 +325,56 @@ class URAlgorithm:
             rp, ci, llr = ind.to_host()
             out.append((name, primary.create(rp, ci, primary.columnIDs, ids.columnIDs, llr)))
         return out
+
+
+    def _dataset_params(self, n: int):
+        """The DatasetParams of the n event matrices of a device build, as calcAll fills them (:322-341)"""
+        from .device import DatasetParams
+        ap = self.ap
+        if not ap.indicators:
+            return [DatasetParams(_get_or_else(ap.maxEventsPerEventType, DefaultURAlgoParams.MaxEventsPerEventType),
+                                  _get_or_else(ap.maxCorrelatorsPerEventType, DefaultURAlgoParams.MaxCorrelatorsPerEventType), None) for _ in range(n)]
+        if len(ap.indicators) < n:
+            raise IndexError("indicators(i) is matched to the event matrices by position (URAlgorithm.scala:334-340)")
+        return [DatasetParams(_get_or_else(ap.indicators[i].maxItemsPerUser, DefaultURAlgoParams.MaxEventsPerEventType),
+                              _get_or_else(ap.indicators[i].maxCorrelatorsPerItem, DefaultURAlgoParams.MaxCorrelatorsPerEventType),
+                              ap.indicators[i].minLLR) for i in range(n)]
+
+    def train_from_history(self, history, after_ms: Optional[int] = None, before_ms: Optional[int] = None, ranks=None, properties=None, date_names=None,
+                           seed: Optional[int] = None):
+        """Retrain from the event store on the device (decision D23 of DESIGN.md): DataSource.readTraining -> Preparator.prepare -> calcAll over a
+        history.DeviceHistory -- the streams that `append` grows and `trim` ages -- without a copy of the events on the host.  The event types are
+        modelEventNames, the primary first; the events with after_ms <= time < before_ms (None: open); the users with at least minEventsPerUser (the
+        algorithm parameter, absent = 1) primary events in the window.  DeviceHistory.matrices -> device.cross_occurrence_device with the DatasetParams
+        of train_events_on_device -> recommend.DeviceModel.from_indicators with the item and column dictionaries of history.model: the id spaces are the
+        history's and do not change.  ranks, properties, date_names go to from_indicators; when all three are None the new model takes over
+        history.model's fill_order, properties and dates, which are indexed by the same primary item ids.  seed: default the algorithm parameter, else
+        the clock.  history.model is not rebound: the caller decides when to swap.
+
+        ValueError: recsModel is not "all" or "collabFiltering"; the history has no model; it does not hold the stream of an event type (the primary's
+        first); what DeviceHistory.matrices raises."""
+        from .device import cross_occurrence_device
+        from .recommend import DeviceModel
+        from .similarity_analysis import _seed_to_int
+        if self.recsModel not in ("all", "collabFiltering"):
+            raise ValueError(f"train_from_history builds the CCO model: recsModel must be all or collabFiltering, not {self.recsModel!r}")
+        old = history.model
+        if old is None:
+            raise ValueError("train_from_history: the history was built without a model to take the item and column dictionaries from")
+        names = list(self.modelEventNames)
+        if names[0] not in history.types:
+            raise ValueError(f"train_from_history: the history holds no stream of the primary event {names[0]!r}")
+        ap = self.ap
+        _, _, mats = history.matrices(names, after_ms, before_ms, _get_or_else(ap.minEventsPerUser, 1))
+        if seed is None:
+            seed = ap.seed if ap.seed is not None else int(time.time() * 1000)
+        res = cross_occurrence_device(history.sess, [mats[n] for n in names], self._dataset_params(len(names)), _seed_to_int(seed))
+        column_ids = {c.name: c.column_ids for c in old.correlators if c.column_ids is not None}
+        fresh = ranks is not None or properties is not None or date_names is not None
+        model = DeviceModel.from_indicators(history.sess, list(zip(names, res)), ranks, old.item_ids, column_ids, properties, date_names or ())
+        if not fresh:
+            model.fill_order, model.properties, model.dates = old.fill_order, old.properties, old.dates
+        return model
 
 
 def toStringMap(indexedDataset: IndexedDataset, actionName: str) -> Dict[str, Dict[str, List[str]]]:
