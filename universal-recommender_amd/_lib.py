@@ -36,6 +36,10 @@ REC_WEIGHT_ONE = 1 << 15   # urcco_dev_recommend_weighted (URCCO_REC_WEIGHT_*): 
 REC_WEIGHT_MAX = 1 << 20   # ... from 1 to 32.0
 EVAL_MAX_KS = 8        # urcco_dev_rank_metrics (URCCO_EVAL_MAX_KS): cut-offs per call
 EVAL_TREE_BLOCK = 256  # positions one block of the tree sum reduces (csrc/cco_eval.h): beyond it a further pass runs over the partials
+RANK_POPULAR, RANK_TRENDING, RANK_HOT = 1, 2, 3   # urcco_dev_history_ranks (URCCO_RANK_*): the ranking type = the number of intervals
+RANK_NONE = -(1 << 63)   # the item has no rank in the field (INT64_MIN)
+RANK_MAX_STREAMS = 16
+RANK_MAX_FIELDS = 4    # urcco_dev_fill_order: rank fields per call
 HIST_STATS_LEN = 8     # urcco_dev_history_rows (URCCO_HIST_STATS_LEN): pairs per class, selects, exclusion rows per class, overflows
 REC_LDS_LIMIT = 3072   # work bound w(q) up to which a query runs in the LDS class (csrc/cco_kernels.h)
 EXCH_SIZES = 4   # int64 words of a shard's record (include/urcco.h URCCO_EXCH_SIZES)
@@ -147,6 +151,11 @@ class HistEvent(C.Structure):
                 ("term_col_idx", C.c_void_p), ("term_capacity", C.c_int64)]
 
 
+class RankStream(C.Structure):
+    """urcco_rank_stream: one event stream of urcco_dev_history_ranks."""
+    _fields_ = [("n_events", C.c_int64), ("items", C.c_void_p), ("times_ms", C.c_void_p), ("col_map", C.c_void_p), ("n_cols", C.c_int32), ("reserved", C.c_int32)]
+
+
 class ItemEvent(C.Structure):
     """urcco_item_event: one event type of urcco_dev_item_bounds / _rows."""
     _fields_ = [("n_cols", C.c_int32), ("max_terms", C.c_int32), ("ind_row_ptr", C.c_void_p), ("ind_col_idx", C.c_void_p), ("term_row_ptr", C.c_void_p),
@@ -223,6 +232,8 @@ SYMBOLS = {
     "urcco_dev_history_trim": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p]),
     "urcco_dev_history_users": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, C.c_int32, _p, _p]),
     "urcco_dev_history_matrix": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, C.c_int32, _p, C.c_int64, _p, _p, C.c_int64, _p]),
+    "urcco_dev_history_ranks": (C.c_int, [_p, C.POINTER(RankStream), C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _p, _p]),
+    "urcco_dev_fill_order": (C.c_int, [_p, C.c_int32, C.POINTER(C.c_void_p), C.c_int32, _p]),
     "urcco_dev_history_bounds": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.POINTER(HistEvent), C.c_int32, _p, _p, _p]),
     "urcco_dev_history_rows": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.POINTER(HistEvent), C.c_int32, _p, _p, C.c_int32, _p, _p, C.c_int64, _p]),
     "urcco_dev_item_bounds": (C.c_int, [_p, C.c_int64, _p, C.c_int32, C.POINTER(ItemEvent), C.c_int32]),

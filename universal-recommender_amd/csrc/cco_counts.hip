@@ -664,5 +664,97 @@ hipError_t launch_pop_counts(hipStream_t st, int n_cu, int64_t n, const int32_t*
   return hipGetLastError();
 }
 
+// ============================================================================================
+// The same histograms over the streams of a resident history (urcco_dev_history_ranks, decision D24): one table that several streams add to, times
+// that may be absent (the open popular call: every event is in interval 0), a last interval that may have no end, and ids counted in the STREAM's
+// column space -- table[b * stride + c] for 0 <= c < limit.  A stream with a column map is counted into a table of its own columns and folded into
+// the item table afterwards, one thread per column (rank_fold_kernel): n_cols gathers of the map per stream instead of one scattered gather per event.
+// The caller clears the table; cc_insert's cache sits in front of it as above.
+// ============================================================================================
+__global__ __launch_bounds__(CC_THREADS) void rank_counts_kernel(int64_t n, const int32_t* __restrict__ item, const int64_t* __restrict__ t_ms, int32_t limit,
+                                                               int32_t stride, int n_buckets, int open_end, PopBounds bounds, int32_t* __restrict__ table) {
+  __shared__ int s_key[CC_SLOTS];
+  __shared__ int s_cnt[CC_SLOTS];
+  for (int s = threadIdx.x; s < CC_SLOTS; s += CC_THREADS) {
+    s_key[s] = 0;
+    s_cnt[s] = 0;
+  }
+  __syncthreads();
+  for (int64_t e = (int64_t)blockIdx.x * CC_THREADS + threadIdx.x; e < n; e += (int64_t)gridDim.x * CC_THREADS) {
+    const int c = item[e];
+    if (c < 0 || c >= limit) continue;
+    int b = 0;
+    if (t_ms) {
+      const long long t = t_ms[e];
+      b = -1;
+#pragma unroll
+      for (int k = 0; k < 3; ++k)
+        if (k < n_buckets && t >= bounds.b[k] && (t < bounds.b[k + 1] || (open_end && k == n_buckets - 1))) b = k;
+    }
+    if (b >= 0) cc_insert(s_key, s_cnt, table, b * stride + c);
+  }
+  __syncthreads();
+  for (int s = threadIdx.x; s < CC_SLOTS; s += CC_THREADS)
+    if (s_key[s] != 0) atomicAdd(&table[s_key[s] - 1], s_cnt[s]);
+}
+
+// counts[b * n_items + col_map[c]] += col_counts[b * n_cols + c]: an integer atomic, because two columns may map to one item
+__global__ __launch_bounds__(256) void rank_fold_kernel(const int32_t* __restrict__ col_counts, const int32_t* __restrict__ col_map, int32_t n_cols, int32_t n_items,
+                                                        int n_buckets, int32_t* __restrict__ counts) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= n_cols) return;
+  const int i = col_map[c];
+  if (i < 0 || i >= n_items) return;
+  for (int b = 0; b < n_buckets; ++b) {
+    const int v = col_counts[(int64_t)b * n_cols + c];
+    if (v != 0) atomicAdd(&counts[(int64_t)b * n_items + i], v);
+  }
+}
+
+// popular: c0 > 0 ? c0; trending: c0, c1 > 0 ? c1 - c0; hot: c0, c1, c2 > 0 ? (c2 - c1) - (c1 - c0); else RANK_NONE -- the joins of PopModel.scala:113-179
+__global__ __launch_bounds__(256) void rank_derive_kernel(const int32_t* __restrict__ counts, int32_t n_items, int n_buckets, int64_t* __restrict__ out_rank,
+                                                          int32_t* __restrict__ out_counts) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_items) return;
+  long long c[3] = {0, 0, 0};
+  bool all = true;
+  for (int b = 0; b < n_buckets; ++b) {
+    const int v = counts[(int64_t)b * n_items + i];
+    c[b] = v;
+    all = all && v > 0;
+    if (out_counts) out_counts[(int64_t)b * n_items + i] = v;
+  }
+  const long long r = n_buckets == 1 ? c[0] : (n_buckets == 2 ? c[1] - c[0] : (c[2] - c[1]) - (c[1] - c[0]));
+  out_rank[i] = all ? r : RANK_NONE;
+}
+
+hipError_t launch_rank_counts(hipStream_t st, int n_cu, const RankStream* streams, int n_streams, int32_t n_items, int n_buckets, const int64_t* bounds, bool open_end,
+                              int32_t* counts, int32_t* col_counts, int64_t* out_rank, int32_t* out_counts) {
+  hipError_t e = hipMemsetAsync(counts, 0, sizeof(int32_t) * (size_t)n_items * (size_t)n_buckets, st);
+  if (e != hipSuccess) return e;
+  PopBounds pb;
+  for (int k = 0; k < 4; ++k) pb.b[k] = k <= n_buckets ? bounds[k] : bounds[n_buckets];
+  for (int s = 0; s < n_streams; ++s) {
+    const RankStream& r = streams[s];
+    if (r.n_events == 0 || r.n_cols == 0) continue;
+    int64_t blocks = (r.n_events + (int64_t)CC_THREADS * 8 - 1) / ((int64_t)CC_THREADS * 8);
+    const int64_t cap = (int64_t)n_cu * 4;
+    if (blocks > cap) blocks = cap;
+    if (!r.col_map) {  // the stream's columns are the items: straight into the item table, ids at or beyond n_items dropped
+      const int32_t limit = r.n_cols < n_items ? r.n_cols : n_items;
+      hipLaunchKernelGGL(rank_counts_kernel, dim3((unsigned)blocks), dim3(CC_THREADS), 0, st, r.n_events, r.items, r.times_ms, limit, n_items, n_buckets, open_end ? 1 : 0,
+                         pb, counts);
+      continue;
+    }
+    e = hipMemsetAsync(col_counts, 0, sizeof(int32_t) * (size_t)r.n_cols * (size_t)n_buckets, st);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(rank_counts_kernel, dim3((unsigned)blocks), dim3(CC_THREADS), 0, st, r.n_events, r.items, r.times_ms, r.n_cols, r.n_cols, n_buckets, open_end ? 1 : 0,
+                       pb, col_counts);
+    hipLaunchKernelGGL(rank_fold_kernel, dim3((unsigned)(((int64_t)r.n_cols + 255) / 256)), dim3(256), 0, st, col_counts, r.col_map, r.n_cols, n_items, n_buckets, counts);
+  }
+  hipLaunchKernelGGL(rank_derive_kernel, dim3((unsigned)(((int64_t)n_items + 255) / 256)), dim3(256), 0, st, counts, n_items, n_buckets, out_rank, out_counts);
+  return hipGetLastError();
+}
+
 
 }  // namespace urcco

@@ -237,6 +237,35 @@ hipError_t launch_publish_word(hipStream_t st, const unsigned long long* src, un
 hipError_t launch_pop_counts(hipStream_t st, int n_cu, int64_t n, const int32_t* item, const int64_t* t_ms, int32_t n_items, int n_buckets,
                              const int64_t* bounds, int32_t* counts);
 
+// ---- backfill ranks from a resident history (decision D24; include/urcco.h urcco_dev_history_ranks / urcco_dev_fill_order) ----------------------
+constexpr int RANK_MAX_STREAMS = 16;            // == URCCO_RANK_MAX_STREAMS ... of include/urcco.h (checked in urcco_internal.h)
+constexpr int RANK_MAX_FIELDS = 4;
+constexpr long long RANK_NONE = INT64_MIN;      // the item has no rank in the field
+struct RankStream {
+  int64_t n_events;
+  const int32_t* items;      // column id per stream position
+  const int64_t* times_ms;   // nullable: only the open popular call
+  const int32_t* col_map;    // nullable (identity): [n_cols] -> item id or -1
+  int32_t n_cols;
+};
+// The interval histograms of launch_pop_counts summed over the streams (cco_counts.hip), then the ranks.  counts [n_buckets * n_items], col_counts
+// [n_buckets * the largest n_cols of a stream with a col_map]: scratch.  open_end: the last interval has no end.  out_counts: nullable.
+hipError_t launch_rank_counts(hipStream_t st, int n_cu, const RankStream* streams, int n_streams, int32_t n_items, int n_buckets, const int64_t* bounds, bool open_end,
+                              int32_t* counts, int32_t* col_counts, int64_t* out_rank, int32_t* out_counts);
+// The backfill order (cco_ranks.h, compiled into cco_misc.hip behind cco_eval.h): a stable LSD radix sort of (key, item) pairs, 8-bit digits.
+constexpr int RK_TILE = 2048;                   // pairs one block counts and places per pass
+inline int64_t fill_order_tiles(int32_t n_items) { return ((int64_t)n_items + RK_TILE - 1) / RK_TILE; }
+struct FillOrderScratch {
+  unsigned long long* keys[2];   // [n_items] each: the two sides the passes alternate between
+  int32_t* ids[2];               // [n_items] each
+  unsigned long long* differ;    // [2 * RANK_MAX_FIELDS]: per field the bits in which two keys differ, then per field the smallest key
+  int32_t* hist;                 // [256 * fill_order_tiles]: digit-major per-tile digit counts
+  int64_t* offsets;              // [256 * fill_order_tiles + 1]: their exclusive scan
+  int64_t* tile_sums;            // scan_tile_words(256 * fill_order_tiles)
+};
+// ranks: host array of n_fields device pointers
+hipError_t launch_fill_order(hipStream_t st, int32_t n_items, const int64_t* const* ranks, int n_fields, const FillOrderScratch& s, int32_t* out_order);
+
 // out[e] = col_idx[e] | counts16[col_idx[e]] << (32 - count_bits) for e < *nnz_dev (<= nnz_bound); counts16 / bad16 as launch_narrow_counts leaves them;
 // bad[0] (zeroed here) = counts that do not fit (or 1 when *bad16 != 0: nothing packed)
 hipError_t launch_pack_counts(hipStream_t st, int n_cu, const int32_t* col_idx, const int64_t* nnz_dev, int64_t nnz_bound, const unsigned short* counts16,

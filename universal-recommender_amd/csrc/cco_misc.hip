@@ -13,6 +13,7 @@
 #include "cco_select.h"
 #include "cco_recommend.h"
 #include "cco_eval.h"
+#include "cco_ranks.h"
 
 
 namespace urcco {

@@ -836,6 +836,61 @@ int urcco_dev_history_matrix(urcco_session* s, int64_t n_events, const int32_t* 
   return URCCO_OK;
 }
 
+int urcco_dev_history_ranks(urcco_session* s, const urcco_rank_stream* streams, int32_t n_streams, int32_t n_items, int32_t type, int64_t t_start, int64_t t_end,
+                            int64_t* out_rank, int32_t* out_counts) {
+  if (!s || n_items < 0 || (n_items > 0 && !out_rank)) return fail(URCCO_BAD_ARG, "urcco_dev_history_ranks: bad argument");
+  if (type < URCCO_RANK_POPULAR || type > URCCO_RANK_HOT) return fail(URCCO_BAD_ARG, "urcco_dev_history_ranks: type must be popular (1), trending (2) or hot (3), got %d", type);
+  if (n_streams < 0 || n_streams > URCCO_RANK_MAX_STREAMS || (n_streams > 0 && !streams))
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_ranks: between 0 and %d streams, got %d", URCCO_RANK_MAX_STREAMS, n_streams);
+  if (t_end < t_start) return fail(URCCO_BAD_ARG, "urcco_dev_history_ranks: t_end lies before t_start");
+  const int n_int = type;  // popular 1, trending 2, hot 3 intervals
+  int64_t bounds[4] = {t_start, t_end, t_end, t_end};
+  if (n_int > 1) {
+    int64_t d;
+    if (__builtin_sub_overflow(t_end, t_start, &d)) return fail(URCCO_BAD_ARG, "urcco_dev_history_ranks: t_end - t_start does not fit 64 bits");
+    const int64_t step = d / n_int;  // the reference's integer division (PopModel.scala:133, :158)
+    for (int k = 1; k < n_int; ++k) bounds[k] = t_start + k * step;
+    bounds[n_int] = t_end;
+  }
+  if ((int64_t)n_items * 3 > 0x7ffffff0ll) return fail(URCCO_BAD_ARG, "urcco_dev_history_ranks: too many items");
+  const bool open = type == URCCO_RANK_POPULAR && t_start == INT64_MIN && t_end == INT64_MAX;
+  urcco::RankStream rs[URCCO_RANK_MAX_STREAMS];
+  int64_t total = 0;
+  int32_t map_cols = 0;  // the widest stream that is counted in its own column space
+  for (int k = 0; k < n_streams; ++k) {
+    const urcco_rank_stream& in = streams[k];
+    if (in.n_events < 0 || in.n_cols < 0 || (in.n_events > 0 && !in.items)) return fail(URCCO_BAD_ARG, "urcco_dev_history_ranks: stream %d: bad argument", k);
+    if (!in.times_ms && !open) return fail(URCCO_BAD_ARG, "urcco_dev_history_ranks: stream %d: only the popular ranking over the open window needs no times_ms", k);
+    if (in.col_map && (int64_t)in.n_cols * 3 > 0x7ffffff0ll) return fail(URCCO_BAD_ARG, "urcco_dev_history_ranks: stream %d: too many columns", k);
+    total += in.n_events;
+    if (total > 0x7fffffffll) return fail(URCCO_BAD_ARG, "urcco_dev_history_ranks: the streams hold 2^31 events or more: the counts are 32-bit");
+    if (in.col_map && in.n_events > 0 && in.n_cols > map_cols) map_cols = in.n_cols;
+    rs[k] = urcco::RankStream{in.n_events, in.items, in.times_ms, in.col_map, in.n_cols};
+  }
+  if (n_items == 0) return URCCO_OK;
+  int32_t *counts, *col_counts;
+  URC(ArenaLayout(s).add(&counts, (size_t)n_items * (size_t)n_int).add(&col_counts, (size_t)map_cols * (size_t)n_int).commit());
+  HIPC(urcco::launch_rank_counts(s->stream, s->n_cu, rs, n_streams, n_items, n_int, bounds, t_end == INT64_MAX, counts, col_counts, out_rank, out_counts));
+  return URCCO_OK;
+}
+
+int urcco_dev_fill_order(urcco_session* s, int32_t n_items, const int64_t* const* ranks, int32_t n_fields, int32_t* out_order) {
+  if (!s || n_items < 0 || (n_items > 0 && !out_order)) return fail(URCCO_BAD_ARG, "urcco_dev_fill_order: bad argument");
+  if (n_fields < 0 || n_fields > URCCO_RANK_MAX_FIELDS || (n_fields > 0 && !ranks))
+    return fail(URCCO_BAD_ARG, "urcco_dev_fill_order: between 0 and %d rank fields, got %d", URCCO_RANK_MAX_FIELDS, n_fields);
+  for (int f = 0; f < n_fields; ++f)
+    if (!ranks[f]) return fail(URCCO_BAD_ARG, "urcco_dev_fill_order: rank field %d is NULL", f);
+  if (n_items == 0) return URCCO_OK;
+  urcco::FillOrderScratch w{};
+  if (n_fields > 0) {
+    const size_t n = (size_t)n_items, m = 256 * (size_t)urcco::fill_order_tiles(n_items);
+    URC(ArenaLayout(s).add(&w.keys[0], n).add(&w.keys[1], n).add(&w.ids[0], n).add(&w.ids[1], n).add(&w.differ, 2 * urcco::RANK_MAX_FIELDS).add(&w.hist, m)
+            .add(&w.offsets, m + 1).add(&w.tile_sums, scan_tile_words((int64_t)m)).commit());
+  }
+  HIPC(urcco::launch_fill_order(s->stream, n_items, ranks, n_fields, w, out_order));
+  return URCCO_OK;
+}
+
 int urcco_dev_history_bounds(urcco_session* s, int64_t n_queries, const int32_t* q_users, int64_t n_users, urcco_hist_event* events, int32_t n_types,
                              const int64_t* extra_row_ptr, const int32_t* extra_col_idx, int64_t* excl_row_ptr) {
   urcco::HistArgs a;

@@ -23,6 +23,8 @@ static_assert(urcco::REC_MAX_CLAUSES == URCCO_REC_MAX_CLAUSES && urcco::REC_MAX_
               "include/urcco.h and cco_kernels.h agree on the recommendation call");
 static_assert(urcco::HIST_STATS_LEN == URCCO_HIST_STATS_LEN, "include/urcco.h and cco_kernels.h agree on the history calls");
 static_assert(urcco::EVAL_MAX_KS == URCCO_EVAL_MAX_KS, "include/urcco.h and cco_kernels.h agree on the evaluation call");
+static_assert(urcco::RANK_MAX_STREAMS == URCCO_RANK_MAX_STREAMS && urcco::RANK_MAX_FIELDS == URCCO_RANK_MAX_FIELDS && urcco::RANK_NONE == URCCO_RANK_NONE,
+              "include/urcco.h and cco_kernels.h agree on the rank calls");
 
 struct urcco_session;
 namespace urcco_detail {

@@ -386,6 +386,37 @@ class DeviceSession:
                                                       _ptr(row_of), n_rows, _ptr(row_ptr), _ptr(col_idx), capacity, _ptr(nnz)))
         return row_ptr, col_idx, nnz
 
+    def history_ranks(self, streams, n_items: int, type: int, t_start: int, t_end: int, counts: bool = False):
+        """urcco_dev_history_ranks (decision D24): the popular (1) / trending (2) / hot (3) rank of every item of the primary's dictionary from event streams
+        on the device.  streams: per stream (n_events, items int32, times_ms int64 | None, col_map int32 | None, n_cols).  The window [t_start, t_end) is cut
+        into `type` intervals; t_end = 2^63 - 1: no end.  Returns rank int64 [n_items] (_lib.RANK_NONE: no rank), with counts=True (rank, counts int32
+        [type, n_items]).  Does not synchronise."""
+        arr = (_lib.RankStream * max(len(streams), 1))()
+        for k, (n, items, times, col_map, n_cols) in enumerate(streams):
+            arr[k] = _lib.RankStream(int(n), _ptr(items), _ptr(times), _ptr(col_map), int(n_cols), 0)
+        rank = self.empty(max(n_items, 1), torch.int64)
+        cnt = self.empty(max(n_items * int(type), 1), torch.int32) if counts else None
+        self._check(self.lib.urcco_dev_history_ranks(self.handle, arr, len(streams), int(n_items), int(type), int(t_start), int(t_end), _ptr(rank), _ptr(cnt)))
+        rank = rank[:n_items]
+        return (rank, cnt[: n_items * int(type)].view(int(type), n_items)) if counts else rank
+
+    def fill_order(self, ranks) -> torch.Tensor:
+        """urcco_dev_fill_order (decision D24): the backfill order of a model from up to _lib.RANK_MAX_FIELDS rank fields -- int64 device tensors of one length,
+        _lib.RANK_NONE where an item has no rank: the items sorted by (field 0 desc, field 1 desc, ..., item id asc), an item without a rank last in its
+        field.  Returns int32 [n_items].  Does not synchronise."""
+        ranks = list(ranks)
+        if not ranks:
+            raise ValueError("fill_order: at least one rank field (a model without ranks has no fill order)")
+        n_items = int(ranks[0].numel())
+        if any(r.dtype != torch.int64 or int(r.numel()) != n_items for r in ranks):
+            raise ValueError("fill_order: int64 rank fields of one length expected")
+        if n_items == 0:
+            return self.empty(0, torch.int32)
+        ptrs = (C.c_void_p * len(ranks))(*[r.data_ptr() for r in ranks])
+        out = self.empty(max(n_items, 1), torch.int32)
+        self._check(self.lib.urcco_dev_fill_order(self.handle, n_items, ptrs, len(ranks), _ptr(out)))
+        return out[:n_items]
+
     def history_rows(self, q_users: torch.Tensor, n_users: int, events, n_items: int, extra=None, stats: bool = False, timing: bool = False, keep_bounds: bool = False):
         """urcco_dev_history_bounds + urcco_dev_history_rows: the user-history term rows and the exclusion rows of a batch of queries.
         q_users: int32 [n_queries] dense user ids (< 0 or >= n_users: unknown).  events: per event type (n_cols, max_items, blacklist, idx_row_ptr, idx_pos,

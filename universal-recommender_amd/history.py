@@ -285,6 +285,53 @@ class DeviceHistory:
         nnz = torch.cat([c[2] for c in calls.values()]).cpu().tolist()      # the second read
         return row_of, n_rows, {ev: DevCsr(n_rows, self.types[ev].n_cols, rp, ci, int(k)) for (ev, (rp, ci, _)), k in zip(calls.items(), nnz)}
 
+    def ranks(self, rankings, now_ms: Optional[int] = None, model_event_names=None) -> Dict[str, torch.Tensor]:
+        """The backfill rank fields from the resident streams (decision D24 of DESIGN.md; include/urcco.h urcco_dev_history_ranks): PopModel.calc per entry
+        of `rankings`, over the events the history holds instead of an event list on the host.  rankings: the dict form of pop_model.getRanks, {name?, type?,
+        eventNames?, duration_s?, end_ms?} per ranking.  Returns {field name: int64 device tensor [model.n_items]} in the order of `rankings`, _lib.RANK_NONE
+        where the item has no rank; the values are the reference's doubles as integers.  The field name defaults by type (pop_model.nameByType).
+        eventNames None: the primary, model_event_names[0] (default: the model's first correlator); an empty list: every stream the history holds; a
+        name it does not hold contributes nothing.  end = end_ms, else now_ms, else the clock; start = end - duration_s * 1000 (default 3650 days).
+        Every stream position counts, whoever its user is.  `userDefined` and unknown types give a field of RANK_NONE throughout (the reference returns an
+        empty RDD).  One call per ranking, no synchronisation; the history is not modified.
+
+        ValueError: the history has no model; the type is `random` (not served from the history); a stream without times (every ranking is a window);
+        a _Stream built by hand without n_events."""
+        from . import _lib
+        from .pop_model import RankingFieldName, RankingType, nameByType
+        model = self.model
+        if model is None:
+            raise ValueError("ranks: the history was built without a model to take the primary's item dictionary from")
+        if now_ms is None:
+            import time
+            now_ms = int(time.time() * 1000)
+        primary = list(model_event_names[:1]) if model_event_names is not None else [model.correlators[0].name]
+        codes = {RankingType.Popular: _lib.RANK_POPULAR, RankingType.Trending: _lib.RANK_TRENDING, RankingType.Hot: _lib.RANK_HOT}
+        out: Dict[str, torch.Tensor] = {}
+        for r in rankings:
+            rtype = r.get("type") or RankingType.Popular
+            if rtype == RankingType.Random:
+                raise ValueError("ranks: `random` ranks are not served from the history")
+            field = r.get("name") or nameByType.get(rtype, RankingFieldName.UnknownRank)
+            if rtype not in codes:
+                out[field] = torch.full((model.n_items,), _lib.RANK_NONE, dtype=torch.int64).to(self.sess.device)
+                continue
+            names = r["eventNames"] if r.get("eventNames") is not None else primary
+            streams = []
+            for ev in (list(dict.fromkeys(names)) if names else list(self.types)):
+                st = self.types.get(ev)
+                if st is None:
+                    continue
+                if st.n_events < 0:
+                    raise ValueError(f"stream {ev!r}: built without its number of events (_Stream.n_events)")
+                if st.times is None:
+                    raise ValueError(f"ranks: the stream {ev!r} has no times, a ranking window cannot apply to it")
+                streams.append((st.n_events, st.items, st.times, st.col_map, st.n_cols))
+            end = int(r["end_ms"] if r.get("end_ms") is not None else now_ms)
+            start = end - int(r.get("duration_s", 3650 * 86400)) * 1000
+            out[field] = self.sess.history_ranks(streams, model.n_items, codes[rtype], start, end)
+        return out
+
     @staticmethod
     def from_dict(sess: DeviceSession, model, history: Dict[str, Dict[str, List[str]]]) -> "DeviceHistory":
         """The dict form of batch_predict's `history` (user -> {event name: [item ids, oldest first]}) loaded onto the device: every user gets a

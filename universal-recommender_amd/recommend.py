@@ -80,6 +80,21 @@ class DeviceModel:
         self.properties = properties    # None: built without item properties -- batch_predict serves no business rules
         self.dates = dates or {}        # date property -> int64 [n_items] epoch milliseconds, NO_VALUE where the item has none
         self._term_weights: Dict[str, Dict[str, torch.Tensor]] = {}   # term_weights(kind), built on first use
+        self.rank_fields: Dict[str, torch.Tensor] = {}   # set_ranks: ranking field name -> int64 [n_items], _lib.RANK_NONE = no rank
+
+    def set_ranks(self, fields: Dict[str, torch.Tensor]) -> "DeviceModel":
+        """The backfill order from rank fields on the device (decision D24 of DESIGN.md): fields = {ranking field name: int64 device tensor [n_items],
+        _lib.RANK_NONE where the item has no rank}, in the order of the reference's rankingFieldNames -- what history.DeviceHistory.ranks returns.  The
+        tensors are kept as rank_fields and fill_order becomes the items sorted by every field in turn, larger rank first, an item without a rank last,
+        then item index (`sort: [_score desc, <each ranking field> desc]`, URAlgorithm.scala:730-738) -- DeviceSession.fill_order.  Nothing else of the
+        model changes and nothing is rebuilt: a serving model takes fresh trending / hot ranks between two trainings.  {} clears both.  Returns self."""
+        fields = dict(fields)
+        for name, r in fields.items():
+            if r.dtype != torch.int64 or int(r.numel()) != self.n_items:
+                raise ValueError(f"rank field {name!r}: an int64 tensor with one entry per item of the primary expected")
+        self.rank_fields = fields
+        self.fill_order = self.sess.fill_order(list(fields.values())) if fields else None
+        return self
 
     @staticmethod
     def from_indicators(sess: DeviceSession, correlators: Sequence[Tuple[str, object]], ranks: Optional[Dict[object, float]] = None,

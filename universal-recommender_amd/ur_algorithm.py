@@ -340,15 +340,27 @@ class URAlgorithm:
                               _get_or_else(ap.indicators[i].maxCorrelatorsPerItem, DefaultURAlgoParams.MaxCorrelatorsPerEventType),
                               ap.indicators[i].minLLR) for i in range(n)]
 
+    def ranks_from_history(self, history, now_ms: Optional[int] = None):
+        """URAlgorithm.getRanksRDD :537-560 over a history.DeviceHistory instead of the event store handed to the constructor (decision D24 of DESIGN.md):
+        the `rankings` of the algorithm parameters, mapped as getRanks maps them -- durations through duration_seconds, offsetDate through _iso_ms, the
+        default one all-time popRank on the primary event -- and counted on the device.  Returns {ranking field name: int64 device tensor [n_items]}: what
+        recommend.DeviceModel.set_ranks takes.  See history.DeviceHistory.ranks."""
+        rankings = [{"name": r.name, "type": r.type, "eventNames": r.eventNames,
+                     "duration_s": duration_seconds(r.duration if r.duration is not None else DefaultURAlgoParams.BackfillDuration),
+                     "end_ms": _iso_ms(r.offsetDate)} for r in self.rankingsParams]
+        return history.ranks(rankings, now_ms, self.modelEventNames)
+
     def train_from_history(self, history, after_ms: Optional[int] = None, before_ms: Optional[int] = None, ranks=None, properties=None, date_names=None,
-                           seed: Optional[int] = None):
+                           seed: Optional[int] = None, now_ms: Optional[int] = None):
         """Retrain from the event store on the device (decision D23 of DESIGN.md): DataSource.readTraining -> Preparator.prepare -> calcAll over a
         history.DeviceHistory -- the streams that `append` grows and `trim` ages -- without a copy of the events on the host.  The event types are
         modelEventNames, the primary first; the events with after_ms <= time < before_ms (None: open); the users with at least minEventsPerUser (the
         algorithm parameter, absent = 1) primary events in the window.  DeviceHistory.matrices -> device.cross_occurrence_device with the DatasetParams
         of train_events_on_device -> recommend.DeviceModel.from_indicators with the item and column dictionaries of history.model: the id spaces are the
         history's and do not change.  ranks, properties, date_names go to from_indicators; when all three are None the new model takes over
-        history.model's fill_order, properties and dates, which are indexed by the same primary item ids.  seed: default the algorithm parameter, else
+        history.model's fill_order, properties and dates, which are indexed by the same primary item ids.  ranks="history" (decision D24): the backfill
+        ranks are counted from the history itself -- model.set_ranks(self.ranks_from_history(history, now_ms)) on the new model, around now_ms (default
+        the clock); properties and dates are then taken over from history.model unless given.  seed: default the algorithm parameter, else
         the clock.  history.model is not rebound: the caller decides when to swap.
 
         ValueError: recsModel is not "all" or "collabFiltering"; the history has no model; it does not hold the stream of an event type (the primary's
@@ -370,10 +382,15 @@ class URAlgorithm:
             seed = ap.seed if ap.seed is not None else int(time.time() * 1000)
         res = cross_occurrence_device(history.sess, [mats[n] for n in names], self._dataset_params(len(names)), _seed_to_int(seed))
         column_ids = {c.name: c.column_ids for c in old.correlators if c.column_ids is not None}
-        fresh = ranks is not None or properties is not None or date_names is not None
-        model = DeviceModel.from_indicators(history.sess, list(zip(names, res)), ranks, old.item_ids, column_ids, properties, date_names or ())
+        from_history = isinstance(ranks, str)
+        if from_history and ranks != "history":
+            raise ValueError(f"train_from_history: ranks is a dict item -> rank, None or \"history\", not {ranks!r}")
+        fresh = (ranks is not None and not from_history) or properties is not None or date_names is not None
+        model = DeviceModel.from_indicators(history.sess, list(zip(names, res)), None if from_history else ranks, old.item_ids, column_ids, properties, date_names or ())
         if not fresh:
-            model.fill_order, model.properties, model.dates = old.fill_order, old.properties, old.dates
+            model.fill_order, model.rank_fields, model.properties, model.dates = old.fill_order, old.rank_fields, old.properties, old.dates
+        if from_history:
+            model.set_ranks(self.ranks_from_history(history, now_ms))
         return model
 
 
