@@ -806,6 +806,70 @@ int urcco_dev_item_bounds(urcco_session* s, int64_t n_queries, const int32_t* q_
 int urcco_dev_item_rows(urcco_session* s, int64_t n_queries, const int32_t* q_items, int32_t n_items, urcco_item_event* events, int32_t n_types,
                         int64_t* stats_dev /* nullable */);
 
+/* Device-resident item properties (DESIGN.md decision D25): what the reference reads with PEventStore.aggregateProperties(entityType = "item")
+ * (DataSource.scala:93-97) and indexes next to the indicators -- here aggregated on the device from the $set / $unset / $delete events where they arrive,
+ * so that a serving model takes an inventory change without a rebuild.  One property is one stream of $set and $unset events (item, time, and per $set a
+ * value: a slice of value ids for a list of strings, an int64 for a date); the $delete events of all items are one more stream.
+ *
+ * THE RULE (the contract: PredictionIO's per-key comparison of set, unset and delete times).  Per item i and property p, over all events applied so far:
+ *   S        the $set of (i, p) with the largest (time, stream position): of two sets with equal time the later one in the stream wins
+ *   U, D     the largest time of an $unset of (i, p); the largest time of a $delete of i
+ *   alive    S exists and time(S) > U and time(S) > D.  An $unset or a $delete at the millisecond of the set wins the tie
+ *   value    that of S alone: a $set replaces the value, lists are not merged
+ *   deleted  a $delete of i exists and no property of i has a set later than D.  A later $set of one key revives that key only
+ * The rule does not depend on the order of the events: it is exact under any batching and reproducible bit for bit.  An event with time INT64_MIN is
+ * ignored (INT64_MIN is "no value", and "nothing seen" below).
+ *
+ * State, caller-owned, zero-initialised; per property three arrays of n_items words, per store one:
+ *   t_set  (uint64)   time of S as (uint64)t ^ 2^63 -- unsigned words that order as the signed times do -- 0 = no $set seen
+ *   pos_set (uint32)  stream position of S + 1, 0 = none          t_unset (uint64)  U, biased alike, 0 = none          t_del (uint64)  D, alike
+ * All-zero is "nothing seen": a new store is zeros, a grown catalogue is the old state extended by zeros.
+ *
+ * urcco_dev_props_apply: the events at stream positions pos_base .. pos_base + n_new of one property.  kinds[j] URCCO_PROP_SET or URCCO_PROP_UNSET (any
+ *   other value: the event is ignored; kinds == NULL: all SET).  Two launches: t_set / t_unset = max(., time); then every SET whose time equals t_set of
+ *   its item: pos_set = max(., pos_base + j + 1).  Each reads the word first and issues the atomic only when the event would raise it.  Stream positions
+ *   only grow, so a stream applied in any number of batches leaves the bits one call over the whole stream leaves.  Items outside 0 .. n_items are ignored.
+ * urcco_dev_props_delete: t_del = max(., time) over n $delete events.
+ * urcco_dev_props_bounds / _rows: a list-of-strings property as an item x value matrix, by the two-call protocol of urcco_dev_history_bounds / _rows.
+ *   val_ptr (int64 [state.n_events + 1]) and values (int32 [n_values] value ids) hold the value slice of every stream position (an $unset's is empty).
+ *   _bounds  row_ptr = the exclusive scan of the bounds; the bound of item i = the length of S's slice when the property is alive, else 0.  The caller reads
+ *            the total row_ptr[n_items] and allocates col_idx.
+ *   _rows    row_ptr as _bounds left it; on return row_ptr / col_idx are the CSR whose row i holds the distinct value ids of S's slice, ascending, ids outside
+ *            0 .. n_cols dropped: bit for bit what urcco_dev_csr_from_pairs gives for the (item, value id) pairs of the alive winners.  An alive property
+ *            set to [] is an empty row.  A row is written iff its bound ENDS within the capacity (row_ptr[i + 1] as _bounds left it <= capacity); every
+ *            other row is left empty.  Nothing is written at or past col_idx[capacity].  state.t_del == NULL: no deletes.
+ *   Contents of pos_set or val_ptr that name no position / no slice (positions beyond n_events, slice ends outside 0 .. n_values) may give wrong rows,
+ *   never an access outside the arrays.  The CSC for boost clauses comes from urcco_dev_column_counts + urcco_dev_transpose.
+ * urcco_dev_props_dates: out[i] = date_values[position of S] when the property is alive, else INT64_MIN.  date_values: int64 per stream position.
+ * urcco_dev_props_exists: out_mask[i] = 0 iff item i is deleted by the rule over the n_props properties whose t_set arrays are given, else 1; an item
+ *   without any event gets 1.  The mask is urcco_dev_recommend's item_mask.
+ * All six enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: a negative n_items, n_new, n, n_values,
+ * n_cols, capacity or state.n_events; pos_base < 0 or pos_base + n_new >= 2^31; state.n_events >= 2^31; n_props outside 0..URCCO_PROP_MAX; a NULL the call
+ * needs.  Needed: items and times_ms when n_new (n) > 0; the state arrays the call names when n_items > 0 (apply: also with n_new == 0); val_ptr when
+ * n_items > 0 and state.n_events > 0; values when n_values > 0; col_idx when capacity > 0; date_values when state.n_events > 0; row_ptr always; t_sets and
+ * each of its pointers when n_props > 0 and n_items > 0; out / out_mask when n_items > 0.
+ * ABI: additions within ABI 305 -- the presence of the symbols is the feature test. */
+#define URCCO_PROP_SET 0
+#define URCCO_PROP_UNSET 1
+#define URCCO_PROP_MAX 16
+typedef struct urcco_prop_state {
+  const uint64_t* t_set;      /* device [n_items] */
+  const uint32_t* pos_set;    /* device [n_items] */
+  const uint64_t* t_unset;    /* device [n_items] */
+  const uint64_t* t_del;      /* device [n_items], the store's; nullable: no $delete was ever applied */
+  int64_t n_events;           /* stream positions of the property applied so far */
+} urcco_prop_state;
+int urcco_dev_props_apply(urcco_session* s, int32_t n_items, int64_t n_new, const int32_t* items, const int64_t* times_ms, const uint8_t* kinds /* nullable: all SET */,
+                          int64_t pos_base, uint64_t* t_set, uint32_t* pos_set, uint64_t* t_unset);
+int urcco_dev_props_delete(urcco_session* s, int32_t n_items, int64_t n, const int32_t* items, const int64_t* times_ms, uint64_t* t_del);
+int urcco_dev_props_bounds(urcco_session* s, int32_t n_items, const urcco_prop_state* state /* host */, const int64_t* val_ptr, int64_t n_values,
+                           int64_t* row_ptr /* [n_items + 1] */);
+int urcco_dev_props_rows(urcco_session* s, int32_t n_items, const urcco_prop_state* state /* host */, const int64_t* val_ptr, const int32_t* values, int64_t n_values,
+                         int32_t n_cols, int64_t* row_ptr /* [n_items + 1]: bounds on entry, final on return */, int32_t* col_idx, int64_t capacity);
+int urcco_dev_props_dates(urcco_session* s, int32_t n_items, const urcco_prop_state* state /* host */, const int64_t* date_values, int64_t* out /* [n_items] */);
+int urcco_dev_props_exists(urcco_session* s, int32_t n_items, const uint64_t* t_del, const uint64_t* const* t_sets /* host array of n_props device pointers */,
+                           int32_t n_props, uint8_t* out_mask /* [n_items] */);
+
 /* Test hooks (device level): LLR of SimilarityAnalysis.logLikelihoodRatio evaluated by the device code for
  * n argument tuples; u01 of the down-sampling RNG.  All pointers device. */
 int urcco_dev_llr(urcco_session* s, int64_t n, const int64_t* with_a, const int64_t* with_b, const int64_t* with_ab,

@@ -40,7 +40,9 @@ RANK_POPULAR, RANK_TRENDING, RANK_HOT = 1, 2, 3   # urcco_dev_history_ranks (URC
 RANK_NONE = -(1 << 63)   # the item has no rank in the field (INT64_MIN)
 RANK_MAX_STREAMS = 16
 RANK_MAX_FIELDS = 4    # urcco_dev_fill_order: rank fields per call
-HIST_STATS_LEN = 8     # urcco_dev_history_rows (URCCO_HIST_STATS_LEN): pairs per class, selects, exclusion rows per class, overflows
+PROP_SET, PROP_UNSET = 0, 1   # urcco_dev_props_apply (URCCO_PROP_*): the kind of a property event
+PROP_MAX = 16          # urcco_dev_props_exists: properties per call
+HIST_STATS_LEN = 8    # urcco_dev_history_rows (URCCO_HIST_STATS_LEN): pairs per class, selects, exclusion rows per class, overflows
 REC_LDS_LIMIT = 3072   # work bound w(q) up to which a query runs in the LDS class (csrc/cco_kernels.h)
 EXCH_SIZES = 4   # int64 words of a shard's record (include/urcco.h URCCO_EXCH_SIZES)
 # bits of urcco_session_set_debug / urcco_context_set_debug: the names and values of csrc/cco_kernels.h (tests/test_c_abi_surface.py compares them)
@@ -162,6 +164,11 @@ class ItemEvent(C.Structure):
                 ("term_col_idx", C.c_void_p), ("term_capacity", C.c_int64)]
 
 
+class PropState(C.Structure):
+    """urcco_prop_state: the aggregation state of one item property (urcco_dev_props_bounds / _rows / _dates)."""
+    _fields_ = [("t_set", C.c_void_p), ("pos_set", C.c_void_p), ("t_unset", C.c_void_p), ("t_del", C.c_void_p), ("n_events", C.c_int64)]
+
+
 # every symbol include/urcco.h declares: (restype, argtypes)
 _p = C.c_void_p
 SYMBOLS = {
@@ -238,6 +245,12 @@ SYMBOLS = {
     "urcco_dev_history_rows": (C.c_int, [_p, C.c_int64, _p, C.c_int64, C.POINTER(HistEvent), C.c_int32, _p, _p, C.c_int32, _p, _p, C.c_int64, _p]),
     "urcco_dev_item_bounds": (C.c_int, [_p, C.c_int64, _p, C.c_int32, C.POINTER(ItemEvent), C.c_int32]),
     "urcco_dev_item_rows": (C.c_int, [_p, C.c_int64, _p, C.c_int32, C.POINTER(ItemEvent), C.c_int32, _p]),
+    "urcco_dev_props_apply": (C.c_int, [_p, C.c_int32, C.c_int64, _p, _p, _p, C.c_int64, _p, _p, _p]),
+    "urcco_dev_props_delete": (C.c_int, [_p, C.c_int32, C.c_int64, _p, _p, _p]),
+    "urcco_dev_props_bounds": (C.c_int, [_p, C.c_int32, C.POINTER(PropState), _p, C.c_int64, _p]),
+    "urcco_dev_props_rows": (C.c_int, [_p, C.c_int32, C.POINTER(PropState), _p, _p, C.c_int64, C.c_int32, _p, _p, C.c_int64]),
+    "urcco_dev_props_dates": (C.c_int, [_p, C.c_int32, C.POINTER(PropState), _p, _p]),
+    "urcco_dev_props_exists": (C.c_int, [_p, C.c_int32, _p, C.POINTER(C.c_void_p), C.c_int32, _p]),
     "urcco_dev_llr": (C.c_int, [_p, C.c_int64, _p, _p, _p, _p, _p]),
     "urcco_dev_u01": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p]),
     "urcco_dev_u01_rng": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, C.c_int32, _p]),

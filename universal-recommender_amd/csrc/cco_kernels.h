@@ -488,6 +488,37 @@ struct ItemArgs {
 hipError_t launch_item_bounds(hipStream_t st, int n_cu, const ItemArgs& a, int32_t* bnd, int64_t* tile_sums, int64_t* const* term_row_ptr);
 hipError_t launch_item_rows(hipStream_t st, int n_cu, const ItemArgs& a, int64_t* tile_sums, int64_t* const* term_row_ptr, int32_t* const* term_col_idx, int64_t* stats_dev);
 
+// ---- device-resident item properties (cco_props.h, compiled into ingest_kernels.hip behind cco_items.h; decision D25) ----
+constexpr unsigned PROP_SET = 0, PROP_UNSET = 1;  // include/urcco.h URCCO_PROP_*
+constexpr int PROP_MAX = 16;                      // URCCO_PROP_MAX: properties per urcco_dev_props_exists call
+struct PropState {
+  const unsigned long long* t_set;    // [n_items]: biased time of the latest $set, 0 = none
+  const unsigned* pos_set;            // [n_items]: its stream position + 1
+  const unsigned long long* t_unset;  // [n_items]: biased time of the latest $unset
+  const unsigned long long* t_del;    // nullable [n_items]: biased time of the item's latest $delete
+  int64_t n_events;                   // positions the property's stream holds
+};
+struct PropRows {
+  PropState st;
+  const int64_t* val_ptr;   // [n_events + 1]: the value slice of every stream position
+  const int32_t* values;    // [n_values] value ids
+  int64_t n_values;
+  RawRows raw;              // scratch, n_items rows; capacity = entries of the caller's col_idx
+  int32_t n_items, n_cols;
+};
+struct PropSets {
+  const unsigned long long* t_set[PROP_MAX];
+  int32_t n_props;
+};
+hipError_t launch_props_apply(hipStream_t st, int n_cu, int32_t n_items, int64_t n, const int32_t* items, const int64_t* times, const uint8_t* kinds, int64_t pos_base,
+                              unsigned long long* t_set, unsigned* pos_set, unsigned long long* t_unset);
+hipError_t launch_props_delete(hipStream_t st, int n_cu, int32_t n_items, int64_t n, const int32_t* items, const int64_t* times, unsigned long long* t_del);
+// bnd [n_items]: scratch
+hipError_t launch_props_bounds(hipStream_t st, int n_cu, const PropRows& a, int32_t* bnd, int64_t* tile_sums, int64_t* row_ptr);
+hipError_t launch_props_rows(hipStream_t st, int n_cu, const PropRows& a, int64_t* tile_sums, int64_t* row_ptr, int32_t* col_idx);
+hipError_t launch_props_dates(hipStream_t st, int n_cu, int32_t n_items, const PropState& s, const int64_t* date_values, int64_t* out);
+hipError_t launch_props_exists(hipStream_t st, int n_cu, int32_t n_items, const unsigned long long* t_del, const PropSets& sets, uint8_t* mask);
+
 hipError_t launch_llr_test(hipStream_t st, int64_t n, const int64_t* a, const int64_t* b, const int64_t* ab, const int64_t* nu, double* out);
 hipError_t launch_u01_test(hipStream_t st, int64_t n, uint32_t seed, const int32_t* row, const int32_t* col, double* out, int rng32 = 0);
 

@@ -984,6 +984,93 @@ int urcco_dev_item_rows(urcco_session* s, int64_t n_queries, const int32_t* q_it
 
 }  // extern "C"
 
+// urcco_dev_props_bounds / _rows / _dates: the state's checks and its device form
+static int props_state(const char* who, urcco_session* s, int32_t n_items, const urcco_prop_state* state, urcco::PropState* out) {
+  if (!s || n_items < 0 || !state || state->n_events < 0 || state->n_events > 0x7fffffffll)
+    return fail(URCCO_BAD_ARG, "%s: bad argument (a property's stream holds fewer than 2^31 events)", who);
+  if (n_items > 0 && (!state->t_set || !state->pos_set || !state->t_unset)) return fail(URCCO_BAD_ARG, "%s: NULL state array", who);
+  *out = urcco::PropState{reinterpret_cast<const unsigned long long*>(state->t_set), state->pos_set, reinterpret_cast<const unsigned long long*>(state->t_unset),
+                          reinterpret_cast<const unsigned long long*>(state->t_del), state->n_events};
+  return URCCO_OK;
+}
+
+static int props_rows_args(const char* who, urcco_session* s, int32_t n_items, const urcco_prop_state* state, const int64_t* val_ptr, const int32_t* values,
+                           int64_t n_values, int32_t n_cols, const int64_t* row_ptr, bool rows, urcco::PropRows* a) {
+  *a = urcco::PropRows{};
+  URC(props_state(who, s, n_items, state, &a->st));
+  if (n_values < 0 || n_cols < 0 || !row_ptr || (n_items > 0 && state->n_events > 0 && !val_ptr) || (rows && n_values > 0 && !values))
+    return fail(URCCO_BAD_ARG, "%s: bad argument", who);
+  a->val_ptr = val_ptr; a->values = values; a->n_values = n_values; a->n_items = n_items; a->n_cols = n_cols;
+  return URCCO_OK;
+}
+
+extern "C" {
+
+int urcco_dev_props_apply(urcco_session* s, int32_t n_items, int64_t n_new, const int32_t* items, const int64_t* times_ms, const uint8_t* kinds, int64_t pos_base,
+                          uint64_t* t_set, uint32_t* pos_set, uint64_t* t_unset) {
+  if (!s || n_items < 0 || n_new < 0 || pos_base < 0 || n_new > 0x7fffffffll || pos_base > 0x7fffffffll - n_new)
+    return fail(URCCO_BAD_ARG, "urcco_dev_props_apply: bad argument (pos_base + n_new stays below 2^31)");
+  if ((n_new > 0 && (!items || !times_ms)) || (n_items > 0 && (!t_set || !pos_set || !t_unset))) return fail(URCCO_BAD_ARG, "urcco_dev_props_apply: NULL argument");
+  HIPC(urcco::launch_props_apply(s->stream, s->n_cu, n_items, n_new, items, times_ms, kinds, pos_base, reinterpret_cast<unsigned long long*>(t_set), pos_set,
+                                 reinterpret_cast<unsigned long long*>(t_unset)));
+  return URCCO_OK;
+}
+
+int urcco_dev_props_delete(urcco_session* s, int32_t n_items, int64_t n, const int32_t* items, const int64_t* times_ms, uint64_t* t_del) {
+  if (!s || n_items < 0 || n < 0 || n > 0x7fffffffll) return fail(URCCO_BAD_ARG, "urcco_dev_props_delete: bad argument (fewer than 2^31 events a call)");
+  if ((n > 0 && (!items || !times_ms)) || (n_items > 0 && !t_del)) return fail(URCCO_BAD_ARG, "urcco_dev_props_delete: NULL argument");
+  HIPC(urcco::launch_props_delete(s->stream, s->n_cu, n_items, n, items, times_ms, reinterpret_cast<unsigned long long*>(t_del)));
+  return URCCO_OK;
+}
+
+int urcco_dev_props_bounds(urcco_session* s, int32_t n_items, const urcco_prop_state* state, const int64_t* val_ptr, int64_t n_values, int64_t* row_ptr) {
+  urcco::PropRows a;
+  URC(props_rows_args("urcco_dev_props_bounds", s, n_items, state, val_ptr, nullptr, n_values, 0, row_ptr, false, &a));
+  int32_t* bnd;
+  int64_t* tile_sums;
+  URC(ArenaLayout(s).add(&bnd, (size_t)n_items).add(&tile_sums, scan_tile_words(n_items)).commit());
+  HIPC(urcco::launch_props_bounds(s->stream, s->n_cu, a, bnd, tile_sums, row_ptr));
+  return URCCO_OK;
+}
+
+int urcco_dev_props_rows(urcco_session* s, int32_t n_items, const urcco_prop_state* state, const int64_t* val_ptr, const int32_t* values, int64_t n_values, int32_t n_cols,
+                         int64_t* row_ptr, int32_t* col_idx, int64_t capacity) {
+  urcco::PropRows a;
+  URC(props_rows_args("urcco_dev_props_rows", s, n_items, state, val_ptr, values, n_values, n_cols, row_ptr, true, &a));
+  if (capacity < 0 || (capacity > 0 && !col_idx)) return fail(URCCO_BAD_ARG, "urcco_dev_props_rows: a capacity needs col_idx, and is not negative");
+  ArenaLayout L(s);
+  int64_t* tile_sums;
+  L.add(&tile_sums, scan_tile_words(n_items));
+  add_raw_rows(L, &a.raw, (size_t)n_items, capacity);
+  URC(L.commit());
+  HIPC(urcco::launch_props_rows(s->stream, s->n_cu, a, tile_sums, row_ptr, col_idx));
+  return URCCO_OK;
+}
+
+int urcco_dev_props_dates(urcco_session* s, int32_t n_items, const urcco_prop_state* state, const int64_t* date_values, int64_t* out) {
+  urcco::PropState st;
+  URC(props_state("urcco_dev_props_dates", s, n_items, state, &st));
+  if (n_items > 0 && (!out || (state->n_events > 0 && !date_values))) return fail(URCCO_BAD_ARG, "urcco_dev_props_dates: NULL argument");
+  HIPC(urcco::launch_props_dates(s->stream, s->n_cu, n_items, st, date_values, out));
+  return URCCO_OK;
+}
+
+int urcco_dev_props_exists(urcco_session* s, int32_t n_items, const uint64_t* t_del, const uint64_t* const* t_sets, int32_t n_props, uint8_t* out_mask) {
+  if (!s || n_items < 0) return fail(URCCO_BAD_ARG, "urcco_dev_props_exists: bad argument");
+  if (n_props < 0 || n_props > URCCO_PROP_MAX) return fail(URCCO_BAD_ARG, "urcco_dev_props_exists: between 0 and %d properties, got %d", URCCO_PROP_MAX, n_props);
+  if (n_items > 0 && (!t_del || !out_mask || (n_props > 0 && !t_sets))) return fail(URCCO_BAD_ARG, "urcco_dev_props_exists: NULL argument");
+  urcco::PropSets sets{};
+  sets.n_props = n_items > 0 ? n_props : 0;
+  for (int p = 0; p < sets.n_props; ++p) {
+    if (!t_sets[p]) return fail(URCCO_BAD_ARG, "urcco_dev_props_exists: t_set array %d is NULL", p);
+    sets.t_set[p] = reinterpret_cast<const unsigned long long*>(t_sets[p]);
+  }
+  HIPC(urcco::launch_props_exists(s->stream, s->n_cu, n_items, reinterpret_cast<const unsigned long long*>(t_del), sets, out_mask));
+  return URCCO_OK;
+}
+
+}  // extern "C"
+
 // urcco_dev_recommend (n_rules == 0), urcco_dev_recommend_rules and urcco_dev_recommend_weighted (clause_weights != NULL)
 static int recommend_call(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
                           const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,

@@ -458,6 +458,56 @@ class DeviceSession:
                                        lambda cis, totals, st: self.lib.urcco_dev_item_rows(*head, _ptr(st)))
         return list(zip(rps, cis)), info
 
+    # ---- device-resident item properties (decision D25; include/urcco.h urcco_dev_props_*) ----
+    # The state of a property is three tensors of one entry per item -- t_set int64, pos_set int32, t_unset int64 -- and the store's t_del int64: the bits
+    # of the header's unsigned words (torch computes on the signed types), zeros = nothing seen.
+    def props_apply(self, n_items: int, items: torch.Tensor, times: torch.Tensor, kinds: Optional[torch.Tensor], pos_base: int, t_set: torch.Tensor,
+                    pos_set: torch.Tensor, t_unset: torch.Tensor, n_new: Optional[int] = None):
+        """urcco_dev_props_apply: the events at stream positions pos_base .. of one property into its state, in place.  items int32, times int64, kinds
+        uint8 (_lib.PROP_SET / PROP_UNSET) or None (all sets); n_new: the events to read (default: all of `items`).  Does not synchronise."""
+        n_new = int(items.numel()) if n_new is None else int(n_new)
+        self._check(self.lib.urcco_dev_props_apply(self.handle, int(n_items), n_new, _ptr(items), _ptr(times), _ptr(kinds), int(pos_base), _ptr(t_set), _ptr(pos_set),
+                                                   _ptr(t_unset)))
+
+    def props_delete(self, n_items: int, items: torch.Tensor, times: torch.Tensor, t_del: torch.Tensor):
+        """urcco_dev_props_delete: $delete events (items int32, times int64) into the store's t_del, in place.  Does not synchronise."""
+        self._check(self.lib.urcco_dev_props_delete(self.handle, int(n_items), int(items.numel()), _ptr(items), _ptr(times), _ptr(t_del)))
+
+    @staticmethod
+    def _prop_state(state) -> "_lib.PropState":
+        t_set, pos_set, t_unset, t_del, n_events = state
+        return _lib.PropState(_ptr(t_set), _ptr(pos_set), _ptr(t_unset), _ptr(t_del), int(n_events))
+
+    def props_rows(self, n_items: int, state, val_ptr: torch.Tensor, values: torch.Tensor, n_values: int, n_cols: int, keep_bounds: bool = False):
+        """urcco_dev_props_bounds + urcco_dev_props_rows: a list-of-strings property as an item x value CSR.  state: (t_set, pos_set, t_unset, t_del | None,
+        n_events); val_ptr int64 [n_events + 1] and values int32 [n_values]: the value slice of every stream position.  Returns (row_ptr int64
+        [n_items + 1], col_idx int32, info as item_rows gives it): row i = the distinct value ids, ascending, of the winning $set of item i when the
+        property is alive.  Reads the bound total between the two calls: one synchronisation."""
+        st = self._prop_state(state)
+        rp = self.empty(int(n_items) + 1, torch.int64)
+        head = (self.handle, int(n_items), C.byref(st), _ptr(val_ptr))
+        cis, info = self._bounded_rows(None, 0, int(n_items), [rp], False, False, keep_bounds, lambda: self.lib.urcco_dev_props_bounds(*head, int(n_values), _ptr(rp)),
+                                       lambda cis, totals, _st: self.lib.urcco_dev_props_rows(*head, _ptr(values), int(n_values), int(n_cols), _ptr(rp), _ptr(cis[0]),
+                                                                                              int(totals[0])))
+        return rp, cis[0], info
+
+    def props_dates(self, n_items: int, state, date_values: torch.Tensor) -> torch.Tensor:
+        """urcco_dev_props_dates: int64 [n_items], the date of the winning $set (date_values: int64 per stream position) where the property is alive,
+        else INT64_MIN.  Does not synchronise."""
+        st = self._prop_state(state)
+        out = self.empty(max(int(n_items), 1), torch.int64)
+        self._check(self.lib.urcco_dev_props_dates(self.handle, int(n_items), C.byref(st), _ptr(date_values), _ptr(out)))
+        return out[: int(n_items)]
+
+    def props_exists(self, n_items: int, t_del: torch.Tensor, t_sets) -> torch.Tensor:
+        """urcco_dev_props_exists: uint8 [n_items], 0 where the item is deleted -- a $delete that no $set of any of the properties (t_sets: their t_set
+        tensors, at most _lib.PROP_MAX) is later than -- else 1: the item_mask of the recommend calls.  Does not synchronise."""
+        t_sets = list(t_sets)
+        ptrs = (C.c_void_p * max(len(t_sets), 1))(*[t.data_ptr() for t in t_sets])
+        out = self.empty(max(int(n_items), 1), torch.uint8)
+        self._check(self.lib.urcco_dev_props_exists(self.handle, int(n_items), _ptr(t_del), ptrs, len(t_sets), _ptr(out)))
+        return out[: int(n_items)]
+
     def _bounded_rows(self, arr, n_types, nq, rps, stats, timing, keep_bounds, bounds, rows):
         """The two-call protocol of history_rows and item_rows.  bounds() leaves in every row_ptr of `rps` the scan of its rows' upper bounds; their
         totals are read (the one synchronisation) and size the col_idx tensors, those of the first n_types go into the struct array `arr`;

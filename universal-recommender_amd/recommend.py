@@ -96,6 +96,17 @@ class DeviceModel:
         self.fill_order = self.sess.fill_order(list(fields.values())) if fields else None
         return self
 
+    def set_properties(self, props) -> "DeviceModel":
+        """The item properties of a serving model from a properties.DeviceProperties (decision D25 of DESIGN.md): `properties` and `dates` become what
+        props.materialise() cuts from the property events aggregated on the device -- an item that sold out, changed category or got a new expire date
+        reaches the rules without a rebuild.  The cached term weights are dropped: the idf arrays of the property matrices depend on them.  Nothing else
+        of the model changes; the "deleted" mask is props.item_mask(), for batch_predict(item_mask=...).  Returns self."""
+        if int(props.n_items) != self.n_items:
+            raise ValueError("the properties hold another number of items than the model")
+        self.properties, self.dates = props.materialise()
+        self._term_weights = {}
+        return self
+
     @staticmethod
     def from_indicators(sess: DeviceSession, correlators: Sequence[Tuple[str, object]], ranks: Optional[Dict[object, float]] = None,
                         item_ids: Optional[BiDictionary] = None, column_ids: Optional[Dict[str, BiDictionary]] = None,

@@ -300,6 +300,12 @@ class URAlgorithm:
         from .evaluate import evaluate
         return evaluate(self, model, train, test, ks, num, event_names, truth_event, chunk, user_bias, item_mask, now_ms, term_weights)
 
+    def properties_from_events(self, model, events):
+        """A properties.DeviceProperties for `model` over the item property events `events` ($set / $unset / $delete, see DeviceProperties.apply), its
+        date properties the algorithm's dateNames: model.set_properties(...) and item_mask=....item_mask() serve them (decision D25)."""
+        from .properties import DeviceProperties
+        return DeviceProperties(model.sess, model, self.dateNames).apply(events)
+
     def predict(self, model, query: dict, history, item_mask=None, now_ms: Optional[int] = None, term_weights=None) -> dict:
         return self.batch_predict(model, [query], history, item_mask, now_ms, term_weights=term_weights)[0]
 
