@@ -913,6 +913,22 @@ int urcco_dev_dictionary_verify(urcco_session* s, const urcco_key_table* table, 
  * be merged into that user silently. */
 int urcco_dev_dictionary_verify_against(urcco_session* s, const urcco_key_table* table, int64_t n, const uint64_t* keys, const int32_t* select,
                                         const uint64_t* check_keys, const uint64_t* dict_check_keys, const int64_t* first_pos, int64_t* n_mismatch);
+/* A batch of keys against a LIVE table (DESIGN.md decision D26): the keys the table knows keep their ids, the others get the next ids in order of
+ * first appearance in the batch.  The table after build(S0), extend(B1), ..., extend(Bk) answers every lookup as the table of ONE
+ * urcco_dev_dictionary_build over S0 ++ B1 ++ ... ++ Bk with min_count = 1; a build with n = 0 yields the empty table to start from.  The table keeps
+ * its own id count and the min_count it was built with; an addition within the ABI number: the presence of the symbol is the feature test.
+ *   ids       device out [n], nullable: ids[p] = the id of keys[p] after the call, -1 where select[p] < 0
+ *   new_pos   device out, capacity n: new_pos[j] = the position within this batch of the first appearance of id n_before + j, for the
+ *             *n_ids - n_before new ids -- with the batch's strings the host extends its id -> string list
+ *   n_ids     host out: the number of ids after the call (the call synchronises the stream, as the build does)
+ * Capacity: before a batch is inserted the table has the smallest power of two >= max(1024, 2 (n_ids + n)) slots, the build's rule over what it could
+ * hold afterwards; a table that is too small is rehashed into fresh arrays (device memory for both while the call runs).
+ * URCCO_BAD_ARG, the message names the cause, and the table is exactly as it was -- every later lookup and extend behave as if the call had not
+ * happened: a selected position holds the reserved key ~0; the table was built with min_count > 1 (its keys without an id cannot be told from new
+ * keys); n_ids + n exceeds 2^31 - 1, or n >= 2^32 - 1; a NULL or negative argument.  ids and new_pos are undefined after a refused call.
+ * Not served: removing keys. */
+int urcco_dev_dictionary_extend(urcco_session* s, urcco_key_table* table, int64_t n, const uint64_t* keys, const int32_t* select, int32_t* ids,
+                                int64_t* new_pos, int64_t* n_ids);
 /* Frees the table (hipFree: waits for device work still using it). */
 void urcco_key_table_destroy(urcco_key_table* table);
 /* IndexedDatasetSpark's row assembly: (row id, column id) pairs (pairs with a negative id are skipped) -> binary CSR

@@ -195,6 +195,25 @@ hipError_t launch_dictionary_lookup(hipStream_t st, int n_cu, KeyTable t, int64_
                                     int32_t* ids);
 hipError_t launch_dictionary_verify(hipStream_t st, int n_cu, KeyTable t, int64_t n, const unsigned long long* keys, const int32_t* select,
                                     const unsigned long long* check, const unsigned long long* ref_check, const int64_t* first_pos, unsigned long long* err);
+// ---- growable dictionary (cco_dictionary.h, compiled into ingest_kernels.hip behind cco_props.h; decision D26) ----
+// One batch against a live table built with min_count = 1 whose capacity is at least 2 x (n_before + n).  gate[0] (out) = selected positions holding the
+// reserved key ~0: when it is not 0 the table was not touched and every other output is undefined.  prefix[n] = the number of new ids.
+struct DictExtend {
+  KeyTable t;
+  int64_t n;
+  const unsigned long long* keys;  // [n]
+  const int32_t* select;           // nullable [n]: positions with a negative entry take no part
+  int64_t n_before;                // ids of the table before the call
+  int32_t* ids;                    // nullable out [n]: the id of keys[p] after the call, -1 where select[p] < 0
+  int64_t* new_pos;                // out [n]: new_pos[j] = the batch position of the first appearance of id n_before + j
+  int32_t* flag;                   // scratch [n]
+  int64_t* prefix;                 // scratch [n + 1]
+  int64_t* tile_sums;              // scratch: ceil(n / SCAN_TILE) + 1 words
+  unsigned* gate;                  // out [1]
+};
+hipError_t launch_dictionary_extend(hipStream_t st, int n_cu, const DictExtend& a);
+// every (key, id) pair with id >= 0 of `from` into `to`: keys ~0, minpos ~0 and id -1 throughout, at least twice as many slots as pairs.  `to.count` is not touched.
+hipError_t launch_dictionary_rehash(hipStream_t st, int n_cu, KeyTable from, KeyTable to);
 // Raw rows on their way to sorted, duplicate-free rows (cco_sorted_rows.h): the scratch of the CSR build, of every history and of every item event type
 struct RawRows {
   int64_t* raw_ptr;  // [n_rows + 1]: the raw row starts (scan of the bounds)

@@ -240,3 +240,4 @@ hipError_t launch_csr_from_pairs(hipStream_t st, int n_cu, int64_t n, const int3
 #include "cco_history.h"  // device-resident user history: uses ig_grid, cco_sorted_rows.h and cco_select.h
 #include "cco_items.h"    // device-resident item queries: the same over the model's own indicator rows
 #include "cco_props.h"    // device-resident item properties: $set / $unset / $delete aggregated in place; the winners' value lists through cco_sorted_rows.h
+#include "cco_dictionary.h"  // growable dictionary: a batch of keys against a live table, new keys get the next ids; uses ig_mix, ig_find, ig_grid

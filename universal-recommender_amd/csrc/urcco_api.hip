@@ -608,6 +608,8 @@ struct urcco_key_table {
   urcco::KeyTable t{};  // the kernels' view of the four arrays above
   int64_t capacity = 0;
   int device = 0;
+  int64_t n_ids = 0;      // ids handed out so far: set by the build, raised by urcco_dev_dictionary_extend
+  int32_t min_count = 1;  // what the table was built with: only a table of min_count 1 can be extended (cco_dictionary.h, the invariant)
 };
 
 void urcco_key_table_destroy(urcco_key_table* table) {
@@ -652,7 +654,71 @@ int urcco_dev_dictionary_build(urcco_session* s, int64_t n, const uint64_t* keys
     return fail(URCCO_BAD_ARG, "urcco_dev_dictionary_build: %u selected position(s) hold the reserved key ~0 (2^64 - 1, the integer id -1): it marks an empty slot",
                 n_reserved);
   *n_ids = ids;
+  tab->n_ids = ids;
+  tab->min_count = min_count < 1 ? 1 : min_count;
   *table = tab.release();
+  return URCCO_OK;
+}
+
+// A batch against a live table (cco_dictionary.h, decision D26).  Nothing of `table` changes before the one synchronisation at the end has shown that the
+// batch is accepted: a table that has to grow is rehashed into fresh arrays that replace the old ones only then -- the old arrays are released after the
+// stream has passed the rehash, and a refused call leaves them as they were.
+int urcco_dev_dictionary_extend(urcco_session* s, urcco_key_table* table, int64_t n, const uint64_t* keys, const int32_t* select, int32_t* ids,
+                                int64_t* new_pos, int64_t* n_ids) {
+  if (!s || !table || n < 0 || !n_ids || (n > 0 && (!keys || !new_pos))) return fail(URCCO_BAD_ARG, "urcco_dev_dictionary_extend: bad argument");
+  if (table->min_count > 1)
+    return fail(URCCO_BAD_ARG, "urcco_dev_dictionary_extend: the table was built with min_count %d: its keys without an id cannot be told from new keys",
+                table->min_count);
+  if (n >= ((int64_t)1 << 32) - 1) return fail(URCCO_BAD_ARG, "urcco_dev_dictionary_extend: at most 2^32 - 2 events per batch, got %lld", (long long)n);
+  if (table->n_ids + n > (int64_t)INT32_MAX)
+    return fail(URCCO_BAD_ARG, "urcco_dev_dictionary_extend: %lld ids and a batch of %lld could exceed the 2^31 - 1 ids a table holds", (long long)table->n_ids,
+                (long long)n);
+  if (n == 0) {
+    *n_ids = table->n_ids;
+    HIPC(hipStreamSynchronize(s->stream));
+    return URCCO_OK;
+  }
+  int64_t need = 1024;  // the build's rule over what the table could hold afterwards: the load never exceeds one half
+  while (need < 2 * (table->n_ids + n)) need <<= 1;
+  DBuf<unsigned long long> g_keys;
+  DBuf<unsigned> g_minpos;
+  DBuf<int32_t> g_id;
+  urcco::KeyTable t = table->t;
+  const bool grow = need > table->capacity;
+  if (grow) {
+    URC(g_keys.alloc((size_t)need));
+    URC(g_minpos.alloc((size_t)need));
+    URC(g_id.alloc((size_t)need));
+    t.keys = g_keys.p; t.minpos = g_minpos.p; t.id = g_id.p;
+    t.count = nullptr;  // only a build with min_count > 1 reads counts
+    t.mask = (unsigned long long)need - 1ull;
+    HIPC(hipMemsetAsync(t.keys, 0xFF, sizeof(unsigned long long) * (size_t)need, s->stream));
+    HIPC(hipMemsetAsync(t.minpos, 0xFF, sizeof(unsigned) * (size_t)need, s->stream));
+    HIPC(hipMemsetAsync(t.id, 0xFF, sizeof(int32_t) * (size_t)need, s->stream));
+    HIPC(urcco::launch_dictionary_rehash(s->stream, s->n_cu, table->t, t));
+  }
+  urcco::DictExtend a{};
+  a.t = t; a.n = n; a.keys = reinterpret_cast<const unsigned long long*>(keys); a.select = select; a.n_before = table->n_ids; a.ids = ids; a.new_pos = new_pos;
+  URC(ArenaLayout(s).add(&a.flag, (size_t)n).add(&a.prefix, (size_t)n + 1).add(&a.tile_sums, scan_tile_words(n)).add(&a.gate, 1).commit());
+  HIPC(urcco::launch_dictionary_extend(s->stream, s->n_cu, a));
+  int64_t fresh = 0;
+  unsigned n_reserved = 0;
+  HIPC(hipMemcpyAsync(&fresh, a.prefix + n, sizeof(int64_t), hipMemcpyDeviceToHost, s->stream));
+  HIPC(hipMemcpyAsync(&n_reserved, a.gate, sizeof(unsigned), hipMemcpyDeviceToHost, s->stream));
+  HIPC(hipStreamSynchronize(s->stream));
+  if (n_reserved)  // (the grown arrays go with this frame; the table's own were only read)
+    return fail(URCCO_BAD_ARG, "urcco_dev_dictionary_extend: %u selected position(s) hold the reserved key ~0 (2^64 - 1, the integer id -1): it marks an empty slot",
+                n_reserved);
+  if (grow) {  // the stream has passed the rehash: the move-assignments release the old arrays
+    table->keys = std::move(g_keys);
+    table->minpos = std::move(g_minpos);
+    table->id = std::move(g_id);
+    (void)table->count.release();
+    table->t = t;
+    table->capacity = need;
+  }
+  table->n_ids += fresh;
+  *n_ids = table->n_ids;
   return URCCO_OK;
 }
 

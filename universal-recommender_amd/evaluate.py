@@ -53,8 +53,8 @@ def evaluate(algo, model: DeviceModel, train, test, ks: Sequence[int] = (1, 5, 1
     one at the end.  term_weights: passed to user_recommendations (decision D20) -- what the weights buy on a data set is measured by evaluating twice."""
     if not isinstance(train, DeviceHistory) or not isinstance(test, DeviceHistory):
         raise ValueError("evaluate needs two history.DeviceHistory objects, the training and the held-out events")
-    if train.n_users != test.n_users or not (train.user_ids is test.user_ids or train.user_ids == test.user_ids):
-        raise ValueError("train and test must share one user id space")
+    if train.n_users != test.n_users or train.user_dict is not test.user_dict or not (train.user_ids is test.user_ids or train.user_ids == test.user_ids):
+        raise ValueError("train and test must share one user id space")      # (keyed histories: ONE dictionary object; append_keys({}) levels n_users)
     if event_names is not None and len(event_names) and all(isinstance(e, (list, tuple)) for e in event_names):
         return [evaluate(algo, model, train, test, ks, num, list(mix), truth_event, chunk, user_bias, item_mask, now_ms, term_weights) for mix in event_names]
     ks = [int(k) for k in ks]

@@ -8,7 +8,8 @@ themselves ((user id, column id, time) per event and event type, as the device i
 urcco_dev_history_bounds + urcco_dev_history_rows call.
 
 The user ids of a history are its OWN dense ids; they need not be the user dictionary of the model build: the reference's event store
-also knows users that `minEventsPerUser` dropped from the model, and their history is used all the same.
+also knows users that `minEventsPerUser` dropped from the model, and their history is used all the same.  A KEYED history (from_key_streams, decision
+D26) numbers them itself: events name their users by 64-bit key, one growable device dictionary hands out the ids, and no host dict is kept.
 
 Recency is (time desc, stream position desc): of two events with equal time the later one in the stream is the more recent (the reference
 leaves such ties to the event store).  Events whose item lies outside the event type's column dictionary (id -1) count toward the cap but
@@ -53,11 +54,15 @@ class DeviceHistory:
         self.sess, self.n_users, self.user_ids, self.types = sess, int(n_users), user_ids, types
         self.model = model     # the model the column maps came from: `append` needs it for an event name the history does not hold yet
         self.last_trim: Dict[str, Tuple[int, int]] = {}     # `trim`: event -> (events before, events after) of the last call
+        self.user_dict = None      # a keyed history (from_key_streams): the growable ingest.DevDictionary user key -> dense id; user_ids is then None
+        self.check = False         # ... whose streams carry the users' check keys as a fourth entry
 
     def user_index(self, user) -> int:
         """Dense id of a query's user, -1 when the history does not know it."""
         if user is None:
             return -1
+        if self.user_dict is not None:
+            return self.user_indices([user])[0]
         if self.user_ids is not None:
             i = self.user_ids.get(user)
             return -1 if i is None else int(i)
@@ -66,6 +71,77 @@ class DeviceHistory:
         except (TypeError, ValueError):
             return -1
         return i if 0 <= i < self.n_users else -1
+
+    def user_indices(self, users) -> List[int]:
+        """user_index for a whole batch of query users.  A keyed history hashes the users' strings once (preparator.hash_keys of str(user), the keys
+        from_key_streams was fed), looks them up in its user dictionary with one call and copies the ids to the host once: no synchronisation per user.
+        A user the shared dictionary already knows but this history has not reached yet (an id >= n_users) is unknown, -1."""
+        users = list(users)
+        if self.user_dict is None:
+            return [self.user_index(u) for u in users]
+        named = [n for n, u in enumerate(users) if u is not None]
+        out = [-1] * len(users)
+        if named:
+            from . import ingest
+            from .preparator import hash_keys
+            keys = torch.from_numpy(hash_keys([str(users[n]) for n in named], library=self.sess.lib)).to(self.sess.device)
+            for n, i in zip(named, ingest.dictionary_lookup(self.sess, self.user_dict, keys).cpu().tolist()):
+                out[n] = i if i < self.n_users else -1
+        return out
+
+    @staticmethod
+    def from_key_streams(sess: DeviceSession, model, streams: Dict[str, tuple], check: bool = False, user_dict=None) -> "DeviceHistory":
+        """A history whose users are named by 64-bit keys (decision D26 of DESIGN.md): streams = event name -> (user keys int64, items, times int64 | None),
+        device tensors of one length per event type.  The user keys are preparator.hash_keys of the users' id strings; ONE growable device dictionary,
+        shared by all event types, gives them their dense ids in order of first appearance -- the event types in the order the dict lists them -- and
+        queries that name a user by its string are resolved through it (user_indices).  items: int32 dense column ids as from_streams takes them, or
+        int64 keys (hash_keys of the items' id strings) looked up in model.key_dictionary(event): a key outside the catalogue gives -1, an event that
+        counts toward the cap and gives no term.  New ITEMS are not served: the model's column spaces are sized by the catalogue.
+        check: every stream carries the users' check keys (hash_keys with preparator.CHECK_SEED) as a fourth entry; ingest.HashCollision when two user
+        strings share a key (the state it leaves: ingest.DevDictionary.extend).  user_dict: an ingest.DevDictionary to share -- the training and the
+        held-out history of evaluate are built over one; default a new, empty one.  `append_keys` adds events, and users, later."""
+        from . import ingest
+        dh = DeviceHistory(sess, 0, None, {}, model)
+        dh.user_dict = user_dict if user_dict is not None else ingest.dictionary_build(sess, sess.empty(0, torch.int64))
+        dh.check = bool(check)
+        return dh.append_keys(streams)
+
+    def append_keys(self, streams: Dict[str, tuple]) -> "DeviceHistory":
+        """`append` for a keyed history: streams as from_key_streams takes them, the event types with new events only.  Per event type, in the order the
+        dict lists them, one ingest.DevDictionary.extend resolves the batch's users on the device -- a user not seen before gets the next id -- and the
+        existing `append` merges the dense streams; n_users grows to the dictionary's n_ids (an empty dict brings a history level with a dictionary that
+        another history has extended).  No host work per event or per user.
+        ValueError -- nothing is modified: not a keyed history; a stream's tensors do not fit; what `append` refuses."""
+        from . import ingest
+        if self.user_dict is None:
+            raise ValueError("append_keys needs a keyed history (DeviceHistory.from_key_streams)")
+        for ev, tup in streams.items():      # everything `append` would refuse, before the dictionary grows
+            if len(tup) != (4 if self.check else 3):
+                raise ValueError(f"stream {ev!r}: (user keys, items, times{', user check keys' if self.check else ''}) expected")
+            keys, items, times = tup[:3]
+            if keys.dtype != torch.int64 or items.dtype not in (torch.int32, torch.int64) or keys.numel() != items.numel():
+                raise ValueError(f"stream {ev!r}: int64 user keys and int32 item ids or int64 item keys of one length expected")
+            if self.check and (tup[3].dtype != torch.int64 or tup[3].numel() != keys.numel()):
+                raise ValueError(f"stream {ev!r}: int64 check keys, one per event, expected")
+            if times is not None and (times.dtype != torch.int64 or times.numel() != keys.numel()):
+                raise ValueError(f"stream {ev!r}: int64 times, one per event, expected")
+            if items.dtype == torch.int64 and self.model is None:
+                raise ValueError(f"stream {ev!r}: item keys need the model whose catalogue they are looked up in")
+            st = self.types.get(ev)
+            if st is None and self.model is None:
+                raise ValueError(f"stream {ev!r}: the history does not hold this event type and was built without a model to take its columns from")
+            if st is not None and (times is None) != (st.times is None):
+                raise ValueError(f"stream {ev!r}: the stream {'has no times' if st.times is None else 'has times'}, the batch must agree")
+            if st is not None and st.n_events < 0:
+                raise ValueError(f"stream {ev!r}: built without its number of events (_Stream.n_events)")
+        dense = {}
+        for ev, tup in streams.items():
+            keys, items, times = tup[:3]
+            if items.dtype == torch.int64:
+                items = ingest.dictionary_lookup(self.sess, self.model.key_dictionary(ev), items)
+            users, _ = self.user_dict.extend(keys, check_keys=tup[3] if self.check else None)
+            dense[ev] = (users, items, times)
+        return self.append(dense, n_users=self.user_dict.n_ids)
 
     @staticmethod
     def _col_map(sess: DeviceSession, model, ev: str) -> Tuple[int, Optional[torch.Tensor]]:
@@ -193,7 +269,7 @@ class DeviceHistory:
     def trim(self, before_ms: Optional[int] = None, drop_users=None, events: Optional[List[str]] = None) -> "DeviceHistory":
         """Retention, in place (decision D22 of DESIGN.md; include/urcco.h urcco_dev_history_trim); returns self.  before_ms: the events with time <
         before_ms leave the event types named in `events` (default: every type that has times) -- the reference's eventWindow.  drop_users: an
-        iterable of user keys (resolved through user_index, unknown ones ignored) or an int32 tensor of dense ids; their events leave EVERY event type,
+        iterable of user keys (resolved through user_indices, once per call; unknown ones ignored) or an int32 tensor of dense ids; their events leave EVERY event type,
         whatever `events` says -- the event store's $delete of a user.  The users keep their ids: user_ids and n_users are unchanged, a dropped user
         is answered like a user without events.  Every result afterwards is the one of from_streams over the filtered whole streams with the same
         n_users; `append` works on as before.
@@ -218,7 +294,7 @@ class DeviceHistory:
                 raise ValueError("trim: drop_users as a tensor holds int32 dense user ids")
             drop = drop_users.reshape(-1).to(sess.device) if drop_users.numel() else None
         elif drop_users is not None:
-            ids = [i for i in (self.user_index(u) for u in drop_users) if i >= 0]
+            ids = [i for i in self.user_indices(drop_users) if i >= 0]
             drop = torch.tensor(ids, dtype=torch.int32).to(sess.device) if ids else None
         todo = [ev for ev in self.types if ev in by_time or drop is not None]
         for ev in todo:

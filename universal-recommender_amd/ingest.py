@@ -24,13 +24,68 @@ from .device import DevCsr, DeviceSession, _ptr
 
 
 class DevDictionary:
-    """urcco_key_table + the first-occurrence positions of its ids (first_pos[id] = index into the stream it was built from)."""
+    """urcco_key_table + the first-occurrence positions of its ids (first_pos[id] = index into the stream it was built from).
+
+    `extend` makes the dictionary growable (decision D26 of DESIGN.md): a table built with min_count = 1 -- `dictionary_build` over no keys gives the empty
+    one -- takes batch after batch, and answers every lookup as one build over all of them would.  first_pos speaks of the build's stream alone: it
+    becomes None with the first id an extend adds, and dictionary_verify / _verify_against, which index it, are then refused (BAD_ARG); an extended
+    dictionary is checked through extend(check_keys=...)."""
 
     def __init__(self, sess: DeviceSession, handle: C.c_void_p, n_ids: int, first_pos: torch.Tensor):
         self._sess = sess
         self.handle = handle
         self.n_ids = int(n_ids)
         self.first_pos = first_pos[: self.n_ids]
+        self.check_keys: Optional[torch.Tensor] = None   # extend(check_keys=...): int64 [>= n_ids] on the device, the check key of every id's first appearance
+
+    def with_check_keys(self, check_keys: torch.Tensor) -> "DevDictionary":
+        """Seeds the per-id check keys of a dictionary that dictionary_build made: check_keys = the second hashes of the stream it was built from, gathered
+        at first_pos.  Returns self."""
+        if self.first_pos is None:
+            raise ValueError("the dictionary was extended already: its first positions are gone")
+        self.check_keys = check_keys[self.first_pos].clone() if self.n_ids else self._sess.empty(1, torch.int64)
+        return self
+
+    def extend(self, keys: torch.Tensor, select: Optional[torch.Tensor] = None, check_keys: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+        """A batch against the live table (urcco_dev_dictionary_extend): keys the dictionary knows keep their ids, the others get the next ids in order of
+        first appearance.  Returns (ids int32 [n]: the id of every position, -1 where select[p] < 0; new_pos int64 [ids added]: the batch position of each
+        new id's first appearance -- with the batch's strings the caller extends its id -> string list).  n_ids grows; one synchronisation.
+        UrccoError BAD_ARG with the dictionary unchanged: a selected position holds the reserved key ~0, the table was built with min_count > 1, too many ids.
+
+        check_keys (the second hashes of the batch's strings): the dictionary keeps one check key per id on the device -- those of the new ids are gathered
+        at new_pos and appended to a buffer that grows as the history's buffers do (history.GROWTH) -- and HashCollision is raised when a position's check
+        key differs from its id's.  A dictionary that holds ids needs them for every id (with_check_keys after the build, check_keys in every extend:
+        ValueError otherwise, before anything changes).  After a HashCollision the batch IS in the dictionary: its other new keys have their ids and
+        check keys, n_ids has grown; the colliding string shares the id of the string it collided with and has no id of its own -- re-key with another
+        seed, as after a collision in the build."""
+        from .history import GROWTH
+        sess, n = self._sess, int(keys.numel())
+        if check_keys is not None and int(check_keys.numel()) != n:
+            raise ValueError("extend: one check key per key expected")
+        if self.n_ids and (check_keys is None) != (self.check_keys is None):
+            raise ValueError("extend: the dictionary keeps check keys for every id or for none (with_check_keys after the build, check_keys in every extend)")
+        ids, new_pos = sess.empty(max(n, 1), torch.int32), sess.empty(max(n, 1), torch.int64)
+        n_ids = C.c_int64()
+        sess._check(sess.lib.urcco_dev_dictionary_extend(sess.handle, self.handle, n, _ptr(keys), _ptr(select), _ptr(ids), _ptr(new_pos), C.byref(n_ids)))
+        n_before, self.n_ids = self.n_ids, int(n_ids.value)
+        ids, new_pos = ids[:n], new_pos[: self.n_ids - n_before]
+        if self.n_ids > n_before:
+            self.first_pos = None
+        if check_keys is not None:
+            buf = self.check_keys
+            if buf is None or int(buf.numel()) < self.n_ids:
+                buf = sess.empty(max(self.n_ids, GROWTH * (int(buf.numel()) if buf is not None else 0), 1), torch.int64)
+                if n_before:
+                    buf[:n_before].copy_(self.check_keys[:n_before])
+            buf[n_before: self.n_ids] = check_keys[new_pos]
+            self.check_keys = buf
+            took_part = ids >= 0
+            bad = int((check_keys[took_part] != buf[ids[took_part].long()]).sum().item())
+            if bad:
+                err = HashCollision(f"two ids share a 64-bit key ({bad} position(s) of the batch carry another check key than their id)")
+                err.n_mismatch = bad      # what dictionary_verify counts for a build
+                raise err
+        return ids, new_pos
 
     def close(self):
         if self.handle:

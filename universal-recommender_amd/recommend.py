@@ -81,6 +81,7 @@ class DeviceModel:
         self.dates = dates or {}        # date property -> int64 [n_items] epoch milliseconds, NO_VALUE where the item has none
         self._term_weights: Dict[str, Dict[str, torch.Tensor]] = {}   # term_weights(kind), built on first use
         self.rank_fields: Dict[str, torch.Tensor] = {}   # set_ranks: ranking field name -> int64 [n_items], _lib.RANK_NONE = no rank
+        self._key_dicts: Dict[str, object] = {}          # key_dictionary(ev), built on first use
 
     def set_ranks(self, fields: Dict[str, torch.Tensor]) -> "DeviceModel":
         """The backfill order from rank fields on the device (decision D24 of DESIGN.md): fields = {ranking field name: int64 device tensor [n_items],
@@ -182,6 +183,27 @@ class DeviceModel:
         except (TypeError, ValueError):
             return None
         return i if 0 <= i < c.n_cols else None
+
+    def key_dictionary(self, ev: str):
+        """The device dictionary 64-bit key -> column id of an event type (decision D26 of DESIGN.md): preparator.hash_keys of the strings of its column_ids in
+        id order -- of item_ids for an event name outside the model -- built once, on first use.  First-appearance ids over distinct strings in id order
+        ARE those ids, so a lookup of an item's key answers its column id, and -1 for a key outside the catalogue.  ValueError: the model carries no
+        strings for that id space; ingest.HashCollision: two of them share a key."""
+        from . import ingest
+        from .preparator import hash_keys
+        d = self._key_dicts.get(ev)
+        if d is None:
+            c = self.by_name.get(ev)
+            names = c.column_ids if c is not None else self.item_ids
+            if names is None:
+                raise ValueError(f"event {ev!r}: the model was built over dense integer ids, it has no strings to key")
+            keys = torch.from_numpy(hash_keys(names.keys, library=self.sess.lib)).to(self.sess.device)
+            d = ingest.dictionary_build(self.sess, keys)
+            if d.n_ids != len(names):
+                d.close()
+                raise ingest.HashCollision(f"event {ev!r}: two item ids share a 64-bit key")
+            self._key_dicts[ev] = d
+        return d
 
     def term_weights(self, kind: str = "idf") -> Dict[str, torch.Tensor]:
         """{event name or list-of-strings property name: uint32 device tensor [n_cols]}: the term weights of decision D20 for every matrix a should-clause
@@ -346,6 +368,7 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
     served = model.properties is not None
     from .history import DeviceHistory
     dh = history if isinstance(history, DeviceHistory) else None
+    q_user_ids = dh.user_indices([q.get("user") for q in queries]) if dh is not None else None      # once per call: a keyed history resolves them on the device
     dated = served and ap.availableDateName is not None and ap.expireDateName is not None and ap.availableDateName in model.dates and ap.expireDateName in model.dates
     for n, q in enumerate(queries):
         user_bias = q.get("userBias", ap.userBias if ap.userBias is not None else 1.0)
@@ -447,7 +470,7 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
         # a rule cannot be absent for one row of a call: queries share a call only when they carry the same rules and the same property clauses
         key = (_boost(user_bias), _boost(item_bias), _boost(set_bias), start + num, tuple(slot for slot, _ in boosted), tuple(rules), hist_key)
         groups.setdefault(key, []).append(n)
-        plans.append((terms, np.unique(np.array([i for i in excl if i is not None], np.int64)), start, num, rules, dh.user_index(user) if dh is not None else -1,
+        plans.append((terms, np.unique(np.array([i for i in excl if i is not None], np.int64)), start, num, rules, q_user_ids[n] if dh is not None else -1,
                       user is not None, q_item))
 
     # ---- one call per group ----
@@ -658,7 +681,7 @@ def user_recommendations(algo, model: DeviceModel, history, users=None, num: Opt
             raise ValueError("users as a tensor: dense user ids, int32, one dimension")
         q_all = users.to(dev)
     else:
-        q_all = torch.tensor([dh.user_index(u) for u in users], dtype=torch.int32).to(dev)
+        q_all = torch.tensor(dh.user_indices(users), dtype=torch.int32).to(dev)
     n = int(q_all.numel())
     dates = []
     if served and ap.availableDateName is not None and ap.expireDateName is not None and ap.availableDateName in model.dates and ap.expireDateName in model.dates:
