@@ -165,6 +165,19 @@ class DeviceProblem:
             self.ev.append((s.n_cols, rp, pos, items, times, self._put(s.col_map) if s.col_map is not None else None))
         self.by_user = [user_positions(s, p.n_users) if subset is None else user_positions_of(s, subset) for s in p.streams]
 
+    @classmethod
+    def over(cls, sess, p: Problem, ev):
+        """The problem over streams and indexes that already live on the device -- ev: per stream (n_cols, idx_row_ptr, idx_pos, items, times | None,
+        col_map | None), e.g. the live tensors of a DeviceHistory; only the queries and the extra rows are copied"""
+        d = cls.__new__(cls)
+        d.sess, d.p, d._put_cache = sess, p, {}
+        d.q_users = d._put(p.q_users)
+        d.extra = (d._put(p.extra_rp), d._put(p.extra_ci))
+        d.ev = list(ev)
+        assert len(d.ev) == len(p.streams)
+        d.by_user = [user_positions(s, p.n_users) for s in p.streams]
+        return d
+
     def _put(self, a):
         if id(a) in self._put_cache:              # streams may share an array (two event types over one stream): one copy on the device
             return self._put_cache[id(a)][1]

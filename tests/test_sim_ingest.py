@@ -250,3 +250,110 @@ def test_native_string_hash_known_answers_and_collision_check(sim_session, sim_l
     uk2_bad[np.asarray(users2) == "v9"] = uk[users.index("u2")]
     with pytest.raises(ingest.HashCollision):
         ingest.prepare_device(sim_session, [("buy", t(uk), t(ik), t(uc), t(ic)), ("view", t(uk2_bad), t(ik2), t(uc2), t(ic2))], 1)
+
+
+# ---- the key hash against the public specification -------------------------------------------------------------------------------------------------
+_M64 = 2**64 - 1
+_P1, _P2, _P3, _P4, _P5 = 11400714785074694791, 14029467366897019727, 1609587929392839161, 9650029242287828579, 2870177450012600261
+
+
+def _rotl(x, r):
+    return ((x << r) | (x >> (64 - r))) & _M64
+
+
+def _round(acc, lane):
+    return (_rotl((acc + lane * _P2) & _M64, 31) * _P1) & _M64
+
+
+def xxh64_ref(data: bytes, seed: int = 0) -> int:
+    """XXH64 restated from the public xxHash specification (doc/xxhash_spec.md of the xxHash project), integers masked to 64 bits: stripes of 32
+    bytes into four accumulators, their convergence, the 8 / 4 / 1 byte tail, the avalanche."""
+    n, p = len(data), 0
+    le = lambda k: int.from_bytes(data[p:p + k], "little")      # noqa: E731
+    if n >= 32:
+        acc = [(seed + _P1 + _P2) & _M64, (seed + _P2) & _M64, seed & _M64, (seed - _P1) & _M64]
+        while p + 32 <= n:
+            for k in range(4):
+                acc[k] = _round(acc[k], le(8))
+                p += 8
+        h = (_rotl(acc[0], 1) + _rotl(acc[1], 7) + _rotl(acc[2], 12) + _rotl(acc[3], 18)) & _M64
+        for a in acc:
+            h = ((h ^ _round(0, a)) * _P1 + _P4) & _M64
+    else:
+        h = (seed + _P5) & _M64
+    h = (h + n) & _M64
+    while p + 8 <= n:
+        h = (_rotl(h ^ _round(0, le(8)), 27) * _P1 + _P4) & _M64
+        p += 8
+    if p + 4 <= n:
+        h = (_rotl(h ^ (le(4) * _P1) & _M64, 23) * _P2 + _P3) & _M64
+        p += 4
+    while p < n:
+        h = (_rotl(h ^ (data[p] * _P5) & _M64, 11) * _P1) & _M64
+        p += 1
+    h = ((h ^ (h >> 33)) * _P2) & _M64
+    h = ((h ^ (h >> 29)) * _P3) & _M64
+    return h ^ (h >> 32)
+
+
+def _key_ref(s: str, seed: int) -> int:
+    h = xxh64_ref(s.encode("utf-8"), seed)
+    return 0 if h == _M64 else h      # ~0 is the device dictionary's reserved value
+
+
+def utf8_string(rng, n_bytes: int, last: int = 0) -> str:
+    """A str of random code points that encodes to exactly n_bytes of UTF-8: characters of 1 to 4 bytes, so most bytes are >= 0x80.  last: the
+    encoded length of the final character (0: any) -- behind a character of 2 to 4 bytes the string's last 1 to 3 bytes are all >= 0x80"""
+    spans = ((0x01, 0x80), (0x80, 0x800), (0x800, 0xD800), (0x10000, 0x110000))      # below the surrogates: every code point encodes
+    out, left = [], n_bytes - last
+    while left:
+        k = int(rng.integers(1, min(left, 4) + 1))
+        out.append(chr(int(rng.integers(*spans[k - 1]))))
+        left -= k
+    if last:
+        out.append(chr(int(rng.integers(*spans[last - 1]))))
+    return "".join(out)
+
+
+HASH_LENGTHS = range(0, 101)
+HASH_MANY = 70_000      # above the 65536 strings from which urcco_hash_strings splits the work over threads
+
+
+def test_native_string_hash_against_the_specification(sim_lib):
+    """hash_keys == XXH64 of the UTF-8 bytes for every length from 0 to 100 bytes (no stripe, one to three stripes, each with every tail of 8-, 4- and
+    1-byte steps: 36 = one stripe and a 4-byte tail) over random non-ASCII strings, for the key seed and the check seed.  Per length one string of
+    random characters and one that ends in a character of 2, 3 and 4 bytes each: the one-byte steps of the tail then read only bytes >= 0x80.  The
+    pure-Python restatement is itself held to the known answers of the public algorithm."""
+    from universal_recommender_amd.preparator import CHECK_SEED, HASH_SEED, hash_keys
+    assert [xxh64_ref(s.encode()) for s in ("", "a", "user-1", "Iphone 6", "x" * 40)] == [0xef46db3751d8e999, 0xd24ec4f1a98c6e5b, 0xa173746b114c6be8,
+                                                                                         0x4ae1af7e7ed5ca3b, 0x926f564e1b3e18d5]
+    assert xxh64_ref(b"", CHECK_SEED) == 0xc4349fc93c010000 and xxh64_ref(b"x" * 40, CHECK_SEED) == 0x5c39218a651d07bb
+    rng = np.random.default_rng(61)
+    strs = [utf8_string(rng, n, last) for n in HASH_LENGTHS for last in (0, 2, 3, 4) if last <= n]
+    enc = [s.encode("utf-8") for s in strs]
+    assert {len(e) for e in enc} == set(HASH_LENGTHS) and len(strs) > 3 * len(HASH_LENGTHS)
+    assert any(len(e) == 36 and min(e[32:]) >= 0x80 for e in enc)                                  # a 32-byte stripe, then a 4-byte tail
+    for tail in (1, 2, 3):      # a tail of `tail` one-byte steps, all on bytes >= 0x80: alone, behind the 4-byte step, the 8-byte steps, a stripe, and all of them
+        assert all(any(len(e) == n and min(e[-tail:]) >= 0x80 for e in enc) for n in (4 + tail, 8 + tail, 12 + tail, 32 + tail, 44 + tail) + ((tail,) if tail > 1 else ()))
+    assert HASH_SEED != CHECK_SEED
+    for seed in (HASH_SEED, CHECK_SEED):
+        got = hash_keys(strs, seed, sim_lib).view(np.uint64).tolist()
+        assert got == [_key_ref(s, seed) for s in strs], [len(e) for e, g, s in zip(enc, got, strs) if g != _key_ref(s, seed)]
+
+
+def test_native_string_hash_over_the_threaded_split(sim_lib):
+    """One call over 70 000 strings equals the specification string by string, and the strings hashed in calls below the split: strings of 1 to 45
+    bytes, non-ASCII among them, all distinct, so a range hashed twice, skipped or shifted at a boundary shows.  The library splits n >= 65536 at
+    n * t / nt over nt = 8 threads on a host of 16 or more hardware threads and over 4 from 4 on; on a smaller host it does not split, and this test
+    then checks the single-threaded call alone."""
+    from universal_recommender_amd.preparator import hash_keys
+    rng = np.random.default_rng(67)
+    pool = [utf8_string(rng, int(n)) for n in rng.integers(0, 41, 500)]
+    strs = [f"{pool[k % 500]}{k}" for k in range(HASH_MANY)]
+    assert HASH_MANY >= 1 << 16 and len(set(strs)) == HASH_MANY and any(max(s.encode()) >= 0x80 for s in strs)
+    got = hash_keys(strs, 0, sim_lib).view(np.uint64)
+    assert got.size == HASH_MANY
+    want = np.array([_key_ref(s, 0) for s in strs], np.uint64)
+    assert np.array_equal(got, want), np.flatnonzero(got != want)[:10]
+    per_call = np.concatenate([hash_keys(strs[a:a + 999], 0, sim_lib).view(np.uint64) for a in range(0, HASH_MANY, 999)])      # single-threaded calls
+    assert np.array_equal(got, per_call), np.flatnonzero(got != per_call)[:10]

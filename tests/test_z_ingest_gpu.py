@@ -35,3 +35,11 @@ def test_events_to_model_without_leaving_the_device_on_gpu(gpu_session):
 
 def test_native_hash_and_collision_check_on_gpu(gpu_session):
     logic.test_native_string_hash_known_answers_and_collision_check(gpu_session, gpu_session.lib)
+
+
+def test_native_hash_against_the_specification_on_gpu(gpu_session):
+    logic.test_native_string_hash_against_the_specification(gpu_session.lib)
+
+
+def test_native_hash_over_the_threaded_split_on_gpu(gpu_session):
+    logic.test_native_string_hash_over_the_threaded_split(gpu_session.lib)
