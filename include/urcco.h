@@ -638,7 +638,27 @@ int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double
  *                     hold, the result may be wrong, but no access leaves the arrays
  *   URCCO_BAD_ARG: n_events >= 2^31, a negative count, n_users > 0x7ffffff0, a NULL the call needs, out_times and times_ms not NULL together.  Needed:
  *   items, idx_pos, out_items and out_pos only when n_events > 0; idx_row_ptr when n_users > 0; drop_users when n_drop > 0; out_row_ptr and out_counts always.
- * urcco_dev_history_users / urcco_dev_history_matrix (DESIGN.md decision D23): the Preparator's output -- which users train, and one event type's user x
+ * urcco_dev_history_cap (DESIGN.md decision D27): urcco_dev_history_trim with a bound on the events a user keeps.  The arguments are the trim's plus
+ *   max_per_user; every rule, output, capacity and malformed-index guarantee of the trim holds unchanged, and one rule is added:
+ *   dropped by cap    the valid index entries of user u are those of its segment (row starts clamped as the trim clamps them) with
+ *                     0 <= idx_pos[e] < n_events.  The recency key of an entry is the rows': (times_ms[p] ^ sign bit, p) compared as unsigned, p alone
+ *                     when times_ms == NULL.  The event an entry names is dropped when the entry's key is not among the max_per_user largest keys of
+ *                     u's valid entries.  Keys are unique, so the order is total: the result is reproducible bit for bit and does not depend on the
+ *                     order inside a segment
+ *   kept events       an event is kept iff it passes the time rule, is not a listed user's and passes the cap rule.  The three rules are independent:
+ *                     each is decided on the stream as it is passed in.  The time rule removes a suffix of every user's recency order, so cap-then-time
+ *                     equals time-then-cap: one call with all three rules gives what a call with the cap alone and a call with the other two give,
+ *                     in either order
+ *   nobody's events   a position that no index entry names follows the time rule alone, as in the trim
+ *   no cap            max_per_user == INT32_MAX: the outputs are bit-identical to urcco_dev_history_trim's with the same other arguments (the same
+ *                     kernels are launched)
+ *   classes           by the entries m of the user's segment, chosen on the device: m <= max_per_user nothing (two row starts are read); m <= 64 one
+ *                     wave ranking the keys in registers; m <= 4096 one block, the threshold = the max_per_user-th largest key by a radix select
+ *                     over keys in LDS; larger the same with the keys re-read from global memory per discriminating digit.  No sort of a user's events
+ *   malformed index   entries outside 0 .. n_events take no part in the ranking and drop nothing; duplicated positions may give a wrong result; no
+ *                     access leaves the arrays
+ *   URCCO_BAD_ARG: max_per_user < 1, and the trim's refusals.
+ * urcco_dev_history_users /urcco_dev_history_matrix (DESIGN.md decision D23): the Preparator's output -- which users train, and one event type's user x
  *   column matrix with sorted, duplicate-free rows -- from the stream and the index alone; no `users` array exists after an append or a trim.
  *   window            the event at stream position p is in the window when times_ms == NULL, or when t_lo <= times_ms[p] and (t_hi == INT64_MAX or
  *                     times_ms[p] < t_hi): signed compares, the start inclusive, the end exclusive as in urcco_dev_pop_counts, INT64_MAX = no end.  With
@@ -673,7 +693,7 @@ int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double
  * stats_dev (nullable, int64[URCCO_HIST_STATS_LEN]): (query, type) pairs served by [0] the wave class (<= 64 events), [1] the block class (<= 4096, keys in
  *   LDS), [2] the global class; [3] pairs that ran the select (n_u > max_items); exclusion rows built by [4] one wave, [5] one block; [6] rows dropped
  *   for lack of capacity (0 when the caller sized its buffers by the bounds); [7] 0.
- * All seven enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: n_events >= 2^31, n_types outside
+ * All eight enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: n_events >= 2^31, n_types outside
  * 1..URCCO_REC_MAX_CLAUSES, max_items < 1, n_queries * (n_types + 1) >= 2^31, a NULL the call needs, a half-NULL extra pair, a negative capacity.
  * ABI: additions within ABI 305 -- the presence of the symbols is the feature test. */
 #define URCCO_HIST_STATS_LEN 8
@@ -693,6 +713,15 @@ int urcco_dev_history_trim(urcco_session* s,
                            int32_t* out_items, int64_t* out_times /* NULL iff times_ms NULL */,
                            int64_t* out_row_ptr /* [n_users + 1] */, int32_t* out_pos,
                            int64_t* out_counts /* device [2] */);
+int urcco_dev_history_cap(urcco_session* s,
+                          int64_t n_events, const int32_t* items, const int64_t* times_ms /* nullable */,
+                          int64_t n_users, const int64_t* idx_row_ptr /* [n_users + 1] */, const int32_t* idx_pos,
+                          int64_t min_time_ms,                          /* read only when times_ms != NULL */
+                          int64_t n_drop, const int32_t* drop_users,    /* device; nullable iff n_drop == 0 */
+                          int32_t max_per_user,                         /* >= 1; INT32_MAX = no cap */
+                          int32_t* out_items, int64_t* out_times /* NULL iff times_ms NULL */,
+                          int64_t* out_row_ptr /* [n_users + 1] */, int32_t* out_pos,
+                          int64_t* out_counts /* device [2] */);
 /* which users train, and under which row number */
 int urcco_dev_history_users(urcco_session* s, int64_t n_events, const int64_t* times_ms /* nullable */,
                             int64_t n_users, const int64_t* idx_row_ptr /* [n_users + 1] */, const int32_t* idx_pos,
@@ -843,7 +872,28 @@ int urcco_dev_item_rows(urcco_session* s, int64_t n_queries, const int32_t* q_it
  * urcco_dev_props_dates: out[i] = date_values[position of S] when the property is alive, else INT64_MIN.  date_values: int64 per stream position.
  * urcco_dev_props_exists: out_mask[i] = 0 iff item i is deleted by the rule over the n_props properties whose t_set arrays are given, else 1; an item
  *   without any event gets 1.  The mask is urcco_dev_recommend's item_mask.
- * All six enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: a negative n_items, n_new, n, n_values,
+ * urcco_dev_props_compact (DESIGN.md decision D28): one property's stream without the values that no item's state names any more.
+ *   winners         the positions pos_set[i] - 1 that lie in 0 .. state.n_events, one per item; K = their number.  Numbered in ascending old position they
+ *                   are the new stream: positions keep their relative order, so a later urcco_dev_props_apply with pos_base = K breaks equal-time ties
+ *                   exactly as it would have on the uncompacted stream
+ *   out_pos_set     [n_items]: the new position + 1; 0 where pos_set[i] was 0 or named no position
+ *   out_old_pos     [0 .. K): the old position of every new position -- what the caller gathers its own per-position arrays by
+ *   lists           val_ptr != NULL: out_val_ptr[0 .. K] and out_values[0 .. V) hold the winners' slices in new order.  A winner whose property is not
+ *                   alive by THE RULE (time(S) <= U or <= D) gets an empty slice: it can never become alive again, because a maximum only grows; its
+ *                   position is kept, so that t_set and pos_set stay consistent.  V = out_val_ptr[K]
+ *   dates           date_values != NULL: out_date_values[0 .. K) is gathered.  val_ptr and date_values are not given together; with neither, the
+ *                   positions alone are compacted
+ *   out_counts      device int64 [2] = {K, V} (V = 0 without val_ptr)
+ *   untouched       t_set, t_unset and t_del are read to decide "alive" and never written; pos_set is read only
+ *   capacities      nothing is written at or past out_old_pos[K], out_val_ptr[K + 1], out_values[V] or out_date_values[K].  K <= min(n_items,
+ *                   state.n_events) and V <= n_values: a caller that does not know them sizes by those bounds.  Outputs must not overlap inputs
+ *   malformed input slice ends are clamped into 0 .. n_values as _rows clamps them, and the new slice starts into 0 .. n_values (slices that overlap cannot
+ *                   make V exceed n_values); two items that name one position keep it once.  The result may be wrong, no access leaves the arrays
+ *   The slices are copied balanced by entries, not by items: one winner may hold 8193 values while a million hold two.  Atomics only to mark the winners.
+ *   URCCO_BAD_ARG: the state's refusals (below), a negative n_values, val_ptr and date_values together, a NULL the call needs.  Needed: out_counts always;
+ *   out_pos_set when n_items > 0; out_old_pos when n_items > 0 and state.n_events > 0; out_val_ptr with val_ptr; values and out_values with val_ptr when
+ *   also n_values > 0, n_items > 0 and state.n_events > 0; out_date_values with date_values when n_items > 0 and state.n_events > 0.
+ * All seven enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: a negative n_items, n_new, n, n_values,
  * n_cols, capacity or state.n_events; pos_base < 0 or pos_base + n_new >= 2^31; state.n_events >= 2^31; n_props outside 0..URCCO_PROP_MAX; a NULL the call
  * needs.  Needed: items and times_ms when n_new (n) > 0; the state arrays the call names when n_items > 0 (apply: also with n_new == 0); val_ptr when
  * n_items > 0 and state.n_events > 0; values when n_values > 0; col_idx when capacity > 0; date_values when state.n_events > 0; row_ptr always; t_sets and
@@ -869,6 +919,12 @@ int urcco_dev_props_rows(urcco_session* s, int32_t n_items, const urcco_prop_sta
 int urcco_dev_props_dates(urcco_session* s, int32_t n_items, const urcco_prop_state* state /* host */, const int64_t* date_values, int64_t* out /* [n_items] */);
 int urcco_dev_props_exists(urcco_session* s, int32_t n_items, const uint64_t* t_del, const uint64_t* const* t_sets /* host array of n_props device pointers */,
                            int32_t n_props, uint8_t* out_mask /* [n_items] */);
+int urcco_dev_props_compact(urcco_session* s, int32_t n_items, const urcco_prop_state* state /* host */,
+                            const int64_t* val_ptr /* nullable: [state.n_events + 1] of a list property */, const int32_t* values, int64_t n_values,
+                            const int64_t* date_values /* nullable: [state.n_events] of a date property */,
+                            uint32_t* out_pos_set /* [n_items] */, int32_t* out_old_pos /* [K] */,
+                            int64_t* out_val_ptr /* [K + 1] */, int32_t* out_values /* [V] */, int64_t* out_date_values /* [K] */,
+                            int64_t* out_counts /* device [2]: K, V */);
 
 /* Test hooks (device level): LLR of SimilarityAnalysis.logLikelihoodRatio evaluated by the device code for
  * n argument tuples; u01 of the down-sampling RNG.  All pointers device. */

@@ -237,6 +237,7 @@ SYMBOLS = {
     "urcco_dev_history_index": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_append": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_trim": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p]),
+    "urcco_dev_history_cap": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, C.c_int32, _p, _p, _p, _p, _p]),
     "urcco_dev_history_users": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, C.c_int32, _p, _p]),
     "urcco_dev_history_matrix": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, C.c_int32, _p, C.c_int64, _p, _p, C.c_int64, _p]),
     "urcco_dev_history_ranks": (C.c_int, [_p, C.POINTER(RankStream), C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _p, _p]),
@@ -251,6 +252,7 @@ SYMBOLS = {
     "urcco_dev_props_rows": (C.c_int, [_p, C.c_int32, C.POINTER(PropState), _p, _p, C.c_int64, C.c_int32, _p, _p, C.c_int64]),
     "urcco_dev_props_dates": (C.c_int, [_p, C.c_int32, C.POINTER(PropState), _p, _p]),
     "urcco_dev_props_exists": (C.c_int, [_p, C.c_int32, _p, C.POINTER(C.c_void_p), C.c_int32, _p]),
+    "urcco_dev_props_compact": (C.c_int, [_p, C.c_int32, C.POINTER(PropState), _p, _p, C.c_int64, _p, _p, _p, _p, _p, _p, _p]),
     "urcco_dev_llr": (C.c_int, [_p, C.c_int64, _p, _p, _p, _p, _p]),
     "urcco_dev_u01": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p]),
     "urcco_dev_u01_rng": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, C.c_int32, _p]),

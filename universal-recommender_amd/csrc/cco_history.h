@@ -340,6 +340,164 @@ hipError_t launch_history_trim(hipStream_t st, int n_cu, const TrimArgs& a) {
   return hipGetLastError();
 }
 
+// ---- cap (decision D27) --------------------------------------------------------------------------------------------
+// The trim with one more rule: of every user only the max_per_user most recent events stay.  The cap marks what it drops into the bitmap D that
+// ht_mark_kernel fills, before ht_keep_kernel turns D into S; everything behind the mark is the trim's sequence, unchanged.  The recency key is the
+// rows' (time ^ sign, position): an entry is dropped when its key is not among the max_per_user largest of the user's valid entries (those naming a
+// position inside the stream).  Three classes by the user's entries m = its clamped segment, chosen on the device:
+//   m <= cap   nothing: a lane per user reads the two row starts and is done
+//   <= 64      one wave, a user at a time by ballot rounds over the wave's 64 users: keys in registers, rank by cross-lane compares
+//   larger     one block per user of `list` (cursor ctr[0], filled by the wave kernel): the threshold = the cap-th largest key by the select of
+//              cco_select.h, keys in LDS up to SR_LDS entries, re-read from global memory per discriminating digit beyond; entries below it set their bit
+// An entry that names no position has the key (0, 0) in the select and sets no bit: no valid key is smaller, so the threshold among all m keys is the
+// threshold among the valid ones whenever more than cap of them exist, and (0, 0) -- nothing dropped -- otherwise.  No sort; atomicOr only for dropped
+// entries, one atomicAdd on the cursor per user beyond a wave.  Row starts are clamped into 0 .. n_e as in the mark: no access leaves the arrays.
+__global__ __launch_bounds__(256) void hc_mark_wave_kernel(int64_t n_events, int64_t n_users, const int64_t* __restrict__ idx_row_ptr, const int32_t* __restrict__ idx_pos,
+                                                           const int64_t* __restrict__ times_ms, int32_t cap, unsigned long long* __restrict__ bits,
+                                                           int32_t* __restrict__ list, unsigned long long* __restrict__ ctr) {
+  const int lane = threadIdx.x & (SR_WAVE - 1);
+  const int64_t n_e = ht_entries(idx_row_ptr, n_users, n_events);
+  const int64_t n_waves = (int64_t)gridDim.x * (256 / SR_WAVE);
+  for (int64_t u0 = ((int64_t)blockIdx.x * (256 / SR_WAVE) + threadIdx.x / SR_WAVE) * SR_WAVE; u0 < n_users; u0 += n_waves * SR_WAVE) {  // wave-uniform
+    const int64_t u = u0 + lane;
+    int64_t lo = 0, m = 0;
+    if (u < n_users) {
+      lo = ht_clamp(idx_row_ptr[u], n_e);
+      m = ht_clamp(idx_row_ptr[u + 1], n_e) - lo;
+    }
+    if (m > SR_WAVE && m > cap) list[atomicAdd(ctr, 1ull)] = (int32_t)u;
+    unsigned long long todo = __ballot(m > cap && m <= SR_WAVE);
+    while (todo) {  // wave-uniform: one user of the wave class per round
+      const int src = __ffsll((long long)todo) - 1;
+      todo &= todo - 1ull;
+      const int64_t seg = __shfl((long long)lo, src);
+      const int n = (int)__shfl((long long)m, src);
+      unsigned p = 0;
+      unsigned long long tk = 0;
+      bool valid = false;
+      if (lane < n) {
+        const int q = idx_pos[seg + lane];
+        valid = q >= 0 && q < n_events;
+        if (valid) {
+          p = (unsigned)q;
+          tk = times_ms ? (unsigned long long)times_ms[q] ^ HS_SIGN : 0ull;
+        }
+      }
+      int rank = 0;  // valid entries of the user more recent than this lane's
+      for (int o = 0; o < n; ++o) {
+        const unsigned long long ot = __shfl(tk, o);
+        const unsigned op = __shfl(p, o);
+        const int ov = __shfl((int)valid, o);
+        rank += (ov && (ot > tk || (ot == tk && op > p))) ? 1 : 0;
+      }
+      if (valid && rank >= cap) atomicOr(&bits[p >> 6], 1ull << (p & 63));
+    }
+  }
+}
+
+// The dropped entries of one user of m > max(cap, 64) entries, by the whole block behind the barrier that makes the LDS keys visible.  IN_LDS: the keys
+// are s_time[i], s_pos[i] (the raw entry; s_time is 0 where it names no position); else they are read through ipos.  A template parameter for hs_window's reason.
+template <bool IN_LDS>
+__device__ __forceinline__ void hc_mark_user(int64_t n_events, unsigned n, unsigned cap, const int32_t* __restrict__ ipos, const int64_t* __restrict__ times,
+                                             const unsigned long long* s_time, const unsigned* s_pos, SelScratch& s_select, unsigned long long* __restrict__ bits) {
+  const unsigned n_ev = (unsigned)n_events;  // < 2^31: a negative entry is beyond it as an unsigned
+  auto raw_p = [&](unsigned i) -> unsigned { return IN_LDS ? s_pos[i] : (unsigned)ipos[i]; };
+  auto key_p = [&](unsigned i) -> unsigned {
+    const unsigned p = raw_p(i);
+    return p < n_ev ? p : 0u;
+  };
+  auto key_t = [&](unsigned i) -> unsigned long long {
+    if (IN_LDS) return s_time[i];
+    const unsigned p = (unsigned)ipos[i];
+    return times && p < n_ev ? (unsigned long long)times[p] ^ HS_SIGN : 0ull;
+  };
+  SelKey common;
+  const SelKey differ = sel_differ<256>(n, key_t, key_p, s_select, common);
+  const SelKey thr = sel_kth_largest<256>(n, cap, key_t, key_p, differ, common, s_select);
+  for (unsigned i = threadIdx.x; i < n; i += 256) {
+    const unsigned p = raw_p(i);
+    if (p >= n_ev) continue;
+    const unsigned long long kt = key_t(i);
+    if (kt < thr.hi || (kt == thr.hi && p < thr.lo)) atomicOr(&bits[p >> 6], 1ull << (p & 63));
+  }
+}
+
+// One block per user of `list`.
+__global__ __launch_bounds__(256) void hc_mark_block_kernel(int64_t n_events, int64_t n_users, const int64_t* __restrict__ idx_row_ptr, const int32_t* __restrict__ idx_pos,
+                                                            const int64_t* __restrict__ times_ms, int32_t cap, unsigned long long* __restrict__ bits,
+                                                            const int32_t* __restrict__ list, const unsigned long long* __restrict__ ctr) {
+  __shared__ unsigned long long s_buf[SR_LDS + SR_LDS / 2];  // SR_LDS times (8 bytes), then SR_LDS raw entries
+  __shared__ SelScratch s_select;
+  unsigned long long* s_time = s_buf;
+  unsigned* s_pos = reinterpret_cast<unsigned*>(s_buf + SR_LDS);
+  const int64_t n_e = ht_entries(idx_row_ptr, n_users, n_events);
+  int64_t n_big = (int64_t)ctr[0];
+  if (n_big > n_users) n_big = n_users;
+  for (int64_t li = blockIdx.x; li < n_big; li += gridDim.x) {  // block-uniform
+    const int u = list[li];
+    if (u < 0 || u >= n_users) continue;
+    const int64_t lo = ht_clamp(idx_row_ptr[u], n_e);
+    const int64_t m = ht_clamp(idx_row_ptr[u + 1], n_e) - lo;
+    if (m <= cap) continue;
+    const bool in_lds = m <= SR_LDS;
+    const int32_t* __restrict__ ipos = idx_pos + lo;
+    if (in_lds)
+      for (int i = threadIdx.x; i < (int)m; i += 256) {
+        const int q = ipos[i];
+        s_pos[i] = (unsigned)q;
+        s_time[i] = times_ms && q >= 0 && q < n_events ? (unsigned long long)times_ms[q] ^ HS_SIGN : 0ull;
+      }
+    __syncthreads();
+    if (in_lds) hc_mark_user<true>(n_events, (unsigned)m, (unsigned)cap, ipos, times_ms, s_time, s_pos, s_select, bits);
+    else hc_mark_user<false>(n_events, (unsigned)m, (unsigned)cap, ipos, times_ms, s_time, s_pos, s_select, bits);
+    __syncthreads();  // the keys and the select's scratch are free for the next user
+  }
+}
+
+// launch_history_trim with the cap's mark in front of the keep: c.list [n_users], c.ctr [1] and the trim's scratch.  max_per_user == INT32_MAX launches what the trim launches.
+hipError_t launch_history_cap(hipStream_t st, int n_cu, const CapArgs& c) {
+  const TrimArgs& a = c.trim;
+  const int64_t n = a.n_events, n_words = (n + 63) >> 6;
+  hipError_t e;
+  if (n > 0) {
+    const bool has_drop = a.n_drop > 0 && a.n_users > 0;
+    const bool has_cap = c.max_per_user != 0x7fffffff && a.n_users > 0;
+    if (has_drop || has_cap) {
+      e = hipMemsetAsync(a.s_bits, 0, sizeof(unsigned long long) * (size_t)n_words, st);
+      if (e != hipSuccess) return e;
+    }
+    if (has_drop) {
+      const int64_t jobs = a.n_drop * HT_SPLIT, cap = (int64_t)n_cu * 8;
+      hipLaunchKernelGGL(ht_mark_kernel, dim3((unsigned)(jobs < cap ? jobs : cap)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.idx_pos, a.n_drop, a.drop_users,
+                         a.s_bits);
+    }
+    if (has_cap) {
+      e = hipMemsetAsync(c.ctr, 0, sizeof(unsigned long long), st);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(hc_mark_wave_kernel, dim3(ig_grid(a.n_users, n_cu)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.idx_pos, a.times_ms, c.max_per_user,
+                         a.s_bits, c.list, c.ctr);
+      const int64_t heavy = n / SR_WAVE + 1;  // users of more than a wave's entries, at most
+      const int64_t most = heavy < a.n_users ? heavy : a.n_users, grid = most < (int64_t)n_cu * 8 ? most : (int64_t)n_cu * 8;
+      hipLaunchKernelGGL(hc_mark_block_kernel, dim3((unsigned)grid), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.idx_pos, a.times_ms, c.max_per_user, a.s_bits,
+                         c.list, c.ctr);
+    }
+    hipLaunchKernelGGL(ht_keep_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, a.times_ms, a.min_time_ms, has_drop || has_cap, a.s_bits, a.s_cnt);
+    hipLaunchKernelGGL(ht_entries_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.idx_pos, a.s_bits, a.i_bits, a.i_cnt);
+  }
+  e = launch_scan_i32(st, a.s_cnt, n_words, a.s_base, a.tile_sums);
+  if (e != hipSuccess) return e;
+  e = launch_scan_i32(st, a.i_cnt, n_words, a.i_base, a.tile_sums);
+  if (e != hipSuccess) return e;
+  if (n > 0) {
+    hipLaunchKernelGGL(ht_compact_stream_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, a.items, a.times_ms, a.s_bits, a.s_base, a.out_items, a.out_times);
+    hipLaunchKernelGGL(ht_compact_index_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.idx_pos, a.s_bits, a.s_base, a.i_bits, a.i_base,
+                       a.out_pos);
+  }
+  hipLaunchKernelGGL(ht_row_ptr_kernel, dim3(ig_grid(a.n_users + 1, n_cu)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.i_bits, a.s_base, a.i_base, a.out_row_ptr,
+                     a.out_counts);
+  return hipGetLastError();
+}
+
 // ---- matrices (decision D23) ---------------------------------------------------------------------------------------
 // The Preparator's output from the index and the item stream alone: which users train (users), and per event type the user x column matrix whose rows are
 // the users' distinct in-window columns, ascending (matrix) -- the arrays launch_csr_from_pairs gives for the pairs (row_of[user], item), without a `users` array.

@@ -443,6 +443,14 @@ struct TrimArgs {
   int64_t* tile_sums;                   // scratch: scan_tile_words(ceil(n_events / 64))
 };
 hipError_t launch_history_trim(hipStream_t st, int n_cu, const TrimArgs& a);
+// the trim with a per-user cap on the stored events (decision D27; include/urcco.h urcco_dev_history_cap)
+struct CapArgs {
+  TrimArgs trim;
+  int32_t max_per_user;          // INT32_MAX: no cap, the launches of launch_history_trim
+  int32_t* list;                 // scratch [n_users]: users above the cap of more than a wave's entries
+  unsigned long long* ctr;       // scratch [1]: their number
+};
+hipError_t launch_history_cap(hipStream_t st, int n_cu, const CapArgs& c);
 // the users that train and their row numbers, one event type's user x column matrix (decision D23; include/urcco.h urcco_dev_history_users / _matrix)
 constexpr int64_t HM_BITMAP_BUDGET = 8ll << 20;  // bytes of arena the column bitmaps of one _matrix launch may take
 constexpr int HM_BITMAP_BLOCKS = 64;             // blocks of the bitmap class at most: one bitmap each
@@ -537,6 +545,29 @@ hipError_t launch_props_bounds(hipStream_t st, int n_cu, const PropRows& a, int3
 hipError_t launch_props_rows(hipStream_t st, int n_cu, const PropRows& a, int64_t* tile_sums, int64_t* row_ptr, int32_t* col_idx);
 hipError_t launch_props_dates(hipStream_t st, int n_cu, int32_t n_items, const PropState& s, const int64_t* date_values, int64_t* out);
 hipError_t launch_props_exists(hipStream_t st, int n_cu, int32_t n_items, const unsigned long long* t_del, const PropSets& sets, uint8_t* mask);
+// one property's stream without the superseded values (decision D28; include/urcco.h urcco_dev_props_compact)
+struct CompactArgs {
+  PropState st;
+  const int64_t* val_ptr;        // nullable: not a list property
+  const int32_t* values;
+  int64_t n_values;
+  const int64_t* date_values;    // nullable: not a date property
+  int32_t n_items;
+  unsigned* out_pos_set;         // [n_items]
+  int32_t* out_old_pos;          // [K]
+  int64_t* out_val_ptr;          // [K + 1]
+  int32_t* out_values;           // [V]
+  int64_t* out_date_values;      // [K]
+  int64_t* out_counts;           // [2]: K, V
+  unsigned long long* bits;      // scratch [ceil(n_events / 64)]: one bit per stream position, "an item's winner"
+  int32_t* cnt;                  // scratch [ceil(n_events / 64)]: the words' popcounts
+  int64_t* base;                 // scratch [ceil(n_events / 64) + 1]: their exclusive scan
+  int32_t* len;                  // scratch [min(n_items, n_events)]: the new positions' slice lengths
+  int64_t* src;                  // scratch [min(n_items, n_events)]: where in `values` their slices start
+  int64_t* val_base;             // scratch [min(n_items, n_events) + 1]: the scan of len
+  int64_t* tile_sums;            // scratch: scan_tile_words(max(ceil(n_events / 64), min(n_items, n_events)))
+};
+hipError_t launch_props_compact(hipStream_t st, int n_cu, const CompactArgs& a);
 
 hipError_t launch_llr_test(hipStream_t st, int64_t n, const int64_t* a, const int64_t* b, const int64_t* ab, const int64_t* nu, double* out);
 hipError_t launch_u01_test(hipStream_t st, int64_t n, uint32_t seed, const int32_t* row, const int32_t* col, double* out, int rng32 = 0);

@@ -241,4 +241,160 @@ hipError_t launch_props_exists(hipStream_t st, int n_cu, int32_t n_items, const 
   return hipGetLastError();
 }
 
+// ---- compaction (decision D28) -------------------------------------------------------------------------------------
+// One property's stream without the values no item's state names any more: the winners -- the positions pos_set[i] - 1 inside the stream, one per item --
+// numbered in ascending old position are the new stream.  Filter-then-compact, as the history's trim:
+//   mark       W: one bit per stream position, zeroed; every item sets the bit of its winner (atomicOr: the only atomics, one per item with a set)
+//   count      cnt[w] = popcount of word w; launch_scan_i32 -> base; rank(p) = ht_rank(base, W, p); K = base[number of words]
+//   items      out_pos_set[i] = rank(winner) + 1, else 0; a list property: len[rank] = the winner's slice length, clamped as pr_window clamps it, when the
+//              property is alive, else 0 (a maximum only grows: a dead winner never lives again), src[rank] = the slice's clamped start
+//   positions  out_old_pos[rank(p)] = p for every set bit; a date property: out_date_values[rank(p)] = date_values[p]
+//   scan       len over the bound min(n_items, n_events) of K (zero beyond K: the array is cleared first) -> the new slice starts, every one
+//              clamped to n_values (only a malformed val_ptr, whose slices overlap, reaches the clamp): V = the last
+//   copy       balanced by ENTRIES, the append's copy kernel over (new slice starts, src): a block takes PC_TILE consecutive entries of out_values,
+//              finds the tile's first and last winner with one binary search each, and every entry then finds its winner among those -- staged in LDS when
+//              the tile touches at most PC_LDS winners (empty slices in between included), in global memory otherwise.  One winner of 8193 values is four
+//              tiles; a million of two values are a thousand winners a tile
+// Two items that name one position set one bit and write the same rank; when one of them is alive and the other is not, which length wins is
+// unspecified -- the result may be wrong, but every length is 0 or the clamped slice's, so no access leaves the arrays.
+constexpr int PC_TILE = 2048;  // entries of out_values per block and round: 8 per thread
+constexpr int PC_LDS = 2048;   // winners of a tile whose slice starts and sources are staged in LDS (8 + 16 KiB)
+static_assert(PC_LDS >= PC_TILE, "a tile of one-value winners must fit the staging");
+
+namespace {
+// the winner of item i whatever the property's life: the position pos_set names, or -1
+__device__ __forceinline__ int64_t pc_winner(const PropState& s, int64_t i) {
+  const int64_t p = (int64_t)s.pos_set[i] - 1;
+  return p >= 0 && p < s.n_events ? p : -1;
+}
+}  // namespace
+
+__global__ __launch_bounds__(256) void pc_mark_kernel(CompactArgs a) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n_items; i += (int64_t)gridDim.x * 256) {
+    const int64_t p = pc_winner(a.st, i);
+    if (p >= 0) atomicOr(&a.bits[p >> 6], 1ull << (p & 63));
+  }
+}
+
+__global__ __launch_bounds__(256) void pc_count_kernel(CompactArgs a) {
+  const int64_t n_words = (a.st.n_events + 63) >> 6;
+  for (int64_t w = (int64_t)blockIdx.x * 256 + threadIdx.x; w < n_words; w += (int64_t)gridDim.x * 256) a.cnt[w] = __popcll(a.bits[w]);
+}
+
+__global__ __launch_bounds__(256) void pc_items_kernel(CompactArgs a) {
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < a.n_items; i += (int64_t)gridDim.x * 256) {
+    const int64_t p = pc_winner(a.st, i);
+    if (p < 0) {
+      a.out_pos_set[i] = 0u;
+      continue;
+    }
+    const int64_t j = ht_rank(a.base, a.bits, p);
+    a.out_pos_set[i] = (unsigned)j + 1u;
+    if (!a.val_ptr) continue;
+    int64_t lo = a.val_ptr[p], hi = a.val_ptr[p + 1];
+    if (lo < 0) lo = 0;
+    if (hi > a.n_values) hi = a.n_values;
+    if (hi < lo) hi = lo;
+    a.len[j] = pr_alive(a.st, (int)i) ? (hi - lo > 0x7fffffffll ? 0x7fffffff : (int32_t)(hi - lo)) : 0;
+    a.src[j] = lo;
+  }
+}
+
+__global__ __launch_bounds__(256) void pc_positions_kernel(CompactArgs a) {
+  for (int64_t p = (int64_t)blockIdx.x * 256 + threadIdx.x; p < a.st.n_events; p += (int64_t)gridDim.x * 256) {
+    const unsigned long long word = a.bits[p >> 6];
+    const int b = (int)(p & 63);
+    if (!((word >> b) & 1ull)) continue;
+    const int64_t j = a.base[p >> 6] + __popcll(word & ((1ull << b) - 1ull));
+    a.out_old_pos[j] = (int32_t)p;
+    if (a.date_values) a.out_date_values[j] = a.date_values[p];
+  }
+}
+
+// out_val_ptr[0 .. K] = the scan of the lengths, clamped to n_values; the first thread writes the counts
+__global__ __launch_bounds__(256) void pc_finish_kernel(CompactArgs a) {
+  const int64_t k = a.base[(a.st.n_events + 63) >> 6];
+  if (a.val_ptr)
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j <= k; j += (int64_t)gridDim.x * 256) {
+      const int64_t v = a.val_base[j];
+      a.out_val_ptr[j] = v < a.n_values ? v : a.n_values;
+    }
+  if (blockIdx.x == 0 && threadIdx.x == 0) {
+    a.out_counts[0] = k;
+    const int64_t v = a.val_ptr ? a.val_base[k] : 0;
+    a.out_counts[1] = v < a.n_values ? v : a.n_values;
+  }
+}
+
+// out_values[e] = values[src[j(e)] + e - out_val_ptr[j(e)]] for every entry e below V = out_val_ptr[K]: K and V are read here, the host knows only the bound n_values
+__global__ __launch_bounds__(256) void pc_copy_kernel(CompactArgs a) {
+  __shared__ int s_start[PC_LDS];      // slice starts relative to the tile's first entry; [0] = 0: the first winner's slice may begin before the tile
+  __shared__ int64_t s_delta[PC_LDS];  // source index minus destination index of the winner's slice
+  __shared__ int64_t s_j[2];
+  const int64_t* __restrict__ vp = a.out_val_ptr;
+  const int64_t k = a.base[(a.st.n_events + 63) >> 6];
+  const int64_t n_v = vp[k];
+  for (int64_t e0 = (int64_t)blockIdx.x * PC_TILE; e0 < n_v; e0 += (int64_t)gridDim.x * PC_TILE) {  // block-uniform
+    const int n = (int)(n_v - e0 < PC_TILE ? n_v - e0 : PC_TILE);
+    if (threadIdx.x < 2) s_j[threadIdx.x] = ha_user_of(vp, 0, k, threadIdx.x == 0 ? e0 : e0 + n - 1);
+    __syncthreads();
+    const int64_t j_lo = s_j[0], j_hi = s_j[1];
+    const int64_t span = j_hi - j_lo + 1;
+    if (span >= 1 && span <= PC_LDS) {  // block-uniform
+      for (int i = threadIdx.x; i < (int)span; i += 256) {
+        const int64_t r = vp[j_lo + i] - e0;
+        s_start[i] = r < 0 ? 0 : (int)r;
+        s_delta[i] = a.src[j_lo + i] - vp[j_lo + i];
+      }
+      __syncthreads();
+      for (int t = threadIdx.x; t < n; t += 256) {
+        int lo = 0, hi = (int)span;
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (s_start[mid] <= t) lo = mid;
+          else hi = mid;
+        }
+        a.out_values[e0 + t] = a.values[e0 + t + s_delta[lo]];
+      }
+    } else {
+      for (int t = threadIdx.x; t < n; t += 256) {
+        const int64_t j = ha_user_of(vp, j_lo, j_hi + 1, e0 + t);
+        a.out_values[e0 + t] = a.values[e0 + t + a.src[j] - vp[j]];
+      }
+    }
+    __syncthreads();  // s_j and the staged slice are free for the next tile
+  }
+}
+
+// a.bits, cnt, base, len, src, val_base, tile_sums: scratch.  Outputs must not overlap inputs.
+hipError_t launch_props_compact(hipStream_t st, int n_cu, const CompactArgs& a) {
+  const int64_t n = a.st.n_events, n_words = (n + 63) >> 6;
+  const int64_t k_max = a.n_items < n ? a.n_items : n;
+  hipError_t e;
+  if (n_words > 0) {
+    e = hipMemsetAsync(a.bits, 0, sizeof(unsigned long long) * (size_t)n_words, st);
+    if (e != hipSuccess) return e;
+    if (a.n_items > 0) hipLaunchKernelGGL(pc_mark_kernel, dim3(ig_grid(a.n_items, n_cu)), dim3(256), 0, st, a);
+    hipLaunchKernelGGL(pc_count_kernel, dim3(ig_grid(n_words, n_cu)), dim3(256), 0, st, a);
+  }
+  e = launch_scan_i32(st, a.cnt, n_words, a.base, a.tile_sums);
+  if (e != hipSuccess) return e;
+  if (a.val_ptr && k_max > 0) {
+    e = hipMemsetAsync(a.len, 0, sizeof(int32_t) * (size_t)k_max, st);
+    if (e != hipSuccess) return e;
+  }
+  if (a.n_items > 0) hipLaunchKernelGGL(pc_items_kernel, dim3(ig_grid(a.n_items, n_cu)), dim3(256), 0, st, a);
+  if (n > 0) hipLaunchKernelGGL(pc_positions_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, a);
+  if (a.val_ptr) {
+    e = launch_scan_i32(st, a.len, k_max, a.val_base, a.tile_sums);
+    if (e != hipSuccess) return e;
+  }
+  hipLaunchKernelGGL(pc_finish_kernel, dim3(ig_grid(k_max + 1, n_cu)), dim3(256), 0, st, a);
+  if (a.val_ptr && a.n_values > 0 && k_max > 0) {
+    const int64_t tiles = (a.n_values + PC_TILE - 1) / PC_TILE, cap = (int64_t)n_cu * 8;
+    hipLaunchKernelGGL(pc_copy_kernel, dim3((unsigned)(tiles < cap ? tiles : cap)), dim3(256), 0, st, a);
+  }
+  return hipGetLastError();
+}
+
 }  // namespace urcco

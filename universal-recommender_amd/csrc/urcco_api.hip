@@ -854,6 +854,28 @@ int urcco_dev_history_trim(urcco_session* s, int64_t n_events, const int32_t* it
   return URCCO_OK;
 }
 
+int urcco_dev_history_cap(urcco_session* s, int64_t n_events, const int32_t* items, const int64_t* times_ms, int64_t n_users, const int64_t* idx_row_ptr,
+                          const int32_t* idx_pos, int64_t min_time_ms, int64_t n_drop, const int32_t* drop_users, int32_t max_per_user, int32_t* out_items,
+                          int64_t* out_times, int64_t* out_row_ptr, int32_t* out_pos, int64_t* out_counts) {
+  if (!s || n_events < 0 || n_events > 0x7fffffffll || n_users < 0 || n_users > 0x7ffffff0ll || n_drop < 0)
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_cap: bad argument (a stream holds fewer than 2^31 events)");
+  if (max_per_user < 1) return fail(URCCO_BAD_ARG, "urcco_dev_history_cap: max_per_user must be >= 1, got %d", max_per_user);
+  if (!out_row_ptr || !out_counts || (n_events > 0 && (!items || !idx_pos || !out_items || !out_pos)) || (n_users > 0 && !idx_row_ptr) || (n_drop > 0 && !drop_users))
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_cap: NULL argument");
+  if ((times_ms == nullptr) != (out_times == nullptr)) return fail(URCCO_BAD_ARG, "urcco_dev_history_cap: times_ms and out_times are both NULL or both given");
+  urcco::CapArgs c{};
+  urcco::TrimArgs& a = c.trim;
+  c.max_per_user = max_per_user;
+  a.n_events = n_events; a.n_users = n_users; a.n_drop = n_drop; a.min_time_ms = min_time_ms;
+  a.items = items; a.times_ms = times_ms; a.idx_row_ptr = idx_row_ptr; a.idx_pos = idx_pos; a.drop_users = drop_users;
+  a.out_items = out_items; a.out_times = out_times; a.out_row_ptr = out_row_ptr; a.out_pos = out_pos; a.out_counts = out_counts;
+  const size_t n_words = (size_t)((n_events + 63) >> 6);
+  URC(ArenaLayout(s).add(&a.s_bits, n_words).add(&a.i_bits, n_words).add(&a.s_cnt, n_words).add(&a.i_cnt, n_words).add(&a.s_base, n_words + 1).add(&a.i_base, n_words + 1)
+          .add(&a.tile_sums, scan_tile_words((int64_t)n_words)).add(&c.list, (size_t)n_users).add(&c.ctr, 1).commit());
+  HIPC(urcco::launch_history_cap(s->stream, s->n_cu, c));
+  return URCCO_OK;
+}
+
 // the window of urcco_dev_history_users / _matrix: without times only the open one
 static bool history_window_ok(const int64_t* times_ms, int64_t t_lo, int64_t t_hi) { return times_ms || (t_lo == INT64_MIN && t_hi == INT64_MAX); }
 
@@ -1132,6 +1154,28 @@ int urcco_dev_props_exists(urcco_session* s, int32_t n_items, const uint64_t* t_
     sets.t_set[p] = reinterpret_cast<const unsigned long long*>(t_sets[p]);
   }
   HIPC(urcco::launch_props_exists(s->stream, s->n_cu, n_items, reinterpret_cast<const unsigned long long*>(t_del), sets, out_mask));
+  return URCCO_OK;
+}
+
+int urcco_dev_props_compact(urcco_session* s, int32_t n_items, const urcco_prop_state* state, const int64_t* val_ptr, const int32_t* values, int64_t n_values,
+                            const int64_t* date_values, uint32_t* out_pos_set, int32_t* out_old_pos, int64_t* out_val_ptr, int32_t* out_values,
+                            int64_t* out_date_values, int64_t* out_counts) {
+  urcco::CompactArgs a{};
+  URC(props_state("urcco_dev_props_compact", s, n_items, state, &a.st));
+  if (n_values < 0 || !out_counts) return fail(URCCO_BAD_ARG, "urcco_dev_props_compact: bad argument");
+  if (val_ptr && date_values) return fail(URCCO_BAD_ARG, "urcco_dev_props_compact: a property holds lists (val_ptr) or dates (date_values), not both");
+  const bool any = n_items > 0 && state->n_events > 0;  // a winner may exist
+  if ((n_items > 0 && !out_pos_set) || (any && !out_old_pos) || (val_ptr && !out_val_ptr) || (val_ptr && any && n_values > 0 && (!values || !out_values)) ||
+      (date_values && any && !out_date_values))
+    return fail(URCCO_BAD_ARG, "urcco_dev_props_compact: NULL argument");
+  a.val_ptr = val_ptr; a.values = values; a.n_values = val_ptr ? n_values : 0; a.date_values = date_values; a.n_items = n_items;
+  a.out_pos_set = out_pos_set; a.out_old_pos = out_old_pos; a.out_val_ptr = out_val_ptr; a.out_values = out_values; a.out_date_values = out_date_values;
+  a.out_counts = out_counts;
+  const size_t n_words = (size_t)((state->n_events + 63) >> 6);
+  const size_t k_max = (size_t)((int64_t)n_items < state->n_events ? (int64_t)n_items : state->n_events);
+  URC(ArenaLayout(s).add(&a.bits, n_words).add(&a.cnt, n_words).add(&a.base, n_words + 1).add(&a.len, k_max).add(&a.src, k_max).add(&a.val_base, k_max + 1)
+          .add(&a.tile_sums, scan_tile_words((int64_t)(n_words > k_max ? n_words : k_max))).commit());
+  HIPC(urcco::launch_props_compact(s->stream, s->n_cu, a));
   return URCCO_OK;
 }
 

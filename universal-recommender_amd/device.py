@@ -351,6 +351,28 @@ class DeviceSession:
                                                     _ptr(drop_users) if n_drop else None, _ptr(o_items), _ptr(o_times), _ptr(o_rp), _ptr(o_pos), _ptr(counts)))
         return o_items, o_times, o_rp, o_pos, counts
 
+    def history_cap(self, n_events: int, items: torch.Tensor, times: Optional[torch.Tensor], idx_row_ptr: torch.Tensor, idx_pos: torch.Tensor,
+                    max_per_user: Optional[int], min_time_ms: Optional[int] = None, drop_users: Optional[torch.Tensor] = None, out=None):
+        """urcco_dev_history_cap (decision D27): history_trim with one more rule -- of every user only the max_per_user most recent events stay, by
+        the rows' recency key (time, stream position); None: no cap, the outputs are history_trim's.  The three rules are independent and decided on
+        the stream as passed in.  Arguments, result and `out` as in history_trim.  Does not synchronise."""
+        n, n_users = int(n_events), int(idx_row_ptr.numel()) - 1
+        n_drop = int(drop_users.numel()) if drop_users is not None else 0
+        if out is None:
+            out = (self.empty(max(n, 1), torch.int32), self.empty(max(n, 1), torch.int64) if times is not None else None, self.empty(n_users + 1, torch.int64),
+                   self.empty(max(n, 1), torch.int32))
+        o_items, o_times, o_rp, o_pos = out
+        if o_items.numel() < n or o_pos.numel() < n or o_rp.numel() < n_users + 1 or (o_times is not None and o_times.numel() < n):
+            raise ValueError("history_cap: the output tensors are smaller than n_events / n_users + 1")
+        cap = (1 << 31) - 1 if max_per_user is None else int(max_per_user)
+        if cap < 1 or cap > (1 << 31) - 1:
+            raise ValueError(f"history_cap: max_per_user must be in 1 .. 2^31 - 1, got {max_per_user}")
+        counts = self.empty(2, torch.int64)
+        self._check(self.lib.urcco_dev_history_cap(self.handle, n, _ptr(items), _ptr(times), n_users, _ptr(idx_row_ptr), _ptr(idx_pos),
+                                                   int(min_time_ms) if min_time_ms is not None and times is not None else -(1 << 63), n_drop,
+                                                   _ptr(drop_users) if n_drop else None, cap, _ptr(o_items), _ptr(o_times), _ptr(o_rp), _ptr(o_pos), _ptr(counts)))
+        return o_items, o_times, o_rp, o_pos, counts
+
     @staticmethod
     def _window(after_ms: Optional[int], before_ms: Optional[int]):
         return (-(1 << 63) if after_ms is None else int(after_ms), (1 << 63) - 1 if before_ms is None else int(before_ms))
@@ -507,6 +529,34 @@ class DeviceSession:
         out = self.empty(max(int(n_items), 1), torch.uint8)
         self._check(self.lib.urcco_dev_props_exists(self.handle, int(n_items), _ptr(t_del), ptrs, len(t_sets), _ptr(out)))
         return out[: int(n_items)]
+
+    def props_compact(self, n_items: int, state, val_ptr: Optional[torch.Tensor] = None, values: Optional[torch.Tensor] = None, n_values: int = 0,
+                      date_values: Optional[torch.Tensor] = None, out=None):
+        """urcco_dev_props_compact (decision D28): one property's stream without the values no item's state names any more.  state as in props_rows; a
+        list property gives val_ptr / values / n_values, a date property date_values.  Returns (pos_set int32 [n_items], old_pos int32, val_ptr int64 |
+        None, values int32 | None, date_values int64 | None, counts int64 [2] = [K, V] on the device): the first K (old_pos, date_values), K + 1
+        (val_ptr) and V (values) entries are the result.  out: (val_ptr, values, date_values) tensors to write into, sized by the bounds
+        min(n_items, n_events) + 1, n_values and min(n_items, n_events); they must not share memory with the inputs.  Does not synchronise."""
+        n_items, n_events, n_values = int(n_items), int(state[4]), int(n_values)
+        k_max = min(n_items, n_events)
+        st = self._prop_state(state)
+        o_vp, o_vals, o_dates = out if out is not None else (None, None, None)
+        if val_ptr is not None:
+            o_vp = o_vp if o_vp is not None else self.empty(k_max + 1, torch.int64)
+            o_vals = o_vals if o_vals is not None else self.empty(max(n_values, 1), torch.int32)
+            if o_vp.numel() < k_max + 1 or o_vals.numel() < n_values:
+                raise ValueError("props_compact: the output tensors are smaller than min(n_items, n_events) + 1 / n_values")
+        if date_values is not None:
+            o_dates = o_dates if o_dates is not None else self.empty(max(k_max, 1), torch.int64)
+            if o_dates.numel() < k_max:
+                raise ValueError("props_compact: the output tensor is smaller than min(n_items, n_events)")
+        pos_set = self.empty(max(n_items, 1), torch.int32)
+        old_pos = self.empty(max(k_max, 1), torch.int32)
+        counts = self.empty(2, torch.int64)
+        self._check(self.lib.urcco_dev_props_compact(self.handle, n_items, C.byref(st), _ptr(val_ptr), _ptr(values) if val_ptr is not None else None, n_values,
+                                                     _ptr(date_values), _ptr(pos_set), _ptr(old_pos), _ptr(o_vp) if val_ptr is not None else None,
+                                                     _ptr(o_vals) if val_ptr is not None else None, _ptr(o_dates) if date_values is not None else None, _ptr(counts)))
+        return pos_set, old_pos, o_vp if val_ptr is not None else None, o_vals if val_ptr is not None else None, o_dates if date_values is not None else None, counts
 
     def _bounded_rows(self, arr, n_types, nq, rps, stats, timing, keep_bounds, bounds, rows):
         """The two-call protocol of history_rows and item_rows.  bounds() leaves in every row_ptr of `rps` the scan of its rows' upper bounds; their

@@ -266,7 +266,7 @@ class DeviceHistory:
             self.user_ids = user_ids
         return self
 
-    def trim(self, before_ms: Optional[int] = None, drop_users=None, events: Optional[List[str]] = None) -> "DeviceHistory":
+    def trim(self, before_ms: Optional[int] = None, drop_users=None, events: Optional[List[str]] = None, max_events_per_user=None) -> "DeviceHistory":
         """Retention, in place (decision D22 of DESIGN.md; include/urcco.h urcco_dev_history_trim); returns self.  before_ms: the events with time <
         before_ms leave the event types named in `events` (default: every type that has times) -- the reference's eventWindow.  drop_users: an
         iterable of user keys (resolved through user_indices, once per call; unknown ones ignored) or an int32 tensor of dense ids; their events leave EVERY event type,
@@ -274,12 +274,20 @@ class DeviceHistory:
         is answered like a user without events.  Every result afterwards is the one of from_streams over the filtered whole streams with the same
         n_users; `append` works on as before.
 
-        A type for which neither rule applies costs no call.  One device-to-host read, of the counts of all types together.  The outputs of the
+        max_events_per_user (decision D27; urcco_dev_history_cap): None -- no cap, the call and the cost of before; an int -- of every user only that
+        many most recent events (by time, then stream position; by position alone in a stream without times) stay in every type named in `events`
+        (default: every type, with or without times); a dict {event: int} names the capped types itself, whatever `events` says.  The cap is decided on the
+        stream as it is, independently of the other two rules.  Two consequences.  Exclusion rows read EVERY event of a blacklist type, not a window of
+        them: a cap on a blacklist type shortens the blacklist -- the dict form exists so that a caller can leave such types out.  And
+        `matrices` / train_from_history see only what is stored: a capped history trains on the capped events.  Term rows with max_items <= the cap
+        are unchanged by it.
+
+        A type for which no rule applies costs no call.  One device-to-host read, of the counts of all types together.  The outputs of the
         call become the stream's buffers, with the capacity the old ones had: their tail is the spare capacity the next append fills.  The index
         pair of before becomes the spare pair.  `last_trim` = {event: (events before, events after)} of the types that were trimmed.
 
-        ValueError -- nothing is modified: `events` names a type the history does not hold, or, with before_ms, one without times; drop_users is a
-        tensor of another dtype; a _Stream built by hand without n_events."""
+        ValueError -- nothing is modified: `events` or the cap's dict names a type the history does not hold, or, with before_ms, `events` one without
+        times; a cap below 1 or above 2^31 - 1; drop_users is a tensor of another dtype; a _Stream built by hand without n_events."""
         named = list(self.types) if events is None else list(events)
         for ev in named:
             if ev not in self.types:
@@ -287,6 +295,16 @@ class DeviceHistory:
             if before_ms is not None and events is not None and self.types[ev].times is None:
                 raise ValueError(f"trim: the stream {ev!r} has no times, before_ms cannot apply to it")
         by_time = {ev for ev in named if self.types[ev].times is not None} if before_ms is not None else set()
+        caps: Dict[str, int] = {}
+        if isinstance(max_events_per_user, dict):
+            caps = {ev: int(c) for ev, c in max_events_per_user.items()}
+        elif max_events_per_user is not None:
+            caps = {ev: int(max_events_per_user) for ev in named}
+        for ev, c in caps.items():
+            if ev not in self.types:
+                raise ValueError(f"trim: the history holds no event type {ev!r}")
+            if c < 1 or c > (1 << 31) - 1:
+                raise ValueError(f"trim: max_events_per_user must be in 1 .. 2^31 - 1, got {c} for {ev!r}")
         sess = self.sess
         drop = None
         if isinstance(drop_users, torch.Tensor):
@@ -296,7 +314,7 @@ class DeviceHistory:
         elif drop_users is not None:
             ids = [i for i in self.user_indices(drop_users) if i >= 0]
             drop = torch.tensor(ids, dtype=torch.int32).to(sess.device) if ids else None
-        todo = [ev for ev in self.types if ev in by_time or drop is not None]
+        todo = [ev for ev in self.types if ev in by_time or drop is not None or ev in caps]
         for ev in todo:
             if self.types[ev].n_events < 0:
                 raise ValueError(f"stream {ev!r}: built without its number of events (_Stream.n_events)")
@@ -312,7 +330,11 @@ class DeviceHistory:
                 spare = (sess.empty(max(live[0].numel(), self.n_users + 1), torch.int64), sess.empty(max(live[1].numel(), n), torch.int32))
             out = (sess.empty((st.items_buf if st.items_buf is not None else st.items).numel(), torch.int32),
                    sess.empty((st.times_buf if st.times_buf is not None else st.times).numel(), torch.int64) if st.times is not None else None, spare[0], spare[1])
-            calls.append((ev, out, sess.history_trim(n, st.items, st.times, st.idx_row_ptr, st.idx_pos, before_ms if ev in by_time else None, drop, out)[4]))
+            cut = before_ms if ev in by_time else None
+            if ev in caps:
+                calls.append((ev, out, sess.history_cap(n, st.items, st.times, st.idx_row_ptr, st.idx_pos, caps[ev], cut, drop, out)[4]))
+            else:
+                calls.append((ev, out, sess.history_trim(n, st.items, st.times, st.idx_row_ptr, st.idx_pos, cut, drop, out)[4]))
         counts = torch.stack([c for _, _, c in calls]).cpu().tolist() if calls else []
         self.last_trim = {ev: (0, 0) for ev in todo}
         for (ev, (o_items, o_times, o_rp, o_pos), _), (k, _) in zip(calls, counts):

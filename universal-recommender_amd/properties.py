@@ -11,8 +11,8 @@ latest $unset of the key and the latest $delete of the item, a tie going to the 
 it has a $delete that no $set of any of its keys is later than.  The rule does not depend on the order or the batching of the events.
 
 Served: list-of-strings properties (rule matrices) and the properties in `date_names` (ISO-8601 strings through URModel.extractJvalue, as
-`_device_properties` parses them).  Not served: compaction of superseded values out of the value streams (a stream only grows), merging list values
-across sets, properties of any other type (ignored, as `_device_properties` ignores them), items outside the primary's dictionary (ignored), the JVM
+`_device_properties` parses them); `compact` takes the superseded values out of the value streams (decision D28), when the caller says so.  Not
+served: merging list values across sets, properties of any other type (ignored, as `_device_properties` ignores them), items outside the primary's dictionary (ignored), the JVM
 seam, the multi-GPU build."""
 from __future__ import annotations
 
@@ -55,6 +55,7 @@ class DeviceProperties:
         self.n_items = int(model.n_items)
         self.streams: Dict[str, _PropStream] = {}
         self.t_del = self._zeros(self.n_items, torch.int64)
+        self.last_compact: Dict[str, Tuple[int, int, int, int]] = {}   # `compact`: name -> (events before, after, values before, after) of the last call
 
     # ---- buffers ----
     def _zeros(self, n: int, dtype) -> torch.Tensor:
@@ -246,6 +247,52 @@ class DeviceProperties:
             else:
                 dates[name] = sess.props_dates(n, self._state(s), s.date_vals)
         return props, dates
+
+    def compact(self, names: Optional[Sequence[str]] = None) -> "DeviceProperties":
+        """The streams of the properties `names` (default: all) without the events no item's state names any more (decision D28 of DESIGN.md;
+        include/urcco.h urcco_dev_props_compact); returns self.  Of every item the winning $set's position stays -- with an empty value slice where the
+        property is not alive: a maximum only grows, it cannot live again -- and the positions keep their order, so `apply`, `apply_streams`,
+        `materialise`, `item_mask` and `grow` work on as before and give, bit for bit, what they would have given without the call.  The outputs become the
+        buffers, with the capacity the old ones had: their tail is the spare capacity the next `apply` fills.  One device-to-host read, of the counts
+        of all properties together.  `last_compact` = {name: (events before, events after, values before, values after)}.  No automatic trigger: the
+        caller decides when, as with DeviceHistory.trim.  ValueError -- nothing is modified: a name the store does not hold."""
+        todo = list(self.streams) if names is None else list(names)
+        for name in todo:
+            if name not in self.streams:
+                raise ValueError(f"compact: the store holds no property {name!r}")
+        sess = self.sess
+        calls = []
+        for name in todo:      # every call first, then the one read of the counts; the store changes only after both
+            s = self.streams[name]
+            if s.n_events == 0:
+                continue
+            if s.is_date:
+                out = (None, None, sess.empty(s.date_vals.numel(), torch.int64))
+                r = sess.props_compact(self.n_items, self._state(s), date_values=s.date_vals, out=out)
+            else:
+                vals = s.vals if s.vals is not None else sess.empty(1, torch.int32)
+                out = (sess.empty(s.val_ptr.numel(), torch.int64), sess.empty(vals.numel(), torch.int32), None)
+                r = sess.props_compact(self.n_items, self._state(s), s.val_ptr, vals, s.n_values, out=out)
+            calls.append((s, r))
+        counts = torch.stack([r[5] for _, r in calls]).cpu().tolist() if calls else []
+        self.last_compact = {name: (self.streams[name].n_events, self.streams[name].n_events, self.streams[name].n_values, self.streams[name].n_values) for name in todo}
+        for (s, (pos_set, old_pos, o_vp, o_vals, o_dates, _)), (k, v) in zip(calls, counts):
+            k, v = int(k), int(v)
+            self.last_compact[s.name] = (s.n_events, k, s.n_values, v)
+            order = old_pos[:k].long()
+            for attr in ("items", "times", "kinds"):      # the streams' own arrays follow the positions: n_events stays the length of every one
+                buf = getattr(s, attr)
+                new = sess.empty(buf.numel(), buf.dtype)
+                if k:
+                    new[:k].copy_(buf[order])
+                setattr(s, attr, new)
+            s.pos_set = pos_set
+            if s.is_date:
+                s.date_vals = o_dates
+            else:
+                s.val_ptr, s.vals = o_vp, o_vals
+            s.n_events, s.n_values = k, v
+        return self
 
     def item_mask(self) -> torch.Tensor:
         """uint8 [n_items] on the device: 0 where the item is deleted, else 1 -- the item_mask of batch_predict.  Does not synchronise."""
