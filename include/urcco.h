@@ -658,6 +658,27 @@ int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double
  *   malformed index   entries outside 0 .. n_events take no part in the ranking and drop nothing; duplicated positions may give a wrong result; no
  *                     access leaves the arrays
  *   URCCO_BAD_ARG: max_per_user < 1, and the trim's refusals.
+ * urcco_dev_history_dedup (DESIGN.md decision D29): urcco_dev_history_trim with one event per user and item -- the event store's removeDuplicates.  The
+ *   arguments are the trim's plus n_cols and keep; every rule, output, capacity and malformed-index guarantee of the trim holds unchanged, and one rule
+ *   is added:
+ *   candidates        the valid index entries of user u (its segment, row starts clamped as the trim clamps them, 0 <= idx_pos[e] < n_events) whose
+ *                     event p survives the time rule (times_ms == NULL or times_ms[p] >= min_time_ms) and carries a column: 0 <= items[p] < n_cols
+ *   dropped as a duplicate   among the candidates of one user that carry the same item exactly one stays: the one with the largest recency key
+ *                     (times_ms[p] ^ sign bit, p) compared as unsigned -- p alone when times_ms == NULL -- for URCCO_DEDUP_LAST, the smallest for
+ *                     URCCO_DEDUP_FIRST.  Keys are unique, so the result does not depend on the order inside a segment and is reproducible bit for bit.
+ *                     FIRST is what the reference's event store keeps (the earliest event of a group); LAST keeps the recency order of the query
+ *                     window intact.  Neither is a default: keep must be given
+ *   no column         an event with items[p] < 0 or >= n_cols is a duplicate of nothing and is left alone by this rule
+ *   kept events       an event is kept iff it passes the time rule, is not a listed user's and is not dropped as a duplicate.  Duplicates are decided
+ *                     among the survivors of the time rule, so one call with all three rules gives what urcco_dev_history_trim with the same cut and
+ *                     users followed by a call with this rule alone gives, for both keep values; a second call changes nothing
+ *   classes           by the entries m of the user's segment, chosen on the device: m <= 1 nothing; m <= 64 one wave comparing items and keys across
+ *                     lanes; m <= 2048 one block with a hash table of 4096 slots in LDS keyed by item; larger one block with a table over the n_cols
+ *                     columns in arena scratch (12 bytes per column, 4 without times), restored to zero by a walk over the user's entries.  The tables
+ *                     of one call take at most 64 MiB (64 blocks at most; one block when a single table is larger than that).  No sort
+ *   malformed index   entries outside 0 .. n_events are no candidates and drop nothing; a position named twice in one segment may give a wrong result;
+ *                     no access leaves the arrays
+ *   URCCO_BAD_ARG: n_cols < 1, keep outside {URCCO_DEDUP_FIRST, URCCO_DEDUP_LAST}, and the trim's refusals.
  * urcco_dev_history_users /urcco_dev_history_matrix (DESIGN.md decision D23): the Preparator's output -- which users train, and one event type's user x
  *   column matrix with sorted, duplicate-free rows -- from the stream and the index alone; no `users` array exists after an append or a trim.
  *   window            the event at stream position p is in the window when times_ms == NULL, or when t_lo <= times_ms[p] and (t_hi == INT64_MAX or
@@ -693,7 +714,7 @@ int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double
  * stats_dev (nullable, int64[URCCO_HIST_STATS_LEN]): (query, type) pairs served by [0] the wave class (<= 64 events), [1] the block class (<= 4096, keys in
  *   LDS), [2] the global class; [3] pairs that ran the select (n_u > max_items); exclusion rows built by [4] one wave, [5] one block; [6] rows dropped
  *   for lack of capacity (0 when the caller sized its buffers by the bounds); [7] 0.
- * All eight enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: n_events >= 2^31, n_types outside
+ * All nine enqueue on the session's stream and do not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: n_events >= 2^31, n_types outside
  * 1..URCCO_REC_MAX_CLAUSES, max_items < 1, n_queries * (n_types + 1) >= 2^31, a NULL the call needs, a half-NULL extra pair, a negative capacity.
  * ABI: additions within ABI 305 -- the presence of the symbols is the feature test. */
 #define URCCO_HIST_STATS_LEN 8
@@ -722,6 +743,18 @@ int urcco_dev_history_cap(urcco_session* s,
                           int32_t* out_items, int64_t* out_times /* NULL iff times_ms NULL */,
                           int64_t* out_row_ptr /* [n_users + 1] */, int32_t* out_pos,
                           int64_t* out_counts /* device [2] */);
+#define URCCO_DEDUP_FIRST 1
+#define URCCO_DEDUP_LAST 2
+int urcco_dev_history_dedup(urcco_session* s,
+                            int64_t n_events, const int32_t* items, const int64_t* times_ms /* nullable */,
+                            int64_t n_users, const int64_t* idx_row_ptr /* [n_users + 1] */, const int32_t* idx_pos,
+                            int64_t min_time_ms,                          /* read only when times_ms != NULL */
+                            int64_t n_drop, const int32_t* drop_users,    /* device; nullable iff n_drop == 0 */
+                            int32_t n_cols,                               /* >= 1: the stream's columns */
+                            int32_t keep,                                 /* URCCO_DEDUP_FIRST or URCCO_DEDUP_LAST */
+                            int32_t* out_items, int64_t* out_times /* NULL iff times_ms NULL */,
+                            int64_t* out_row_ptr /* [n_users + 1] */, int32_t* out_pos,
+                            int64_t* out_counts /* device [2] */);
 /* which users train, and under which row number */
 int urcco_dev_history_users(urcco_session* s, int64_t n_events, const int64_t* times_ms /* nullable */,
                             int64_t n_users, const int64_t* idx_row_ptr /* [n_users + 1] */, const int32_t* idx_pos,

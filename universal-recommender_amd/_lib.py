@@ -42,6 +42,8 @@ RANK_MAX_STREAMS = 16
 RANK_MAX_FIELDS = 4    # urcco_dev_fill_order: rank fields per call
 PROP_SET, PROP_UNSET = 0, 1   # urcco_dev_props_apply (URCCO_PROP_*): the kind of a property event
 PROP_MAX = 16          # urcco_dev_props_exists: properties per call
+DEDUP_FIRST, DEDUP_LAST = 1, 2   # urcco_dev_history_dedup (URCCO_DEDUP_*): which event of a (user, item) group stays
+HD_LDS = 2048          # entries of a user up to which the dedup's LDS class serves it (csrc/cco_kernels.h); the column-table class begins above
 HIST_STATS_LEN = 8    # urcco_dev_history_rows (URCCO_HIST_STATS_LEN): pairs per class, selects, exclusion rows per class, overflows
 REC_LDS_LIMIT = 3072   # work bound w(q) up to which a query runs in the LDS class (csrc/cco_kernels.h)
 EXCH_SIZES = 4   # int64 words of a shard's record (include/urcco.h URCCO_EXCH_SIZES)
@@ -238,6 +240,7 @@ SYMBOLS = {
     "urcco_dev_history_append": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_trim": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p]),
     "urcco_dev_history_cap": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, C.c_int32, _p, _p, _p, _p, _p]),
+    "urcco_dev_history_dedup": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, C.c_int32, C.c_int32, _p, _p, _p, _p, _p]),
     "urcco_dev_history_users": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, C.c_int32, _p, _p]),
     "urcco_dev_history_matrix": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, C.c_int32, _p, C.c_int64, _p, _p, C.c_int64, _p]),
     "urcco_dev_history_ranks": (C.c_int, [_p, C.POINTER(RankStream), C.c_int32, C.c_int32, C.c_int32, C.c_int64, C.c_int64, _p, _p]),

@@ -498,6 +498,297 @@ hipError_t launch_history_cap(hipStream_t st, int n_cu, const CapArgs& c) {
   return hipGetLastError();
 }
 
+// ---- dedup (decision D29) ------------------------------------------------------------------------------------------
+// The trim with one more rule: of the events of one user that carry the same item only one stays, the most recent (DEDUP_LAST) or the earliest
+// (DEDUP_FIRST) by the rows' recency key.  As the cap, the rule only marks what it drops into the bitmap D in front of the trim's unchanged sequence.
+// A candidate is a valid entry (a position inside the stream) whose event passes the time rule and whose item lies in 0 .. n_cols; every other entry
+// is left alone.  The key is turned so that LARGER IS BETTER for both rules -- (t, p + 1) for LAST, (~t, ~p) for FIRST, t = time ^ sign (0 without
+// times) -- and its position half is never 0, the value of an empty table word.  Positions are unique inside a user's segment, so "my position half is
+// the largest among the entries of my item that carry the largest time half" names exactly one entry.  Three classes by the entries m of the clamped
+// segment, chosen on the device:
+//   m <= 1    nothing: a lane per user reads the two row starts and is done
+//   <= 64     one wave, a user at a time by ballot rounds: item and key in registers, one pass of shuffles over the m lanes decides "another
+//             candidate carries my item and a better key"
+//   <= HD_LDS one block per user of the list's front (ctr[0]): an open-addressing table in LDS keyed by item, HD_SLOTS = 2 * HD_LDS slots (load <= 1/2:
+//             distinct items <= entries), s_item claimed by atomicCAS, one 64-bit word s_best per slot.  (a) claim or find the slot, atomicMax the
+//             time half; (b) the entries that hold the best time zero the word and atomicMax their position half into it; (c) an entry whose position
+//             half is not the word sets its bit.  Without times (a) takes the position half and (b) falls away.  Slot, key and position of the
+//             HD_LDS / 256 = 8 entries of a thread stay in registers: no second probe, no second gather.  The touched slots are reset by their entries.
+//   larger    the blocks b < tb_blocks own one table over the stream's columns each in arena scratch (n_cols words of 8 bytes for the time half,
+//             when the stream has times, and n_cols of 4 bytes for the position half), all zero on entry and between users; they take the users
+//             of the list's back (ctr[1]) in turn.  The same phases with global atomics, the entries re-read per phase four gather chains at a
+//             time, then one more walk that stores 0 to the touched columns: cost by m, never by n_cols.  Every access to a table is an atomic or an
+//             agent-scope load / store, so no line of it is held in a CU's L1 (the bitmap rule of D23).
+// atomicOr only for dropped entries; one atomicAdd on a cursor per user beyond a wave.  Row starts are clamped into 0 .. n_e, entries that name no
+// position are skipped: whatever the index holds, no access leaves the arrays.  A position named twice inside one segment (a malformed index) gives
+// two entries of one key: both stay or both go.
+constexpr int HD_SLOTS = 2 * HD_LDS;     // slots of the LDS table: 16 KiB of items + 32 KiB of best-key words
+constexpr int HD_SLOT_BITS = 12;
+constexpr unsigned HD_EMPTY = 0xffffffffu;  // s_item of a free slot: no column id (they are below 2^31)
+static_assert(HD_SLOTS == 1 << HD_SLOT_BITS && HD_LDS % 256 == 0, "the slot hash takes the top HD_SLOT_BITS bits; a thread holds HD_LDS / 256 entries");
+
+namespace {
+struct HdEntry {
+  int item;               // < 0: no candidate
+  unsigned pk;            // position half of the key, never 0
+  unsigned long long tk;  // time half, 0 without times
+};
+
+__device__ __forceinline__ HdEntry hd_load(const TrimArgs& a, int n_cols, bool first, int q) {
+  HdEntry e{-1, 0u, 0ull};
+  if (q < 0 || q >= a.n_events) return e;
+  unsigned long long tk = 0ull;
+  if (a.times_ms) {
+    const int64_t t = a.times_ms[q];
+    if (t < a.min_time_ms) return e;
+    tk = (unsigned long long)t ^ HS_SIGN;
+    if (first) tk = ~tk;
+  }
+  const int it = a.items[q];
+  if (it < 0 || it >= n_cols) return e;
+  e.item = it;
+  e.tk = tk;
+  e.pk = first ? ~(unsigned)q : (unsigned)q + 1u;
+  return e;
+}
+
+// f(entry, position) for the candidates among ipos[0 .. m), by the whole block: four independent gather chains per thread in flight
+template <typename F>
+__device__ __forceinline__ void hd_for_candidates(const TrimArgs& a, int n_cols, bool first, const int32_t* __restrict__ ipos, int64_t m, F f) {
+  for (int64_t i = threadIdx.x; i < m; i += 256 * 4) {
+    int q[4];
+    HdEntry e[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = i + k * 256 < m ? ipos[i + k * 256] : -1;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) e[k] = hd_load(a, n_cols, first, q[k]);
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (e[k].item >= 0) f(e[k], q[k]);
+  }
+}
+
+__device__ __forceinline__ void hd_drop(unsigned long long* __restrict__ bits, int q) { atomicOr(&bits[q >> 6], 1ull << (q & 63)); }
+}  // namespace
+
+__global__ __launch_bounds__(256) void hd_mark_wave_kernel(DedupArgs d) {
+  const TrimArgs& a = d.trim;
+  const int lane = threadIdx.x & (SR_WAVE - 1);
+  const bool first = d.keep == DEDUP_FIRST;
+  const int64_t n_e = ht_entries(a.idx_row_ptr, a.n_users, a.n_events);
+  const int64_t n_waves = (int64_t)gridDim.x * (256 / SR_WAVE);
+  for (int64_t u0 = ((int64_t)blockIdx.x * (256 / SR_WAVE) + threadIdx.x / SR_WAVE) * SR_WAVE; u0 < a.n_users; u0 += n_waves * SR_WAVE) {  // wave-uniform
+    const int64_t u = u0 + lane;
+    int64_t lo = 0, m = 0;
+    if (u < a.n_users) {
+      lo = ht_clamp(a.idx_row_ptr[u], n_e);
+      m = ht_clamp(a.idx_row_ptr[u + 1], n_e) - lo;
+    }
+    if (m > SR_WAVE) {
+      if (m <= HD_LDS) d.list[atomicAdd(&d.ctr[0], 1ull)] = (int32_t)u;
+      else d.list[a.n_users - 1 - (int64_t)atomicAdd(&d.ctr[1], 1ull)] = (int32_t)u;
+    }
+    unsigned long long todo = __ballot(m >= 2 && m <= SR_WAVE);
+    while (todo) {  // wave-uniform: one user of the wave class per round
+      const int src = __ffsll((long long)todo) - 1;
+      todo &= todo - 1ull;
+      const int64_t seg = __shfl((long long)lo, src);
+      const int n = (int)__shfl((long long)m, src);
+      const int q = lane < n ? a.idx_pos[seg + lane] : -1;
+      const HdEntry e = hd_load(a, d.n_cols, first, q);
+      bool beaten = false;  // another candidate of the user carries this lane's item and a better key
+      for (int o = 0; o < n; ++o) {
+        const int oi = __shfl(e.item, o);
+        const unsigned op = __shfl(e.pk, o);
+        unsigned long long ot = 0ull;
+        if (a.times_ms) ot = __shfl(e.tk, o);  // wave-uniform
+        beaten |= oi == e.item && (ot > e.tk || (ot == e.tk && op > e.pk));
+      }
+      if (e.item >= 0 && beaten) hd_drop(a.s_bits, q);
+    }
+  }
+}
+
+namespace {
+// One user of 65 .. HD_LDS entries by the whole block; the LDS table is empty on entry and on return.
+__device__ __forceinline__ void hd_mark_lds_user(const TrimArgs& a, int n_cols, bool first, const int32_t* __restrict__ ipos, int m, unsigned* s_item,
+                                                 unsigned long long* s_best) {
+  constexpr int PER = HD_LDS / 256;
+  const bool timed = a.times_ms != nullptr;
+  int q[PER], slot[PER];
+  HdEntry e[PER];
+#pragma unroll
+  for (int k = 0; k < PER; ++k) q[k] = (int)threadIdx.x + k * 256 < m ? ipos[threadIdx.x + k * 256] : -1;
+#pragma unroll
+  for (int k = 0; k < PER; ++k) e[k] = hd_load(a, n_cols, first, q[k]);
+#pragma unroll
+  for (int k = 0; k < PER; ++k) {  // (a) claim or find the item's slot: at most HD_LDS of the HD_SLOTS are ever taken, the probe ends
+    slot[k] = 0;
+    if (e[k].item < 0) continue;
+    unsigned h = ((unsigned)e[k].item * 0x9E3779B1u) >> (32 - HD_SLOT_BITS);
+    for (;;) {
+      const unsigned was = atomicCAS(&s_item[h], HD_EMPTY, (unsigned)e[k].item);
+      if (was == HD_EMPTY || was == (unsigned)e[k].item) break;
+      h = (h + 1u) & (HD_SLOTS - 1);
+    }
+    slot[k] = (int)h;
+    atomicMax(&s_best[h], timed ? e[k].tk : (unsigned long long)e[k].pk);
+  }
+  __syncthreads();
+  if (timed) {  // block-uniform
+    unsigned win = 0u;  // (b) the entries that carry their item's best time
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+      if (e[k].item >= 0 && s_best[slot[k]] == e[k].tk) win |= 1u << k;
+    __syncthreads();  // every entry has read the best time: the word is free for the position half
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+      if ((win >> k) & 1u) s_best[slot[k]] = 0ull;
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < PER; ++k)
+      if ((win >> k) & 1u) atomicMax(&s_best[slot[k]], (unsigned long long)e[k].pk);
+    __syncthreads();
+  }
+#pragma unroll
+  for (int k = 0; k < PER; ++k)  // (c) only an entry that went into the word can find its own position half there
+    if (e[k].item >= 0 && s_best[slot[k]] != (unsigned long long)e[k].pk) hd_drop(a.s_bits, q[k]);
+  __syncthreads();
+#pragma unroll
+  for (int k = 0; k < PER; ++k)
+    if (e[k].item >= 0) {
+      s_item[slot[k]] = HD_EMPTY;
+      s_best[slot[k]] = 0ull;
+    }
+  __syncthreads();  // the table is empty again
+}
+
+// One user of more than HD_LDS entries by the whole block, over the block's column table: t_best [n_cols] (not read without times), p_best [n_cols],
+// all zero on entry and on return.
+__device__ __forceinline__ void hd_mark_table_user(const TrimArgs& a, int n_cols, bool first, const int32_t* __restrict__ ipos, int64_t m,
+                                                   unsigned long long* t_best, unsigned* p_best) {
+  const bool timed = a.times_ms != nullptr;
+  if (timed) {  // block-uniform
+    hd_for_candidates(a, n_cols, first, ipos, m, [&](const HdEntry& e, int) { atomicMax(&t_best[e.item], e.tk); });
+    __threadfence();  // this thread's maxima are performed ...
+    __syncthreads();  // ... and so are everybody's
+    hd_for_candidates(a, n_cols, first, ipos, m, [&](const HdEntry& e, int) {
+      if (__hip_atomic_load(&t_best[e.item], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == e.tk) atomicMax(&p_best[e.item], e.pk);
+    });
+  } else {
+    hd_for_candidates(a, n_cols, first, ipos, m, [&](const HdEntry& e, int) { atomicMax(&p_best[e.item], e.pk); });
+  }
+  __threadfence();
+  __syncthreads();
+  hd_for_candidates(a, n_cols, first, ipos, m, [&](const HdEntry& e, int q) {
+    if (__hip_atomic_load(&p_best[e.item], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != e.pk) hd_drop(a.s_bits, q);
+  });
+  __syncthreads();  // every entry has read its column: the walk that restores the zeros may begin
+  hd_for_candidates(a, n_cols, first, ipos, m, [&](const HdEntry& e, int) {
+    if (timed) __hip_atomic_store(&t_best[e.item], 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(&p_best[e.item], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  });
+  __threadfence();
+  __syncthreads();  // the table is zero again before the block's next user
+}
+}  // namespace
+
+// The listed users.  Blocks below tb_blocks first take the column-table users of the list's back, table b to block b; then every block takes
+// LDS-class users of the list's front.  A user is never split over blocks.
+__global__ __launch_bounds__(256) void hd_mark_block_kernel(DedupArgs d) {
+  __shared__ unsigned s_item[HD_SLOTS];
+  __shared__ unsigned long long s_best[HD_SLOTS];
+  const TrimArgs& a = d.trim;
+  const bool first = d.keep == DEDUP_FIRST;
+  const int64_t n_e = ht_entries(a.idx_row_ptr, a.n_users, a.n_events);
+  const int tb = d.tb_blocks < (int)gridDim.x ? d.tb_blocks : (int)gridDim.x;
+  if ((int)blockIdx.x < tb) {  // block-uniform
+    int64_t n_heavy = (int64_t)d.ctr[1];
+    if (n_heavy > a.n_users) n_heavy = a.n_users;
+    unsigned long long* t_best = d.tables + (int64_t)blockIdx.x * d.table_words;
+    unsigned* p_best = reinterpret_cast<unsigned*>(t_best + (a.times_ms ? d.n_cols : 0));
+    for (int64_t li = blockIdx.x; li < n_heavy; li += tb) {  // block-uniform
+      const int u = d.list[a.n_users - 1 - li];
+      if (u < 0 || u >= a.n_users) continue;
+      const int64_t lo = ht_clamp(a.idx_row_ptr[u], n_e);
+      const int64_t m = ht_clamp(a.idx_row_ptr[u + 1], n_e) - lo;
+      if (m <= HD_LDS) continue;
+      hd_mark_table_user(a, d.n_cols, first, a.idx_pos + lo, m, t_best, p_best);
+    }
+  }
+  for (int i = threadIdx.x; i < HD_SLOTS; i += 256) {
+    s_item[i] = HD_EMPTY;
+    s_best[i] = 0ull;
+  }
+  __syncthreads();
+  int64_t n_big = (int64_t)d.ctr[0];
+  if (n_big > a.n_users) n_big = a.n_users;
+  for (int64_t li = blockIdx.x; li < n_big; li += gridDim.x) {  // block-uniform
+    const int u = d.list[li];
+    if (u < 0 || u >= a.n_users) continue;
+    const int64_t lo = ht_clamp(a.idx_row_ptr[u], n_e);
+    const int64_t m = ht_clamp(a.idx_row_ptr[u + 1], n_e) - lo;
+    if (m < 2 || m > HD_LDS) continue;
+    hd_mark_lds_user(a, d.n_cols, first, a.idx_pos + lo, (int)m, s_item, s_best);
+  }
+}
+
+int64_t history_dedup_table_words(int32_t n_cols, bool timed) { return (timed ? (int64_t)n_cols : 0) + (((int64_t)n_cols + 1) >> 1); }
+
+int32_t history_dedup_table_blocks(int32_t n_cols, bool timed, int64_t budget_bytes) {
+  const int64_t bytes = history_dedup_table_words(n_cols, timed) * (int64_t)sizeof(unsigned long long);
+  const int64_t b = budget_bytes / (bytes > 0 ? bytes : 1);
+  return (int32_t)(b < 1 ? 1 : b < HD_TABLE_BLOCKS ? b : HD_TABLE_BLOCKS);
+}
+
+// launch_history_trim with the duplicates' mark in front of the keep: d.list [n_users], d.ctr [2], d.tables [tb_blocks * table_words] and the trim's scratch.
+hipError_t launch_history_dedup(hipStream_t st, int n_cu, const DedupArgs& d) {
+  const TrimArgs& a = d.trim;
+  const int64_t n = a.n_events, n_words = (n + 63) >> 6;
+  hipError_t e;
+  if (n > 0) {
+    const bool has_drop = a.n_drop > 0 && a.n_users > 0;
+    const bool has_dedup = n > 1 && a.n_users > 0;  // a duplicate takes two events
+    if (has_drop || has_dedup) {
+      e = hipMemsetAsync(a.s_bits, 0, sizeof(unsigned long long) * (size_t)n_words, st);
+      if (e != hipSuccess) return e;
+    }
+    if (has_drop) {
+      const int64_t jobs = a.n_drop * HT_SPLIT, cap = (int64_t)n_cu * 8;
+      hipLaunchKernelGGL(ht_mark_kernel, dim3((unsigned)(jobs < cap ? jobs : cap)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.idx_pos, a.n_drop, a.drop_users,
+                         a.s_bits);
+    }
+    if (has_dedup) {
+      e = hipMemsetAsync(d.ctr, 0, sizeof(unsigned long long) * 2, st);
+      if (e != hipSuccess) return e;
+      hipLaunchKernelGGL(hd_mark_wave_kernel, dim3(ig_grid(a.n_users, n_cu)), dim3(256), 0, st, d);
+      if (n > SR_WAVE) {
+        if (d.tb_blocks > 0) {  // only a stream of more than HD_LDS events can hold a user of the table class
+          e = hipMemsetAsync(d.tables, 0, sizeof(unsigned long long) * (size_t)d.tb_blocks * (size_t)d.table_words, st);
+          if (e != hipSuccess) return e;
+        }
+        const int64_t heavy = n / SR_WAVE + 1;  // users of more than a wave's entries, at most
+        const int64_t most = heavy < a.n_users ? heavy : a.n_users, grid = most < (int64_t)n_cu * 8 ? most : (int64_t)n_cu * 8;
+        hipLaunchKernelGGL(hd_mark_block_kernel, dim3((unsigned)grid), dim3(256), 0, st, d);
+      }
+    }
+    hipLaunchKernelGGL(ht_keep_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, a.times_ms, a.min_time_ms, has_drop || has_dedup, a.s_bits, a.s_cnt);
+    hipLaunchKernelGGL(ht_entries_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.idx_pos, a.s_bits, a.i_bits, a.i_cnt);
+  }
+  e = launch_scan_i32(st, a.s_cnt, n_words, a.s_base, a.tile_sums);
+  if (e != hipSuccess) return e;
+  e = launch_scan_i32(st, a.i_cnt, n_words, a.i_base, a.tile_sums);
+  if (e != hipSuccess) return e;
+  if (n > 0) {
+    hipLaunchKernelGGL(ht_compact_stream_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, a.items, a.times_ms, a.s_bits, a.s_base, a.out_items, a.out_times);
+    hipLaunchKernelGGL(ht_compact_index_kernel, dim3(ig_grid(n, n_cu)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.idx_pos, a.s_bits, a.s_base, a.i_bits, a.i_base,
+                       a.out_pos);
+  }
+  hipLaunchKernelGGL(ht_row_ptr_kernel, dim3(ig_grid(a.n_users + 1, n_cu)), dim3(256), 0, st, n, a.n_users, a.idx_row_ptr, a.i_bits, a.s_base, a.i_base, a.out_row_ptr,
+                     a.out_counts);
+  return hipGetLastError();
+}
+
 // ---- matrices (decision D23) ---------------------------------------------------------------------------------------
 // The Preparator's output from the index and the item stream alone: which users train (users), and per event type the user x column matrix whose rows are
 // the users' distinct in-window columns, ascending (matrix) -- the arrays launch_csr_from_pairs gives for the pairs (row_of[user], item), without a `users` array.

@@ -451,6 +451,23 @@ struct CapArgs {
   unsigned long long* ctr;       // scratch [1]: their number
 };
 hipError_t launch_history_cap(hipStream_t st, int n_cu, const CapArgs& c);
+// the trim with one event per user and item (decision D29; include/urcco.h urcco_dev_history_dedup)
+enum { DEDUP_FIRST = 1, DEDUP_LAST = 2 };        // == URCCO_DEDUP_FIRST / _LAST of include/urcco.h
+constexpr int HD_LDS = 2048;                     // entries of a user the LDS class serves at most; the column-table class begins above
+constexpr int64_t HD_TABLE_BUDGET = 64ll << 20;  // bytes of arena the column tables of one _dedup launch may take
+constexpr int HD_TABLE_BLOCKS = 64;              // blocks of the column-table class at most: one table each
+int64_t history_dedup_table_words(int32_t n_cols, bool timed);                        // 64-bit words of one table: n_cols best times (with times) + n_cols 32-bit best positions
+int32_t history_dedup_table_blocks(int32_t n_cols, bool timed, int64_t budget_bytes);  // min(HD_TABLE_BLOCKS, budget / bytes of one table), at least 1
+struct DedupArgs {
+  TrimArgs trim;
+  int32_t n_cols, keep;          // keep: DEDUP_FIRST or DEDUP_LAST
+  int32_t tb_blocks;             // blocks of the column-table class; 0 = no user can be that heavy (n_events <= HD_LDS)
+  int64_t table_words;           // history_dedup_table_words
+  int32_t* list;                 // scratch [n_users]: users of 65 .. HD_LDS entries from the front, heavier ones from the back
+  unsigned long long* ctr;       // scratch [2]: their numbers
+  unsigned long long* tables;    // scratch [tb_blocks * table_words]
+};
+hipError_t launch_history_dedup(hipStream_t st, int n_cu, const DedupArgs& d);
 // the users that train and their row numbers, one event type's user x column matrix (decision D23; include/urcco.h urcco_dev_history_users / _matrix)
 constexpr int64_t HM_BITMAP_BUDGET = 8ll << 20;  // bytes of arena the column bitmaps of one _matrix launch may take
 constexpr int HM_BITMAP_BLOCKS = 64;             // blocks of the bitmap class at most: one bitmap each

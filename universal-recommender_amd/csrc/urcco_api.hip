@@ -876,6 +876,38 @@ int urcco_dev_history_cap(urcco_session* s, int64_t n_events, const int32_t* ite
   return URCCO_OK;
 }
 
+int urcco_dev_history_dedup(urcco_session* s, int64_t n_events, const int32_t* items, const int64_t* times_ms, int64_t n_users, const int64_t* idx_row_ptr,
+                            const int32_t* idx_pos, int64_t min_time_ms, int64_t n_drop, const int32_t* drop_users, int32_t n_cols, int32_t keep, int32_t* out_items,
+                            int64_t* out_times, int64_t* out_row_ptr, int32_t* out_pos, int64_t* out_counts) {
+  if (!s || n_events < 0 || n_events > 0x7fffffffll || n_users < 0 || n_users > 0x7ffffff0ll || n_drop < 0)
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_dedup: bad argument (a stream holds fewer than 2^31 events)");
+  if (n_cols < 1) return fail(URCCO_BAD_ARG, "urcco_dev_history_dedup: n_cols must be >= 1, got %d", n_cols);
+  if (keep != URCCO_DEDUP_FIRST && keep != URCCO_DEDUP_LAST)
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_dedup: keep must be URCCO_DEDUP_FIRST (1) or URCCO_DEDUP_LAST (2), got %d", keep);
+  if (!out_row_ptr || !out_counts || (n_events > 0 && (!items || !idx_pos || !out_items || !out_pos)) || (n_users > 0 && !idx_row_ptr) || (n_drop > 0 && !drop_users))
+    return fail(URCCO_BAD_ARG, "urcco_dev_history_dedup: NULL argument");
+  if ((times_ms == nullptr) != (out_times == nullptr)) return fail(URCCO_BAD_ARG, "urcco_dev_history_dedup: times_ms and out_times are both NULL or both given");
+  urcco::DedupArgs d{};
+  urcco::TrimArgs& a = d.trim;
+  d.n_cols = n_cols; d.keep = keep;
+  a.n_events = n_events; a.n_users = n_users; a.n_drop = n_drop; a.min_time_ms = min_time_ms;
+  a.items = items; a.times_ms = times_ms; a.idx_row_ptr = idx_row_ptr; a.idx_pos = idx_pos; a.drop_users = drop_users;
+  a.out_items = out_items; a.out_times = out_times; a.out_row_ptr = out_row_ptr; a.out_pos = out_pos; a.out_counts = out_counts;
+  // URCCO_HD_TABLE_BUDGET lowers the bytes the column tables of the heaviest class may take (read per call): with few bytes one block serves many heavy users
+  int64_t budget = urcco::HD_TABLE_BUDGET;
+  if (const char* e = getenv("URCCO_HD_TABLE_BUDGET")) {
+    const long long v = atoll(e);
+    if (v >= 0 && v < budget) budget = v;
+  }
+  d.table_words = urcco::history_dedup_table_words(n_cols, times_ms != nullptr);
+  d.tb_blocks = n_events > urcco::HD_LDS && n_users > 0 ? urcco::history_dedup_table_blocks(n_cols, times_ms != nullptr, budget) : 0;  // no user of a shorter stream is that heavy
+  const size_t n_words = (size_t)((n_events + 63) >> 6);
+  URC(ArenaLayout(s).add(&a.s_bits, n_words).add(&a.i_bits, n_words).add(&a.s_cnt, n_words).add(&a.i_cnt, n_words).add(&a.s_base, n_words + 1).add(&a.i_base, n_words + 1)
+          .add(&a.tile_sums, scan_tile_words((int64_t)n_words)).add(&d.list, (size_t)n_users).add(&d.ctr, 2).add(&d.tables, (size_t)d.tb_blocks * (size_t)d.table_words).commit());
+  HIPC(urcco::launch_history_dedup(s->stream, s->n_cu, d));
+  return URCCO_OK;
+}
+
 // the window of urcco_dev_history_users / _matrix: without times only the open one
 static bool history_window_ok(const int64_t* times_ms, int64_t t_lo, int64_t t_hi) { return times_ms || (t_lo == INT64_MIN && t_hi == INT64_MAX); }
 

@@ -373,6 +373,28 @@ class DeviceSession:
                                                    _ptr(drop_users) if n_drop else None, cap, _ptr(o_items), _ptr(o_times), _ptr(o_rp), _ptr(o_pos), _ptr(counts)))
         return o_items, o_times, o_rp, o_pos, counts
 
+    def history_dedup(self, n_events: int, items: torch.Tensor, times: Optional[torch.Tensor], idx_row_ptr: torch.Tensor, idx_pos: torch.Tensor,
+                      n_cols: int, keep: str, min_time_ms: Optional[int] = None, drop_users: Optional[torch.Tensor] = None, out=None):
+        """urcco_dev_history_dedup (decision D29): history_trim with one more rule -- of the events of one user that carry the same item (a column in
+        0 .. n_cols) only one stays, by the rows' recency key (time, stream position): keep = "last" the most recent, "first" the earliest.  The
+        duplicates are decided among the events that survive the time rule.  Arguments, result and `out` as in history_trim.  Does not synchronise."""
+        n, n_users = int(n_events), int(idx_row_ptr.numel()) - 1
+        n_drop = int(drop_users.numel()) if drop_users is not None else 0
+        if out is None:
+            out = (self.empty(max(n, 1), torch.int32), self.empty(max(n, 1), torch.int64) if times is not None else None, self.empty(n_users + 1, torch.int64),
+                   self.empty(max(n, 1), torch.int32))
+        o_items, o_times, o_rp, o_pos = out
+        if o_items.numel() < n or o_pos.numel() < n or o_rp.numel() < n_users + 1 or (o_times is not None and o_times.numel() < n):
+            raise ValueError("history_dedup: the output tensors are smaller than n_events / n_users + 1")
+        if keep not in ("first", "last"):
+            raise ValueError(f"history_dedup: keep must be 'first' or 'last', got {keep!r}")
+        counts = self.empty(2, torch.int64)
+        self._check(self.lib.urcco_dev_history_dedup(self.handle, n, _ptr(items), _ptr(times), n_users, _ptr(idx_row_ptr), _ptr(idx_pos),
+                                                     int(min_time_ms) if min_time_ms is not None and times is not None else -(1 << 63), n_drop,
+                                                     _ptr(drop_users) if n_drop else None, int(n_cols), _lib.DEDUP_FIRST if keep == "first" else _lib.DEDUP_LAST,
+                                                     _ptr(o_items), _ptr(o_times), _ptr(o_rp), _ptr(o_pos), _ptr(counts)))
+        return o_items, o_times, o_rp, o_pos, counts
+
     @staticmethod
     def _window(after_ms: Optional[int], before_ms: Optional[int]):
         return (-(1 << 63) if after_ms is None else int(after_ms), (1 << 63) - 1 if before_ms is None else int(before_ms))

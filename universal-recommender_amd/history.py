@@ -266,7 +266,8 @@ class DeviceHistory:
             self.user_ids = user_ids
         return self
 
-    def trim(self, before_ms: Optional[int] = None, drop_users=None, events: Optional[List[str]] = None, max_events_per_user=None) -> "DeviceHistory":
+    def trim(self, before_ms: Optional[int] = None, drop_users=None, events: Optional[List[str]] = None, max_events_per_user=None,
+             remove_duplicates=None) -> "DeviceHistory":
         """Retention, in place (decision D22 of DESIGN.md; include/urcco.h urcco_dev_history_trim); returns self.  before_ms: the events with time <
         before_ms leave the event types named in `events` (default: every type that has times) -- the reference's eventWindow.  drop_users: an
         iterable of user keys (resolved through user_indices, once per call; unknown ones ignored) or an int32 tensor of dense ids; their events leave EVERY event type,
@@ -282,12 +283,23 @@ class DeviceHistory:
         `matrices` / train_from_history see only what is stored: a capped history trains on the capped events.  Term rows with max_items <= the cap
         are unchanged by it.
 
+        remove_duplicates (decision D29; urcco_dev_history_dedup): None -- nothing, the calls and the cost of before; "first" / "last" -- of the
+        events of one user that carry the same item only the earliest / the most recent (by time, then stream position) stays in every type named in
+        `events` (default: every type); a dict {event: "first" | "last"} names the types itself.  The duplicates are decided among the events that
+        survive before_ms; events without a column (an item outside the type's columns) are never duplicates.  Per type one call that carries the
+        time cut and the listed users as well.  Together with a cap on the same type the duplicates go first and the cap is decided over the
+        survivors: the first calls of all types run, the counts are read, the caps of those types run, the counts are read once more -- one extra
+        device-to-host read.  Consequences: `matrices` / train_from_history over an open window give the same matrices before and after (their
+        rows are duplicate-free anyway).  With "last" a term row whose max_items is at least the user's event count is unchanged, shorter windows
+        now hold the most recent DISTINCT items.  With "first" an item's recency becomes that of its first event: it may leave a window it was in.
+        A de-duplicated blacklist type excludes the same items as before.
+
         A type for which no rule applies costs no call.  One device-to-host read, of the counts of all types together.  The outputs of the
         call become the stream's buffers, with the capacity the old ones had: their tail is the spare capacity the next append fills.  The index
         pair of before becomes the spare pair.  `last_trim` = {event: (events before, events after)} of the types that were trimmed.
 
         ValueError -- nothing is modified: `events` or the cap's dict names a type the history does not hold, or, with before_ms, `events` one without
-        times; a cap below 1 or above 2^31 - 1; drop_users is a tensor of another dtype; a _Stream built by hand without n_events."""
+        times; a cap below 1 or above 2^31 - 1; remove_duplicates naming a type the history does not hold or a value other than the two strings; drop_users is a tensor of another dtype; a _Stream built by hand without n_events."""
         named = list(self.types) if events is None else list(events)
         for ev in named:
             if ev not in self.types:
@@ -305,6 +317,16 @@ class DeviceHistory:
                 raise ValueError(f"trim: the history holds no event type {ev!r}")
             if c < 1 or c > (1 << 31) - 1:
                 raise ValueError(f"trim: max_events_per_user must be in 1 .. 2^31 - 1, got {c} for {ev!r}")
+        dedup: Dict[str, str] = {}
+        if isinstance(remove_duplicates, dict):
+            dedup = dict(remove_duplicates)
+        elif remove_duplicates is not None:
+            dedup = {ev: remove_duplicates for ev in named}
+        for ev, keep in dedup.items():
+            if ev not in self.types:
+                raise ValueError(f"trim: the history holds no event type {ev!r}")
+            if not isinstance(keep, str) or keep not in ("first", "last"):
+                raise ValueError(f"trim: remove_duplicates must be 'first' or 'last', got {keep!r} for {ev!r}")
         sess = self.sess
         drop = None
         if isinstance(drop_users, torch.Tensor):
@@ -314,7 +336,7 @@ class DeviceHistory:
         elif drop_users is not None:
             ids = [i for i in self.user_indices(drop_users) if i >= 0]
             drop = torch.tensor(ids, dtype=torch.int32).to(sess.device) if ids else None
-        todo = [ev for ev in self.types if ev in by_time or drop is not None or ev in caps]
+        todo = [ev for ev in self.types if ev in by_time or drop is not None or ev in caps or ev in dedup]
         for ev in todo:
             if self.types[ev].n_events < 0:
                 raise ValueError(f"stream {ev!r}: built without its number of events (_Stream.n_events)")
@@ -331,16 +353,31 @@ class DeviceHistory:
             out = (sess.empty((st.items_buf if st.items_buf is not None else st.items).numel(), torch.int32),
                    sess.empty((st.times_buf if st.times_buf is not None else st.times).numel(), torch.int64) if st.times is not None else None, spare[0], spare[1])
             cut = before_ms if ev in by_time else None
-            if ev in caps:
+            if ev in dedup:
+                calls.append((ev, out, sess.history_dedup(n, st.items, st.times, st.idx_row_ptr, st.idx_pos, st.n_cols, dedup[ev], cut, drop, out)[4]))
+            elif ev in caps:
                 calls.append((ev, out, sess.history_cap(n, st.items, st.times, st.idx_row_ptr, st.idx_pos, caps[ev], cut, drop, out)[4]))
             else:
                 calls.append((ev, out, sess.history_trim(n, st.items, st.times, st.idx_row_ptr, st.idx_pos, cut, drop, out)[4]))
         counts = torch.stack([c for _, _, c in calls]).cpu().tolist() if calls else []
-        self.last_trim = {ev: (0, 0) for ev in todo}
+        second = []          # the types with both rules: the cap over what the first call kept, into buffers of the same capacity
         for (ev, (o_items, o_times, o_rp, o_pos), _), (k, _) in zip(calls, counts):
+            if ev in dedup and ev in caps and k > 0:
+                out = (sess.empty(o_items.numel(), torch.int32), sess.empty(o_times.numel(), torch.int64) if o_times is not None else None,
+                       sess.empty(o_rp.numel(), torch.int64), sess.empty(o_pos.numel(), torch.int32))
+                second.append((ev, out, sess.history_cap(k, o_items[:k], o_times[:k] if o_times is not None else None, o_rp[: self.n_users + 1], o_pos[:k],
+                                                         caps[ev], None, None, out)[4]))
+        counts2 = dict(zip((ev for ev, _, _ in second), torch.stack([c for _, _, c in second]).cpu().tolist())) if second else {}
+        outs2 = {ev: out for ev, out, _ in second}
+        self.last_trim = {ev: (0, 0) for ev in todo}
+        for (ev, first_out, _), (k, _) in zip(calls, counts):
             st = self.types[ev]
-            self.last_trim[ev] = (st.n_events, int(k))
             st.idx_spare = st.idx_buf if st.idx_buf is not None else (st.idx_row_ptr, st.idx_pos)
+            if ev in outs2:      # the first call's index pair is the spare one now
+                st.idx_spare = (first_out[2], first_out[3])
+                k = counts2[ev][0]
+            o_items, o_times, o_rp, o_pos = outs2.get(ev, first_out)
+            self.last_trim[ev] = (st.n_events, int(k))
             st.items_buf, st.items = o_items, o_items[: max(k, 1)]      # an empty stream still has an array
             if o_times is not None:
                 st.times_buf, st.times = o_times, o_times[: max(k, 1)]
