@@ -591,6 +591,40 @@ int urcco_dev_rank_metrics(urcco_session* s, int64_t n_queries, int32_t num,
                            int64_t* out_sums_i, double* out_sums_f);                     /* device, nullable pair: [2 + 2 * n_ks], [2 * n_ks] */
 int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double* x /* device [n * n_cols] */, double* out /* device [n_cols] */);
 
+/* Why an item was recommended: the terms behind every score of a table of recommendations -- the user's own past items, the similar item's correlators,
+ * the matched property values -- without copying an indicator or history row to the host (the reference leaves this to Elasticsearch's `explain`).
+ * DESIGN.md decision D30.  For query q and slot j < c = min(max(rec_count[q], 0), num), i = rec_idx[q * num + j]:
+ *   out_m[(q * num + j) * n_clauses + c] = M_c(q, i) = the sum of w_c[h] over the entries h of row i of I_c that lie in T_c(q): an exact integer in units of
+ *       2^-15.  weight == NULL is URCCO_REC_WEIGHT_ONE throughout; every loaded weight is clamped to 1 .. URCCO_REC_WEIGHT_MAX exactly as
+ *       urcco_dev_recommend_weighted clamps it.
+ *   CONTRACT with the recommend calls: ((0.0 + boost_0 ((double)M_0 2^-15)) + boost_1 ((double)M_1 2^-15)) + ..., folded in call order without contraction,
+ *       equals bit for bit the out_score that urcco_dev_recommend, _rules and _weighted wrote for the same clauses (I_c here is the CSR of the matrix whose
+ *       CSC they were given; boosts, query rows and weight arrays the same).
+ *   out_n[q * num + j] = min(max_terms, the number of matching entries over all clauses); the listed terms (out_clause, out_term, out_contrib)
+ *       [(q * num + j) * max_terms + r], r < out_n, are the first out_n matches in the total order (contrib desc, clause asc, term asc), with
+ *       contrib = boost_c * ((double)w_c[h] * 2^-15).  Entries behind out_n are not written.
+ *   A slot at or behind c, and a slot whose i lies outside 0..n_items: out_n = 0 and out_m = 0; nothing of rec_idx at or behind c is read.  A column outside
+ *   0..n_cols in a row of I_c never matches.  The rows of I_c are duplicate-free as the build and urcco_dev_props_rows leave them (the caller's duty): a
+ *   repeated entry counts and is listed each time.
+ * Enqueues on the session's stream and does not synchronise; no scratch, no float atomics: every output is reproducible bit for bit.  URCCO_BAD_ARG: num
+ * outside 1..URCCO_REC_MAX_NUM, n_clauses outside 1..URCCO_REC_MAX_CLAUSES, max_terms outside 1..URCCO_EXPLAIN_MAX_TERMS, a boost that is not positive and
+ * finite, n_cols < 0, a NULL array the call needs, n_queries * num * max(n_clauses, max_terms) >= 2^31.  n_queries == 0 is legal.
+ * ABI: an addition within ABI 305 -- the presence of the symbol is the feature test. */
+#define URCCO_EXPLAIN_MAX_TERMS 64
+typedef struct urcco_explain_clause {
+  int32_t n_cols, reserved;
+  double boost;                                       /* > 0, finite: the clause's boost in the recommend call */
+  const int64_t* m_row_ptr; const int32_t* m_col_idx; /* device CSR of I_c, n_items x n_cols, order inside a row unspecified */
+  const int64_t* q_row_ptr; const int32_t* q_col_idx; /* device CSR of T_c, n_queries x n_cols, sorted unique */
+  const uint32_t* weight;                             /* device [n_cols], nullable: the array given to urcco_dev_recommend_weighted */
+} urcco_explain_clause;
+int urcco_dev_explain(urcco_session* s, int64_t n_queries, int32_t n_items, int32_t num,
+                      const int32_t* rec_count, const int32_t* rec_idx,      /* as urcco_dev_recommend leaves them, rows strided by num */
+                      const urcco_explain_clause* clauses, int32_t n_clauses, int32_t max_terms,
+                      int64_t* out_m,        /* [n_queries * num * n_clauses] */
+                      int32_t* out_n,        /* [n_queries * num] */
+                      int32_t* out_clause, int32_t* out_term, double* out_contrib /* [n_queries * num * max_terms] */);
+
 /* Device-resident user history: the event-store half of a batch of queries (getBiasedRecentUserActions, URAlgorithm.scala:795-839; getExcludedItems,
  * :741-767), from event streams that already sit in HBM -- (user id, column id, time) per event and event type, dense ids as urcco_dev_dictionary_lookup
  * yields them.  DESIGN.md decision D17.  For a query user u and event type e with cap max_items (the indicator's maxItemsPerUser):

@@ -25,7 +25,10 @@ report); and, as a comparison point only, the HIP-event time of a torch.isin + c
 --weights: the same problem once more through urcco_dev_recommend_weighted (decision D20) under the model's idf term weights (DeviceModel.term_weights:
 one urcco_dev_idf_weights call per event type, timed on its own), its time printed next to the unweighted call's of the same process; and once with arrays
 that hold WEIGHT_ONE alone, whose ids and score bits must be the unweighted call's.
-usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--rules] [--weights] [--device-history] [--device-items] [--evaluate] [--no-torch]"""
+--explain: urcco_dev_explain (decision D30, max_terms = 5) over the table the timed urcco_dev_recommend call left, its HIP-event time next to that call's; the
+fold of its per-clause sums is compared with the scores; and the host route for the same batch on this box: the copies of the indicator matrices, the
+query rows and the table, then np.intersect1d per (query, slot, clause) over the first 2000 queries, scaled to the batch.
+usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--rules] [--weights] [--device-history] [--device-items] [--evaluate] [--explain] [--no-torch]"""
 import argparse
 import os
 import sys
@@ -49,6 +52,7 @@ ap.add_argument("--weights", action="store_true", help="also time the weighted c
 ap.add_argument("--device-history", action="store_true", help="also time history_bounds + history_rows against the host planning loop")
 ap.add_argument("--device-items", action="store_true", help="also time item_bounds + item_rows against the host planning loop of item queries")
 ap.add_argument("--evaluate", action="store_true", help="also time rank_metrics, evaluate end to end and a torch restatement of the hits")
+ap.add_argument("--explain", action="store_true", help="also time urcco_dev_explain over the call's table against the host route (fetch rows + numpy intersect)")
 ap.add_argument("--no-torch", action="store_true", help="skip the torch comparison")
 args = ap.parse_args()
 
@@ -264,6 +268,37 @@ if args.evaluate:
     t_hits, ms_isin = timed(torch_hits, args.reps)
     print(f"torch.isin + cumsum restatement of the per-user hits alone (comparison point): {min(ms_isin):.3f} ms best ({[round(x, 3) for x in ms_isin]}); "
           f"hits equal: {bool(torch.equal(t_hits, e_hits))}")
+
+if args.explain:
+    import time
+
+    import numpy as np
+    E = 5
+    e_clauses = [(c.n_cols, b, c.row_ptr, c.col_idx, cl[4], cl[5], None) for c, b, cl in zip(model.correlators, boosts, clauses)]
+    (e_m, e_n, e_clause, e_term, e_contrib), ms_e = timed(lambda: sess.explain(count, idx, e_clauses, E, n_items), args.reps)
+    fold = torch.zeros_like(score)
+    for c, b in enumerate(boosts):
+        fold = fold + b * (e_m[:, :, c].to(torch.float64) * 2.0 ** -15)
+    live = torch.arange(num, device=dev)[None, :] < count[:, None]
+    print(f"urcco_dev_explain (max_terms = {E}, the table of the call above, allocation of the zeroed outputs included): {min(ms_e):.2f} ms best, "
+          f"{sorted(ms_e)[len(ms_e) // 2]:.2f} ms median of {args.reps} ({[round(x, 2) for x in ms_e]}) -- its urcco_dev_recommend call: {min(ms_hip):.2f} ms best")
+    print(f"  matches listed {int(e_n.sum().item())} over {int(live.sum().item())} slots ({int((e_n > 0).sum().item())} with a term); the fold of out_m is the score bit for bit on "
+          f"every returned slot: {bool(torch.equal(torch.where(live, fold, 0.0).view(torch.int64), torch.where(live, score, 0.0).view(torch.int64)))}")
+    # the host route for the same batch: fetch the indicator matrices, the query rows and the table, then intersect per (query, slot, clause) in numpy
+    t0 = time.perf_counter()
+    host = [(c.row_ptr.cpu().numpy(), c.col_idx.cpu().numpy(), cl[4].cpu().numpy(), cl[5].cpu().numpy()) for c, cl in zip(model.correlators, clauses)]
+    h_count, h_idx = count.cpu().numpy(), idx.cpu().numpy()
+    t1 = time.perf_counter()
+    sample = min(nq, 2000)
+    listed = 0
+    for q in range(sample):
+        for j in range(int(h_count[q])):
+            i = int(h_idx[q, j])
+            for rp, ci, qrp, qci in host:
+                listed += np.intersect1d(ci[rp[i]:rp[i + 1]], qci[qrp[q]:qrp[q + 1]]).size
+    t2 = time.perf_counter()
+    print(f"  host route: copies of the matrices, the query rows and the table {(t1 - t0) * 1e3:.1f} ms; numpy intersect over the first {sample} queries {(t2 - t1) * 1e3:.1f} ms "
+          f"({listed} matches) = {(t2 - t1) * 1e3 * nq / sample:.0f} ms for the batch at that rate (wall clock, this box's CPU)")
 
 if args.no_torch:
     sess.close()

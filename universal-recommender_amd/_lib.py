@@ -35,6 +35,8 @@ RULE_ANY, RULE_NONE, RULE_RANGE = 0, 1, 2
 REC_WEIGHT_ONE = 1 << 15   # urcco_dev_recommend_weighted (URCCO_REC_WEIGHT_*): term weights are uint32 in units of 2^-15 ...
 REC_WEIGHT_MAX = 1 << 20   # ... from 1 to 32.0
 EVAL_MAX_KS = 8        # urcco_dev_rank_metrics (URCCO_EVAL_MAX_KS): cut-offs per call
+EXPLAIN_MAX_TERMS = 64  # urcco_dev_explain (URCCO_EXPLAIN_MAX_TERMS): listed terms per result
+EXPLAIN_LDS_TERMS = 8192  # query terms over all clauses up to which urcco_dev_explain stages them in LDS (csrc/cco_explain.h)
 EVAL_TREE_BLOCK = 256  # positions one block of the tree sum reduces (csrc/cco_eval.h): beyond it a further pass runs over the partials
 RANK_POPULAR, RANK_TRENDING, RANK_HOT = 1, 2, 3   # urcco_dev_history_ranks (URCCO_RANK_*): the ranking type = the number of intervals
 RANK_NONE = -(1 << 63)   # the item has no rank in the field (INT64_MIN)
@@ -148,6 +150,12 @@ class RecRule(C.Structure):
                 ("q_col_idx", C.c_void_p), ("item_value", C.c_void_p), ("q_lo", C.c_void_p), ("q_hi", C.c_void_p)]
 
 
+class ExplainClause(C.Structure):
+    """urcco_explain_clause: one should-clause of urcco_dev_explain -- the CSR of the matrix whose CSC the recommend call was given."""
+    _fields_ = [("n_cols", C.c_int32), ("reserved", C.c_int32), ("boost", C.c_double), ("m_row_ptr", C.c_void_p), ("m_col_idx", C.c_void_p),
+                ("q_row_ptr", C.c_void_p), ("q_col_idx", C.c_void_p), ("weight", C.c_void_p)]
+
+
 class HistEvent(C.Structure):
     """urcco_hist_event: one event type of urcco_dev_history_bounds / _rows."""
     _fields_ = [("n_cols", C.c_int32), ("max_items", C.c_int32), ("blacklist", C.c_int32), ("reserved", C.c_int32), ("idx_row_ptr", C.c_void_p),
@@ -236,6 +244,7 @@ SYMBOLS = {
     "urcco_dev_idf_weights": (C.c_int, [_p, C.c_int32, _p, C.c_int64, _p]),
     "urcco_dev_rank_metrics": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p, _p, C.POINTER(C.c_int32), C.c_int32, _p, _p, _p, _p, _p, _p]),
     "urcco_dev_tree_sum": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p]),
+    "urcco_dev_explain": (C.c_int, [_p, C.c_int64, C.c_int32, C.c_int32, _p, _p, C.POINTER(ExplainClause), C.c_int32, C.c_int32, _p, _p, _p, _p, _p]),
     "urcco_dev_history_index": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_append": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_trim": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p]),

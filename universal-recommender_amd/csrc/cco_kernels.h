@@ -395,6 +395,31 @@ hipError_t launch_rank_metrics(hipStream_t st, int n_cu, int64_t n_queries, int3
                                const int32_t* truth_col_idx, const int32_t* ks, int32_t n_ks, const double* discount, double* ideal, int32_t* out_hits, double* out_ap,
                                double* out_ndcg, int64_t* out_sums_i, double* out_sums_f, double* pa, double* pb);
 
+// ---- the terms behind a score (cco_explain.h, compiled into cco_misc.hip behind cco_eval.h; decision D30) ----------------------
+constexpr int EXPLAIN_MAX_TERMS = 64;  // == URCCO_EXPLAIN_MAX_TERMS of include/urcco.h
+struct ExplClause {
+  const int64_t* m_row_ptr;    // CSR of I_c (n_items x n_cols), order inside a row unspecified
+  const int32_t* m_col_idx;
+  const int64_t* q_row_ptr;    // CSR of the query terms T_c (n_queries x n_cols), sorted unique columns
+  const int32_t* q_col_idx;
+  const uint32_t* weight;      // nullable: [n_cols] term weights in units of 2^-15 (REC_WEIGHT_ONE throughout)
+  double boost;
+  int32_t n_cols, reserved;
+};
+struct ExplArgs {
+  ExplClause c[REC_MAX_CLAUSES];
+  int64_t n_queries;
+  int32_t n_items, num, n_clauses, max_terms;
+  const int32_t* rec_count;
+  const int32_t* rec_idx;
+  int64_t* out_m;              // [n_queries * num * n_clauses]
+  int32_t* out_n;              // [n_queries * num]
+  int32_t* out_clause;         // [n_queries * num * max_terms], like out_term and out_contrib
+  int32_t* out_term;
+  double* out_contrib;
+};
+hipError_t launch_explain(hipStream_t st, int n_cu, const ExplArgs& a);
+
 // ---- device-resident user history (cco_history.h, compiled into ingest_kernels.hip; decision D17) ----------------------
 constexpr int HIST_STATS_LEN = 8;   // == URCCO_HIST_STATS_LEN of include/urcco.h
 enum { HIST_STAT_WAVE = 0, HIST_STAT_BLOCK = 1, HIST_STAT_GLOBAL = 2, HIST_STAT_SELECT = 3, HIST_STAT_EXCL_WAVE = 4, HIST_STAT_EXCL_BLOCK = 5, HIST_STAT_OVERFLOW = 6 };

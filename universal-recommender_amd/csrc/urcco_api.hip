@@ -1328,6 +1328,34 @@ int urcco_dev_rank_metrics(urcco_session* s, int64_t n_queries, int32_t num, con
   return URCCO_OK;
 }
 
+int urcco_dev_explain(urcco_session* s, int64_t n_queries, int32_t n_items, int32_t num, const int32_t* rec_count, const int32_t* rec_idx,
+                      const urcco_explain_clause* clauses, int32_t n_clauses, int32_t max_terms, int64_t* out_m, int32_t* out_n, int32_t* out_clause, int32_t* out_term,
+                      double* out_contrib) {
+  if (!s || n_queries < 0 || n_items < 0) return fail(URCCO_BAD_ARG, "urcco_dev_explain: bad argument");
+  if (num < 1 || num > URCCO_REC_MAX_NUM) return fail(URCCO_BAD_ARG, "urcco_dev_explain: num must lie in 1..%d, got %d", URCCO_REC_MAX_NUM, num);
+  if (n_clauses < 1 || n_clauses > URCCO_REC_MAX_CLAUSES || !clauses)
+    return fail(URCCO_BAD_ARG, "urcco_dev_explain: between 1 and %d clauses, got %d", URCCO_REC_MAX_CLAUSES, n_clauses);
+  if (max_terms < 1 || max_terms > URCCO_EXPLAIN_MAX_TERMS)
+    return fail(URCCO_BAD_ARG, "urcco_dev_explain: max_terms must lie in 1..%d, got %d", URCCO_EXPLAIN_MAX_TERMS, max_terms);
+  if (n_queries > 0x7fffffffll || n_queries * (int64_t)num * (int64_t)(n_clauses > max_terms ? n_clauses : max_terms) > 0x7fffffffll)
+    return fail(URCCO_BAD_ARG, "urcco_dev_explain: too many queries");
+  urcco::ExplArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int c = 0; c < n_clauses; ++c) {
+    const urcco_explain_clause& in = clauses[c];
+    if (!(in.boost > 0.0) || in.boost > 1.7976931348623157e308) return fail(URCCO_BAD_ARG, "urcco_dev_explain: clause %d: the boost must be positive and finite", c);
+    if (in.n_cols < 0 || !in.m_row_ptr || !in.m_col_idx || !in.q_row_ptr || !in.q_col_idx) return fail(URCCO_BAD_ARG, "urcco_dev_explain: clause %d: bad matrix", c);
+    a.c[c] = urcco::ExplClause{in.m_row_ptr, in.m_col_idx, in.q_row_ptr, in.q_col_idx, in.weight, in.boost, in.n_cols, 0};
+  }
+  if (n_queries > 0 && (!rec_count || !rec_idx || !out_m || !out_n || !out_clause || !out_term || !out_contrib))
+    return fail(URCCO_BAD_ARG, "urcco_dev_explain: an array is missing");
+  a.n_queries = n_queries; a.n_items = n_items; a.num = num; a.n_clauses = n_clauses; a.max_terms = max_terms;
+  a.rec_count = rec_count; a.rec_idx = rec_idx;
+  a.out_m = out_m; a.out_n = out_n; a.out_clause = out_clause; a.out_term = out_term; a.out_contrib = out_contrib;
+  HIPC(urcco::launch_explain(s->stream, s->n_cu, a));
+  return URCCO_OK;
+}
+
 int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double* x, double* out) {
   if (!s || n < 0 || n_cols < 1 || n_cols > 1024 || !out || (n > 0 && !x) || n * (int64_t)n_cols > 0x7fffffffll)
     return fail(URCCO_BAD_ARG, "urcco_dev_tree_sum: bad argument");

@@ -297,6 +297,33 @@ class DeviceSession:
         return (hits[: n * len(ks)].view(shape), ap[: n * len(ks)].view(shape), ndcg[: n * len(ks)].view(shape) if ndcg is not None else None, s_i,
                 s_f[: 2 * len(ks)] if s_f is not None else None)
 
+    def explain(self, count: torch.Tensor, idx: torch.Tensor, clauses, max_terms: int, n_items: int):
+        """urcco_dev_explain (decision D30): the terms behind every score of the recommendation table (count int32 [n], idx int32 [n, num], as recommend
+        leaves them).  clauses: (n_cols, boost, ind_row_ptr, ind_col_idx, q_row_ptr, q_col_idx, weight | None) per should-clause of the recommend call, in
+        its order -- the CSR of the matrix whose CSC that call was given, the same boost, query rows and uint32 weight array.
+        Returns (m int64 [n, num, n_clauses], n int32 [n, num], clause int32 [n, num, max_terms], term int32 [n, num, max_terms], contrib float64
+        [n, num, max_terms]), allocated zeroed: m = the exact per-clause sums in units of 2^-15, whose fold ((0.0 + boost_0 m_0 2^-15) + ...) is the score
+        bit for bit; the first n[q, j] listed terms are the best matches in the order (contrib desc, clause asc, term asc).  Enqueues, does not synchronise."""
+        n = int(count.numel())
+        num = int(idx.shape[1]) if idx.dim() == 2 else (int(idx.numel()) // n if n else 1)
+        max_terms = int(max_terms)
+        arr = (_lib.ExplainClause * max(len(clauses), 1))()
+        for c, (n_cols, boost, rp, ci, qrp, qci, w) in enumerate(clauses):
+            if w is not None and (w.dtype != torch.uint32 or w.numel() < int(n_cols)):
+                raise ValueError(f"clauses[{c}]: the weight is a uint32 tensor of at least n_cols = {int(n_cols)} entries")
+            arr[c].n_cols, arr[c].boost = int(n_cols), float(boost)
+            arr[c].m_row_ptr, arr[c].m_col_idx, arr[c].q_row_ptr, arr[c].q_col_idx, arr[c].weight = _ptr(rp), _ptr(ci), _ptr(qrp), _ptr(qci), _ptr(w)
+        slots, nc, mt = n * max(num, 0), len(clauses), max(max_terms, 0)
+        m = torch.zeros(max(slots * nc, 1), dtype=torch.int64, device=self.device)
+        o_n = torch.zeros(max(slots, 1), dtype=torch.int32, device=self.device)
+        o_clause = torch.zeros(max(slots * mt, 1), dtype=torch.int32, device=self.device)
+        o_term = torch.zeros(max(slots * mt, 1), dtype=torch.int32, device=self.device)
+        o_contrib = torch.zeros(max(slots * mt, 1), dtype=torch.float64, device=self.device)
+        self._check(self.lib.urcco_dev_explain(self.handle, n, n_items, num, _ptr(count), _ptr(idx), arr, len(clauses), max_terms, _ptr(m), _ptr(o_n), _ptr(o_clause),
+                                              _ptr(o_term), _ptr(o_contrib)))
+        return (m[: slots * nc].view(n, num, nc), o_n[:slots].view(n, num), o_clause[: slots * mt].view(n, num, mt), o_term[: slots * mt].view(n, num, mt),
+                o_contrib[: slots * mt].view(n, num, mt))
+
     def tree_sum(self, x: torch.Tensor) -> torch.Tensor:
         """urcco_dev_tree_sum: the pairwise sums of decision D19 over the rows of a contiguous float64 [n, n_cols] tensor, one per column: what
         `while x.size > 1: x = x[0::2] + x[1::2]` leaves of each column padded with +0.0 to a power of two.  Enqueues, does not synchronise."""

@@ -321,8 +321,29 @@ def _max_query_events(ap) -> int:
     return ap.maxQueryEvents if ap.maxQueryEvents is not None else 100
 
 
+_CLAUSE_KINDS = {"user": "user", "item": "item", "field": "field", "set": "itemSet"}
+
+
+def _explain_max(explain) -> Optional[int]:
+    if explain is None:
+        return None
+    if isinstance(explain, bool) or int(explain) != explain or not 1 <= int(explain) <= _lib.EXPLAIN_MAX_TERMS:
+        raise ValueError(f"explain: None or the number of terms to list per item, 1..{_lib.EXPLAIN_MAX_TERMS}")
+    return int(explain)
+
+
+def _term_name(model: DeviceModel, m, term: int):
+    """the item id of a column of an indicator matrix, or the value of a column of a property matrix"""
+    if isinstance(m, _Property):
+        inv = m.__dict__.get("_inverse")
+        if inv is None:
+            inv = m.__dict__["_inverse"] = {v: k for k, v in m.values.items()}
+        return inv.get(term)
+    return m.column_ids.inverse(term) if m.column_ids is not None else term
+
+
 def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host",
-                  term_weights=None) -> List[dict]:
+                  term_weights=None, explain: Optional[int] = None) -> List[dict]:
     """URAlgorithm.predict for a list of query dicts: [{"itemScores": [{"item", "score"}, ...]}, ...] in the order of `queries`.
     history: user -> {event name: [item ids, oldest first]} (the event store's view of the user), or a history.DeviceHistory: the event streams
     resident on the device.  With a DeviceHistory the user-history term rows (the ("user", ev) clauses, or the ("hist", ev) ANY rules under
@@ -341,8 +362,14 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
     clause out): an all-empty clause adds 0.0 * boost, so every score stays bit-identical to the host route, but the 16-clause limit of a call can be
     reached earlier.
     term_weights: None (the algorithm's termWeights parameter, absent: every matching term scores 1 -- the calls are then the unweighted ones), "none",
-    "idf" (DeviceModel.term_weights) or {event or property name: uint32 device tensor}: decision D20, see the module's head."""
+    "idf" (DeviceModel.term_weights) or {event or property name: uint32 device tensor}: decision D20, see the module's head.
+    explain: None (nothing changes) or E in 1..64 (decision D30): one urcco_dev_explain call follows the recommend call of every group, over the same
+    clauses, boosts and weight arrays with the matrices' CSR in place of their CSC, and every item score gains
+    "because": [{"clause": "user" | "item" | "field" | "itemSet", "name": event type or property, "term": item id or property value, "weight": boost
+    times the term's weight}, ...] -- its at most E strongest matching terms, strongest first, ties by clause order, then column id: the user's own past
+    items, the query item's correlators, the matched property values.  A backfill item gets []."""
     tw = _term_weights(algo, model, term_weights)
+    explain = _explain_max(explain)
     if item_rows not in ("host", "device"):
         raise ValueError(f"item_rows must be 'host' or 'device', got {item_rows!r}")
     dev_items = item_rows == "device"
@@ -540,11 +567,21 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
                     rules.append((_lib.RULE_NONE if rk[0] == "none" else _lib.RULE_ANY, m.n_cols, m.row_ptr, m.col_idx, qrp, qci))
         count, idx, score, _ = model.sess.recommend(len(members), model.n_items, clauses, fetch, excl, mask_t, model.fill_order, flags, stats=False, rules=rules,
                                                     weights=weights)
+        why = None
+        if explain is not None and clauses:                                                     # the same clauses over the CSR of their matrices (D30)
+            why = model.sess.explain(count, idx, [(c.n_cols, boost, c.row_ptr, c.col_idx, cl[4], cl[5], None if weights is None else weights[k])
+                                                  for k, ((_, c, boost), cl) in enumerate(zip(slots, clauses))], explain, model.n_items)
         model.sess.synchronize()
         count, idx, score = count.cpu().numpy(), idx.cpu().numpy(), score.cpu().numpy()
+        if why is not None:
+            w_n, w_clause, w_term, w_contrib = (t.cpu().numpy() for t in why[1:])
         for r, n in enumerate(members):
             start, num = plans[n][2], plans[n][3]
             results[n] = {"itemScores": [{"item": model.item_name(int(idx[r, j])), "score": float(score[r, j])} for j in range(start, min(int(count[r]), start + num))]}
+            for j, row in enumerate(results[n]["itemScores"] if explain is not None else (), start):
+                row["because"] = [] if why is None else [
+                    {"clause": _CLAUSE_KINDS[slots[k][0][0]], "name": slots[k][0][1], "term": _term_name(model, slots[k][1], int(w_term[r, j, x])),
+                     "weight": float(w_contrib[r, j, x])} for x in range(int(w_n[r, j])) for k in (int(w_clause[r, j, x]),)]
     return results
 
 
@@ -633,7 +670,8 @@ def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = Non
 
 
 def user_recommendations(algo, model: DeviceModel, history, users=None, num: Optional[int] = None, event_names: Optional[Sequence[str]] = None,
-                         user_bias: Optional[float] = None, chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None):
+                         user_bias: Optional[float] = None, chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None,
+                         explain: Optional[int] = None):
     """The per-user table, the user-side twin of similar_items: row n is what batch_predict answers to {"user": users[n]} (with "eventNames", "num" and
     "userBias" where given) over the same DeviceHistory -- the same items in the same order with the same scores -- as three device tensors (count
     int32 [n], idx int32 [n, num], score float64 [n, num]); entries behind count[n] are -1 / 0.0.  No Python work per user: the queries go `chunk`
@@ -644,9 +682,13 @@ def user_recommendations(algo, model: DeviceModel, history, users=None, num: Opt
     the query's `eventNames`, default the model's event types.  user_bias > 0: one should-clause per event type over the user's recent items, boost
     = the bias; user_bias < 0: the rows are ANY rules instead (a model built with item properties, {} will do) -- every query carries them, so an
     unknown user or an event without history matches nothing, as in batch_predict.  The blacklist events' exclusions, backfill, recsModel, item_mask
-    the available / expire date rule around now_ms and term_weights are those of batch_predict."""
+    the available / expire date rule around now_ms and term_weights are those of batch_predict.
+    explain: None, or E in 1..64 (decision D30): the result is (count, idx, score, n, clause, term, contrib, names) -- after the three tensors above, n int32
+    [n, num] = the listed terms of a slot, clause / term int32 and contrib float64 [n, num, E] = their clause (an index into names, the list of
+    ("user", event type) in clause order), column id and boost x weight, in batch_predict's order; zeros behind n.  userBias < 0 leaves no clause: n = 0."""
     from .history import DeviceHistory
     tw = _term_weights(algo, model, term_weights)
+    explain = _explain_max(explain)
     if not isinstance(history, DeviceHistory):
         raise ValueError("user_recommendations needs a history.DeviceHistory (the event streams resident on the device)")
     dh = history
@@ -696,6 +738,11 @@ def user_recommendations(algo, model: DeviceModel, history, users=None, num: Opt
     count = torch.zeros(n, dtype=torch.int32, device=dev)
     idx = torch.full((n, num), -1, dtype=torch.int32, device=dev)
     score = torch.zeros((n, num), dtype=torch.float64, device=dev)
+    names = [("user", c.name) for c in model.correlators if c.name in hist_events] if bias >= 0 else []
+    if explain is not None:
+        w_n = torch.zeros((n, num), dtype=torch.int32, device=dev)
+        w_clause, w_term = (torch.zeros((n, num, explain), dtype=torch.int32, device=dev) for _ in range(2))
+        w_contrib = torch.zeros((n, num, explain), dtype=torch.float64, device=dev)
     for lo in range(0, n, chunk):
         q = q_all[lo:lo + chunk].contiguous()
         m = int(q.numel())
@@ -716,8 +763,15 @@ def user_recommendations(algo, model: DeviceModel, history, users=None, num: Opt
             clauses = [(c.n_cols, _boost(bias), c.col_ptr, c.row_idx) + hist_rows[c.name] for c in model.correlators if c.name in hist_rows]
             weights = None if tw is None else [tw.get(c.name) for c in model.correlators if c.name in hist_rows]
         c, i, s, _ = sess.recommend(m, model.n_items, clauses, num, excl, mask_t, model.fill_order, flags, stats=False, rules=rules, weights=weights)
+        if explain is not None and clauses:                                                     # outputs behind n come back as zeros
+            by = [x for x in model.correlators if x.name in hist_rows]
+            _, w_n[lo:lo + m], w_clause[lo:lo + m], w_term[lo:lo + m], w_contrib[lo:lo + m] = sess.explain(
+                c, i, [cl[:2] + (x.row_ptr, x.col_idx) + cl[4:] + (None if weights is None else weights[k],) for k, (cl, x) in enumerate(zip(clauses, by))],
+                explain, model.n_items)
         live = torch.arange(num, device=dev)[None, :] < c[:, None]
         count[lo:lo + m] = c
         idx[lo:lo + m] = torch.where(live, i, idx[lo:lo + m])
         score[lo:lo + m] = torch.where(live, s, score[lo:lo + m])
+    if explain is not None:
+        return count, idx, score, w_n, w_clause, w_term, w_contrib, names
     return count, idx, score

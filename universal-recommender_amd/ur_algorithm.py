@@ -268,16 +268,17 @@ class URAlgorithm:
 
 
     def batch_predict(self, model, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host",
-                      term_weights=None) -> List[dict]:
+                      term_weights=None, explain: Optional[int] = None) -> List[dict]:
         """URAlgorithm.predict (:484-535) for a batch of queries against a recommend.DeviceModel: user history, similar-item and itemSet
         queries, blacklists, backfill by rank and -- for a model built with item properties -- the business rules (fields, dateRange, available /
         expire dates around now_ms, negative biases); see recommend.batch_predict for what is mirrored and what is left out.  history: the dict
         user -> {event: [items, oldest first]} or a history.DeviceHistory (the event streams resident on the device).  item_rows="device": the query
         items' own indicator lists are cut on the device instead of planned one by one from a host copy of the matrices.  term_weights (here and in the
         methods below): None = the algorithm parameter termWeights (absent: every matching term scores 1), "none", "idf" or {event or property name:
-        uint32 device tensor} -- decision D20, see recommend.py."""
+        uint32 device tensor} -- decision D20, see recommend.py.  explain=E (here, in predict and in user_recommendations; None: nothing changes): every
+        item score gains "because", the at most E terms behind it (decision D30)."""
         from .recommend import batch_predict
-        return batch_predict(self, model, queries, history, item_mask, now_ms, item_rows, term_weights)
+        return batch_predict(self, model, queries, history, item_mask, now_ms, item_rows, term_weights, explain)
 
     def similar_items(self, model, items=None, num: Optional[int] = None, item_bias: Optional[float] = None, return_self: Optional[bool] = None,
                       chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None):
@@ -287,11 +288,11 @@ class URAlgorithm:
         return similar_items(self, model, items, num, item_bias, return_self, chunk, item_mask, now_ms, term_weights)
 
     def user_recommendations(self, model, history, users=None, num: Optional[int] = None, event_names=None, user_bias: Optional[float] = None,
-                             chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None):
+                             chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None, explain: Optional[int] = None):
         """The per-user table of `users` (None: every user id of the history.DeviceHistory) as device tensors (count, idx, score): row n is what
         batch_predict answers to {"user": users[n]} over the same history; see recommend.user_recommendations."""
         from .recommend import user_recommendations
-        return user_recommendations(self, model, history, users, num, event_names, user_bias, chunk, item_mask, now_ms, term_weights)
+        return user_recommendations(self, model, history, users, num, event_names, user_bias, chunk, item_mask, now_ms, term_weights, explain)
 
     def evaluate(self, model, train, test, ks=(1, 5, 10, 20), num: Optional[int] = None, event_names=None, truth_event: Optional[str] = None,
                  chunk: int = 65536, user_bias: Optional[float] = None, item_mask=None, now_ms: Optional[int] = None, term_weights=None):
@@ -306,8 +307,8 @@ class URAlgorithm:
         from .properties import DeviceProperties
         return DeviceProperties(model.sess, model, self.dateNames).apply(events)
 
-    def predict(self, model, query: dict, history, item_mask=None, now_ms: Optional[int] = None, term_weights=None) -> dict:
-        return self.batch_predict(model, [query], history, item_mask, now_ms, term_weights=term_weights)[0]
+    def predict(self, model, query: dict, history, item_mask=None, now_ms: Optional[int] = None, term_weights=None, explain: Optional[int] = None) -> dict:
+        return self.batch_predict(model, [query], history, item_mask, now_ms, term_weights=term_weights, explain=explain)[0]
 
     def train_events_on_device(self, trainingData, sess) -> List[Tuple[str, IndexedDataset]]:
         """Preparator.prepare + URAlgorithm.calcAll without leaving the GPU in between: the event streams are hashed on
