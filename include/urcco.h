@@ -472,13 +472,29 @@ int urcco_dev_pop_counts(urcco_session* s, int64_t n_events, const int32_t* item
  * items, strongest rank first (`sort: [_score desc, popRank desc]`, :730-738) -- without fill_order the item index.  Items nothing hit take part with score 0
  * (the match_all clause of :668-681) unless URCCO_REC_NO_BACKFILL is set.  Ids and scores are reproducible bit for bit.
  * Enqueues on the session's stream, does not synchronise; scratch from the session's arena.  URCCO_BAD_ARG: num outside 1..URCCO_REC_MAX_NUM, n_clauses
- * outside 0..URCCO_REC_MAX_CLAUSES (0 = pure backfill), a boost that is not positive and finite, a NULL half of a pointer pair. */
+ * outside 0..URCCO_REC_MAX_CLAUSES (0 = pure backfill), a boost that is not positive and finite, a NULL half of a pointer pair, a flag bit other than
+ * the three below.
+ * Accumulator classes (DESIGN.md decision D31).  A query's work bound w(q) = the summed lengths of the indicator columns its terms name + its exclusions
+ * bounds the distinct items it touches.  w <= 3072: a hash table in LDS.  Everything else: a dense accumulator of n_items slots per resident block (20 bytes
+ * per item and block, 24 weighted, at most 512 MiB -- so the number of resident blocks falls with the catalogue).  URCCO_REC_HASHED adds a third class
+ * between the two: a query beyond the LDS class with w <= URCCO_REC_HASH_LIMIT runs on an open-addressing table of 2^URCCO_REC_HASH_CAP_LOG2 slots per
+ * resident block in arena scratch (load factor <= 0.75, so it cannot fill; home slot (item * 2654435761u) >> (32 - URCCO_REC_HASH_CAP_LOG2), linear probing
+ * that wraps).  Its scratch is  blocks * (2^17 * 8 + 98 304 * 12) bytes = 2.125 MiB per block (2^17 * 12 + ...: 2.625 MiB weighted)  with
+ *   blocks = min(2 * compute units, n_queries, 512 MiB / bytes per block)      -- at most 240, 195 weighted; n_items is not in it,
+ * beside the dense class's scratch, which keeps its sizing for the queries beyond the hashed limit.  URCCO_REC_HASHED_AUTO turns URCCO_REC_HASHED on for the
+ * call exactly when the dense class would get fewer resident blocks than the hashed class.  Counts, ids and score bits do not depend on the class.  Both flags
+ * are accepted by urcco_dev_recommend, urcco_dev_recommend_rules and urcco_dev_recommend_weighted. */
 #define URCCO_REC_MAX_CLAUSES 16
 #define URCCO_REC_MAX_NUM 256
 #define URCCO_REC_NO_BACKFILL 1
-#define URCCO_REC_STATS_LEN 8   /* [0] queries served by the LDS class, [1] by the global-accumulator class,
+#define URCCO_REC_HASHED 0x100
+#define URCCO_REC_HASHED_AUTO 0x200
+#define URCCO_REC_HASH_CAP_LOG2 17
+#define URCCO_REC_HASH_LIMIT 98304   /* 3/4 of the 2^17 slots */
+#define URCCO_REC_STATS_LEN 8   /* [0] queries served by the LDS class, [1] by the global-accumulator (dense) class,
                                    [2] candidate-table overflows (invariant: 0), [3] sum of candidates,
-                                   [4] backfill steps (urcco_dev_recommend_rules with rules only, else 0), rest 0 */
+                                   [4] backfill steps (urcco_dev_recommend_rules with rules only, else 0),
+                                   [5] queries served by the hashed class (0 without URCCO_REC_HASHED); [0] + [1] + [5] == n_queries; rest 0 */
 typedef struct urcco_rec_clause {
   int32_t n_cols;               /* columns of I_c = items of the clause's event type */
   int32_t reserved;

@@ -1,0 +1,11 @@
+"""The hashed accumulator class of urcco_dev_recommend (URCCO_REC_HASHED, decision D31) on the GPU: every case of tests/recommend_hashed_cases.py."""
+import pytest
+
+import recommend_hashed_cases as H
+
+pytestmark = pytest.mark.gpu
+
+
+@pytest.mark.parametrize("case", H.CASES, ids=lambda c: "-".join(map(str, c)))
+def test_hashed_class(gpu_session, monkeypatch, case):
+    getattr(H, case[0])(H.Context(gpu_session, monkeypatch), *case[1:])

@@ -28,7 +28,11 @@ that hold WEIGHT_ONE alone, whose ids and score bits must be the unweighted call
 --explain: urcco_dev_explain (decision D30, max_terms = 5) over the table the timed urcco_dev_recommend call left, its HIP-event time next to that call's; the
 fold of its per-clause sums is compared with the scores; and the host route for the same batch on this box: the copies of the indicator matrices, the
 query rows and the table, then np.intersect1d per (query, slot, clause) over the first 2000 queries, scaled to the batch.
-usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--rules] [--weights] [--device-history] [--device-items] [--evaluate] [--explain] [--no-torch]"""
+--accumulator hashed | auto: the same problem once more with URCCO_REC_HASHED / URCCO_REC_HASHED_AUTO (decision D31), its time next to the flagless call's of the
+same process, the class split stats[0] / stats[1] / stats[5], whether counts, ids and score bits equal the flagless call's, and the distribution of the work
+bound w(q) (median, p90, maximum, share above REC_HASH_LIMIT) -- what a later change of the table's capacity would rest on.  --item-scale S: the item spaces
+of the model as a fraction of BASELINE config 4's (default 0.1: 200K items; 1.0: the 2M-item catalogue).
+usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--item-scale S] [--accumulator dense|hashed|auto] [--rules] [--weights] [--device-history] [--device-items] [--evaluate] [--explain] [--no-torch]"""
 import argparse
 import os
 import sys
@@ -47,6 +51,8 @@ ap.add_argument("--queries", type=int, default=100_000)
 ap.add_argument("--chunk", type=int, default=2048)
 ap.add_argument("--reps", type=int, default=5)
 ap.add_argument("--num", type=int, default=20)
+ap.add_argument("--item-scale", type=float, default=0.1, help="item spaces as a fraction of config 4's (1.0: 2M items)")
+ap.add_argument("--accumulator", choices=sorted(_lib.REC_ACCUMULATORS), default="dense", help="also time the call with this accumulator class for the larger queries")
 ap.add_argument("--rules", action="store_true", help="also time the call under an ANY and a NONE rule")
 ap.add_argument("--weights", action="store_true", help="also time the weighted call under idf term weights")
 ap.add_argument("--device-history", action="store_true", help="also time history_bounds + history_rows against the host planning loop")
@@ -58,7 +64,7 @@ args = ap.parse_args()
 
 assert torch.cuda.is_available(), "needs the GPU: there is no CPU path to time"
 dev = torch.device("cuda", 0)
-cfg = synth.config4(args.users / 10_000_000, item_scale=0.1)
+cfg = synth.config4(args.users / 10_000_000, item_scale=args.item_scale)
 mats = [DevCsr(cfg.n_users, nc, rp, ci, int(rp[-1].item())) for (_, nc, rp, ci) in synth.generate_device(cfg, dev)]
 sess = DeviceSession(dev, _lib.load(os.environ.get("URCCO_LIB", _lib.DEFAULT_PATH)))
 K = 50
@@ -99,6 +105,28 @@ def timed(fn, reps, warm=2):
 st = stats.cpu().tolist()
 print(f"urcco_dev_recommend: {min(ms_hip):.2f} ms best, {sorted(ms_hip)[len(ms_hip) // 2]:.2f} ms median of {args.reps} ({[round(x, 2) for x in ms_hip]})")
 print(f"  class split: {st[0]} queries in the LDS class, {st[1]} in the global class; table overflows {st[2]}; candidates {st[3]} ({st[3] / nq:.0f} per query)")
+
+if args.accumulator != "dense":
+    flag = _lib.REC_ACCUMULATORS[args.accumulator]
+    (a_count, a_idx, a_score, a_stats), ms_a = timed(lambda: sess.recommend(nq, n_items, clauses, num, excl, None, fill, flag), args.reps)
+    hs = a_stats.cpu().tolist()
+    live = torch.arange(num, device=dev)[None, :] < count[:, None]
+    same = torch.equal(a_count, count) and torch.equal(torch.where(live, a_idx, 0), torch.where(live, idx, 0)) and \
+        torch.equal(torch.where(live, a_score, 0.0).view(torch.int64), torch.where(live, score, 0.0).view(torch.int64))
+    print(f"urcco_dev_recommend, accumulator = {args.accumulator}: {min(ms_a):.2f} ms best, {sorted(ms_a)[len(ms_a) // 2]:.2f} ms median of {args.reps} "
+          f"({[round(x, 2) for x in ms_a]}) -- flagless call above: {min(ms_hip):.2f} ms best, {sorted(ms_hip)[len(ms_hip) // 2]:.2f} ms median")
+    print(f"  class split: {hs[0]} LDS, {hs[5]} hashed, {hs[1]} dense (flagless: {st[0]} LDS, {st[1]} dense); table overflows {hs[2]}; candidates {hs[3]} (flagless {st[3]}); "
+          f"counts, ids and score bits equal the flagless call's: {bool(same)}")
+    w = (excl[0][1:] - excl[0][:-1]).clone()
+    for c, (_, _, cp, _, qrp, qci) in zip(model.correlators, clauses):
+        col_len = cp[1:] - cp[:-1]
+        terms = qci[: int(qrp[-1].item())].to(torch.int64)
+        rows = torch.repeat_interleave(torch.arange(nq, device=dev), qrp[1:] - qrp[:-1])
+        w.index_add_(0, rows, col_len[terms])
+    ws = torch.sort(w).values
+    print(f"  work bound w(q): median {int(ws[nq // 2].item())}, p90 {int(ws[min(nq - 1, nq * 9 // 10)].item())}, maximum {int(ws[-1].item())}; "
+          f"above REC_LDS_LIMIT = {_lib.REC_LDS_LIMIT}: {float((w > _lib.REC_LDS_LIMIT).float().mean()):.4%}, above REC_HASH_LIMIT = {_lib.REC_HASH_LIMIT}: "
+          f"{float((w > _lib.REC_HASH_LIMIT).float().mean()):.4%}")
 
 if args.rules:
     # item x value matrix of 10 values: value 0 on every second item (the filter), value 1 + i % 9 on every item (the NONE rule names value 1)

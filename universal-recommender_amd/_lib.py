@@ -48,6 +48,11 @@ DEDUP_FIRST, DEDUP_LAST = 1, 2   # urcco_dev_history_dedup (URCCO_DEDUP_*): whic
 HD_LDS = 2048          # entries of a user up to which the dedup's LDS class serves it (csrc/cco_kernels.h); the column-table class begins above
 HIST_STATS_LEN = 8    # urcco_dev_history_rows (URCCO_HIST_STATS_LEN): pairs per class, selects, exclusion rows per class, overflows
 REC_LDS_LIMIT = 3072   # work bound w(q) up to which a query runs in the LDS class (csrc/cco_kernels.h)
+REC_HASHED = 0x100        # flag (URCCO_REC_HASHED, decision D31): queries beyond the LDS class run in the hashed class up to REC_HASH_LIMIT
+REC_HASHED_AUTO = 0x200   # flag: REC_HASHED exactly when the dense class would get fewer resident blocks than the hashed class
+REC_HASH_CAP_LOG2 = 17    # slots of a block's table: home slot of an item = (item * 2654435761 mod 2^32) >> (32 - REC_HASH_CAP_LOG2), linear probing
+REC_HASH_LIMIT = 3 << (REC_HASH_CAP_LOG2 - 2)   # 98 304: the work bound w(q) up to which a query runs in the hashed class
+REC_ACCUMULATORS = {"dense": 0, "hashed": REC_HASHED, "auto": REC_HASHED_AUTO}   # the `accumulator=` argument of recommend.py -> flag
 EXCH_SIZES = 4   # int64 words of a shard's record (include/urcco.h URCCO_EXCH_SIZES)
 # bits of urcco_session_set_debug / urcco_context_set_debug: the names and values of csrc/cco_kernels.h (tests/test_c_abi_surface.py compares them)
 DBG_GATHER_ONLY = 1

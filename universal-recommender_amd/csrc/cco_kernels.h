@@ -350,6 +350,13 @@ constexpr int REC_STATS_LEN = 8;
 constexpr int REC_LDS_LIMIT = 3072;   // a query whose work bound w(q) (candidate touches + exclusions) is larger runs in the global-accumulator class
 constexpr int REC_WEIGHT_ONE = 1 << 15;  // term weights of urcco_dev_recommend_weighted (decision D20): unsigned integers in units of 2^-15 ...
 constexpr int REC_WEIGHT_MAX = 1 << 20;  // ... from 1 to 32.0
+// The hashed class (decision D31): an open-addressing table per resident block in arena scratch, sized by the query and not by the catalogue.  The capacity
+// is a compile-time constant chosen WITHOUT a measurement (2^17 slots: 2.125 MiB per block, 240 blocks in the 512 MiB budget); retuning it is a later change.
+constexpr int REC_HASHED = 0x100;        // flag: queries beyond the LDS limit whose work bound is at most the hashed limit run in the hashed class
+constexpr int REC_HASHED_AUTO = 0x200;   // flag: REC_HASHED exactly when the dense class would get fewer resident blocks than the hashed class
+constexpr int REC_HASH_CAP_LOG2 = 17;
+constexpr int REC_HASH_CAP = 1 << REC_HASH_CAP_LOG2;    // slots of a block's table
+constexpr int REC_HASH_LIMIT = REC_HASH_CAP / 4 * 3;    // most distinct items (candidates + tombstones) a query of the hashed class can hold: load factor 0.75
 struct RecClause {
   const int64_t* ind_col_ptr;  // CSC of the indicator matrix I_c (n_items x n_cols)
   const int32_t* ind_row_idx;
@@ -376,13 +383,28 @@ struct RecRule {
 };
 struct RecArgs;  // cco_recommend.h
 int32_t recommend_global_blocks(int64_t n_queries, int32_t n_items, int n_cu, bool weighted = false);
-// ctr[5], list[n_queries], pos[n_items] (only with fill_order), g_state / g_m / g_list [g_blocks * n_items] words, g_score [g_blocks * n_items] doubles: scratch.
+// The hashed class's scratch: `blocks` slices of keys / m (or m64 when weighted) [REC_HASH_CAP] and list / score [REC_HASH_LIMIT]; queries [n_queries].
+struct RecHashed {
+  int32_t limit;               // w(q) up to here (and beyond the LDS limit): hashed class (<= REC_HASH_LIMIT)
+  int32_t blocks;              // recommend_hashed_blocks
+  int32_t* queries;
+  unsigned* keys;
+  unsigned* m;                 // unweighted call
+  unsigned long long* m64;     // weighted call
+  int32_t* list;
+  double* score;
+};
+size_t recommend_hashed_block_bytes(bool weighted);
+int32_t recommend_hashed_blocks(int64_t n_queries, int n_cu, bool weighted = false);  // min(2 n_cu, n_queries, 512 MiB / bytes per block): n_items is not in it
+// ctr[8], list[n_queries], pos[n_items] (only with fill_order), g_state / g_m / g_list [g_blocks * n_items] words, g_score [g_blocks * n_items] doubles: scratch.
 // weights != NULL (host array [n_clauses] of device pointers, entries nullable): the weighted kernels; g_m64 [g_blocks * n_items] 64-bit words then takes g_m's place
+// hashed != NULL: the hashed class is on for this call (three-way binning); NULL: the two classes, decisions, lists and counters as ever
 hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t n_items, const RecClause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
                             const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
                             int32_t* out_idx, double* out_score, int64_t* stats_dev, unsigned long long* ctr, int32_t* list, int32_t* pos, int32_t g_blocks,
                             unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit = REC_LDS_LIMIT, const RecRule* rules = nullptr,
-                            int32_t n_rules = 0, const uint32_t* const* weights = nullptr, unsigned long long* g_m64 = nullptr);
+                            int32_t n_rules = 0, const uint32_t* const* weights = nullptr, unsigned long long* g_m64 = nullptr,
+                            const RecHashed* hashed = nullptr);
 hipError_t launch_idf_weights(hipStream_t st, int n_cu, int32_t n_cols, const int64_t* col_ptr, int64_t n_docs, uint32_t* out);
 
 // ---- hold-out evaluation (cco_eval.h, compiled into cco_misc.hip behind cco_recommend.h; decision D19) ----------------------

@@ -5,9 +5,16 @@
 //
 //   rec_inverse_kernel   pos[fill_order[p]] = p: the backfill position of every item
 //   rec_work_kernel      w(q) = sum_c sum_{h in T_c(q)} len(column h of I_c) + exclusions of q: the upper bound of the distinct items the query
-//                        touches; w <= REC_LIMIT goes to the LDS class (list filled from the front), everything else to the global class (from the back)
+//                        touches; w <= REC_LIMIT goes to the LDS class (list filled from the front), everything else to the global class (from the back);
+//                        with the hashed class on (REC_HASHED, decision D31) a query beyond the LDS limit with w <= REC_HASH_LIMIT goes to a list of its own
 //   rec_rows_kernel<0, R>  LDS class: a block per query, an open-addressing table keyed by the item in LDS
-//   rec_rows_kernel<1, R>  global class: the same walk on a dense per-block accumulator of n_items slots in arena scratch, cleared through its touched lists
+//   rec_rows_kernel<1, R>  global (dense) class: the same walk on a dense per-block accumulator of n_items slots in arena scratch, cleared through its touched lists
+//   rec_rows_kernel<2, R>  hashed class: the same walk on an open-addressing table of REC_HASH_CAP = 2^17 slots per resident block in arena scratch -- keys
+//                          (REC_EMPTY, REC_TOMB and item ids as in the LDS table), match counters by slot, a list of SLOTS (candidates from the front, tombstones
+//                          from the back) and the scores by candidate ordinal: 2.125 MiB per block (2.625 MiB weighted) whatever n_items is.  Home slot of an item:
+//                            (item * 2654435761u) >> (32 - REC_HASH_CAP_LOG2),  linear probing that wraps at the end of the table.
+//                          w(q) <= REC_HASH_LIMIT = 3/4 of the slots bounds the distinct items of a query, so the table cannot fill (the LDS table's argument);
+//                          at the end of a query the keys are reset through the two ends of the list, never by a sweep.  Results are the dense class's bit for bit.
 //   rec_rules_ok           R = true (urcco_dev_recommend_rules, decision D16): the per-(query, item) eligibility rules, evaluated wherever item_mask is consulted --
 //                          when an absent item is claimed (a rejected item becomes a tombstone) and per walked backfill position; R = false is the rule-free call
 // Both classes: exclusions enter first as tombstones, masked-out items become tombstones when they are first hit; clause by clause the hits raise a 32-bit
@@ -16,7 +23,8 @@
 // the num-th best candidate, the (at most num) winners are ranked by counting; then the backfill walks fill_order from the front.
 //   rec_rows_kernel<., ., true>  W = true (urcco_dev_recommend_weighted, decision D20): a hit of term h raises the counter by the clause's integer weight w_c[h]
 //                          (units of 2^-15, 1 .. REC_WEIGHT_MAX; a clause without an array: REC_WEIGHT_ONE) and the fold adds boost * ((double)M * 2^-15); the LDS
-//                          class keeps its 32-bit counters, the global class counts in a 64-bit array of its own (g_m64) in place of g_m; W = false is the code above
+//                          class keeps its 32-bit counters, the global and the hashed class count in a 64-bit array of their own (g_m64 / h.m64) in place of
+//                          g_m / h.m; W = false is the code above
 //   rec_idf_kernel         urcco_dev_idf_weights: w[h] = clamp(llrint(log(1 + (n_docs - df + 0.5) / (df + 0.5)) * 2^15), 1, REC_WEIGHT_MAX), a thread per column
 #pragma once
 
@@ -32,6 +40,13 @@ static_assert(REC_LIMIT * 4 <= REC_CAP * 3 && REC_LIMIT <= 65536, "load factor o
 // the 32-bit s_m stays (the kernel clamps every loaded weight to 1 .. REC_WEIGHT_MAX, so a bad array cannot break the bound).  Global class: no cap on the
 // terms, so its weighted form counts in 64 bits: fewer than 2^43 hits of at most 2^20 each.
 static_assert((unsigned long long)REC_LIMIT * (unsigned long long)REC_WEIGHT_MAX < (1ull << 32), "weighted 32-bit LDS match counters: REC_LIMIT hits of REC_WEIGHT_MAX each");
+// Hashed class: w(q) <= REC_HASH_LIMIT bounds the hits.  Unweighted, a counter holds at most REC_HASH_LIMIT < 2^32: 32-bit counters (h.m).  Weighted,
+// REC_HASH_LIMIT * REC_WEIGHT_MAX = 98 304 * 2^20 exceeds 2^32: that instantiation counts in 64 bits (h.m64), as the dense class does.
+static_assert(REC_HASH_LIMIT * 4ll <= REC_HASH_CAP * 3ll && REC_HASH_CAP_LOG2 < 31, "load factor of the hashed table; 31-bit slot numbers in an int32 list");
+static_assert((unsigned long long)REC_HASH_LIMIT < (1ull << 32), "unweighted hashed class: 32-bit match counters hold REC_HASH_LIMIT hits of 1");
+static_assert((unsigned long long)REC_HASH_LIMIT * (unsigned long long)REC_WEIGHT_MAX >= (1ull << 32) &&
+                  (unsigned long long)REC_HASH_LIMIT * (unsigned long long)REC_WEIGHT_MAX < (1ull << 63),
+              "weighted hashed class: REC_HASH_LIMIT hits of REC_WEIGHT_MAX overflow 32 bits, so it relies on the 64-bit counters");
 constexpr double REC_WEIGHT_UNIT = 1.0 / (double)REC_WEIGHT_ONE;  // 2^-15, exact
 constexpr unsigned REC_EMPTY = 0xffffffffu; // (item ids are < 2^31 - 1)
 constexpr unsigned REC_TOMB = 0x80000000u;  // slot of an item that may not be returned
@@ -48,7 +63,8 @@ struct RecArgs {
   const int32_t* fill_order;
   const int32_t* pos;         // nullable: backfill position per item (NULL: the item index)
   int32_t* list;              // [n_queries]: LDS-class queries from the front, global-class queries from the back
-  unsigned long long* ctr;    // [5]: queries of the LDS class, of the global class, table overflows, candidates, backfill steps (only counted under rules)
+  unsigned long long* ctr;    // [8]: queries of the LDS class, of the global class, table overflows, candidates, backfill steps (only counted under rules),
+                              //      queries of the hashed class
   int32_t* out_count;
   int32_t* out_idx;
   double* out_score;
@@ -63,6 +79,8 @@ struct RecArgs {
   // read by the <., ., true> instantiations only (urcco_dev_recommend_weighted)
   const uint32_t* w[REC_MAX_CLAUSES];  // per clause: [n_cols] term weights in units of 2^-15, or NULL = REC_WEIGHT_ONE throughout
   unsigned long long* g_m64;           // global class: the 64-bit match counters, g_blocks slices of n_items, zero between queries (takes the place of g_m)
+  // hashed class (h.queries == NULL: the class is off): h.blocks slices; between queries every key is REC_EMPTY and every counter zero
+  RecHashed h;
 };
 static_assert(sizeof(RecArgs) <= 4096, "kernel arguments: the clause and rule tables travel by value");
 
@@ -91,6 +109,7 @@ __global__ __launch_bounds__(REC_THREADS) void rec_work_kernel(RecArgs a) {
     if (a.excl_row_ptr) w += a.excl_row_ptr[q + 1] - a.excl_row_ptr[q];
     if (lane == 0) {
       if (w <= a.lds_limit) a.list[atomicAdd(&a.ctr[0], 1ull)] = (int32_t)q;
+      else if (a.h.queries && w <= a.h.limit) a.h.queries[atomicAdd(&a.ctr[5], 1ull)] = (int32_t)q;
       else a.list[a.n_queries - 1 - (int64_t)atomicAdd(&a.ctr[1], 1ull)] = (int32_t)q;
     }
   }
@@ -166,12 +185,56 @@ __device__ __forceinline__ bool rec_lds_has(const unsigned* keys, unsigned item)
   return false;
 }
 
-template <bool DENSE, bool RULES, bool WEIGHTED>
+// ---- the hashed class's table: the LDS table's protocol on a slice of global memory that one block owns ----
+__device__ __forceinline__ unsigned rec_hash_home(unsigned item) { return (item * 2654435761u) >> (32 - REC_HASH_CAP_LOG2); }
+
+// Slot of `item` in the block's table, or -1 when the table is full (err).  An absent item is claimed -- as a candidate when `live`, the mask and the rules
+// admit it, else as a tombstone; *claimed: this lane won the slot and owes the list its entry; *tomb: the slot holds an item that may not be returned.
+template <bool RULES>
+__device__ __forceinline__ int rec_hash_touch(unsigned* keys, unsigned item, bool live, const uint8_t* __restrict__ mask, bool* claimed, bool* tomb,
+                                              unsigned long long* err, const RecArgs& a, int64_t q) {
+  unsigned h = rec_hash_home(item);
+  for (int probe = 0; probe < REC_HASH_CAP; ++probe) {
+    unsigned k = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (k == REC_EMPTY) {
+      const bool ok = live && (!mask || mask[item] != 0) && rec_rules_ok<RULES>(a, q, (int32_t)item);
+      k = atomicCAS(&keys[h], REC_EMPTY, ok ? item : (item | REC_TOMB));
+      if (k == REC_EMPTY) {
+        *claimed = true;
+        *tomb = !ok;
+        return (int)h;
+      }
+    }
+    if ((k & ~REC_TOMB) == item) {
+      *tomb = (k & REC_TOMB) != 0;
+      return (int)h;
+    }
+    h = (h + 1) & (REC_HASH_CAP - 1);
+  }
+  atomicAdd(err, 1ull);
+  return -1;
+}
+// is the item in the block's table (candidate or tombstone)?  The global twin of rec_lds_has.
+__device__ __forceinline__ bool rec_hash_has(const unsigned* keys, unsigned item) {
+  unsigned h = rec_hash_home(item);
+  for (int probe = 0; probe < REC_HASH_CAP; ++probe) {
+    const unsigned k = keys[h];
+    if (k == REC_EMPTY) return false;
+    if ((k & ~REC_TOMB) == item) return true;
+    h = (h + 1) & (REC_HASH_CAP - 1);
+  }
+  return false;
+}
+
+// CLASS: 0 = LDS, 1 = dense (global), 2 = hashed
+template <int CLASS, bool RULES, bool WEIGHTED>
 __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
-  __shared__ unsigned s_keys[DENSE ? 1 : REC_CAP];
-  __shared__ unsigned s_m[DENSE ? 1 : REC_CAP];
-  __shared__ unsigned short s_cand[DENSE ? 1 : REC_LIMIT];  // slot of every candidate
-  __shared__ double s_score[DENSE ? 1 : REC_LIMIT];         // by candidate ordinal
+  static_assert(CLASS >= 0 && CLASS <= 2, "0 = LDS, 1 = dense, 2 = hashed");
+  constexpr bool LDS = CLASS == 0, DENSE = CLASS == 1, HASHED = CLASS == 2;
+  __shared__ unsigned s_keys[LDS ? REC_CAP : 1];
+  __shared__ unsigned s_m[LDS ? REC_CAP : 1];
+  __shared__ unsigned short s_cand[LDS ? REC_LIMIT : 1];  // slot of every candidate
+  __shared__ double s_score[LDS ? REC_LIMIT : 1];         // by candidate ordinal
   __shared__ SelScratch s_select;
   __shared__ unsigned s_ncand, s_ntomb, s_nwin;
   __shared__ unsigned s_wcnt[REC_NW];
@@ -189,14 +252,20 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
   unsigned long long* g_m64 = DENSE && WEIGHTED ? a.g_m64 + (size_t)blockIdx.x * (size_t)n_items : nullptr;
   int32_t* g_list = DENSE ? a.g_list + (size_t)blockIdx.x * (size_t)n_items : nullptr;
   double* g_score = DENSE ? a.g_score + (size_t)blockIdx.x * (size_t)n_items : nullptr;
-  const long long n_mine = (long long)a.ctr[DENSE ? 1 : 0];
+  unsigned* h_keys = HASHED ? a.h.keys + (size_t)blockIdx.x * (size_t)REC_HASH_CAP : nullptr;
+  unsigned* h_m = HASHED && !WEIGHTED ? a.h.m + (size_t)blockIdx.x * (size_t)REC_HASH_CAP : nullptr;
+  unsigned long long* h_m64 = HASHED && WEIGHTED ? a.h.m64 + (size_t)blockIdx.x * (size_t)REC_HASH_CAP : nullptr;
+  int32_t* h_list = HASHED ? a.h.list + (size_t)blockIdx.x * (size_t)REC_HASH_LIMIT : nullptr;
+  double* h_score = HASHED ? a.h.score + (size_t)blockIdx.x * (size_t)REC_HASH_LIMIT : nullptr;
+  const long long n_mine = (long long)a.ctr[DENSE ? 1 : HASHED ? 5 : 0];
+  constexpr unsigned CAND_MAX_FIXED = HASHED ? (unsigned)REC_HASH_LIMIT : (unsigned)REC_LIMIT;  // most candidates of the two table classes
 
-  if (!DENSE)
+  if (LDS)
     for (int s = tid; s < REC_CAP; s += REC_THREADS) s_m[s] = 0;  // every fold returns the counters to zero
 
   for (long long at = blockIdx.x; at < n_mine; at += gridDim.x) {
-    const int64_t q = DENSE ? a.list[a.n_queries - 1 - at] : a.list[at];
-    if (!DENSE)
+    const int64_t q = DENSE ? a.list[a.n_queries - 1 - at] : HASHED ? a.h.queries[at] : a.list[at];
+    if (LDS)
       for (int s = tid; s < REC_CAP; s += REC_THREADS) s_keys[s] = REC_EMPTY;
     if (tid == 0) { s_ncand = 0; s_ntomb = 0; s_nwin = 0; }
     __syncthreads();
@@ -224,6 +293,25 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
           if (WEIGHTED) atomicAdd(&g_m64[item], (unsigned long long)wt);
           else atomicAdd(&g_m[item], 1u);
         }
+      } else if (HASHED) {
+        bool claimed = false, tomb = false;
+        const int slot = rec_hash_touch<RULES>(h_keys, (unsigned)item, true, mask, &claimed, &tomb, &a.ctr[2], a, q);
+        if (slot < 0) return;
+        if (claimed) {  // the two ends of the list cannot meet: candidates + tombstones <= w(q) <= REC_HASH_LIMIT
+          const unsigned j = atomicAdd(tomb ? &s_ntomb : &s_ncand, 1u);
+          if (j >= (unsigned)REC_HASH_LIMIT) {
+            atomicAdd(&a.ctr[2], 1ull);
+          } else if (tomb) {
+            h_list[REC_HASH_LIMIT - 1 - (int32_t)j] = slot;
+          } else {
+            h_list[j] = slot;
+            h_score[j] = 0.0;
+          }
+        }
+        if (!tomb) {
+          if (WEIGHTED) atomicAdd(&h_m64[slot], (unsigned long long)wt);
+          else atomicAdd(&h_m[slot], 1u);
+        }
       } else {
         bool fresh = false;
         const int slot = rec_lds_touch<RULES>(s_keys, (unsigned)item, true, mask, &fresh, &a.ctr[2], a, q);
@@ -249,6 +337,14 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
         if ((unsigned)item >= (unsigned)n_items) continue;
         if (DENSE) {
           if (atomicCAS(&g_state[item], 0u, 2u) == 0) g_list[n_items - 1 - (int32_t)atomicAdd(&s_ntomb, 1u)] = item;
+        } else if (HASHED) {
+          bool claimed = false, tomb = false;
+          const int slot = rec_hash_touch<RULES>(h_keys, (unsigned)item, false, mask, &claimed, &tomb, &a.ctr[2], a, q);
+          if (claimed) {
+            const unsigned j = atomicAdd(&s_ntomb, 1u);
+            if (j < (unsigned)REC_HASH_LIMIT) h_list[REC_HASH_LIMIT - 1 - (int32_t)j] = slot;
+            else atomicAdd(&a.ctr[2], 1ull);
+          }
         } else {
           bool fresh = false;
           (void)rec_lds_touch<RULES>(s_keys, (unsigned)item, false, mask, &fresh, &a.ctr[2], a, q);
@@ -277,7 +373,7 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
         }
       }
       __syncthreads();
-      const unsigned nc = s_ncand < (unsigned)(DENSE ? n_items : REC_LIMIT) ? s_ncand : (unsigned)(DENSE ? n_items : REC_LIMIT);
+      const unsigned nc = s_ncand < (DENSE ? (unsigned)n_items : CAND_MAX_FIXED) ? s_ncand : (DENSE ? (unsigned)n_items : CAND_MAX_FIXED);
       const double boost = cl.boost;
       for (unsigned j = tid; j < nc; j += REC_THREADS) {
         if (DENSE && WEIGHTED) {  // (the translation unit is compiled with -ffp-contract=off: product, then sum, one rounding each)
@@ -288,6 +384,14 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
           const int32_t item = g_list[j];
           const unsigned m = g_m[item];
           if (m) { g_score[j] = g_score[j] + boost * (double)m; g_m[item] = 0; }
+        } else if (HASHED && WEIGHTED) {
+          const int32_t slot = h_list[j];
+          const unsigned long long m = h_m64[slot];
+          if (m) { h_score[j] = h_score[j] + boost * ((double)m * REC_WEIGHT_UNIT); h_m64[slot] = 0; }
+        } else if (HASHED) {
+          const int32_t slot = h_list[j];
+          const unsigned m = h_m[slot];
+          if (m) { h_score[j] = h_score[j] + boost * (double)m; h_m[slot] = 0; }
         } else {
           const unsigned slot = s_cand[j];
           const unsigned m = s_m[slot];
@@ -297,9 +401,9 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
       __syncthreads();
     }
 
-    const unsigned nc = s_ncand < (unsigned)(DENSE ? n_items : REC_LIMIT) ? s_ncand : (unsigned)(DENSE ? n_items : REC_LIMIT);
-    auto cand_item = [&](unsigned j) -> int32_t { return DENSE ? g_list[j] : (int32_t)s_keys[s_cand[j]]; };
-    auto cand_score = [&](unsigned j) -> double { return DENSE ? g_score[j] : s_score[j]; };
+    const unsigned nc = s_ncand < (DENSE ? (unsigned)n_items : CAND_MAX_FIXED) ? s_ncand : (DENSE ? (unsigned)n_items : CAND_MAX_FIXED);
+    auto cand_item = [&](unsigned j) -> int32_t { return DENSE ? g_list[j] : HASHED ? (int32_t)h_keys[h_list[j]] : (int32_t)s_keys[s_cand[j]]; };
+    auto cand_score = [&](unsigned j) -> double { return DENSE ? g_score[j] : HASHED ? h_score[j] : s_score[j]; };
     auto item_pos = [&](int32_t item) -> int32_t { return pos_of ? pos_of[item] : item; };
 
     // ---- selection: threshold key (thi, tlo) = the num-th largest of (score bits, ~position); every candidate when there are no more than num ----
@@ -346,7 +450,7 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
         if (p < n_items) {
           item = a.fill_order ? a.fill_order[p] : (int32_t)p;
           ok = (unsigned)item < (unsigned)n_items && (!mask || mask[item] != 0);
-          if (ok) ok = DENSE ? g_state[item] == 0 : !rec_lds_has(s_keys, (unsigned)item);
+          if (ok) ok = DENSE ? g_state[item] == 0 : HASHED ? !rec_hash_has(h_keys, (unsigned)item) : !rec_lds_has(s_keys, (unsigned)item);
           if (RULES && ok) ok = rec_rules_ok<RULES>(a, q, item);
         }
         ++steps;
@@ -378,13 +482,18 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
       const unsigned ntomb = s_ntomb;
       for (unsigned j = tid; j < ntomb; j += REC_THREADS) g_state[g_list[n_items - 1 - (int32_t)j]] = 0;
     }
+    if (HASHED) {  // leave the table as it was found: through the two ends of the list, never a sweep (the fold left every counter zero)
+      for (unsigned j = tid; j < nc; j += REC_THREADS) h_keys[h_list[j]] = REC_EMPTY;
+      const unsigned ntomb = s_ntomb < (unsigned)REC_HASH_LIMIT ? s_ntomb : (unsigned)REC_HASH_LIMIT;
+      for (unsigned j = tid; j < ntomb; j += REC_THREADS) h_keys[h_list[REC_HASH_LIMIT - 1 - (int32_t)j]] = REC_EMPTY;
+    }
     __syncthreads();
   }
 }
 
 __global__ void rec_stats_kernel(const unsigned long long* __restrict__ ctr, int64_t* __restrict__ stats) {
   const int t = threadIdx.x;
-  if (t < REC_STATS_LEN) stats[t] = t < 5 ? (int64_t)ctr[t] : 0;
+  if (t < REC_STATS_LEN) stats[t] = t < 6 ? (int64_t)ctr[t] : 0;  // ctr[5]: queries of the hashed class (0 with the class off)
 }
 
 // urcco_dev_idf_weights: a thread per column.  df = the column's length (clamped to 0 .. n_docs); Lucene's BM25 idf in f64, rounded to units of 2^-15.
@@ -419,11 +528,21 @@ int32_t recommend_global_blocks(int64_t n_queries, int32_t n_items, int n_cu, bo
   return (int32_t)(blocks < 1 ? 1 : blocks);
 }
 
+// resident blocks of the hashed class: a slice is keys + m (4 bytes a slot; weighted: m64, 8) + list (4) + score (8) per REC_HASH_LIMIT entries -- 2.125 MiB, or
+// 2.625 MiB weighted -- at most 512 MiB in all: 240 blocks, 195 weighted.  The catalogue's size is not in the formula.
+size_t recommend_hashed_block_bytes(bool weighted) { return (size_t)REC_HASH_CAP * (weighted ? 12 : 8) + (size_t)REC_HASH_LIMIT * 12; }
+int32_t recommend_hashed_blocks(int64_t n_queries, int n_cu, bool weighted) {
+  int64_t blocks = ((int64_t)512 << 20) / (int64_t)recommend_hashed_block_bytes(weighted);
+  if (blocks > 2 * (int64_t)n_cu) blocks = 2 * (int64_t)n_cu;
+  if (blocks > n_queries) blocks = n_queries;
+  return (int32_t)(blocks < 1 ? 1 : blocks);
+}
+
 hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t n_items, const RecClause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
                             const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
                             int32_t* out_idx, double* out_score, int64_t* stats_dev, unsigned long long* ctr, int32_t* list, int32_t* pos, int32_t g_blocks,
                             unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit, const RecRule* rules, int32_t n_rules,
-                            const uint32_t* const* weights, unsigned long long* g_m64) {
+                            const uint32_t* const* weights, unsigned long long* g_m64, const RecHashed* hashed) {
   const bool weighted = weights != nullptr;  // then g_m64 is the counter array of the global class and g_m is not read
   RecArgs a;
   memset(&a, 0, sizeof(a));
@@ -433,13 +552,17 @@ hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t
   if (weighted)
     for (int c = 0; c < n_clauses; ++c) a.w[c] = weights[c];
   a.g_m64 = g_m64;
+  if (hashed) {
+    a.h = *hashed;
+    if (a.h.limit > REC_HASH_LIMIT) a.h.limit = REC_HASH_LIMIT;
+  }
   a.n_queries = n_queries; a.n_items = n_items; a.n_clauses = n_clauses; a.num = num; a.flags = flags;
   a.lds_limit = lds_limit < REC_LIMIT ? lds_limit : REC_LIMIT;
   a.excl_row_ptr = excl_row_ptr; a.excl_col_idx = excl_col_idx; a.item_mask = item_mask; a.fill_order = fill_order;
   a.pos = fill_order ? pos : nullptr;
   a.list = list; a.ctr = ctr; a.out_count = out_count; a.out_idx = out_idx; a.out_score = out_score;
   a.g_state = g_state; a.g_m = g_m; a.g_list = g_list; a.g_score = g_score; a.g_blocks = g_blocks;
-  hipError_t e = hipMemsetAsync(ctr, 0, 5 * sizeof(unsigned long long), st);
+  hipError_t e = hipMemsetAsync(ctr, 0, 8 * sizeof(unsigned long long), st);
   if (e != hipSuccess) return e;
   if (n_queries > 0) {
     if (fill_order && n_items > 0) {
@@ -450,22 +573,31 @@ hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t
     const size_t slice = (size_t)g_blocks * (size_t)(n_items > 0 ? n_items : 1);
     if ((e = hipMemsetAsync(g_state, 0, slice * sizeof(unsigned), st)) != hipSuccess) return e;
     if ((e = weighted ? hipMemsetAsync(g_m64, 0, slice * sizeof(unsigned long long), st) : hipMemsetAsync(g_m, 0, slice * sizeof(unsigned), st)) != hipSuccess) return e;
+    if (hashed) {  // once per call: every query leaves its slice as it found it
+      const size_t slots = (size_t)a.h.blocks * (size_t)REC_HASH_CAP;
+      if ((e = hipMemsetAsync(a.h.keys, 0xff, slots * sizeof(unsigned), st)) != hipSuccess) return e;
+      if ((e = weighted ? hipMemsetAsync(a.h.m64, 0, slots * sizeof(unsigned long long), st) : hipMemsetAsync(a.h.m, 0, slots * sizeof(unsigned), st)) != hipSuccess) return e;
+    }
     int64_t wb = (n_queries + REC_NW - 1) / REC_NW;
     if (wb > (int64_t)n_cu * 8) wb = (int64_t)n_cu * 8;
     hipLaunchKernelGGL(rec_work_kernel, dim3((unsigned)wb), dim3(REC_THREADS), 0, st, a);
     const int64_t lb = n_queries < (int64_t)n_cu * 2 ? n_queries : (int64_t)n_cu * 2;  // the LDS table lets two blocks share a CU
     if (weighted && n_rules > 0) {
-      hipLaunchKernelGGL((rec_rows_kernel<false, true, true>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
-      hipLaunchKernelGGL((rec_rows_kernel<true, true, true>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<0, true, true>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
+      if (hashed) hipLaunchKernelGGL((rec_rows_kernel<2, true, true>), dim3((unsigned)a.h.blocks), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<1, true, true>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
     } else if (weighted) {
-      hipLaunchKernelGGL((rec_rows_kernel<false, false, true>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
-      hipLaunchKernelGGL((rec_rows_kernel<true, false, true>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<0, false, true>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
+      if (hashed) hipLaunchKernelGGL((rec_rows_kernel<2, false, true>), dim3((unsigned)a.h.blocks), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<1, false, true>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
     } else if (n_rules > 0) {
-      hipLaunchKernelGGL((rec_rows_kernel<false, true, false>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
-      hipLaunchKernelGGL((rec_rows_kernel<true, true, false>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<0, true, false>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
+      if (hashed) hipLaunchKernelGGL((rec_rows_kernel<2, true, false>), dim3((unsigned)a.h.blocks), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<1, true, false>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
     } else {
-      hipLaunchKernelGGL((rec_rows_kernel<false, false, false>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
-      hipLaunchKernelGGL((rec_rows_kernel<true, false, false>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<0, false, false>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
+      if (hashed) hipLaunchKernelGGL((rec_rows_kernel<2, false, false>), dim3((unsigned)a.h.blocks), dim3(REC_THREADS), 0, st, a);
+      hipLaunchKernelGGL((rec_rows_kernel<1, false, false>), dim3((unsigned)g_blocks), dim3(REC_THREADS), 0, st, a);
     }
   }
   if (stats_dev) hipLaunchKernelGGL(rec_stats_kernel, dim3(1), dim3(64), 0, st, ctr, stats_dev);

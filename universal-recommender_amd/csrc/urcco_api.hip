@@ -1223,7 +1223,7 @@ static int recommend_call(urcco_session* s, int64_t n_queries, int32_t n_items, 
   if (n_clauses < 0 || n_clauses > URCCO_REC_MAX_CLAUSES || (n_clauses > 0 && !clauses))
     return fail(URCCO_BAD_ARG, "urcco_dev_recommend: between 0 and %d clauses, got %d", URCCO_REC_MAX_CLAUSES, n_clauses);
   if ((excl_row_ptr == nullptr) != (excl_col_idx == nullptr)) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: the exclusion CSR needs both of its arrays");
-  if (flags & ~URCCO_REC_NO_BACKFILL) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: unknown flags %d", flags);
+  if (flags & ~(URCCO_REC_NO_BACKFILL | URCCO_REC_HASHED | URCCO_REC_HASHED_AUTO)) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: unknown flags %d", flags);
   if (n_queries > 0 && (!out_count || !out_idx || !out_score)) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: output arrays missing");
   urcco::RecClause cl[URCCO_REC_MAX_CLAUSES];
   for (int c = 0; c < n_clauses; ++c) {
@@ -1258,6 +1258,18 @@ static int recommend_call(urcco_session* s, int64_t n_queries, int32_t n_items, 
   for (int c = 0; clause_weights && c < n_clauses; ++c) weighted = weighted || clause_weights[c] != nullptr;
   const int32_t g_blocks = urcco::recommend_global_blocks(n_queries, n_items, s->n_cu, weighted);
   const size_t slice = (size_t)g_blocks * (size_t)(n_items > 0 ? n_items : 1);
+  // The hashed class (D31).  URCCO_REC_HASHED_AUTO turns it on exactly when the dense class would get fewer resident blocks: two counts, no measured threshold.
+  // URCCO_REC_HASH_LIMIT lowers the work bound up to which a query runs in it (read per call, never raises it; the capacity stays): small test shapes reach
+  // the dense class behind the hashed one with it.
+  urcco::RecHashed hs{};
+  hs.blocks = urcco::recommend_hashed_blocks(n_queries, s->n_cu, weighted);
+  const bool hashed = (flags & URCCO_REC_HASHED) != 0 || ((flags & URCCO_REC_HASHED_AUTO) != 0 && g_blocks < hs.blocks);
+  hs.limit = urcco::REC_HASH_LIMIT;
+  if (const char* e = getenv("URCCO_REC_HASH_LIMIT")) {
+    const long v = atol(e);
+    if (v >= 0 && v < hs.limit) hs.limit = (int32_t)v;
+  }
+  const size_t h_slots = hashed ? (size_t)hs.blocks * (size_t)urcco::REC_HASH_CAP : 0, h_list = hashed ? (size_t)hs.blocks * (size_t)urcco::REC_HASH_LIMIT : 0;
   ArenaLayout L(s);
   unsigned long long* ctr;
   int32_t *list, *pos, *g_list;
@@ -1267,10 +1279,12 @@ static int recommend_call(urcco_session* s, int64_t n_queries, int32_t n_items, 
   L.add(&ctr, 8).add(&list, (size_t)n_queries).add(&pos, (size_t)n_items);
   L.add(&g_state, slice).add(&g_m, weighted ? 1 : slice).add(&g_list, slice).add(&g_score, slice);  // the global class's per-block slices
   L.add(&g_m64, weighted ? slice : 1);                                                               // ... the weighted call counts in 64 bits instead of g_m
+  L.add(&hs.queries, hashed ? (size_t)n_queries : 0).add(&hs.keys, h_slots).add(&hs.m, weighted ? 0 : h_slots).add(&hs.m64, weighted ? h_slots : 0);  // the hashed
+  L.add(&hs.list, h_list).add(&hs.score, h_list);                                                                                                     // class's slices
   URC(L.commit());
   HIPC(urcco::launch_recommend(s->stream, s->n_cu, n_queries, n_items, cl, n_clauses, excl_row_ptr, excl_col_idx, item_mask, fill_order, num, flags, out_count, out_idx,
                                out_score, stats_dev, ctr, list, pos, g_blocks, g_state, g_m, g_list, g_score, lds_limit, rl, n_rules, weighted ? clause_weights : nullptr,
-                               g_m64));
+                               g_m64, hashed ? &hs : nullptr));
   return URCCO_OK;
 }
 

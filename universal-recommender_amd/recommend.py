@@ -315,6 +315,18 @@ def _term_weights(algo, model: DeviceModel, term_weights) -> Optional[Dict[str, 
     return term_weights
 
 
+def _accumulator_flag(algo, accumulator) -> int:
+    """None (the algorithm's recommendAccumulator parameter decides; absent: "dense"), "dense", "hashed" or "auto" -> the flag bit of the recommend call
+    (decision D31): 0, REC_HASHED or REC_HASHED_AUTO.  The results do not depend on it, only which accumulator class serves the larger queries."""
+    if accumulator is None:
+        accumulator = getattr(algo.ap, "recommendAccumulator", None)
+    if accumulator is None:
+        accumulator = "dense"
+    if accumulator not in _lib.REC_ACCUMULATORS:
+        raise ValueError(f"accumulator: None, 'dense', 'hashed' or 'auto', got {accumulator!r}")
+    return _lib.REC_ACCUMULATORS[accumulator]
+
+
 def _max_query_events(ap) -> int:
     if ap.indicators:                                                                          # :203-211
         return sum(i.maxItemsPerUser if i.maxItemsPerUser is not None else 100 for i in ap.indicators) * 10
@@ -343,7 +355,7 @@ def _term_name(model: DeviceModel, m, term: int):
 
 
 def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host",
-                  term_weights=None, explain: Optional[int] = None) -> List[dict]:
+                  term_weights=None, explain: Optional[int] = None, accumulator: Optional[str] = None) -> List[dict]:
     """URAlgorithm.predict for a list of query dicts: [{"itemScores": [{"item", "score"}, ...]}, ...] in the order of `queries`.
     history: user -> {event name: [item ids, oldest first]} (the event store's view of the user), or a history.DeviceHistory: the event streams
     resident on the device.  With a DeviceHistory the user-history term rows (the ("user", ev) clauses, or the ("hist", ev) ANY rules under
@@ -367,7 +379,10 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
     clauses, boosts and weight arrays with the matrices' CSR in place of their CSC, and every item score gains
     "because": [{"clause": "user" | "item" | "field" | "itemSet", "name": event type or property, "term": item id or property value, "weight": boost
     times the term's weight}, ...] -- its at most E strongest matching terms, strongest first, ties by clause order, then column id: the user's own past
-    items, the query item's correlators, the matched property values.  A backfill item gets []."""
+    items, the query item's correlators, the matched property values.  A backfill item gets [].
+    accumulator: None (the algorithm's recommendAccumulator parameter, absent: "dense" -- the calls are then today's), "dense", "hashed" (REC_HASHED:
+    queries too large for the LDS class run on a per-block hash table whose size follows the query, not the catalogue) or "auto" (REC_HASHED_AUTO: hashed
+    exactly when the dense class would get fewer resident blocks): decision D31.  The results are the same bit for bit."""
     tw = _term_weights(algo, model, term_weights)
     explain = _explain_max(explain)
     if item_rows not in ("host", "device"):
@@ -385,7 +400,7 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
         raise ValueError("item_rows='device' needs maxQueryEvents >= 1")
     limit = ap.num if ap.num is not None else 20
     blacklist_events = ap.blacklistEvents if ap.blacklistEvents is not None else [primary]      # :236
-    flags = _lib.REC_NO_BACKFILL if algo.recsModel == "collabFiltering" else 0
+    flags = (_lib.REC_NO_BACKFILL if algo.recsModel == "collabFiltering" else 0) | _accumulator_flag(algo, accumulator)
 
     mask_t = _mask_tensor(model, item_mask)
 
@@ -586,7 +601,7 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
 
 
 def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = None, item_bias: Optional[float] = None, return_self: Optional[bool] = None,
-                  chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None):
+                  chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None, accumulator: Optional[str] = None):
     """The item-to-item table ("people who liked this also liked"): row n is what batch_predict answers to {"item": items[n]} -- the same items in the
     same order with the same scores -- as three device tensors (count int32 [n], idx int32 [n, num], score float64 [n, num]); entries behind count[n]
     are -1 / 0.0.  No Python work per item: the queries go `chunk` at a time through DeviceSession.item_rows (decision D18) and recommend, and no
@@ -595,7 +610,7 @@ def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = Non
     as batch_predict serves an unknown item (the backfill alone).  num, item_bias, return_self: default to the algorithm's num (20), itemBias (1.0),
     returnSelf (False).  item_bias > 0: one should-clause per event type of the model over the item's own indicator lists, boost = the bias;
     item_bias < 0: the lists are ANY rules instead (a model built with item properties, {} will do).  The query item is excluded unless return_self.
-    Backfill, recsModel, item_mask, the available / expire date rule around now_ms and term_weights are those of batch_predict."""
+    Backfill, recsModel, item_mask, the available / expire date rule around now_ms, term_weights and accumulator are those of batch_predict."""
     ap = algo.ap
     sess, dev = model.sess, model.sess.device
     tw = _term_weights(algo, model, term_weights)
@@ -616,7 +631,7 @@ def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = Non
     served = model.properties is not None
     if bias < 0 and not served:
         raise NotImplementedError("negative itemBias (similar items as a filter) needs a model built with item properties ({} will do)")
-    flags = _lib.REC_NO_BACKFILL if algo.recsModel == "collabFiltering" else 0
+    flags = (_lib.REC_NO_BACKFILL if algo.recsModel == "collabFiltering" else 0) | _accumulator_flag(algo, accumulator)
     mask_t = _mask_tensor(model, item_mask)
     if items is None:
         q_all = torch.arange(model.n_items, dtype=torch.int32, device=dev)
@@ -671,7 +686,7 @@ def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = Non
 
 def user_recommendations(algo, model: DeviceModel, history, users=None, num: Optional[int] = None, event_names: Optional[Sequence[str]] = None,
                          user_bias: Optional[float] = None, chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None,
-                         explain: Optional[int] = None):
+                         explain: Optional[int] = None, accumulator: Optional[str] = None):
     """The per-user table, the user-side twin of similar_items: row n is what batch_predict answers to {"user": users[n]} (with "eventNames", "num" and
     "userBias" where given) over the same DeviceHistory -- the same items in the same order with the same scores -- as three device tensors (count
     int32 [n], idx int32 [n, num], score float64 [n, num]); entries behind count[n] are -1 / 0.0.  No Python work per user: the queries go `chunk`
@@ -682,7 +697,7 @@ def user_recommendations(algo, model: DeviceModel, history, users=None, num: Opt
     the query's `eventNames`, default the model's event types.  user_bias > 0: one should-clause per event type over the user's recent items, boost
     = the bias; user_bias < 0: the rows are ANY rules instead (a model built with item properties, {} will do) -- every query carries them, so an
     unknown user or an event without history matches nothing, as in batch_predict.  The blacklist events' exclusions, backfill, recsModel, item_mask
-    the available / expire date rule around now_ms and term_weights are those of batch_predict.
+    the available / expire date rule around now_ms, term_weights and accumulator are those of batch_predict.
     explain: None, or E in 1..64 (decision D30): the result is (count, idx, score, n, clause, term, contrib, names) -- after the three tensors above, n int32
     [n, num] = the listed terms of a slot, clause / term int32 and contrib float64 [n, num, E] = their clause (an index into names, the list of
     ("user", event type) in clause order), column id and boost x weight, in batch_predict's order; zeros behind n.  userBias < 0 leaves no clause: n = 0."""
@@ -714,7 +729,7 @@ def user_recommendations(algo, model: DeviceModel, history, users=None, num: Opt
     hist_events = [ev for ev in q_events if ev in dh.types and (ev in model.by_name or ev in blacklist_events)]
     if len(hist_events) > _lib.REC_MAX_CLAUSES:
         raise ValueError(f"a batch names {len(hist_events)} event types, more than the {_lib.REC_MAX_CLAUSES} one history call serves")
-    flags = _lib.REC_NO_BACKFILL if algo.recsModel == "collabFiltering" else 0
+    flags = (_lib.REC_NO_BACKFILL if algo.recsModel == "collabFiltering" else 0) | _accumulator_flag(algo, accumulator)
     mask_t = _mask_tensor(model, item_mask)
     if users is None:
         q_all = torch.arange(dh.n_users, dtype=torch.int32, device=dev)

@@ -136,6 +136,7 @@ class URAlgorithmParams:
     blacklistEvents: Optional[List[str]] = None    # :236: None = the primary event, [] = no blacklist
     returnSelf: Optional[bool] = None              # :237
     termWeights: Optional[str] = None              # additive key: the default of the query side's term_weights (decision D20): absent = every matching term scores 1, "idf"
+    recommendAccumulator: Optional[str] = None     # additive key: the default of the query side's accumulator (decision D31): absent = "dense", "hashed", "auto"
     minEventsPerUser: Optional[int] = None         # additive key: the datasource's minEventsPerUser for train_from_history, which has no DataSource in front of it; absent = 1
 
     @staticmethod
@@ -158,6 +159,7 @@ class URAlgorithmParams:
                                                                   i.get("minLLR")) for i in inds],
             seed=p.get("seed"), num=p.get("num"), maxQueryEvents=p.get("maxQueryEvents"), userBias=p.get("userBias"), itemBias=p.get("itemBias"),
             blacklistEvents=p.get("blacklistEvents"), returnSelf=p.get("returnSelf"), termWeights=p.get("termWeights"),
+            recommendAccumulator=p.get("recommendAccumulator"),
             minEventsPerUser=p.get("minEventsPerUser"))
 
 
@@ -268,7 +270,7 @@ class URAlgorithm:
 
 
     def batch_predict(self, model, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host",
-                      term_weights=None, explain: Optional[int] = None) -> List[dict]:
+                      term_weights=None, explain: Optional[int] = None, accumulator: Optional[str] = None) -> List[dict]:
         """URAlgorithm.predict (:484-535) for a batch of queries against a recommend.DeviceModel: user history, similar-item and itemSet
         queries, blacklists, backfill by rank and -- for a model built with item properties -- the business rules (fields, dateRange, available /
         expire dates around now_ms, negative biases); see recommend.batch_predict for what is mirrored and what is left out.  history: the dict
@@ -278,28 +280,30 @@ class URAlgorithm:
         uint32 device tensor} -- decision D20, see recommend.py.  explain=E (here, in predict and in user_recommendations; None: nothing changes): every
         item score gains "because", the at most E terms behind it (decision D30)."""
         from .recommend import batch_predict
-        return batch_predict(self, model, queries, history, item_mask, now_ms, item_rows, term_weights, explain)
+        return batch_predict(self, model, queries, history, item_mask, now_ms, item_rows, term_weights, explain, accumulator)
 
     def similar_items(self, model, items=None, num: Optional[int] = None, item_bias: Optional[float] = None, return_self: Optional[bool] = None,
-                      chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None):
+                      chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None, accumulator: Optional[str] = None):
         """The item-to-item table of `items` (None: every item of the model) as device tensors (count, idx, score): row n is what batch_predict
         answers to {"item": items[n]}; see recommend.similar_items."""
         from .recommend import similar_items
-        return similar_items(self, model, items, num, item_bias, return_self, chunk, item_mask, now_ms, term_weights)
+        return similar_items(self, model, items, num, item_bias, return_self, chunk, item_mask, now_ms, term_weights, accumulator)
 
     def user_recommendations(self, model, history, users=None, num: Optional[int] = None, event_names=None, user_bias: Optional[float] = None,
-                             chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None, explain: Optional[int] = None):
+                             chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None, explain: Optional[int] = None,
+                             accumulator: Optional[str] = None):
         """The per-user table of `users` (None: every user id of the history.DeviceHistory) as device tensors (count, idx, score): row n is what
         batch_predict answers to {"user": users[n]} over the same history; see recommend.user_recommendations."""
         from .recommend import user_recommendations
-        return user_recommendations(self, model, history, users, num, event_names, user_bias, chunk, item_mask, now_ms, term_weights, explain)
+        return user_recommendations(self, model, history, users, num, event_names, user_bias, chunk, item_mask, now_ms, term_weights, explain, accumulator)
 
     def evaluate(self, model, train, test, ks=(1, 5, 10, 20), num: Optional[int] = None, event_names=None, truth_event: Optional[str] = None,
-                 chunk: int = 65536, user_bias: Optional[float] = None, item_mask=None, now_ms: Optional[int] = None, term_weights=None):
+                 chunk: int = 65536, user_bias: Optional[float] = None, item_mask=None, now_ms: Optional[int] = None, term_weights=None,
+                 accumulator: Optional[str] = None):
         """Hold-out evaluation on the device (decision D19): precision, hit rate, MAP@k and NDCG@k of the recommendations over the `train` history
         against the users' `truth_event` items in the `test` history; a list of event mixes gives a list of reports.  See evaluate.evaluate."""
         from .evaluate import evaluate
-        return evaluate(self, model, train, test, ks, num, event_names, truth_event, chunk, user_bias, item_mask, now_ms, term_weights)
+        return evaluate(self, model, train, test, ks, num, event_names, truth_event, chunk, user_bias, item_mask, now_ms, term_weights, accumulator)
 
     def properties_from_events(self, model, events):
         """A properties.DeviceProperties for `model` over the item property events `events` ($set / $unset / $delete, see DeviceProperties.apply), its
@@ -307,8 +311,9 @@ class URAlgorithm:
         from .properties import DeviceProperties
         return DeviceProperties(model.sess, model, self.dateNames).apply(events)
 
-    def predict(self, model, query: dict, history, item_mask=None, now_ms: Optional[int] = None, term_weights=None, explain: Optional[int] = None) -> dict:
-        return self.batch_predict(model, [query], history, item_mask, now_ms, term_weights=term_weights, explain=explain)[0]
+    def predict(self, model, query: dict, history, item_mask=None, now_ms: Optional[int] = None, term_weights=None, explain: Optional[int] = None,
+                accumulator: Optional[str] = None) -> dict:
+        return self.batch_predict(model, [query], history, item_mask, now_ms, term_weights=term_weights, explain=explain, accumulator=accumulator)[0]
 
     def train_events_on_device(self, trainingData, sess) -> List[Tuple[str, IndexedDataset]]:
         """Preparator.prepare + URAlgorithm.calcAll without leaving the GPU in between: the event streams are hashed on
