@@ -494,7 +494,8 @@ int urcco_dev_pop_counts(urcco_session* s, int64_t n_events, const int32_t* item
 #define URCCO_REC_STATS_LEN 8   /* [0] queries served by the LDS class, [1] by the global-accumulator (dense) class,
                                    [2] candidate-table overflows (invariant: 0), [3] sum of candidates,
                                    [4] backfill steps (urcco_dev_recommend_rules with rules only, else 0),
-                                   [5] queries served by the hashed class (0 without URCCO_REC_HASHED); [0] + [1] + [5] == n_queries; rest 0 */
+                                   [5] queries served by the hashed class (0 without URCCO_REC_HASHED); [0] + [1] + [5] == n_queries;
+                                   [6], [7] urcco_dev_recommend_driven's: queries of the driven class, items they gathered (else 0) */
 typedef struct urcco_rec_clause {
   int32_t n_cols;               /* columns of I_c = items of the clause's event type */
   int32_t reserved;
@@ -564,6 +565,41 @@ int urcco_dev_recommend_weighted(urcco_session* s, int64_t n_queries, int32_t n_
                                  int32_t num, int32_t flags, int32_t* out_count, int32_t* out_idx, double* out_score, int64_t* stats_dev,
                                  const urcco_rec_rule* rules, int32_t n_rules,
                                  const uint32_t* const* clause_weights /* nullable: HOST array [n_clauses] of device pointers [clause.n_cols], entries nullable */);
+
+/* urcco_dev_recommend_weighted with the driven class (DESIGN.md decision D32): a query whose eligible set is bounded by a short item list is answered from
+ * that list -- "recommend inside this category", a `fields` entry with bias < 0.  A driver is an ANY rule r of the call for which the caller also passes the
+ * CSC of its matrix M_r (value -> items).  For query q
+ *   E_r(q) = the union of the columns of M_r named by row q of the rule's query matrix,
+ *   d_r(q) = the sum of those columns' lengths -- an upper bound of |E_r(q)|: an item holding two of the values is listed twice; a column id outside
+ *            0..n_cols contributes nothing, an empty query row gives d = 0,
+ *   d(q)   = the minimum of d_r(q) over the drivers, the lowest rule index winning a tie.
+ * Every eligible item of q lies in E_r(q), the zero-score ones included, so the complete answer is the first num of E_r(q) ^ eligible in the total order
+ * (score desc, backfill position asc) -- under URCCO_REC_NO_BACKFILL only the positive-score items take part.  No item outside E_r(q) can appear: the
+ * backfill is part of the same selection.  A query runs in the driven class when the call carries URCCO_REC_DRIVEN and d(q) <= URCCO_REC_DRIVE_LIMIT (the
+ * LDS class's own limit: the list lives in its 4096-slot table at load factor <= 0.75).  There the candidates are enumerated from the rule's columns, each is
+ * scored from its own rows of the CSR of I_c (clause_rows: the arrays urcco_explain_clause takes) by searching the entries in the sorted T_c(q) -- exact
+ * 64-bit integer sums, folded as above -- and one selection cuts the list: no term walk, no accumulator, no position of fill_order is read.  Counts, ids and
+ * score bits are those of urcco_dev_recommend_weighted.  Queries beyond the limit, and every query of a call without the flag or without drivers, run exactly
+ * as there; URCCO_REC_HASHED and URCCO_REC_HASHED_AUTO keep their meaning for them.
+ * stats[6] = queries served by the driven class ([0] + [1] + [5] + [6] == n_queries), stats[7] = the distinct items they gathered, summed; stats[3] keeps its
+ * meaning (eligible candidates with a positive score: it does not depend on the class), stats[4] counts the walk steps of the other queries alone.
+ * n_drivers == 0, or the flag absent, is urcco_dev_recommend_weighted itself (results and statistics, stats[6..7] == 0).  URCCO_BAD_ARG, in addition: a driver
+ * naming a rule outside 0..n_rules or a rule that is not URCCO_RULE_ANY, the same rule named twice, n_drivers outside 0..URCCO_REC_MAX_RULES, a NULL half of a
+ * pair, clause_rows == NULL with n_drivers > 0 and n_clauses > 0.  The three entry points above reject URCCO_REC_DRIVEN. */
+#define URCCO_REC_DRIVEN 0x400
+#define URCCO_REC_DRIVE_LIMIT 3072
+typedef struct urcco_rec_driver {
+  int32_t rule, reserved;                                  /* index into rules; the rule must be URCCO_RULE_ANY */
+  const int64_t* m_col_ptr; const int32_t* m_row_idx;      /* device: CSC of rules[rule].M (n_items x n_cols), order inside a column unspecified */
+} urcco_rec_driver;
+typedef struct urcco_rec_clause_rows {
+  const int64_t* m_row_ptr; const int32_t* m_col_idx;      /* device: CSR of I_c (n_items x n_cols), as urcco_explain_clause takes it */
+} urcco_rec_clause_rows;
+int urcco_dev_recommend_driven(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses,
+                               const int64_t* excl_row_ptr, const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order,
+                               int32_t num, int32_t flags, int32_t* out_count, int32_t* out_idx, double* out_score, int64_t* stats_dev,
+                               const urcco_rec_rule* rules, int32_t n_rules, const uint32_t* const* clause_weights,
+                               const urcco_rec_driver* drivers, int32_t n_drivers, const urcco_rec_clause_rows* clause_rows /* [n_clauses] */);
 
 /* Term weights by rarity for urcco_dev_recommend_weighted: for column h of a CSC, df = ind_col_ptr[h + 1] - ind_col_ptr[h] (a df above n_docs counts as n_docs),
  *   idf = log(1 + (n_docs - df + 0.5) / (df + 0.5))   in f64 -- Lucene's BM25 idf, the term-rarity half of what the reference's Elasticsearch index computes;

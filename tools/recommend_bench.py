@@ -32,7 +32,7 @@ query rows and the table, then np.intersect1d per (query, slot, clause) over the
 same process, the class split stats[0] / stats[1] / stats[5], whether counts, ids and score bits equal the flagless call's, and the distribution of the work
 bound w(q) (median, p90, maximum, share above REC_HASH_LIMIT) -- what a later change of the table's capacity would rest on.  --item-scale S: the item spaces
 of the model as a fraction of BASELINE config 4's (default 0.1: 200K items; 1.0: the 2M-item catalogue).
-usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--item-scale S] [--accumulator dense|hashed|auto] [--rules] [--weights] [--device-history] [--device-items] [--evaluate] [--explain] [--no-torch]"""
+usage: tools/recommend_bench.py [--users N] [--queries N] [--chunk N] [--reps N] [--item-scale S] [--accumulator dense|hashed|auto] [--rules] [--driven] [--weights] [--device-history] [--device-items] [--evaluate] [--explain] [--no-torch]"""
 import argparse
 import os
 import sys
@@ -54,6 +54,7 @@ ap.add_argument("--num", type=int, default=20)
 ap.add_argument("--item-scale", type=float, default=0.1, help="item spaces as a fraction of config 4's (1.0: 2M items)")
 ap.add_argument("--accumulator", choices=sorted(_lib.REC_ACCUMULATORS), default="dense", help="also time the call with this accumulator class for the larger queries")
 ap.add_argument("--rules", action="store_true", help="also time the call under an ANY and a NONE rule")
+ap.add_argument("--driven", action="store_true", help="also time the call under a rare category filter, walked and driven by the filter's item list in turn")
 ap.add_argument("--weights", action="store_true", help="also time the weighted call under idf term weights")
 ap.add_argument("--device-history", action="store_true", help="also time history_bounds + history_rows against the host planning loop")
 ap.add_argument("--device-items", action="store_true", help="also time item_bounds + item_rows against the host planning loop of item queries")
@@ -145,6 +146,41 @@ if args.rules:
     print(f"urcco_dev_recommend_rules (ANY on a value {float(half.float().mean()):.0%} of the items hold, NONE on a value a ninth hold): {min(ms_rules):.2f} ms best, "
           f"{sorted(ms_rules)[len(ms_rules) // 2]:.2f} ms median of {args.reps} ({[round(x, 2) for x in ms_rules]}) -- rule-free call above: {min(ms_hip):.2f} ms")
     print(f"  candidates {rs[3]} ({rs[3] / nq:.0f} per query, {st[3] / nq:.0f} without rules); backfill steps {rs[4]} ({rs[4] / nq:.2f} per query); full rows {int((r_count == num).sum())} / {nq}")
+
+if args.driven:
+    # the --rules problem with the filter on a rare value: value 0 on about 0.1 % of the items, value 1 + i % 9 on every item (the NONE rule names value 1).
+    # "walk" and "driven" alternate on the same problem in this process, HIP events around every call (decision D32).
+    g = torch.Generator(device="cpu").manual_seed(2)
+    rare = (torch.rand(n_items, generator=g) < 0.001).to(dev)
+    item = torch.arange(n_items, device=dev)
+    m_rp = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(1 + rare.to(torch.int64), 0)])
+    m_ci = torch.empty(int(m_rp[-1].item()), dtype=torch.int32, device=dev)
+    m_ci[m_rp[:-1]] = (1 + item % 9).to(torch.int32)
+    m_ci[m_rp[1:][rare] - 1] = 0
+    order = torch.sort(m_ci.to(torch.int64), stable=True).indices
+    m_cp = torch.cat([torch.zeros(1, dtype=torch.int64, device=dev), torch.cumsum(torch.bincount(m_ci.to(torch.int64), minlength=10), 0)])
+    m_ri = torch.repeat_interleave(item, 1 + rare.to(torch.int64))[order].to(torch.int32)
+    one = torch.arange(nq + 1, dtype=torch.int64, device=dev)
+    rules = [(_lib.RULE_ANY, 10, m_rp, m_ci, one, torch.zeros(nq, dtype=torch.int32, device=dev)),
+             (_lib.RULE_NONE, 10, m_rp, m_ci, one, torch.ones(nq, dtype=torch.int32, device=dev))]
+    rows = [(c.row_ptr, c.col_idx) for c in model.correlators]
+    plans = {"walk": lambda: sess.recommend(nq, n_items, clauses, num, excl, None, fill, 0, rules=rules),
+             "driven": lambda: sess.recommend(nq, n_items, clauses, num, excl, None, fill, _lib.REC_DRIVEN, rules=rules, drivers=[(0, m_cp, m_ri)], clause_rows=rows)}
+    ms, out = {"walk": [], "driven": []}, {}
+    for rep in range(-2, max(args.reps, 5)):            # two warm-up rounds, then the plans in turn
+        for name, fn in plans.items():
+            out[name], t = timed(fn, 1, warm=0)
+            if rep >= 0:
+                ms[name] += t
+    live = torch.arange(num, device=dev)[None, :] < out["walk"][0][:, None]
+    same = torch.equal(out["driven"][0], out["walk"][0]) and torch.equal(torch.where(live, out["driven"][1], 0), torch.where(live, out["walk"][1], 0)) and \
+        torch.equal(torch.where(live, out["driven"][2], 0.0).view(torch.int64), torch.where(live, out["walk"][2], 0.0).view(torch.int64))
+    print(f"urcco_dev_recommend_driven (ANY on a value {int(rare.sum().item())} of {n_items} items hold, NONE on a value a ninth hold), {len(ms['walk'])} alternating repetitions:")
+    for name in plans:
+        s, v = out[name][3].cpu().tolist(), sorted(ms[name])
+        print(f"  {name}: {v[len(v) // 2]:.2f} ms median, {v[0]:.2f} - {v[-1]:.2f} ms ({[round(x, 2) for x in ms[name]]}); backfill steps stats[4] = {s[4]}, "
+              f"driven queries stats[6] = {s[6]}, items gathered stats[7] = {s[7]}, candidates {s[3]}")
+    print(f"  counts, ids and score bits of the two plans are equal: {bool(same)}; full rows {int((out['walk'][0] == num).sum())} / {nq}")
 
 if args.weights:
     _, ms_idf = timed(lambda: [sess.idf_weights(c.col_ptr, c.n_cols, n_items) for c in model.correlators], args.reps)

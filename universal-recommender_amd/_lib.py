@@ -52,7 +52,10 @@ REC_HASHED = 0x100        # flag (URCCO_REC_HASHED, decision D31): queries beyon
 REC_HASHED_AUTO = 0x200   # flag: REC_HASHED exactly when the dense class would get fewer resident blocks than the hashed class
 REC_HASH_CAP_LOG2 = 17    # slots of a block's table: home slot of an item = (item * 2654435761 mod 2^32) >> (32 - REC_HASH_CAP_LOG2), linear probing
 REC_HASH_LIMIT = 3 << (REC_HASH_CAP_LOG2 - 2)   # 98 304: the work bound w(q) up to which a query runs in the hashed class
-REC_ACCUMULATORS = {"dense": 0, "hashed": REC_HASHED, "auto": REC_HASHED_AUTO}   # the `accumulator=` argument of recommend.py -> flag
+REC_DRIVEN = 0x400        # flag (URCCO_REC_DRIVEN, decision D32): queries whose driver list holds at most REC_DRIVE_LIMIT entries are answered from that list
+REC_DRIVE_LIMIT = 3072
+REC_FILTER_PLANS = ("walk", "driven")   # the `filter_plan=` argument of recommend.py
+REC_ACCUMULATORS ={"dense": 0, "hashed": REC_HASHED, "auto": REC_HASHED_AUTO}   # the `accumulator=` argument of recommend.py -> flag
 EXCH_SIZES = 4   # int64 words of a shard's record (include/urcco.h URCCO_EXCH_SIZES)
 # bits of urcco_session_set_debug / urcco_context_set_debug: the names and values of csrc/cco_kernels.h (tests/test_c_abi_surface.py compares them)
 DBG_GATHER_ONLY = 1
@@ -155,6 +158,16 @@ class RecRule(C.Structure):
                 ("q_col_idx", C.c_void_p), ("item_value", C.c_void_p), ("q_lo", C.c_void_p), ("q_hi", C.c_void_p)]
 
 
+class RecDriver(C.Structure):
+    """urcco_rec_driver: the CSC of the matrix of ANY rule `rule` of urcco_dev_recommend_driven."""
+    _fields_ = [("rule", C.c_int32), ("reserved", C.c_int32), ("m_col_ptr", C.c_void_p), ("m_row_idx", C.c_void_p)]
+
+
+class RecClauseRows(C.Structure):
+    """urcco_rec_clause_rows: the CSR of a should-clause's matrix, as ExplainClause carries it."""
+    _fields_ = [("m_row_ptr", C.c_void_p), ("m_col_idx", C.c_void_p)]
+
+
 class ExplainClause(C.Structure):
     """urcco_explain_clause: one should-clause of urcco_dev_explain -- the CSR of the matrix whose CSC the recommend call was given."""
     _fields_ = [("n_cols", C.c_int32), ("reserved", C.c_int32), ("boost", C.c_double), ("m_row_ptr", C.c_void_p), ("m_col_idx", C.c_void_p),
@@ -246,6 +259,8 @@ SYMBOLS = {
                                             C.POINTER(RecRule), C.c_int32]),
     "urcco_dev_recommend_weighted": (C.c_int, [_p, C.c_int64, C.c_int32, C.POINTER(RecClause), C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p,
                                                C.POINTER(RecRule), C.c_int32, C.POINTER(C.c_void_p)]),
+    "urcco_dev_recommend_driven": (C.c_int, [_p, C.c_int64, C.c_int32, C.POINTER(RecClause), C.c_int32, _p, _p, _p, _p, C.c_int32, C.c_int32, _p, _p, _p, _p,
+                                             C.POINTER(RecRule), C.c_int32, C.POINTER(C.c_void_p), C.POINTER(RecDriver), C.c_int32, C.POINTER(RecClauseRows)]),
     "urcco_dev_idf_weights": (C.c_int, [_p, C.c_int32, _p, C.c_int64, _p]),
     "urcco_dev_rank_metrics": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p, _p, C.POINTER(C.c_int32), C.c_int32, _p, _p, _p, _p, _p, _p]),
     "urcco_dev_tree_sum": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p]),

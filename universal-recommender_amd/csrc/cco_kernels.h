@@ -395,16 +395,38 @@ struct RecHashed {
   double* score;
 };
 size_t recommend_hashed_block_bytes(bool weighted);
+// The driven class (decision D32): a query whose eligible set is bounded by the item list of an ANY rule -- d(q) = the summed lengths of the columns of the rule's
+// matrix that the query's rule row names, the smallest over the call's drivers -- is answered from that list: no term walk, no accumulator, no backfill walk.
+constexpr int REC_DRIVEN = 0x400;              // flag: queries with d(q) <= REC_DRIVE_LIMIT run in the driven class (urcco_dev_recommend_driven only)
+constexpr int REC_DRIVE_LIMIT = REC_LDS_LIMIT; // the LDS table of the LDS class holds the list: 4096 slots, load factor 0.75
+struct RecDriver {
+  const int64_t* m_col_ptr;    // CSC of rules[rule].M (value -> items)
+  const int32_t* m_row_idx;
+  int32_t rule, reserved;
+};
+struct RecClauseRows {
+  const int64_t* m_row_ptr;    // CSR of I_c (n_items x n_cols), order inside a row unspecified: what ExplClause takes
+  const int32_t* m_col_idx;
+};
+struct RecDriven {
+  RecDriver d[REC_MAX_RULES];  // ascending by rule: the lowest rule index wins a tie of d
+  RecClauseRows rows[REC_MAX_CLAUSES];
+  int32_t n_drivers;
+  int32_t limit;               // d(q) up to here: driven class (<= REC_DRIVE_LIMIT)
+  int32_t* queries;            // [n_queries] scratch: the driven queries, counted in ctr[6]
+  int32_t* driver_of;          // [n_queries] scratch: index into d of the driver of a driven query
+};
 int32_t recommend_hashed_blocks(int64_t n_queries, int n_cu, bool weighted = false);  // min(2 n_cu, n_queries, 512 MiB / bytes per block): n_items is not in it
 // ctr[8], list[n_queries], pos[n_items] (only with fill_order), g_state / g_m / g_list [g_blocks * n_items] words, g_score [g_blocks * n_items] doubles: scratch.
 // weights != NULL (host array [n_clauses] of device pointers, entries nullable): the weighted kernels; g_m64 [g_blocks * n_items] 64-bit words then takes g_m's place
 // hashed != NULL: the hashed class is on for this call (three-way binning); NULL: the two classes, decisions, lists and counters as ever
+// driven != NULL (needs n_rules > 0): the driven class is on -- its queries leave the binning first, the rest are binned as without it
 hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t n_items, const RecClause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
                             const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
                             int32_t* out_idx, double* out_score, int64_t* stats_dev, unsigned long long* ctr, int32_t* list, int32_t* pos, int32_t g_blocks,
                             unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit = REC_LDS_LIMIT, const RecRule* rules = nullptr,
                             int32_t n_rules = 0, const uint32_t* const* weights = nullptr, unsigned long long* g_m64 = nullptr,
-                            const RecHashed* hashed = nullptr);
+                            const RecHashed* hashed = nullptr, const RecDriven* driven = nullptr);
 hipError_t launch_idf_weights(hipStream_t st, int n_cu, int32_t n_cols, const int64_t* col_ptr, int64_t n_docs, uint32_t* out);
 
 // ---- hold-out evaluation (cco_eval.h, compiled into cco_misc.hip behind cco_recommend.h; decision D19) ----------------------

@@ -91,26 +91,60 @@ __global__ __launch_bounds__(256) void rec_inverse_kernel(int32_t n_items, const
   }
 }
 
+// the w-based split of one query, by the wave that owns it
+__device__ __forceinline__ void rec_work_bin(const RecArgs& a, int64_t q, int lane) {
+  long long w = 0;
+  for (int c = 0; c < a.n_clauses; ++c) {
+    const RecClause& cl = a.c[c];
+    const int64_t e = cl.q_row_ptr[q + 1];
+    for (int64_t t = cl.q_row_ptr[q] + lane; t < e; t += WAVE) {
+      const int32_t h = cl.q_col_idx[t];
+      if ((unsigned)h < (unsigned)cl.n_cols) w += cl.ind_col_ptr[h + 1] - cl.ind_col_ptr[h];
+    }
+  }
+  for (int o = WAVE / 2; o > 0; o >>= 1) w += shfl_xor_u64((unsigned long long)w, o);
+  if (a.excl_row_ptr) w += a.excl_row_ptr[q + 1] - a.excl_row_ptr[q];
+  if (lane == 0) {
+    if (w <= a.lds_limit) a.list[atomicAdd(&a.ctr[0], 1ull)] = (int32_t)q;
+    else if (a.h.queries && w <= a.h.limit) a.h.queries[atomicAdd(&a.ctr[5], 1ull)] = (int32_t)q;
+    else a.list[a.n_queries - 1 - (int64_t)atomicAdd(&a.ctr[1], 1ull)] = (int32_t)q;
+  }
+}
+
 // a wave per query
 __global__ __launch_bounds__(REC_THREADS) void rec_work_kernel(RecArgs a) {
   const int lane = threadIdx.x & (WAVE - 1);
   const int64_t n_waves = (int64_t)gridDim.x * REC_NW;
+  for (int64_t q = (int64_t)blockIdx.x * REC_NW + threadIdx.x / WAVE; q < a.n_queries; q += n_waves) rec_work_bin(a, q, lane);
+}
+
+// The binning of a call with drivers: d(q) first -- per driver the summed lengths of the columns of its matrix that the query's rule row names, the smallest
+// over the drivers (they ascend by rule, so the lowest rule index wins a tie) -- and a query with d <= limit goes to the driven list; the rest as above.
+__global__ __launch_bounds__(REC_THREADS) void rec_work_driven_kernel(RecArgs a, RecDriven dv) {
+  const int lane = threadIdx.x & (WAVE - 1);
+  const int64_t n_waves = (int64_t)gridDim.x * REC_NW;
   for (int64_t q = (int64_t)blockIdx.x * REC_NW + threadIdx.x / WAVE; q < a.n_queries; q += n_waves) {
-    long long w = 0;
-    for (int c = 0; c < a.n_clauses; ++c) {
-      const RecClause& cl = a.c[c];
-      const int64_t e = cl.q_row_ptr[q + 1];
-      for (int64_t t = cl.q_row_ptr[q] + lane; t < e; t += WAVE) {
-        const int32_t h = cl.q_col_idx[t];
-        if ((unsigned)h < (unsigned)cl.n_cols) w += cl.ind_col_ptr[h + 1] - cl.ind_col_ptr[h];
+    long long best = 0;
+    int best_j = -1;
+    for (int j = 0; j < dv.n_drivers; ++j) {
+      const RecRule& r = a.r[dv.d[j].rule];
+      const int64_t* __restrict__ cp = dv.d[j].m_col_ptr;
+      long long d = 0;
+      const int64_t e = r.q_row_ptr[q + 1];
+      for (int64_t t = r.q_row_ptr[q] + lane; t < e; t += WAVE) {
+        const int32_t v = r.q_col_idx[t];
+        if ((unsigned)v < (unsigned)r.n_cols) d += cp[v + 1] - cp[v];
       }
+      for (int o = WAVE / 2; o > 0; o >>= 1) d += shfl_xor_u64((unsigned long long)d, o);
+      if (best_j < 0 || d < best) { best = d; best_j = j; }
     }
-    for (int o = WAVE / 2; o > 0; o >>= 1) w += shfl_xor_u64((unsigned long long)w, o);
-    if (a.excl_row_ptr) w += a.excl_row_ptr[q + 1] - a.excl_row_ptr[q];
-    if (lane == 0) {
-      if (w <= a.lds_limit) a.list[atomicAdd(&a.ctr[0], 1ull)] = (int32_t)q;
-      else if (a.h.queries && w <= a.h.limit) a.h.queries[atomicAdd(&a.ctr[5], 1ull)] = (int32_t)q;
-      else a.list[a.n_queries - 1 - (int64_t)atomicAdd(&a.ctr[1], 1ull)] = (int32_t)q;
+    if (best_j >= 0 && best <= dv.limit) {
+      if (lane == 0) {
+        dv.queries[atomicAdd(&a.ctr[6], 1ull)] = (int32_t)q;
+        dv.driver_of[q] = best_j;
+      }
+    } else {
+      rec_work_bin(a, q, lane);
     }
   }
 }
@@ -491,9 +525,253 @@ __global__ __launch_bounds__(REC_THREADS) void rec_rows_kernel(RecArgs a) {
   }
 }
 
+// ---- the driven class (REC_DRIVEN, decision D32): a block per query answers it from the item list of its driving rule ----
+//   gather   the block walks the columns of the driver's CSC that the query's rule row names (a wave per column below 512 entries, the block beyond) and claims
+//            every item in the LDS table: the union removes its own duplicates, and d(q) <= REC_DRIVE_LIMIT claims cannot fill the 4096 slots.  The claiming lane
+//            alone tests the mask and the rules (all of them: the driving rule costs one short search more, and the predicate stays the one of the other
+//            classes) -- a rejected item turns into a tombstone in place, an admitted one is appended to the candidate list.  Meanwhile the query's term rows
+//            T_c(q) are staged side by side in LDS when they hold no more than REC_DRV_TERMS entries together.
+//   strike   the exclusion row is looked up entry by entry; what is found becomes a tombstone: a blacklist costs probes and no table space.
+//   score    a group of 16 lanes per candidate (an indicator row has at most k entries, a property row a handful: a whole wave would idle three quarters of
+//            its lanes), lanes over the entries of row i of the CSR of I_c, each entry searched in the sorted T_c(q) -- in LDS or, beyond the staging
+//            capacity, in global memory: two instantiations of the body behind one block-uniform branch, so that every load is a ds_read or a global_load.
+//            The matches' weights are summed in 64-bit registers and across the group by integer shuffles; lane 0 folds the clauses in call order with the
+//            expression of the other classes.  No atomic on a score, no accumulator.  A struck candidate scores -1: dead.
+//   select   one sel_kth_largest over the whole list, a dead candidate (struck, or zero under NO_BACKFILL) keyed (0, 0) below every live key ((score bits,
+//            ~position), ~position >= 2^31); the live keys at or above the num-th are the winners, ranked by counting.  The zero-score winners ARE the backfill.
+constexpr int REC_DRV_TERMS = 4096;                        // staged entries of the query's term rows, all clauses together (16 KiB: the LDS class's s_m)
+constexpr int REC_DRV_GROUP = 16;                          // lanes per candidate in the score phase
+constexpr int REC_DRV_NG = REC_THREADS / REC_DRV_GROUP;    // candidates per pass
+static_assert(REC_DRIVE_LIMIT <= REC_LIMIT, "the driven list lives in the LDS class's table");
+static_assert(sizeof(RecArgs) + sizeof(RecDriven) <= 4096, "kernel arguments: both tables travel by value");
+
+// Claim `item` in the table: its slot when this lane inserted it, -1 when it was there (or the table is full: err).
+__device__ __forceinline__ int rec_drv_claim(unsigned* keys, unsigned item, unsigned long long* err) {
+  unsigned h = rec_hash(item);
+  for (int probe = 0; probe < REC_CAP; ++probe) {
+    unsigned k = __hip_atomic_load(&keys[h], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    if (k == REC_EMPTY) {
+      k = atomicCAS(&keys[h], REC_EMPTY, item);
+      if (k == REC_EMPTY) return (int)h;
+    }
+    if ((k & ~REC_TOMB) == item) return -1;
+    h = (h + 1) & (REC_CAP - 1);
+  }
+  atomicAdd(err, 1ull);
+  return -1;
+}
+// slot of the item in the table, -1 when absent
+__device__ __forceinline__ int rec_drv_slot(const unsigned* keys, unsigned item) {
+  unsigned h = rec_hash(item);
+  for (int probe = 0; probe < REC_CAP; ++probe) {
+    const unsigned k = keys[h];
+    if (k == REC_EMPTY) return -1;
+    if ((k & ~REC_TOMB) == item) return (int)h;
+    h = (h + 1) & (REC_CAP - 1);
+  }
+  return -1;
+}
+// is `col` in the sorted row of n entries?  IN_LDS picks the one pointer that is read (see sr_unique: never one pointer chosen at run time)
+template <bool IN_LDS>
+__device__ __forceinline__ bool rec_drv_find(const int32_t* __restrict__ g_row, const int32_t* s_row, int n, int32_t col) {
+  int lo = 0, hi = n;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    const int32_t v = IN_LDS ? s_row[mid] : g_row[mid];
+    if (v < col) lo = mid + 1;
+    else hi = mid;
+  }
+  return lo < n && (IN_LDS ? s_row[lo] : g_row[lo]) == col;
+}
+
+// The score phase over the nc listed candidates; returns this thread's count of live candidates with a positive score.
+template <bool WEIGHTED, bool IN_LDS>
+__device__ __forceinline__ unsigned rec_drv_score(const RecArgs& a, const RecDriven& dv, int64_t q, unsigned nc, const unsigned* s_keys, const unsigned short* s_cand,
+                                                  double* s_score, const int32_t* s_terms, const int* s_toff) {
+  const int grp = threadIdx.x / REC_DRV_GROUP, gl = threadIdx.x & (REC_DRV_GROUP - 1);
+  unsigned n_pos = 0;
+  for (unsigned j0 = 0; j0 < nc; j0 += REC_DRV_NG) {  // block-uniform: every lane takes part in every shuffle
+    const unsigned j = j0 + (unsigned)grp;
+    const unsigned key = j < nc ? s_keys[s_cand[j]] : REC_TOMB;
+    const bool live = (key & REC_TOMB) == 0;
+    const int32_t item = (int32_t)(key & ~REC_TOMB);
+    double score = 0.0;
+    for (int c = 0; c < a.n_clauses; ++c) {
+      const RecClause& cl = a.c[c];
+      unsigned long long m = 0;
+      if (live) {
+        const int64_t tb = cl.q_row_ptr[q];
+        const int nt = IN_LDS ? s_toff[c + 1] - s_toff[c] : (int)(cl.q_row_ptr[q + 1] - tb);
+        const int32_t* __restrict__ g_row = cl.q_col_idx + tb;
+        const int32_t* s_row = s_terms + (IN_LDS ? s_toff[c] : 0);
+        const int64_t e = nt > 0 ? dv.rows[c].m_row_ptr[item + 1] : 0;
+        for (int64_t t = nt > 0 ? dv.rows[c].m_row_ptr[item] + gl : 0; t < e; t += REC_DRV_GROUP) {
+          const int32_t col = dv.rows[c].m_col_idx[t];
+          if ((unsigned)col >= (unsigned)cl.n_cols || !rec_drv_find<IN_LDS>(g_row, s_row, nt, col)) continue;
+          unsigned wt = 1u;
+          if (WEIGHTED) {  // clamped as the other classes clamp it
+            wt = a.w[c] ? a.w[c][col] : (unsigned)REC_WEIGHT_ONE;
+            wt = wt < 1u ? 1u : wt > (unsigned)REC_WEIGHT_MAX ? (unsigned)REC_WEIGHT_MAX : wt;
+          }
+          m += wt;
+        }
+      }
+      for (int o = REC_DRV_GROUP / 2; o > 0; o >>= 1) m += shfl_xor_u64(m, o);  // exact, inside the group of 16
+      // (the translation unit is compiled with -ffp-contract=off: product, then sum, one rounding each -- the other classes' expression)
+      if (m) score = score + cl.boost * (WEIGHTED ? (double)m * REC_WEIGHT_UNIT : (double)m);
+    }
+    if (gl == 0 && j < nc) {
+      s_score[j] = live ? score : -1.0;
+      n_pos += live && score > 0.0 ? 1u : 0u;
+    }
+  }
+  return n_pos;
+}
+
+template <bool WEIGHTED>
+__global__ __launch_bounds__(REC_THREADS) void rec_driven_kernel(RecArgs a, RecDriven dv) {
+  __shared__ unsigned s_keys[REC_CAP];
+  __shared__ int32_t s_terms[REC_DRV_TERMS];
+  __shared__ unsigned short s_cand[REC_LIMIT];  // slot of every candidate
+  __shared__ double s_score[REC_LIMIT];         // by candidate ordinal; -1: struck by the exclusion row
+  __shared__ SelScratch s_select;
+  __shared__ unsigned s_ncand, s_ngath, s_npos, s_nwin;
+  __shared__ int s_toff[REC_MAX_CLAUSES + 1];   // start of every clause's staged row; s_staged: they all fit
+  __shared__ int s_staged;
+  __shared__ double s_wscore[REC_MAX_NUM];
+  __shared__ int32_t s_wpos[REC_MAX_NUM];
+  __shared__ int32_t s_witem[REC_MAX_NUM];
+
+  const int tid = threadIdx.x, lane = tid & (WAVE - 1), wave = tid / WAVE;
+  const int32_t n_items = a.n_items;
+  const int num = a.num;
+  const uint8_t* __restrict__ mask = a.item_mask;
+  const int32_t* __restrict__ pos_of = a.pos;
+  const bool no_backfill = (a.flags & REC_NO_BACKFILL) != 0;
+  const long long n_mine = (long long)a.ctr[6];
+
+  for (long long at = blockIdx.x; at < n_mine; at += gridDim.x) {
+    const int64_t q = dv.queries[at];
+    for (int s = tid; s < REC_CAP; s += REC_THREADS) s_keys[s] = REC_EMPTY;
+    if (tid == 0) {
+      s_ncand = 0; s_ngath = 0; s_npos = 0; s_nwin = 0;
+      long long total = 0;
+      s_toff[0] = 0;
+      for (int c = 0; c < a.n_clauses; ++c) {
+        total += a.c[c].q_row_ptr[q + 1] - a.c[c].q_row_ptr[q];
+        s_toff[c + 1] = total <= REC_DRV_TERMS ? (int)total : REC_DRV_TERMS;
+      }
+      s_staged = total <= REC_DRV_TERMS ? 1 : 0;
+    }
+    __syncthreads();
+
+    // ---- gather: the union of the driver's columns, eligibility by the claiming lane ----
+    const RecDriver& drv = dv.d[dv.driver_of[q]];
+    const RecRule& dr = a.r[drv.rule];
+    const int64_t vb = dr.q_row_ptr[q], nv = dr.q_row_ptr[q + 1] - vb;
+    unsigned gathered = 0;
+    auto claim = [&](int32_t item) {
+      if ((unsigned)item >= (unsigned)n_items) return;
+      const int slot = rec_drv_claim(s_keys, (unsigned)item, &a.ctr[2]);
+      if (slot < 0) return;
+      ++gathered;
+      if ((!mask || mask[item] != 0) && rec_rules_ok<true>(a, q, item)) {
+        const unsigned j = atomicAdd(&s_ncand, 1u);
+        if (j < (unsigned)REC_LIMIT) s_cand[j] = (unsigned short)slot;
+        else atomicAdd(&a.ctr[2], 1ull);
+      } else {
+        __hip_atomic_store(&s_keys[slot], (unsigned)item | REC_TOMB, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      }
+    };
+    for (int64_t t = 0; t < nv; ++t) {  // short columns: a wave per column; long ones: the whole block
+      const int32_t v = dr.q_col_idx[vb + t];
+      if ((unsigned)v >= (unsigned)dr.n_cols) continue;
+      const int64_t s = drv.m_col_ptr[v], e = drv.m_col_ptr[v + 1];
+      if (e - s >= 2 * REC_THREADS) {
+        for (int64_t p = s + tid; p < e; p += REC_THREADS) claim(drv.m_row_idx[p]);
+      } else if ((int)(t & (REC_NW - 1)) == wave) {
+        for (int64_t p = s + lane; p < e; p += WAVE) claim(drv.m_row_idx[p]);
+      }
+    }
+    if (gathered) atomicAdd(&s_ngath, gathered);
+    const bool staged = s_staged != 0;
+    if (staged)
+      for (int c = 0; c < a.n_clauses; ++c) {
+        const int32_t* __restrict__ row = a.c[c].q_col_idx + a.c[c].q_row_ptr[q];
+        const int off = s_toff[c], n = s_toff[c + 1] - off;
+        for (int x = tid; x < n; x += REC_THREADS) s_terms[off + x] = row[x];
+      }
+    __syncthreads();
+
+    // ---- strike: the exclusion row against the table ----
+    if (a.excl_row_ptr) {
+      const int64_t e = a.excl_row_ptr[q + 1];
+      for (int64_t t = a.excl_row_ptr[q] + tid; t < e; t += REC_THREADS) {
+        const int32_t item = a.excl_col_idx[t];
+        if ((unsigned)item >= (unsigned)n_items) continue;
+        const int slot = rec_drv_slot(s_keys, (unsigned)item);
+        if (slot >= 0) s_keys[slot] = (unsigned)item | REC_TOMB;  // (twice in the row: the same word twice)
+      }
+      __syncthreads();
+    }
+
+    // ---- score: every candidate from its own rows ----
+    const unsigned nc = s_ncand < (unsigned)REC_LIMIT ? s_ncand : (unsigned)REC_LIMIT;
+    const unsigned n_pos = staged ? rec_drv_score<WEIGHTED, true>(a, dv, q, nc, s_keys, s_cand, s_score, s_terms, s_toff)
+                                  : rec_drv_score<WEIGHTED, false>(a, dv, q, nc, s_keys, s_cand, s_score, s_terms, s_toff);
+    if (n_pos) atomicAdd(&s_npos, n_pos);
+    __syncthreads();
+
+    auto dead = [&](unsigned j) -> bool { const double sc = s_score[j]; return sc < 0.0 || (no_backfill && !(sc > 0.0)); };
+    auto cand_pos = [&](unsigned j) -> int32_t {
+      const int32_t item = (int32_t)(s_keys[s_cand[j]] & ~REC_TOMB);
+      return pos_of ? pos_of[item] : item;
+    };
+    // ---- selection: the num-th largest key of the list, dead candidates at (0, 0) ----
+    SelKey thr{0ull, 0u};
+    if (nc > (unsigned)num)
+      thr = sel_kth_largest<REC_THREADS>(
+          nc, (unsigned)num, [&](unsigned j) { return dead(j) ? 0ull : (unsigned long long)__double_as_longlong(s_score[j]); },
+          [&](unsigned j) { return dead(j) ? 0u : ~(unsigned)cand_pos(j); }, SelKey{~0ull, ~0u}, SelKey{0ull, 0u}, s_select);
+    const unsigned long long thi = thr.hi;
+    const unsigned tlo = thr.lo;
+    // ---- winners (at most num: the live keys are distinct), ranked by counting ----
+    for (unsigned j = tid; j < nc; j += REC_THREADS) {
+      if (dead(j)) continue;
+      const double sc = s_score[j];
+      const unsigned long long hi = (unsigned long long)__double_as_longlong(sc);
+      if (hi < thi) continue;
+      const int32_t p = cand_pos(j);
+      if (hi == thi && ~(unsigned)p < tlo) continue;
+      const unsigned w = atomicAdd(&s_nwin, 1u);
+      if (w < (unsigned)REC_MAX_NUM) { s_wscore[w] = sc; s_wpos[w] = p; s_witem[w] = (int32_t)(s_keys[s_cand[j]] & ~REC_TOMB); }
+    }
+    __syncthreads();
+    const unsigned nw = s_nwin < (unsigned)num ? s_nwin : (unsigned)num;  // (more only if fill_order is no permutation)
+    if ((unsigned)tid < nw) {
+      const double sc = s_wscore[tid];
+      const unsigned p = (unsigned)s_wpos[tid];
+      unsigned r = 0;
+      for (unsigned u = 0; u < nw; ++u) {
+        const double su = s_wscore[u];
+        r += (su > sc || (su == sc && ((unsigned)s_wpos[u] < p || ((unsigned)s_wpos[u] == p && u < (unsigned)tid)))) ? 1u : 0u;
+      }
+      a.out_idx[q * num + r] = s_witem[tid];
+      a.out_score[q * num + r] = sc;
+    }
+    if (tid == 0) {
+      a.out_count[q] = (int32_t)nw;
+      atomicAdd(&a.ctr[3], (unsigned long long)s_npos);
+      atomicAdd(&a.ctr[7], (unsigned long long)s_ngath);
+    }
+    __syncthreads();
+  }
+}
+
 __global__ void rec_stats_kernel(const unsigned long long* __restrict__ ctr, int64_t* __restrict__ stats) {
   const int t = threadIdx.x;
-  if (t < REC_STATS_LEN) stats[t] = t < 6 ? (int64_t)ctr[t] : 0;  // ctr[5]: queries of the hashed class (0 with the class off)
+  // ctr[5]: queries of the hashed class (0 with the class off); ctr[6], ctr[7]: queries of the driven class and the items they gathered (0 without drivers)
+  if (t < REC_STATS_LEN) stats[t] = (int64_t)ctr[t];
 }
 
 // urcco_dev_idf_weights: a thread per column.  df = the column's length (clamped to 0 .. n_docs); Lucene's BM25 idf in f64, rounded to units of 2^-15.
@@ -542,7 +820,7 @@ hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t
                             const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
                             int32_t* out_idx, double* out_score, int64_t* stats_dev, unsigned long long* ctr, int32_t* list, int32_t* pos, int32_t g_blocks,
                             unsigned* g_state, unsigned* g_m, int32_t* g_list, double* g_score, int32_t lds_limit, const RecRule* rules, int32_t n_rules,
-                            const uint32_t* const* weights, unsigned long long* g_m64, const RecHashed* hashed) {
+                            const uint32_t* const* weights, unsigned long long* g_m64, const RecHashed* hashed, const RecDriven* driven) {
   const bool weighted = weights != nullptr;  // then g_m64 is the counter array of the global class and g_m is not read
   RecArgs a;
   memset(&a, 0, sizeof(a));
@@ -580,8 +858,16 @@ hipError_t launch_recommend(hipStream_t st, int n_cu, int64_t n_queries, int32_t
     }
     int64_t wb = (n_queries + REC_NW - 1) / REC_NW;
     if (wb > (int64_t)n_cu * 8) wb = (int64_t)n_cu * 8;
-    hipLaunchKernelGGL(rec_work_kernel, dim3((unsigned)wb), dim3(REC_THREADS), 0, st, a);
     const int64_t lb = n_queries < (int64_t)n_cu * 2 ? n_queries : (int64_t)n_cu * 2;  // the LDS table lets two blocks share a CU
+    if (driven && n_rules > 0 && driven->n_drivers > 0) {  // the driven queries leave the binning first and are answered by a kernel of their own
+      RecDriven dv = *driven;
+      if (dv.limit > REC_DRIVE_LIMIT) dv.limit = REC_DRIVE_LIMIT;
+      hipLaunchKernelGGL(rec_work_driven_kernel, dim3((unsigned)wb), dim3(REC_THREADS), 0, st, a, dv);
+      if (weighted) hipLaunchKernelGGL((rec_driven_kernel<true>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a, dv);
+      else hipLaunchKernelGGL((rec_driven_kernel<false>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a, dv);
+    } else {
+      hipLaunchKernelGGL(rec_work_kernel, dim3((unsigned)wb), dim3(REC_THREADS), 0, st, a);
+    }
     if (weighted && n_rules > 0) {
       hipLaunchKernelGGL((rec_rows_kernel<0, true, true>), dim3((unsigned)lb), dim3(REC_THREADS), 0, st, a);
       if (hashed) hipLaunchKernelGGL((rec_rows_kernel<2, true, true>), dim3((unsigned)a.h.blocks), dim3(REC_THREADS), 0, st, a);

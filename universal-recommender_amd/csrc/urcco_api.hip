@@ -1213,17 +1213,19 @@ int urcco_dev_props_compact(urcco_session* s, int32_t n_items, const urcco_prop_
 
 }  // extern "C"
 
-// urcco_dev_recommend (n_rules == 0), urcco_dev_recommend_rules and urcco_dev_recommend_weighted (clause_weights != NULL)
+// urcco_dev_recommend (n_rules == 0), urcco_dev_recommend_rules, urcco_dev_recommend_weighted (clause_weights != NULL) and urcco_dev_recommend_driven (allowed_flags
+// with URCCO_REC_DRIVEN; drivers / clause_rows)
 static int recommend_call(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
                           const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
                           int32_t* out_idx, double* out_score, int64_t* stats_dev, const urcco_rec_rule* rules, int32_t n_rules,
-                          const uint32_t* const* clause_weights) {
+                          const uint32_t* const* clause_weights, int32_t allowed_flags = URCCO_REC_NO_BACKFILL | URCCO_REC_HASHED | URCCO_REC_HASHED_AUTO,
+                          const urcco_rec_driver* drivers = nullptr, int32_t n_drivers = 0, const urcco_rec_clause_rows* clause_rows = nullptr) {
   if (!s || n_queries < 0 || n_queries > 0x7fffffffll || n_items < 0 || n_items == 0x7fffffff) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: bad argument");
   if (num < 1 || num > URCCO_REC_MAX_NUM) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: num must lie in 1..%d, got %d", URCCO_REC_MAX_NUM, num);
   if (n_clauses < 0 || n_clauses > URCCO_REC_MAX_CLAUSES || (n_clauses > 0 && !clauses))
     return fail(URCCO_BAD_ARG, "urcco_dev_recommend: between 0 and %d clauses, got %d", URCCO_REC_MAX_CLAUSES, n_clauses);
   if ((excl_row_ptr == nullptr) != (excl_col_idx == nullptr)) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: the exclusion CSR needs both of its arrays");
-  if (flags & ~(URCCO_REC_NO_BACKFILL | URCCO_REC_HASHED | URCCO_REC_HASHED_AUTO)) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: unknown flags %d", flags);
+  if (flags & ~allowed_flags) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: unknown flags %d", flags);
   if (n_queries > 0 && (!out_count || !out_idx || !out_score)) return fail(URCCO_BAD_ARG, "urcco_dev_recommend: output arrays missing");
   urcco::RecClause cl[URCCO_REC_MAX_CLAUSES];
   for (int c = 0; c < n_clauses; ++c) {
@@ -1246,6 +1248,34 @@ static int recommend_call(urcco_session* s, int64_t n_queries, int32_t n_items, 
       return fail(URCCO_BAD_ARG, "urcco_dev_recommend_rules: rule %d: unknown kind %d", j, in.kind);
     }
     rl[j] = urcco::RecRule{in.m_row_ptr, in.m_col_idx, in.q_row_ptr, in.q_col_idx, in.item_value, in.q_lo, in.q_hi, in.kind, in.n_cols};
+  }
+  // The driven class (D32): every driver names an ANY rule of the call, once; they travel ascending by rule, so that the lowest rule index wins a tie of d(q).
+  // URCCO_REC_DRIVE_LIMIT lowers the bound d(q) up to which a query runs in it (read per call, never raises it): small test shapes populate both sides with it.
+  if (n_drivers < 0 || n_drivers > URCCO_REC_MAX_RULES || (n_drivers > 0 && !drivers))
+    return fail(URCCO_BAD_ARG, "urcco_dev_recommend_driven: between 0 and %d drivers, got %d", URCCO_REC_MAX_RULES, n_drivers);
+  if (n_drivers > 0 && n_clauses > 0 && !clause_rows) return fail(URCCO_BAD_ARG, "urcco_dev_recommend_driven: drivers need the clauses' rows");
+  urcco::RecDriven dv{};
+  bool drives[URCCO_REC_MAX_RULES] = {};
+  for (int j = 0; j < n_drivers; ++j) {
+    const urcco_rec_driver& in = drivers[j];
+    if (in.rule < 0 || in.rule >= n_rules || rules[in.rule].kind != URCCO_RULE_ANY)
+      return fail(URCCO_BAD_ARG, "urcco_dev_recommend_driven: driver %d: rule %d is no ANY rule of the call", j, in.rule);
+    if (drives[in.rule]) return fail(URCCO_BAD_ARG, "urcco_dev_recommend_driven: driver %d: rule %d is named twice", j, in.rule);
+    if (!in.m_col_ptr || !in.m_row_idx) return fail(URCCO_BAD_ARG, "urcco_dev_recommend_driven: driver %d: bad matrix", j);
+    drives[in.rule] = true;
+  }
+  for (int r = 0; r < n_rules; ++r)
+    for (int j = 0; drives[r] && j < n_drivers; ++j)
+      if (drivers[j].rule == r) dv.d[dv.n_drivers++] = urcco::RecDriver{drivers[j].m_col_ptr, drivers[j].m_row_idx, r, 0};
+  for (int c = 0; n_drivers > 0 && c < n_clauses; ++c) {
+    if (!clause_rows[c].m_row_ptr || !clause_rows[c].m_col_idx) return fail(URCCO_BAD_ARG, "urcco_dev_recommend_driven: clause %d: bad rows", c);
+    dv.rows[c] = urcco::RecClauseRows{clause_rows[c].m_row_ptr, clause_rows[c].m_col_idx};
+  }
+  const bool driven = (flags & URCCO_REC_DRIVEN) != 0 && dv.n_drivers > 0;
+  dv.limit = urcco::REC_DRIVE_LIMIT;
+  if (const char* e = getenv("URCCO_REC_DRIVE_LIMIT")) {
+    const long v = atol(e);
+    if (v >= 0 && v < dv.limit) dv.limit = (int32_t)v;
   }
   // URCCO_REC_LDS_LIMIT lowers the work bound up to which a query runs in the LDS class (read per call): small test shapes reach the global class with it
   int32_t lds_limit = urcco::REC_LDS_LIMIT;
@@ -1281,10 +1311,11 @@ static int recommend_call(urcco_session* s, int64_t n_queries, int32_t n_items, 
   L.add(&g_m64, weighted ? slice : 1);                                                               // ... the weighted call counts in 64 bits instead of g_m
   L.add(&hs.queries, hashed ? (size_t)n_queries : 0).add(&hs.keys, h_slots).add(&hs.m, weighted ? 0 : h_slots).add(&hs.m64, weighted ? h_slots : 0);  // the hashed
   L.add(&hs.list, h_list).add(&hs.score, h_list);                                                                                                     // class's slices
+  L.add(&dv.queries, driven ? (size_t)n_queries : 0).add(&dv.driver_of, driven ? (size_t)n_queries : 0);                                              // the driven class's lists
   URC(L.commit());
   HIPC(urcco::launch_recommend(s->stream, s->n_cu, n_queries, n_items, cl, n_clauses, excl_row_ptr, excl_col_idx, item_mask, fill_order, num, flags, out_count, out_idx,
                                out_score, stats_dev, ctr, list, pos, g_blocks, g_state, g_m, g_list, g_score, lds_limit, rl, n_rules, weighted ? clause_weights : nullptr,
-                               g_m64, hashed ? &hs : nullptr));
+                               g_m64, hashed ? &hs : nullptr, driven ? &dv : nullptr));
   return URCCO_OK;
 }
 
@@ -1310,6 +1341,14 @@ int urcco_dev_recommend_weighted(urcco_session* s, int64_t n_queries, int32_t n_
                                  const uint32_t* const* clause_weights) {
   return recommend_call(s, n_queries, n_items, clauses, n_clauses, excl_row_ptr, excl_col_idx, item_mask, fill_order, num, flags, out_count, out_idx, out_score, stats_dev,
                         rules, n_rules, clause_weights);
+}
+
+int urcco_dev_recommend_driven(urcco_session* s, int64_t n_queries, int32_t n_items, const urcco_rec_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr,
+                               const int32_t* excl_col_idx, const uint8_t* item_mask, const int32_t* fill_order, int32_t num, int32_t flags, int32_t* out_count,
+                               int32_t* out_idx, double* out_score, int64_t* stats_dev, const urcco_rec_rule* rules, int32_t n_rules,
+                               const uint32_t* const* clause_weights, const urcco_rec_driver* drivers, int32_t n_drivers, const urcco_rec_clause_rows* clause_rows) {
+  return recommend_call(s, n_queries, n_items, clauses, n_clauses, excl_row_ptr, excl_col_idx, item_mask, fill_order, num, flags, out_count, out_idx, out_score, stats_dev,
+                        rules, n_rules, clause_weights, URCCO_REC_NO_BACKFILL | URCCO_REC_HASHED | URCCO_REC_HASHED_AUTO | URCCO_REC_DRIVEN, drivers, n_drivers, clause_rows);
 }
 
 int urcco_dev_idf_weights(urcco_session* s, int32_t n_cols, const int64_t* ind_col_ptr, int64_t n_docs, uint32_t* out_weight) {

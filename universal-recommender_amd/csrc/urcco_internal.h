@@ -20,7 +20,8 @@ static_assert(urcco::REC_MAX_CLAUSES == URCCO_REC_MAX_CLAUSES && urcco::REC_MAX_
                   urcco::REC_STATS_LEN == URCCO_REC_STATS_LEN && urcco::REC_MAX_RULES == URCCO_REC_MAX_RULES && urcco::REC_RULE_ANY == URCCO_RULE_ANY &&
                   urcco::REC_RULE_NONE == URCCO_RULE_NONE && urcco::REC_RULE_RANGE == URCCO_RULE_RANGE &&
                   urcco::REC_WEIGHT_ONE == URCCO_REC_WEIGHT_ONE && urcco::REC_WEIGHT_MAX == URCCO_REC_WEIGHT_MAX && urcco::REC_HASHED == URCCO_REC_HASHED &&
-                  urcco::REC_HASHED_AUTO == URCCO_REC_HASHED_AUTO && urcco::REC_HASH_CAP_LOG2 == URCCO_REC_HASH_CAP_LOG2 && urcco::REC_HASH_LIMIT == URCCO_REC_HASH_LIMIT,
+                  urcco::REC_HASHED_AUTO == URCCO_REC_HASHED_AUTO && urcco::REC_HASH_CAP_LOG2 == URCCO_REC_HASH_CAP_LOG2 && urcco::REC_HASH_LIMIT == URCCO_REC_HASH_LIMIT &&
+                  urcco::REC_DRIVEN == URCCO_REC_DRIVEN && urcco::REC_DRIVE_LIMIT == URCCO_REC_DRIVE_LIMIT,
               "include/urcco.h and cco_kernels.h agree on the recommendation call");
 static_assert(urcco::HIST_STATS_LEN == URCCO_HIST_STATS_LEN, "include/urcco.h and cco_kernels.h agree on the history calls");
 static_assert(urcco::EVAL_MAX_KS == URCCO_EVAL_MAX_KS, "include/urcco.h and cco_kernels.h agree on the evaluation call");

@@ -219,7 +219,7 @@ class DeviceSession:
         return DevIndicators(item_lo, item_hi, b.n_cols, k, c_rp, c_idx, c_llr, stats, b.row_ptr, b.col_idx)
 
     def recommend(self, n_queries: int, n_items: int, clauses, num: int, excl=None, item_mask: Optional[torch.Tensor] = None,
-                  fill_order: Optional[torch.Tensor] = None, flags: int = 0, stats: bool = True, rules=None, weights=None):
+                  fill_order: Optional[torch.Tensor] = None, flags: int = 0, stats: bool = True, rules=None, weights=None, drivers=None, clause_rows=None):
         """urcco_dev_recommend: the top `num` of sum_c boost_c |T_c(q) ^ I_c(i)| per query row over the eligible items, in the order (score
         desc, backfill position asc).  clauses: (n_cols, boost, ind_col_ptr, ind_row_idx, q_row_ptr, q_col_idx) per should-clause, device
         tensors (the CSC of the indicator matrix, the CSR of the query terms); excl: (row_ptr, col_idx) of the exclusion CSR or None.
@@ -230,7 +230,12 @@ class DeviceSession:
         eligible only when every rule holds for (query, item).
         weights (urcco_dev_recommend_weighted, decision D20; None = the calls above): a list parallel to `clauses` of uint32 device tensors [n_cols] -- the
         clause's term weights in units of 2^-15, 1 .. REC_WEIGHT_MAX, e.g. from idf_weights -- or None for a clause whose terms all weigh REC_WEIGHT_ONE;
-        the score is then sum_c boost_c * (sum of the weights of the shared terms) * 2^-15, still exact and independent of the order of the hits."""
+        the score is then sum_c boost_c * (sum of the weights of the shared terms) * 2^-15, still exact and independent of the order of the hits.
+        drivers (urcco_dev_recommend_driven, decision D32; None = the calls above): per driver (rule index, m_col_ptr, m_row_idx) -- the CSC of the matrix of
+        that ANY rule -- with clause_rows, a list parallel to `clauses` of (ind_row_ptr, ind_col_idx), the CSR explain takes.  With REC_DRIVEN in flags a query
+        whose smallest driver list holds at most REC_DRIVE_LIMIT entries is answered from that list; the results are those of the call without drivers."""
+        if clause_rows is not None and len(clause_rows) != len(clauses):
+            raise ValueError("clause_rows: one (ind_row_ptr, ind_col_idx) pair per clause")
         if weights is not None and len(weights) != len(clauses):
             raise ValueError("weights: one entry (a uint32 tensor or None) per clause")
         arr = (_lib.RecClause * max(len(clauses), 1))()
@@ -243,7 +248,7 @@ class DeviceSession:
         st = self.empty(_lib.REC_STATS_LEN, torch.int64) if stats else None
         args = (self.handle, n_queries, n_items, arr, len(clauses), _ptr(excl[0]) if excl is not None else None, _ptr(excl[1]) if excl is not None else None,
                 _ptr(item_mask), _ptr(fill_order), num, flags, _ptr(o_count), _ptr(o_idx), _ptr(o_score), _ptr(st))
-        if rules is None and weights is None:
+        if rules is None and weights is None and drivers is None:
             self._check(self.lib.urcco_dev_recommend(*args))
         else:
             rules = rules or ()
@@ -255,14 +260,23 @@ class DeviceSession:
                 else:
                     rl[j].n_cols = int(rule[1])
                     rl[j].m_row_ptr, rl[j].m_col_idx, rl[j].q_row_ptr, rl[j].q_col_idx = (_ptr(t) for t in rule[2:6])
-            if weights is None:
+            if weights is None and drivers is None:
                 self._check(self.lib.urcco_dev_recommend_rules(*args, rl, len(rules)))
             else:
-                for c, w in enumerate(weights):
+                for c, w in enumerate(weights or ()):
                     if w is not None and (w.dtype != torch.uint32 or w.numel() < int(clauses[c][0])):
                         raise ValueError(f"weights[{c}]: a uint32 tensor of at least n_cols = {int(clauses[c][0])} entries")
-                wp = (C.c_void_p * max(len(weights), 1))(*[_ptr(w) for w in weights])
-                self._check(self.lib.urcco_dev_recommend_weighted(*args, rl, len(rules), wp))
+                wp = (C.c_void_p * max(len(weights), 1))(*[_ptr(w) for w in weights]) if weights is not None else None
+                if drivers is None:
+                    self._check(self.lib.urcco_dev_recommend_weighted(*args, rl, len(rules), wp))
+                else:
+                    dr = (_lib.RecDriver * max(len(drivers), 1))()
+                    for j, (rule, cp, ri) in enumerate(drivers):
+                        dr[j].rule, dr[j].m_col_ptr, dr[j].m_row_idx = int(rule), _ptr(cp), _ptr(ri)
+                    rows = (_lib.RecClauseRows * max(len(clauses), 1))() if clause_rows is not None else None
+                    for c, (rp, ci) in enumerate(clause_rows or ()):
+                        rows[c].m_row_ptr, rows[c].m_col_idx = _ptr(rp), _ptr(ci)
+                    self._check(self.lib.urcco_dev_recommend_driven(*args, rl, len(rules), wp, dr, len(drivers), rows))
         n = max(n_queries, 0)
         return o_count[:n], o_idx[: n * max(num, 0)].view(n, -1) if n and num > 0 else o_idx[:0], o_score[: n * max(num, 0)].view(n, -1) if n and num > 0 else o_score[:0], st
 

@@ -327,6 +327,27 @@ def _accumulator_flag(algo, accumulator) -> int:
     return _lib.REC_ACCUMULATORS[accumulator]
 
 
+def _filter_plan(algo, filter_plan) -> bool:
+    """None (the algorithm's recommendFilterPlan parameter decides; absent: "walk"), "walk" or "driven" -> whether the recommend calls carry REC_DRIVEN and
+    their ANY rules' CSC as drivers (decision D32).  The results do not depend on it, only whether a rare filter's item list or the term walk serves a query."""
+    if filter_plan is None:
+        filter_plan = getattr(algo.ap, "recommendFilterPlan", None)
+    if filter_plan is None:
+        filter_plan = "walk"
+    if filter_plan not in _lib.REC_FILTER_PLANS:
+        raise ValueError(f"filter_plan: None, 'walk' or 'driven', got {filter_plan!r}")
+    return filter_plan == "driven"
+
+
+def _driven_args(driven: bool, flags: int, rules, matrices, clause_matrices) -> dict:
+    """The extra arguments of DeviceSession.recommend under filter_plan="driven": every ANY rule whose matrix (matrices[j], a _Property or a _Correlator, None
+    for a rule that cannot drive) the model holds as a CSC becomes a driver, every clause gets the CSR explain passes.  No such rule: the call as it was."""
+    drivers = [(j, m.col_ptr, m.row_idx) for j, (r, m) in enumerate(zip(rules or (), matrices)) if m is not None and r[0] == _lib.RULE_ANY] if driven else []
+    if not drivers:
+        return dict(flags=flags)
+    return dict(flags=flags | _lib.REC_DRIVEN, drivers=drivers, clause_rows=[(c.row_ptr, c.col_idx) for c in clause_matrices])
+
+
 def _max_query_events(ap) -> int:
     if ap.indicators:                                                                          # :203-211
         return sum(i.maxItemsPerUser if i.maxItemsPerUser is not None else 100 for i in ap.indicators) * 10
@@ -355,7 +376,7 @@ def _term_name(model: DeviceModel, m, term: int):
 
 
 def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host",
-                  term_weights=None, explain: Optional[int] = None, accumulator: Optional[str] = None) -> List[dict]:
+                  term_weights=None, explain: Optional[int] = None, accumulator: Optional[str] = None, filter_plan: Optional[str] = None) -> List[dict]:
     """URAlgorithm.predict for a list of query dicts: [{"itemScores": [{"item", "score"}, ...]}, ...] in the order of `queries`.
     history: user -> {event name: [item ids, oldest first]} (the event store's view of the user), or a history.DeviceHistory: the event streams
     resident on the device.  With a DeviceHistory the user-history term rows (the ("user", ev) clauses, or the ("hist", ev) ANY rules under
@@ -382,9 +403,14 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
     items, the query item's correlators, the matched property values.  A backfill item gets [].
     accumulator: None (the algorithm's recommendAccumulator parameter, absent: "dense" -- the calls are then today's), "dense", "hashed" (REC_HASHED:
     queries too large for the LDS class run on a per-block hash table whose size follows the query, not the catalogue) or "auto" (REC_HASHED_AUTO: hashed
-    exactly when the dense class would get fewer resident blocks): decision D31.  The results are the same bit for bit."""
+    exactly when the dense class would get fewer resident blocks): decision D31.  The results are the same bit for bit.
+    filter_plan: None (the algorithm's recommendFilterPlan parameter, absent: "walk" -- the calls are then today's), "walk" or "driven" (decision D32): every
+    ANY rule of a call -- a `fields` entry with bias < 0, the history or similar-item rows under userBias / itemBias < 0 -- is passed with the CSC of its
+    matrix as a driver, and a query whose smallest such item list holds at most 3072 entries is answered from that list instead of the term walk and the
+    backfill walk.  The results are the same bit for bit; a model built without properties has no rules and behaves as "walk"."""
     tw = _term_weights(algo, model, term_weights)
     explain = _explain_max(explain)
+    driven = _filter_plan(algo, filter_plan)
     if item_rows not in ("host", "device"):
         raise ValueError(f"item_rows must be 'host' or 'device', got {item_rows!r}")
     dev_items = item_rows == "device"
@@ -565,10 +591,11 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
             qrp, qci = (hist_rows[slot[1]] if slot[0] == "user" and dh is not None else item_dev[slot[1]] if slot[0] == "item" and dev_items else
                         _csr([plans[n][0].get(slot, empty) for n in members], dev))
             clauses.append((c.n_cols, boost, c.col_ptr, c.row_idx, qrp, qci))
-        rules = None
+        rules, rule_m = None, []
         if served:
             rules = []
             for rk in rule_keys:
+                rule_m.append(None)
                 if rk[0] == "range":
                     value = model.dates.get(rk[1])
                     if value is None:                                                           # no item holds the property: nothing passes
@@ -580,8 +607,9 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
                     qrp, qci = (hist_rows[rk[1]] if rk[0] == "hist" and rk[1] in hist_rows else item_dev[rk[1]] if rk[0] == "sim" and dev_items else
                                 _csr([plans[n][4][rk] for n in members], dev))
                     rules.append((_lib.RULE_NONE if rk[0] == "none" else _lib.RULE_ANY, m.n_cols, m.row_ptr, m.col_idx, qrp, qci))
-        count, idx, score, _ = model.sess.recommend(len(members), model.n_items, clauses, fetch, excl, mask_t, model.fill_order, flags, stats=False, rules=rules,
-                                                    weights=weights)
+                    rule_m[-1] = m if rk[0] in ("any", "hist", "sim") else None
+        count, idx, score, _ = model.sess.recommend(len(members), model.n_items, clauses, fetch, excl, mask_t, model.fill_order, stats=False, rules=rules,
+                                                    weights=weights, **_driven_args(driven, flags, rules, rule_m, [c for _, c, _ in slots]))
         why = None
         if explain is not None and clauses:                                                     # the same clauses over the CSR of their matrices (D30)
             why = model.sess.explain(count, idx, [(c.n_cols, boost, c.row_ptr, c.col_idx, cl[4], cl[5], None if weights is None else weights[k])
@@ -686,7 +714,7 @@ def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = Non
 
 def user_recommendations(algo, model: DeviceModel, history, users=None, num: Optional[int] = None, event_names: Optional[Sequence[str]] = None,
                          user_bias: Optional[float] = None, chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None,
-                         explain: Optional[int] = None, accumulator: Optional[str] = None):
+                         explain: Optional[int] = None, accumulator: Optional[str] = None, filter_plan: Optional[str] = None):
     """The per-user table, the user-side twin of similar_items: row n is what batch_predict answers to {"user": users[n]} (with "eventNames", "num" and
     "userBias" where given) over the same DeviceHistory -- the same items in the same order with the same scores -- as three device tensors (count
     int32 [n], idx int32 [n, num], score float64 [n, num]); entries behind count[n] are -1 / 0.0.  No Python work per user: the queries go `chunk`
@@ -697,13 +725,14 @@ def user_recommendations(algo, model: DeviceModel, history, users=None, num: Opt
     the query's `eventNames`, default the model's event types.  user_bias > 0: one should-clause per event type over the user's recent items, boost
     = the bias; user_bias < 0: the rows are ANY rules instead (a model built with item properties, {} will do) -- every query carries them, so an
     unknown user or an event without history matches nothing, as in batch_predict.  The blacklist events' exclusions, backfill, recsModel, item_mask
-    the available / expire date rule around now_ms, term_weights and accumulator are those of batch_predict.
+    the available / expire date rule around now_ms, term_weights, accumulator and filter_plan are those of batch_predict.
     explain: None, or E in 1..64 (decision D30): the result is (count, idx, score, n, clause, term, contrib, names) -- after the three tensors above, n int32
     [n, num] = the listed terms of a slot, clause / term int32 and contrib float64 [n, num, E] = their clause (an index into names, the list of
     ("user", event type) in clause order), column id and boost x weight, in batch_predict's order; zeros behind n.  userBias < 0 leaves no clause: n = 0."""
     from .history import DeviceHistory
     tw = _term_weights(algo, model, term_weights)
     explain = _explain_max(explain)
+    driven = _filter_plan(algo, filter_plan)
     if not isinstance(history, DeviceHistory):
         raise ValueError("user_recommendations needs a history.DeviceHistory (the event streams resident on the device)")
     dh = history
@@ -777,7 +806,9 @@ def user_recommendations(algo, model: DeviceModel, history, users=None, num: Opt
         else:                                                                                   # the clauses in the model's order, as batch_predict lays them out
             clauses = [(c.n_cols, _boost(bias), c.col_ptr, c.row_idx) + hist_rows[c.name] for c in model.correlators if c.name in hist_rows]
             weights = None if tw is None else [tw.get(c.name) for c in model.correlators if c.name in hist_rows]
-        c, i, s, _ = sess.recommend(m, model.n_items, clauses, num, excl, mask_t, model.fill_order, flags, stats=False, rules=rules, weights=weights)
+        rule_m = [None] * len(dates) + [model.by_name[ev] for ev in rule_events]
+        c, i, s, _ = sess.recommend(m, model.n_items, clauses, num, excl, mask_t, model.fill_order, stats=False, rules=rules, weights=weights,
+                                    **_driven_args(driven, flags, rules, rule_m, [x for x in model.correlators if x.name in hist_rows] if clauses else []))
         if explain is not None and clauses:                                                     # outputs behind n come back as zeros
             by = [x for x in model.correlators if x.name in hist_rows]
             _, w_n[lo:lo + m], w_clause[lo:lo + m], w_term[lo:lo + m], w_contrib[lo:lo + m] = sess.explain(

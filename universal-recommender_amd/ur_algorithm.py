@@ -137,6 +137,7 @@ class URAlgorithmParams:
     returnSelf: Optional[bool] = None              # :237
     termWeights: Optional[str] = None              # additive key: the default of the query side's term_weights (decision D20): absent = every matching term scores 1, "idf"
     recommendAccumulator: Optional[str] = None     # additive key: the default of the query side's accumulator (decision D31): absent = "dense", "hashed", "auto"
+    recommendFilterPlan: Optional[str] = None      # additive key: the default of the query side's filter_plan (decision D32): absent = "walk", "driven"
     minEventsPerUser: Optional[int] = None         # additive key: the datasource's minEventsPerUser for train_from_history, which has no DataSource in front of it; absent = 1
 
     @staticmethod
@@ -159,7 +160,7 @@ class URAlgorithmParams:
                                                                   i.get("minLLR")) for i in inds],
             seed=p.get("seed"), num=p.get("num"), maxQueryEvents=p.get("maxQueryEvents"), userBias=p.get("userBias"), itemBias=p.get("itemBias"),
             blacklistEvents=p.get("blacklistEvents"), returnSelf=p.get("returnSelf"), termWeights=p.get("termWeights"),
-            recommendAccumulator=p.get("recommendAccumulator"),
+            recommendAccumulator=p.get("recommendAccumulator"), recommendFilterPlan=p.get("recommendFilterPlan"),
             minEventsPerUser=p.get("minEventsPerUser"))
 
 
@@ -270,7 +271,7 @@ class URAlgorithm:
 
 
     def batch_predict(self, model, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host",
-                      term_weights=None, explain: Optional[int] = None, accumulator: Optional[str] = None) -> List[dict]:
+                      term_weights=None, explain: Optional[int] = None, accumulator: Optional[str] = None, filter_plan: Optional[str] = None) -> List[dict]:
         """URAlgorithm.predict (:484-535) for a batch of queries against a recommend.DeviceModel: user history, similar-item and itemSet
         queries, blacklists, backfill by rank and -- for a model built with item properties -- the business rules (fields, dateRange, available /
         expire dates around now_ms, negative biases); see recommend.batch_predict for what is mirrored and what is left out.  history: the dict
@@ -278,9 +279,11 @@ class URAlgorithm:
         items' own indicator lists are cut on the device instead of planned one by one from a host copy of the matrices.  term_weights (here and in the
         methods below): None = the algorithm parameter termWeights (absent: every matching term scores 1), "none", "idf" or {event or property name:
         uint32 device tensor} -- decision D20, see recommend.py.  explain=E (here, in predict and in user_recommendations; None: nothing changes): every
-        item score gains "because", the at most E terms behind it (decision D30)."""
+        item score gains "because", the at most E terms behind it (decision D30).  filter_plan (here, in predict and in user_recommendations): None = the
+        algorithm parameter recommendFilterPlan (absent: "walk"), "walk" or "driven" -- a query under a rare filter is answered from the filter's item list
+        (decision D32); the results are the same."""
         from .recommend import batch_predict
-        return batch_predict(self, model, queries, history, item_mask, now_ms, item_rows, term_weights, explain, accumulator)
+        return batch_predict(self, model, queries, history, item_mask, now_ms, item_rows, term_weights, explain, accumulator, filter_plan)
 
     def similar_items(self, model, items=None, num: Optional[int] = None, item_bias: Optional[float] = None, return_self: Optional[bool] = None,
                       chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None, accumulator: Optional[str] = None):
@@ -291,11 +294,12 @@ class URAlgorithm:
 
     def user_recommendations(self, model, history, users=None, num: Optional[int] = None, event_names=None, user_bias: Optional[float] = None,
                              chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None, explain: Optional[int] = None,
-                             accumulator: Optional[str] = None):
+                             accumulator: Optional[str] = None, filter_plan: Optional[str] = None):
         """The per-user table of `users` (None: every user id of the history.DeviceHistory) as device tensors (count, idx, score): row n is what
         batch_predict answers to {"user": users[n]} over the same history; see recommend.user_recommendations."""
         from .recommend import user_recommendations
-        return user_recommendations(self, model, history, users, num, event_names, user_bias, chunk, item_mask, now_ms, term_weights, explain, accumulator)
+        return user_recommendations(self, model, history, users, num, event_names, user_bias, chunk, item_mask, now_ms, term_weights, explain, accumulator,
+                                    filter_plan)
 
     def evaluate(self, model, train, test, ks=(1, 5, 10, 20), num: Optional[int] = None, event_names=None, truth_event: Optional[str] = None,
                  chunk: int = 65536, user_bias: Optional[float] = None, item_mask=None, now_ms: Optional[int] = None, term_weights=None,
@@ -312,8 +316,9 @@ class URAlgorithm:
         return DeviceProperties(model.sess, model, self.dateNames).apply(events)
 
     def predict(self, model, query: dict, history, item_mask=None, now_ms: Optional[int] = None, term_weights=None, explain: Optional[int] = None,
-                accumulator: Optional[str] = None) -> dict:
-        return self.batch_predict(model, [query], history, item_mask, now_ms, term_weights=term_weights, explain=explain, accumulator=accumulator)[0]
+                accumulator: Optional[str] = None, filter_plan: Optional[str] = None) -> dict:
+        return self.batch_predict(model, [query], history, item_mask, now_ms, term_weights=term_weights, explain=explain, accumulator=accumulator,
+                                  filter_plan=filter_plan)[0]
 
     def train_events_on_device(self, trainingData, sess) -> List[Tuple[str, IndexedDataset]]:
         """Preparator.prepare + URAlgorithm.calcAll without leaving the GPU in between: the event streams are hashed on
