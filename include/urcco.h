@@ -677,6 +677,38 @@ int urcco_dev_explain(urcco_session* s, int64_t n_queries, int32_t n_items, int3
                       int32_t* out_n,        /* [n_queries * num] */
                       int32_t* out_clause, int32_t* out_term, double* out_contrib /* [n_queries * num * max_terms] */);
 
+/* The audience of an item: for every query item the best num USERS -- "which users for this item", the transposed question of urcco_dev_recommend, answered
+ * from user term rows that already sit on the device (urcco_dev_history_rows).  DESIGN.md decision D33.  For user row u and query item i = items[x]:
+ *   score(u, i) = ((0.0 + boost_0 * (double)m_0) + boost_1 * (double)m_1) + ..., m_c = |T_c(u) ^ row i of I_c|, folded in call order without contraction --
+ *       bit for bit the out_score urcco_dev_recommend writes for (u, i) over the same clauses.  With a weight array on any clause the counter is
+ *       M_c = the sum of the clamped weights (1 .. URCCO_REC_WEIGHT_MAX; a clause without an array: URCCO_REC_WEIGHT_ONE) of the shared terms and the fold
+ *       adds boost_c * ((double)M_c * 2^-15), as urcco_dev_recommend_weighted does.
+ *   eligible    score(u, i) > 0 and i not in row u of the exclusion CSR (ascending, distinct: what urcco_dev_history_rows writes).  No backfill: a user
+ *               without a match is in no audience.
+ *   order       (score desc, user id asc); user id = user_ids[u], or u itself when user_ids is NULL; a row whose id is negative belongs to nobody.  The ids
+ *               of a call, and of all calls that accumulate into one result, are distinct (the caller's duty).
+ *   result      io_count[x] <= num, then io_user[x * num + r], io_score[x * num + r] for r < io_count[x]; entries behind the count are not written.
+ * The result ACCUMULATES: on entry io_* hold the result of the earlier calls over other users (io_count zeroed before the first one), on return that of all
+ * users so far -- a caller walks a user base in chunks, and the final result does not depend on the chunks, the slabs or the grid, bit for bit.
+ * The clauses are urcco_explain_clause with the users in the queries' place: the CSR of I_c (rows duplicate-free, a column outside 0..n_cols never matches),
+ * the CSR of T_c (n_users rows, sorted unique), the weight array, the boost.  The same item may be named twice in items; each copy gets its row.
+ * The query items are cut on the device into tiles of at most 64 items whose rows hold at most URCCO_AUD_TERMS (clause, term) pairs together (the
+ * environment variable URCCO_AUD_TERMS lowers the bound, read per call).  stats (nullable, device, URCCO_AUD_STATS_LEN): [0] tiles, [1] slabs of users,
+ * [2] list compactions, [3] (score, user) candidates kept, [4] table or list overflows (0: the bounds hold by construction); the rest 0.
+ * Enqueues on the session's stream and synchronises once, on the tile plan; scratch from the session's arena; no float atomics, no waiting between blocks.
+ * URCCO_BAD_ARG: num outside 1..URCCO_AUDIENCE_MAX_NUM, n_clauses outside 1..URCCO_REC_MAX_CLAUSES, a boost that is not positive and finite, n_cols < 0, a NULL
+ * array the call needs, one half of the exclusion pair, n_users >= 2^31, n_query * num >= 2^31, an entry of items outside 0..n_items, an item whose own rows
+ * hold more than the bound of pairs (the message names the position in items).  n_query == 0 and n_users == 0 are legal.
+ * ABI: an addition within ABI 305 -- the presence of the symbol is the feature test. */
+#define URCCO_AUDIENCE_MAX_NUM 1024
+#define URCCO_AUD_TERMS 3072
+#define URCCO_AUD_STATS_LEN 8
+int urcco_dev_audience(urcco_session* s, int64_t n_users, const int32_t* user_ids /* device [n_users], nullable */, int32_t n_items,
+                       const int32_t* items /* device [n_query] */, int32_t n_query, const urcco_explain_clause* clauses, int32_t n_clauses,
+                       const int64_t* excl_row_ptr, const int32_t* excl_col_idx /* nullable pair: device CSR n_users x n_items */, int32_t num,
+                       int32_t* io_count /* device [n_query] */, int32_t* io_user, double* io_score /* device [n_query * num] */,
+                       int64_t* stats_dev /* nullable */);
+
 /* Device-resident user history: the event-store half of a batch of queries (getBiasedRecentUserActions, URAlgorithm.scala:795-839; getExcludedItems,
  * :741-767), from event streams that already sit in HBM -- (user id, column id, time) per event and event type, dense ids as urcco_dev_dictionary_lookup
  * yields them.  DESIGN.md decision D17.  For a query user u and event type e with cap max_items (the indicator's maxItemsPerUser):

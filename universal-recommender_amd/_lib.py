@@ -37,6 +37,9 @@ REC_WEIGHT_MAX = 1 << 20   # ... from 1 to 32.0
 EVAL_MAX_KS = 8        # urcco_dev_rank_metrics (URCCO_EVAL_MAX_KS): cut-offs per call
 EXPLAIN_MAX_TERMS = 64  # urcco_dev_explain (URCCO_EXPLAIN_MAX_TERMS): listed terms per result
 EXPLAIN_LDS_TERMS = 8192  # query terms over all clauses up to which urcco_dev_explain stages them in LDS (csrc/cco_explain.h)
+AUDIENCE_MAX_NUM = 1024  # urcco_dev_audience (URCCO_AUDIENCE_MAX_NUM): users per query item
+AUD_TERMS = 3072         # (clause, term) pairs the rows of a tile of query items -- and so of one item -- may hold (URCCO_AUD_TERMS)
+AUD_STATS_LEN = 8        # tiles, slabs, compactions, candidates kept, overflows
 EVAL_TREE_BLOCK = 256  # positions one block of the tree sum reduces (csrc/cco_eval.h): beyond it a further pass runs over the partials
 RANK_POPULAR, RANK_TRENDING, RANK_HOT = 1, 2, 3   # urcco_dev_history_ranks (URCCO_RANK_*): the ranking type = the number of intervals
 RANK_NONE = -(1 << 63)   # the item has no rank in the field (INT64_MIN)
@@ -265,6 +268,7 @@ SYMBOLS = {
     "urcco_dev_rank_metrics": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p, _p, C.POINTER(C.c_int32), C.c_int32, _p, _p, _p, _p, _p, _p]),
     "urcco_dev_tree_sum": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p]),
     "urcco_dev_explain": (C.c_int, [_p, C.c_int64, C.c_int32, C.c_int32, _p, _p, C.POINTER(ExplainClause), C.c_int32, C.c_int32, _p, _p, _p, _p, _p]),
+    "urcco_dev_audience": (C.c_int, [_p, C.c_int64, _p, C.c_int32, _p, C.c_int32, C.POINTER(ExplainClause), C.c_int32, _p, _p, C.c_int32, _p, _p, _p, _p]),
     "urcco_dev_history_index": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_append": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_trim": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p]),

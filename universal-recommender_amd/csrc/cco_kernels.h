@@ -464,6 +464,47 @@ struct ExplArgs {
 };
 hipError_t launch_explain(hipStream_t st, int n_cu, const ExplArgs& a);
 
+// ---- the audience of an item (cco_audience.h, compiled into cco_misc.hip behind cco_explain.h; decision D33) ----------------------
+constexpr int AUDIENCE_MAX_NUM = 1024;  // == URCCO_AUDIENCE_MAX_NUM of include/urcco.h
+constexpr int AUD_STATS_LEN = 8;        // == URCCO_AUD_STATS_LEN
+constexpr int AUD_TILE = 64;            // query items of a tile: a lane each
+constexpr int AUD_SLOTS = 4096;         // slots of a tile's LDS table, 16 bytes each
+constexpr int AUD_TERMS = AUD_SLOTS / 4 * 3;  // == URCCO_AUD_TERMS: most (clause, term) pairs of a tile, load factor 0.75
+constexpr int AUD_ROUND = 256;          // users a block scans between two looks at its lists: one append per user and item at the most
+constexpr int AUD_SLAB_MIN = 8 * AUD_ROUND;  // users of a slab at the least (fewer users: one slab)
+constexpr int AUD_MAX_SLABS = 1024;    // the merge kernel holds the slabs' counts of an item in LDS
+enum { AUD_STAT_TILES = 0, AUD_STAT_SLABS = 1, AUD_STAT_COMPACTIONS = 2, AUD_STAT_KEPT = 3, AUD_STAT_OVERFLOW = 4 };
+enum { AUD_HDR_TILES = 0, AUD_HDR_BAD_INDEX = 1, AUD_HDR_BAD_ROWS = 2, AUD_HDR_LEN = 4 };
+struct AudArgs {
+  ExplClause c[REC_MAX_CLAUSES];  // the clauses as urcco_dev_explain takes them: CSR of I_c, CSR of T_c over the users, weights, boost
+  int64_t n_users;
+  const int32_t* user_ids;        // nullable [n_users]: the id a row is reported and ordered by (NULL: the row number); < 0: nobody
+  const int32_t* items;           // [n_query] query items
+  const int64_t* excl_row_ptr;    // nullable pair: CSR n_users x n_items, rows ascending and distinct
+  const int32_t* excl_col_idx;
+  int32_t* io_count;              // [n_query]           in: the result of the earlier chunks; out: that of all chunks so far
+  int32_t* io_user;               // [n_query * num]
+  double* io_score;               // [n_query * num]
+  unsigned long long* stats;      // [AUD_STATS_LEN], never NULL here
+  int32_t n_query, n_items, n_clauses, num;
+  int32_t limit;                  // pairs of a tile (<= AUD_TERMS)
+  int32_t cap;                    // entries of a list (num + 2 AUD_ROUND)
+  int32_t n_slabs, slab_users;    // slab s = users [s * slab_users, (s + 1) * slab_users), slab_users a multiple of AUD_ROUND
+  int32_t n_tiles, blocks;        // known after the plan: tiles, and blocks of the scan (<= the blocks the lists were sized for)
+  int64_t* prefix;                // scratch [n_query + 1]: exclusive scan of the items' pair counts
+  int32_t* tile_start;            // scratch [n_query + 1]
+  int32_t* hdr;                   // scratch [AUD_HDR_LEN]
+  double* list_score;             // scratch [blocks][AUD_TILE + 1][cap]: a list per tile item, and a spare one
+  int32_t* list_user;
+  int32_t* part_count;            // scratch [n_slabs][n_query]
+  double* part_score;             // scratch [n_slabs][n_query][num]
+  int32_t* part_user;
+};
+// cap, n_slabs, slab_users and blocks (the most the scan will run) from what the host knows before the plan
+void audience_geometry(int64_t n_users, int32_t n_query, int32_t num, int n_cu, AudArgs* a);
+hipError_t launch_audience_plan(hipStream_t st, const AudArgs& a);                 // prefix, tile_start, hdr; stats[0..]
+hipError_t launch_audience(hipStream_t st, const AudArgs& a, bool weighted);      // the scan of the chunk and the merge into io_*
+
 // ---- device-resident user history (cco_history.h, compiled into ingest_kernels.hip; decision D17) ----------------------
 constexpr int HIST_STATS_LEN = 8;   // == URCCO_HIST_STATS_LEN of include/urcco.h
 enum { HIST_STAT_WAVE = 0, HIST_STAT_BLOCK = 1, HIST_STAT_GLOBAL = 2, HIST_STAT_SELECT = 3, HIST_STAT_EXCL_WAVE = 4, HIST_STAT_EXCL_BLOCK = 5, HIST_STAT_OVERFLOW = 6 };

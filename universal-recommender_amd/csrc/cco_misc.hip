@@ -14,6 +14,7 @@
 #include "cco_recommend.h"
 #include "cco_eval.h"
 #include "cco_explain.h"
+#include "cco_audience.h"
 #include "cco_ranks.h"
 
 

@@ -1409,6 +1409,60 @@ int urcco_dev_explain(urcco_session* s, int64_t n_queries, int32_t n_items, int3
   return URCCO_OK;
 }
 
+int urcco_dev_audience(urcco_session* s, int64_t n_users, const int32_t* user_ids, int32_t n_items, const int32_t* items, int32_t n_query,
+                       const urcco_explain_clause* clauses, int32_t n_clauses, const int64_t* excl_row_ptr, const int32_t* excl_col_idx, int32_t num,
+                       int32_t* io_count, int32_t* io_user, double* io_score, int64_t* stats_dev) {
+  if (!s || n_users < 0 || n_users > 0x7fffffffll || n_items < 0 || n_items == 0x7fffffff || n_query < 0) return fail(URCCO_BAD_ARG, "urcco_dev_audience: bad argument");
+  if (num < 1 || num > URCCO_AUDIENCE_MAX_NUM) return fail(URCCO_BAD_ARG, "urcco_dev_audience: num must lie in 1..%d, got %d", URCCO_AUDIENCE_MAX_NUM, num);
+  if (n_clauses < 1 || n_clauses > URCCO_REC_MAX_CLAUSES || !clauses)
+    return fail(URCCO_BAD_ARG, "urcco_dev_audience: between 1 and %d clauses, got %d", URCCO_REC_MAX_CLAUSES, n_clauses);
+  if ((excl_row_ptr == nullptr) != (excl_col_idx == nullptr)) return fail(URCCO_BAD_ARG, "urcco_dev_audience: the exclusion CSR needs both of its arrays");
+  if ((int64_t)n_query * (int64_t)num > 0x7fffffffll) return fail(URCCO_BAD_ARG, "urcco_dev_audience: too many query items");
+  urcco::AudArgs a;
+  memset(&a, 0, sizeof(a));
+  bool weighted = false;
+  for (int c = 0; c < n_clauses; ++c) {
+    const urcco_explain_clause& in = clauses[c];
+    if (!(in.boost > 0.0) || in.boost > 1.7976931348623157e308) return fail(URCCO_BAD_ARG, "urcco_dev_audience: clause %d: the boost must be positive and finite", c);
+    if (in.n_cols < 0 || !in.m_row_ptr || !in.m_col_idx || !in.q_row_ptr || !in.q_col_idx) return fail(URCCO_BAD_ARG, "urcco_dev_audience: clause %d: bad matrix", c);
+    a.c[c] = urcco::ExplClause{in.m_row_ptr, in.m_col_idx, in.q_row_ptr, in.q_col_idx, in.weight, in.boost, in.n_cols, 0};
+    weighted = weighted || in.weight != nullptr;  // without an array every weight is WEIGHT_ONE, which the unweighted kernel computes bit for bit
+  }
+  if (n_query > 0 && (!items || !io_count || !io_user || !io_score)) return fail(URCCO_BAD_ARG, "urcco_dev_audience: an array is missing");
+  // URCCO_AUD_TERMS lowers the (clause, term) pairs a tile may hold (read per call, never raises it; the table stays): small test shapes reach several tiles
+  a.limit = urcco::AUD_TERMS;
+  if (const char* e = getenv("URCCO_AUD_TERMS")) {
+    const long v = atol(e);
+    if (v >= 0 && v < a.limit) a.limit = (int32_t)v;
+  }
+  a.n_users = n_users; a.user_ids = user_ids; a.items = items; a.excl_row_ptr = excl_row_ptr; a.excl_col_idx = excl_col_idx;
+  a.io_count = io_count; a.io_user = io_user; a.io_score = io_score;
+  a.n_query = n_query; a.n_items = n_items; a.n_clauses = n_clauses; a.num = num;
+  urcco::audience_geometry(n_users, n_query, num, s->n_cu, &a);
+  const bool scan = n_query > 0 && n_users > 0;
+  const size_t lists = scan ? (size_t)a.blocks * (size_t)(urcco::AUD_TILE + 1) * (size_t)a.cap : 0;
+  const size_t parts = scan ? (size_t)a.n_slabs * (size_t)n_query : 0;
+  unsigned long long* own_stats;
+  URC(ArenaLayout(s).add(&a.prefix, (size_t)n_query + 1).add(&a.tile_start, (size_t)n_query + 1).add(&a.hdr, urcco::AUD_HDR_LEN).add(&own_stats, urcco::AUD_STATS_LEN)
+          .add(&a.list_score, lists).add(&a.list_user, lists).add(&a.part_count, parts).add(&a.part_score, parts * (size_t)num).add(&a.part_user, parts * (size_t)num)
+          .commit());
+  a.stats = stats_dev ? reinterpret_cast<unsigned long long*>(stats_dev) : own_stats;
+  HIPC(urcco::launch_audience_plan(s->stream, a));
+  int32_t hdr[urcco::AUD_HDR_LEN];  // the call's one synchronisation: the tiles size the grid, a bad item fails the call before anything is scanned
+  HIPC(hipMemcpyAsync(hdr, a.hdr, sizeof(hdr), hipMemcpyDeviceToHost, s->stream));
+  HIPC(hipStreamSynchronize(s->stream));
+  if (hdr[urcco::AUD_HDR_BAD_INDEX] < n_query)
+    return fail(URCCO_BAD_ARG, "urcco_dev_audience: items[%d] lies outside 0..%d", hdr[urcco::AUD_HDR_BAD_INDEX], n_items);
+  if (hdr[urcco::AUD_HDR_BAD_ROWS] < n_query)
+    return fail(URCCO_BAD_ARG, "urcco_dev_audience: items[%d]: its rows hold more than %d (clause, term) pairs, the most a tile serves", hdr[urcco::AUD_HDR_BAD_ROWS],
+                a.limit);
+  a.n_tiles = hdr[urcco::AUD_HDR_TILES];
+  const int64_t n_work = (int64_t)a.n_tiles * a.n_slabs;
+  if (n_work < a.blocks) a.blocks = (int32_t)n_work;
+  HIPC(urcco::launch_audience(s->stream, a, weighted));
+  return URCCO_OK;
+}
+
 int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double* x, double* out) {
   if (!s || n < 0 || n_cols < 1 || n_cols > 1024 || !out || (n > 0 && !x) || n * (int64_t)n_cols > 0x7fffffffll)
     return fail(URCCO_BAD_ARG, "urcco_dev_tree_sum: bad argument");

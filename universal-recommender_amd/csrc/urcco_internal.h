@@ -26,7 +26,9 @@ static_assert(urcco::REC_MAX_CLAUSES == URCCO_REC_MAX_CLAUSES && urcco::REC_MAX_
 static_assert(urcco::HIST_STATS_LEN == URCCO_HIST_STATS_LEN, "include/urcco.h and cco_kernels.h agree on the history calls");
 static_assert(urcco::EVAL_MAX_KS == URCCO_EVAL_MAX_KS, "include/urcco.h and cco_kernels.h agree on the evaluation call");
 static_assert(urcco::EXPLAIN_MAX_TERMS == URCCO_EXPLAIN_MAX_TERMS, "include/urcco.h and cco_kernels.h agree on the explain call");
-static_assert(urcco::RANK_MAX_STREAMS == URCCO_RANK_MAX_STREAMS && urcco::RANK_MAX_FIELDS == URCCO_RANK_MAX_FIELDS && urcco::RANK_NONE == URCCO_RANK_NONE,
+static_assert(urcco::AUDIENCE_MAX_NUM == URCCO_AUDIENCE_MAX_NUM && urcco::AUD_TERMS == URCCO_AUD_TERMS && urcco::AUD_STATS_LEN == URCCO_AUD_STATS_LEN,
+              "include/urcco.h and cco_kernels.h agree on the audience call");
+static_assert(urcco::RANK_MAX_STREAMS ==URCCO_RANK_MAX_STREAMS && urcco::RANK_MAX_FIELDS == URCCO_RANK_MAX_FIELDS && urcco::RANK_NONE == URCCO_RANK_NONE,
               "include/urcco.h and cco_kernels.h agree on the rank calls");
 
 struct urcco_session;

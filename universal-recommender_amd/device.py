@@ -338,6 +338,33 @@ class DeviceSession:
         return (m[: slots * nc].view(n, num, nc), o_n[:slots].view(n, num), o_clause[: slots * mt].view(n, num, mt), o_term[: slots * mt].view(n, num, mt),
                 o_contrib[: slots * mt].view(n, num, mt))
 
+    def audience(self, items: torch.Tensor, n_items: int, clauses, num: int, n_users: int, user_ids: Optional[torch.Tensor] = None, excl=None, out=None,
+                 stats: bool = True):
+        """urcco_dev_audience (decision D33): for every query item (items int32 [n], dense ids) the best `num` users in the order (score desc, user id asc)
+        among the n_users rows of the clauses' term CSRs -- those with a positive score whose exclusion row does not hold the item.  clauses: as explain
+        takes them, (n_cols, boost, ind_row_ptr, ind_col_idx, t_row_ptr, t_col_idx, weight | None), the rows of T_c being the users'.  user_ids: int32
+        [n_users], the id a row is reported and ordered by (None: the row number; < 0: nobody).  excl: (row_ptr, col_idx) over the users or None.
+        out: the (count, user_idx, score) an earlier call returned over OTHER users -- the call accumulates into it; None: a fresh, empty result.
+        Returns (count int32 [n], user_idx int32 [n, num], score float64 [n, num], stats int64 [AUD_STATS_LEN] or None); entries behind the count are
+        -1 / 0.0.  Enqueues and synchronises once, on the tile plan."""
+        n, num = int(items.numel()), int(num)
+        arr = (_lib.ExplainClause * max(len(clauses), 1))()
+        for c, (n_cols, boost, rp, ci, qrp, qci, w) in enumerate(clauses):
+            if w is not None and (w.dtype != torch.uint32 or w.numel() < int(n_cols)):
+                raise ValueError(f"clauses[{c}]: the weight is a uint32 tensor of at least n_cols = {int(n_cols)} entries")
+            arr[c].n_cols, arr[c].boost = int(n_cols), float(boost)
+            arr[c].m_row_ptr, arr[c].m_col_idx, arr[c].q_row_ptr, arr[c].q_col_idx, arr[c].weight = _ptr(rp), _ptr(ci), _ptr(qrp), _ptr(qci), _ptr(w)
+        if out is None:
+            slots = max(n * max(num, 0), 1)
+            out = (torch.zeros(max(n, 1), dtype=torch.int32, device=self.device), torch.full((slots,), -1, dtype=torch.int32, device=self.device),
+                   torch.zeros(slots, dtype=torch.float64, device=self.device))
+        count, user, score = (t.view(-1) for t in out)
+        st = self.empty(_lib.AUD_STATS_LEN, torch.int64) if stats else None
+        self._check(self.lib.urcco_dev_audience(self.handle, n_users, _ptr(user_ids), n_items, _ptr(items), n, arr, len(clauses), _ptr(excl[0]) if excl is not None else None,
+                                               _ptr(excl[1]) if excl is not None else None, num, _ptr(count), _ptr(user), _ptr(score), _ptr(st)))
+        shape = (n, max(num, 0))
+        return count[:n], user[: n * shape[1]].view(shape), score[: n * shape[1]].view(shape), st
+
     def tree_sum(self, x: torch.Tensor) -> torch.Tensor:
         """urcco_dev_tree_sum: the pairwise sums of decision D19 over the rows of a contiguous float64 [n, n_cols] tensor, one per column: what
         `while x.size > 1: x = x[0::2] + x[1::2]` leaves of each column padded with +0.0 to a power of two.  Enqueues, does not synchronise."""

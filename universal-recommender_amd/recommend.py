@@ -821,3 +821,75 @@ def user_recommendations(algo, model: DeviceModel, history, users=None, num: Opt
     if explain is not None:
         return count, idx, score, w_n, w_clause, w_term, w_contrib, names
     return count, idx, score
+
+
+def audience(algo, model: DeviceModel, history, items, num: int = 100, users=None, event_names: Optional[Sequence[str]] = None, term_weights=None,
+             user_chunk: int = 65536):
+    """The audience of every item of `items` (decision D33): the `num` users to whom user_recommendations would give the item its highest scores -- the
+    target group of a campaign, a push for a new or promoted item, a restock mail.  An index by item (the reference's Elasticsearch) cannot answer this;
+    the resident DeviceHistory can.  Returns three device tensors (count int32 [n], user_idx int32 [n, num], score float64 [n, num]) in the order (score
+    desc, user index asc); entries behind count[n] are -1 / 0.0.  score[n, r] is, bit for bit, the score user_recommendations(user_bias > 0, the same
+    event_names and term_weights) gives items[n] in the row of user user_idx[n, r]; a user is in an audience only with a positive score and only when the
+    item is not among the user's exclusions (the blacklist events' items): there is no backfill.  DeviceHistory.user_ids maps the indices of a keyed
+    history back.
+    items: a sequence of item ids, or an int32 tensor of dense ids; the same item may be named twice.  users: None = every user of the history, an int32
+    tensor of distinct dense user ids, or a sequence resolved with DeviceHistory.user_indices.  The users go `user_chunk` at a time through
+    DeviceSession.history_rows -- the cut at maxItemsPerUser and the blacklist are those a user query sees -- and one urcco_dev_audience call a chunk
+    accumulates the result, which does not depend on the chunks.  The clauses are the model's event types that the history holds, boost = the
+    algorithm's userBias when positive, else 1.  Not served: business rules and the date filter on the users' side, an item whose own indicator rows hold
+    more than AUD_TERMS entries (ValueError from the library), the multi-GPU build."""
+    from .history import DeviceHistory
+    if not isinstance(history, DeviceHistory):
+        raise ValueError("audience needs a history.DeviceHistory (the event streams resident on the device)")
+    dh, ap = history, algo.ap
+    sess, dev = model.sess, model.sess.device
+    tw = _term_weights(algo, model, term_weights)
+    model_events = list(algo.modelEventNames)
+    for ev in model_events:
+        if ev not in model.by_name:
+            raise ValueError(f"the model holds no indicator matrix for event {ev!r}")
+    num = int(num)
+    if num < 1 or num > _lib.AUDIENCE_MAX_NUM:
+        raise ValueError(f"num must lie in 1..{_lib.AUDIENCE_MAX_NUM}, got {num}")
+    if user_chunk < 1:
+        raise ValueError("audience needs user_chunk >= 1")
+    bias = float(ap.userBias) if ap.userBias is not None and ap.userBias > 0 else 1.0
+    max_items = {i.name: (i.maxItemsPerUser if i.maxItemsPerUser is not None else 500) for i in ap.indicators} if ap.indicators else {e: 100 for e in model_events}
+    blacklist_events = ap.blacklistEvents if ap.blacklistEvents is not None else [model_events[0]]
+    q_events = list(event_names or model_events)
+    hist_events = [ev for ev in q_events if ev in dh.types and (ev in model.by_name or ev in blacklist_events)]
+    if len(hist_events) > _lib.REC_MAX_CLAUSES:
+        raise ValueError(f"a call names {len(hist_events)} event types, more than the {_lib.REC_MAX_CLAUSES} one history call serves")
+    if torch.is_tensor(items):
+        if items.dtype != torch.int32 or items.dim() != 1:
+            raise ValueError("items as a tensor: dense item ids, int32, one dimension")
+        q_items = items.to(dev).contiguous()
+    else:
+        idx_of = [model.item_index(i) for i in items]
+        if any(i is None for i in idx_of):
+            raise ValueError(f"audience: the model does not know item {list(items)[idx_of.index(None)]!r}")
+        q_items = torch.tensor(idx_of, dtype=torch.int32).to(dev)
+    if users is None:
+        u_all = torch.arange(dh.n_users, dtype=torch.int32, device=dev)
+    elif torch.is_tensor(users):
+        if users.dtype != torch.int32 or users.dim() != 1:
+            raise ValueError("users as a tensor: dense user ids, int32, one dimension")
+        u_all = users.to(dev)
+    else:
+        u_all = torch.tensor(dh.user_indices(users), dtype=torch.int32).to(dev)
+    specs = [(dh.types[ev].n_cols, max_items.get(ev, 100), ev in blacklist_events, dh.types[ev].idx_row_ptr, dh.types[ev].idx_pos, dh.types[ev].items,
+              dh.types[ev].times, dh.types[ev].col_map) for ev in hist_events]
+    by = [c for c in model.correlators if c.name in hist_events]
+    out = None
+    for lo in range(0, int(u_all.numel()), user_chunk):
+        u = u_all[lo:lo + user_chunk].contiguous()
+        if not by:
+            break
+        rows, excl, _ = sess.history_rows(u, dh.n_users, specs, model.n_items)
+        hist_rows = dict(zip(hist_events, rows))
+        clauses = [(c.n_cols, _boost(bias), c.row_ptr, c.col_idx) + hist_rows[c.name] + (None if tw is None else tw.get(c.name),) for c in by]
+        out = sess.audience(q_items, model.n_items, clauses, num, int(u.numel()), u, excl, out, stats=False)[:3]
+    if out is None:                                                                             # no user, or no clause: nobody is in an audience
+        n = int(q_items.numel())
+        out = (torch.zeros(n, dtype=torch.int32, device=dev), torch.full((n, num), -1, dtype=torch.int32, device=dev), torch.zeros((n, num), dtype=torch.float64, device=dev))
+    return out

@@ -301,6 +301,12 @@ class URAlgorithm:
         return user_recommendations(self, model, history, users, num, event_names, user_bias, chunk, item_mask, now_ms, term_weights, explain, accumulator,
                                     filter_plan)
 
+    def audience(self, model, history, items, num: int = 100, users=None, event_names=None, term_weights=None, user_chunk: int = 65536):
+        """The audience of every item of `items` (decision D33): the `num` users of the history.DeviceHistory with the highest user_recommendations
+        score for it, as device tensors (count, user_idx, score) in the order (score desc, user index asc); see recommend.audience."""
+        from .recommend import audience
+        return audience(self, model, history, items, num, users, event_names, term_weights, user_chunk)
+
     def evaluate(self, model, train, test, ks=(1, 5, 10, 20), num: Optional[int] = None, event_names=None, truth_event: Optional[str] = None,
                  chunk: int = 65536, user_bias: Optional[float] = None, item_mask=None, now_ms: Optional[int] = None, term_weights=None,
                  accumulator: Optional[str] = None):
