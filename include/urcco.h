@@ -709,6 +709,40 @@ int urcco_dev_audience(urcco_session* s, int64_t n_users, const int32_t* user_id
                        int32_t* io_count /* device [n_query] */, int32_t* io_user, double* io_score /* device [n_query * num] */,
                        int64_t* stats_dev /* nullable */);
 
+/* The quota rule: a post-pass over a result table that keeps at most max_per_value items per value of a property -- "no more than two items of one brand,
+ * one per seller, at most three per category".  DESIGN.md decision D34.  The table is what urcco_dev_recommend* writes: row r holds its first in_count[r]
+ * entries (clamped to 0..width) of in_idx[r * width + .] / in_score[r * width + .] in result order.  Row r is walked in that order; candidate j is kept iff
+ * its item lies in 0..n_items and, for every rule and every value v the item holds in that rule's property, fewer than the rule's max_per_value items kept
+ * so far in the row hold v.  An item without a value under a rule is not constrained by it; an item that repeats in a row is judged like any other
+ * candidate.  The walk ends at num kept or at in_count[r].
+ *   out_count[r] <= num, then out_idx[r * num + k], out_score[r * num + k] for k < out_count[r]: the kept entries in input order, the score's bits copied
+ *       untouched (no float arithmetic at all); the entries behind the count are -1 / +0.0.
+ *   out_short[r] (nullable) 1 when the row ended below num and in_count[r] == width -- the pool may have been too small, ask again with a wider one --
+ *       else 0.  When out_short[r] == 0 the row equals the answer over an unbounded pool.  Nothing beyond that is claimed.
+ * A rule is the item x value CSR of a list-of-strings property (n_items rows, duplicate-free: a value named twice in a row would count twice) and its
+ * maximum.  stats (nullable, device, URCCO_QUOTA_STATS_LEN, all deterministic): [0] rows served from the LDS tables, [1] rows served from tables in
+ * scratch (a row whose walked rounds hold more values, repeats included, than 3/4 of a wave's LDS table; the environment variable URCCO_QUOTA_LDS_SLOTS
+ * lowers that table per call, never raises it), [2] candidates examined, [3] candidates rejected among them, [4] resolve iterations (at least one per
+ * round of 64 candidates with a live item; more where a candidate's fate hung on an earlier one's), [5] short rows; the rest 0.
+ * Enqueues on the session's stream and synchronises once, on the plan's header; scratch from the session's arena; no waiting between blocks.
+ * URCCO_BAD_ARG: width outside 1..URCCO_REC_MAX_NUM, num outside 1..width, n_rules outside 1..URCCO_QUOTA_MAX_RULES, max_per_value < 1, n_rows < 0 or
+ * >= 2^31, n_items < 0, a NULL array the call needs, a candidate whose item holds more than URCCO_QUOTA_MAX_VALUES values over the call's rules together
+ * (the message names the row and the slot).  n_rows == 0 is legal and does nothing.
+ * ABI: an addition within ABI 305 -- the presence of the symbol is the feature test. */
+#define URCCO_QUOTA_MAX_RULES 4
+#define URCCO_QUOTA_MAX_VALUES 192
+#define URCCO_QUOTA_STATS_LEN 8
+typedef struct urcco_quota_rule {
+  const int64_t* row_ptr;  /* device [n_items + 1] */
+  const int32_t* col_idx;  /* device */
+  int32_t max_per_value;
+  int32_t reserved;        /* 0 */
+} urcco_quota_rule;
+int urcco_dev_quota_cut(urcco_session* s, int64_t n_rows, int32_t width, const int32_t* in_count /* device [n_rows] */,
+                        const int32_t* in_idx, const double* in_score /* device [n_rows * width] */, int32_t n_items, const urcco_quota_rule* rules,
+                        int32_t n_rules, int32_t num, int32_t* out_count /* device [n_rows] */, int32_t* out_idx, double* out_score /* device [n_rows * num] */,
+                        int32_t* out_short /* nullable, device [n_rows] */, int64_t* stats_dev /* nullable */);
+
 /* Device-resident user history: the event-store half of a batch of queries (getBiasedRecentUserActions, URAlgorithm.scala:795-839; getExcludedItems,
  * :741-767), from event streams that already sit in HBM -- (user id, column id, time) per event and event type, dense ids as urcco_dev_dictionary_lookup
  * yields them.  DESIGN.md decision D17.  For a query user u and event type e with cap max_items (the indicator's maxItemsPerUser):

@@ -40,6 +40,10 @@ EXPLAIN_LDS_TERMS = 8192  # query terms over all clauses up to which urcco_dev_e
 AUDIENCE_MAX_NUM = 1024  # urcco_dev_audience (URCCO_AUDIENCE_MAX_NUM): users per query item
 AUD_TERMS = 3072         # (clause, term) pairs the rows of a tile of query items -- and so of one item -- may hold (URCCO_AUD_TERMS)
 AUD_STATS_LEN = 8        # tiles, slabs, compactions, candidates kept, overflows
+QUOTA_MAX_RULES = 4      # urcco_dev_quota_cut (URCCO_QUOTA_MAX_RULES): quota rules per call
+QUOTA_MAX_VALUES = 192   # values one candidate may hold over the call's rules together (URCCO_QUOTA_MAX_VALUES)
+QUOTA_STATS_LEN = 8      # LDS rows, global rows, examined, rejected, resolve iterations, short rows
+QUOTA_LDS_SLOTS = 1024   # slots of a wave's LDS table (csrc/cco_kernels.h); a row whose walked rounds hold more than 3/4 of it in values goes to scratch
 EVAL_TREE_BLOCK = 256  # positions one block of the tree sum reduces (csrc/cco_eval.h): beyond it a further pass runs over the partials
 RANK_POPULAR, RANK_TRENDING, RANK_HOT = 1, 2, 3   # urcco_dev_history_ranks (URCCO_RANK_*): the ranking type = the number of intervals
 RANK_NONE = -(1 << 63)   # the item has no rank in the field (INT64_MIN)
@@ -177,6 +181,11 @@ class ExplainClause(C.Structure):
                 ("q_row_ptr", C.c_void_p), ("q_col_idx", C.c_void_p), ("weight", C.c_void_p)]
 
 
+class QuotaRule(C.Structure):
+    """urcco_quota_rule: the item x value CSR of a list-of-strings property and the most kept items that may share one of its values."""
+    _fields_ = [("row_ptr", C.c_void_p), ("col_idx", C.c_void_p), ("max_per_value", C.c_int32), ("reserved", C.c_int32)]
+
+
 class HistEvent(C.Structure):
     """urcco_hist_event: one event type of urcco_dev_history_bounds / _rows."""
     _fields_ = [("n_cols", C.c_int32), ("max_items", C.c_int32), ("blacklist", C.c_int32), ("reserved", C.c_int32), ("idx_row_ptr", C.c_void_p),
@@ -269,6 +278,7 @@ SYMBOLS = {
     "urcco_dev_tree_sum": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p]),
     "urcco_dev_explain": (C.c_int, [_p, C.c_int64, C.c_int32, C.c_int32, _p, _p, C.POINTER(ExplainClause), C.c_int32, C.c_int32, _p, _p, _p, _p, _p]),
     "urcco_dev_audience": (C.c_int, [_p, C.c_int64, _p, C.c_int32, _p, C.c_int32, C.POINTER(ExplainClause), C.c_int32, _p, _p, C.c_int32, _p, _p, _p, _p]),
+    "urcco_dev_quota_cut": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p, C.c_int32, C.POINTER(QuotaRule), C.c_int32, C.c_int32, _p, _p, _p, _p, _p]),
     "urcco_dev_history_index": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_append": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_trim": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p]),

@@ -505,6 +505,42 @@ void audience_geometry(int64_t n_users, int32_t n_query, int32_t num, int n_cu, 
 hipError_t launch_audience_plan(hipStream_t st, const AudArgs& a);                 // prefix, tile_start, hdr; stats[0..]
 hipError_t launch_audience(hipStream_t st, const AudArgs& a, bool weighted);      // the scan of the chunk and the merge into io_*
 
+// ---- the quota rule over a result table (cco_quota.h, compiled into cco_misc.hip behind cco_audience.h; decision D34) ----------------------
+constexpr int QUOTA_MAX_RULES = 4;      // == URCCO_QUOTA_MAX_RULES of include/urcco.h
+constexpr int QUOTA_MAX_VALUES = 192;   // == URCCO_QUOTA_MAX_VALUES: values one candidate may hold over the call's rules together
+constexpr int QUOTA_STATS_LEN = 8;      // == URCCO_QUOTA_STATS_LEN
+constexpr int QUOTA_LDS_SLOTS = 1024;   // slots of a wave's LDS table, 16 bytes each (key | count, lane set): 64 KiB a block of four waves
+constexpr int QUOTA_GLOBAL_SLOTS = 1 << 16;  // slots of a resident wave's table in arena scratch: REC_MAX_NUM x QUOTA_MAX_VALUES at load 3/4
+constexpr int QUOTA_GLOBAL_WAVES = 128;      // resident waves of the global tier at the most (1 MiB of scratch each)
+enum { QUOTA_STAT_LDS_ROWS = 0, QUOTA_STAT_GLOBAL_ROWS = 1, QUOTA_STAT_EXAMINED = 2, QUOTA_STAT_REJECTED = 3, QUOTA_STAT_ITERATIONS = 4, QUOTA_STAT_SHORT = 5 };
+enum { QUOTA_HDR_BAD = 0, QUOTA_HDR_OVERFLOWS = 1, QUOTA_HDR_LEN = 2 };
+struct QuotaRule {
+  const int64_t* row_ptr;         // CSR item x value of a list-of-strings property, rows duplicate-free
+  const int32_t* col_idx;
+  int32_t max_per_value, pad;
+};
+struct QuotaArgs {
+  QuotaRule rule[QUOTA_MAX_RULES];
+  const int32_t* in_count;        // [n_rows]
+  const int32_t* in_idx;          // [n_rows * width]
+  const unsigned long long* in_score;  // [n_rows * width] the scores as words: copied, never computed with
+  int32_t* out_count;             // [n_rows]
+  int32_t* out_idx;               // [n_rows * num]
+  unsigned long long* out_score;  // [n_rows * num]
+  int32_t* out_short;             // nullable [n_rows]
+  unsigned long long* stats;      // [QUOTA_STATS_LEN], never NULL here
+  int64_t n_rows;
+  int32_t n_items, n_rules, width, num;
+  int32_t lds_slots;              // slots a wave uses of its LDS table: a power of two <= QUOTA_LDS_SLOTS
+  int32_t g_waves;                // resident waves of the global tier
+  unsigned long long* hdr;        // scratch [QUOTA_HDR_LEN]: the first candidate beyond QUOTA_MAX_VALUES as row << 8 | slot (none: all ones); overflowed rows
+  int32_t* ovf_rows;              // scratch [n_rows]: the rows the LDS tier handed on
+  unsigned long long* g_slot;     // scratch [g_waves][QUOTA_GLOBAL_SLOTS]
+  unsigned long long* g_pend;
+};
+hipError_t launch_quota_plan(hipStream_t st, int n_cu, const QuotaArgs& a);  // hdr and stats cleared, then the plan
+hipError_t launch_quota_cut(hipStream_t st, int n_cu, const QuotaArgs& a);   // the LDS tier, then the global tier over its overflow list
+
 // ---- device-resident user history (cco_history.h, compiled into ingest_kernels.hip; decision D17) ----------------------
 constexpr int HIST_STATS_LEN = 8;   // == URCCO_HIST_STATS_LEN of include/urcco.h
 enum { HIST_STAT_WAVE = 0, HIST_STAT_BLOCK = 1, HIST_STAT_GLOBAL = 2, HIST_STAT_SELECT = 3, HIST_STAT_EXCL_WAVE = 4, HIST_STAT_EXCL_BLOCK = 5, HIST_STAT_OVERFLOW = 6 };

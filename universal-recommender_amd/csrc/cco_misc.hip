@@ -15,6 +15,7 @@
 #include "cco_eval.h"
 #include "cco_explain.h"
 #include "cco_audience.h"
+#include "cco_quota.h"
 #include "cco_ranks.h"
 
 

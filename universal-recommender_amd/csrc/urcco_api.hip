@@ -1463,6 +1463,49 @@ int urcco_dev_audience(urcco_session* s, int64_t n_users, const int32_t* user_id
   return URCCO_OK;
 }
 
+int urcco_dev_quota_cut(urcco_session* s, int64_t n_rows, int32_t width, const int32_t* in_count, const int32_t* in_idx, const double* in_score, int32_t n_items,
+                        const urcco_quota_rule* rules, int32_t n_rules, int32_t num, int32_t* out_count, int32_t* out_idx, double* out_score, int32_t* out_short,
+                        int64_t* stats_dev) {
+  if (!s || n_rows < 0 || n_rows > 0x7fffffffll || n_items < 0 || n_items == 0x7fffffff) return fail(URCCO_BAD_ARG, "urcco_dev_quota_cut: bad argument");
+  if (width < 1 || width > URCCO_REC_MAX_NUM) return fail(URCCO_BAD_ARG, "urcco_dev_quota_cut: width must lie in 1..%d, got %d", URCCO_REC_MAX_NUM, width);
+  if (num < 1 || num > width) return fail(URCCO_BAD_ARG, "urcco_dev_quota_cut: num must lie in 1..width = %d, got %d", width, num);
+  if (n_rules < 1 || n_rules > URCCO_QUOTA_MAX_RULES || !rules)
+    return fail(URCCO_BAD_ARG, "urcco_dev_quota_cut: between 1 and %d rules, got %d", URCCO_QUOTA_MAX_RULES, n_rules);
+  urcco::QuotaArgs a;
+  memset(&a, 0, sizeof(a));
+  for (int q = 0; q < n_rules; ++q) {
+    if (rules[q].max_per_value < 1) return fail(URCCO_BAD_ARG, "urcco_dev_quota_cut: rule %d: max_per_value must be at least 1, got %d", q, rules[q].max_per_value);
+    if (!rules[q].row_ptr || !rules[q].col_idx) return fail(URCCO_BAD_ARG, "urcco_dev_quota_cut: rule %d: an array of the property matrix is missing", q);
+    a.rule[q] = urcco::QuotaRule{rules[q].row_ptr, rules[q].col_idx, rules[q].max_per_value, 0};
+  }
+  if (n_rows == 0) return URCCO_OK;
+  if (!in_count || !in_idx || !in_score || !out_count || !out_idx || !out_score) return fail(URCCO_BAD_ARG, "urcco_dev_quota_cut: an array is missing");
+  // URCCO_QUOTA_LDS_SLOTS lowers the slots a wave uses of its LDS table (read per call, never raises them; a power of two, 64 at the least): small test
+  // shapes reach the global tier with it
+  a.lds_slots = urcco::QUOTA_LDS_SLOTS;
+  if (const char* e = getenv("URCCO_QUOTA_LDS_SLOTS")) {
+    const long v = atol(e);
+    while (a.lds_slots > 64 && (long)a.lds_slots > v) a.lds_slots >>= 1;
+  }
+  a.in_count = in_count; a.in_idx = in_idx; a.in_score = reinterpret_cast<const unsigned long long*>(in_score);
+  a.out_count = out_count; a.out_idx = out_idx; a.out_score = reinterpret_cast<unsigned long long*>(out_score); a.out_short = out_short;
+  a.n_rows = n_rows; a.n_items = n_items; a.n_rules = n_rules; a.width = width; a.num = num;
+  a.g_waves = (int32_t)(n_rows < urcco::QUOTA_GLOBAL_WAVES ? n_rows : urcco::QUOTA_GLOBAL_WAVES);
+  unsigned long long* own_stats;
+  URC(ArenaLayout(s).add(&a.hdr, urcco::QUOTA_HDR_LEN).add(&own_stats, urcco::QUOTA_STATS_LEN).add(&a.ovf_rows, (size_t)n_rows)
+          .add(&a.g_slot, (size_t)a.g_waves * urcco::QUOTA_GLOBAL_SLOTS).add(&a.g_pend, (size_t)a.g_waves * urcco::QUOTA_GLOBAL_SLOTS).commit());
+  a.stats = stats_dev ? reinterpret_cast<unsigned long long*>(stats_dev) : own_stats;
+  HIPC(urcco::launch_quota_plan(s->stream, s->n_cu, a));
+  unsigned long long hdr[urcco::QUOTA_HDR_LEN];  // the call's one synchronisation: a candidate beyond the value bound fails the call before anything is cut
+  HIPC(hipMemcpyAsync(hdr, a.hdr, sizeof(hdr), hipMemcpyDeviceToHost, s->stream));
+  HIPC(hipStreamSynchronize(s->stream));
+  if (hdr[urcco::QUOTA_HDR_BAD] != ~0ull)
+    return fail(URCCO_BAD_ARG, "urcco_dev_quota_cut: row %lld, slot %d: the item holds more than %d values over the call's rules, the most a candidate may",
+                (long long)(hdr[urcco::QUOTA_HDR_BAD] >> 8), (int)(hdr[urcco::QUOTA_HDR_BAD] & 255ull), URCCO_QUOTA_MAX_VALUES);
+  HIPC(urcco::launch_quota_cut(s->stream, s->n_cu, a));
+  return URCCO_OK;
+}
+
 int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double* x, double* out) {
   if (!s || n < 0 || n_cols < 1 || n_cols > 1024 || !out || (n > 0 && !x) || n * (int64_t)n_cols > 0x7fffffffll)
     return fail(URCCO_BAD_ARG, "urcco_dev_tree_sum: bad argument");

@@ -28,6 +28,8 @@ static_assert(urcco::EVAL_MAX_KS == URCCO_EVAL_MAX_KS, "include/urcco.h and cco_
 static_assert(urcco::EXPLAIN_MAX_TERMS == URCCO_EXPLAIN_MAX_TERMS, "include/urcco.h and cco_kernels.h agree on the explain call");
 static_assert(urcco::AUDIENCE_MAX_NUM == URCCO_AUDIENCE_MAX_NUM && urcco::AUD_TERMS == URCCO_AUD_TERMS && urcco::AUD_STATS_LEN == URCCO_AUD_STATS_LEN,
               "include/urcco.h and cco_kernels.h agree on the audience call");
+static_assert(urcco::QUOTA_MAX_RULES == URCCO_QUOTA_MAX_RULES && urcco::QUOTA_MAX_VALUES == URCCO_QUOTA_MAX_VALUES && urcco::QUOTA_STATS_LEN == URCCO_QUOTA_STATS_LEN,
+              "include/urcco.h and cco_kernels.h agree on the quota call");
 static_assert(urcco::RANK_MAX_STREAMS ==URCCO_RANK_MAX_STREAMS && urcco::RANK_MAX_FIELDS == URCCO_RANK_MAX_FIELDS && urcco::RANK_NONE == URCCO_RANK_NONE,
               "include/urcco.h and cco_kernels.h agree on the rank calls");
 

@@ -365,6 +365,36 @@ class DeviceSession:
         shape = (n, max(num, 0))
         return count[:n], user[: n * shape[1]].view(shape), score[: n * shape[1]].view(shape), st
 
+    def quota_cut(self, count: torch.Tensor, idx: torch.Tensor, score: torch.Tensor, rules, num: int, n_items: Optional[int] = None, stats: bool = True):
+        """urcco_dev_quota_cut (decision D34): the quota rule over a result table -- count int32 [n], idx int32 [n, width], score float64 [n, width] as
+        recommend returns them.  Every row is walked in result order and a candidate is kept iff, for every rule and every value its item holds in that
+        rule's property, fewer than the rule's maximum of the row's kept items hold the value; the walk ends at `num` kept.  rules: 1..4 of (row_ptr
+        int64 [n_items + 1], col_idx int32, max_per_value) -- the item x value CSR of a list-of-strings property.  n_items: the catalogue's size (None:
+        from the first rule's row_ptr); an index outside it is never kept.  Returns (count int32 [n], idx int32 [n, num], score float64 [n, num] -- the
+        kept entries in input order, score bits untouched, -1 / 0.0 behind the count --, short int32 [n]: 1 where a full pool did not fill the row, stats
+        int64 [QUOTA_STATS_LEN] or None).  Enqueues and synchronises once, on the plan."""
+        n, width, num = int(count.numel()), int(idx.shape[1]) if idx.dim() == 2 else 0, int(num)
+        if idx.dtype != torch.int32 or score.dtype != torch.float64 or count.dtype != torch.int32 or idx.shape != score.shape or idx.dim() != 2 or idx.shape[0] != n:
+            raise ValueError("quota_cut: count int32 [n], idx int32 [n, width] and score float64 [n, width] expected")
+        idx, score, count = idx.contiguous(), score.contiguous(), count.contiguous()
+        arr = (_lib.QuotaRule * max(len(rules), 1))()
+        for q, (rp, ci, most) in enumerate(rules):
+            if rp.dtype != torch.int64 or ci.dtype != torch.int32:
+                raise ValueError(f"rules[{q}]: row_ptr int64 and col_idx int32 expected")
+            arr[q].row_ptr, arr[q].col_idx, arr[q].max_per_value = _ptr(rp), _ptr(ci), int(most)
+        if n_items is None:
+            n_items = int(rules[0][0].numel()) - 1 if rules else 0
+        slots = max(n * max(num, 0), 1)
+        o_count, o_short = self.empty(max(n, 1), torch.int32), self.empty(max(n, 1), torch.int32)
+        o_idx, o_score = self.empty(slots, torch.int32), self.empty(slots, torch.float64)
+        st = self.empty(_lib.QUOTA_STATS_LEN, torch.int64) if stats else None
+        if n == 0 and st is not None:
+            st.zero_()
+        self._check(self.lib.urcco_dev_quota_cut(self.handle, n, width, _ptr(count), _ptr(idx), _ptr(score), n_items, arr, len(rules), num, _ptr(o_count), _ptr(o_idx),
+                                                _ptr(o_score), _ptr(o_short), _ptr(st)))
+        shape = (n, max(num, 0))
+        return o_count[:n], o_idx[: n * shape[1]].view(shape), o_score[: n * shape[1]].view(shape), o_short[:n], st
+
     def tree_sum(self, x: torch.Tensor) -> torch.Tensor:
         """urcco_dev_tree_sum: the pairwise sums of decision D19 over the rows of a contiguous float64 [n, n_cols] tensor, one per column: what
         `while x.size > 1: x = x[0::2] + x[1::2]` leaves of each column padded with +0.0 to a power of two.  Enqueues, does not synchronise."""

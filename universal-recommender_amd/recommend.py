@@ -348,6 +348,38 @@ def _driven_args(driven: bool, flags: int, rules, matrices, clause_matrices) -> 
     return dict(flags=flags | _lib.REC_DRIVEN, drivers=drivers, clause_rows=[(c.row_ptr, c.col_idx) for c in clause_matrices])
 
 
+def _quota_spec(algo, model: DeviceModel, quota) -> tuple:
+    """quota= -> ((property, max), ...), () for none.  None: the algorithm's recommendQuota parameter decides (absent: none); [] switches it off."""
+    if quota is None:
+        quota = getattr(algo.ap, "recommendQuota", None)
+    if not quota:
+        return ()
+    spec = tuple((r["name"], int(r["max"])) for r in quota)
+    if len(spec) > _lib.QUOTA_MAX_RULES:
+        raise ValueError(f"quota: {len(spec)} rules, more than the {_lib.QUOTA_MAX_RULES} one cut serves")
+    for name, most in spec:
+        if model.properties is None or name not in model.properties:
+            raise ValueError(f"quota: the model holds no list property {name!r}")
+        if most < 1:
+            raise ValueError(f"quota: {name!r}: max must be at least 1, got {most}")
+    return spec
+
+
+def _quota_pool(pool, num: int) -> int:
+    """The results the quota is cut from: pool=, default min(256, 4 x num)"""
+    pool = int(pool) if pool is not None else min(_lib.REC_MAX_NUM, 4 * num)
+    if pool < num or pool > _lib.REC_MAX_NUM:
+        raise ValueError(f"pool must lie in num = {num}..{_lib.REC_MAX_NUM}, got {pool}")
+    return pool
+
+
+def _quota_cut(model: DeviceModel, spec: tuple, count, idx, score, num: int):
+    """urcco_dev_quota_cut over a result table (decision D34) -> (count, idx, score, short): per row the first `num` results, in order, that leave every
+    value of every rule's property on at most max items; short: 1 where a full pool did not fill the row."""
+    rules = [(model.properties[name].row_ptr, model.properties[name].col_idx, most) for name, most in spec]
+    return model.sess.quota_cut(count, idx, score, rules, num, model.n_items, stats=False)[:4]
+
+
 def _max_query_events(ap) -> int:
     if ap.indicators:                                                                          # :203-211
         return sum(i.maxItemsPerUser if i.maxItemsPerUser is not None else 100 for i in ap.indicators) * 10
@@ -376,7 +408,8 @@ def _term_name(model: DeviceModel, m, term: int):
 
 
 def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host",
-                  term_weights=None, explain: Optional[int] = None, accumulator: Optional[str] = None, filter_plan: Optional[str] = None) -> List[dict]:
+                  term_weights=None, explain: Optional[int] = None, accumulator: Optional[str] = None, filter_plan: Optional[str] = None, quota=None,
+                  pool: Optional[int] = None) -> List[dict]:
     """URAlgorithm.predict for a list of query dicts: [{"itemScores": [{"item", "score"}, ...]}, ...] in the order of `queries`.
     history: user -> {event name: [item ids, oldest first]} (the event store's view of the user), or a history.DeviceHistory: the event streams
     resident on the device.  With a DeviceHistory the user-history term rows (the ("user", ev) clauses, or the ("hist", ev) ANY rules under
@@ -407,7 +440,11 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
     filter_plan: None (the algorithm's recommendFilterPlan parameter, absent: "walk" -- the calls are then today's), "walk" or "driven" (decision D32): every
     ANY rule of a call -- a `fields` entry with bias < 0, the history or similar-item rows under userBias / itemBias < 0 -- is passed with the CSC of its
     matrix as a driver, and a query whose smallest such item list holds at most 3072 entries is answered from that list instead of the term walk and the
-    backfill walk.  The results are the same bit for bit; a model built without properties has no rules and behaves as "walk"."""
+    backfill walk.  The results are the same bit for bit; a model built without properties has no rules and behaves as "walk".
+    quota, pool: None (the algorithm's recommendQuota parameter, absent: no quota -- the calls are then today's) or [{"name": list property, "max": m},
+    ...] (decision D34); a query's own "quota" key overrides it for that query.  Such a query fetches pool (default min(256, 4 x (from + num))) results
+    and its group -- queries share a call only under the same rule set -- is cut on the device to from + num results that leave every value of every
+    named property on at most m items, before the rows become itemScores.  Not with explain."""
     tw = _term_weights(algo, model, term_weights)
     explain = _explain_max(explain)
     driven = _filter_plan(algo, filter_plan)
@@ -481,6 +518,9 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
             raise ValueError(f"query {n}: num must be >= 1 and from >= 0")
         if start + num > _lib.REC_MAX_NUM:
             raise ValueError(f"query {n}: from + num = {start + num} exceeds {_lib.REC_MAX_NUM}")
+        q_quota = _quota_spec(algo, model, q["quota"] if "quota" in q else quota)
+        if q_quota and explain is not None:
+            raise NotImplementedError("quota and explain in one call are not served: the cut moves the result slots")
         q_events = list(q.get("eventNames") or model_events)
         user, item, item_set = q.get("user"), q.get("item"), list(q.get("itemSet") or [])
         terms: Dict[tuple, np.ndarray] = {}
@@ -536,7 +576,8 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
         for slot, cols in boosted:
             terms[("field",) + slot] = cols
         # a rule cannot be absent for one row of a call: queries share a call only when they carry the same rules and the same property clauses
-        key = (_boost(user_bias), _boost(item_bias), _boost(set_bias), start + num, tuple(slot for slot, _ in boosted), tuple(rules), hist_key)
+        key = (_boost(user_bias), _boost(item_bias), _boost(set_bias), start + num, tuple(slot for slot, _ in boosted), tuple(rules), hist_key,
+               (q_quota, _quota_pool(pool, start + num)) if q_quota else None)
         groups.setdefault(key, []).append(n)
         plans.append((terms, np.unique(np.array([i for i in excl if i is not None], np.int64)), start, num, rules, q_user_ids[n] if dh is not None else -1,
                       user is not None, q_item))
@@ -545,7 +586,7 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
     results: List[Optional[dict]] = [None] * len(queries)
     dev = model.sess.device
     empty = np.zeros(0, np.int64)
-    for (ub, ib, sb, fetch, field_slots, rule_keys, hist_key), members in groups.items():
+    for (ub, ib, sb, fetch, field_slots, rule_keys, hist_key, quota_key), members in groups.items():
         hist_rows: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
         excl = _csr([plans[n][1] for n in members], dev)
         if hist_key is not None and hist_key[0]:                                                # one history call for the group
@@ -608,8 +649,10 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
                                 _csr([plans[n][4][rk] for n in members], dev))
                     rules.append((_lib.RULE_NONE if rk[0] == "none" else _lib.RULE_ANY, m.n_cols, m.row_ptr, m.col_idx, qrp, qci))
                     rule_m[-1] = m if rk[0] in ("any", "hist", "sim") else None
-        count, idx, score, _ = model.sess.recommend(len(members), model.n_items, clauses, fetch, excl, mask_t, model.fill_order, stats=False, rules=rules,
-                                                    weights=weights, **_driven_args(driven, flags, rules, rule_m, [c for _, c, _ in slots]))
+        count, idx, score, _ = model.sess.recommend(len(members), model.n_items, clauses, quota_key[1] if quota_key else fetch, excl, mask_t, model.fill_order,
+                                                    stats=False, rules=rules, weights=weights, **_driven_args(driven, flags, rules, rule_m, [c for _, c, _ in slots]))
+        if quota_key:                                                                           # one cut per group: the rule set is part of its key
+            count, idx, score, _ = _quota_cut(model, quota_key[0], count, idx, score, fetch)
         why = None
         if explain is not None and clauses:                                                     # the same clauses over the CSR of their matrices (D30)
             why = model.sess.explain(count, idx, [(c.n_cols, boost, c.row_ptr, c.col_idx, cl[4], cl[5], None if weights is None else weights[k])
@@ -629,7 +672,8 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
 
 
 def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = None, item_bias: Optional[float] = None, return_self: Optional[bool] = None,
-                  chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None, accumulator: Optional[str] = None):
+                  chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None, accumulator: Optional[str] = None, quota=None,
+                  pool: Optional[int] = None):
     """The item-to-item table ("people who liked this also liked"): row n is what batch_predict answers to {"item": items[n]} -- the same items in the
     same order with the same scores -- as three device tensors (count int32 [n], idx int32 [n, num], score float64 [n, num]); entries behind count[n]
     are -1 / 0.0.  No Python work per item: the queries go `chunk` at a time through DeviceSession.item_rows (decision D18) and recommend, and no
@@ -638,8 +682,14 @@ def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = Non
     as batch_predict serves an unknown item (the backfill alone).  num, item_bias, return_self: default to the algorithm's num (20), itemBias (1.0),
     returnSelf (False).  item_bias > 0: one should-clause per event type of the model over the item's own indicator lists, boost = the bias;
     item_bias < 0: the lists are ANY rules instead (a model built with item properties, {} will do).  The query item is excluded unless return_self.
-    Backfill, recsModel, item_mask, the available / expire date rule around now_ms, term_weights and accumulator are those of batch_predict."""
+    Backfill, recsModel, item_mask, the available / expire date rule around now_ms, term_weights and accumulator are those of batch_predict.
+    quota, pool: as in user_recommendations -- the table is built with num = pool, cut on the device, and `short` is returned as a fourth tensor."""
     ap = algo.ap
+    spec = _quota_spec(algo, model, quota)
+    if spec:
+        num = int(num if num is not None else ap.num if ap.num is not None else 20)
+        table = similar_items(algo, model, items, _quota_pool(pool, num), item_bias, return_self, chunk, item_mask, now_ms, term_weights, accumulator, quota=[])
+        return _quota_cut(model, spec, *table, num)
     sess, dev = model.sess, model.sess.device
     tw = _term_weights(algo, model, term_weights)
     model_events = list(algo.modelEventNames)
@@ -714,7 +764,8 @@ def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = Non
 
 def user_recommendations(algo, model: DeviceModel, history, users=None, num: Optional[int] = None, event_names: Optional[Sequence[str]] = None,
                          user_bias: Optional[float] = None, chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None,
-                         explain: Optional[int] = None, accumulator: Optional[str] = None, filter_plan: Optional[str] = None):
+                         explain: Optional[int] = None, accumulator: Optional[str] = None, filter_plan: Optional[str] = None, quota=None,
+                         pool: Optional[int] = None):
     """The per-user table, the user-side twin of similar_items: row n is what batch_predict answers to {"user": users[n]} (with "eventNames", "num" and
     "userBias" where given) over the same DeviceHistory -- the same items in the same order with the same scores -- as three device tensors (count
     int32 [n], idx int32 [n, num], score float64 [n, num]); entries behind count[n] are -1 / 0.0.  No Python work per user: the queries go `chunk`
@@ -728,8 +779,21 @@ def user_recommendations(algo, model: DeviceModel, history, users=None, num: Opt
     the available / expire date rule around now_ms, term_weights, accumulator and filter_plan are those of batch_predict.
     explain: None, or E in 1..64 (decision D30): the result is (count, idx, score, n, clause, term, contrib, names) -- after the three tensors above, n int32
     [n, num] = the listed terms of a slot, clause / term int32 and contrib float64 [n, num, E] = their clause (an index into names, the list of
-    ("user", event type) in clause order), column id and boost x weight, in batch_predict's order; zeros behind n.  userBias < 0 leaves no clause: n = 0."""
+    ("user", event type) in clause order), column id and boost x weight, in batch_predict's order; zeros behind n.  userBias < 0 leaves no clause: n = 0.
+    quota: None (the algorithm's recommendQuota parameter, absent: no quota -- the call is then today's), or [{"name": list property, "max": m}, ...], at
+    most four (decision D34): the table is built with num = pool (default min(256, 4 x num)) and every row is then cut on the device to its first num
+    results, in order, that leave every value of every named property on at most m of the row's items.  The result is (count, idx, score, short): short
+    int32 [n] is 1 where a full pool did not fill the row (a wider pool might), and a row with short == 0 is the answer over an unbounded pool.  Not with
+    explain.  A property the model does not hold raises ValueError."""
     from .history import DeviceHistory
+    spec = _quota_spec(algo, model, quota)
+    if spec:
+        if explain is not None:
+            raise NotImplementedError("quota and explain in one call are not served: the cut moves the result slots")
+        num = int(num if num is not None else algo.ap.num if algo.ap.num is not None else 20)
+        table = user_recommendations(algo, model, history, users, _quota_pool(pool, num), event_names, user_bias, chunk, item_mask, now_ms, term_weights, None,
+                                     accumulator, filter_plan, quota=[])
+        return _quota_cut(model, spec, *table, num)
     tw = _term_weights(algo, model, term_weights)
     explain = _explain_max(explain)
     driven = _filter_plan(algo, filter_plan)
