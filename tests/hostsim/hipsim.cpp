@@ -51,6 +51,21 @@ std::atomic<long long> g_live[LIVE_KINDS];
 }  // namespace
 void live_add(int kind, long long delta) { g_live[kind].fetch_add(delta, std::memory_order_relaxed); }
 
+// ---- stream audit: operations issued with the null stream ------------------------------------------------
+bool poison_knob_on() {  // as the library reads it (debug_cfg, csrc/urcco_api.hip): once, set and not "0"
+  static const bool on = [] { const char* e = getenv("URCCO_DEBUG_POISON"); return e && *e && *e != '0'; }();
+  return on;
+}
+namespace {
+std::atomic<long long> g_null_ops{0};
+std::mutex g_null_mu;
+char g_null_first[256] = "";  // the first offender since the last reset
+}  // namespace
+void null_stream_op(const char* name) {
+  std::lock_guard<std::mutex> lk(g_null_mu);  // count and name change together (an offender is rare: the lock costs nothing that matters)
+  if (g_null_ops.fetch_add(1, std::memory_order_relaxed) == 0) snprintf(g_null_first, sizeof(g_null_first), "%s", name);
+}
+
 // ---- guard-page allocations (HIPSIM_GUARD=1) ------------------------------------------------------------
 bool guard_on() {
   static const bool on = [] { const char* e = getenv("HIPSIM_GUARD"); return e && *e && *e != '0'; }();
@@ -314,3 +329,16 @@ extern "C" void* hipsim_guard_malloc(size_t n) { return hipsim::guard_alloc(n ? 
 extern "C" void hipsim_guard_release(void* p) { if (p) (void)hipsim::guard_free(p); }
 // objects of `kind` (hipsim::LiveKind: 0 device allocations, 1 host allocations, 2 events, 3 streams) created and not yet destroyed
 extern "C" long long hipsim_live(int kind) { return kind >= 0 && kind < hipsim::LIVE_KINDS ? hipsim::g_live[kind].load() : -1; }
+// stream audit: operations issued with the null stream since the last reset, and the first of them (a kernel's name, or the call's); "" when none
+extern "C" long long hipsim_null_stream_ops(void) { return hipsim::g_null_ops.load(); }
+extern "C" const char* hipsim_null_stream_first(void) {  // a copy taken under the lock, valid until the calling thread asks again
+  static thread_local char copy[sizeof(hipsim::g_null_first)];
+  std::lock_guard<std::mutex> lk(hipsim::g_null_mu);
+  snprintf(copy, sizeof(copy), "%s", hipsim::g_null_ops.load() ? hipsim::g_null_first : "");
+  return copy;
+}
+extern "C" void hipsim_null_stream_reset(void) {
+  std::lock_guard<std::mutex> lk(hipsim::g_null_mu);
+  hipsim::g_null_first[0] = 0;
+  hipsim::g_null_ops.store(0);
+}

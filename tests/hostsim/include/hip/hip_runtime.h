@@ -83,6 +83,15 @@ constexpr size_t GUARD_PAGE = 4096;
 // Live-object counters (tests/test_sim_resources.py): what the library has created and not yet given back, read through hipsim_live(kind).
 enum LiveKind { LIVE_DEVICE = 0, LIVE_HOST = 1, LIVE_EVENT = 2, LIVE_STREAM = 3, LIVE_KINDS = 4 };
 void live_add(int kind, long long delta);
+// Stream audit (tests/test_sim_streams.py): every stream-taking operation issued with the NULL stream, and every blocking one (hipMemcpy, hipMemset,
+// hipDeviceSynchronize: the null stream by definition), is counted and the first one remembered -- a kernel by its name, a call by the call's.  A session
+// of this build always holds a non-null stream, so whatever a session-level call counts here it issued off its stream; on a GPU next to
+// hipStreamNonBlocking streams such an operation is ordered with nothing.  Read through hipsim_null_stream_ops() / hipsim_null_stream_first().
+void null_stream_op(const char* name);
+static inline void audit_stream(const void* st, const char* name) { if (!st) null_stream_op(name); }
+// The one exemption: the blocking hipMemset is not counted while URCCO_DEBUG_POISON is set.  The library's only hipMemset is debug_poison's
+// (csrc/urcco_api.hip), which is reached under that knob alone -- a fault-hunting aid that poisons an arena outside any stream order on purpose.
+bool poison_knob_on();
 static inline void* raw_alloc(size_t n, int kind) {
   void* p = guard_on() ? guard_alloc(n ? n : 1) : malloc(n ? n : 1);
   if (p) live_add(kind, 1);
@@ -104,6 +113,7 @@ static inline void raw_free(void* p, int kind) {
 
 #define hipLaunchKernelGGL(kern, grid, block, shmem, stream, ...) \
   do {                                                                                                              \
+    hipsim::audit_stream(stream, #kern);                                                                             \
     if (hipsim::stream_device(stream) != hipsim::cur_device) hipsim::last_error = hipErrorInvalidHandle;             \
     else hipsim::launch(dim3(grid), dim3(block), [=]() { kern(__VA_ARGS__); });                                      \
   } while (0)
@@ -263,12 +273,12 @@ enum { hipHostMallocDefault = 0, hipHostMallocPortable = 1, hipHostMallocMapped 
 static inline hipError_t hipHostGetDevicePointer(void** dev, void* host, unsigned) { *dev = host; return hipSuccess; }
 static inline hipError_t hipHostMalloc(void** p, size_t n, unsigned = 0) { *p = hipsim::raw_alloc(n, hipsim::LIVE_HOST); return *p ? hipSuccess : hipErrorOutOfMemory; }
 static inline hipError_t hipHostFree(void* p) { hipsim::raw_free(p, hipsim::LIVE_HOST); return hipSuccess; }
-static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { if (n) memcpy(d, s, n); return hipSuccess; }
-static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t = nullptr) { if (n) memcpy(d, s, n); return hipSuccess; }
-static inline hipError_t hipMemset(void* d, int v, size_t n) { if (n) memset(d, v, n); return hipSuccess; }
-static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t = nullptr) { if (n) memset(d, v, n); return hipSuccess; }
-static inline hipError_t hipStreamSynchronize(hipStream_t) { return hipSuccess; }
-static inline hipError_t hipDeviceSynchronize() { return hipSuccess; }
+static inline hipError_t hipMemcpy(void* d, const void* s, size_t n, hipMemcpyKind) { hipsim::null_stream_op("hipMemcpy"); if (n) memcpy(d, s, n); return hipSuccess; }
+static inline hipError_t hipMemcpyAsync(void* d, const void* s, size_t n, hipMemcpyKind, hipStream_t st = nullptr) { hipsim::audit_stream(st, "hipMemcpyAsync"); if (n) memcpy(d, s, n); return hipSuccess; }
+static inline hipError_t hipMemset(void* d, int v, size_t n) { if (!hipsim::poison_knob_on()) hipsim::null_stream_op("hipMemset"); if (n) memset(d, v, n); return hipSuccess; }
+static inline hipError_t hipMemsetAsync(void* d, int v, size_t n, hipStream_t st = nullptr) { hipsim::audit_stream(st, "hipMemsetAsync"); if (n) memset(d, v, n); return hipSuccess; }
+static inline hipError_t hipStreamSynchronize(hipStream_t st) { hipsim::audit_stream(st, "hipStreamSynchronize"); return hipSuccess; }
+static inline hipError_t hipDeviceSynchronize() { hipsim::null_stream_op("hipDeviceSynchronize"); return hipSuccess; }
 static inline hipError_t hipStreamCreate(hipStream_t* s) { *s = new hipsimStream{hipsim::cur_device}; hipsim::live_add(hipsim::LIVE_STREAM, 1); return hipSuccess; }
 static inline hipError_t hipStreamDestroy(hipStream_t s) { if (s) hipsim::live_add(hipsim::LIVE_STREAM, -1); delete static_cast<hipsimStream*>(s); return hipSuccess; }
 enum { hipStreamDefault = 0, hipStreamNonBlocking = 1 };
@@ -301,9 +311,10 @@ template <typename F> static inline hipError_t hipOccupancyMaxActiveBlocksPerMul
 static inline hipError_t hipEventCreate(hipEvent_t* e) { *e = new hipsimEvent(); (*e)->device = hipsim::cur_device; hipsim::live_add(hipsim::LIVE_EVENT, 1); return hipSuccess; }
 enum { hipEventDefault = 0, hipEventDisableTiming = 2 };
 static inline hipError_t hipEventCreateWithFlags(hipEvent_t* e, unsigned) { return hipEventCreate(e); }
-static inline hipError_t hipStreamWaitEvent(hipStream_t, hipEvent_t, unsigned) { return hipSuccess; }
+static inline hipError_t hipStreamWaitEvent(hipStream_t st, hipEvent_t, unsigned) { hipsim::audit_stream(st, "hipStreamWaitEvent"); return hipSuccess; }
 static inline hipError_t hipEventDestroy(hipEvent_t e) { if (e) hipsim::live_add(hipsim::LIVE_EVENT, -1); delete e; return hipSuccess; }
 static inline hipError_t hipEventRecord(hipEvent_t e, hipStream_t st = nullptr) {
+  hipsim::audit_stream(st, "hipEventRecord");
   if (e->device != hipsim::stream_device(st)) return hipErrorInvalidHandle;  // an event belongs to the device it was created on
   e->t = std::chrono::steady_clock::now();
   return hipSuccess;

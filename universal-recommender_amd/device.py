@@ -72,7 +72,15 @@ def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
 
 
 class DeviceSession:
-    """urcco_session bound to a torch device; launches go on torch's current stream for that device."""
+    """urcco_session bound to a torch device and to one stream of it: `stream`, or torch's current stream for that device when the session is made.
+
+    The stream contract.  Every launch, copy, memset and event record of the library goes on the session's stream and on no other; the calls do not
+    synchronise unless their docstring says so.  The Python layer (recommend.py, history.py, properties.py, evaluate.py and the tensors this class
+    allocates) runs its torch ops on torch's CURRENT stream.  So a caller who binds the session to a stream of its own -- `side = torch.cuda.Stream()`,
+    `DeviceSession(device, library, stream=side)` -- makes every call inside `with torch.cuda.stream(side):`, and orders the inputs it prepared elsewhere
+    with that stream itself (an event, or a synchronisation): torch's side streams are non-blocking, the null stream's implicit barrier does not reach
+    them.  A session made on the null stream (stream handle 0) gets a blocking stream the library creates and destroys; a stream the caller passed is
+    never destroyed by the library and outlives the session.  tests/test_sim_streams.py and tests/test_gpu_streams.py hold both halves to this."""
 
     def __init__(self, device: torch.device, library=None, stream: Optional["torch.cuda.Stream"] = None):
         self.device = torch.device(device)
