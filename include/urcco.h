@@ -743,6 +743,38 @@ int urcco_dev_quota_cut(urcco_session* s, int64_t n_rows, int32_t width, const i
                         int32_t n_rules, int32_t num, int32_t* out_count /* device [n_rows] */, int32_t* out_idx, double* out_score /* device [n_rows * num] */,
                         int32_t* out_short /* nullable, device [n_rows] */, int64_t* stats_dev /* nullable */);
 
+/* List metrics of a recommendation table: what a table shows rather than whether it is right -- the companions of MAP and NDCG in offline evaluation
+ * (catalogue coverage, the Gini coefficient of exposure, novelty, intra-list similarity).  DESIGN.md decision D35.  The three calls return exact integers;
+ * the caller forms the floats.  The table and the cut-offs are urcco_dev_rank_metrics': rec_count [n_rows], rec_idx rows strided by num, 1 <= num <=
+ * URCCO_REC_MAX_NUM; ks strictly ascending, each in 1..num, 1 <= n_ks <= URCCO_EVAL_MAX_KS.  c = min(max(rec_count[q], 0), num); nothing at or behind c is
+ * read; an entry outside 0..n_items is skipped everywhere.  x(j) = the smallest x with j < ks[x]; a position j >= ks[n_ks - 1] is ignored.
+ * urcco_dev_list_exposure: inout_bucket[x * n_items + i] += the number of table positions (q, j), j < c, with rec_idx[q * num + j] == i and x(j) == x; a
+ *   repeated entry counts each time.  The call ADDS: a user base walked in chunks accumulates one histogram (zeroed by the caller before the first call),
+ *   and the result depends neither on the chunks nor on the grid.  A block counts a tile of rows into an LDS table and flushes one atomic per distinct
+ *   key; a key that finds the table full goes straight to memory (the environment variable URCCO_EXPO_LDS_SLOTS lowers the table per call, never raises it).
+ * urcco_dev_exposure_stats: out_expo[x * n_items + i] = bucket[0][i] + ... + bucket[x][i], the times item i is shown within the first ks[x] positions;
+ *   out_stats[x * 4 + 0..3] over expo_x = [covered: items with expo > 0, total: sum of expo, sq: sum of expo^2 (modulo 2^64: exact while total < 2^32),
+ *   R: sum over p = 1..n_items of p * c_(p) with c_(1) <= c_(2) <= ... the exposures in ascending order (ties are interchangeable)].  The caller's duty:
+ *   n_items * total < 2^63.  From these, in integers on the host: coverage = covered / n_items, gini = 2 R / (n_items total) - (n_items + 1) / n_items,
+ *   herfindahl = sq / total^2.  The order comes from the radix sort behind urcco_dev_fill_order.
+ * urcco_dev_list_links: against a similarity matrix given as a CSR over the items (n_items rows; the primary event's indicator matrix as the build left it,
+ *   rows in stored order, NOT sorted by column; a row's entries distinct -- a repeated one counts each time).  In row q every valid item has its first
+ *   position; a later repeat of an item is neither a source nor a target.  out_linked[q * n_ks + x] = the number of ordered pairs (a, b), a != b, both
+ *   first positions < min(ks[x], c), such that r_b occurs in row r_a of the matrix; an entry equal to r_a itself is ignored.  out_sums (nullable, ADDED to):
+ *   [sum_q linked[q][x] per x, sum_q m (m - 1) with m = min(ks[x], c) per x].  A wave per row walks the flattened entries of the sources' matrix rows 64 at
+ *   a time: the work of a row is the sum of those rows' lengths.
+ * All enqueue on the session's stream and do not synchronise; scratch (exposure_stats) from the session's arena; no float arithmetic, no float atomics: every
+ * number is reproducible bit for bit.  URCCO_BAD_ARG: num outside 1..URCCO_REC_MAX_NUM, n_ks outside 1..URCCO_EVAL_MAX_KS, ks not strictly ascending or a k
+ * outside 1..num, a negative size, n_rows * n_ks >= 2^31, n_ks * n_items >= 2^31, a NULL array the call needs.  n_rows == 0 and n_items == 0 are legal.
+ * ABI: additions within ABI 305 -- the presence of the symbols is the feature test. */
+int urcco_dev_list_exposure(urcco_session* s, int64_t n_rows, int32_t num, const int32_t* rec_count, const int32_t* rec_idx /* device, rows strided by num */,
+                            int32_t n_items, const int32_t* ks_host, int32_t n_ks, uint32_t* inout_bucket /* device [n_ks * n_items] */);
+int urcco_dev_exposure_stats(urcco_session* s, int32_t n_items, int32_t n_ks, const uint32_t* bucket /* device [n_ks * n_items] */,
+                             int64_t* out_expo /* device [n_ks * n_items] */, int64_t* out_stats /* device [n_ks * 4] */);
+int urcco_dev_list_links(urcco_session* s, int64_t n_rows, int32_t num, const int32_t* rec_count, const int32_t* rec_idx, int32_t n_items,
+                         const int64_t* sim_row_ptr /* device [n_items + 1] */, const int32_t* sim_col_idx /* device */, const int32_t* ks_host, int32_t n_ks,
+                         int32_t* out_linked /* device [n_rows * n_ks] */, int64_t* out_sums /* nullable, device [2 * n_ks] */);
+
 /* Device-resident user history: the event-store half of a batch of queries (getBiasedRecentUserActions, URAlgorithm.scala:795-839; getExcludedItems,
  * :741-767), from event streams that already sit in HBM -- (user id, column id, time) per event and event type, dense ids as urcco_dev_dictionary_lookup
  * yields them.  DESIGN.md decision D17.  For a query user u and event type e with cap max_items (the indicator's maxItemsPerUser):

@@ -279,6 +279,9 @@ SYMBOLS = {
     "urcco_dev_explain": (C.c_int, [_p, C.c_int64, C.c_int32, C.c_int32, _p, _p, C.POINTER(ExplainClause), C.c_int32, C.c_int32, _p, _p, _p, _p, _p]),
     "urcco_dev_audience": (C.c_int, [_p, C.c_int64, _p, C.c_int32, _p, C.c_int32, C.POINTER(ExplainClause), C.c_int32, _p, _p, C.c_int32, _p, _p, _p, _p]),
     "urcco_dev_quota_cut": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p, C.c_int32, C.POINTER(QuotaRule), C.c_int32, C.c_int32, _p, _p, _p, _p, _p]),
+    "urcco_dev_list_exposure": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _p]),
+    "urcco_dev_exposure_stats": (C.c_int, [_p, C.c_int32, C.c_int32, _p, _p, _p]),
+    "urcco_dev_list_links": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, C.c_int32, _p, _p, C.POINTER(C.c_int32), C.c_int32, _p, _p]),
     "urcco_dev_history_index": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_append": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_trim": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p]),

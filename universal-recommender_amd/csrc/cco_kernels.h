@@ -541,6 +541,27 @@ struct QuotaArgs {
 hipError_t launch_quota_plan(hipStream_t st, int n_cu, const QuotaArgs& a);  // hdr and stats cleared, then the plan
 hipError_t launch_quota_cut(hipStream_t st, int n_cu, const QuotaArgs& a);   // the LDS tier, then the global tier over its overflow list
 
+// ---- list metrics of a result table (cco_listmetrics.h, compiled into cco_misc.hip behind cco_ranks.h; decision D35) ----------------------
+constexpr int LM_EXPO_SLOTS = 4096;     // slots of a block's LDS exposure table, 8 bytes each (key, count): 32 KiB a block
+struct ListArgs {
+  const int32_t* rec_count;       // [n_rows]
+  const int32_t* rec_idx;         // [n_rows * num]
+  const int64_t* sim_row_ptr;     // links: CSR over the items, rows in stored order
+  const int32_t* sim_col_idx;
+  unsigned* bucket;               // exposure: [n_ks * n_items], added to
+  int32_t* out_linked;            // links: [n_rows * n_ks]
+  unsigned long long* out_sums;   // links, nullable: [2 * n_ks], added to
+  int64_t n_rows, tile_rows;      // tile_rows: set by launch_list_exposure
+  int32_t num, n_items, n_ks, k_max;
+  int32_t ks[EVAL_MAX_KS];
+  int32_t slots;                  // exposure: slots a block uses of its LDS table, a power of two <= LM_EXPO_SLOTS
+};
+hipError_t launch_list_exposure(hipStream_t st, int n_cu, ListArgs a);
+// expo [n_ks * n_items], stats [n_ks * 4] = covered, total, sum of squares, R per cut-off; w (one field over n_items) and order [n_items]: scratch
+hipError_t launch_exposure_stats(hipStream_t st, int n_cu, int32_t n_items, int32_t n_ks, const uint32_t* bucket, int64_t* out_expo, int64_t* out_stats,
+                                 const FillOrderScratch& w, int32_t* order);
+hipError_t launch_list_links(hipStream_t st, int n_cu, const ListArgs& a);
+
 // ---- device-resident user history (cco_history.h, compiled into ingest_kernels.hip; decision D17) ----------------------
 constexpr int HIST_STATS_LEN = 8;   // == URCCO_HIST_STATS_LEN of include/urcco.h
 enum { HIST_STAT_WAVE = 0, HIST_STAT_BLOCK = 1, HIST_STAT_GLOBAL = 2, HIST_STAT_SELECT = 3, HIST_STAT_EXCL_WAVE = 4, HIST_STAT_EXCL_BLOCK = 5, HIST_STAT_OVERFLOW = 6 };

@@ -17,6 +17,7 @@
 #include "cco_audience.h"
 #include "cco_quota.h"
 #include "cco_ranks.h"
+#include "cco_listmetrics.h"
 
 
 namespace urcco {

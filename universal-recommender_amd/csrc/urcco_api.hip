@@ -1506,6 +1506,67 @@ int urcco_dev_quota_cut(urcco_session* s, int64_t n_rows, int32_t width, const i
   return URCCO_OK;
 }
 
+// the table and cut-off rules the list-metrics calls share with urcco_dev_rank_metrics; fills the table half of `a`
+static int list_args(const char* who, urcco_session* s, int64_t n_rows, int32_t num, const int32_t* rec_count, const int32_t* rec_idx, int32_t n_items,
+                     const int32_t* ks_host, int32_t n_ks, urcco::ListArgs* a) {
+  if (!s || n_rows < 0 || n_items < 0) return fail(URCCO_BAD_ARG, "%s: bad argument", who);
+  if (num < 1 || num > URCCO_REC_MAX_NUM) return fail(URCCO_BAD_ARG, "%s: num must lie in 1..%d, got %d", who, URCCO_REC_MAX_NUM, num);
+  if (n_ks < 1 || n_ks > URCCO_EVAL_MAX_KS || !ks_host) return fail(URCCO_BAD_ARG, "%s: between 1 and %d cut-offs, got %d", who, URCCO_EVAL_MAX_KS, n_ks);
+  for (int x = 0; x < n_ks; ++x)
+    if (ks_host[x] < 1 || ks_host[x] > num || (x > 0 && ks_host[x] <= ks_host[x - 1]))
+      return fail(URCCO_BAD_ARG, "%s: the cut-offs must ascend strictly inside 1..num", who);
+  if (n_rows > 0x7fffffffll / n_ks) return fail(URCCO_BAD_ARG, "%s: too many rows", who);
+  if ((int64_t)n_ks * (int64_t)n_items > 0x7fffffffll) return fail(URCCO_BAD_ARG, "%s: too many items", who);
+  if (n_rows > 0 && (!rec_count || !rec_idx)) return fail(URCCO_BAD_ARG, "%s: an array is missing", who);
+  memset(a, 0, sizeof(*a));
+  a->rec_count = rec_count; a->rec_idx = rec_idx; a->n_rows = n_rows; a->num = num; a->n_items = n_items; a->n_ks = n_ks; a->k_max = ks_host[n_ks - 1];
+  for (int x = 0; x < n_ks; ++x) a->ks[x] = ks_host[x];
+  return URCCO_OK;
+}
+
+int urcco_dev_list_exposure(urcco_session* s, int64_t n_rows, int32_t num, const int32_t* rec_count, const int32_t* rec_idx, int32_t n_items, const int32_t* ks_host,
+                            int32_t n_ks, uint32_t* inout_bucket) {
+  urcco::ListArgs a;
+  URC(list_args("urcco_dev_list_exposure", s, n_rows, num, rec_count, rec_idx, n_items, ks_host, n_ks, &a));
+  if (n_rows == 0 || n_items == 0) return URCCO_OK;
+  if (!inout_bucket) return fail(URCCO_BAD_ARG, "urcco_dev_list_exposure: an array is missing");
+  // URCCO_EXPO_LDS_SLOTS lowers the slots a block uses of its LDS table (read per call, never raises them; a power of two, 16 at the least): small test
+  // shapes reach the straight-to-global path with it
+  a.slots = urcco::LM_EXPO_SLOTS;
+  if (const char* e = getenv("URCCO_EXPO_LDS_SLOTS")) {
+    const long v = atol(e);
+    while (a.slots > 16 && (long)a.slots > v) a.slots >>= 1;
+  }
+  a.bucket = inout_bucket;
+  HIPC(urcco::launch_list_exposure(s->stream, s->n_cu, a));
+  return URCCO_OK;
+}
+
+int urcco_dev_exposure_stats(urcco_session* s, int32_t n_items, int32_t n_ks, const uint32_t* bucket, int64_t* out_expo, int64_t* out_stats) {
+  if (!s || n_items < 0 || !out_stats) return fail(URCCO_BAD_ARG, "urcco_dev_exposure_stats: bad argument");
+  if (n_ks < 1 || n_ks > URCCO_EVAL_MAX_KS) return fail(URCCO_BAD_ARG, "urcco_dev_exposure_stats: between 1 and %d cut-offs, got %d", URCCO_EVAL_MAX_KS, n_ks);
+  if ((int64_t)n_ks * (int64_t)n_items > 0x7fffffffll) return fail(URCCO_BAD_ARG, "urcco_dev_exposure_stats: too many items");
+  if (n_items > 0 && (!bucket || !out_expo)) return fail(URCCO_BAD_ARG, "urcco_dev_exposure_stats: an array is missing");
+  urcco::FillOrderScratch w{};
+  int32_t* order;
+  const size_t n = (size_t)n_items, m = 256 * (size_t)urcco::fill_order_tiles(n_items);
+  URC(ArenaLayout(s).add(&w.keys[0], n).add(&w.keys[1], n).add(&w.ids[0], n).add(&w.ids[1], n).add(&w.differ, 2 * urcco::RANK_MAX_FIELDS).add(&w.hist, m)
+          .add(&w.offsets, m + 1).add(&w.tile_sums, scan_tile_words((int64_t)m)).add(&order, n).commit());
+  HIPC(urcco::launch_exposure_stats(s->stream, s->n_cu, n_items, n_ks, bucket, out_expo, out_stats, w, order));
+  return URCCO_OK;
+}
+
+int urcco_dev_list_links(urcco_session* s, int64_t n_rows, int32_t num, const int32_t* rec_count, const int32_t* rec_idx, int32_t n_items, const int64_t* sim_row_ptr,
+                         const int32_t* sim_col_idx, const int32_t* ks_host, int32_t n_ks, int32_t* out_linked, int64_t* out_sums) {
+  urcco::ListArgs a;
+  URC(list_args("urcco_dev_list_links", s, n_rows, num, rec_count, rec_idx, n_items, ks_host, n_ks, &a));
+  if (n_rows == 0) return URCCO_OK;
+  if (!out_linked || (n_items > 0 && (!sim_row_ptr || !sim_col_idx))) return fail(URCCO_BAD_ARG, "urcco_dev_list_links: an array is missing");
+  a.sim_row_ptr = sim_row_ptr; a.sim_col_idx = sim_col_idx; a.out_linked = out_linked; a.out_sums = reinterpret_cast<unsigned long long*>(out_sums);
+  HIPC(urcco::launch_list_links(s->stream, s->n_cu, a));
+  return URCCO_OK;
+}
+
 int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double* x, double* out) {
   if (!s || n < 0 || n_cols < 1 || n_cols > 1024 || !out || (n > 0 && !x) || n * (int64_t)n_cols > 0x7fffffffll)
     return fail(URCCO_BAD_ARG, "urcco_dev_tree_sum: bad argument");

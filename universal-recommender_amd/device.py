@@ -403,6 +403,61 @@ class DeviceSession:
         shape = (n, max(num, 0))
         return o_count[:n], o_idx[: n * shape[1]].view(shape), o_score[: n * shape[1]].view(shape), o_short[:n], st
 
+    @staticmethod
+    def _table(count: torch.Tensor, idx: torch.Tensor, ks):
+        """(n, num, count, idx, the cut-offs as a list, the same as a host array) of a recommendation table for the list-metrics calls"""
+        n = int(count.numel())
+        if count.dtype != torch.int32 or idx.dtype != torch.int32 or idx.dim() != 2 or idx.shape[0] != n:
+            raise ValueError("count int32 [n] and idx int32 [n, num] expected")
+        ks = [int(k) for k in ks]
+        return n, int(idx.shape[1]), count.contiguous(), idx.contiguous(), ks, (C.c_int32 * max(len(ks), 1))(*ks)
+
+    def list_exposure(self, count: torch.Tensor, idx: torch.Tensor, ks, n_items: int, bucket: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """urcco_dev_list_exposure (decision D35): bucket[x, i] += the positions j < count of the table (count int32 [n], idx int32 [n, num]) that show item i
+        with ks[x - 1] <= j < ks[x].  bucket: the uint32 [n_ks, n_items] tensor an earlier call returned -- the call adds into it, so a table walked in chunks
+        gives one histogram; None: a fresh zeroed one.  Entries outside 0..n_items and positions behind the last cut-off are skipped.  Enqueues, does not
+        synchronise."""
+        n, num, count, idx, ks, ks_arr = self._table(count, idx, ks)
+        if bucket is None:
+            bucket = torch.zeros((len(ks), max(int(n_items), 0)), dtype=torch.uint32, device=self.device)
+        if bucket.dtype != torch.uint32 or tuple(bucket.shape) != (len(ks), int(n_items)) or not bucket.is_contiguous():
+            raise ValueError("bucket: the contiguous uint32 [n_ks, n_items] tensor of an earlier call expected")
+        self._check(self.lib.urcco_dev_list_exposure(self.handle, n, num, _ptr(count), _ptr(idx), int(n_items), ks_arr, len(ks), _ptr(bucket)))
+        return bucket
+
+    def exposure_stats(self, bucket: torch.Tensor):
+        """urcco_dev_exposure_stats (decision D35): from the histogram of list_exposure (uint32 [n_ks, n_items]) -> (expo int64 [n_ks, n_items]: the times an
+        item is shown within the first ks[x] positions, stats int64 [n_ks, 4]: per cut-off the covered items, the total exposure, the sum of its squares and
+        R = sum of ascending rank * exposure).  Enqueues, does not synchronise."""
+        if bucket.dtype != torch.uint32 or bucket.dim() != 2 or not bucket.is_contiguous():
+            raise ValueError("bucket: a contiguous uint32 [n_ks, n_items] tensor expected")
+        n_ks, n_items = int(bucket.shape[0]), int(bucket.shape[1])
+        expo = self.empty(max(n_ks * n_items, 1), torch.int64)
+        stats = self.empty(max(n_ks * 4, 1), torch.int64)
+        self._check(self.lib.urcco_dev_exposure_stats(self.handle, n_items, n_ks, _ptr(bucket), _ptr(expo), _ptr(stats)))
+        return expo[: n_ks * n_items].view(n_ks, n_items), stats[: n_ks * 4].view(n_ks, 4)
+
+    def list_links(self, count: torch.Tensor, idx: torch.Tensor, sim_row_ptr: torch.Tensor, sim_col_idx: torch.Tensor, ks, n_items: int,
+                   sums: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None):
+        """urcco_dev_list_links (decision D35): linked int32 [n, n_ks] -- per table row and cut-off the ordered pairs of distinct listed items (first
+        positions below min(ks[x], count)) of which the first's row of the similarity CSR (sim_row_ptr int64 [n_items + 1], sim_col_idx int32, rows in any
+        order) names the second.  sums: the int64 [2 n_ks] tensor an earlier call returned, added to (None: a fresh zeroed one): [sum of linked per k, sum of
+        m (m - 1) with m = min(k, count) per k].  out: a contiguous int32 [n, n_ks] tensor to write into.  Returns (linked, sums).  Enqueues, does not
+        synchronise."""
+        n, num, count, idx, ks, ks_arr = self._table(count, idx, ks)
+        if sim_row_ptr.dtype != torch.int64 or sim_col_idx.dtype != torch.int32:
+            raise ValueError("sim_row_ptr int64 and sim_col_idx int32 expected")
+        if out is not None and (out.dtype != torch.int32 or tuple(out.shape) != (n, len(ks)) or not out.is_contiguous()):
+            raise ValueError("out: a contiguous int32 [n, n_ks] tensor expected")
+        linked = out.view(-1) if out is not None else self.empty(max(n * len(ks), 1), torch.int32)
+        if sums is None:
+            sums = torch.zeros(max(2 * len(ks), 1), dtype=torch.int64, device=self.device)
+        if sums.dtype != torch.int64 or sums.dim() != 1 or int(sums.numel()) < 2 * len(ks) or not sums.is_contiguous():
+            raise ValueError("sums: the contiguous int64 [2 n_ks] tensor of an earlier call expected")
+        self._check(self.lib.urcco_dev_list_links(self.handle, n, num, _ptr(count), _ptr(idx), int(n_items), _ptr(sim_row_ptr), _ptr(sim_col_idx), ks_arr, len(ks),
+                                                 _ptr(linked), _ptr(sums)))
+        return linked[: n * len(ks)].view(n, len(ks)), sums
+
     def tree_sum(self, x: torch.Tensor) -> torch.Tensor:
         """urcco_dev_tree_sum: the pairwise sums of decision D19 over the rows of a contiguous float64 [n, n_cols] tensor, one per column: what
         `while x.size > 1: x = x[0::2] + x[1::2]` leaves of each column padded with +0.0 to a power of two.  Enqueues, does not synchronise."""

@@ -315,11 +315,19 @@ class URAlgorithm:
 
     def evaluate(self, model, train, test, ks=(1, 5, 10, 20), num: Optional[int] = None, event_names=None, truth_event: Optional[str] = None,
                  chunk: int = 65536, user_bias: Optional[float] = None, item_mask=None, now_ms: Optional[int] = None, term_weights=None,
-                 accumulator: Optional[str] = None):
+                 accumulator: Optional[str] = None, list_metrics: bool = False, popularity=None):
         """Hold-out evaluation on the device (decision D19): precision, hit rate, MAP@k and NDCG@k of the recommendations over the `train` history
-        against the users' `truth_event` items in the `test` history; a list of event mixes gives a list of reports.  See evaluate.evaluate."""
+        against the users' `truth_event` items in the `test` history; a list of event mixes gives a list of reports.  list_metrics: the list metrics
+        of decision D35 over the same tables as well.  See evaluate.evaluate."""
         from .evaluate import evaluate
-        return evaluate(self, model, train, test, ks, num, event_names, truth_event, chunk, user_bias, item_mask, now_ms, term_weights, accumulator)
+        return evaluate(self, model, train, test, ks, num, event_names, truth_event, chunk, user_bias, item_mask, now_ms, term_weights, accumulator, list_metrics,
+                        popularity)
+
+    def list_metrics(self, model, count, idx, ks=(1, 5, 10, 20), popularity=None, chunk: int = 65536, bucket=None):
+        """Coverage, Gini, Herfindahl, intra-list similarity and (with popularity) novelty of a recommendation table at the cut-offs `ks` (decision
+        D35), e.g. of what user_recommendations returns with and without quota=.  See evaluate.list_metrics."""
+        from .evaluate import list_metrics
+        return list_metrics(model, count, idx, ks, popularity, chunk, bucket)
 
     def properties_from_events(self, model, events):
         """A properties.DeviceProperties for `model` over the item property events `events` ($set / $unset / $delete, see DeviceProperties.apply), its
