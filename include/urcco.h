@@ -775,6 +775,38 @@ int urcco_dev_list_links(urcco_session* s, int64_t n_rows, int32_t num, const in
                          const int64_t* sim_row_ptr /* device [n_items + 1] */, const int32_t* sim_col_idx /* device */, const int32_t* ks_host, int32_t n_ks,
                          int32_t* out_linked /* device [n_rows * n_ks] */, int64_t* out_sums /* nullable, device [2 * n_ks] */);
 
+/* Diversified re-rank: a greedy maximal-marginal-relevance (MMR) pass over a result table against the links of a similarity matrix -- the act on the one
+ * number urcco_dev_list_links reports that neither the score nor a quota addresses: the top of a CCO table is often each other's correlators.  DESIGN.md
+ * decision D36.  The table is what urcco_dev_recommend* writes: row r holds its first c = clamp(in_count[r], 0, width) entries of in_idx[r * width + .] /
+ * in_score[r * width + .]; 1 <= width <= URCCO_REC_MAX_NUM, 1 <= num <= width.  The matrix is urcco_dev_list_links': a CSR over the items, n_items rows in
+ * stored order, not sorted by column.  penalty: a finite f64 >= 0.  Per row:
+ *   eligible   position j < c is eligible iff its item lies in 0..n_items and no earlier position of the row holds the same item; no other is ever output.
+ *   link       eligible positions a != b with items x, y are linked iff y occurs in matrix row x OR x occurs in matrix row y: symmetric even where the
+ *              matrix stores the pair once.  Entries outside 0..n_items and an entry equal to its own row are ignored; repeated entries change nothing.
+ *   weight     top = the largest score among the eligible positions; w = fl(penalty * top), or 0 when top <= 0: every link to an item already chosen costs
+ *              `penalty` of the row's best score, under unit weights and under idf weights alike.
+ *   selection  step t = 0 .. min(num, eligible) - 1: for every eligible, unchosen j, n_j = the chosen positions linked to j and key_j = fl(score_j -
+ *              fl(w * (double)n_j)) -- the product first, then the difference, one rounding each, never fused.  The largest key is chosen; on equal keys
+ *              the smaller position.
+ *   The caller's duty: the scores are finite (urcco_dev_recommend* writes them so) and so is penalty * top.
+ * out_count[r] = the steps, then in selection order out_idx, out_score (the INPUT score's bits copied, never the key), out_pos (nullable: the input
+ * position) and out_links (nullable: n_j at the moment of selection), all [n_rows * num]; behind the count -1 / +0.0 / -1 / 0.  penalty == 0 gives the
+ * eligible entries in stable descending-score order.  A wider table may change a row; nothing else is claimed, and there is no `short` flag.
+ * stats (nullable, device, URCCO_DIVERSIFY_STATS_LEN, all deterministic): [0] rows, [1] matrix entries walked (the lengths of the eligible positions' matrix
+ * rows, summed), [2] linked unordered pairs found, [3] rows whose output is the eligible prefix in input order (an empty output included); the rest 0.
+ * A wave per row builds the links as a bit matrix in LDS from the flattened entries of the eligible positions' matrix rows -- the work of a row is the sum
+ * of those rows' lengths -- and selects from registers.  Enqueues on the session's stream and does NOT synchronise; scratch (with stats only) from the
+ * session's arena; no waiting between blocks, no atomic outside LDS, no float atomic: every output is reproducible bit for bit.
+ * URCCO_BAD_ARG: width outside 1..URCCO_REC_MAX_NUM, num outside 1..width, a negative or non-finite penalty, n_rows < 0 or >= 2^31, n_items < 0, a NULL
+ * array the call needs.  n_rows == 0 is legal (stats, where given, are then all 0).
+ * ABI: an addition within ABI 305 -- the presence of the symbol is the feature test. */
+#define URCCO_DIVERSIFY_STATS_LEN 8
+int urcco_dev_diversify(urcco_session* s, int64_t n_rows, int32_t width, const int32_t* in_count /* device [n_rows] */, const int32_t* in_idx,
+                        const double* in_score /* device [n_rows * width] */, int32_t n_items, const int64_t* sim_row_ptr /* device [n_items + 1] */,
+                        const int32_t* sim_col_idx /* device */, double penalty, int32_t num, int32_t* out_count /* device [n_rows] */, int32_t* out_idx,
+                        double* out_score /* device [n_rows * num] */, int32_t* out_pos /* nullable */, int32_t* out_links /* nullable */,
+                        int64_t* stats_dev /* nullable */);
+
 /* Device-resident user history: the event-store half of a batch of queries (getBiasedRecentUserActions, URAlgorithm.scala:795-839; getExcludedItems,
  * :741-767), from event streams that already sit in HBM -- (user id, column id, time) per event and event type, dense ids as urcco_dev_dictionary_lookup
  * yields them.  DESIGN.md decision D17.  For a query user u and event type e with cap max_items (the indicator's maxItemsPerUser):

@@ -44,6 +44,7 @@ QUOTA_MAX_RULES = 4      # urcco_dev_quota_cut (URCCO_QUOTA_MAX_RULES): quota ru
 QUOTA_MAX_VALUES = 192   # values one candidate may hold over the call's rules together (URCCO_QUOTA_MAX_VALUES)
 QUOTA_STATS_LEN = 8      # LDS rows, global rows, examined, rejected, resolve iterations, short rows
 QUOTA_LDS_SLOTS = 1024   # slots of a wave's LDS table (csrc/cco_kernels.h); a row whose walked rounds hold more than 3/4 of it in values goes to scratch
+DIVERSIFY_STATS_LEN = 8  # urcco_dev_diversify (URCCO_DIVERSIFY_STATS_LEN): rows, matrix entries walked, linked pairs, rows left as their eligible prefix
 EVAL_TREE_BLOCK = 256  # positions one block of the tree sum reduces (csrc/cco_eval.h): beyond it a further pass runs over the partials
 RANK_POPULAR, RANK_TRENDING, RANK_HOT = 1, 2, 3   # urcco_dev_history_ranks (URCCO_RANK_*): the ranking type = the number of intervals
 RANK_NONE = -(1 << 63)   # the item has no rank in the field (INT64_MIN)
@@ -282,6 +283,7 @@ SYMBOLS = {
     "urcco_dev_list_exposure": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, C.c_int32, C.POINTER(C.c_int32), C.c_int32, _p]),
     "urcco_dev_exposure_stats": (C.c_int, [_p, C.c_int32, C.c_int32, _p, _p, _p]),
     "urcco_dev_list_links": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, C.c_int32, _p, _p, C.POINTER(C.c_int32), C.c_int32, _p, _p]),
+    "urcco_dev_diversify": (C.c_int, [_p, C.c_int64, C.c_int32, _p, _p, _p, C.c_int32, _p, _p, C.c_double, C.c_int32, _p, _p, _p, _p, _p, _p]),
     "urcco_dev_history_index": (C.c_int, [_p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_append": (C.c_int, [_p, C.c_int64, C.c_int64, _p, _p, C.c_int64, _p, C.c_int64, _p, _p]),
     "urcco_dev_history_trim": (C.c_int, [_p, C.c_int64, _p, _p, C.c_int64, _p, _p, C.c_int64, C.c_int64, _p, _p, _p, _p, _p, _p]),

@@ -562,6 +562,28 @@ hipError_t launch_exposure_stats(hipStream_t st, int n_cu, int32_t n_items, int3
                                  const FillOrderScratch& w, int32_t* order);
 hipError_t launch_list_links(hipStream_t st, int n_cu, const ListArgs& a);
 
+// ---- greedy MMR re-rank of a result table over indicator links (cco_diversify.h, compiled into cco_misc.hip behind cco_listmetrics.h; decision D36) ----
+constexpr int DIV_STATS_LEN = 8;  // == URCCO_DIVERSIFY_STATS_LEN
+struct DivArgs {
+  const int32_t* in_count;             // [n_rows]
+  const int32_t* in_idx;               // [n_rows * width]
+  const unsigned long long* in_score;  // [n_rows * width] f64 as words: the selection computes with them, the output copies them
+  const int64_t* sim_row_ptr;          // CSR over the items, rows in stored order
+  const int32_t* sim_col_idx;
+  int32_t* out_count;                  // [n_rows]
+  int32_t* out_idx;                    // [n_rows * num]
+  unsigned long long* out_score;       // [n_rows * num]
+  int32_t* out_pos;                    // nullable [n_rows * num]
+  int32_t* out_links;                  // nullable [n_rows * num]
+  unsigned long long* stats;           // nullable [DIV_STATS_LEN]
+  unsigned long long* partial;         // scratch [diversify_blocks() * 3] when stats is wanted, else NULL
+  double penalty;
+  int64_t n_rows;
+  int32_t n_items, width, num;
+};
+int64_t diversify_blocks(int64_t n_rows, int n_cu);  // the grid of launch_diversify
+hipError_t launch_diversify(hipStream_t st, int n_cu, const DivArgs& a);  // the rows, then stats from the blocks' partial sums
+
 // ---- device-resident user history (cco_history.h, compiled into ingest_kernels.hip; decision D17) ----------------------
 constexpr int HIST_STATS_LEN = 8;   // == URCCO_HIST_STATS_LEN of include/urcco.h
 enum { HIST_STAT_WAVE = 0, HIST_STAT_BLOCK = 1, HIST_STAT_GLOBAL = 2, HIST_STAT_SELECT = 3, HIST_STAT_EXCL_WAVE = 4, HIST_STAT_EXCL_BLOCK = 5, HIST_STAT_OVERFLOW = 6 };

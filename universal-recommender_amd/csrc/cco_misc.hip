@@ -18,6 +18,7 @@
 #include "cco_quota.h"
 #include "cco_ranks.h"
 #include "cco_listmetrics.h"
+#include "cco_diversify.h"
 
 
 namespace urcco {

@@ -1567,6 +1567,28 @@ int urcco_dev_list_links(urcco_session* s, int64_t n_rows, int32_t num, const in
   return URCCO_OK;
 }
 
+int urcco_dev_diversify(urcco_session* s, int64_t n_rows, int32_t width, const int32_t* in_count, const int32_t* in_idx, const double* in_score, int32_t n_items,
+                        const int64_t* sim_row_ptr, const int32_t* sim_col_idx, double penalty, int32_t num, int32_t* out_count, int32_t* out_idx, double* out_score,
+                        int32_t* out_pos, int32_t* out_links, int64_t* stats_dev) {
+  if (!s || n_rows < 0 || n_rows > 0x7fffffffll || n_items < 0) return fail(URCCO_BAD_ARG, "urcco_dev_diversify: bad argument");
+  if (width < 1 || width > URCCO_REC_MAX_NUM) return fail(URCCO_BAD_ARG, "urcco_dev_diversify: width must lie in 1..%d, got %d", URCCO_REC_MAX_NUM, width);
+  if (num < 1 || num > width) return fail(URCCO_BAD_ARG, "urcco_dev_diversify: num must lie in 1..width = %d, got %d", width, num);
+  if (!(penalty >= 0.0) || penalty > 1.7976931348623157e308) return fail(URCCO_BAD_ARG, "urcco_dev_diversify: penalty must be finite and >= 0, got %g", penalty);
+  if (n_rows > 0 && (!in_count || !in_idx || !in_score || !out_count || !out_idx || !out_score || (n_items > 0 && (!sim_row_ptr || !sim_col_idx))))
+    return fail(URCCO_BAD_ARG, "urcco_dev_diversify: an array is missing");
+  if (n_rows == 0 && !stats_dev) return URCCO_OK;
+  urcco::DivArgs a;
+  memset(&a, 0, sizeof(a));
+  a.in_count = in_count; a.in_idx = in_idx; a.in_score = reinterpret_cast<const unsigned long long*>(in_score);
+  a.sim_row_ptr = sim_row_ptr; a.sim_col_idx = sim_col_idx;
+  a.out_count = out_count; a.out_idx = out_idx; a.out_score = reinterpret_cast<unsigned long long*>(out_score); a.out_pos = out_pos; a.out_links = out_links;
+  a.stats = reinterpret_cast<unsigned long long*>(stats_dev);
+  a.penalty = penalty; a.n_rows = n_rows; a.n_items = n_items; a.width = width; a.num = num;
+  if (stats_dev) URC(ArenaLayout(s).add(&a.partial, 3 * (size_t)urcco::diversify_blocks(n_rows, s->n_cu)).commit());
+  HIPC(urcco::launch_diversify(s->stream, s->n_cu, a));
+  return URCCO_OK;
+}
+
 int urcco_dev_tree_sum(urcco_session* s, int64_t n, int32_t n_cols, const double* x, double* out) {
   if (!s || n < 0 || n_cols < 1 || n_cols > 1024 || !out || (n > 0 && !x) || n * (int64_t)n_cols > 0x7fffffffll)
     return fail(URCCO_BAD_ARG, "urcco_dev_tree_sum: bad argument");

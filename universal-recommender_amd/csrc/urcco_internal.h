@@ -30,6 +30,7 @@ static_assert(urcco::AUDIENCE_MAX_NUM == URCCO_AUDIENCE_MAX_NUM && urcco::AUD_TE
               "include/urcco.h and cco_kernels.h agree on the audience call");
 static_assert(urcco::QUOTA_MAX_RULES == URCCO_QUOTA_MAX_RULES && urcco::QUOTA_MAX_VALUES == URCCO_QUOTA_MAX_VALUES && urcco::QUOTA_STATS_LEN == URCCO_QUOTA_STATS_LEN,
               "include/urcco.h and cco_kernels.h agree on the quota call");
+static_assert(urcco::DIV_STATS_LEN == URCCO_DIVERSIFY_STATS_LEN, "include/urcco.h and cco_kernels.h agree on the diversify call");
 static_assert(urcco::RANK_MAX_STREAMS ==URCCO_RANK_MAX_STREAMS && urcco::RANK_MAX_FIELDS == URCCO_RANK_MAX_FIELDS && urcco::RANK_NONE == URCCO_RANK_NONE,
               "include/urcco.h and cco_kernels.h agree on the rank calls");
 

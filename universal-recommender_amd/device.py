@@ -458,6 +458,33 @@ class DeviceSession:
                                                  _ptr(linked), _ptr(sums)))
         return linked[: n * len(ks)].view(n, len(ks)), sums
 
+    def diversify(self, count: torch.Tensor, idx: torch.Tensor, score: torch.Tensor, row_ptr: torch.Tensor, col_idx: torch.Tensor, penalty: float, num: int,
+                  n_items: Optional[int] = None, stats: bool = False):
+        """urcco_dev_diversify (decision D36): the greedy MMR re-rank of a result table -- count int32 [n], idx int32 [n, width], score float64 [n, width] as
+        recommend returns them -- over the links of a similarity CSR (row_ptr int64 [n_items + 1], col_idx int32, rows in any order; n_items None: from
+        row_ptr).  Per row, step by step, the eligible entry (a valid item at its first position) with the largest score - (penalty * the row's best score) *
+        (its links to the entries already chosen) is taken, ties to the smaller position; two entries are linked when either's matrix row names the other.
+        Returns (count int32 [n], idx int32 [n, num], score float64 [n, num] -- the input score's bits --, pos int32 [n, num]: the input position, links
+        int32 [n, num]: the links to the earlier picks at selection, stats int64 [DIVERSIFY_STATS_LEN] or None); -1 / 0.0 / -1 / 0 behind the count.
+        Enqueues, does not synchronise."""
+        n, width, num = int(count.numel()), int(idx.shape[1]) if idx.dim() == 2 else 0, int(num)
+        if idx.dtype != torch.int32 or score.dtype != torch.float64 or count.dtype != torch.int32 or idx.shape != score.shape or idx.dim() != 2 or idx.shape[0] != n:
+            raise ValueError("diversify: count int32 [n], idx int32 [n, width] and score float64 [n, width] expected")
+        if row_ptr.dtype != torch.int64 or col_idx.dtype != torch.int32:
+            raise ValueError("diversify: row_ptr int64 and col_idx int32 expected")
+        idx, score, count = idx.contiguous(), score.contiguous(), count.contiguous()
+        if n_items is None:
+            n_items = int(row_ptr.numel()) - 1
+        slots = max(n * max(num, 0), 1)
+        o_count, o_idx, o_score = self.empty(max(n, 1), torch.int32), self.empty(slots, torch.int32), self.empty(slots, torch.float64)
+        o_pos, o_links = self.empty(slots, torch.int32), self.empty(slots, torch.int32)
+        st = self.empty(_lib.DIVERSIFY_STATS_LEN, torch.int64) if stats else None
+        self._check(self.lib.urcco_dev_diversify(self.handle, n, width, _ptr(count), _ptr(idx), _ptr(score), int(n_items), _ptr(row_ptr), _ptr(col_idx), float(penalty),
+                                                num, _ptr(o_count), _ptr(o_idx), _ptr(o_score), _ptr(o_pos), _ptr(o_links), _ptr(st)))
+        shape = (n, max(num, 0))
+        return o_count[:n], o_idx[: n * shape[1]].view(shape), o_score[: n * shape[1]].view(shape), o_pos[: n * shape[1]].view(shape), \
+            o_links[: n * shape[1]].view(shape), st
+
     def tree_sum(self, x: torch.Tensor) -> torch.Tensor:
         """urcco_dev_tree_sum: the pairwise sums of decision D19 over the rows of a contiguous float64 [n, n_cols] tensor, one per column: what
         `while x.size > 1: x = x[0::2] + x[1::2]` leaves of each column padded with +0.0 to a power of two.  Enqueues, does not synchronise."""

@@ -380,6 +380,30 @@ def _quota_cut(model: DeviceModel, spec: tuple, count, idx, score, num: int):
     return model.sess.quota_cut(count, idx, score, rules, num, model.n_items, stats=False)[:4]
 
 
+def _diversity(algo, diversify) -> float:
+    """diversify= -> the MMR penalty, 0.0 for off.  None: the algorithm's recommendDiversity parameter decides (absent: off); 0 switches it off."""
+    if diversify is None:
+        diversify = getattr(algo.ap, "recommendDiversity", None)
+    penalty = float(diversify or 0.0)
+    if not 0.0 <= penalty < float("inf"):
+        raise ValueError(f"diversify: the penalty must be finite and >= 0, got {penalty}")
+    return penalty
+
+
+def _diversify(model: DeviceModel, penalty: float, count, idx, score, num: int):
+    """urcco_dev_diversify over a result table (decision D36) -> (count, idx, score): per row the greedy MMR order of its first `num` picks against the
+    links of the primary event's indicator matrix, every link to an earlier pick costing `penalty` of the row's best score."""
+    sim = model.correlators[0]
+    return model.sess.diversify(count, idx, score, sim.row_ptr, sim.col_idx, penalty, num, model.n_items)[:3]
+
+
+def _post_pass(model: DeviceModel, spec: tuple, penalty: float, table, pool: int, num: int):
+    """A pool-wide table -> the caller's: diversified (the whole pool when a quota follows, which then cuts that order), then cut"""
+    if penalty:
+        table = _diversify(model, penalty, *table, pool if spec else num)
+    return _quota_cut(model, spec, *table, num) if spec else table
+
+
 def _max_query_events(ap) -> int:
     if ap.indicators:                                                                          # :203-211
         return sum(i.maxItemsPerUser if i.maxItemsPerUser is not None else 100 for i in ap.indicators) * 10
@@ -409,7 +433,7 @@ def _term_name(model: DeviceModel, m, term: int):
 
 def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host",
                   term_weights=None, explain: Optional[int] = None, accumulator: Optional[str] = None, filter_plan: Optional[str] = None, quota=None,
-                  pool: Optional[int] = None) -> List[dict]:
+                  pool: Optional[int] = None, diversify: Optional[float] = None) -> List[dict]:
     """URAlgorithm.predict for a list of query dicts: [{"itemScores": [{"item", "score"}, ...]}, ...] in the order of `queries`.
     history: user -> {event name: [item ids, oldest first]} (the event store's view of the user), or a history.DeviceHistory: the event streams
     resident on the device.  With a DeviceHistory the user-history term rows (the ("user", ev) clauses, or the ("hist", ev) ANY rules under
@@ -444,7 +468,11 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
     quota, pool: None (the algorithm's recommendQuota parameter, absent: no quota -- the calls are then today's) or [{"name": list property, "max": m},
     ...] (decision D34); a query's own "quota" key overrides it for that query.  Such a query fetches pool (default min(256, 4 x (from + num))) results
     and its group -- queries share a call only under the same rule set -- is cut on the device to from + num results that leave every value of every
-    named property on at most m items, before the rows become itemScores.  Not with explain."""
+    named property on at most m items, before the rows become itemScores.  Not with explain.
+    diversify: None (the algorithm's recommendDiversity parameter, absent: off -- the calls are then today's), 0 (off) or a penalty > 0 (decision D36); a
+    query's own "diversify" key overrides it and becomes part of the group key.  Such a query fetches pool results and its group is re-ranked on the device
+    by the greedy MMR rule of user_recommendations to from + num results; under a quota as well the whole pool is re-ranked and the quota cuts that order.
+    Not with explain."""
     tw = _term_weights(algo, model, term_weights)
     explain = _explain_max(explain)
     driven = _filter_plan(algo, filter_plan)
@@ -521,6 +549,9 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
         q_quota = _quota_spec(algo, model, q["quota"] if "quota" in q else quota)
         if q_quota and explain is not None:
             raise NotImplementedError("quota and explain in one call are not served: the cut moves the result slots")
+        q_div = _diversity(algo, q["diversify"] if "diversify" in q else diversify)
+        if q_div and explain is not None:
+            raise NotImplementedError("diversify and explain in one call are not served: the re-rank moves the result slots")
         q_events = list(q.get("eventNames") or model_events)
         user, item, item_set = q.get("user"), q.get("item"), list(q.get("itemSet") or [])
         terms: Dict[tuple, np.ndarray] = {}
@@ -577,7 +608,7 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
             terms[("field",) + slot] = cols
         # a rule cannot be absent for one row of a call: queries share a call only when they carry the same rules and the same property clauses
         key = (_boost(user_bias), _boost(item_bias), _boost(set_bias), start + num, tuple(slot for slot, _ in boosted), tuple(rules), hist_key,
-               (q_quota, _quota_pool(pool, start + num)) if q_quota else None)
+               (q_quota, _quota_pool(pool, start + num), q_div) if q_quota or q_div else None)
         groups.setdefault(key, []).append(n)
         plans.append((terms, np.unique(np.array([i for i in excl if i is not None], np.int64)), start, num, rules, q_user_ids[n] if dh is not None else -1,
                       user is not None, q_item))
@@ -586,7 +617,7 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
     results: List[Optional[dict]] = [None] * len(queries)
     dev = model.sess.device
     empty = np.zeros(0, np.int64)
-    for (ub, ib, sb, fetch, field_slots, rule_keys, hist_key, quota_key), members in groups.items():
+    for (ub, ib, sb, fetch, field_slots, rule_keys, hist_key, post_key), members in groups.items():
         hist_rows: Dict[str, Tuple[torch.Tensor, torch.Tensor]] = {}
         excl = _csr([plans[n][1] for n in members], dev)
         if hist_key is not None and hist_key[0]:                                                # one history call for the group
@@ -649,10 +680,10 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
                                 _csr([plans[n][4][rk] for n in members], dev))
                     rules.append((_lib.RULE_NONE if rk[0] == "none" else _lib.RULE_ANY, m.n_cols, m.row_ptr, m.col_idx, qrp, qci))
                     rule_m[-1] = m if rk[0] in ("any", "hist", "sim") else None
-        count, idx, score, _ = model.sess.recommend(len(members), model.n_items, clauses, quota_key[1] if quota_key else fetch, excl, mask_t, model.fill_order,
+        count, idx, score, _ = model.sess.recommend(len(members), model.n_items, clauses, post_key[1] if post_key else fetch, excl, mask_t, model.fill_order,
                                                     stats=False, rules=rules, weights=weights, **_driven_args(driven, flags, rules, rule_m, [c for _, c, _ in slots]))
-        if quota_key:                                                                           # one cut per group: the rule set is part of its key
-            count, idx, score, _ = _quota_cut(model, quota_key[0], count, idx, score, fetch)
+        if post_key:                                                                            # one re-rank and one cut per group: both are part of its key
+            count, idx, score = _post_pass(model, post_key[0], post_key[2], (count, idx, score), post_key[1], fetch)[:3]
         why = None
         if explain is not None and clauses:                                                     # the same clauses over the CSR of their matrices (D30)
             why = model.sess.explain(count, idx, [(c.n_cols, boost, c.row_ptr, c.col_idx, cl[4], cl[5], None if weights is None else weights[k])
@@ -673,7 +704,7 @@ def batch_predict(algo, model: DeviceModel, queries: Sequence[dict], history, it
 
 def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = None, item_bias: Optional[float] = None, return_self: Optional[bool] = None,
                   chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None, accumulator: Optional[str] = None, quota=None,
-                  pool: Optional[int] = None):
+                  pool: Optional[int] = None, diversify: Optional[float] = None):
     """The item-to-item table ("people who liked this also liked"): row n is what batch_predict answers to {"item": items[n]} -- the same items in the
     same order with the same scores -- as three device tensors (count int32 [n], idx int32 [n, num], score float64 [n, num]); entries behind count[n]
     are -1 / 0.0.  No Python work per item: the queries go `chunk` at a time through DeviceSession.item_rows (decision D18) and recommend, and no
@@ -683,13 +714,15 @@ def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = Non
     returnSelf (False).  item_bias > 0: one should-clause per event type of the model over the item's own indicator lists, boost = the bias;
     item_bias < 0: the lists are ANY rules instead (a model built with item properties, {} will do).  The query item is excluded unless return_self.
     Backfill, recsModel, item_mask, the available / expire date rule around now_ms, term_weights and accumulator are those of batch_predict.
-    quota, pool: as in user_recommendations -- the table is built with num = pool, cut on the device, and `short` is returned as a fourth tensor."""
+    quota, pool: as in user_recommendations -- the table is built with num = pool, cut on the device, and `short` is returned as a fourth tensor.
+    diversify: as in user_recommendations -- the table is built with num = pool and re-ranked on the device (decision D36); the return keeps its shape."""
     ap = algo.ap
-    spec = _quota_spec(algo, model, quota)
-    if spec:
+    spec, penalty = _quota_spec(algo, model, quota), _diversity(algo, diversify)
+    if spec or penalty:
         num = int(num if num is not None else ap.num if ap.num is not None else 20)
-        table = similar_items(algo, model, items, _quota_pool(pool, num), item_bias, return_self, chunk, item_mask, now_ms, term_weights, accumulator, quota=[])
-        return _quota_cut(model, spec, *table, num)
+        wide = _quota_pool(pool, num)
+        table = similar_items(algo, model, items, wide, item_bias, return_self, chunk, item_mask, now_ms, term_weights, accumulator, quota=[], diversify=0)
+        return _post_pass(model, spec, penalty, table, wide, num)
     sess, dev = model.sess, model.sess.device
     tw = _term_weights(algo, model, term_weights)
     model_events = list(algo.modelEventNames)
@@ -765,7 +798,7 @@ def similar_items(algo, model: DeviceModel, items=None, num: Optional[int] = Non
 def user_recommendations(algo, model: DeviceModel, history, users=None, num: Optional[int] = None, event_names: Optional[Sequence[str]] = None,
                          user_bias: Optional[float] = None, chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None,
                          explain: Optional[int] = None, accumulator: Optional[str] = None, filter_plan: Optional[str] = None, quota=None,
-                         pool: Optional[int] = None):
+                         pool: Optional[int] = None, diversify: Optional[float] = None):
     """The per-user table, the user-side twin of similar_items: row n is what batch_predict answers to {"user": users[n]} (with "eventNames", "num" and
     "userBias" where given) over the same DeviceHistory -- the same items in the same order with the same scores -- as three device tensors (count
     int32 [n], idx int32 [n, num], score float64 [n, num]); entries behind count[n] are -1 / 0.0.  No Python work per user: the queries go `chunk`
@@ -784,16 +817,23 @@ def user_recommendations(algo, model: DeviceModel, history, users=None, num: Opt
     most four (decision D34): the table is built with num = pool (default min(256, 4 x num)) and every row is then cut on the device to its first num
     results, in order, that leave every value of every named property on at most m of the row's items.  The result is (count, idx, score, short): short
     int32 [n] is 1 where a full pool did not fill the row (a wider pool might), and a row with short == 0 is the answer over an unbounded pool.  Not with
-    explain.  A property the model does not hold raises ValueError."""
+    explain.  A property the model does not hold raises ValueError.
+    diversify: None (the algorithm's recommendDiversity parameter, absent: off -- the call is then today's), 0 (off) or a penalty > 0 (decision D36): the
+    table is built with num = pool (as under a quota) and every row is re-ranked on the device by a greedy maximal-marginal-relevance pass -- the best
+    entry, then step by step the entry with the largest score - penalty x (the row's best score) x (its links to the entries already picked); two items
+    are linked when either's row of the primary event's indicator matrix names the other; ties go to the better-ranked entry.  The result keeps its shape
+    (count, idx, score), the scores are the pool's own.  With a quota in the same call the whole pool is re-ranked and the quota cuts that order: (count,
+    idx, score, short).  A wider pool may change a row.  Not with explain."""
     from .history import DeviceHistory
-    spec = _quota_spec(algo, model, quota)
-    if spec:
+    spec, penalty = _quota_spec(algo, model, quota), _diversity(algo, diversify)
+    if spec or penalty:
         if explain is not None:
-            raise NotImplementedError("quota and explain in one call are not served: the cut moves the result slots")
+            raise NotImplementedError(f"{'quota' if spec else 'diversify'} and explain in one call are not served: the {'cut' if spec else 're-rank'} moves the result slots")
         num = int(num if num is not None else algo.ap.num if algo.ap.num is not None else 20)
-        table = user_recommendations(algo, model, history, users, _quota_pool(pool, num), event_names, user_bias, chunk, item_mask, now_ms, term_weights, None,
-                                     accumulator, filter_plan, quota=[])
-        return _quota_cut(model, spec, *table, num)
+        wide = _quota_pool(pool, num)
+        table = user_recommendations(algo, model, history, users, wide, event_names, user_bias, chunk, item_mask, now_ms, term_weights, None, accumulator,
+                                     filter_plan, quota=[], diversify=0)
+        return _post_pass(model, spec, penalty, table, wide, num)
     tw = _term_weights(algo, model, term_weights)
     explain = _explain_max(explain)
     driven = _filter_plan(algo, filter_plan)

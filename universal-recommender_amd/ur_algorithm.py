@@ -139,6 +139,7 @@ class URAlgorithmParams:
     recommendAccumulator: Optional[str] = None     # additive key: the default of the query side's accumulator (decision D31): absent = "dense", "hashed", "auto"
     recommendFilterPlan: Optional[str] = None      # additive key: the default of the query side's filter_plan (decision D32): absent = "walk", "driven"
     recommendQuota: Optional[List[dict]] = None    # additive key: the default of the query side's quota (decision D34): absent = none, [{"name": property, "max": m}, ...]
+    recommendDiversity: Optional[float] = None     # additive key: the default of the query side's diversify (decision D36): absent = off, the MMR penalty per link
     minEventsPerUser: Optional[int] = None         # additive key: the datasource's minEventsPerUser for train_from_history, which has no DataSource in front of it; absent = 1
 
     @staticmethod
@@ -162,7 +163,7 @@ class URAlgorithmParams:
             seed=p.get("seed"), num=p.get("num"), maxQueryEvents=p.get("maxQueryEvents"), userBias=p.get("userBias"), itemBias=p.get("itemBias"),
             blacklistEvents=p.get("blacklistEvents"), returnSelf=p.get("returnSelf"), termWeights=p.get("termWeights"),
             recommendAccumulator=p.get("recommendAccumulator"), recommendFilterPlan=p.get("recommendFilterPlan"),
-            recommendQuota=p.get("recommendQuota"), minEventsPerUser=p.get("minEventsPerUser"))
+            recommendQuota=p.get("recommendQuota"), recommendDiversity=p.get("recommendDiversity"), minEventsPerUser=p.get("minEventsPerUser"))
 
 
 def _get_or_else(v, default):
@@ -273,7 +274,7 @@ class URAlgorithm:
 
     def batch_predict(self, model, queries: Sequence[dict], history, item_mask=None, now_ms: Optional[int] = None, item_rows: str = "host",
                       term_weights=None, explain: Optional[int] = None, accumulator: Optional[str] = None, filter_plan: Optional[str] = None, quota=None,
-                      pool: Optional[int] = None) -> List[dict]:
+                      pool: Optional[int] = None, diversify: Optional[float] = None) -> List[dict]:
         """URAlgorithm.predict (:484-535) for a batch of queries against a recommend.DeviceModel: user history, similar-item and itemSet
         queries, blacklists, backfill by rank and -- for a model built with item properties -- the business rules (fields, dateRange, available /
         expire dates around now_ms, negative biases); see recommend.batch_predict for what is mirrored and what is left out.  history: the dict
@@ -285,27 +286,30 @@ class URAlgorithm:
         algorithm parameter recommendFilterPlan (absent: "walk"), "walk" or "driven" -- a query under a rare filter is answered from the filter's item list
         (decision D32); the results are the same.  quota=[{"name": property, "max": m}, ...] (here, in similar_items and in user_recommendations; None =
         the algorithm parameter recommendQuota, absent: none): at most m results per value of a list property, cut on the device from the best `pool`
-        (default min(256, 4 x num)) results (decision D34); a query's own "quota" key overrides it."""
+        (default min(256, 4 x num)) results (decision D34); a query's own "quota" key overrides it.  diversify=penalty (here, in similar_items and in
+        user_recommendations; None = the algorithm parameter recommendDiversity, absent: off; 0: off): the best `pool` results are re-ranked on the device
+        by a greedy MMR pass over the primary indicator's links (decision D36); a query's own "diversify" key overrides it."""
         from .recommend import batch_predict
-        return batch_predict(self, model, queries, history, item_mask, now_ms, item_rows, term_weights, explain, accumulator, filter_plan, quota, pool)
+        return batch_predict(self, model, queries, history, item_mask, now_ms, item_rows, term_weights, explain, accumulator, filter_plan, quota, pool, diversify)
 
     def similar_items(self, model, items=None, num: Optional[int] = None, item_bias: Optional[float] = None, return_self: Optional[bool] = None,
                       chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None, accumulator: Optional[str] = None,
-                      quota=None, pool: Optional[int] = None):
+                      quota=None, pool: Optional[int] = None, diversify: Optional[float] = None):
         """The item-to-item table of `items` (None: every item of the model) as device tensors (count, idx, score): row n is what batch_predict
-        answers to {"item": items[n]}; under a quota (count, idx, score, short); see recommend.similar_items."""
+        answers to {"item": items[n]}; under a quota (count, idx, score, short); under diversify re-ranked; see recommend.similar_items."""
         from .recommend import similar_items
-        return similar_items(self, model, items, num, item_bias, return_self, chunk, item_mask, now_ms, term_weights, accumulator, quota, pool)
+        return similar_items(self, model, items, num, item_bias, return_self, chunk, item_mask, now_ms, term_weights, accumulator, quota, pool, diversify)
 
     def user_recommendations(self, model, history, users=None, num: Optional[int] = None, event_names=None, user_bias: Optional[float] = None,
                              chunk: int = 65536, item_mask=None, now_ms: Optional[int] = None, term_weights=None, explain: Optional[int] = None,
-                             accumulator: Optional[str] = None, filter_plan: Optional[str] = None, quota=None, pool: Optional[int] = None):
+                             accumulator: Optional[str] = None, filter_plan: Optional[str] = None, quota=None, pool: Optional[int] = None,
+                             diversify: Optional[float] = None):
         """The per-user table of `users` (None: every user id of the history.DeviceHistory) as device tensors (count, idx, score): row n is what
-        batch_predict answers to {"user": users[n]} over the same history; under a quota (count, idx, score, short); see
+        batch_predict answers to {"user": users[n]} over the same history; under a quota (count, idx, score, short); under diversify re-ranked; see
         recommend.user_recommendations."""
         from .recommend import user_recommendations
         return user_recommendations(self, model, history, users, num, event_names, user_bias, chunk, item_mask, now_ms, term_weights, explain, accumulator,
-                                    filter_plan, quota, pool)
+                                    filter_plan, quota, pool, diversify)
 
     def audience(self, model, history, items, num: int = 100, users=None, event_names=None, term_weights=None, user_chunk: int = 65536):
         """The audience of every item of `items` (decision D33): the `num` users of the history.DeviceHistory with the highest user_recommendations
